@@ -11,7 +11,10 @@ N > 1 (default): every rank owns an independent window (weak scaling, no data-pa
 time.  `--shard-factors` instead solves ONE window cooperatively (factors sharded, RCCL all-reduce of the
 moments per linearisation; strong scaling).
 
-Prints ONE JSON line (rank 0).  Extra objects: `roofline` for the dominant kernel (HIP events on the
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times exactly --steps steps and prints the headline (`value`,
+`ms_per_step` = milliseconds of one timed step).  `--dump-outputs DIR` also writes what the last timed step computed as
+DIR/<name>.npy (inputs are seeded: two builds compare output for output).  Everything else is measured only under `--full`.
+Extra objects of `--full`: `roofline` for the dominant kernel (HIP events on the
 estimator's stream), `cpu_baseline` = the CPU oracle timed on this box's host cores on the same window,
 `batched` = lio_est_batch: B in {8, 64, 512} copies of the window solved per launch chain — solves/s and the
 device time, algorithmic bytes and roofline fraction of every stage (the single-window path is latency-bound; this is the path's
@@ -103,6 +106,28 @@ def make_estimator(lib, ds, clouds, kind, W, Wo):
 def one_step(est):
     est.restore()
     return est.solve()
+
+
+def dump_outputs(path, est, rep):
+    """What the last timed step handed its caller, as <path>/<name>.npy: the solved window (Ps, Rs, Vs, Bas, Bgs, the lidar-IMU
+    extrinsic), the newest frame's laser-odometry transform, the marginalization prior the step left for the next one, and the
+    report's counts and costs (its stage timings are left out: they differ from run to run).  A few kB in all."""
+    est.sync()   # the last step's deferred marginalization
+    os.makedirs(path, exist_ok=True)
+    arrays = dict(est.get_window())
+    q, t = est.laser_odom_transform()
+    arrays["laser_odom_q"], arrays["laser_odom_t"] = q, t
+    prior = est.prior()
+    if prior is not None:
+        arrays.update(prior_JtJ=prior["JtJ"], prior_Jtr=prior["Jtr"], prior_x0=prior["x0"])
+    counts = ("iterations", "successful_steps", "termination", "n_lidar_residuals", "n_local_map", "laser_odom_iterations", "turn_off",
+              "convergence_flag", "marginalized", "laser_odom_kz")
+    arrays["report_counts"] = np.array([getattr(rep, k) for k in counts], dtype=np.float64)
+    arrays["report_costs"] = np.array([rep.cost_pim_before, rep.cost_ppp_before, rep.cost_marg_before, rep.initial_cost, rep.final_cost]
+                                      + list(rep.cost_trace), dtype=np.float64)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32 if a.dtype == np.float32 else np.float64))
 
 
 def self_launch(args):
@@ -352,9 +377,17 @@ def main():
     ap.add_argument("--workload", default="hdl64", choices=["hdl64", "vlp16", "keyframes"],
                     help="hdl64 (default, the headline metric) / vlp16: sliding-window solves.  keyframes: BASELINE.json configs[4], "
                          "--keyframes HDL-64 keyframes refined per step, the keyframe list sharded over the ranks + all-gather of the poses")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides the headline: per-kernel timing and roofline, PMC passes, CPU baseline, batched "
+                         "windows, fed-GPU points, keyframe batch, per-scan stages, and at N > 1 the sharded and keyframe extras.  "
+                         "Default: set up, warm up, time exactly --steps steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (window state, marginalization prior, solve "
+                         "report) as DIR/<name>.npy (float32 / float64); the inputs are the same from run to run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--min-seconds", type=float, default=0.5,
-                    help="the timed --steps block is repeated until the timed region covers at least this long; the line reports the median block")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="repeat the timed --steps block until the timed region covers at least this long and report the median block "
+                         "(default 0: one block of exactly --steps steps)")
     ap.add_argument("--no-pmc", action="store_true", help="skip the two child rocprofv3 --pmc passes that measure roofline.traffic live")
     ap.add_argument("--pmc-child", default=None, help=argparse.SUPPRESS)   # internal: a few solves on the pickled workload, run under rocprofv3
     ap.add_argument("--cpu-steps", type=int, default=8)
@@ -370,6 +403,10 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs and (args.workload == "keyframes" or args.dry_launch):
+        raise SystemExit("--dump-outputs: the sliding-window workloads (hdl64, vlp16) only")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args))          # one rank per GPU under torch.distributed.run, same flags
 
@@ -442,9 +479,9 @@ def main():
         dist_util.barrier(world)
         return dist_util.max_over_ranks(time.perf_counter() - t0, world, device="cuda"), r
 
-    # A block of --steps steps is tens of milliseconds: it is repeated (same bracket every time) until the timed region covers
-    # --min-seconds, and the line reports the MEDIAN block (box-to-box and block-to-block spread: `timing`).  No HIP events are
-    # recorded inside the timed blocks; the per-kernel times come from a separate block afterwards.
+    # One block of exactly --steps steps.  With --min-seconds the block is repeated (same bracket every time) until the timed region
+    # covers that long, and the line reports the MEDIAN block (block-to-block spread: `timing`).  No HIP events are recorded inside
+    # the timed blocks; the per-kernel times of --full come from a separate block afterwards.
     first, rep = timed_block()
     n_blocks = int(max(1, min(200, np.ceil(args.min_seconds / max(first, 1e-6)))))
     n_blocks = int(dist_util.max_over_ranks(float(n_blocks), world, device="cuda"))
@@ -456,6 +493,8 @@ def main():
     value = world * args.steps / dt_max
     if args.shard_factors:
         value = args.steps / dt_max  # one window solved cooperatively: total work is fixed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, est, rep)
     # N > 1 (one rank per GPU, independent windows): the line's value is the THROUGHPUT mode — every rank solves --rank-windows windows per
     # step through lio_est_batch — because that is what a node full of GPUs is for; N ranks x one latency-bound window each is carried as
     # `single_window`.  At N = 1 the headline stays the single window and the same mode is the `batched` extra.
@@ -463,22 +502,55 @@ def main():
     if world > 1 and not args.shard_factors and args.rank_windows > 0:
         thr = throughput_measure(hip, est_config(hip, ds, kind, W, Wo), est, args.rank_windows, args.steps, args.warmup, rank, world, sync=torch.cuda.synchronize, device="cuda")
 
-    resident = est.kernel_timing("moments_resident")   # passes served by the resident moments kernel so far (the timed blocks above)
-    est.enable_kernel_timing(-1)                       # untimed block: HIP events around the resident kernel's launches (dispatch -> exit)
-    for _ in range(max(5, args.steps // 5)):
-        one_step(est)
-    est.sync()
-    resident_launch = est.kernel_timing("moments_resident_launch")
-    est.enable_kernel_timing(False)
-    names = ["features", "odom_features", "odom_rows", "odom_update", "moments", "voxel", "knn_grid", "concat"]
-    est.enable_kernel_timing(1)   # HIP events around EVERY launch of each kernel kind on the estimator's stream: untimed block
-    for _ in range(max(5, args.steps // 5)):
-        one_step(est)
-    est.sync()
-    kt = {n: est.kernel_timing(n) for n in names}
-    est.enable_kernel_timing(False)
-
     if rank == 0:
+        out = {
+            "metric": "sliding-window solves/sec, 64-line 130k-pt scans, window=15 (opt_window=5)" if kind == "outdoor"
+            else "sliding-window solves/sec, VLP-16 28.8k-pt scans, window=15 (opt_window=5) [NOT the headline workload]",
+            "value": round(value, 3),
+            "unit": "solves/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(1e3 * dt_max / args.steps, 4),
+            "timing": {"blocks": n_blocks, "steps_per_block": args.steps, "timed_seconds": round(float(np.sum(block_s)), 4),
+                       "ms_per_step_min": round(1e3 * float(np.min(block_s)) / args.steps, 4), "ms_per_step_max": round(1e3 * float(np.max(block_s)) / args.steps, 4),
+                       "note": "value / ms_per_step = one block of exactly --steps steps (the MEDIAN block when --min-seconds repeats it; barrier + synchronize on both sides, max over ranks); a step = restore + SolveOptimization, the --steps of a block looped inside the library (lio_est_solve_restored: no Python between two solves)"},
+            "higher_is_better": True,
+            "scaling": "strong" if args.shard_factors else "weak",
+            "vs_baseline": None,
+            "dtype": "f64 (solve) / f32 (features)",
+            "data": "synthetic",
+            "config": {
+                "workload": "HDL-64E outdoor_test_config_64, S_outdoor ray-cast scans, window_size=15 opt_window_size=5, one SolveOptimization per step, clouds resident in HBM"
+                if kind == "outdoor" else "VLP-16 indoor, window_size=15 opt_window_size=5",
+                "points_per_scan": int(ds.frames[0].scan.shape[0]),
+                "n_lidar_residuals": int(rep.n_lidar_residuals),
+                "local_map_points": int(rep.n_local_map),
+                "surf_stack_points": int(new_stack_n),
+                "solver_iterations": int(rep.iterations),
+                "laser_odom_iterations": int(rep.laser_odom_iterations),
+                "parallelism": (f"1 window, factors sharded over {world} ranks + all-reduce" if args.shard_factors else f"{world} independent windows") if world > 1 else "1 window",
+            },
+            "setup_s": round(setup_s, 2),
+        }
+
+    if args.full:
+        resident = est.kernel_timing("moments_resident")   # passes served by the resident moments kernel so far (the timed blocks above)
+        est.enable_kernel_timing(-1)                       # untimed block: HIP events around the resident kernel's launches (dispatch -> exit)
+        for _ in range(max(5, args.steps // 5)):
+            one_step(est)
+        est.sync()
+        resident_launch = est.kernel_timing("moments_resident_launch")
+        est.enable_kernel_timing(False)
+        names = ["features", "odom_features", "odom_rows", "odom_update", "moments", "voxel", "knn_grid", "concat"]
+        est.enable_kernel_timing(1)   # HIP events around EVERY launch of each kernel kind on the estimator's stream: untimed block
+        for _ in range(max(5, args.steps // 5)):
+            one_step(est)
+        est.sync()
+        kt = {n: est.kernel_timing(n) for n in names}
+        est.enable_kernel_timing(False)
+
+    if rank == 0 and args.full:
         def per_launch(n):
             k = kt[n]
             L = max(k["launches"], 1)
@@ -639,34 +711,7 @@ def main():
         cpu = None if (args.no_cpu_baseline or world > 1) else cpu_baseline(kind, W, Wo, args.cpu_steps, ds)  # N = 1 only
         odom_io = 3 if kind == "outdoor" else 2
         pp_med = float(np.median(pp_ms[1:]))
-        out = {
-            "metric": "sliding-window solves/sec, 64-line 130k-pt scans, window=15 (opt_window=5)" if kind == "outdoor"
-            else "sliding-window solves/sec, VLP-16 28.8k-pt scans, window=15 (opt_window=5) [NOT the headline workload]",
-            "value": round(value, 3),
-            "unit": "solves/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(1e3 * dt_max / args.steps, 4),
-            "timing": {"blocks": n_blocks, "steps_per_block": args.steps, "timed_seconds": round(float(np.sum(block_s)), 4),
-                       "ms_per_step_min": round(1e3 * float(np.min(block_s)) / args.steps, 4), "ms_per_step_max": round(1e3 * float(np.max(block_s)) / args.steps, 4),
-                       "note": "value / ms_per_step = the MEDIAN block of exactly --steps steps (barrier + synchronize on both sides, max over ranks); a step = restore + SolveOptimization, the --steps of a block looped inside the library (lio_est_solve_restored: no Python between two solves)"},
-            "higher_is_better": True,
-            "scaling": "strong" if args.shard_factors else "weak",
-            "vs_baseline": None,
-            "dtype": "f64 (solve) / f32 (features)",
-            "data": "synthetic",
-            "config": {
-                "workload": "HDL-64E outdoor_test_config_64, S_outdoor ray-cast scans, window_size=15 opt_window_size=5, one SolveOptimization per step, clouds resident in HBM"
-                if kind == "outdoor" else "VLP-16 indoor, window_size=15 opt_window_size=5",
-                "points_per_scan": int(ds.frames[0].scan.shape[0]),
-                "n_lidar_residuals": int(rep.n_lidar_residuals),
-                "local_map_points": int(rep.n_local_map),
-                "surf_stack_points": int(new_stack_n),
-                "solver_iterations": int(rep.iterations),
-                "laser_odom_iterations": int(rep.laser_odom_iterations),
-                "parallelism": (f"1 window, factors sharded over {world} ranks + all-reduce" if args.shard_factors else f"{world} independent windows") if world > 1 else "1 window",
-            },
+        out.update({
             "roofline": roofline,
             "cpu_baseline": cpu,
             "sharded": None,
@@ -697,8 +742,7 @@ def main():
                 "total": round(pp_med + (packer_ms or 0.0) + (1e3 * dt_max / args.steps + step_extra_ms) / odom_io, 4),
                 "note": "total = per 10 Hz sweep after IMU init: PointProcessor + PointOdometry in packer mode (the estimator disables it after IMU init, SURVEY.md A.18) + 1/odom_io of an estimator step (ProcessImu of the interval's samples + PushFrame + SolveOptimization + SlideWindow).  total_before_imu_init = PointProcessor + scan-to-scan odometry + scan-to-map (no solves yet)",
             },
-            "setup_s": round(setup_s, 2),
-        }
+        })
     # N > 1: the two modes with a real exchange step, measured in the same run on every rank (collective), reported by rank 0 in
     # the same line.  They come LAST and under a watchdog: if a rank fails or a collective never completes, rank 0 still prints the
     # line it has (the weak-scaling measurement) with the failure noted, instead of hanging the whole run.
@@ -723,7 +767,7 @@ def main():
                              "compare with the N = 1 line's batched.points[windows = windows_per_rank].value, not with its single-window value"}
         else:
             out["throughput_mode_note"] = "identical windows disagreed on a rank: the line falls back to the single-window figure"
-    if world > 1 and not args.shard_factors:
+    if args.full and world > 1 and not args.shard_factors:
         done = threading.Event()
 
         def watchdog():
@@ -767,7 +811,7 @@ def keyframes_workload(args, hip, rank, world, torch, dist):
         return
     n_kf, dt_max, alg_bytes, ms, captured = m["n_kf"], m["dt_max"], m["alg_bytes"], m["device_ms"], m["captured"]
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         o = keyframe_batch_stats(_oracle_lib(), captured, 4, reps=1, distinct_maps=False)
         cpu = {"value": o["keyframes_per_s"], "unit": "keyframes/s", "cores": 1, "kind": "port",
                "sample": "4 keyframes of the same workload refined one after the other by the CPU oracle (oracle/mapping.h RefineKeyframe)"}

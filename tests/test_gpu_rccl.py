@@ -144,7 +144,7 @@ def test_bench_with_two_gpus_runs_over_rccl():
 
     if torch.cuda.device_count() < 2:
         pytest.skip("one GPU visible: the N > 1 control flow is covered by the gloo tests, RCCL at world 1 above")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-pmc", "--no-fed",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-pmc", "--no-fed",
                         "--keyframes", "40", "--windows", "0", "--rank-windows", "40"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of the resident moments kernel on the GPU box.  Output under gpurun_out/r3_res/.
 O=gpurun_out/r3_res; mkdir -p $O; rm -f $O/*
-B="python bench.py --no-pmc --no-cpu-baseline --windows 0 --keyframes 0"
+B="python bench.py --full --no-pmc --no-cpu-baseline --windows 0 --keyframes 0"
 run() { name=$1; shift; env "$@" LIO_DEBUG_TIMING=1 timeout 300 $B > $O/bench_$name.json 2> $O/bench_$name.err; }
 timeout 600 python -m pytest tests/test_gpu_contract.py -q -x 2>&1 | tail -3
 run off LIO_RESIDENT_MOMENTS=0

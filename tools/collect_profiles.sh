@@ -6,9 +6,9 @@ O=$R/gpurun_out/r3final
 mkdir -p $O
 cd $R
 (timeout 900 python -m pytest tests -q -m gpu > $O/pytest_gpu.log 2>&1; echo rc=$? >> $O/pytest_gpu.log)
-(timeout 600 python bench.py > $O/bench.json 2> $O/bench.err)
-(timeout 300 python bench.py --workload vlp16 --no-pmc --no-cpu-baseline --windows 0 --keyframes 0 > $O/bench_vlp16.json 2> $O/bench_vlp16.err)
-B="python bench.py --no-pmc --no-cpu-baseline --windows 0 --keyframes 0 --no-fed"
+(timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err)
+(timeout 300 python bench.py --full --workload vlp16 --no-pmc --no-cpu-baseline --windows 0 --keyframes 0 > $O/bench_vlp16.json 2> $O/bench_vlp16.err)
+B="python bench.py --full --no-pmc --no-cpu-baseline --windows 0 --keyframes 0 --no-fed"
 (LIO_RESIDENT_MOMENTS=0 LIO_DEBUG_TIMING=1 timeout 200 $B > $O/bench_resident_off.json 2> $O/bench_resident_off.err)
 (LIO_DEBUG_TIMING=1 timeout 200 $B > $O/bench_dbg.json 2> $O/bench_dbg.err)
 (LIO_RESIDENT_ROUNDS=1 LIO_DEBUG_TIMING=1 timeout 200 $B > $O/bench_resident_rounds.json 2> $O/bench_resident_rounds.err)
@@ -19,19 +19,19 @@ B="python bench.py --no-pmc --no-cpu-baseline --windows 0 --keyframes 0 --no-fed
 (timeout 120 tools/micro/pingpong > $O/pingpong.txt 2>&1)
 (LIO_DEBUG_TIMING=1 timeout 120 python profiles/pp_profile.py > $O/pp_dbg.log 2>&1)
 cd /tmp && export TMPDIR=/tmp
-(timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/prof_s -o st -- python $R/bench.py --no-pmc --no-cpu-baseline --no-fed --steps 20 --warmup 3 > /dev/null 2>&1)
+(timeout 400 rocprofv3 --kernel-trace --stats -d $TMPDIR/prof_s -o st -- python $R/bench.py --full --no-pmc --no-cpu-baseline --no-fed --steps 20 --warmup 3 > /dev/null 2>&1)
 python $R/profiles/summarize_rocpd.py /tmp/prof_s/st_results.db > $O/kernel_stats.md
 (timeout 200 rocprofv3 --kernel-trace --stats -d /tmp/prof_pp -o pp -- python $R/profiles/pp_profile.py > /dev/null 2>&1)
 python $R/profiles/summarize_rocpd.py /tmp/prof_pp/pp_results.db > $O/pp_kernel_stats.md
-(timeout 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d /tmp/prof_f -o f -- python $R/bench.py --no-pmc --no-cpu-baseline --no-fed --steps 5 --warmup 1 --windows 0 --keyframes 40 > /dev/null 2>&1)
-(timeout 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d /tmp/prof_w -o w -- python $R/bench.py --no-pmc --no-cpu-baseline --no-fed --steps 5 --warmup 1 --windows 0 --keyframes 40 > /dev/null 2>&1)
+(timeout 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $TMPDIR/prof_f -o f -- python $R/bench.py --full --no-pmc --no-cpu-baseline --no-fed --steps 5 --warmup 1 --windows 0 --keyframes 40 > /dev/null 2>&1)
+(timeout 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $TMPDIR/prof_w -o w -- python $R/bench.py --full --no-pmc --no-cpu-baseline --no-fed --steps 5 --warmup 1 --windows 0 --keyframes 40 > /dev/null 2>&1)
 python $R/profiles/pmc_summary.py /tmp/prof_f/f_results.db /tmp/prof_w/w_results.db $O/pmc.json > $O/pmc_hbm_traffic.md
-(timeout 300 rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace -d /tmp/prof_m -o m -- python $R/bench.py --no-pmc --no-cpu-baseline --no-fed --steps 5 --warmup 1 --windows 0 --keyframes 0 > /dev/null 2>&1)
+(timeout 300 rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace -d $TMPDIR/prof_m -o m -- python $R/bench.py --full --no-pmc --no-cpu-baseline --no-fed --steps 5 --warmup 1 --windows 0 --keyframes 0 > /dev/null 2>&1)
 (LIO_MOMENTS=mfma timeout 300 rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU --kernel-trace -d /tmp/prof_mb -o mb -- python $R/tools/batched_moments.py 512 > $O/batched_mfma.txt 2>&1)
 (LIO_MOMENTS=valu timeout 300 rocprofv3 --pmc SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU --kernel-trace -d /tmp/prof_vb -o vb -- python $R/tools/batched_moments.py 512 > $O/batched_valu.txt 2>&1)
 (LIO_MOMENTS=mfma timeout 120 python $R/tools/batched_moments.py > $O/batched_mfma_plain.txt 2>&1)
 (LIO_MOMENTS=valu timeout 120 python $R/tools/batched_moments.py > $O/batched_valu_plain.txt 2>&1)
-(timeout 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES --kernel-trace -d /tmp/prof_q -o q -- python $R/bench.py --no-pmc --no-cpu-baseline --no-fed --steps 5 --warmup 1 --windows 0 --keyframes 40 > /dev/null 2>&1)
+(timeout 300 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES --kernel-trace -d $TMPDIR/prof_q -o q -- python $R/bench.py --full --no-pmc --no-cpu-baseline --no-fed --steps 5 --warmup 1 --windows 0 --keyframes 40 > /dev/null 2>&1)
 python - <<'PY' > $O/pmc_counters.md
 import sqlite3, glob
 def table(dbglob, title, pick):

@@ -4,7 +4,7 @@ O=$R/gpurun_out/r2pmcf
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 -L 2>/dev/null | grep -o "SQ_[A-Z_0-9]*" | sort -u > $O/sq_counters.txt
-run() { tag=$1; shift; timeout 300 rocprofv3 --pmc "$@" --kernel-trace -d /tmp/p_$tag -o p -- python $R/bench.py --no-pmc --no-cpu-baseline --steps 5 --warmup 1 --windows 0 --keyframes 0 > /dev/null 2> $O/err_$tag.txt; python - "$tag" <<'PY'
+run() { tag=$1; shift; timeout 300 rocprofv3 --pmc "$@" --kernel-trace -d $TMPDIR/p_$tag -o p -- python $R/bench.py --full --no-pmc --no-cpu-baseline --steps 5 --warmup 1 --windows 0 --keyframes 0 > /dev/null 2> $O/err_$tag.txt; python - "$tag" <<'PY'
 import sqlite3, sys, os, glob
 tag = sys.argv[1]
 db = glob.glob(f"/tmp/p_{tag}/*results.db")

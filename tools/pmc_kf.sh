@@ -2,7 +2,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r3e
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-run() { tag=$1; shift; timeout 300 rocprofv3 --pmc "$@" --kernel-trace -d /tmp/p_$tag -o p -- python $R/bench.py --no-pmc --no-cpu-baseline --steps 3 --warmup 1 --windows 0 --keyframes 300 > /dev/null 2> $O/err_$tag.txt; python - "$tag" <<'PY'
+run() { tag=$1; shift; timeout 300 rocprofv3 --pmc "$@" --kernel-trace -d $TMPDIR/p_$tag -o p -- python $R/bench.py --full --no-pmc --no-cpu-baseline --steps 3 --warmup 1 --windows 0 --keyframes 300 > /dev/null 2> $O/err_$tag.txt; python - "$tag" <<'PY'
 import sqlite3, sys, os, glob
 tag = sys.argv[1]
 db = glob.glob(f"/tmp/p_{tag}/*results.db")
