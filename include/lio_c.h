@@ -543,7 +543,7 @@ int lio_est_batch_sync(lio_est_batch *);
  * (it runs on a stream of its own beside this solve's first stages and is joined in front of the problems' upload); with the
  * option "time_kernels" (measurement runs: HIP events around every launch of the trust-region loop, on the stream it runs on)
  * [17..19] summed duration (ms) and [20..22] number of the last solve's launches of the aux row, the moments pass and the step
- * kernel, else 0; [23] reserved.  out: 24 doubles. */
+ * kernel, else 0; [23] reserved (0).  out: 24 doubles. */
 int lio_est_batch_get_clock(const lio_est_batch *, double *out24);
 /* Execution choices of a batch that its results do not depend on (bit for bit: tests/test_gpu_batch_scale.py), by name; value 0
  * (occupancy: -1) = chosen by the size of the launch, the default.  "lanes_per_query" 1 | 2 | 4 | 8 (search kernels of

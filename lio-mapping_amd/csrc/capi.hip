@@ -6,6 +6,7 @@
 #include <new>
 
 #include "../../include/lio_c.h"
+#include "../../include/lio_test_hooks.h"
 #include "est_batch.h"
 #include "seg_sort.h"
 #include "estimator.h"
@@ -868,6 +869,16 @@ size_t lio_est_get_features(const lio_est *h, int frame, double *pt, double *co,
   guarded([&] { n = h->e->GetFeatures(frame, pt, co, sc); return LIO_OK; });
   return n;
 }
+int lio_est_eval_lidar_moments(lio_est *h, int n_passes, const double *Rt, double *out, int *path_out) {
+  if (!h || n_passes < 1 || !Rt || !out) return LIO_ERR_ARG;
+  if (!h->e->inited_) return LIO_ERR_STATE;
+  return guarded([&] {
+    const int path = h->e->EvalLidarMoments(n_passes, Rt, out);
+    if (path < 0) return LIO_ERR_STATE;
+    if (path_out) *path_out = path;
+    return LIO_OK;
+  });
+}
 int lio_est_get_laser_odom_transform(const lio_est *h, lio_transform_f *out) {
   if (!h || !out) return LIO_ERR_ARG;
   fromT(h->e->laser_odom_transform_, out);
@@ -1077,6 +1088,15 @@ int lio_est_batch_stage_digest(lio_est_batch *h, int stage, unsigned long long *
   if (!h->b) return LIO_ERR_STATE;
   return guarded([&] { h->b->StageDigest(stage, out); if (h->b2) h->b2->StageDigest(stage, out + h->n1); return LIO_OK; });
 }
+int lio_est_batch_get_moments(lio_est_batch *h, int window, double *out, double *Rt) {
+  if (!h || !out || !Rt || window < 0) return LIO_ERR_ARG;
+  if (!h->b) return LIO_ERR_STATE;
+  if (window >= int(h->members.size())) return LIO_ERR_ARG;
+  return guarded([&] {
+    const bool ok = window < h->n1 ? h->b->GetMoments(window, out, Rt) : h->b2->GetMoments(window - h->n1, out, Rt);
+    return ok ? int(LIO_OK) : int(LIO_ERR_STATE);
+  });
+}
 int lio_est_batch_get_clock(const lio_est_batch *h, double *out) {
   if (!h || !out) return LIO_ERR_ARG;
   if (!h->b) return LIO_ERR_STATE;
@@ -1103,6 +1123,7 @@ int lio_est_batch_get_clock(const lio_est_batch *h, double *out) {
   out[8] = c.n_device; out[9] = c.rounds;
   out[16] = c.dev_marg_wait;
   for (int k = 0; k < 3; ++k) { out[17 + k] = c.kernel_ms[k]; out[20 + k] = double(c.kernel_launches[k]); }
+  out[23] = 0.0;   // reserved
   return LIO_OK;
 }
 

@@ -58,6 +58,12 @@ class EstimatorBatch {
   // cell run: the placement order inside a cell is not defined), 2 feature flags, 3 plane coefficients of the set flags, 4 the newest
   // frame's Gauss-Newton state, 5 the trust-region loop's final state, 6 the final moments partials.  Waits for the batch.
   void StageDigest(int stage, unsigned long long *out);
+  // Test hook (lio_est_batch_get_moments): window w's moments at the point its last Solve() accepted — S_buf at st.s_cur, Wo x 258
+  // (S 16 x 16 row-major, cost, count) — and the T_{pivot<-i} of that point (Wo x 12: R row-major, t).  false: the window was not
+  // solved on the device.  Waits for the batch.
+  bool GetMoments(int w, double *out, double *Rt);
+  // lio_est_get_features of a member whose last Solve() ran on the device: its feature slots live in the batch's arrays
+  size_t GetFeatures(int w, int frame, double *pt, double *co, double *sc);
   hipStream_t stream() const { return stream_; }
   // execution choices (batch_kernels.h: BatchKnobs) by name: lanes_per_query, occupancy, loop_groups, aux_threads, aux_stream, finish_threads;
   // false: unknown name or a value the knob does not take

@@ -69,7 +69,10 @@ EstimatorBatch::~EstimatorBatch() {
     if (stream_marg_) (void)hipStreamSynchronize(stream_marg_);
     for (size_t w = 0; w < win_.size(); ++w)
       for (int k = 0; k < 2; ++k) if (win_[w].dev_prior[k]) win_[w].dev_prior[k]->materialize();   // nobody may be left holding a shell
-    for (Estimator *e : m_) { e->solve_hook_ = nullptr; e->ReleaseAdoptedStream(); }
+    for (Estimator *e : m_) {
+      e->solve_hook_ = nullptr; e->ReleaseAdoptedStream();
+      if (e->feat_batch_ == this) { e->feat_batch_ = nullptr; e->feat_batch_w_ = -1; }   // (its getter falls back to the handle's own slots)
+    }
   } catch (...) {}
   for (void *p : {static_cast<void *>(h_win_), static_cast<void *>(h_grid_), static_cast<void *>(h_vout_), static_cast<void *>(h_odom_), static_cast<void *>(h_bs_),
                   static_cast<void *>(h_pb_), static_cast<void *>(h_st_), static_cast<void *>(h_mg_), static_cast<void *>(h_prior_), static_cast<void *>(h_nconv_),
@@ -257,6 +260,43 @@ void EstimatorBatch::StageDigest(int stage, unsigned long long *out) {
     }
     out[w] = h;
   }
+}
+
+bool EstimatorBatch::GetMoments(int w, double *out, double *Rt) {
+  if (w < 0 || w >= size() || !win_[size_t(w)].device) return false;
+  Sync();
+  for (hipStream_t g : stream_grp_) LIO_HIP(hipStreamSynchronize(g));
+  const Estimator *e = win_[size_t(w)].e;
+  const int Wo = e->Wo_;
+  const std::vector<DevState> st = fetch(d_st_.p + w, 1);
+  const std::vector<double> S = fetch(slab_.p + size_t(w) * lay_.total + lay_.Sbuf + size_t(st[0].s_cur) * Wo * LIO_MOMENT_OUT, size_t(Wo) * LIO_MOMENT_OUT);
+  for (int f = 0; f < Wo; ++f) {
+    std::memcpy(out + size_t(f) * 258, S.data() + size_t(f) * LIO_MOMENT_OUT, 258 * sizeof(double));
+    relative_lidar_pose(st[0].x.pose[0], st[0].x.pose[f + 1], st[0].x.ex, Rt + size_t(f) * 12, Rt + size_t(f) * 12 + 9);
+  }
+  return true;
+}
+
+size_t EstimatorBatch::GetFeatures(int w, int frame, double *pt, double *co, double *sc) {
+  const Estimator *e = win_[size_t(w)].e;
+  if (frame < 0 || frame > e->W_ || e->nslots_[frame] == 0) return 0;
+  Sync();
+  const size_t off = size_t(h_win_[w].slot_base) + size_t(e->slot_off_[frame]), ns = size_t(e->nslots_[frame]);
+  const size_t M = e->stacks_[frame].n;
+  const std::vector<uint8_t> v = fetch(valid_all_.p + off, ns);
+  const std::vector<float4> c = fetch(coef_all_.p + off, ns);
+  const std::vector<float> s = fetch(score_all_.p + off, ns);
+  const std::vector<float4> p = fetch(e->stacks_[frame].buf.p, M);
+  size_t k = 0;
+  for (size_t i = 0; i < ns; ++i) {
+    if (!v[i]) continue;
+    const float4 &pp = p[i % M];
+    if (pt) { pt[3 * k] = pp.x; pt[3 * k + 1] = pp.y; pt[3 * k + 2] = pp.z; }
+    if (co) { co[4 * k] = c[i].x; co[4 * k + 1] = c[i].y; co[4 * k + 2] = c[i].z; co[4 * k + 3] = c[i].w; }
+    if (sc) sc[k] = s[i];
+    ++k;
+  }
+  return k;
 }
 
 int EstimatorBatch::Solve(lio_solve_report *reps) {
@@ -663,6 +703,7 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
   clk_.total = t6 - t0;
   for (int w = 0; w < B; ++w) {
     if (!win_[w].device) continue;
+    win_[w].e->feat_batch_ = this; win_[w].e->feat_batch_w_ = w;   // its feature slots are in valid_all_ / coef_all_ / score_all_
     lio_solve_report &R = reps[w];
     R.ms_build_map = clk_.map; R.ms_features = clk_.grid_features; R.ms_prepare = clk_.describe + clk_.pack; R.ms_opt = clk_.solve; R.ms_marg = clk_.finish;
     R.ms_total = t5 - t0;

@@ -150,6 +150,8 @@ class MargWorker {
   bool quit_ = false;
 };
 
+class EstimatorBatch;
+
 class Estimator {
  public:
   explicit Estimator(const EstConfig &cfg);
@@ -194,6 +196,11 @@ class Estimator {
   void BeginFrame(const V3d &acc, const V3d &gyr);
   size_t GetLocalMap(float *out);
   size_t GetFeatures(int frame, double *pt, double *co, double *sc);
+  // lio_est_eval_lidar_moments: the lidar moments of frames pivot+1 .. pivot+Wo at caller-given T_{pivot<-i} (Rt: n_passes x Wo x 12,
+  // R row-major then t), every pass inside ONE solve scope through the path the estimator is configured for; out: n_passes x Wo x 258
+  // (S 16 x 16 row-major, cost, count).  A sharded estimator returns its own share (no all-reduce).  Returns the path of the last pass:
+  // 0 MFMA launch pair, 1 VALU launch pair, 2 resident kernel.
+  int EvalLidarMoments(int n_passes, const double *Rt, double *out);
   void Snapshot();
   bool Restore();
   // this handle's snapshot <- a copy of src's (same configuration; clouds copied into buffers of this handle): B windows of the
@@ -258,7 +265,8 @@ class Estimator {
   void FillMomentArgs(MomentArgs &ma, int &max_slots) const;
   void LidarEval(const WindowParams &P, std::vector<FrameMoments> &m);
   void LidarLaunch(const WindowParams &P);             // asynchronous part: frame transforms + moments kernels
-  void LidarWait(std::vector<FrameMoments> &m);        // stream sync (+ all-reduce when sharded) + unpack
+  void LidarLaunchMoments(const MomentArgs &ma, bool reduce = true);   // ... from a filled MomentArgs (reduce = false: a shard's own share)
+  void LidarWait(std::vector<FrameMoments> &m, bool reduce = true);    // stream sync (+ all-reduce when sharded and `reduce`) + unpack
   bool LidarWaitFrame(int i, FrameMoments &fm);       // per-frame form (resident kernel only; false otherwise)
   void PushCloud(DeviceCloud &&c, size_t n, int n_before);
   void PushState(int from);
@@ -281,6 +289,10 @@ class Estimator {
   DBuf<float> f_score_;
   std::vector<int> slot_off_, nslots_;
   size_t total_slots_ = 0;
+  // the batch whose arrays hold this window's feature slots (its last Solve ran the window on the device) and the window's index in it;
+  // null once the single-window path builds features again (BuildLocalMap) or the batch is gone
+  EstimatorBatch *feat_batch_ = nullptr;
+  int feat_batch_w_ = -1;
   DBuf<float> d_transforms_;
   DBuf<OdomState> d_odom_;
   DBuf<double> d_odom_partials_, d_moment_partials_, d_moment_out_;

@@ -2,6 +2,7 @@
 // Reference call structure: Estimator.cc:430-774 (ProcessLaserOdom), :1361-1646 (BuildLocalMap),
 // :1648-2438 (SolveOptimization), :2440-2568 (VectorToDouble/DoubleToVector), :2570-2666 (SlideWindow).
 #include "estimator.h"
+#include "est_batch.h"
 #include "marg_kernels.h"
 #include "rccl_comm.h"
 
@@ -252,6 +253,7 @@ size_t Estimator::GetLocalMap(float *out) {
 }
 
 size_t Estimator::GetFeatures(int frame, double *pt, double *co, double *sc) {
+  if (feat_batch_) return feat_batch_->GetFeatures(feat_batch_w_, frame, pt, co, sc);   // the last solve ran in a batch, on the device
   if (frame < 0 || frame > W_ || nslots_[frame] == 0) return 0;
   const int off = slot_off_[frame], ns = nslots_[frame];
   const size_t M = stacks_[frame].n;
@@ -463,6 +465,7 @@ void Estimator::FusePivotOnce() {
 
 void Estimator::BuildLocalMap(lio_solve_report *rep) {
   const double t0 = now_ms();
+  feat_batch_ = nullptr; feat_batch_w_ = -1;   // the feature slots are this handle's own again
   const int pivot = W_ - Wo_;
   const Rigidd lb = toDouble(transform_lb_);
   const Rigidd T_pivot = LidarPose(pivot, lb);
@@ -858,12 +861,16 @@ void Estimator::ResidentEnd() {
 }
 
 void Estimator::LidarLaunch(const WindowParams &P) {
-  const double t_dbg0 = now_ms();
-  struct DbgAcc { Estimator *e; double t0; ~DbgAcc() { e->dbg_eval_ms_ += now_ms() - t0; } } dbg_acc{this, t_dbg0};
   MomentArgs ma;
   int max_slots = 0;
   FillMomentArgs(ma, max_slots);
   for (int i = 1; i <= Wo_; ++i) relative_lidar_pose(P.pose[0].data(), P.pose[i].data(), P.ex.data(), ma.fr[i - 1].R, ma.fr[i - 1].t);
+  LidarLaunchMoments(ma);
+}
+
+void Estimator::LidarLaunchMoments(const MomentArgs &ma, bool reduce) {
+  const double t_dbg0 = now_ms();
+  struct DbgAcc { Estimator *e; double t0; ~DbgAcc() { e->dbg_eval_ms_ += now_ms() - t0; } } dbg_acc{this, t_dbg0};
   if (res_active_ || ResidentBegin(ma)) {
     res_t_ring_ = now_ms();
     ResidentRing(ma);
@@ -885,7 +892,7 @@ void Estimator::LidarLaunch(const WindowParams &P) {
     // per-shard moments -> whole-window moments without leaving HBM: fold into a device buffer, SUM all-reduce over xGMI on the
     // same stream, then the 10 KB result goes to the pinned landing zone
     launch_lidar_moments(ma, f_valid_.p, f_coef_.p, d_moment_partials_.p, d_moment_out_.p, stream_);
-    rccl_all_reduce_sum_f64(rccl_comm_, d_moment_out_.p, size_t(Wo_) * LIO_MOMENT_OUT, stream_);
+    if (reduce) rccl_all_reduce_sum_f64(rccl_comm_, d_moment_out_.p, size_t(Wo_) * LIO_MOMENT_OUT, stream_);
     LIO_HIP(hipMemcpyAsync(h_moment_out_, d_moment_out_.p, sizeof(double) * Wo_ * LIO_MOMENT_OUT, hipMemcpyDeviceToHost, stream_));
   } else {
     moment_signal_ = HostSignal();
@@ -896,6 +903,35 @@ void Estimator::LidarLaunch(const WindowParams &P) {
     launch_lidar_moments(ma, f_valid_.p, f_coef_.p, d_moment_partials_.p, h_moment_out_, stream_, moment_signal_);
   }
   timers_.end(th, stream_);
+}
+
+int Estimator::EvalLidarMoments(int n_passes, const double *Rt, double *out) {
+  if (feat_batch_) return -1;   // the slot layout is the batch's (its arrays, not f_valid_ / f_coef_): lio_est_build_local_map first
+  // the guards of SolveOptimizationHost: one solve scope, so that with the resident form the passes are passes 1 .. n of one launch
+  struct ActiveSolve { ActiveSolve() { g_active_solves.fetch_add(1); } ~ActiveSolve() { g_active_solves.fetch_sub(1); } } active_solve;
+  struct ResidentScope { Estimator *e; ~ResidentScope() { e->ResidentEnd(); } } resident_scope{this};
+  res_allowed_ = true;
+  MomentArgs ma;
+  int max_slots = 0;
+  FillMomentArgs(ma, max_slots);
+  std::vector<FrameMoments> m(size_t(Wo_) + 1);
+  int path = 0;
+  for (int p = 0; p < n_passes; ++p) {
+    for (int f = 0; f < Wo_; ++f) {
+      const double *src = Rt + (size_t(p) * Wo_ + f) * 12;
+      for (int k = 0; k < 9; ++k) ma.fr[f].R[k] = src[k];
+      for (int k = 0; k < 3; ++k) ma.fr[f].t[k] = src[9 + k];
+    }
+    LidarLaunchMoments(ma, false);
+    path = res_active_ ? 2 : (ma.form == 2 ? 1 : 0);
+    LidarWait(m, false);
+    for (int f = 0; f < Wo_; ++f) {
+      double *dst = out + (size_t(p) * Wo_ + f) * 258;
+      std::memcpy(dst, m[size_t(f) + 1].S, 256 * sizeof(double));
+      dst[256] = m[size_t(f) + 1].cost; dst[257] = m[size_t(f) + 1].count;
+    }
+  }
+  return path;
 }
 
 bool Estimator::BenchBatchedMoments(int B, int reps, double *avg_ms, double *bytes) {
@@ -959,7 +995,7 @@ bool Estimator::LidarWaitFrame(int i, FrameMoments &fm) {
   return true;
 }
 
-void Estimator::LidarWait(std::vector<FrameMoments> &m) {
+void Estimator::LidarWait(std::vector<FrameMoments> &m, bool reduce) {
   const double t_dbg0 = now_ms();
   struct DbgAcc { Estimator *e; double t0; ~DbgAcc() { e->dbg_eval_ms_ += now_ms() - t0; e->dbg_eval_n_++; } } dbg_acc{this, t_dbg0};
   if (res_active_) { ResidentWait(m); dbg_sync_ms_ += now_ms() - t_dbg0; res_ring_to_done_ms_ += now_ms() - res_t_ring_; return; }
@@ -967,7 +1003,7 @@ void Estimator::LidarWait(std::vector<FrameMoments> &m) {
   else LIO_HIP(hipStreamSynchronize(stream_));
   dbg_sync_ms_ += now_ms() - t_dbg0;
   timers_.resolve();
-  if (shard_world_ > 1 && allreduce_ && !rccl_comm_) {
+  if (reduce && shard_world_ > 1 && allreduce_ && !rccl_comm_) {
     // per-shard moments -> whole-window moments through the caller's callback (gloo on CPU hosts; the RCCL form never gets here)
     if (allreduce_(h_moment_out_, Wo_ * LIO_MOMENT_OUT, allreduce_user_) != 0) throw std::runtime_error("factor-sharding all-reduce failed");
   }

@@ -443,7 +443,8 @@ __global__ void __launch_bounds__(MOMENT_THREADS) k_lidar_moments_resident(Momen
       ok[it] = in && valid[fr.slot_off + si] != 0;
       const float4 po = fr.stack[si % fr.M];
       px[it] = po.x; py[it] = po.y; pz[it] = po.z;
-      cf[it] = coef[fr.slot_off + si];
+      // (a frame without slots has no slot of its own to load from: its slot_off may be the end of the slot arrays)
+      cf[it] = coef[fr.slot_end > fr.slot_begin ? fr.slot_off + si : 0];
     }
   }
   __shared__ double zbuf[MOMENT_THREADS / 64][64 * ZROW];

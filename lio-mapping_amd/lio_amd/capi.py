@@ -261,6 +261,11 @@ _SIGS = {
     "lio_est_enable_kernel_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "lio_est_get_kernel_timing": (C.c_int, [C.c_void_p, C.c_char_p, c_double_p, c_double_p]),
 }
+# include/lio_test_hooks.h: test hooks kept apart from the ABI of lio_c.h
+_TEST_SIGS = {
+    "lio_est_eval_lidar_moments": (C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p, C.POINTER(C.c_int)]),
+    "lio_est_batch_get_moments": (C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
+}
 
 
 def _dp(a):
@@ -296,6 +301,16 @@ class LioLib:
         self.dll = C.CDLL(path)
         for name, (res, args) in _SIGS.items():
             fn = getattr(self.dll, name)
+            fn.restype = res
+            fn.argtypes = args
+        # the test hooks (include/lio_test_hooks.h): a library built before a hook existed still loads, and only a call to the
+        # missing hook fails (AttributeError); tests/test_abi.py holds both libraries to the whole header
+        self.missing = []
+        for name, (res, args) in _TEST_SIGS.items():
+            fn = getattr(self.dll, name, None)
+            if fn is None:
+                self.missing.append(name)
+                continue
             fn.restype = res
             fn.argtypes = args
         self.backend = self.dll.lio_backend().decode()
@@ -941,6 +956,16 @@ class Estimator:
             self.lib.dll.lio_est_get_features(self.h, frame, _dp(pt), _dp(co), _dp(sc))
         return pt, co, sc
 
+    def eval_lidar_moments(self, Rt):
+        """Rt: (n_passes, Wo, 12) T_{pivot<-i} (R row-major, t) -> (moments (n_passes, Wo, 258): S 16x16 row-major, cost, count;
+        path of the last pass: 0 MFMA launch pair, 1 VALU launch pair, 2 resident kernel, -1 the oracle)"""
+        Rt = _f64(Rt)
+        n_passes, wo = Rt.shape[0], Rt.shape[1]
+        out = np.zeros((n_passes, wo, 258))
+        path = C.c_int(-3)
+        _chk(self.lib.dll.lio_est_eval_lidar_moments(self.h, n_passes, _dp(Rt), _dp(out), C.byref(path)), "lio_est_eval_lidar_moments")
+        return out, path.value
+
     def laser_odom_transform(self):
         T = TransformF()
         _chk(self.lib.dll.lio_est_get_laser_odom_transform(self.h, C.byref(T)), "lio_est_get_laser_odom_transform")
@@ -1077,6 +1102,13 @@ class EstimatorBatch:
         out = (C.c_ulonglong * len(self.members))()
         _chk(self.lib.dll.lio_est_batch_stage_digest(self.h, int(stage), out), "lio_est_batch_stage_digest")
         return np.array(list(out), dtype=np.uint64)
+
+    def moments(self, window):
+        """(moments (Wo, 258), Rt (Wo, 12)) of window `window` at the point its last batch solve accepted"""
+        wo = self.members[window].cfg.opt_window_size
+        out, Rt = np.zeros((wo, 258)), np.zeros((wo, 12))
+        _chk(self.lib.dll.lio_est_batch_get_moments(self.h, int(window), _dp(out), _dp(Rt)), "lio_est_batch_get_moments")
+        return out, Rt
 
     def clock(self):
         out = (C.c_double * 24)()

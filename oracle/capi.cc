@@ -5,6 +5,7 @@
 #include <new>
 
 #include "../include/lio_c.h"
+#include "../include/lio_test_hooks.h"
 #include "estimator.h"
 #include "imu_init.h"
 #include "mapping.h"
@@ -689,6 +690,39 @@ size_t lio_est_get_features(const lio_est *h, int frame, double *pt, double *co,
   }
   return f.size();
 }
+int lio_est_eval_lidar_moments(lio_est *h, int n_passes, const double *Rt, double *out, int *path_out) {
+  // the defining sums, serially in fp64 over the oracle's own feature slots (no reference counterpart: a test hook)
+  if (!h || n_passes < 1 || !Rt || !out) return LIO_ERR_ARG;
+  const Estimator &e = h->est;
+  if (!e.inited) return LIO_ERR_STATE;
+  const int pivot = e.W - e.Wo;
+  for (int p = 0; p < n_passes; ++p)
+    for (int f = 0; f < e.Wo; ++f) {
+      const double *R = Rt + (size_t(p) * e.Wo + f) * 12, *t = R + 9;
+      double *o = out + (size_t(p) * e.Wo + f) * 258;
+      for (int k = 0; k < 258; ++k) o[k] = 0.0;
+      const int idx = pivot + 1 + f;
+      if (idx >= int(e.feature_frames.size())) continue;
+      double cost = 0.0, count = 0.0;
+      for (const PlaneFeature &ft : e.feature_frames[size_t(idx)]) {
+        const double *c = ft.coeffs;
+        const double px = ft.point.x, py = ft.point.y, pz = ft.point.z;
+        const double q[3] = {R[0] * px + R[1] * py + R[2] * pz + t[0], R[3] * px + R[4] * py + R[5] * pz + t[1], R[6] * px + R[7] * py + R[8] * pz + t[2]};
+        const double r = c[0] * q[0] + c[1] * q[1] + c[2] * q[2] + c[3];
+        const double rho1 = 1.0 / (1.0 + r * r);
+        const double z[13] = {c[0] * px, c[0] * py, c[0] * pz, c[0], c[1] * px, c[1] * py, c[1] * pz, c[1], c[2] * px, c[2] * py, c[2] * pz, c[2], c[3]};
+        for (int a = 0; a < 13; ++a)
+          for (int b = a; b < 13; ++b) o[a * 16 + b] += rho1 * z[a] * z[b];
+        cost += 0.5 * std::log1p(r * r);
+        count += 1.0;
+      }
+      for (int a = 0; a < 13; ++a)
+        for (int b = 0; b < a; ++b) o[a * 16 + b] = o[b * 16 + a];   // S is symmetric: the lower triangle is the upper one
+      o[256] = cost; o[257] = count;
+    }
+  if (path_out) *path_out = -1;
+  return LIO_OK;
+}
 int lio_est_get_laser_odom_transform(const lio_est *h, lio_transform_f *out) {
   if (!h || !out) return LIO_ERR_ARG;
   fromT(h->est.laser_odom_transform, out);
@@ -864,6 +898,15 @@ int lio_est_batch_stage_digest(lio_est_batch *b, int stage, unsigned long long *
   if (!b || !out || stage < 0 || stage > 9) return LIO_ERR_ARG;
   if (b->dissolved) return LIO_ERR_STATE;
   for (size_t w = 0; w < b->members.size(); ++w) out[w] = 0;
+  return LIO_OK;
+}
+int lio_est_batch_get_moments(lio_est_batch *b, int window, double *out, double *Rt) {
+  if (!b || !out || !Rt || window < 0) return LIO_ERR_ARG;
+  if (b->dissolved) return LIO_ERR_STATE;
+  if (window >= int(b->members.size())) return LIO_ERR_ARG;
+  const int Wo = b->members[size_t(window)]->est.Wo;
+  for (int k = 0; k < Wo * 258; ++k) out[k] = 0.0;
+  for (int k = 0; k < Wo * 12; ++k) Rt[k] = 0.0;
   return LIO_OK;
 }
 int lio_est_batch_get_clock(const lio_est_batch *b, double *out) {

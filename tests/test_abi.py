@@ -69,6 +69,46 @@ def test_header_is_plain_c_and_links_against_the_oracle(tmp_path, oracle):
     _c_translation_unit(tmp_path, os.path.join(ROOT, "oracle", "liblio_oracle.so"), "oracle-cpu")
 
 
+def _declared_test_hooks():
+    text = open(os.path.join(ROOT, "include", "lio_test_hooks.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return sorted(set(re.findall(r"\b(lio_[a-z0-9_]+)\s*\(", text)))
+
+
+def test_test_hooks_are_bound_and_exported_by_both_libraries(oracle):
+    """include/lio_test_hooks.h: every hook bound in Python and exported by the product and the oracle"""
+    hooks = _declared_test_hooks()
+    assert len(hooks) >= 2
+    assert set(hooks) == set(capi._TEST_SIGS.keys())
+    assert not set(hooks) & set(_declared_symbols())
+    dll = ctypes.CDLL(capi.HIP_LIB_PATH)
+    for s in hooks:
+        assert hasattr(dll, s), s
+        assert hasattr(oracle.dll, s), s
+    assert oracle.missing == []
+
+
+@pytest.mark.parametrize("lib", ["hip", "oracle"])
+def test_test_hook_header_is_plain_c_and_links(tmp_path, oracle, lib):
+    """the hooks' header compiled by a C compiler and linked with each library"""
+    import subprocess
+
+    path = capi.HIP_LIB_PATH if lib == "hip" else os.path.join(ROOT, "oracle", "liblio_oracle.so")
+    src = tmp_path / "hooks.c"
+    src.write_text('#include "lio_test_hooks.h"\n#include <stdio.h>\n'
+                   "int main(void) {\n"
+                   "  int path = 7;\n"
+                   "  if (lio_est_eval_lidar_moments(NULL, 1, NULL, NULL, &path) != LIO_ERR_ARG || path != 7) return 1;\n"
+                   "  if (lio_est_batch_get_moments(NULL, 0, NULL, NULL) != LIO_ERR_ARG) return 2;\n"
+                   '  puts("hooks ok");\n  return 0;\n}\n')
+    exe = tmp_path / "hooks"
+    libdir, libname = os.path.dirname(path), os.path.basename(path)
+    subprocess.run(["gcc", "-std=c99", "-pedantic-errors", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe),
+                    "-L", libdir, "-l" + libname[3:-3], "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib"], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0 and "hooks ok" in r.stdout, r.stderr + r.stdout
+
+
 def test_product_has_no_cpu_fallback(hip):
     """Without a GPU every data-path entry point must fail loudly (LIO_ERR_DEVICE), never compute on the CPU."""
     import torch

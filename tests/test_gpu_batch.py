@@ -6,6 +6,8 @@ launch B of solve_kernels.hip and the batched marginalization of marg_kernels.hi
   marginalization, with different window sizes, keep_features on and off, in one batch;
 * a batch against the oracle, teacher-forced step by step: equal decisions and iteration counts, 1e-4 m / 1e-4 rad;
 * BASELINE.json's HDL-64E / window 15 / opt 5 configuration in a batch, against the oracle and against the single-window handle."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -157,6 +159,12 @@ def test_headline_configuration_in_a_batch(hip, oracle):
     clk = batch.clock()
     assert int(clk["n_device"]) == len(seeds), clk
     print("batch clock (ms):", {k: round(v, 3) for k, v in clk.items()})
+    # lio_est_batch_get_clock writes all 24 values, the reserved [23] included (LioBatch.clock() cannot show it: its buffer starts
+    # zeroed and it drops [23]): called directly on a buffer full of NaN
+    raw = (ctypes.c_double * 24)(*([float("nan")] * 24))
+    assert hip.dll.lio_est_batch_get_clock(batch.h, raw) == 0
+    assert all(np.isfinite(v) for v in raw), list(raw)
+    assert raw[23] == 0.0
     # the oracle and the default single-window path on the first window
     eo, eh = make(oracle, seeds[0]), make(hip, seeds[0])
     ro, rh = eo.solve(), eh.solve()
