@@ -356,7 +356,6 @@ typedef struct {
                                  environment select it too.  Ignores max_solver_time */
   int inline_marg;            /* 1: marginalization inside lio_est_solve_optimization instead of the worker thread (LIO_ASYNC_MARG=0) */
   int stream_sync;            /* 1: hipStreamSynchronize + D2H copies instead of completion words in host memory (LIO_HOST_SIGNAL=0) */
-  int moments_form;           /* 0: by launch size, 1: fp64 MFMA form, 2: structured fp64 VALU form (LIO_MOMENTS=mfma|valu) */
   int resident_moments;       /* 0: by default rule (on), 1: on, 2: off, 3: its partition with launches only — the lidar moments of a solve
                                  come from ONE resident kernel that waits for each linearisation point on a doorbell in host memory
                                  (LIO_RESIDENT_MOMENTS=0|1).  "On" is a permission: a solve takes the resident form while it is the only
@@ -546,14 +545,12 @@ int lio_est_batch_sync(lio_est_batch *);
  * kernel, else 0; [23] reserved (0).  out: 24 doubles. */
 int lio_est_batch_get_clock(const lio_est_batch *, double *out24);
 /* Execution choices of a batch that its results do not depend on (bit for bit: tests/test_gpu_batch_scale.py), by name; value 0
- * (occupancy: -1) = chosen by the size of the launch, the default.  "lanes_per_query" 1 | 2 | 4 | 8 (search kernels of
- * CalculateFeatures / CalculateLaserOdom), "occupancy" 0 | 6 | 8 waves per SIMD of their one-lane-per-query forms, "loop_groups"
- * 1 .. 4 launch chains of the trust-region loop side by side, "aux_threads" 64 | 128 | 256 threads per block of the IMU / prior
- * row, "aux_stream" 0 | 1, "finish_threads" 1 .. 8 host threads of the write-back, "parts" 1 | 2 (a batch of at least 96 windows is solved
- * as two halves side by side from two host threads — one half's host phases and latency-bound stages fill with the other's kernels; the
- * clock then gives the longer half's host times and the SUM of the halves' device times), "time_kernels" 0 | 1 (lio_est_batch_get_clock).  The environment variables LIO_BW_LPQ,
- * LIO_BW_OCC, LIO_BW_GROUPS, LIO_BW_AUX_THREADS, LIO_BW_AUX_STREAM, LIO_BW_FINISH_THREADS set a new batch's defaults (read once
- * at lio_est_batch_create).  LIO_ERR_ARG: unknown name or value.  The oracle accepts and ignores them. */
+ * = chosen by the size of the launch, the default.  "lanes_per_query" 1 | 4 | 8 (search kernels of CalculateFeatures /
+ * CalculateLaserOdom), "loop_groups" 1 .. 4 launch chains of the trust-region loop side by side, "aux_threads" 64 | 128 | 256 threads
+ * per block of the IMU / prior row, "finish_threads" 1 .. 8 host threads of the write-back, "parts" 1 | 2 (a batch of at least 96
+ * windows is solved as two halves side by side from two host threads — one half's host phases and latency-bound stages fill with the
+ * other's kernels; the clock then gives the longer half's host times and the SUM of the halves' device times), "time_kernels" 0 | 1
+ * (lio_est_batch_get_clock).  LIO_ERR_ARG: unknown name or value.  The oracle accepts and ignores them. */
 int lio_est_batch_set_option(lio_est_batch *, const char *name, int value);
 /* Test hook: the segmented stable radix sort of the batched BuildLocalMap (csrc/seg_sort.h; it orders a window's points by PCL's voxel
  * index, Estimator.cc:1518-1519, and by K-NN cell, :1544-1545): `passes` passes of `bits` (1 .. 9) bits from bit 0 over

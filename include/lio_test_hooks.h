@@ -17,9 +17,10 @@ extern "C" {
  * Rt: n_passes x Wo x 12 (R row-major, t); out: n_passes x Wo x 258 (S 16x16 row-major, cost, count) with
  * S = sum_k rho'_k z_k z_k^T, z = [w (x) [p;1]; d] (13 values padded to 16), rho' = 1 / (1 + r^2), cost = 0.5 sum log(1 + r^2).
  * All passes run inside ONE solve scope, so with the resident form they are passes 1..n of one resident launch.  With factor sharding
- * the result is this rank's share, before any all-reduce.  path_out_or_null: 0 MFMA launch pair, 1 VALU launch pair, 2 resident
- * kernel (the oracle: -1).  The oracle forms the defining sums serially in fp64 over its own feature slots.  LIO_ERR_STATE when the
- * handle's feature slots live in a batch (its last solve ran in one): lio_est_build_local_map first. */
+ * the result is this rank's share, before any all-reduce.  path_out_or_null: 0 MFMA launch pair, 2 resident kernel (the oracle: -1;
+ * 1, the VALU launch pair of earlier versions, is no longer returned).  The oracle forms the defining sums serially in fp64 over its
+ * own feature slots.  LIO_ERR_STATE when the handle's feature slots live in a batch (its last solve ran in one): lio_est_build_local_map
+ * first. */
 int lio_est_eval_lidar_moments(lio_est *, int n_passes, const double *Rt, double *out, int *path_out_or_null);
 
 /* What stage 6 of lio_est_batch_stage_digest stands for, as numbers — the normal-equation moments of window `window` at the point its

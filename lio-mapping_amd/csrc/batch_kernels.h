@@ -37,20 +37,16 @@ struct BwVoxOut { int count; VoxParams params; int range_overflow; };
 // the K-NN grid of a window (host-computed from the filter's bounds, uploaded before the cell build)
 struct BatchGrid { GridDesc g; int cell_off; int n_filtered; };
 
-// Execution choices of a batch that the results do NOT depend on (every one of them keeps the sums' orders): 0 (occupancy: -1) = by the
-// size of the launch.  They live in the batch handle (lio_est_batch_set_option); the environment variables named here only set the
-// defaults of a new batch, read once at lio_est_batch_create.
+// Execution choices of a batch that the results do NOT depend on (every one of them keeps the sums' orders): 0 = by the size of the
+// launch.  They live in the batch handle (lio_est_batch_set_option).
 struct BatchKnobs {
-  int lanes_per_query = 0;   // 1 / 2 / 4 / 8 lanes per query of the search kernels (LIO_BW_LPQ); by size: 1 from 100 k queries, 4 from 15 k, else 8
-  int occupancy = -1;        // 0 / 6 / 8 waves per SIMD of the one-lane-per-query kernels (LIO_BW_OCC); by default features 8, rounds as compiled
-  int loop_groups = 0;       // 1 .. 4 launch chains of the trust-region loop side by side (LIO_BW_GROUPS); by size: 4 from 32 windows, 2 from 256
-  int aux_threads = 0;       // 64 / 128 / 256 threads per block of the aux row (LIO_BW_AUX_THREADS); by size: 64 from 128 windows per launch
-  int aux_stream = 0;        // 1: the aux row on a side stream (LIO_BW_AUX_STREAM; measured slower)
+  int lanes_per_query = 0;   // 1 / 4 / 8 lanes per query of the search kernels; by size: 1 from 100 k queries, 4 from 15 k, else 8
+  int loop_groups = 0;       // 1 .. 4 launch chains of the trust-region loop side by side; by size: 4 from 32 windows, 2 from 256
+  int aux_threads = 0;       // 64 / 128 / 256 threads per block of the aux row; by size: 64 from 128 windows per launch
   int finish_threads = 0;    // 1 .. 8 host threads of the write-back; by size: 4 from 128 windows
   int time_kernels = 0;      // 1: HIP events around every launch of the trust-region loop's three kernels on the stream they run on (measurement
                              //    runs only: the events serialise the host's enqueue; BatchClock::kernel_ms / kernel_launches)
 };
-BatchKnobs batch_knobs_from_env();
 
 int bw_round_blocks(int M);   // search blocks of one round of a window's newest frame: 64 queries each, whatever the lanes per query
 

@@ -4,7 +4,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 
 #include "batch_kernels.h"
 #include "seg_sort.h"
@@ -365,31 +364,15 @@ __global__ void __launch_bounds__(64 * LPQ) k_bw_features(const BatchWin *__rest
                                                          uint8_t *__restrict__ valid_all, float4 *__restrict__ coef_all, float *__restrict__ score_all) {
   bw_features_body<LPQ>(win, grid, sorted_all, cells_all, valid_all, coef_all, score_all);
 }
-// the one-lane-per-query form at a fixed occupancy (the keyframe batch's k_kf_round1_w8 gained 15 % from eight waves per SIMD at 64
-// VGPRs): LIO_BW_OCC = 6 / 8 selects these for A/B runs
-#define BW_FEAT_OCC(W)                                                                                                                            \
-  __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W, W)))                                                                \
-  k_bw_features1_w##W(const BatchWin *__restrict__ win, const BatchGrid *__restrict__ grid, const float4 *__restrict__ sorted_all,                \
-                      const int *__restrict__ cells_all, uint8_t *__restrict__ valid_all, float4 *__restrict__ coef_all, float *__restrict__ score_all) { \
-    bw_features_body<1>(win, grid, sorted_all, cells_all, valid_all, coef_all, score_all);                                                        \
-  }
-BW_FEAT_OCC(6)
-BW_FEAT_OCC(8)
-// Measured at 64 / 512 windows (profiles/r5_m_occupancy.txt): features 0.747 / 5.69 ms by the compiler's choice (84 VGPRs, 5 waves),
-// 0.709 / 5.25 at 6 waves, 0.699 / 5.02 at 8 (64 VGPRs, 84 B of spills); the rounds lose at both (0.835 / 5.98 -> 0.897 / 6.72 ->
-// 1.137 / 8.68: their fit + row phase spills 176 - 240 B).  Default: features at 8, rounds as compiled; BatchKnobs::occupancy = 0 / 6 / 8 forces both.
-static int env_int(const char *name, int dflt) { const char *e = std::getenv(name); return e ? std::atoi(e) : dflt; }
-BatchKnobs batch_knobs_from_env() {
-  BatchKnobs k;
-  { const int v = env_int("LIO_BW_LPQ", 0); if (v == 1 || v == 2 || v == 4 || v == 8) k.lanes_per_query = v; }
-  { const int v = env_int("LIO_BW_OCC", -1); if (v == 0 || v == 6 || v == 8) k.occupancy = v; }
-  { const int v = env_int("LIO_BW_GROUPS", 0); if (v >= 1 && v <= 4) k.loop_groups = v; }
-  { const int v = env_int("LIO_BW_AUX_THREADS", 0); if (v == 64 || v == 128 || v == 256) k.aux_threads = v; }
-  k.aux_stream = env_int("LIO_BW_AUX_STREAM", 0) != 0 ? 1 : 0;
-  { const int v = env_int("LIO_BW_FINISH_THREADS", 0); if (v >= 1 && v <= 8) k.finish_threads = v; }
-  return k;
+// The one-lane-per-query form of the features at six waves per SIMD (the keyframe batch's k_kf_round1_w8 gained 15 % from eight
+// waves per SIMD at 64 VGPRs).  Measured at 512 windows (round 6, flat candidate lists): features 4.09 ms at 6 waves, 4.29 at 8,
+// 4.31 as compiled; the rounds lose at a fixed occupancy (4.84 ms as compiled, 6.39 at 6: their fit + row phase spills), so
+// k_bw_odom_round<1> keeps the compiler's choice (earlier numbers: profiles/r5_m_occupancy.txt).
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6, 6)))
+k_bw_features1_w6(const BatchWin *__restrict__ win, const BatchGrid *__restrict__ grid, const float4 *__restrict__ sorted_all,
+                  const int *__restrict__ cells_all, uint8_t *__restrict__ valid_all, float4 *__restrict__ coef_all, float *__restrict__ score_all) {
+  bw_features_body<1>(win, grid, sorted_all, cells_all, valid_all, coef_all, score_all);
 }
-static int bw_occ(const BatchKnobs &k, bool features) { return k.occupancy >= 0 ? k.occupancy : (features ? 6 : 0); }   // (round 6, flat candidate lists: features 4.09 ms at 6 waves, 4.29 at 8, 4.31 as compiled; rounds 4.84 as compiled, 6.39 at 6 — 512 windows)
 static int bw_lanes_per_query(const BatchKnobs &k, long long total_queries) {
   if (k.lanes_per_query) return k.lanes_per_query;
   // measured with the flat candidate lists (round 6, tools/r6 logs): one lane per query wins from ~100 k queries per launch (8 windows' newest
@@ -401,12 +384,7 @@ void launch_bw_features(const BatchWin *win, const BatchGrid *grid, int B, int m
   if (B <= 0 || max_M <= 0 || max_static <= 0) return;
   const dim3 g(cdiv(max_M, 64), max_static, B);
   switch (bw_lanes_per_query(knobs, total_queries)) {
-    case 1:
-      if (bw_occ(knobs, true) == 8) hipLaunchKernelGGL(k_bw_features1_w8, g, dim3(64), 0, s, win, grid, sorted_all, cells_all, valid_all, coef_all, score_all);
-      else if (bw_occ(knobs, true) == 6) hipLaunchKernelGGL(k_bw_features1_w6, g, dim3(64), 0, s, win, grid, sorted_all, cells_all, valid_all, coef_all, score_all);
-      else hipLaunchKernelGGL(k_bw_features<1>, g, dim3(64), 0, s, win, grid, sorted_all, cells_all, valid_all, coef_all, score_all);
-      break;
-    case 2: hipLaunchKernelGGL(k_bw_features<2>, g, dim3(128), 0, s, win, grid, sorted_all, cells_all, valid_all, coef_all, score_all); break;
+    case 1: hipLaunchKernelGGL(k_bw_features1_w6, g, dim3(64), 0, s, win, grid, sorted_all, cells_all, valid_all, coef_all, score_all); break;
     case 4: hipLaunchKernelGGL(k_bw_features<4>, g, dim3(256), 0, s, win, grid, sorted_all, cells_all, valid_all, coef_all, score_all); break;
     default: hipLaunchKernelGGL(k_bw_features<8>, g, dim3(512), 0, s, win, grid, sorted_all, cells_all, valid_all, coef_all, score_all); break;
   }
@@ -447,15 +425,6 @@ __global__ void __launch_bounds__(64 * LPQ) k_bw_odom_round(const BatchWin *__re
                                                            double *__restrict__ partials, int round) {
   bw_odom_round_body<LPQ>(win, grid, odom, sorted_all, cells_all, valid_all, coef_all, score_all, partials, round);
 }
-#define BW_ROUND_OCC(W)                                                                                                                           \
-  __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(W, W)))                                                                \
-  k_bw_odom_round1_w##W(const BatchWin *__restrict__ win, const BatchGrid *__restrict__ grid, const OdomState *__restrict__ odom,                 \
-                        const float4 *__restrict__ sorted_all, const int *__restrict__ cells_all, uint8_t *__restrict__ valid_all,                \
-                        float4 *__restrict__ coef_all, float *__restrict__ score_all, double *__restrict__ partials, int round) {                 \
-    bw_odom_round_body<1>(win, grid, odom, sorted_all, cells_all, valid_all, coef_all, score_all, partials, round);                               \
-  }
-BW_ROUND_OCC(6)
-BW_ROUND_OCC(8)
 __global__ void __launch_bounds__(1024) k_bw_odom_update(const BatchWin *__restrict__ win, OdomState *__restrict__ odom, const double *__restrict__ partials,
                                                         int round, int *__restrict__ n_converged) {
   const int w = blockIdx.x;
@@ -471,12 +440,7 @@ void launch_bw_odom_round(const BatchWin *win, const BatchGrid *grid, int B, int
   if (B <= 0 || max_nb <= 0) return;
   const dim3 g(max_nb, B);
   switch (bw_lanes_per_query(knobs, total_queries)) {
-    case 1:
-      if (bw_occ(knobs, false) == 8) hipLaunchKernelGGL(k_bw_odom_round1_w8, g, dim3(64), 0, s, win, grid, odom, sorted_all, cells_all, valid_all, coef_all, score_all, partials, round);
-      else if (bw_occ(knobs, false) == 6) hipLaunchKernelGGL(k_bw_odom_round1_w6, g, dim3(64), 0, s, win, grid, odom, sorted_all, cells_all, valid_all, coef_all, score_all, partials, round);
-      else hipLaunchKernelGGL(k_bw_odom_round<1>, g, dim3(64), 0, s, win, grid, odom, sorted_all, cells_all, valid_all, coef_all, score_all, partials, round);
-      break;
-    case 2: hipLaunchKernelGGL(k_bw_odom_round<2>, g, dim3(128), 0, s, win, grid, odom, sorted_all, cells_all, valid_all, coef_all, score_all, partials, round); break;
+    case 1: hipLaunchKernelGGL(k_bw_odom_round<1>, g, dim3(64), 0, s, win, grid, odom, sorted_all, cells_all, valid_all, coef_all, score_all, partials, round); break;
     case 4: hipLaunchKernelGGL(k_bw_odom_round<4>, g, dim3(256), 0, s, win, grid, odom, sorted_all, cells_all, valid_all, coef_all, score_all, partials, round); break;
     default: hipLaunchKernelGGL(k_bw_odom_round<8>, g, dim3(512), 0, s, win, grid, odom, sorted_all, cells_all, valid_all, coef_all, score_all, partials, round); break;
   }

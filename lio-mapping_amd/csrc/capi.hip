@@ -698,7 +698,6 @@ lio_est *lio_est_create(const lio_est_config *c) {
   e.device_solve = c->device_solve != 0; e.inline_marg = c->inline_marg != 0;
   for (const char *name : {"LIO_DEVICE_SOLVE", "LIO_DEVICE_MARG"}) if (const char *v = std::getenv(name)) { if (std::atoi(v) != 0) e.device_solve = true; else if (std::string(name) == "LIO_DEVICE_SOLVE") e.device_solve = false; }
   e.stream_sync = c->stream_sync != 0;
-  e.moments_form = (c->moments_form == 1 || c->moments_form == 2) ? c->moments_form : 0;
   e.resident_moments = (c->resident_moments >= 1 && c->resident_moments <= 3) ? c->resident_moments : 0;
   // Estimator.cc:189-194: the estimator's filter sizes and thresholds configure its PointMapping base (created on first use)
   h->map_cfg.corner_filter_size = c->corner_filter_size; h->map_cfg.surf_filter_size = c->surf_filter_size;
@@ -988,8 +987,7 @@ int lio_est_solve_restored(lio_est *h, int steps, lio_solve_report *rep) {
 static void batch_build_parts(lio_est_batch *h) {
   h->b.reset(); h->b2.reset();   // (a part's destructor brings its device-resident priors back to the host objects)
   const int n = int(h->members.size());
-  static const int env_parts = [] { const char *e = std::getenv("LIO_BW_PARTS"); const int v = e ? std::atoi(e) : 0; return (v == 1 || v == 2) ? v : 0; }();
-  const int want = h->parts_opt ? h->parts_opt : (env_parts ? env_parts : (n >= kBatchSplitFrom ? 2 : 1));
+  const int want = h->parts_opt ? h->parts_opt : (n >= kBatchSplitFrom ? 2 : 1);
   const int parts = (want == 2 && n >= 2) ? 2 : 1;
   h->n1 = parts == 2 ? (n + 1) / 2 : n;
   std::vector<Estimator *> es;

@@ -864,17 +864,14 @@ __global__ void __launch_bounds__(128) k_kf_round(const KfDesc *__restrict__ kd,
                                                  int mapping_mode, uint8_t *__restrict__ valid, float4 *__restrict__ coef) {
   kf_round_body<LPQ>(kd, md, st, stack_all, order, min_match_sq_dis, min_plane_dis, mapping_mode, valid, coef);
 }
-#define KF_OCC_VARIANT(W)                                                                                                                      \
-  __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(W, W)))                                                            \
-  k_kf_round1_w##W(const KfDesc *__restrict__ kd, const KfMapDesc *__restrict__ md, const OdomState *__restrict__ st,                          \
-                   const float4 *__restrict__ stack_all, const uint32_t *__restrict__ order, float min_match_sq_dis, float min_plane_dis,      \
-                   int mapping_mode, uint8_t *__restrict__ valid, float4 *__restrict__ coef) {                                                 \
-    kf_round_body<1>(kd, md, st, stack_all, order, min_match_sq_dis, min_plane_dis, mapping_mode, valid, coef);                                \
-  }
 // the one-lane-per-query form is bound by gather latency: 8 waves per SIMD (64 VGPRs, the fit phase spills a little) beats
 // the 5 waves the default allocation gives by 15% (54.4 -> 46.1 ms at 1000 HDL-64 keyframes)
-KF_OCC_VARIANT(8)
-KF_OCC_VARIANT(6)
+__global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(8, 8)))
+k_kf_round1_w8(const KfDesc *__restrict__ kd, const KfMapDesc *__restrict__ md, const OdomState *__restrict__ st,
+               const float4 *__restrict__ stack_all, const uint32_t *__restrict__ order, float min_match_sq_dis, float min_plane_dis,
+               int mapping_mode, uint8_t *__restrict__ valid, float4 *__restrict__ coef) {
+  kf_round_body<1>(kd, md, st, stack_all, order, min_match_sq_dis, min_plane_dis, mapping_mode, valid, coef);
+}
 
 __global__ void __launch_bounds__(ODOM_ROW_THREADS) k_kf_rows(const KfDesc *__restrict__ kd, const OdomState *__restrict__ st,
                                                               const float4 *__restrict__ stack_all, const uint8_t *__restrict__ valid,
@@ -931,17 +928,12 @@ void launch_kf_round(const KfDesc *kd, const KfMapDesc *md, const OdomState *st,
   // lanes per query: a small batch is latency-bound (8 lanes shorten each query's dependent candidate walk); once the batch
   // fills the GPU many times over, one lane per query wins 1.8x (no merge rounds, no idle lanes in the fit): measured
   // 96 / 69 / 59 / 55 ms for 8 / 4 / 2 / 1 lanes at 1000 HDL-64 keyframes.  The result does not depend on the split.
-  static const int lpq_env = [] { const char *e = std::getenv("LIO_KF_LPQ"); return e ? std::atoi(e) : 0; }();
-  const int lpq = lpq_env ? lpq_env : (total_queries >= 250000 ? 1 : total_queries >= 60000 ? 4 : 8);   // (round 6, flat candidate lists: 16 keyframes = 377 k queries 0.89 ms at one lane against 0.96 at four; 8 keyframes 0.62 against 0.55)
+  const int lpq = total_queries >= 250000 ? 1 : total_queries >= 60000 ? 4 : 8;   // (round 6, flat candidate lists: 16 keyframes = 377 k queries 0.89 ms at one lane against 0.96 at four; 8 keyframes 0.62 against 0.55)
   const int bx = std::max(1, cdiv((long long)std::max(max_Mc, max_Ms) * lpq, 128));
   const dim3 grid(bx, 2, n_keyframes);
-#define KF_ROUND(L) hipLaunchKernelGGL(k_kf_round<L>, grid, dim3(128), 0, s, kd, md, st, stack_all, order, min_match_sq_dis, min_plane_dis, mapping_mode, valid, coef)
-  static const int occ_env = [] { const char *e = std::getenv("LIO_KF_OCC"); return e ? std::atoi(e) : 8; }();   // A/B: 0 as compiled, 6, 8 waves per SIMD
-  if (lpq == 1 && occ_env == 8) hipLaunchKernelGGL(k_kf_round1_w8, grid, dim3(128), 0, s, kd, md, st, stack_all, order, min_match_sq_dis, min_plane_dis, mapping_mode, valid, coef);
-  else if (lpq == 1 && occ_env == 6) hipLaunchKernelGGL(k_kf_round1_w6, grid, dim3(128), 0, s, kd, md, st, stack_all, order, min_match_sq_dis, min_plane_dis, mapping_mode, valid, coef);
-  else if (lpq == 1) KF_ROUND(1);
-  else if (lpq == 2) KF_ROUND(2); else if (lpq == 4) KF_ROUND(4); else KF_ROUND(8);
-#undef KF_ROUND
+  if (lpq == 1) hipLaunchKernelGGL(k_kf_round1_w8, grid, dim3(128), 0, s, kd, md, st, stack_all, order, min_match_sq_dis, min_plane_dis, mapping_mode, valid, coef);
+  else if (lpq == 4) hipLaunchKernelGGL(k_kf_round<4>, grid, dim3(128), 0, s, kd, md, st, stack_all, order, min_match_sq_dis, min_plane_dis, mapping_mode, valid, coef);
+  else hipLaunchKernelGGL(k_kf_round<8>, grid, dim3(128), 0, s, kd, md, st, stack_all, order, min_match_sq_dis, min_plane_dis, mapping_mode, valid, coef);
   LIO_HIP(hipGetLastError());
 }
 void launch_kf_rows(const KfDesc *kd, const OdomState *st, int n_keyframes, int max_nb, const float4 *stack_all, const uint8_t *valid, const float4 *coef,

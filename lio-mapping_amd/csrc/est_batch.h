@@ -65,7 +65,7 @@ class EstimatorBatch {
   // lio_est_get_features of a member whose last Solve() ran on the device: its feature slots live in the batch's arrays
   size_t GetFeatures(int w, int frame, double *pt, double *co, double *sc);
   hipStream_t stream() const { return stream_; }
-  // execution choices (batch_kernels.h: BatchKnobs) by name: lanes_per_query, occupancy, loop_groups, aux_threads, aux_stream, finish_threads;
+  // execution choices (batch_kernels.h: BatchKnobs) by name: lanes_per_query, loop_groups, aux_threads, finish_threads, time_kernels;
   // false: unknown name or a value the knob does not take
   bool SetOption(const char *name, int value);
   const BatchKnobs &knobs() const { return knobs_; }
@@ -95,10 +95,8 @@ class EstimatorBatch {
   // marginalization runs on a stream of its own behind the loop and is joined before the next solve's problems go up: it
   // overlaps the next solve's filter, features and rounds.
   static constexpr int kGroups = 4;
-  // (LIO_BW_AUX_STREAM=1, an experiment kept for re-measurement: the aux row of an iteration on a side stream beside the moments pass.)
-  hipStream_t stream_grp_[kGroups] = {}, stream_aux_[kGroups] = {}, stream_marg_ = nullptr;
-  hipEvent_t ev_fork_ = nullptr, ev_grp_[kGroups] = {}, ev_aux_[kGroups] = {},
-             ev_step_[kGroups] = {}, ev_marg_ = nullptr;
+  hipStream_t stream_grp_[kGroups] = {}, stream_marg_ = nullptr;
+  hipEvent_t ev_fork_ = nullptr, ev_grp_[kGroups] = {}, ev_marg_ = nullptr;
   bool marg_in_flight_ = false;
   BatchKnobs knobs_;
   std::vector<char> ok_;

@@ -16,7 +16,7 @@ static double bnow_ms() { return std::chrono::duration<double, std::milli>(std::
 static int round_up(int v, int m) { return (v + m - 1) / m * m; }
 template <typename T> static void pinned(T *&p, size_t n) { LIO_HIP(hipHostMalloc(reinterpret_cast<void **>(&p), sizeof(T) * std::max<size_t>(n, 1))); std::memset(static_cast<void *>(p), 0, sizeof(T) * std::max<size_t>(n, 1)); }
 
-EstimatorBatch::EstimatorBatch(const std::vector<Estimator *> &members) : m_(members), knobs_(batch_knobs_from_env()) {
+EstimatorBatch::EstimatorBatch(const std::vector<Estimator *> &members) : m_(members) {
   if (m_.empty()) throw std::runtime_error("EstimatorBatch: no windows");
   for (Estimator *e : m_) if (!e) throw std::runtime_error("EstimatorBatch: null window");
   const size_t B = m_.size();
@@ -27,18 +27,16 @@ EstimatorBatch::EstimatorBatch(const std::vector<Estimator *> &members) : m_(mem
   LIO_HIP(hipSetDevice(device_id_));
   prepare_bw_step_kernel();
   prepare_bw_marg_kernel();
+  prepare_seg_sort_kernels();
   ok_.assign(B, 0);
   LIO_HIP(hipStreamCreate(&stream_));
   for (hipEvent_t &e : ev_) LIO_HIP(hipEventCreate(&e));
   for (hipEvent_t &e : ev_wait_) LIO_HIP(hipEventCreate(&e));
   for (hipStream_t &g : stream_grp_) LIO_HIP(hipStreamCreate(&g));
-  for (hipStream_t &g : stream_aux_) LIO_HIP(hipStreamCreate(&g));
   LIO_HIP(hipStreamCreate(&stream_marg_));
   LIO_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
   LIO_HIP(hipEventCreateWithFlags(&ev_marg_, hipEventDisableTiming));
   for (hipEvent_t &e : ev_grp_) LIO_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (hipEvent_t &e : ev_aux_) LIO_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (hipEvent_t &e : ev_step_) LIO_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   win_.resize(B);
   for (size_t w = 0; w < B; ++w) { win_[w].e = m_[w]; m_[w]->AdoptStream(stream_); }
   pinned(h_win_, B); pinned(h_grid_, B); pinned(h_vout_, B); pinned(h_odom_, B); pinned(h_bs_, B); pinned(h_pb_, B); pinned(h_st_, B); pinned(h_mg_, B);
@@ -82,12 +80,9 @@ EstimatorBatch::~EstimatorBatch() {
   for (hipEvent_t e : ev_wait_) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ev_k_) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ev_grp_) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : ev_aux_) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : ev_step_) if (e) (void)hipEventDestroy(e);
   if (ev_fork_) (void)hipEventDestroy(ev_fork_);
   if (ev_marg_) (void)hipEventDestroy(ev_marg_);
   for (hipStream_t g : stream_grp_) if (g) (void)hipStreamDestroy(g);
-  for (hipStream_t g : stream_aux_) if (g) (void)hipStreamDestroy(g);
   if (stream_marg_) (void)hipStreamDestroy(stream_marg_);
   if (stream_) (void)hipStreamDestroy(stream_);
 }
@@ -95,11 +90,9 @@ EstimatorBatch::~EstimatorBatch() {
 bool EstimatorBatch::SetOption(const char *name, int v) {
   if (!name) return false;
   const std::string n(name);
-  if (n == "lanes_per_query") { if (v != 0 && v != 1 && v != 2 && v != 4 && v != 8) return false; knobs_.lanes_per_query = v; }
-  else if (n == "occupancy") { if (v != -1 && v != 0 && v != 6 && v != 8) return false; knobs_.occupancy = v; }
+  if (n == "lanes_per_query") { if (v != 0 && v != 1 && v != 4 && v != 8) return false; knobs_.lanes_per_query = v; }
   else if (n == "loop_groups") { if (v < 0 || v > kGroups) return false; knobs_.loop_groups = v; }
   else if (n == "aux_threads") { if (v != 0 && v != 64 && v != 128 && v != 256) return false; knobs_.aux_threads = v; }
-  else if (n == "aux_stream") { if (v != 0 && v != 1) return false; knobs_.aux_stream = v; }
   else if (n == "finish_threads") { if (v < 0 || v > 8) return false; knobs_.finish_threads = v; }
   else if (n == "time_kernels") { if (v != 0 && v != 1) return false; knobs_.time_kernels = v; }
   else return false;
@@ -552,22 +545,19 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
     // 1.86 / 1.84 / 1.78 / 1.79, 64: 2.51 / 2.10 / 2.08 / 2.15, 128: 3.46 / 3.23 / 2.77 / 3.21 (four chains = four hardware queues), 256: 5.60 /
     // 5.05 / 5.28 / 5.04, 512: 10.3 / 9.6 / 9.6 / 9.6.
     const int G = knobs_.loop_groups ? std::min(knobs_.loop_groups, B) : (B >= 32 ? (B < 256 ? 4 : 2) : 1);
-    // knobs_.aux_stream: the aux row on a side stream beside the moments.  Measured slower on the MI355X (two events per iteration cost
-    // more than the 41 us they hide: loop 2.92 ms against 2.68 at 64 windows, profiles/r5_e_aux_stream_ab_and_step_phases.txt): off.
     const BatchBases bases{slab_.p, partials_.p, d_st_.p, d_pb_.p, d_mg_.p};
-    const bool side_aux = knobs_.aux_stream != 0;
     static const int prof_it = [] { const char *e = std::getenv("LIO_DEBUG_TIMING_IT"); return e ? std::atoi(e) : 3; }();
-    if (G > 1 || side_aux) LIO_HIP(hipEventRecord(ev_fork_, s));
+    if (G > 1) LIO_HIP(hipEventRecord(ev_fork_, s));
     // The groups' chains are enqueued INTERLEAVED, iteration by iteration: a group's chain is 3 x (max_iterations + 1) launches, ~130 us of
     // host enqueue time — enqueued one whole chain after the other, group g started that much behind group g - 1 and the loop ended that
     // much later (at 64 windows the loop is one chain's latency, not throughput).
-    struct Grp { int w0, w1, bpf, wo, npad, it, n; hipStream_t sg, sa; };
+    struct Grp { int w0, w1, bpf, wo, npad, it, n; hipStream_t sg; };
     Grp grp[kGroups];
     int it_max = 0;
     for (int g = 0; g < G; ++g) {
       Grp &q = grp[g];
       q.w0 = int((long long)B * g / G); q.w1 = int((long long)B * (g + 1) / G);
-      q.sg = G > 1 ? stream_grp_[g] : s; q.sa = stream_aux_[g];
+      q.sg = G > 1 ? stream_grp_[g] : s;
       if (G > 1) LIO_HIP(hipStreamWaitEvent(q.sg, ev_fork_, 0));
       q.bpf = 1; q.wo = 1; q.npad = DS_NB; q.it = 0; q.n = 0;
       for (int w = q.w0; w < q.w1; ++w) {
@@ -582,18 +572,10 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
       for (int g = 0; g < G; ++g) {
         const Grp &q = grp[g];
         if (q.n == 0 || k > q.it) continue;
-        const int w0 = q.w0, w1 = q.w1, g_bpf = q.bpf, g_wo = q.wo, g_npad = q.npad, g_it = q.it;
-        hipStream_t sg = q.sg, sa = q.sa;
+        const int w0 = q.w0, w1 = q.w1, g_bpf = q.bpf, g_wo = q.wo, g_npad = q.npad;
+        hipStream_t sg = q.sg;
         const BatchSolve *gb = d_bs_.p + w0;
-        if (side_aux) {   // aux row beside the moments; the step kernel joins the two
-          LIO_HIP(hipStreamWaitEvent(sa, k == 0 ? ev_fork_ : ev_step_[g], 0));
-          launch_bw_aux(gb, bases, w1 - w0, g_wo, knobs_.aux_threads, sa);
-          LIO_HIP(hipEventRecord(ev_aux_[g], sa));
-          launch_bw_moments(gb, bases, w1 - w0, g_bpf, g_wo, valid_all_.p, coef_all_.p, sg);
-          LIO_HIP(hipStreamWaitEvent(sg, ev_aux_[g], 0));
-          launch_bw_step(gb, bases, w1 - w0, g_wo, g_npad, sg);
-          if (k < g_it) LIO_HIP(hipEventRecord(ev_step_[g], sg));
-        } else if (knobs_.time_kernels) {   // measurement run: the three launches bracketed by events on their stream
+        if (knobs_.time_kernels) {   // measurement run: the three launches bracketed by events on their stream
           while (ev_k_.size() < size_t(ev_k_used_ + 4)) { hipEvent_t e = nullptr; LIO_HIP(hipEventCreate(&e)); ev_k_.push_back(e); }
           hipEvent_t *ek = ev_k_.data() + ev_k_used_;
           ev_k_used_ += 4;

@@ -36,7 +36,7 @@ struct EstConfig {
   int init_window_factor = 3;
   // execution switches (lio_est_config's trailing block; environment overrides are applied in the constructor)
   bool device_solve = false, inline_marg = false, stream_sync = false;
-  int moments_form = 0, resident_moments = 0;
+  int resident_moments = 0;
 };
 
 struct DeviceCloud {
@@ -199,7 +199,7 @@ class Estimator {
   // lio_est_eval_lidar_moments: the lidar moments of frames pivot+1 .. pivot+Wo at caller-given T_{pivot<-i} (Rt: n_passes x Wo x 12,
   // R row-major then t), every pass inside ONE solve scope through the path the estimator is configured for; out: n_passes x Wo x 258
   // (S 16 x 16 row-major, cost, count).  A sharded estimator returns its own share (no all-reduce).  Returns the path of the last pass:
-  // 0 MFMA launch pair, 1 VALU launch pair, 2 resident kernel.
+  // 0 MFMA launch pair, 2 resident kernel.
   int EvalLidarMoments(int n_passes, const double *Rt, double *out);
   void Snapshot();
   bool Restore();
@@ -296,7 +296,6 @@ class Estimator {
   DBuf<float> d_transforms_;
   DBuf<OdomState> d_odom_;
   DBuf<double> d_odom_partials_, d_moment_partials_, d_moment_out_;
-  int moments_form_ = 0;            // 0 by launch size, 1 MFMA, 2 VALU
   // Resident moments (solve_kernels.h): one launch per solve; every linearisation is a doorbell write + a spin on
   // the blocks' completion words.  Begun lazily by the first LidarLaunch of a SolveOptimization, stopped when it returns.
   bool resident_moments_ = true;    // configured (lio_est_config.resident_moments / LIO_RESIDENT_MOMENTS)

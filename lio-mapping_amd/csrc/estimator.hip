@@ -90,10 +90,9 @@ Estimator::Estimator(const EstConfig &cfg) : cfg_(cfg), W_(cfg.W), Wo_(cfg.Wo) {
   LIO_HIP(hipDeviceSynchronize());   // the memsets above run on the null stream; the kernels that read them on streams of our own
   // Execution switches: lio_est_config's trailing block, each overridable by its environment variable (A/B runs of a built host).
   async_marg_ = !cfg.inline_marg;
-  host_signal_ = !cfg.stream_sync; moments_form_ = cfg.moments_form;
+  host_signal_ = !cfg.stream_sync;
   resident_moments_ = cfg.resident_moments != 2;
   resident_never_ = cfg.resident_moments == 3;
-  if (const char *e = std::getenv("LIO_MOMENTS")) moments_form_ = std::string(e) == "mfma" ? 1 : (std::string(e) == "valu" ? 2 : moments_form_);
   if (const char *e = std::getenv("LIO_RESIDENT_MOMENTS")) resident_moments_ = std::atoi(e) != 0;
   d_res_relay_.reserve(size_t(LIO_MAX_FRAMES) * LIO_RES_DOOR);
   LIO_HIP(hipMemset(d_res_relay_.p, 0, sizeof(double) * LIO_MAX_FRAMES * LIO_RES_DOOR));
@@ -221,13 +220,12 @@ static std::atomic<uint64_t> g_content_id{1};
 // a process that drives many windows admits only as many as fit (four moments kernels of ~100 blocks);
 // a solve that is not admitted takes the launch path, with the same results.
 static std::atomic<int> g_resident_moments{0};
+static const int kMaxResidentMoments = 4;
 // Solves in flight in this process.  A resident moments kernel holds ~100 CUs' worth of registers while it waits for the host,
 // which is free when the GPU has nothing else to do and expensive when other windows' feature kernels want those CUs: measured
 // on the MI355X with four windows solving on four host threads, 3290 solves/s with every solve resident, 3530 with one at a time,
 // 4230 with none (launch pairs).  So a solve takes the resident form only while it is the ONLY solve in flight.
 static std::atomic<int> g_active_solves{0};
-// (process-wide, hence an environment knob and not a lio_est_config field; 0 = every solve takes the launch path)
-static const int kMaxResidentMoments = [] { const char *e = std::getenv("LIO_MAX_RESIDENT_MOMENTS"); return e ? std::max(0, std::atoi(e)) : 4; }();
 
 void Estimator::SetSurfStack(int frame, const float *xyzi, size_t n) {
   DeviceCloud &c = stacks_[frame];
@@ -684,12 +682,11 @@ void Estimator::FillMomentArgs(MomentArgs &ma, int &max_slots) const {
     max_slots = std::max(max_slots, f.nslots);
   }
   ma.blocks_per_frame = moment_blocks_per_frame(max_slots);
-  ma.form = moments_form_;
   // With the resident form configured, BOTH paths use its partition (blocks per frame so that a lane holds <= per_lane
   // 64-slot chunks per wave, fp64-MFMA form): the launch path — taken when a pass cannot use the resident kernel (kernel timing, factor
   // sharding, stream_sync) — then yields bit-identical moments.
   const int rb = ResidentBpf(max_slots, ma.nframes);
-  if (rb > 0) { ma.blocks_per_frame = rb; ma.form = 1; }
+  if (rb > 0) ma.blocks_per_frame = rb;
 }
 
 // Blocks per frame of the resident form's partition (0: the window does not fit) and, in *per_lane, the residuals a lane keeps.
@@ -699,7 +696,7 @@ void Estimator::FillMomentArgs(MomentArgs &ma, int &max_slots) const {
 // counts, so the partition — and with it every bit of the result — does not depend on how a pass is executed.
 int Estimator::ResidentBpf(int max_slots, int nframes, int *per_lane) const {
   if (per_lane) *per_lane = 0;
-  if (!resident_moments_ || moments_form_ == 2) return 0;
+  if (!resident_moments_) return 0;
   for (int r : {1, 2, 4, 8}) {
     if (res_per_lane_ > 0 && r != res_per_lane_) continue;
     const int b = resident_blocks_per_frame(max_slots, nframes, r);
@@ -923,7 +920,7 @@ int Estimator::EvalLidarMoments(int n_passes, const double *Rt, double *out) {
       for (int k = 0; k < 3; ++k) ma.fr[f].t[k] = src[9 + k];
     }
     LidarLaunchMoments(ma, false);
-    path = res_active_ ? 2 : (ma.form == 2 ? 1 : 0);
+    path = res_active_ ? 2 : 0;
     LidarWait(m, false);
     for (int f = 0; f < Wo_; ++f) {
       double *dst = out + (size_t(p) * Wo_ + f) * 258;
@@ -971,9 +968,9 @@ bool Estimator::BenchBatchedMoments(int B, int reps, double *avg_ms, double *byt
   LIO_HIP(hipMemcpyAsync(d_frames.p, frames.data(), sizeof(MomentFrame) * nf, hipMemcpyHostToDevice, stream_));
   hipEvent_t e0, e1;
   LIO_HIP(hipEventCreate(&e0)); LIO_HIP(hipEventCreate(&e1));
-  for (int w = 0; w < 2; ++w) launch_lidar_moments_batched(d_frames.p, nf, bpf, max_slots, valid_b.p, coef_b.p, partials.p, out.p, stream_, moments_form_);
+  for (int w = 0; w < 2; ++w) launch_lidar_moments_batched(d_frames.p, nf, bpf, valid_b.p, coef_b.p, partials.p, out.p, stream_);
   LIO_HIP(hipEventRecord(e0, stream_));
-  for (int r = 0; r < reps; ++r) launch_lidar_moments_batched(d_frames.p, nf, bpf, max_slots, valid_b.p, coef_b.p, partials.p, out.p, stream_, moments_form_);
+  for (int r = 0; r < reps; ++r) launch_lidar_moments_batched(d_frames.p, nf, bpf, valid_b.p, coef_b.p, partials.p, out.p, stream_);
   LIO_HIP(hipEventRecord(e1, stream_));
   LIO_HIP(hipStreamSynchronize(stream_));
   float ms = 0;

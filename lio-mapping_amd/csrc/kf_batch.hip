@@ -12,6 +12,7 @@ namespace lio {
 static const int kChunk = 32768;  // keyframes per launch (grid y/z limit 65535)
 
 KfBatchDev::KfBatchDev(const lio_map_config &cfg) : cfg_(cfg) {
+  prepare_seg_sort_kernels();   // (this batch's device: the current one, where its stream goes too)
   LIO_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
   LIO_HIP(hipEventCreate(&ev0_));
   LIO_HIP(hipEventCreate(&ev1_));

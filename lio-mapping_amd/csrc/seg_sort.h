@@ -34,12 +34,15 @@ struct SegDesc {
 struct KeyLayout { int mx, my, mz; int bx, by; int bits; };   // mins in the stored key's offset space; shifts; total bits (> 27: not sortable in three 9-bit passes)
 
 struct SegSortPlan {
-  int threads;          // 256, 512 (or 1024) per block: tile = threads * SS_ITEMS
+  int threads;          // 256 or 512 per block: tile = threads * SS_ITEMS
   int max_tiles;        // tiles of the largest segment
   size_t hist_entries;  // total (digit, tile) entries of one pass: sum over segments of tiles << bits
 };
 // tile size by the size of the launch; fills desc[k].hist_off.  sizes[k] = elements of segment k.
 SegSortPlan seg_sort_plan(SegDesc *desc, int nseg, int bits_per_pass);
+
+// per device, before the first seg_sort_pass on it (the current device)
+void prepare_seg_sort_kernels();
 
 // One pass on digit [shift, shift + bits) of the keys.  layout != nullptr: mode 1 (per-segment layouts, device array); vals_in == nullptr:
 // the values are the elements' own positions in the array (first pass).  hist: plan.hist_entries uint32 of scratch.

@@ -29,7 +29,6 @@ struct MomentArgs {
   MomentFrame fr[LIO_MAX_FRAMES];
   int nframes;
   int blocks_per_frame;
-  int form;   // 0: MFMA or VALU form by chunks per wave, 1: MFMA, 2: VALU (lio_est_config.moments_form)
 };
 
 // partials: nframes * blocks_per_frame * LIO_MOMENT_OUT doubles; out: nframes * LIO_MOMENT_OUT doubles (k_moment_reduce folds them)
@@ -74,8 +73,8 @@ int resident_blocks_per_frame(int max_slots, int nframes, int per_lane);
 void launch_lidar_moments_resident(const MomentArgs &a, const ResidentArgs &ra, int per_lane, const uint8_t *valid, const float4 *coef, hipStream_t s);
 int moment_blocks_per_frame_batched(int max_slots, int nframes);
 // same pass over `nframes` frame descriptors held in device memory (any number of windows in one launch)
-void launch_lidar_moments_batched(const MomentFrame *d_frames, int nframes, int blocks_per_frame, int max_slots, const uint8_t *valid,
-                                  const float4 *coef, double *partials, double *out, hipStream_t s, int form = 0);
+void launch_lidar_moments_batched(const MomentFrame *d_frames, int nframes, int blocks_per_frame, const uint8_t *valid,
+                                  const float4 *coef, double *partials, double *out, hipStream_t s);
 
 // One iteration of the device-resident dogleg (solve_step.h) for every window of a batch: launch A (moments at the candidate + aux
 // row) and launch B (one workgroup per window), both on `s`, no host interaction.  BatchSolve is declared in solve_step.h.

@@ -22,16 +22,6 @@ namespace lio {
 
 #define MOMENT_THREADS 256
 
-// Two kernels compute the same moments: the fp64-MFMA form (default) and a structured fp64-VALU form (73 sums per lane,
-// lio_est_config.moments_form = 2 / LIO_MOMENTS=valu).  Measured on the MI355X (tools/batched_moments.py, B windows of the bench
-// workload in one launch): round 2 chose the VALU form from four chunks per wave on (4.5 vs 3.4 TB/s algorithmic at B = 512) because
-// the MFMA kernel paid the HBM latency once per chunk; with its loads issued three chunks ahead and four blocks per CU the MFMA form
-// is level at B = 64 (3.57 vs 3.70 TB/s) and ahead at B = 512 (4.01 vs 3.82), so it is used at every size.
-static bool use_mfma(int max_slots, int blocks_per_frame, int form) {
-  (void)max_slots; (void)blocks_per_frame;
-  return form != 2;
-}
-
 int moment_blocks_per_frame(int max_slots) {
   // one residual per lane, 256 residuals per block-iteration; aim for ~2 iterations per block
   int b = cdiv(max_slots, 256 * 2);
@@ -158,132 +148,7 @@ __device__ __forceinline__ void lidar_moments_body(const MomentFrame &fr, const 
 }
 
 // ------------------------------------------------------------------------------------------------
-// Structured form of the same moments, on the fp64 vector units.  z z^T has only 73 distinct entries:
-//   z = sw [w (x) ph ; d],  ph = (p, 1)   =>   S[(a,i),(b,j)] = (s_a s_b)(ph_i ph_j): 6 pairs (a<=b) x 10 pairs (i<=j) = 60,
-//   S[(a,i),12] = s_a (ph_i dd): 12,  S[12,12] = dd^2: 1.
-// Every lane keeps the 73 sums of ITS residuals in registers (73 FMAs per residual instead of the 16 MFMAs = 512 flop per
-// residual of the padded 16x16 product) and the block folds them once at the end through LDS.  Measured on gfx950 the fp64
-// MFMA does not overlap fp64 VALU work (both ~78.6 TF peak, and the pipelined MFMA kernel tops out at a third of it), so the
-// 3.5x fewer flops win whenever a wave has more than a couple of chunks.
-#define LIO_NACC 73
-#define RED_ROW (16 * 17 + 1)
-
-// one residual into the 73 per-lane sums (shared by the launch form and the resident form: identical arithmetic)
-__device__ __forceinline__ void sym_accumulate(const double *__restrict__ Rm, const double *__restrict__ tv, float fpx, float fpy, float fpz, float4 c, bool ok,
-                                               double (&a)[LIO_NACC], LogProduct &lp, double &cnt) {
-  const double px = fpx, py = fpy, pz = fpz;
-  const double w0 = ok ? double(c.x) : 0.0, w1 = ok ? double(c.y) : 0.0, w2 = ok ? double(c.z) : 0.0, d = ok ? double(c.w) : 0.0;
-  const double qx = Rm[0] * px + Rm[1] * py + Rm[2] * pz + tv[0];
-  const double qy = Rm[3] * px + Rm[4] * py + Rm[5] * pz + tv[1];
-  const double qz = Rm[6] * px + Rm[7] * py + Rm[8] * pz + tv[2];
-  const double r = w0 * qx + w1 * qy + w2 * qz + d;
-  const double sq = r * r;
-  const double sw = ok ? rsqrt_1p(1.0 + sq) : 0.0;
-  const double S[3] = {sw * w0, sw * w1, sw * w2};
-  const double dd = sw * d;
-  lp.mul(ok ? 1.0 + sq : 1.0);
-  cnt += ok ? 1.0 : 0.0;
-  const double P[10] = {px * px, px * py, px * pz, px, py * py, py * pz, py, pz * pz, pz, 1.0};
-  const double W[6] = {S[0] * S[0], S[0] * S[1], S[0] * S[2], S[1] * S[1], S[1] * S[2], S[2] * S[2]};
-  const double Q[4] = {px * dd, py * dd, pz * dd, dd};
-#pragma unroll
-  for (int ab = 0; ab < 6; ++ab)
-#pragma unroll
-    for (int ij = 0; ij < 10; ++ij) a[ab * 10 + ij] = __builtin_fma(W[ab], P[ij], a[ab * 10 + ij]);
-#pragma unroll
-  for (int sa = 0; sa < 3; ++sa)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) a[60 + sa * 4 + i] = __builtin_fma(S[sa], Q[i], a[60 + sa * 4 + i]);
-  a[72] = __builtin_fma(dd, dd, a[72]);
-}
-
-// block fold of the 73 per-lane sums (+ cost, count) into uniq[0..74], 16 accumulators at a time:
-// [16][16 slices of 16 threads, padded to 17] then [16][16 slices].  Ends with a barrier: uniq is readable by every thread.
-struct SymFoldLds {
-  double red[16 * RED_ROW];
-  double red2[16 * 17];
-  double uniq[LIO_NACC + 2];
-  double cw[MOMENT_THREADS / 64][2];
-};
-__device__ __forceinline__ void sym_block_fold(const double (&a)[LIO_NACC], const LogProduct &lp, double cnt, SymFoldLds &L) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int kk = tid & 15, sl = tid >> 4;
-#pragma unroll
-  for (int g = 0; g < (LIO_NACC + 15) / 16; ++g) {
-#pragma unroll
-    for (int k = 0; k < 16; ++k)
-      if (g * 16 + k < LIO_NACC) L.red[k * RED_ROW + sl * 17 + kk] = a[g * 16 + k];
-    __syncthreads();
-    double v = 0.0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) v += L.red[kk * RED_ROW + sl * 17 + j];
-    L.red2[kk * 17 + sl] = v;
-    __syncthreads();
-    if (tid < 16 && g * 16 + tid < LIO_NACC) {
-      double w = 0.0;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) w += L.red2[tid * 17 + q];
-      L.uniq[g * 16 + tid] = w;
-    }
-    __syncthreads();
-  }
-  double cost = 0.5 * lp.log_value();
-  for (int off = 32; off > 0; off >>= 1) { cost += __shfl_down(cost, off, 64); cnt += __shfl_down(cnt, off, 64); }
-  if (lane == 0) { L.cw[wv][0] = cost; L.cw[wv][1] = cnt; }
-  __syncthreads();
-  if (tid < 2) {
-    double w = 0.0;
-    for (int q = 0; q < MOMENT_THREADS / 64; ++q) w += L.cw[q][tid];
-    L.uniq[LIO_NACC + tid] = w;
-  }
-  __syncthreads();
-}
-// (row, col) of the 16x16 moment matrix -> index into the 73 sums (-1: structural zero)
-__host__ __device__ inline int sym_unique_index(int r, int cidx) {
-  if (r >= 13 || cidx >= 13) return -1;
-  if (r == 12 && cidx == 12) return 72;
-  if (r == 12 || cidx == 12) return 60 + (r == 12 ? cidx : r);
-  const int ra = r >> 2, ri = r & 3, ca = cidx >> 2, ci = cidx & 3;
-  const int a0 = ra < ca ? ra : ca, a1 = ra < ca ? ca : ra, i0 = ri < ci ? ri : ci, i1 = ri < ci ? ci : ri;
-  const int ab = a0 == 0 ? a1 : (a0 == 1 ? 2 + a1 : 5);                          // 00 01 02 11 12 22
-  const int ij = i0 == 0 ? i1 : (i0 == 1 ? 3 + i1 : (i0 == 2 ? 5 + i1 : 9));     // 00 01 02 03 11 12 13 22 23 33
-  return ab * 10 + ij;
-}
-
-__device__ __forceinline__ void lidar_moments_sym_body(const MomentFrame &fr, const uint8_t *__restrict__ valid, const float4 *__restrict__ coef,
-                                                       double *__restrict__ partials, int nblk) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int waves_total = nblk * (MOMENT_THREADS / 64);
-  const int wid = blockIdx.x * (MOMENT_THREADS / 64) + wv;
-  double a[LIO_NACC];
-#pragma unroll
-  for (int k = 0; k < LIO_NACC; ++k) a[k] = 0.0;
-  double cnt = 0.0;
-  LogProduct lp;
-  const int stride = waves_total * 64;
-  for (int base = fr.slot_begin + wid * 64; base < fr.slot_end; base += stride) {
-    const int sidx = base + lane;
-    const bool in = sidx < fr.slot_end;
-    const int si = in ? sidx : fr.slot_begin;
-    const bool ok = in && valid[fr.slot_off + si] != 0;
-    const float4 po = fr.stack[si % fr.M];
-    const float4 c = coef[fr.slot_off + si];
-    sym_accumulate(fr.R, fr.t, po.x, po.y, po.z, c, ok, a, lp, cnt);
-  }
-  __shared__ SymFoldLds L;
-  sym_block_fold(a, lp, cnt, L);
-  double *dst = partials + (size_t(blockIdx.y) * nblk + blockIdx.x) * LIO_MOMENT_OUT;
-  {
-    // expand the 73 sums into the row-major 16x16 layout the host expects (13x13 used, rest zero)
-    const int u = sym_unique_index(tid >> 4, tid & 15);
-    dst[tid] = u >= 0 ? L.uniq[u] : 0.0;
-    if (tid < 2) dst[256 + tid] = L.uniq[LIO_NACC + tid];
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Resident form: see solve_kernels.h.  Block b = frame * blocks_per_frame + j serves frame `frame` with the lane -> residual map
-// of k_lidar_moments_sym at the same blocks per frame (wave w of the frame takes slots slot_begin + 64 w + lane + it * stride).
+// Resident form: see solve_kernels.h.
 // one poll of a frame's doorbell record in HBM by lanes 0..15: returns the sequence number both cache lines agree on (NaN while
 // they differ); v keeps the lane's slot
 __device__ __forceinline__ double door_poll(const double *door, int lane, double &v) {
@@ -598,15 +463,6 @@ __global__ void __launch_bounds__(MOMENT_THREADS) k_lidar_moments_resident(Momen
   }
 }
 
-__global__ void __launch_bounds__(MOMENT_THREADS) k_lidar_moments_sym(MomentArgs a, const uint8_t *__restrict__ valid,
-                                                                      const float4 *__restrict__ coef, double *__restrict__ partials) {
-  lidar_moments_sym_body(a.fr[blockIdx.y], valid, coef, partials, gridDim.x);
-}
-__global__ void __launch_bounds__(MOMENT_THREADS) k_lidar_moments_sym_batched(const MomentFrame *__restrict__ frames, const uint8_t *__restrict__ valid,
-                                                                              const float4 *__restrict__ coef, double *__restrict__ partials) {
-  lidar_moments_sym_body(frames[blockIdx.y], valid, coef, partials, gridDim.x);
-}
-
 __global__ void __launch_bounds__(MOMENT_THREADS) k_lidar_moments(MomentArgs a, const uint8_t *__restrict__ valid,
                                                                   const float4 *__restrict__ coef, double *__restrict__ partials) {
   lidar_moments_body(a.fr[blockIdx.y], valid, coef, partials, gridDim.x);
@@ -713,8 +569,8 @@ void launch_lidar_moments_resident(const MomentArgs &a, const ResidentArgs &ra, 
 // any company): 2048 slots per block — eight 64-slot chunks per wave, enough for the chunk loop's three-deep prefetch to fill the
 // MFMA issue slots — and never more than 64 blocks per frame.
 int batch_blocks_per_frame(int max_slots) {
-  // slots per block: a function of the window's own size only (bit-identity of a window alone and in a batch); LIO_BW_SLOTS_PER_BLOCK for A/B runs
-  static const int per_block = [] { const char *e = std::getenv("LIO_BW_SLOTS_PER_BLOCK"); const int v = e ? std::atoi(e) : 0; return v >= 256 ? v : MOMENT_THREADS * 16; }();   // 4096: measured against 1024 / 2048 / 8192 / 16384 at 64 and 512 windows (profiles/r5_l_*): fewer partials for the step kernel's fold, still 640 blocks per 32 windows
+  // slots per block: a function of the window's own size only (bit-identity of a window alone and in a batch)
+  const int per_block = MOMENT_THREADS * 16;   // 4096: measured against 1024 / 2048 / 8192 / 16384 at 64 and 512 windows (profiles/r5_l_*): fewer partials for the step kernel's fold, still 640 blocks per 32 windows
   return std::max(1, std::min(cdiv(max_slots, per_block), 64));
 }
 
@@ -725,13 +581,10 @@ int moment_blocks_per_frame_batched(int max_slots, int nframes) {
   return std::max(1, std::min(want, moment_blocks_per_frame(max_slots)));
 }
 
-void launch_lidar_moments_batched(const MomentFrame *d_frames, int nframes, int blocks_per_frame, int max_slots, const uint8_t *valid,
-                                  const float4 *coef, double *partials, double *out, hipStream_t s, int form) {
+void launch_lidar_moments_batched(const MomentFrame *d_frames, int nframes, int blocks_per_frame, const uint8_t *valid,
+                                  const float4 *coef, double *partials, double *out, hipStream_t s) {
   if (nframes <= 0) return;
-  if (use_mfma(max_slots, blocks_per_frame, form))
-    hipLaunchKernelGGL(k_lidar_moments_batched, dim3(blocks_per_frame, nframes), dim3(MOMENT_THREADS), 0, s, d_frames, valid, coef, partials);
-  else
-    hipLaunchKernelGGL(k_lidar_moments_sym_batched, dim3(blocks_per_frame, nframes), dim3(MOMENT_THREADS), 0, s, d_frames, valid, coef, partials);
+  hipLaunchKernelGGL(k_lidar_moments_batched, dim3(blocks_per_frame, nframes), dim3(MOMENT_THREADS), 0, s, d_frames, valid, coef, partials);
   hipLaunchKernelGGL(k_moment_reduce, dim3(nframes, 3), dim3(REDUCE_THREADS), 0, s, partials, blocks_per_frame, out, HostSignal());
   LIO_HIP(hipGetLastError());
 }
@@ -739,12 +592,7 @@ void launch_lidar_moments_batched(const MomentFrame *d_frames, int nframes, int 
 void launch_lidar_moments(const MomentArgs &a, const uint8_t *valid, const float4 *coef, double *partials, double *out, hipStream_t s,
                           const HostSignal &sig) {
   if (a.nframes <= 0) return;
-  int max_slots = 0;
-  for (int k = 0; k < a.nframes; ++k) max_slots = std::max(max_slots, a.fr[k].slot_end - a.fr[k].slot_begin);
-  if (use_mfma(max_slots, a.blocks_per_frame, a.form))
-    hipLaunchKernelGGL(k_lidar_moments, dim3(a.blocks_per_frame, a.nframes), dim3(MOMENT_THREADS), 0, s, a, valid, coef, partials);
-  else
-    hipLaunchKernelGGL(k_lidar_moments_sym, dim3(a.blocks_per_frame, a.nframes), dim3(MOMENT_THREADS), 0, s, a, valid, coef, partials);
+  hipLaunchKernelGGL(k_lidar_moments, dim3(a.blocks_per_frame, a.nframes), dim3(MOMENT_THREADS), 0, s, a, valid, coef, partials);
   hipLaunchKernelGGL(k_moment_reduce, dim3(a.nframes, 3), dim3(REDUCE_THREADS), 0, s, partials, a.blocks_per_frame, out, sig);
   LIO_HIP(hipGetLastError());
 }

@@ -94,7 +94,6 @@ class EstConfig(C.Structure):
         ("device_solve", C.c_int),
         ("inline_marg", C.c_int),
         ("stream_sync", C.c_int),
-        ("moments_form", C.c_int),
         ("resident_moments", C.c_int),
     ]
 
@@ -958,7 +957,7 @@ class Estimator:
 
     def eval_lidar_moments(self, Rt):
         """Rt: (n_passes, Wo, 12) T_{pivot<-i} (R row-major, t) -> (moments (n_passes, Wo, 258): S 16x16 row-major, cost, count;
-        path of the last pass: 0 MFMA launch pair, 1 VALU launch pair, 2 resident kernel, -1 the oracle)"""
+        path of the last pass: 0 MFMA launch pair, 2 resident kernel, -1 the oracle)"""
         Rt = _f64(Rt)
         n_passes, wo = Rt.shape[0], Rt.shape[1]
         out = np.zeros((n_passes, wo, 258))

@@ -182,7 +182,7 @@ def make_window(lib, data, kind, keep=0, stacks=None, seed=3, build=True, **cfg_
     features built.  keep: keep_features (the newest frame then has rounds x M slots).  stacks: {frame: xyzi} replacing the
     voxel-filtered stacks of optimised frames before the map is built (slot counts of a frame = its stack's size).
     seed: of the perturbation; build: False leaves the map to a batch solve.
-    cfg_fields: further lio_est_config fields (resident_moments, moments_form, stream_sync)."""
+    cfg_fields: further lio_est_config fields (resident_moments, stream_sync)."""
     from lio_amd import capi, pipeline
 
     ds, clouds = data

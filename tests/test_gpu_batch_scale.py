@@ -4,10 +4,10 @@ built was three headline windows, and bench.py's own `all_windows_same_decisions
 Root cause found in round 6 (profiles/r6_a_determinism_diagnosis.txt): two races on the step kernel's LDS control block (solve_step.h).
 They only bit when blocks of the OTHER loop group shared a SIMD with a step workgroup — i.e. from 32 windows on, at random.
 
-* every kernel variant and host path the launch sizes select (one / two / four / eight lanes per query, the forced-occupancy forms,
-  one to three loop groups, the aux row's block sizes, the threaded write-back) is forced on a small batch through
+* every kernel variant and host path the launch sizes select (one / four / eight lanes per query, one to three loop groups, the aux
+  row's block sizes, the threaded write-back, one and two parts) is forced on a small batch through
   lio_est_batch_set_option: same bits in every stage (lio_est_batch_stage_digest), same reports, windows and priors;
-* B identical copies of BASELINE.json's headline window (HDL-64E, window 15 / opt 5) at B = 40 (k_bw_features1_w8,
+* B identical copies of BASELINE.json's headline window (HDL-64E, window 15 / opt 5) at B = 40 (k_bw_features1_w6,
   k_bw_odom_round<1>, two loop groups) and B = 136 (+ one-wave aux blocks, four write-back threads): every copy equals copy 0 in
   every stage on repeated steps, copy 0 equals the window solved alone (a batch of one) bit for bit and the oracle within
   1e-4 m / 1e-4 rad at equal iteration counts; then one more frame WITHOUT a restore, so that the device-resident prior feeds the
@@ -64,18 +64,18 @@ def _assert_same_state(a, b, what):
             np.testing.assert_array_equal(x[2], y[2], err_msg=f"{what}: window {k} prior")
 
 
-OPTION_SETS = [   # (lanes_per_query, occupancy, loop_groups, aux_threads, finish_threads, parts)
-    (8, -1, 1, 256, 1, 1),       # what a small batch takes by itself
-    (4, -1, 1, 256, 1, 2),       # ... as two parts on two host threads (2 + 1 windows)
-    (2, -1, 2, 128, 2, 1),
-    (1, 0, 2, 64, 1, 2),         # one lane per query as compiled
-    (1, 6, 3, 64, 3, 1),
-    (1, 8, 0, 64, 8, 2),         # the forms a batch of 512 headline windows runs
-    (0, -1, 0, 0, 0, 0),         # everything by size again
+OPTION_SETS = [   # (lanes_per_query, loop_groups, aux_threads, finish_threads, parts)
+    (8, 1, 256, 1, 1),       # what a small batch takes by itself
+    (4, 1, 256, 1, 2),       # ... as two parts on two host threads (2 + 1 windows)
+    (4, 2, 128, 2, 1),
+    (1, 2, 64, 1, 2),        # one lane per query: k_bw_features1_w6, k_bw_odom_round<1>
+    (1, 3, 64, 3, 1),
+    (1, 0, 64, 8, 2),        # the choices of a batch of 512 headline windows (two parts, one loop group each)
+    (0, 0, 0, 0, 0),         # everything by size again
 ]
 
 
-def test_execution_choices_do_not_change_a_bit(hip):
+def test_kept_execution_choices_do_not_change_a_bit(hip):
     """Three different windows (sizes, keep_features) in one batch, restored and solved under every option set, then pushed one frame
     further without a restore (the prior comes from the device): digests of all stages, reports, windows and priors are the first set's."""
     specs = [("indoor", 4, 2, 0, 11, 3), ("indoor", 6, 3, 1, 13, 5), ("indoor", 5, 2, 0, 12, 7)]
@@ -98,8 +98,8 @@ def test_execution_choices_do_not_change_a_bit(hip):
     for _, _, _, est in runs:
         est.snapshot()
     first = None
-    for lpq, occ, groups, aux, fin, parts in OPTION_SETS:
-        for name, v in (("parts", parts), ("lanes_per_query", lpq), ("occupancy", occ), ("loop_groups", groups), ("aux_threads", aux), ("finish_threads", fin)):
+    for lpq, groups, aux, fin, parts in OPTION_SETS:
+        for name, v in (("parts", parts), ("lanes_per_query", lpq), ("loop_groups", groups), ("aux_threads", aux), ("finish_threads", fin)):
             batch.set_option(name, v)
         reps = batch.solve_restored(1)
         assert int(batch.clock()["n_device"]) == len(runs)
@@ -115,13 +115,17 @@ def test_execution_choices_do_not_change_a_bit(hip):
             first = (dg, st1, dg2, st2)
             assert all(k[0][8] == 1 for k in st1), "the compared step must marginalise (the prior of the second step comes from the device)"
             continue
-        what = f"options {(lpq, occ, groups, aux, fin, parts)}"
+        what = f"options {(lpq, groups, aux, fin, parts)}"
         np.testing.assert_array_equal(dg, first[0], err_msg=what)
         np.testing.assert_array_equal(dg2, first[2], err_msg=what + " (second step)")
         _assert_same_state(st1, first[1], what)
         _assert_same_state(st2, first[3], what + " (second step)")
     with pytest.raises(capi.LioError):
         batch.set_option("lanes_per_query", 3)
+    # removed choices: two lanes per query, the forced-occupancy forms and the aux row on a side stream
+    for name, v in (("lanes_per_query", 2), ("occupancy", 0), ("aux_stream", 0)):
+        with pytest.raises(capi.LioError):
+            batch.set_option(name, v)
     batch.close()
 
 

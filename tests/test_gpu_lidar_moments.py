@@ -3,7 +3,7 @@ rounded fp64 sums of the same per-residual terms — entry by entry, through eve
 
 * lio_est_eval_lidar_moments: the resident kernel (k_lidar_moments_resident<R>, R = LIO_RES_PER_LANE 1 / 2 / 4 / 8), the MFMA launch
   pair (k_lidar_moments + k_moment_reduce) over the resident partition (resident_moments = 3) and its own (resident_moments = 2),
-  the VALU launch pair (moments_form = 2), stream_sync, and factor sharding (world 2, both ranks in this process: the shares add up);
+  stream_sync, and factor sharding (world 2, both ranks in this process: the shares add up);
   several passes at different poses inside one solve scope, as the doorbell sees them across a solve;
 * lio_est_batch_get_moments: k_bw_moments' result at the point a batch solve accepted (one and two parts).
 
@@ -18,7 +18,7 @@ import moments_ref as mr
 
 pytestmark = pytest.mark.gpu
 
-# name -> (lio_est_config fields, LIO_RES_PER_LANE or None, the path the hook must report: 0 MFMA pair, 1 VALU pair, 2 resident)
+# name -> (lio_est_config fields, LIO_RES_PER_LANE or None, the path the hook must report: 0 MFMA pair, 2 resident)
 PATHS = {
     "resident_r1": (dict(resident_moments=1), "1", 2),
     "resident_r2": (dict(resident_moments=1), "2", 2),
@@ -26,7 +26,6 @@ PATHS = {
     "resident_r8": (dict(resident_moments=1), "8", 2),
     "pair_resident_partition": (dict(resident_moments=3), None, 0),
     "pair_own_partition": (dict(resident_moments=2), None, 0),
-    "valu": (dict(moments_form=2), None, 1),
     "stream_sync": (dict(resident_moments=1, stream_sync=1), None, 0),
 }
 SHAPES = [  # per optimised frame of the VLP-16 window (Wo 4): slot count; frames whose points are all far from the map; sparse last
@@ -91,7 +90,7 @@ def test_headline_window(hip, outdoor, path, monkeypatch):
 
 
 @pytest.mark.parametrize("shape", range(len(SHAPES)))
-@pytest.mark.parametrize("path", ["resident_r1", "resident_r2", "resident_r4", "resident_r8", "pair_resident_partition", "pair_own_partition", "valu"])
+@pytest.mark.parametrize("path", ["resident_r1", "resident_r2", "resident_r4", "resident_r8", "pair_resident_partition", "pair_own_partition"])
 def test_shapes(hip, oracle, indoor, path, shape, monkeypatch):
     counts, far, sparse = SHAPES[shape]
     stacks = mr.shape_stacks(oracle, indoor, "indoor", counts, far, sparse)
@@ -104,7 +103,7 @@ def test_shapes(hip, oracle, indoor, path, shape, monkeypatch):
 
 
 @pytest.mark.parametrize("kind", ["indoor", "outdoor"])
-@pytest.mark.parametrize("path,expect", [("resident_r8", 2), ("resident_r1", 0), ("valu", 1)])
+@pytest.mark.parametrize("path,expect", [("resident_r8", 2), ("resident_r1", 0)])
 def test_keep_features_window(hip, indoor, outdoor, kind, path, expect, monkeypatch):
     """keep_features = 1: the newest frame holds rounds x M slots (slot j's point: stack[j % M]).  At 8 residuals per lane the
     resident kernel takes the window; at 1 per lane it needs more blocks than the device keeps co-resident, and the launch pair must

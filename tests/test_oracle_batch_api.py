@@ -67,8 +67,9 @@ def test_batch_contract_shared_with_the_product(oracle):
         np.testing.assert_array_equal(a.get_window()[key], before[key])   # member 0 was NOT solved
     batch.set_option("lanes_per_query", 1)
     batch.set_option("loop_groups", 2)
-    with pytest.raises(capi.LioError):
-        batch.set_option("no_such_option", 1)
+    for name in ("no_such_option", "occupancy", "aux_stream"):   # (the last two: choices the product no longer has)
+        with pytest.raises(capi.LioError):
+            batch.set_option(name, 1)
     # destroying a member first: the batch is dissolved, its other members are free again, the batch handle only accepts destroy
     oracle.dll.lio_est_destroy(fresh.h)
     fresh.h = None
