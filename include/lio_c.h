@@ -349,17 +349,15 @@ typedef struct {
                                  1 = refine in the window, 2 = calibrate the rotation first (EstimateExtrinsicRotation) */
   int init_window_factor;     /* 3    Estimator.h:80: only every n-th frame enters the window until the IMU is initialised */
   /* ---- execution switches of the product (no reference counterpart; results are the same up to the documented tolerances, the
-   * oracle ignores them).  0 = the shipped default.  An environment variable (named at each field), when set, overrides the
-   * field at lio_est_create — for A/B runs of a host that cannot be rebuilt. */
+   * oracle ignores them).  0 = the shipped default. */
   int device_solve;           /* 1: the handle solves as a batch of ONE window (lio_est_batch below: trust-region loop and marginalization on
-                                 the device, the prior stays there between solves); LIO_DEVICE_SOLVE=1 or LIO_DEVICE_MARG=1 in the
-                                 environment select it too.  Ignores max_solver_time */
-  int inline_marg;            /* 1: marginalization inside lio_est_solve_optimization instead of the worker thread (LIO_ASYNC_MARG=0) */
-  int stream_sync;            /* 1: hipStreamSynchronize + D2H copies instead of completion words in host memory (LIO_HOST_SIGNAL=0) */
+                                 the device, the prior stays there between solves).  Ignores max_solver_time */
+  int inline_marg;            /* 1: marginalization inside lio_est_solve_optimization instead of the worker thread */
+  int stream_sync;            /* 1: hipStreamSynchronize + D2H copies instead of completion words in host memory */
   int resident_moments;       /* 0: by default rule (on), 1: on, 2: off, 3: its partition with launches only — the lidar moments of a solve
-                                 come from ONE resident kernel that waits for each linearisation point on a doorbell in host memory
-                                 (LIO_RESIDENT_MOMENTS=0|1).  "On" is a permission: a solve takes the resident form while it is the only
-                                 solve in flight in the process and its factor slots fit 256 co-resident blocks, and a launch pair
+                                 come from ONE resident kernel that waits for each linearisation point on a doorbell in host memory.
+                                 "On" is a permission: a solve takes the resident form while it is the only solve in flight in the
+                                 process and its factor slots fit 256 co-resident blocks, and a launch pair
                                  per linearisation otherwise — over the SAME partition of the factor slots, so the moments do not
                                  depend on which of the two ran (3 pins the launch pairs: what a refused solve gets).  2 is round 2's
                                  launch pair with its own partition: the same sums in a different order, last-ulp differences */
@@ -434,8 +432,8 @@ int lio_est_solve_optimization(lio_est *, lio_solve_report *report_or_null);
 int lio_est_slide_window(lio_est *);
 /* The product defers the marginalization of a solve (host-only work whose result, the prior, is first read by the next
  * solve) to a worker thread; every reader joins it first, so results are those of the synchronous sequence.  This call
- * waits for all deferred work of the handle (no reference counterpart; a no-op in the oracle).  LIO_ASYNC_MARG=0 in the
- * environment keeps the marginalization inside lio_est_solve_optimization. */
+ * waits for all deferred work of the handle (no reference counterpart; a no-op in the oracle).  lio_est_config.inline_marg = 1
+ * keeps the marginalization inside lio_est_solve_optimization. */
 int lio_est_sync(lio_est *);
 
 /* ---- test hooks (no reference counterpart): inject / read a window ---- */
@@ -490,7 +488,7 @@ int lio_dense_spd_solve(const double *A, const double *b, int n, double *x_out);
  * system.  A: (m + n)^2 row-major, b: m + n, the first m parameters are marginalised (m <= 15, n <= 80).  Out: lin_jac n x n
  * row-major = diag(sqrt(s_k > 1e-8 ? s_k : 0)) V^T, lin_res n = diag(1 / sqrt(s_k) or 0) V^T bs, evals n (ascending s_k of the
  * Schur complement).  The product runs it on the device (csrc/marg_kernels.hip: Jacobi eigensolver in LDS, Schur complement on
- * the fp64 matrix cores) — the path LIO_DEVICE_MARG=1 switches the estimator to. */
+ * the fp64 matrix cores) — the path lio_est_config.device_solve = 1 switches the estimator to. */
 int lio_marginalize_schur(const double *A, const double *b, int m, int n, double *lin_jac, double *lin_res, double *evals);
 
 /* In-memory snapshot / restore of the whole estimator state (bench + parity loops). */

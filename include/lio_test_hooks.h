@@ -23,6 +23,11 @@ extern "C" {
  * first. */
 int lio_est_eval_lidar_moments(lio_est *, int n_passes, const double *Rt, double *out, int *path_out_or_null);
 
+/* Residuals per lane of the resident moments kernel (and the partition of the factor slots that goes with it) for the handle's later
+ * solves and lio_est_eval_lidar_moments calls: 1, 2, 4 or 8 forces that count, 0 restores the rule that picks it per window.  Any
+ * other value: LIO_ERR_ARG.  The oracle checks the argument and otherwise ignores it. */
+int lio_est_force_moments_per_lane(lio_est *, int per_lane);
+
 /* What stage 6 of lio_est_batch_stage_digest stands for, as numbers — the normal-equation moments of window `window` at the point its
  * last lio_est_batch_solve accepted (Wo x 258: S 16x16 row-major, cost, count) and the T_{pivot<-i} they were evaluated at (Rt: Wo x 12,
  * R row-major then t), read from the device state.  LIO_ERR_STATE when the window was not solved on the device.  Waits for the batch.

@@ -696,7 +696,6 @@ lio_est *lio_est_create(const lio_est_config *c) {
   e.max_num_iterations = c->max_num_iterations; e.max_solver_time = c->max_solver_time; e.extrinsic_stage = c->extrinsic_stage;
   e.init_window_factor = c->init_window_factor > 0 ? c->init_window_factor : 1;
   e.device_solve = c->device_solve != 0; e.inline_marg = c->inline_marg != 0;
-  for (const char *name : {"LIO_DEVICE_SOLVE", "LIO_DEVICE_MARG"}) if (const char *v = std::getenv(name)) { if (std::atoi(v) != 0) e.device_solve = true; else if (std::string(name) == "LIO_DEVICE_SOLVE") e.device_solve = false; }
   e.stream_sync = c->stream_sync != 0;
   e.resident_moments = (c->resident_moments >= 1 && c->resident_moments <= 3) ? c->resident_moments : 0;
   // Estimator.cc:189-194: the estimator's filter sizes and thresholds configure its PointMapping base (created on first use)
@@ -877,6 +876,11 @@ int lio_est_eval_lidar_moments(lio_est *h, int n_passes, const double *Rt, doubl
     if (path_out) *path_out = path;
     return LIO_OK;
   });
+}
+int lio_est_force_moments_per_lane(lio_est *h, int per_lane) {
+  if (!h || !(per_lane == 0 || per_lane == 1 || per_lane == 2 || per_lane == 4 || per_lane == 8)) return LIO_ERR_ARG;
+  h->e->ForceResidentPerLane(per_lane);
+  return LIO_OK;
 }
 int lio_est_get_laser_odom_transform(const lio_est *h, lio_transform_f *out) {
   if (!h || !out) return LIO_ERR_ARG;

@@ -64,8 +64,6 @@ class VoxelGridDev {
   HostSignal sig_{};
   bool use_signal_ = true;
 };
-// LIO_HOST_SIGNAL=0: every wait is a hipStreamSynchronize again
-bool host_signal_enabled();
 
 struct GridDesc {
   int origin[3];   // cell coordinate of cell (0,0,0)

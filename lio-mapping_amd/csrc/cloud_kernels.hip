@@ -312,11 +312,6 @@ void launch_cloud_bounds(const float4 *pts, int n, DBuf<float> &partial, VoxPara
   LIO_HIP(hipGetLastError());
 }
 
-bool host_signal_enabled() {
-  static const bool on = [] { const char *e = std::getenv("LIO_HOST_SIGNAL"); return e ? std::atoi(e) != 0 : true; }();
-  return on;
-}
-
 // launch() enqueues the whole filter on `s` (no host sync); finish() waits for it and returns the output count.  Two
 // filters launched on two streams overlap (the scan-to-map step filters its corner and surf stacks that way).
 void VoxelGridDev::launch(const float4 *in, size_t n, float leaf, DBuf<float4> &out, hipStream_t s) {
@@ -349,8 +344,7 @@ void VoxelGridDev::enqueue(bool exact) {
     h_flag_ = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(h_count_) + 128);
   }
   int *d_range = count_.p + 1;   // zero between runs: with the mailbox k_vox_centroids clears it after reading it (one fill command less)
-  const bool use_sig = use_signal_ && host_signal_enabled();
-  if (!use_sig) LIO_HIP(hipMemsetAsync(d_range, 0, sizeof(int), s));   // copy-back path: the host reads the flag behind the kernels, so they cannot clear it
+  if (!use_signal_) LIO_HIP(hipMemsetAsync(d_range, 0, sizeof(int), s));   // copy-back path: the host reads the flag behind the kernels, so they cannot clear it
   int npartial = 0;
   if (exact) {
     const int nb = std::min(cdiv(ni, 256), 512);
@@ -369,7 +363,7 @@ void VoxelGridDev::enqueue(bool exact) {
   tile_heads_.reserve(ntiles);
   hipLaunchKernelGGL(k_vox_tile_heads, dim3(ntiles + 1), dim3(VOX_TILE), 0, s, keys2_.p, ni, tile_heads_.p, partial_.p, npartial, inv_leaf, params_.p);
   sig_ = HostSignal();
-  if (use_sig) { sig_.flag = h_flag_; sig_.seq = ++seq_; }
+  if (use_signal_) { sig_.flag = h_flag_; sig_.seq = ++seq_; }
 
   hipLaunchKernelGGL(k_vox_centroids, dim3(ntiles), dim3(VOX_TILE), 0, s, in, keys2_.p, vals2_.p, tile_heads_.p, ni, out.p, count_.p, params_.p, d_range,
                      reinterpret_cast<VoxMail *>(h_count_), sig_);

@@ -229,7 +229,7 @@ class Estimator {
   int last_event_ = EV_SKIPPED;
   std::shared_ptr<MargPrior> last_marg_;   // read through JoinMarg() only: a marginalization may still be running
   MargWorker marg_worker_;
-  bool async_marg_ = true;                  // LIO_ASYNC_MARG=0 computes it inside SolveOptimization
+  bool async_marg_ = true;                  // lio_est_config.inline_marg = 1: computed inside SolveOptimization
   unsigned marg_epoch_ = 0, marg_task_epoch_ = 0;   // Restore() bumps the epoch: a result computed for a discarded state is dropped
   // materialize: a prior that a batched solve left on the device (MargPrior::on_device) is brought to the host as well — every
   // reader of its matrices on the host needs that; the batch itself, which feeds the next solve from the device copy, does not
@@ -298,9 +298,9 @@ class Estimator {
   DBuf<double> d_odom_partials_, d_moment_partials_, d_moment_out_;
   // Resident moments (solve_kernels.h): one launch per solve; every linearisation is a doorbell write + a spin on
   // the blocks' completion words.  Begun lazily by the first LidarLaunch of a SolveOptimization, stopped when it returns.
-  bool resident_moments_ = true;    // configured (lio_est_config.resident_moments / LIO_RESIDENT_MOMENTS)
+  bool resident_moments_ = true;    // configured (lio_est_config.resident_moments)
   bool resident_never_ = false;     // resident_moments = 3: the resident form's partition, launch pairs only (what a refused solve gets)
-  int res_per_lane_ = 0;            // residuals a lane keeps in registers: 0 = chosen per window (ResidentBpf), LIO_RES_PER_LANE forces 1, 2, 4, 8
+  int res_per_lane_ = 0;            // residuals a lane keeps in registers: 0 = chosen per window (ResidentBpf), lio_est_force_moments_per_lane forces 1, 2, 4, 8
   int res_lanes_ = 4;               // ... of the launch in flight
   bool res_allowed_ = false;        // inside SolveOptimization
   bool res_active_ = false;         // a resident kernel is waiting on the doorbell
@@ -322,6 +322,7 @@ class Estimator {
   double res_launch_ms_ = 0; int res_launches_ = 0;
  public:
   void ResidentLaunchTiming(bool on) { res_time_launch_ = on; }
+  void ForceResidentPerLane(int per_lane) { res_per_lane_ = per_lane; }   // lio_est_force_moments_per_lane (0: ResidentBpf's rule)
   int ResidentLaunchStats(double *total_ms);
  private:
   double res_diag_us_[4] = {0, 0, 0, 0}, res_polls_ = 0, res_relay_us_ = 0, res_ring_to_done_ms_ = 0, res_t_ring_ = 0, res_echo_ms_ = 0;
@@ -341,7 +342,7 @@ class Estimator {
   double *h_moment_out_ = nullptr;  // pinned
   OdomState *h_odom_ = nullptr;     // pinned landing zone of the laser-odom state peeks
   // Completion words (dev.h: HostSignal) in coherent pinned memory: [0, 96) one per block of k_moment_reduce, [128] the
-  // newest-frame round.  The host spins on them instead of hipStreamSynchronize (LIO_HOST_SIGNAL=0 restores the synchronize calls).
+  // newest-frame round.  The host spins on them instead of hipStreamSynchronize (lio_est_config.stream_sync restores the synchronize calls).
   unsigned *h_signal_ = nullptr;
   unsigned signal_seq_[2] = {0, 0};
   bool host_signal_ = true;

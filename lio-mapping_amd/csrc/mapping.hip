@@ -615,15 +615,10 @@ void MappingDev::Optimize(bool four_dof) {
                        f_valid_.p, f_coef_.p, f_abs_.p, d_conv, s);
       launch_odom_rows(stack_all_.p, M, M, f_valid_.p, f_coef_.p, d_state_.p, d_partials_.p, nb, s, four_dof ? 2 : 1);
       // the last round before a look at the convergence flag posts the state to the host's mailbox (dev.h: HostSignal)
-      if (iter == until - 1 && host_signal_enabled()) { sig.flag = h_flag_; sig.seq = ++seq_; }
+      if (iter == until - 1) { sig.flag = h_flag_; sig.seq = ++seq_; }
       launch_odom_update(d_partials_.p, nb, d_state_.p, iter, s, 50, four_dof ? 1 : 0, h_state_, sig);
     }
-    if (sig.flag) {
-      wait_host_signal(sig, s);
-    } else {
-      LIO_HIP(hipMemcpyAsync(h_state_, d_state_.p, sizeof(OdomState), hipMemcpyDeviceToHost, s));
-      LIO_HIP(hipStreamSynchronize(s));
-    }
+    wait_host_signal(sig, s);   // until > iter: the inner loop ran and its last round posted sig
     if (h_state_->converged) done = true;
   }
   st = *h_state_;

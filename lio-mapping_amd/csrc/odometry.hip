@@ -418,35 +418,23 @@ void OdometryDev::Process(const float *sharp, size_t n_sharp, const float *less_
       const int nb = std::max(1, std::min(cdiv(nq, ODO_ROW_THREADS), 64));
       d_partials_.reserve(size_t(nb) * 28);
       d_trace_.reserve(size_t(max_iter_) * 8);
-      const bool mail = host_signal_enabled();
       HostSignal sig{};
       bool have_state = false;
       for (int iter = 0; iter < max_iter_; ++iter) {
         if (iter > 0 && iter % 5 == 0) {  // look at the abort flag where the reference refreshes correspondences
-          if (mail) {
-            wait_host_signal(sig, s);
-          } else {
-            LIO_HIP(hipMemcpyAsync(h_state_, d_state_.p, sizeof(st), hipMemcpyDeviceToHost, s));  // pinned landing zone
-            LIO_HIP(hipStreamSynchronize(s));
-          }
+          wait_host_signal(sig, s);
           st = *h_state_;
           if (st.converged) { have_state = true; break; }
         }
         if (nq > 0 && iter % 5 == 0) hipLaunchKernelGGL(k_odo_corr, dim3(nq), dim3(64), 0, s, a, d_state_.p, idx_.p);
         hipLaunchKernelGGL(k_odo_rows, dim3(nb), dim3(ODO_ROW_THREADS), 0, s, a, d_state_.p, idx_.p, iter, d_partials_.p);
-        const bool post = mail && (iter % 5 == 4 || iter == max_iter_ - 1);
         HostSignal sg{};
-        if (post) { sig.flag = h_flag_; sig.seq = ++seq_; sg = sig; }
+        if (iter % 5 == 4 || iter == max_iter_ - 1) { sig.flag = h_flag_; sig.seq = ++seq_; sg = sig; }
         hipLaunchKernelGGL(k_odo_update, dim3(1), dim3(256), 0, s, d_partials_.p, nb, d_state_.p, iter, h_state_, sg, d_trace_.p);
       }
       LIO_HIP(hipGetLastError());
-      if (!have_state) {
-        if (sig.flag) {
-          wait_host_signal(sig, s);
-        } else {
-          LIO_HIP(hipMemcpyAsync(h_state_, d_state_.p, sizeof(st), hipMemcpyDeviceToHost, s));
-          LIO_HIP(hipStreamSynchronize(s));
-        }
+      if (!have_state) {   // the last iteration posted the state (max_iter_ >= 1)
+        wait_host_signal(sig, s);
         st = *h_state_;
       }
       if (st.iters > 0) {   // the records of the iterations that ran (every launch behind them is complete: the state came back)

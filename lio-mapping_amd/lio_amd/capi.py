@@ -263,6 +263,7 @@ _SIGS = {
 # include/lio_test_hooks.h: test hooks kept apart from the ABI of lio_c.h
 _TEST_SIGS = {
     "lio_est_eval_lidar_moments": (C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p, C.POINTER(C.c_int)]),
+    "lio_est_force_moments_per_lane": (C.c_int, [C.c_void_p, C.c_int]),
     "lio_est_batch_get_moments": (C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
 }
 
@@ -964,6 +965,10 @@ class Estimator:
         path = C.c_int(-3)
         _chk(self.lib.dll.lio_est_eval_lidar_moments(self.h, n_passes, _dp(Rt), _dp(out), C.byref(path)), "lio_est_eval_lidar_moments")
         return out, path.value
+
+    def force_moments_per_lane(self, per_lane):
+        """residuals per lane of the resident moments kernel for later solves and eval_lidar_moments: 1 / 2 / 4 / 8, 0 = chosen per window"""
+        _chk(self.lib.dll.lio_est_force_moments_per_lane(self.h, int(per_lane)), "lio_est_force_moments_per_lane")
 
     def laser_odom_transform(self):
         T = TransformF()

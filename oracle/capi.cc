@@ -723,6 +723,10 @@ int lio_est_eval_lidar_moments(lio_est *h, int n_passes, const double *Rt, doubl
   if (path_out) *path_out = -1;
   return LIO_OK;
 }
+int lio_est_force_moments_per_lane(lio_est *h, int per_lane) {
+  if (!h || !(per_lane == 0 || per_lane == 1 || per_lane == 2 || per_lane == 4 || per_lane == 8)) return LIO_ERR_ARG;
+  return LIO_OK;   // no resident kernel: nothing to force
+}
 int lio_est_get_laser_odom_transform(const lio_est *h, lio_transform_f *out) {
   if (!h || !out) return LIO_ERR_ARG;
   fromT(h->est.laser_odom_transform, out);

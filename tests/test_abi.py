@@ -75,10 +75,10 @@ def _declared_test_hooks():
     return sorted(set(re.findall(r"\b(lio_[a-z0-9_]+)\s*\(", text)))
 
 
-def test_test_hooks_are_bound_and_exported_by_both_libraries(oracle):
+def test_each_test_hook_is_bound_and_exported_by_both_libraries(oracle):
     """include/lio_test_hooks.h: every hook bound in Python and exported by the product and the oracle"""
     hooks = _declared_test_hooks()
-    assert len(hooks) >= 2
+    assert len(hooks) >= 3
     assert set(hooks) == set(capi._TEST_SIGS.keys())
     assert not set(hooks) & set(_declared_symbols())
     dll = ctypes.CDLL(capi.HIP_LIB_PATH)
@@ -100,6 +100,7 @@ def test_test_hook_header_is_plain_c_and_links(tmp_path, oracle, lib):
                    "  int path = 7;\n"
                    "  if (lio_est_eval_lidar_moments(NULL, 1, NULL, NULL, &path) != LIO_ERR_ARG || path != 7) return 1;\n"
                    "  if (lio_est_batch_get_moments(NULL, 0, NULL, NULL) != LIO_ERR_ARG) return 2;\n"
+                   "  if (lio_est_force_moments_per_lane(NULL, 0) != LIO_ERR_ARG) return 3;\n"
                    '  puts("hooks ok");\n  return 0;\n}\n')
     exe = tmp_path / "hooks"
     libdir, libname = os.path.dirname(path), os.path.basename(path)

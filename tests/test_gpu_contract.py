@@ -161,7 +161,7 @@ def test_teacher_forced_chain_of_20_solves(hip, oracle, kind, frame_dt):
 
 
 def test_stream_sync_fallback_gives_the_same_bits(hip, oracle):
-    """lio_est_config.stream_sync = 1 (the LIO_HOST_SIGNAL=0 path: D2H copies + hipStreamSynchronize instead of completion words in
+    """lio_est_config.stream_sync = 1 (D2H copies + hipStreamSynchronize instead of completion words in
     host memory) must stay alive: same kernels, same arithmetic => the same window bit for bit over solve + slide + solve.  This
     also pins the resident moments kernel to its launch form: with stream_sync the lidar moments come from k_lidar_moments +
     k_moment_reduce launches instead of the resident kernel's passes."""

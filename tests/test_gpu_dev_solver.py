@@ -2,7 +2,7 @@
 register-resident 16x16 diagonal block on one wave (v_readlane broadcasts), row-parallel triangular solves, fp64-MFMA
 trailing updates, blocked back-substitution — against numpy / the oracle's Cholesky on random SPD systems at the sizes the
 solver sees (D = 90 / 96 for opt window 5, 120 / 126 for 7, ragged sizes in between), and the whole solve with the host loop
-(LIO_DEVICE_SOLVE=0) as the reference for the device loop."""
+(device_solve = 0) as the reference for the device loop."""
 import numpy as np
 import pytest
 
@@ -38,8 +38,8 @@ def test_dense_spd_solve_rejects_indefinite(hip):
         hip.dense_spd_solve(A, np.ones(33))
 
 
-def test_device_loop_equals_host_loop(hip, monkeypatch):
-    """The same chain through the device-resident dogleg (LIO_DEVICE_SOLVE=1) and through the host loop: two estimators in
+def test_device_loop_equals_host_loop(hip):
+    """The same chain through the device-resident dogleg (device_solve = 1) and through the host loop: two estimators in
     lockstep, the device one handed the host one's states, extrinsic and prior before every step (tests/golden/README.md:
     a chain amplifies its inputs' differences).  Identical iteration counts, accepted / rejected steps, termination codes,
     convergence flags; cost traces within 1e-7; states within 1e-7 m after every step; priors equal to 1e-7."""
@@ -49,8 +49,8 @@ def test_device_loop_equals_host_loop(hip, monkeypatch):
     clouds = [pipeline.feature_clouds(hip, ds.lidar, f.scan) for f in ds.frames]
 
     def make(device):
-        monkeypatch.setenv("LIO_DEVICE_SOLVE", "1" if device else "0")   # read when the estimator is created
         cfg = pipeline.config_indoor(hip, 4, 2)
+        cfg.device_solve = 1 if device else 0
         cfg.cutoff_deskew, cfg.keep_features, cfg.prior_factor = 1, 0, 1
         pipeline.set_extrinsic(cfg, ds)
         est = capi.Estimator(hip, cfg)

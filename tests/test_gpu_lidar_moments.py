@@ -1,8 +1,9 @@
 """The product's lidar moments S = sum rho' z z^T, cost and count (csrc/solve_kernels.h) against tests/moments_ref.py — exactly
 rounded fp64 sums of the same per-residual terms — entry by entry, through every path that produces them:
 
-* lio_est_eval_lidar_moments: the resident kernel (k_lidar_moments_resident<R>, R = LIO_RES_PER_LANE 1 / 2 / 4 / 8), the MFMA launch
-  pair (k_lidar_moments + k_moment_reduce) over the resident partition (resident_moments = 3) and its own (resident_moments = 2),
+* lio_est_eval_lidar_moments: the resident kernel (k_lidar_moments_resident<R>, R = 1 / 2 / 4 / 8 through
+  lio_est_force_moments_per_lane), the MFMA launch pair (k_lidar_moments + k_moment_reduce) over the resident partition
+  (resident_moments = 3) and its own (resident_moments = 2),
   stream_sync, and factor sharding (world 2, both ranks in this process: the shares add up);
   several passes at different poses inside one solve scope, as the doorbell sees them across a solve;
 * lio_est_batch_get_moments: k_bw_moments' result at the point a batch solve accepted (one and two parts).
@@ -18,12 +19,12 @@ import moments_ref as mr
 
 pytestmark = pytest.mark.gpu
 
-# name -> (lio_est_config fields, LIO_RES_PER_LANE or None, the path the hook must report: 0 MFMA pair, 2 resident)
+# name -> (lio_est_config fields, residuals per lane to force or None, the path the hook must report: 0 MFMA pair, 2 resident)
 PATHS = {
-    "resident_r1": (dict(resident_moments=1), "1", 2),
-    "resident_r2": (dict(resident_moments=1), "2", 2),
-    "resident_r4": (dict(resident_moments=1), "4", 2),
-    "resident_r8": (dict(resident_moments=1), "8", 2),
+    "resident_r1": (dict(resident_moments=1), 1, 2),
+    "resident_r2": (dict(resident_moments=1), 2, 2),
+    "resident_r4": (dict(resident_moments=1), 4, 2),
+    "resident_r8": (dict(resident_moments=1), 8, 2),
     "pair_resident_partition": (dict(resident_moments=3), None, 0),
     "pair_own_partition": (dict(resident_moments=2), None, 0),
     "stream_sync": (dict(resident_moments=1, stream_sync=1), None, 0),
@@ -56,13 +57,12 @@ def _report():
         print(f"[moments] {k[0]:24s} {k[1]:28s} max|S-S_ref|/A {s:.2e}  max|cost err| {c:.2e}  rel {cr:.2e}")
 
 
-def _window(hip, data, kind, path, monkeypatch, **kw):
+def _window(hip, data, kind, path, **kw):
     fields, per_lane, expect = PATHS[path]
-    if per_lane is None:
-        monkeypatch.delenv("LIO_RES_PER_LANE", raising=False)
-    else:
-        monkeypatch.setenv("LIO_RES_PER_LANE", per_lane)   # read when the estimator is created
-    return mr.make_window(hip, data, kind, **kw, **fields), expect
+    est = mr.make_window(hip, data, kind, **kw, **fields)
+    if per_lane is not None:
+        est.force_moments_per_lane(per_lane)
+    return est, expect
 
 
 def _check(est, passes, path, case, expect_path):
@@ -81,9 +81,9 @@ def _check(est, passes, path, case, expect_path):
 
 
 @pytest.mark.parametrize("path", list(PATHS))
-def test_headline_window(hip, outdoor, path, monkeypatch):
+def test_headline_window(hip, outdoor, path):
     """the HDL-64E window (W 15 / Wo 5, keep_features 0 so that the resident form takes it)"""
-    est, expect = _window(hip, outdoor, "outdoor", path, monkeypatch)
+    est, expect = _window(hip, outdoor, "outdoor", path)
     passes = mr.make_passes(mr.window_rt(est.get_window(), 15, 5), 21)
     feats, _ = _check(est, passes, path, "headline", expect)
     assert sum(f[0].shape[0] for f in feats) > 20000
@@ -91,10 +91,10 @@ def test_headline_window(hip, outdoor, path, monkeypatch):
 
 @pytest.mark.parametrize("shape", range(len(SHAPES)))
 @pytest.mark.parametrize("path", ["resident_r1", "resident_r2", "resident_r4", "resident_r8", "pair_resident_partition", "pair_own_partition"])
-def test_shapes(hip, oracle, indoor, path, shape, monkeypatch):
+def test_shapes(hip, oracle, indoor, path, shape):
     counts, far, sparse = SHAPES[shape]
     stacks = mr.shape_stacks(oracle, indoor, "indoor", counts, far, sparse)
-    est, expect = _window(hip, indoor, "indoor", path, monkeypatch, stacks=stacks)
+    est, expect = _window(hip, indoor, "indoor", path, stacks=stacks)
     passes = mr.make_passes(mr.window_rt(est.get_window(), 8, 4), 30 + shape)
     feats, out = _check(est, passes, path, f"slots {counts}", expect)
     for f in far:
@@ -102,31 +102,50 @@ def test_shapes(hip, oracle, indoor, path, shape, monkeypatch):
         assert np.all(out[:, f, :] == 0.0)
 
 
-@pytest.mark.parametrize("kind", ["indoor", "outdoor"])
-@pytest.mark.parametrize("path,expect", [("resident_r8", 2), ("resident_r1", 0)])
-def test_keep_features_window(hip, indoor, outdoor, kind, path, expect, monkeypatch):
-    """keep_features = 1: the newest frame holds rounds x M slots (slot j's point: stack[j % M]).  At 8 residuals per lane the
-    resident kernel takes the window; at 1 per lane it needs more blocks than the device keeps co-resident, and the launch pair must
-    take the passes instead (path 0) — with the same sums."""
+def _keep_features_window(hip, indoor, outdoor, kind, path, expect):
+    """keep_features = 1: the newest frame holds rounds x M slots (slot j's point: stack[j % M])"""
     data = indoor if kind == "indoor" else outdoor
     W, Wo = (8, 4) if kind == "indoor" else (15, 5)
-    est, _ = _window(hip, data, kind, path, monkeypatch, keep=1)
+    est, _ = _window(hip, data, kind, path, keep=1)
     passes = mr.make_passes(mr.window_rt(est.get_window(), W, Wo), 40)
     feats, _ = _check(est, passes, path, f"{kind} keep_features", expect)
     assert feats[-1][0].shape[0] > est.get_surf_stack(W).shape[0]
+    return est, passes
+
+
+@pytest.mark.parametrize("kind", ["indoor", "outdoor"])
+@pytest.mark.parametrize("path,expect", [("resident_r8", 2)])
+def test_keep_features_window(hip, indoor, outdoor, kind, path, expect):
+    """the keep_features window at 8 residuals per lane: the resident kernel takes it (1 per lane: test_force_moments_per_lane)"""
+    _keep_features_window(hip, indoor, outdoor, kind, path, expect)
+
+
+@pytest.mark.parametrize("kind", ["indoor", "outdoor"])
+def test_force_moments_per_lane(hip, indoor, outdoor, kind):
+    """lio_est_force_moments_per_lane on the keep_features window.  At 1 residual per lane the window needs more blocks than the
+    device keeps co-resident, and the launch pair must take the passes instead (path 0) — with the same sums.  0 hands the choice
+    back to the rule, which finds a count whose blocks are co-resident (path 2).  Values other than 0 / 1 / 2 / 4 / 8 are refused."""
+    from lio_amd import capi
+
+    est, passes = _keep_features_window(hip, indoor, outdoor, kind, "resident_r1", 0)
+    est.force_moments_per_lane(0)
+    assert est.eval_lidar_moments(passes)[1] == 2
+    for v in (-1, 3, 16):
+        with pytest.raises(capi.LioError):
+            est.force_moments_per_lane(v)
 
 
 @pytest.mark.parametrize("case", ["headline", "shapes"])
-def test_factor_sharding_shares_add_up(hip, oracle, indoor, outdoor, case, monkeypatch):
+def test_factor_sharding_shares_add_up(hip, oracle, indoor, outdoor, case):
     """world 2, both ranks in this process with a no-op all-reduce: each rank's hook returns its own share (slot_begin, slot_end),
     and the two shares add up to the whole window's moments"""
     outs = []
     for rank in range(2):
         if case == "headline":
-            est, _ = _window(hip, outdoor, "outdoor", "resident_r1", monkeypatch)
+            est, _ = _window(hip, outdoor, "outdoor", "resident_r1")
             W, Wo = 15, 5
         else:
-            est, _ = _window(hip, indoor, "indoor", "resident_r1", monkeypatch, stacks=mr.shape_stacks(oracle, indoor, "indoor", (1, 65, 257, 769)))
+            est, _ = _window(hip, indoor, "indoor", "resident_r1", stacks=mr.shape_stacks(oracle, indoor, "indoor", (1, 65, 257, 769)))
             W, Wo = 8, 4
         est.set_factor_sharding(rank, 2, lambda buf: None)
         passes = mr.make_passes(mr.window_rt(est.get_window(), W, Wo), 50)

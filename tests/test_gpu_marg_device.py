@@ -1,6 +1,6 @@
 """Marginalization's dense tail on the device (csrc/marg_kernels.hip; MarginalizationFactor.cc:271-302): the Jacobi
 eigensolver + fp64-MFMA Schur complement against the numpy second source (tests/golden/second_source.py), the oracle, and —
-through the estimator with LIO_DEVICE_MARG=1 — against the host path and the oracle on a chain of solves."""
+through the estimator with device_solve = 1 — against the host path and the oracle on a chain of solves."""
 import os
 import sys
 
@@ -73,13 +73,11 @@ def test_out_of_range_shapes_are_rejected(hip):
 
 
 @pytest.mark.parametrize("kind,W,Wo", [("indoor", 6, 3), ("outdoor", 15, 5)])
-def test_estimator_with_device_marginalization(hip, oracle, monkeypatch, kind, W, Wo):
-    """LIO_DEVICE_MARG=1: the prior of every step comes from the device kernel.  Same decisions and windows as the oracle over
+def test_estimator_with_device_marginalization(hip, oracle, kind, W, Wo):
+    """device_solve = 1: the prior of every step comes from the device kernel.  Same decisions and windows as the oracle over
     a chain of solves (teacher-forced, tests/window_util.py), and the priors agree on the order-equivariant invariants."""
     from window_util import assert_windows_close, force_all, make_pair
-    monkeypatch.setenv("LIO_DEVICE_MARG", "1")
-    ds, clouds, (ea, eb) = make_pair((hip, oracle), kind, W, Wo, W + 5, 0.2 if kind == "indoor" else 0.3)
-    monkeypatch.delenv("LIO_DEVICE_MARG")
+    ds, clouds, (ea, eb) = make_pair((hip, oracle), kind, W, Wo, W + 5, 0.2 if kind == "indoor" else 0.3, cfg_fields={"device_solve": 1})
     for est in (ea, eb):
         est.solve()
         est.slide()

@@ -368,16 +368,16 @@ def test_sequence_with_marginalization(hip, oracle):
     np.testing.assert_allclose(pa["x0"], pb["x0"], atol=1e-4)
 
 
-def test_deferred_marginalization_equals_inline(hip, monkeypatch):
+def test_deferred_marginalization_equals_inline(hip):
     """The marginalization worker only moves WHEN the prior is computed: a sequence of solves with
-    it gives bit-identical windows and priors to the same sequence with LIO_ASYNC_MARG=0, also across snapshot /
+    it gives bit-identical windows and priors to the same sequence with inline_marg = 1, also across snapshot /
     restore (which drops an in-flight result of the discarded state)."""
     ds = synth.make_dataset("indoor", 10, 0.2)
     clouds = [pipeline.feature_clouds(hip, ds.lidar, f.scan) for f in ds.frames]
 
     def run(async_on):
-        monkeypatch.setenv("LIO_ASYNC_MARG", "1" if async_on else "0")
         cfg = pipeline.config_indoor(hip, 4, 2)
+        cfg.inline_marg = 0 if async_on else 1
         cfg.cutoff_deskew, cfg.keep_features, cfg.prior_factor = 1, 0, 1
         pipeline.set_extrinsic(cfg, ds)
         est = capi.Estimator(hip, cfg)

@@ -133,3 +133,18 @@ def test_oracle_batch_moments_are_zeros(oracle, indoor):
     assert out.shape == (4, 258) and Rt.shape == (4, 12)
     assert np.all(out == 0) and np.all(Rt == 0)
     b.close()
+
+
+def test_oracle_force_moments_per_lane(oracle, indoor):
+    """the hook checks its argument (0, 1, 2, 4, 8) and otherwise leaves the oracle's sums alone"""
+    from lio_amd import capi
+
+    est = mr.make_window(oracle, indoor, "indoor")
+    passes = mr.make_passes(mr.window_rt(est.get_window(), 8, 4), 13)
+    out, _ = est.eval_lidar_moments(passes)
+    for v in (-1, 3, 16):
+        with pytest.raises(capi.LioError):
+            est.force_moments_per_lane(v)
+    for v in (1, 2, 4, 8, 0):
+        est.force_moments_per_lane(v)
+        assert np.array_equal(est.eval_lidar_moments(passes)[0], out)

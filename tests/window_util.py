@@ -4,10 +4,12 @@ import numpy as np
 from lio_amd import capi, pipeline, synth
 
 
-def make_pair(libs, kind, W, Wo, n_frames, frame_dt, keep=0, deskew=False, prior_factor=1, seed=3, sigmas=(0.01, 0.001, 0.01), pp_lib=None):
+def make_pair(libs, kind, W, Wo, n_frames, frame_dt, keep=0, deskew=False, prior_factor=1, seed=3, sigmas=(0.01, 0.001, 0.01), pp_lib=None,
+              cfg_fields=None):
     """One estimator per library in `libs`, all initialised with the same window (frames 0..W of a seeded synthetic
     run, ground truth + the same perturbation) and the same stacks.  Feature clouds come from `pp_lib` (default: the
-    last library, i.e. the oracle in (hip, oracle))."""
+    last library, i.e. the oracle in (hip, oracle)).  cfg_fields: further lio_est_config fields (execution switches such as
+    device_solve, which the oracle ignores)."""
     ds = synth.make_dataset(kind, n_frames, frame_dt)
     pp_lib = pp_lib or libs[-1]
     clouds = [pipeline.feature_clouds(pp_lib, ds.lidar, f.scan) for f in ds.frames]
@@ -17,6 +19,8 @@ def make_pair(libs, kind, W, Wo, n_frames, frame_dt, keep=0, deskew=False, prior
         cfg.keep_features = keep
         cfg.prior_factor = prior_factor
         cfg.cutoff_deskew = 0 if deskew else 1
+        for k, v in (cfg_fields or {}).items():
+            setattr(cfg, k, v)
         pipeline.set_extrinsic(cfg, ds)
         est = capi.Estimator(lib, cfg)
         pipeline.init_window(est, lib, ds, [c[0] for c in clouds], pos_sigma=sigmas[0], rot_sigma=sigmas[1], vel_sigma=sigmas[2], seed=seed)
