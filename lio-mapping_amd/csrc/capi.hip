@@ -879,7 +879,7 @@ int lio_est_eval_lidar_moments(lio_est *h, int n_passes, const double *Rt, doubl
 }
 int lio_est_force_moments_per_lane(lio_est *h, int per_lane) {
   if (!h || !(per_lane == 0 || per_lane == 1 || per_lane == 2 || per_lane == 4 || per_lane == 8)) return LIO_ERR_ARG;
-  h->e->ForceResidentPerLane(per_lane);
+  h->e->resident_.ForcePerLane(per_lane);
   return LIO_OK;
 }
 int lio_est_get_laser_odom_transform(const lio_est *h, lio_transform_f *out) {
@@ -1174,7 +1174,7 @@ int lio_est_bench_batched_moments(lio_est *h, int n_windows, int reps, double *a
 }
 int lio_est_enable_kernel_timing(lio_est *h, int on) {
   if (!h) return LIO_ERR_ARG;
-  h->e->ResidentLaunchTiming(on == -1);   // -1: only the resident moments kernel's launches are bracketed (it stays in use)
+  h->e->resident_.LaunchTiming(on == -1);   // -1: only the resident moments kernel's launches are bracketed (it stays in use)
   h->e->timers_.on = on > 0;
   h->e->timers_.sample = on > 1 ? on : 1;
   h->e->timers_.reset();
@@ -1189,13 +1189,13 @@ int lio_est_get_kernel_timing(lio_est *h, const char *name, double *total_ms, do
     // the resident moments kernel cannot be bracketed by HIP events per pass (one launch serves a whole solve): its passes are
     // timed on the device's wall clock, doorbell copy seen -> sums posted, slowest frame; counted since the handle was created
     int passes = 0;
-    const double us = h->e->ResidentBusyUs(&passes, bytes);
+    const double us = h->e->resident_.BusyUs(&passes, bytes);
     if (total_ms) *total_ms = us * 1e-3;
     return passes;
   }
   if (std::strcmp(name, "moments_resident_launch") == 0) {   // dispatch-to-exit spans recorded under lio_est_enable_kernel_timing(-1)
     int n = 0;
-    guarded([&] { n = h->e->ResidentLaunchStats(total_ms); return LIO_OK; });
+    guarded([&] { n = h->e->resident_.LaunchStats(total_ms, h->e->stream()); return LIO_OK; });
     return n;
   }
   for (int k = 0; k < KT_COUNT; ++k)

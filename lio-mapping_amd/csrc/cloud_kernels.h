@@ -46,13 +46,13 @@ class VoxelGridDev {
   VoxelGridDev() = default;
   VoxelGridDev(const VoxelGridDev &) = delete;
   VoxelGridDev &operator=(const VoxelGridDev &) = delete;
-  ~VoxelGridDev();
 
  private:
   const float4 *p_in_ = nullptr; size_t p_n_ = 0; DBuf<float4> *p_out_ = nullptr; hipStream_t p_stream_ = nullptr;  // the pending launch
   float p_leaf_ = 0.f;
   void enqueue(bool exact);
-  int *h_count_ = nullptr;          // pinned: output count, followed by the VoxParams
+  HostBuf<char> h_mail_;            // pinned, coherent, allocated on first use
+  int *h_count_ = nullptr;          // ... its views: output count, followed by the VoxParams
   VoxParams *h_params_ = nullptr;
   DBuf<float> partial_;
   DBuf<VoxParams> params_;
@@ -108,12 +108,6 @@ struct FeatArgs {
 // when *skip_flag != 0 the launch is a no-op (converged laser-odom loop).
 void launch_features(const FeatArgs &a, const float *transforms, const float4 *map_sorted, const int *cells, const GridDesc &g,
                      uint8_t *valid, float4 *coef, float *score, const int *skip_flag, hipStream_t s, float4 *abs_coef = nullptr);
-
-// Corner branch of PointMapping::OptimizeTransformTobeMapped (PointMapping.cc:377-517): 5-NN in the corner map, 3x3
-// covariance eigen-decomposition, line residual; slots [slot_off, slot_off+M).  transform: device, 8 floats.
-void launch_line_features(const float4 *stack, int M, int slot_off, const float *transform, const float fixed_pz[3], float min_match_sq_dis,
-                          const float4 *map_sorted, const int *cells, const GridDesc &g, uint8_t *valid, float4 *coef,
-                          const int *skip_flag, hipStream_t s);
 
 // stateless K-NN (lio_knn entry point): idx/sqd are m*k
 void launch_knn(const float4 *query, int m, int k, float radius_sq, const float4 *map_sorted, const int *cells, const GridDesc &g,

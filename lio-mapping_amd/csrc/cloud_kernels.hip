@@ -337,9 +337,9 @@ void VoxelGridDev::enqueue(bool exact) {
   out.reserve(n);
   if (!h_count_) {
     // coherent pinned memory: k_vox_centroids posts the count, the bounds and the range flag here (VoxMail), then the completion word
-    LIO_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_count_), 256, hipHostMallocCoherent));
+    h_mail_.alloc(256, hipHostMallocCoherent, true);
     static_assert(sizeof(VoxMail) <= 128, "mailbox layout");
-    std::memset(h_count_, 0, 256);
+    h_count_ = reinterpret_cast<int *>(h_mail_.p);
     h_params_ = reinterpret_cast<VoxParams *>(h_count_ + 1);
     h_flag_ = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(h_count_) + 128);
   }
@@ -411,10 +411,6 @@ size_t VoxelGridDev::finish(VoxParams *host_params) {
 size_t VoxelGridDev::run(const float4 *in, size_t n, float leaf, DBuf<float4> &out, hipStream_t s, VoxParams *host_params) {
   launch(in, n, leaf, out, s);
   return finish(host_params);
-}
-
-VoxelGridDev::~VoxelGridDev() {
-  if (h_count_) (void)hipHostFree(h_count_);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -564,8 +560,9 @@ __global__ void __launch_bounds__(FEAT_THREADS) k_features(FeatArgs a, const flo
   features_block<MAPPING, LPQ>(a.fr[blockIdx.y], feat_scalars(a), int(blockIdx.x), transforms, map, cells, g, valid, coef, score, abs_coef);
 }
 
-// Corner branch of the scan-to-map step: one query per FEAT_LPQ lanes, 5-NN, covariance of the 5 neighbours, line
-// direction = eigenvector of the largest eigenvalue (accepted when it dominates 3x the middle one).
+// Corner branch of the scan-to-map step (PointMapping::OptimizeTransformTobeMapped, PointMapping.cc:377-517): one query per
+// FEAT_LPQ lanes, 5-NN, covariance of the 5 neighbours, line direction = eigenvector of the largest eigenvalue (accepted when
+// it dominates 3x the middle one).
 template <int LPQ = FEAT_LPQ>
 __device__ __forceinline__ void line_features_body(int block_x, const float4 *__restrict__ stack, int M, int slot_off, const float *__restrict__ tp,
                                                    const Vec3<float> &pz, float min_match_sq_dis, const float4 *__restrict__ map,
@@ -634,14 +631,6 @@ __device__ __forceinline__ void line_features_body(int block_x, const float4 *__
   valid[slot] = ok; coef[slot] = c;
 }
 
-__global__ void __launch_bounds__(128) k_line_features(const float4 *__restrict__ stack, int M, int slot_off, const float *__restrict__ tp,
-                                                      Vec3<float> pz, float min_match_sq_dis, const float4 *__restrict__ map,
-                                                      const int *__restrict__ cells, GridDesc g, uint8_t *__restrict__ valid,
-                                                      float4 *__restrict__ coef, const int *__restrict__ skip_flag) {
-  if (skip_flag && *skip_flag) return;
-  line_features_body(blockIdx.x, stack, M, slot_off, tp, pz, min_match_sq_dis, map, cells, g, valid, coef);
-}
-
 // One round of the scan-to-map search in ONE launch: blockIdx.y = 0 runs the corner (line) branch against the corner map,
 // blockIdx.y = 1 the surf (plane) branch against the surf map.  No cross-stream events, one dispatch.
 struct MapRoundArgs {
@@ -670,15 +659,6 @@ void launch_map_round(const FeatArgs &surf, const float4 *corner_stack, int Mc, 
                  cdiv((long long)surf.max_M * 8, 128)};
   const int bx = std::max(1, std::max(m.blocks_corner, m.blocks_surf));
   hipLaunchKernelGGL(k_map_round, dim3(bx, 2), dim3(128), 0, s, surf, m, transform, valid, coef, abs_coef, skip_flag);
-  LIO_HIP(hipGetLastError());
-}
-
-void launch_line_features(const float4 *stack, int M, int slot_off, const float *transform, const float fixed_pz[3], float min_match_sq_dis,
-                          const float4 *map_sorted, const int *cells, const GridDesc &g, uint8_t *valid, float4 *coef,
-                          const int *skip_flag, hipStream_t s) {
-  if (M <= 0) return;
-  hipLaunchKernelGGL(k_line_features, dim3(cdiv((long long)M * FEAT_LPQ, 128)), dim3(128), 0, s, stack, M, slot_off, transform,
-                     Vec3<float>(fixed_pz[0], fixed_pz[1], fixed_pz[2]), min_match_sq_dis, map_sorted, cells, g, valid, coef, skip_flag);
   LIO_HIP(hipGetLastError());
 }
 

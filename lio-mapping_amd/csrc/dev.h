@@ -4,8 +4,10 @@
 #include <type_traits>
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -71,6 +73,29 @@ struct DBuf {
     p = np; cap = ncap;
   }
 };
+
+// Pinned host array: fixed size, the allocation flags are the caller's (coherent for completion words and landing zones that
+// kernels store to while the host polls).  The owner's destructor must have drained every stream that can still touch it.
+template <typename T>
+struct HostBuf {
+  T *p = nullptr;
+  size_t n = 0;
+  HostBuf() = default;
+  HostBuf(const HostBuf &) = delete;
+  HostBuf &operator=(const HostBuf &) = delete;
+  HostBuf(HostBuf &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+  HostBuf &operator=(HostBuf &&o) noexcept { if (this != &o) { release(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; } return *this; }
+  ~HostBuf() { release(); }
+  void release() { if (p) (void)hipHostFree(p); p = nullptr; n = 0; }
+  void alloc(size_t count, unsigned flags, bool zero = false) {
+    release();
+    LIO_HIP(hipHostMalloc(reinterpret_cast<void **>(&p), count * sizeof(T), flags));
+    n = count;
+    if (zero) std::memset(static_cast<void *>(p), 0, count * sizeof(T));
+  }
+};
+
+inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 struct Stopwatch {
   hipEvent_t a{}, b{};

@@ -85,6 +85,7 @@ class EstimatorBatch {
     int key_bits = 0;                          // bits the window's relative voxel keys took in its last solve (0: not known yet)
     size_t part_off = 0;                       // doubles into partials_
   };
+  void Init(), Close() noexcept;
   void FetchPrior(int w, int buf, MargPrior &pr);
   void Materialize(int w, int buf);
   std::vector<Estimator *> m_;
@@ -110,10 +111,10 @@ class EstimatorBatch {
   Slab lay_{};
   BatchClock clk_;
   // pinned staging (one entry per window)
-  BatchWin *h_win_ = nullptr; BatchGrid *h_grid_ = nullptr; BwVoxOut *h_vout_ = nullptr; OdomState *h_odom_ = nullptr;
-  BatchSolve *h_bs_ = nullptr; DevProblem *h_pb_ = nullptr; DevState *h_st_ = nullptr; DevMarg *h_mg_ = nullptr;
-  double *h_prior_ = nullptr;   // one ds_prior_mats_size(MARG_MAX_N) slot per window: priors on their way to the device
-  int *h_nconv_ = nullptr;
+  HostBuf<BatchWin> h_win_; HostBuf<BatchGrid> h_grid_; HostBuf<BwVoxOut> h_vout_; HostBuf<OdomState> h_odom_;
+  HostBuf<BatchSolve> h_bs_; HostBuf<DevProblem> h_pb_; HostBuf<DevState> h_st_; HostBuf<DevMarg> h_mg_;
+  HostBuf<double> h_prior_;   // one ds_prior_mats_size(MARG_MAX_N) slot per window: priors on their way to the device
+  HostBuf<int> h_nconv_;
   // device
   DBuf<BatchWin> d_win_; DBuf<BatchGrid> d_grid_; DBuf<BwVoxOut> d_vout_; DBuf<OdomState> d_odom_;
   DBuf<BatchSolve> d_bs_; DBuf<DevProblem> d_pb_; DBuf<DevState> d_st_; DBuf<DevMarg> d_mg_;
@@ -122,7 +123,7 @@ class EstimatorBatch {
   DBuf<uint32_t> keys_, keysb_, vals_, valsb_, ckeys_, sort_hist_;   // the segmented sort's ping-pong pairs (filter, then K-NN grid) and its histograms
   DBuf<SegDesc> d_seg_;
   DBuf<KeyLayout> d_layout_;
-  SegDesc *h_seg_ = nullptr;
+  HostBuf<SegDesc> h_seg_;
   DBuf<float> bounds_partial_, score_all_;
   DBuf<int> tile_heads_, range_overflow_, cells_all_, nconv_;
   DBuf<VoxParams> vparams_;

@@ -2,7 +2,6 @@
 // solve_kernels.hip (launch A / launch B of the trust-region loop), marg_kernels.hip (marginalization).
 #include "est_batch.h"
 
-#include <chrono>
 #include <exception>
 #include <string>
 #include <thread>
@@ -12,13 +11,15 @@
 
 namespace lio {
 
-static double bnow_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static int round_up(int v, int m) { return (v + m - 1) / m * m; }
-template <typename T> static void pinned(T *&p, size_t n) { LIO_HIP(hipHostMalloc(reinterpret_cast<void **>(&p), sizeof(T) * std::max<size_t>(n, 1))); std::memset(static_cast<void *>(p), 0, sizeof(T) * std::max<size_t>(n, 1)); }
 
 EstimatorBatch::EstimatorBatch(const std::vector<Estimator *> &members) : m_(members) {
+  // the argument checks come before anything is created: Close() walks m_ and the pinned staging is sized by B >= 1
   if (m_.empty()) throw std::runtime_error("EstimatorBatch: no windows");
   for (Estimator *e : m_) if (!e) throw std::runtime_error("EstimatorBatch: null window");
+  try { Init(); } catch (...) { Close(); throw; }   // (a constructor that throws does not run the destructor)
+}
+void EstimatorBatch::Init() {
   const size_t B = m_.size();
   // one device per batch: the members' buffers, this batch's streams and the kernels' per-device attributes (hipFuncSetAttribute
   // applies to the current device only) all belong to the device the windows were created on
@@ -39,8 +40,9 @@ EstimatorBatch::EstimatorBatch(const std::vector<Estimator *> &members) : m_(mem
   for (hipEvent_t &e : ev_grp_) LIO_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   win_.resize(B);
   for (size_t w = 0; w < B; ++w) { win_[w].e = m_[w]; m_[w]->AdoptStream(stream_); }
-  pinned(h_win_, B); pinned(h_grid_, B); pinned(h_vout_, B); pinned(h_odom_, B); pinned(h_bs_, B); pinned(h_pb_, B); pinned(h_st_, B); pinned(h_mg_, B);
-  pinned(h_prior_, B * ds_prior_mats_size(MARG_MAX_N)); pinned(h_nconv_, 4); pinned(h_seg_, 2 * B);
+  const auto pin = [](auto &h, size_t n) { h.alloc(n, hipHostMallocDefault, true); };   // zero-filled; B >= 1: no empty allocation
+  pin(h_win_, B); pin(h_grid_, B); pin(h_vout_, B); pin(h_odom_, B); pin(h_bs_, B); pin(h_pb_, B); pin(h_st_, B); pin(h_mg_, B);
+  pin(h_prior_, B * ds_prior_mats_size(MARG_MAX_N)); pin(h_nconv_, 4); pin(h_seg_, 2 * B);
   d_win_.reserve(B); d_grid_.reserve(B); d_vout_.reserve(B); d_odom_.reserve(B); d_bs_.reserve(B); d_pb_.reserve(B); d_st_.reserve(B); d_mg_.reserve(B);
   range_overflow_.reserve(B); vparams_.reserve(B); nconv_.reserve(4); d_seg_.reserve(2 * B); d_layout_.reserve(B);
   LIO_HIP(hipMemsetAsync(range_overflow_.p, 0, sizeof(int) * range_overflow_.cap, stream_));
@@ -61,21 +63,18 @@ EstimatorBatch::EstimatorBatch(const std::vector<Estimator *> &members) : m_(mem
   LIO_HIP(hipStreamSynchronize(stream_));
 }
 
-EstimatorBatch::~EstimatorBatch() {
+EstimatorBatch::~EstimatorBatch() { Close(); }
+void EstimatorBatch::Close() noexcept {   // (the pinned and device buffers are members: they go after this, when both streams have drained)
   try {
     if (stream_) (void)hipStreamSynchronize(stream_);
     if (stream_marg_) (void)hipStreamSynchronize(stream_marg_);
     for (size_t w = 0; w < win_.size(); ++w)
       for (int k = 0; k < 2; ++k) if (win_[w].dev_prior[k]) win_[w].dev_prior[k]->materialize();   // nobody may be left holding a shell
-    for (Estimator *e : m_) {
+    for (Estimator *e : m_) {   // (after a partial Init(): ReleaseAdoptedStream is a no-op for a member that was never adopted)
       e->solve_hook_ = nullptr; e->ReleaseAdoptedStream();
       if (e->feat_batch_ == this) { e->feat_batch_ = nullptr; e->feat_batch_w_ = -1; }   // (its getter falls back to the handle's own slots)
     }
   } catch (...) {}
-  for (void *p : {static_cast<void *>(h_win_), static_cast<void *>(h_grid_), static_cast<void *>(h_vout_), static_cast<void *>(h_odom_), static_cast<void *>(h_bs_),
-                  static_cast<void *>(h_pb_), static_cast<void *>(h_st_), static_cast<void *>(h_mg_), static_cast<void *>(h_prior_), static_cast<void *>(h_nconv_),
-                  static_cast<void *>(h_seg_)})
-    if (p) (void)hipHostFree(p);
   for (hipEvent_t e : ev_) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ev_wait_) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : ev_k_) if (e) (void)hipEventDestroy(e);
@@ -169,8 +168,8 @@ void EstimatorBatch::StageDigest(int stage, unsigned long long *out) {
   for (hipStream_t g : stream_grp_) LIO_HIP(hipStreamSynchronize(g));
   const int B = size();
   for (int w = 0; w < B; ++w) {
-    const BatchWin &bw = h_win_[w];
-    const BatchGrid &G = h_grid_[w];
+    const BatchWin &bw = h_win_.p[w];
+    const BatchGrid &G = h_grid_.p[w];
     unsigned long long h = 0;
     switch (stage) {
       case 0: {
@@ -206,7 +205,7 @@ void EstimatorBatch::StageDigest(int stage, unsigned long long *out) {
       case 4: { const std::vector<OdomState> o = fetch(d_odom_.p + w, 1); h = fnv1a(o.data(), sizeof(OdomState)); break; }
       case 5: { const std::vector<DevState> o = fetch(d_st_.p + w, 1); h = fnv1a(o.data(), sizeof(DevState)); break; }
       case 8: {   // scaled H at the accepted point (upper triangle), + on stderr whether it is positive definite
-        const DevProblem &pb = h_pb_[w];
+        const DevProblem &pb = h_pb_.p[w];
         const int n = pb.n, ld = pb.ld;
         const std::vector<double> Hc = fetch(slab_.p + size_t(w) * lay_.total + lay_.Hcur, size_t(pb.n_pad) * ld);
         h = mix64(n);
@@ -230,11 +229,11 @@ void EstimatorBatch::StageDigest(int stage, unsigned long long *out) {
       }
       case 9: {   // marginalization: sweeps and phase stamps of the last launch (stderr under LIO_DEBUG_DIGEST); digest of the new prior
         const std::vector<double> mi = fetch(slab_.p + size_t(w) * lay_.total + lay_.marg_info, MARG_MAX_N + 24);
-        const std::vector<double> pm = fetch(slab_.p + size_t(w) * lay_.total + lay_.prior[1 - win_[w].cur], ds_prior_mats_size(h_mg_[w].n));
-        h = fnv1a(pm.data(), pm.size() * sizeof(double), mix64(h_mg_[w].n));
+        const std::vector<double> pm = fetch(slab_.p + size_t(w) * lay_.total + lay_.prior[1 - win_[w].cur], ds_prior_mats_size(h_mg_.p[w].n));
+        h = fnv1a(pm.data(), pm.size() * sizeof(double), mix64(h_mg_.p[w].n));
         if (std::getenv("LIO_DEBUG_DIGEST") && (w == 0 || w == B - 1))
           std::fprintf(stderr, "[digest] window %d marginalization: m %d n %d QL sweeps %g / %g; shader clocks: assembly %.0f, Amm eig %.0f, pinv + T + S %.0f, S eig %.0f, factors out %.0f, J^T J %.0f\n",
-                       w, h_mg_[w].m, h_mg_[w].n, mi[0], mi[1], mi[MARG_MAX_N + 9] - mi[MARG_MAX_N + 8], mi[MARG_MAX_N + 10] - mi[MARG_MAX_N + 9], mi[MARG_MAX_N + 11] - mi[MARG_MAX_N + 10], mi[MARG_MAX_N + 12] - mi[MARG_MAX_N + 11],
+                       w, h_mg_.p[w].m, h_mg_.p[w].n, mi[0], mi[1], mi[MARG_MAX_N + 9] - mi[MARG_MAX_N + 8], mi[MARG_MAX_N + 10] - mi[MARG_MAX_N + 9], mi[MARG_MAX_N + 11] - mi[MARG_MAX_N + 10], mi[MARG_MAX_N + 12] - mi[MARG_MAX_N + 11],
                        mi[MARG_MAX_N + 13] - mi[MARG_MAX_N + 12], mi[MARG_MAX_N + 14] - mi[MARG_MAX_N + 13]);
         if (std::getenv("LIO_DEBUG_DIGEST") && w == 0 && mi[MARG_MAX_N + 16] != 0.0)
           std::fprintf(stderr, "[digest] S eig, thread 0: reduction %.0f, QL %.0f of which wave 0's recurrence %.0f, its waits at the sweeps' barriers %.0f\n", mi[MARG_MAX_N + 16], mi[MARG_MAX_N + 19], mi[MARG_MAX_N + 17], mi[MARG_MAX_N + 18]);
@@ -274,7 +273,7 @@ size_t EstimatorBatch::GetFeatures(int w, int frame, double *pt, double *co, dou
   const Estimator *e = win_[size_t(w)].e;
   if (frame < 0 || frame > e->W_ || e->nslots_[frame] == 0) return 0;
   Sync();
-  const size_t off = size_t(h_win_[w].slot_base) + size_t(e->slot_off_[frame]), ns = size_t(e->nslots_[frame]);
+  const size_t off = size_t(h_win_.p[w].slot_base) + size_t(e->slot_off_[frame]), ns = size_t(e->nslots_[frame]);
   const size_t M = e->stacks_[frame].n;
   const std::vector<uint8_t> v = fetch(valid_all_.p + off, ns);
   const std::vector<float4> c = fetch(coef_all_.p + off, ns);
@@ -293,7 +292,7 @@ size_t EstimatorBatch::GetFeatures(int w, int frame, double *pt, double *co, dou
 }
 
 int EstimatorBatch::Solve(lio_solve_report *reps) {
-  const double t0 = bnow_ms();
+  const double t0 = now_ms();
   const int B = size();
   hipStream_t s = stream_;
   std::vector<lio_solve_report> local;
@@ -308,7 +307,7 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
   for (int w = 0; w < B; ++w) {
     Win &Wn = win_[w];
     Estimator *e = Wn.e;
-    BatchWin &bw = h_win_[w];
+    BatchWin &bw = h_win_.p[w];
     Wn.device = e->BatchEligible();
     Wn.prior_used.reset();
     if (Wn.device) {
@@ -333,11 +332,11 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
   bounds_partial_.reserve(N / 256 * 8, s); tile_heads_.reserve(N / 256, s);
   valid_all_.reserve(std::max(slot, 16), s); coef_all_.reserve(std::max(slot, 16), s); score_all_.reserve(std::max(slot, 16), s);
   odom_partials_.reserve(size_t(std::max(part_rows, 1)) * 28, s);
-  const double t1 = bnow_ms();
+  const double t1 = now_ms();
   clk_.describe = t1 - t0;
   // ------------------------------------------------------------------------------------------------ BuildLocalMap
   LIO_HIP(hipEventRecord(ev_[0], s));
-  LIO_HIP(hipMemcpyAsync(d_win_.p, h_win_, sizeof(BatchWin) * B, hipMemcpyHostToDevice, s));
+  LIO_HIP(hipMemcpyAsync(d_win_.p, h_win_.p, sizeof(BatchWin) * B, hipMemcpyHostToDevice, s));
   LIO_HIP(hipMemsetAsync(nconv_.p, 0, sizeof(int), s));
   launch_bw_setup(d_win_.p, B, max_slots, valid_all_.p, d_odom_.p, nconv_.p, s);
   // The filter's order: 9-bit passes over the keys relative to each window's bounds (pass 0 converts the stored absolute keys on the fly
@@ -351,8 +350,8 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
                         std::min(31, SS_MAX_BITS * vox_passes - 1), s);
   const uint32_t *keys_sorted = nullptr, *vals_sorted = nullptr;
   {
-    SegDesc *seg = h_seg_;
-    for (int w = 0; w < B; ++w) seg[w] = SegDesc{h_win_[w].loc_off, h_win_[w].n_local, 0};
+    SegDesc *seg = h_seg_.p;
+    for (int w = 0; w < B; ++w) seg[w] = SegDesc{h_win_.p[w].loc_off, h_win_.p[w].n_local, 0};
     const SegSortPlan plan = seg_sort_plan(seg, B, SS_MAX_BITS);
     sort_hist_.reserve(std::max<size_t>(plan.hist_entries, 1), s);
     LIO_HIP(hipMemcpyAsync(d_seg_.p, seg, sizeof(SegDesc) * B, hipMemcpyHostToDevice, s));
@@ -367,19 +366,19 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
     keys_sorted = ki; vals_sorted = vi;
   }
   launch_bw_vox_finish(d_win_.p, B, max_cap, local_all_.p, keys_sorted, vals_sorted, tile_heads_.p, filtered_all_.p, vparams_.p, range_overflow_.p, d_vout_.p, s);
-  LIO_HIP(hipMemcpyAsync(h_vout_, d_vout_.p, sizeof(BwVoxOut) * B, hipMemcpyDeviceToHost, s));
+  LIO_HIP(hipMemcpyAsync(h_vout_.p, d_vout_.p, sizeof(BwVoxOut) * B, hipMemcpyDeviceToHost, s));
   LIO_HIP(hipEventRecord(ev_[1], s));
   LIO_HIP(hipStreamSynchronize(s));
-  const double t2 = bnow_ms();
+  const double t2 = now_ms();
   clk_.map = t2 - t1;
   // ------------------------------------------------------------------------------------------------ K-NN grids, features, rounds
   size_t cell_total = 0;
   int max_filtered = 0;
   for (int w = 0; w < B; ++w) {
     Win &Wn = win_[w];
-    BatchGrid &G = h_grid_[w];
+    BatchGrid &G = h_grid_.p[w];
     std::memset(&G, 0, sizeof(G));
-    const BwVoxOut &vo = h_vout_[w];
+    const BwVoxOut &vo = h_vout_.p[w];
     size_t ncells = 1;
     G.g.dims[0] = G.g.dims[1] = G.g.dims[2] = 1;
     G.g.inv_cell = 1.f;
@@ -407,15 +406,15 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
   }
   if (cell_total > size_t(INT_MAX)) throw std::runtime_error("EstimatorBatch: the batch's cell tables exceed 2^31 entries");
   cells_all_.reserve(cell_total, s);
-  LIO_HIP(hipMemcpyAsync(d_grid_.p, h_grid_, sizeof(BatchGrid) * B, hipMemcpyHostToDevice, s));
+  LIO_HIP(hipMemcpyAsync(d_grid_.p, h_grid_.p, sizeof(BatchGrid) * B, hipMemcpyHostToDevice, s));
   launch_bw_cell_keys(d_win_.p, d_grid_.p, B, max_filtered, filtered_all_.p, ckeys_.p, s);
   {
     // a window's filtered points ordered by cell: as many 9-bit passes as the largest table's index needs
-    SegDesc *seg = h_seg_ + B;
+    SegDesc *seg = h_seg_.p + B;
     int bits = 1;
     for (int w = 0; w < B; ++w) {
-      seg[w] = SegDesc{h_win_[w].loc_off, h_grid_[w].n_filtered, 0};
-      const long long nc = (long long)h_grid_[w].g.dims[0] * h_grid_[w].g.dims[1] * h_grid_[w].g.dims[2];
+      seg[w] = SegDesc{h_win_.p[w].loc_off, h_grid_.p[w].n_filtered, 0};
+      const long long nc = (long long)h_grid_.p[w].g.dims[0] * h_grid_.p[w].g.dims[1] * h_grid_.p[w].g.dims[2];
       while ((1ll << bits) < nc) ++bits;
     }
     const int passes = std::max(1, (bits + SS_MAX_BITS - 1) / SS_MAX_BITS);
@@ -441,7 +440,7 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
   // ---- while the device searches: the problems of Estimator.cc:1660-1921, packed for the device loop.  Their uploads overwrite
   // what the previous solve's marginalization (on its own stream) still reads: everything enqueued from here on waits for it —
   // it has had this solve's filter, grids, features and first rounds to finish.
-  const double t3a = bnow_ms();
+  const double t3a = now_ms();
   ev_wait_valid_ = false;
   if (marg_in_flight_) {
     LIO_HIP(hipEventRecord(ev_wait_[0], s));
@@ -460,10 +459,10 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
     for (int i = e->W_ - e->Wo_ + 1; i <= e->W_; ++i) ms = std::max(ms, e->nslots_[i]);
     Wn.max_slots = ms;
     Wn.bpf = batch_blocks_per_frame(ms);
-    if (e->total_slots_ == 0 || !e->BatchPackProblem(Wn.bpf, h_pb_[w], h_st_[w], &Wn.prior_used)) { Wn.device = false; continue; }
+    if (e->total_slots_ == 0 || !e->BatchPackProblem(Wn.bpf, h_pb_.p[w], h_st_.p[w], &Wn.prior_used)) { Wn.device = false; continue; }
     Wn.part_off = part_total;
     part_total += size_t(e->Wo_) * Wn.bpf * LIO_MOMENT_OUT;
-    max_bpf = std::max(max_bpf, Wn.bpf); max_wo = std::max(max_wo, e->Wo_); max_npad = std::max(max_npad, h_pb_[w].n_pad);
+    max_bpf = std::max(max_bpf, Wn.bpf); max_wo = std::max(max_wo, e->Wo_); max_npad = std::max(max_npad, h_pb_.p[w].n_pad);
     // the prior's matrices on the device: already there (the previous solve's marginalization left them, or an earlier upload), or sent now
     if (Wn.prior_used) {
       int k = -1;
@@ -474,7 +473,7 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
         MargPrior &pr = *Wn.prior_used;
         pr.materialize();
         const size_t n = size_t(pr.n);
-        double *h = h_prior_ + size_t(w) * ds_prior_mats_size(MARG_MAX_N);
+        double *h = h_prior_.p + size_t(w) * ds_prior_mats_size(MARG_MAX_N);
         std::memcpy(h, pr.JtJ.a.data(), sizeof(double) * n * n);
         std::memcpy(h + n * n, pr.lin_jac.a.data(), sizeof(double) * n * n);
         std::memcpy(h + 2 * n * n, pr.lin_res.data(), sizeof(double) * n);
@@ -487,36 +486,36 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
       Wn.cur = 0;
     }
   }
-  LIO_HIP(hipMemcpyAsync(d_pb_.p, h_pb_, sizeof(DevProblem) * B, hipMemcpyHostToDevice, s));
-  LIO_HIP(hipMemcpyAsync(d_st_.p, h_st_, sizeof(DevState) * B, hipMemcpyHostToDevice, s));
-  clk_.pack = bnow_ms() - t3a;
+  LIO_HIP(hipMemcpyAsync(d_pb_.p, h_pb_.p, sizeof(DevProblem) * B, hipMemcpyHostToDevice, s));
+  LIO_HIP(hipMemcpyAsync(d_st_.p, h_st_.p, sizeof(DevState) * B, hipMemcpyHostToDevice, s));
+  clk_.pack = now_ms() - t3a;
   // ---- the remaining rounds, with a look at the number of converged windows every second round
   for (; round < 10; ++round) {
     if (round >= 3 && round % 2 == 1) {
-      LIO_HIP(hipMemcpyAsync(h_nconv_, nconv_.p, sizeof(int), hipMemcpyDeviceToHost, s));
+      LIO_HIP(hipMemcpyAsync(h_nconv_.p, nconv_.p, sizeof(int), hipMemcpyDeviceToHost, s));
       LIO_HIP(hipStreamSynchronize(s));
-      if (*h_nconv_ >= B) break;
+      if (*h_nconv_.p >= B) break;
     }
     launch_bw_odom_round(d_win_.p, d_grid_.p, B, max_nb, q_newest, knobs_, round, d_odom_.p, sorted_all_.p, cells_all_.p, valid_all_.p, coef_all_.p, score_all_.p, odom_partials_.p,
                          nconv_.p, s);
   }
   clk_.rounds = round;
   LIO_HIP(hipEventRecord(ev_[4], s));
-  LIO_HIP(hipMemcpyAsync(h_odom_, d_odom_.p, sizeof(OdomState) * B, hipMemcpyDeviceToHost, s));
+  LIO_HIP(hipMemcpyAsync(h_odom_.p, d_odom_.p, sizeof(OdomState) * B, hipMemcpyDeviceToHost, s));
   LIO_HIP(hipStreamSynchronize(s));
-  const double t3 = bnow_ms();
+  const double t3 = now_ms();
   clk_.grid_features = t3 - t2;
   // ------------------------------------------------------------------------------------------------ the trust-region loop
   partials_.reserve(std::max<size_t>(part_total, 1), s);
   int max_it = 0, n_dev = 0;
   for (int w = 0; w < B; ++w) {
     Win &Wn = win_[w];
-    BatchSolve &S = h_bs_[w];
+    BatchSolve &S = h_bs_.p[w];
     std::memset(static_cast<void *>(&S), 0, sizeof(S));
     S.marg = d_mg_.p + w;
     if (!Wn.device) continue;
     Estimator *e = Wn.e;
-    e->BatchSetOdom(h_odom_[w]);
+    e->BatchSetOdom(h_odom_.p[w]);
     const int pivot = e->W_ - e->Wo_;
     double *slab = slab_.p + size_t(w) * lay_.total;
     S.active = 1; S.nframes = e->Wo_; S.bpf = Wn.bpf;
@@ -524,7 +523,7 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
       MomentFrame &f = S.fr[i - 1];
       const int idx = pivot + i;
       f.stack = e->stacks_[idx].buf.p; f.M = std::max<int>(1, int(e->stacks_[idx].n));
-      f.slot_off = h_win_[w].slot_base + e->slot_off_[idx]; f.nslots = e->nslots_[idx]; f.slot_begin = 0; f.slot_end = f.nslots;
+      f.slot_off = h_win_.p[w].slot_base + e->slot_off_[idx]; f.nslots = e->nslots_[idx]; f.slot_begin = 0; f.slot_end = f.nslots;
     }
     S.pb = d_pb_.p + w; S.st = d_st_.p + w;
     S.prior_mats = slab + lay_.prior[Wn.cur]; S.next_prior_mats = slab + lay_.prior[1 - Wn.cur];
@@ -537,7 +536,7 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
     max_it = std::max(max_it, e->cfg_.max_num_iterations);
     ++n_dev;
   }
-  LIO_HIP(hipMemcpyAsync(d_bs_.p, h_bs_, sizeof(BatchSolve) * B, hipMemcpyHostToDevice, s));
+  LIO_HIP(hipMemcpyAsync(d_bs_.p, h_bs_.p, sizeof(BatchSolve) * B, hipMemcpyHostToDevice, s));
   if (n_dev > 0) {
     // iteration k evaluates candidate k (k = 0: the initial point); a window that is done costs its blocks one load each.
     // Groups of windows run their chains side by side (see est_batch.h); one group below 32 windows.
@@ -563,7 +562,7 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
       for (int w = q.w0; w < q.w1; ++w) {
         if (!win_[w].device) continue;
         const Estimator *e = win_[w].e;
-        q.bpf = std::max(q.bpf, win_[w].bpf); q.wo = std::max(q.wo, e->Wo_); q.npad = std::max(q.npad, h_pb_[w].n_pad);
+        q.bpf = std::max(q.bpf, win_[w].bpf); q.wo = std::max(q.wo, e->Wo_); q.npad = std::max(q.npad, h_pb_.p[w].n_pad);
         q.it = std::max(q.it, e->cfg_.max_num_iterations); ++q.n;
       }
       if (q.n > 0) it_max = std::max(it_max, q.it);
@@ -589,20 +588,20 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
         } else {
           launch_bw_solve_iteration(gb, bases, w1 - w0, g_bpf, g_wo, g_npad, knobs_.aux_threads, valid_all_.p, coef_all_.p, sg);
         }
-        if (h_bs_[0].prof && w0 == 0 && k == prof_it)   // LIO_DEBUG_TIMING: keep the stamps of this iteration's launch B beside the last one's
-          LIO_HIP(hipMemcpyAsync(h_bs_[0].prof + 32, h_bs_[0].prof, 32 * sizeof(long long), hipMemcpyDeviceToDevice, sg));
+        if (h_bs_.p[0].prof && w0 == 0 && k == prof_it)   // LIO_DEBUG_TIMING: keep the stamps of this iteration's launch B beside the last one's
+          LIO_HIP(hipMemcpyAsync(h_bs_.p[0].prof + 32, h_bs_.p[0].prof, 32 * sizeof(long long), hipMemcpyDeviceToDevice, sg));
       }
     if (G > 1)
       for (int g = 0; g < G; ++g) { LIO_HIP(hipEventRecord(ev_grp_[g], grp[g].sg)); LIO_HIP(hipStreamWaitEvent(s, ev_grp_[g], 0)); }
     LIO_HIP(hipEventRecord(ev_[5], s));
-    LIO_HIP(hipMemcpyAsync(h_st_, d_st_.p, sizeof(DevState) * B, hipMemcpyDeviceToHost, s));
+    LIO_HIP(hipMemcpyAsync(h_st_.p, d_st_.p, sizeof(DevState) * B, hipMemcpyDeviceToHost, s));
     LIO_HIP(hipStreamSynchronize(s));
   } else {
     LIO_HIP(hipEventRecord(ev_[5], s));
   }
-  if (h_bs_[0].prof) {   // LIO_DEBUG_TIMING: the phase stamps of window 0's last launch B (shader clock, 100 MHz wall clock is not used here)
+  if (h_bs_.p[0].prof) {   // LIO_DEBUG_TIMING: the phase stamps of window 0's last launch B (shader clock, 100 MHz wall clock is not used here)
     long long pr[96];
-    LIO_HIP(hipMemcpy(pr, h_bs_[0].prof, sizeof(pr), hipMemcpyDeviceToHost));
+    LIO_HIP(hipMemcpy(pr, h_bs_.p[0].prof, sizeof(pr), hipMemcpyDeviceToHost));
     for (int half = 1; half >= 0; --half) {
       std::fprintf(stderr, "[lio_hip timing] launch B of window 0, %s, clock64 ticks from its start:", half ? "iteration LIO_DEBUG_TIMING_IT (default 3)" : "last launch");
       for (int k = 0; k < 32; ++k) std::fprintf(stderr, " P%d %lld", k, pr[32 * half + k] ? pr[32 * half + k] - pr[32 * half] : -1);
@@ -612,7 +611,7 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
                  pr[65] - pr[64], pr[66] - pr[65], pr[67] - pr[66], pr[68] - pr[67]);
   }
   clk_.iterations = max_it + 1;
-  const double t4 = bnow_ms();
+  const double t4 = now_ms();
   clk_.solve = t4 - t3;
   // ------------------------------------------------------------------------------------------------ write-back, marginalization
   int max_n = 1, n_marg = 0;
@@ -624,10 +623,10 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
   auto finish_range = [&](int w0, int w1) {
     for (int w = w0; w < w1; ++w) {
       Win &Wn = win_[w];
-      DevMarg &mg = h_mg_[w];
+      DevMarg &mg = h_mg_.p[w];
       std::memset(&mg, 0, sizeof(mg));
       if (!Wn.device) continue;
-      const DevState &st = h_st_[w];
+      const DevState &st = h_st_.p[w];
       if (st.need_host || !st.started) continue;
       margs[w] = Wn.e->BatchFinish(st, Wn.prior_used, reps[w], mg, &shells[w]) ? 1 : 0;
     }
@@ -650,7 +649,7 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
   for (int w = 0; w < B; ++w) {
     Win &Wn = win_[w];
     if (!Wn.device) { host_path.push_back(w); continue; }
-    const DevState &st = h_st_[w];
+    const DevState &st = h_st_.p[w];
     if (st.need_host || !st.started) { Wn.device = false; host_path.push_back(w); continue; }
     if (margs[w]) {
       const int nb = 1 - Wn.cur;
@@ -660,7 +659,7 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
       shell->fetch = [this, w, nb](MargPrior &pr) { FetchPrior(w, nb, pr); };
       Wn.dev_prior[nb] = shell;
       Wn.e->last_marg_ = shell;
-      max_n = std::max(max_n, h_mg_[w].n);
+      max_n = std::max(max_n, h_mg_.p[w].n);
       ++n_marg;
     }
     Wn.prior_used.reset();
@@ -668,19 +667,19 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
   clk_.n_device = B - int(host_path.size()); clk_.n_host = int(host_path.size());
   if (n_marg > 0) {
     // (the host has waited for the loop; the marginalization's inputs — final moments, states, problems — are complete)
-    LIO_HIP(hipMemcpyAsync(d_mg_.p, h_mg_, sizeof(DevMarg) * B, hipMemcpyHostToDevice, stream_marg_));
+    LIO_HIP(hipMemcpyAsync(d_mg_.p, h_mg_.p, sizeof(DevMarg) * B, hipMemcpyHostToDevice, stream_marg_));
     launch_bw_marginalize(d_bs_.p, BatchBases{slab_.p, partials_.p, d_st_.p, d_pb_.p, d_mg_.p}, B, max_wo, max_n, stream_marg_);
     LIO_HIP(hipEventRecord(ev_marg_, stream_marg_));
     marg_in_flight_ = true;
   }
   LIO_HIP(hipEventRecord(ev_[6], stream_marg_));
   ev_valid_ = true;
-  const double t5 = bnow_ms();
+  const double t5 = now_ms();
   clk_.finish = t5 - t4;
   // ------------------------------------------------------------------------------------------------ windows the device loop did not take
   for (int w = 0; w < B; ++w) ok_[size_t(w)] = 1;
   for (int w : host_path) ok_[size_t(w)] = win_[w].e->SolveOptimizationHost(&reps[w]) ? 1 : 0;
-  const double t6 = bnow_ms();
+  const double t6 = now_ms();
   clk_.fallback = t6 - t5;
   clk_.total = t6 - t0;
   for (int w = 0; w < B; ++w) {

@@ -16,6 +16,7 @@
 #include "host_init.h"
 #include "host_solver.h"
 #include "batch_kernels.h"
+#include "resident_moments.h"
 #include "solve_step.h"
 
 namespace lio {
@@ -254,9 +255,15 @@ class Estimator {
   void *allreduce_user_ = nullptr;
   void *rccl_comm_ = nullptr;               // ncclComm_t (lio_est_set_factor_sharding_rccl): the all-reduce runs on stream_, in HBM
   bool Sharded() const { return shard_world_ > 1 && (allreduce_ || rccl_comm_); }
+  // begun lazily by the first LidarLaunchMoments of a solve scope, stopped when the scope closes.  Public for the C entry points, which
+  // use ForcePerLane, LaunchTiming, LaunchStats and BusyUs only; the protocol calls (Open .. End) are the estimator's
+  ResidentMoments resident_;
+  hipStream_t stream() const { return stream_; }
 
  private:
   friend class EstimatorBatch;
+  struct ResidentScope { Estimator *e; ~ResidentScope() { e->resident_.End(e->stream_); } };   // closes a solve scope on every exit path
+  void Init(), Close() noexcept;
   struct HostState;  // snapshot payload
   Rigidd LidarPose(int i, const Rigidd &lb) const;
   Rigidf RelTransform(int i, const Rigidd &T_pivot, const Rigidd &lb) const;
@@ -296,54 +303,11 @@ class Estimator {
   DBuf<float> d_transforms_;
   DBuf<OdomState> d_odom_;
   DBuf<double> d_odom_partials_, d_moment_partials_, d_moment_out_;
-  // Resident moments (solve_kernels.h): one launch per solve; every linearisation is a doorbell write + a spin on
-  // the blocks' completion words.  Begun lazily by the first LidarLaunch of a SolveOptimization, stopped when it returns.
-  bool resident_moments_ = true;    // configured (lio_est_config.resident_moments)
-  bool resident_never_ = false;     // resident_moments = 3: the resident form's partition, launch pairs only (what a refused solve gets)
-  int res_per_lane_ = 0;            // residuals a lane keeps in registers: 0 = chosen per window (ResidentBpf), lio_est_force_moments_per_lane forces 1, 2, 4, 8
-  int res_lanes_ = 4;               // ... of the launch in flight
-  bool res_allowed_ = false;        // inside SolveOptimization
-  bool res_active_ = false;         // a resident kernel is waiting on the doorbell
-  int res_bpf_ = 0, res_nframes_ = 0;
-  unsigned res_seq_ = 0;            // sequence number of the last pass rung (monotonic over the life of the handle)
-  int res_relaunches_ = 0;          // launches that replaced an expired one within this solve (bounded: ResidentAwaitWord)
-  unsigned res_launch_seq_ = 0;     // first sequence number of the launch in flight (its STOP value is derived from it)
-  double *h_res_door_ = nullptr, *h_res_out_ = nullptr;    // coherent pinned host memory: doorbell, per-frame folded records
-  unsigned *h_res_words_ = nullptr;
-  long long res_timeout_ticks_ = 0;
-  double res_tick_us_ = 0.01;       // microseconds per wall-clock tick
-  double res_busy_us_ = 0, res_bytes_ = 0; int res_passes_ = 0, res_passes_total_ = 0;   // device-side busy time of the passes (doorbell copy seen -> sums posted), SURVEY 8(d) bytes
-  MomentArgs res_args_{};
-  DBuf<double> d_res_relay_, d_res_part_;   // HBM: the doorbell as republished by the relay block; the per-block records
-  // lio_est_enable_kernel_timing(-1): HIP events around every launch of the resident kernel (it stays in use, unlike under
-  // the per-kernel timing of on >= 1): its dispatch-to-exit span, which is what rocprofv3 reports for it
-  bool res_time_launch_ = false;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> res_launch_events_;
-  double res_launch_ms_ = 0; int res_launches_ = 0;
- public:
-  void ResidentLaunchTiming(bool on) { res_time_launch_ = on; }
-  void ForceResidentPerLane(int per_lane) { res_per_lane_ = per_lane; }   // lio_est_force_moments_per_lane (0: ResidentBpf's rule)
-  int ResidentLaunchStats(double *total_ms);
- private:
-  double res_diag_us_[4] = {0, 0, 0, 0}, res_polls_ = 0, res_relay_us_ = 0, res_ring_to_done_ms_ = 0, res_t_ring_ = 0, res_echo_ms_ = 0;
-  int ResidentBpf(int max_slots, int nframes, int *per_lane = nullptr) const;
-  bool ResidentBegin(const MomentArgs &ma);
-  void ResidentRing(const MomentArgs &ma);
-  void ResidentWait(std::vector<FrameMoments> &m);
-  void ResidentWaitFrame(int f, FrameMoments &fm);   // frame f (0-based) of the pass in flight, as soon as its word is in
-  void ResidentAwaitWord(int f);
-  void ResidentUnpackFrame(int f, FrameMoments &fm);
-  void ResidentPassDone();
-  void ResidentLaunchKernel(unsigned first_seq);
- public:
-  void ResidentEnd();
-  double ResidentBusyUs(int *passes, double *bytes) const { if (passes) *passes = res_passes_total_; if (bytes) *bytes = res_bytes_; return res_busy_us_; }
- private:
-  double *h_moment_out_ = nullptr;  // pinned
-  OdomState *h_odom_ = nullptr;     // pinned landing zone of the laser-odom state peeks
+  HostBuf<double> h_moment_out_;    // pinned, coherent
+  HostBuf<OdomState> h_odom_;       // pinned, coherent landing zone of the laser-odom state peeks
   // Completion words (dev.h: HostSignal) in coherent pinned memory: [0, 96) one per block of k_moment_reduce, [128] the
   // newest-frame round.  The host spins on them instead of hipStreamSynchronize (lio_est_config.stream_sync restores the synchronize calls).
-  unsigned *h_signal_ = nullptr;
+  HostBuf<unsigned> h_signal_;
   unsigned signal_seq_[2] = {0, 0};
   bool host_signal_ = true;
   int device_id_ = 0;

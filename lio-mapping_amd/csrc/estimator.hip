@@ -9,13 +9,11 @@
 #include <atomic>
 #include <cfloat>
 #include <climits>
-#include <chrono>
 #include <cstring>
 
 namespace lio {
 
 static const bool g_debug_timing = std::getenv("LIO_DEBUG_TIMING") != nullptr;   // read once: the solve is a hot path
-static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // math_utils.h:186-232 (degrees)
 static V3d R2ypr(const M3d &R) {
@@ -64,6 +62,9 @@ struct Estimator::HostState {
 };
 
 Estimator::Estimator(const EstConfig &cfg) : cfg_(cfg), W_(cfg.W), Wo_(cfg.Wo) {
+  try { Init(); } catch (...) { Close(); throw; }   // (a constructor that throws does not run the destructor)
+}
+void Estimator::Init() {
   int ndev = 0;
   LIO_HIP(hipGetDeviceCount(&ndev));
   if (ndev <= 0) throw DeviceError("no HIP device: the product has no CPU path");
@@ -71,16 +72,16 @@ Estimator::Estimator(const EstConfig &cfg) : cfg_(cfg), W_(cfg.W), Wo_(cfg.Wo) {
   LIO_HIP(hipStreamCreate(&stream2_));
   LIO_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
   LIO_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
-  transform_lb_ = cfg.transform_lb;
+  transform_lb_ = cfg_.transform_lb;
   Ps_.assign(W_ + 1, V3d()); Vs_ = Bas_ = Bgs_ = Ps_;
   Rs_.assign(W_ + 1, M3d::identity());
   pre_integrations_.assign(W_ + 1, nullptr);
   stacks_.resize(W_ + 1);
   size_surf_stack_.assign(W_ + 1, 0);
   slot_off_.assign(W_ + 1, 0); nslots_.assign(W_ + 1, 0);
-  g_vec_ = V3d(0, 0, -cfg.pim.g_norm);
+  g_vec_ = V3d(0, 0, -cfg_.pim.g_norm);
   all_laser_transforms_.assign(W_ + 1, LaserFrame());
-  extrinsic_stage_ = cfg.extrinsic_stage;
+  extrinsic_stage_ = cfg_.extrinsic_stage;
   R_WI_ = M3d::identity();
   // ClearState (Estimator.cc:234-288): the running pre-integration exists before the first IMU sample
   tmp_pre_integration_ = std::make_shared<Preintegration>(acc_last_, gyr_last_, Bas_[0], Bgs_[0], cfg_.pim);
@@ -89,45 +90,21 @@ Estimator::Estimator(const EstConfig &cfg) : cfg_(cfg), W_(cfg.W), Wo_(cfg.Wo) {
   LIO_HIP(hipMemset(d_moment_out_.p, 0, sizeof(double) * LIO_MAX_FRAMES * LIO_MOMENT_OUT));   // the two pad entries per frame stay zero under the all-reduce
   LIO_HIP(hipDeviceSynchronize());   // the memsets above run on the null stream; the kernels that read them on streams of our own
   // Execution switches: lio_est_config's trailing block.
-  async_marg_ = !cfg.inline_marg;
-  host_signal_ = !cfg.stream_sync;
-  resident_moments_ = cfg.resident_moments != 2;
-  resident_never_ = cfg.resident_moments == 3;
-  d_res_relay_.reserve(size_t(LIO_MAX_FRAMES) * LIO_RES_DOOR);
-  LIO_HIP(hipMemset(d_res_relay_.p, 0, sizeof(double) * LIO_MAX_FRAMES * LIO_RES_DOOR));
-  d_res_part_.reserve(size_t(LIO_RES_MAX_BLOCKS) * LIO_MOMENT_OUT);
-  LIO_HIP(hipMemset(d_res_part_.p, 0, sizeof(double) * LIO_RES_MAX_BLOCKS * LIO_MOMENT_OUT));   // flags: no pass has sequence number 0
-  LIO_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_res_door_), sizeof(double) * LIO_MAX_FRAMES * LIO_RES_DOOR, hipHostMallocCoherent));
-  LIO_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_res_out_), sizeof(double) * LIO_MAX_FRAMES * LIO_RES_OUT, hipHostMallocCoherent));
-  LIO_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_res_words_), sizeof(unsigned) * (LIO_MAX_FRAMES + 2), hipHostMallocCoherent));   // + the relay block's word + its echo
-  std::memset(h_res_door_, 0, sizeof(double) * LIO_MAX_FRAMES * LIO_RES_DOOR);
-  std::memset(h_res_words_, 0, sizeof(unsigned) * (LIO_MAX_FRAMES + 2));
-  std::memset(h_res_out_, 0, sizeof(double) * LIO_MAX_FRAMES * LIO_RES_OUT);   // the diagnostic slots are read whether or not the kernel fills them
-  {
-    int khz = 0, dev = 0;
-    LIO_HIP(hipGetDevice(&dev));
-    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0) khz = 100000;   // 100 MHz on gfx9
-    res_tick_us_ = 1e3 / double(khz);
-    res_timeout_ticks_ = (long long)(0.2 * 1e3 * khz);   // 200 ms without a doorbell: the block posts LIO_RES_EXPIRED and exits
-  }
+  async_marg_ = !cfg_.inline_marg;
+  host_signal_ = !cfg_.stream_sync;
+  resident_.Init(cfg_.resident_moments);
   // coherent (fine-grained): kernels store results and completion words here and the host reads them while the stream is live
-  LIO_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_moment_out_), sizeof(double) * LIO_MAX_FRAMES * LIO_MOMENT_OUT, hipHostMallocCoherent));
-  LIO_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_odom_), sizeof(OdomState), hipHostMallocCoherent));
-  LIO_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_signal_), 256 * sizeof(unsigned), hipHostMallocCoherent));
-  std::memset(h_signal_, 0, 256 * sizeof(unsigned));
+  h_moment_out_.alloc(size_t(LIO_MAX_FRAMES) * LIO_MOMENT_OUT, hipHostMallocCoherent);
+  h_odom_.alloc(1, hipHostMallocCoherent);
+  h_signal_.alloc(256, hipHostMallocCoherent, true);
   vox_.set_host_signal(host_signal_);
   LIO_HIP(hipGetDevice(&device_id_));
 }
 
-Estimator::~Estimator() {
-  try { ResidentEnd(); if (stream_) (void)hipStreamSynchronize(stream_); } catch (...) {}
+Estimator::~Estimator() { Close(); }
+void Estimator::Close() noexcept {   // (the pinned and device buffers are members: they go after this, when stream_ has drained)
+  try { resident_.End(stream_); if (stream_) (void)hipStreamSynchronize(stream_); } catch (...) {}
   try { JoinMarg(); } catch (...) {}
-  if (h_res_door_) (void)hipHostFree(h_res_door_);
-  if (h_res_out_) (void)hipHostFree(h_res_out_);
-  if (h_res_words_) (void)hipHostFree(h_res_words_);
-  if (h_moment_out_) (void)hipHostFree(h_moment_out_);
-  if (h_signal_) (void)hipHostFree(h_signal_);
-  if (h_odom_) (void)hipHostFree(h_odom_);
   if (ev_fork_) (void)hipEventDestroy(ev_fork_);
   if (ev_join_) (void)hipEventDestroy(ev_join_);
   if (stream2_) (void)hipStreamDestroy(stream2_);
@@ -137,7 +114,7 @@ Estimator::~Estimator() {
 // A batch (est_batch.h) takes over the handle's stream: everything the handle enqueues from now on (Restore's copies, SlideWindow's
 // concat, PushFrame's filter) is ordered with the batch's own launches without an event per window and solve.
 void Estimator::AdoptStream(hipStream_t s) {
-  ResidentEnd();
+  resident_.End(stream_);
   LIO_HIP(hipStreamSynchronize(stream_));
   LIO_HIP(hipStreamSynchronize(stream2_));
   if (owns_stream_) LIO_HIP(hipStreamDestroy(stream_));
@@ -212,16 +189,12 @@ void Estimator::SetWindow(const double *Ps, const double *Rs, const double *Vs, 
 }
 
 static std::atomic<uint64_t> g_content_id{1};
-// Resident kernels hold their CUs until the host (or a peer block) feeds them, so the blocks of ALL of them must be co-resident:
-// a process that drives many windows admits only as many as fit (four moments kernels of ~100 blocks);
-// a solve that is not admitted takes the launch path, with the same results.
-static std::atomic<int> g_resident_moments{0};
-static const int kMaxResidentMoments = 4;
 // Solves in flight in this process.  A resident moments kernel holds ~100 CUs' worth of registers while it waits for the host,
 // which is free when the GPU has nothing else to do and expensive when other windows' feature kernels want those CUs: measured
 // on the MI355X with four windows solving on four host threads, 3290 solves/s with every solve resident, 3530 with one at a time,
 // 4230 with none (launch pairs).  So a solve takes the resident form only while it is the ONLY solve in flight.
 static std::atomic<int> g_active_solves{0};
+struct ActiveSolve { ActiveSolve() { g_active_solves.fetch_add(1); } ~ActiveSolve() { g_active_solves.fetch_sub(1); } };
 
 void Estimator::SetSurfStack(int frame, const float *xyzi, size_t n) {
   DeviceCloud &c = stacks_[frame];
@@ -569,19 +542,19 @@ void Estimator::BuildLocalMap(lio_solve_report *rep) {
           if (mail) {
             wait_host_signal(sig, stream_);   // the round before this one has posted its state
           } else {
-            LIO_HIP(hipMemcpyAsync(h_odom_, d_odom_.p, sizeof(st), hipMemcpyDeviceToHost, stream_));  // pinned: a pageable target costs ~10 us more
+            LIO_HIP(hipMemcpyAsync(h_odom_.p, d_odom_.p, sizeof(st), hipMemcpyDeviceToHost, stream_));  // pinned: a pageable target costs ~10 us more
             LIO_HIP(hipStreamSynchronize(stream_));
           }
-          st = *h_odom_;
+          st = *h_odom_.p;
           if (st.converged) { have_state = true; break; }
           ++chunk;
         }
-        if (mail) { sig.flag = h_signal_ + 128; sig.seq = ++signal_seq_[1]; }
+        if (mail) { sig.flag = h_signal_.p + 128; sig.seq = ++signal_seq_[1]; }
         // one round = search + plane fit + rows (k_odom_round) and fold + 6x6 step (k_odom_update_wide)
         const double ns = keep_mult > 1 ? double(iter + 1) * M : double(M);
         int t1h = timers_.begin(KT_ODOM_FEATURES, 16.0 * (double(M) + double(local_filtered_.n)) + 72.0 * M + 33.0 * ns, stream_);
         launch_odom_round(fo, slot_off_[W_], iter, keep_mult > 1 ? 1 : 0, d_odom_.p, grid_.sorted(), grid_.cells(), grid_.desc(), f_valid_.p, f_coef_.p,
-                          f_score_.p, d_odom_partials_.p, stream_, mail ? h_odom_ : nullptr, sig, lpq);
+                          f_score_.p, d_odom_partials_.p, stream_, mail ? h_odom_.p : nullptr, sig, lpq);
         timers_.end(t1h, stream_);
       }
     }
@@ -592,10 +565,10 @@ void Estimator::BuildLocalMap(lio_solve_report *rep) {
       if (sig.flag) {
         wait_host_signal(sig, stream_);
       } else {
-        LIO_HIP(hipMemcpyAsync(h_odom_, d_odom_.p, sizeof(st), hipMemcpyDeviceToHost, stream_));
+        LIO_HIP(hipMemcpyAsync(h_odom_.p, d_odom_.p, sizeof(st), hipMemcpyDeviceToHost, stream_));
         LIO_HIP(hipStreamSynchronize(stream_));
       }
-      st = *h_odom_;
+      st = *h_odom_.p;
       timers_.resolve();
     }
     laser_odom_iters_ = st.iters;
@@ -681,176 +654,8 @@ void Estimator::FillMomentArgs(MomentArgs &ma, int &max_slots) const {
   // With the resident form configured, BOTH paths use its partition (blocks per frame so that a lane holds <= per_lane
   // 64-slot chunks per wave, fp64-MFMA form): the launch path — taken when a pass cannot use the resident kernel (kernel timing, factor
   // sharding, stream_sync) — then yields bit-identical moments.
-  const int rb = ResidentBpf(max_slots, ma.nframes);
+  const int rb = resident_.Bpf(max_slots, ma.nframes);
   if (rb > 0) ma.blocks_per_frame = rb;
-}
-
-// Blocks per frame of the resident form's partition (0: the window does not fit) and, in *per_lane, the residuals a lane keeps.
-// Fewer residuals per lane = more blocks = a shorter accumulate phase (1.7 us of MFMA per wave at four, 0.85 at two); the frame
-// fold costs one memory round trip as long as a frame's blocks fit one batch of loads (RES_FOLD_BATCH = 64).  So: the smallest
-// per-lane count whose blocks are all co-resident (<= 256) with at most 64 per frame.  A pure function of the window's slot
-// counts, so the partition — and with it every bit of the result — does not depend on how a pass is executed.
-int Estimator::ResidentBpf(int max_slots, int nframes, int *per_lane) const {
-  if (per_lane) *per_lane = 0;
-  if (!resident_moments_) return 0;
-  for (int r : {1, 2, 4, 8}) {
-    if (res_per_lane_ > 0 && r != res_per_lane_) continue;
-    const int b = resident_blocks_per_frame(max_slots, nframes, r);
-    if (b > 0 && (b <= 64 || r == 8 || res_per_lane_ > 0)) { if (per_lane) *per_lane = r; return b; }
-  }
-  return 0;
-}
-
-void Estimator::ResidentLaunchKernel(unsigned first_seq) {
-  ResidentArgs ra{h_res_door_, h_res_out_, h_res_words_, first_seq, res_timeout_ticks_, d_res_relay_.p, d_res_part_.p, g_debug_timing ? 1 : 0};
-  res_launch_seq_ = first_seq;   // (a launch's STOP value is derived from it; see ResidentAwaitWord for the one case where the HBM copy must be cleared)
-  launch_lidar_moments_resident(res_args_, ra, res_lanes_, f_valid_.p, f_coef_.p, stream_);
-}
-
-// The resident kernel of this solve: launched behind everything the feature stage enqueued on stream_; it returns when the host
-// writes LIO_RES_STOP (ResidentEnd) or after res_timeout_ticks_ without a doorbell.
-bool Estimator::ResidentBegin(const MomentArgs &ma) {
-  if (!res_allowed_ || resident_never_ || !host_signal_ || timers_.on || Sharded() || rccl_comm_) return false;
-  int max_slots = 0;
-  for (int k = 0; k < ma.nframes; ++k) max_slots = std::max(max_slots, ma.fr[k].nslots);
-  int per_lane = 0;
-  if (ResidentBpf(max_slots, ma.nframes, &per_lane) != ma.blocks_per_frame || ma.blocks_per_frame <= 0) return false;
-  if (g_active_solves.load(std::memory_order_relaxed) > 1) return false;
-  if (res_seq_ > 0xF0000000u) {   // 32-bit sequence numbers: start over long before they wrap (no launch is in flight here)
-    LIO_HIP(hipStreamSynchronize(stream_));
-    LIO_HIP(hipMemset(d_res_part_.p, 0, sizeof(double) * LIO_RES_MAX_BLOCKS * LIO_MOMENT_OUT));
-    std::memset(h_res_words_, 0, sizeof(unsigned) * (LIO_MAX_FRAMES + 2));
-    res_seq_ = 0;
-  }
-  if (g_resident_moments.fetch_add(1) >= kMaxResidentMoments) { g_resident_moments.fetch_sub(1); return false; }
-  struct Admission { bool keep = false; ~Admission() { if (!keep) g_resident_moments.fetch_sub(1); } } admission;   // released if the launch throws
-  res_args_ = ma; res_lanes_ = per_lane;
-  res_bpf_ = ma.blocks_per_frame; res_nframes_ = ma.nframes;
-  for (int f = 0; f < res_nframes_; ++f) {   // idle doorbell: neither the expected sequence number nor STOP
-    __atomic_store_n(reinterpret_cast<unsigned long long *>(h_res_door_ + f * LIO_RES_DOOR + 7), 0ull, __ATOMIC_RELEASE);
-    __atomic_store_n(reinterpret_cast<unsigned long long *>(h_res_door_ + f * LIO_RES_DOOR + 15), 0ull, __ATOMIC_RELEASE);
-  }
-  if (res_time_launch_) {
-    hipEvent_t a, b;
-    LIO_HIP(hipEventCreate(&a)); LIO_HIP(hipEventCreate(&b));
-    LIO_HIP(hipEventRecord(a, stream_));
-    res_launch_events_.push_back({a, b});
-  }
-  res_relaunches_ = 0;
-  ResidentLaunchKernel(res_seq_ + 1);
-  res_active_ = true; admission.keep = true;
-  return true;
-}
-
-int Estimator::ResidentLaunchStats(double *total_ms) {
-  LIO_HIP(hipStreamSynchronize(stream_));
-  for (auto &ev : res_launch_events_) {
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, ev.first, ev.second) == hipSuccess) { res_launch_ms_ += ms; ++res_launches_; }
-    (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second);
-  }
-  res_launch_events_.clear();
-  if (total_ms) *total_ms = res_launch_ms_;
-  return res_launches_;
-}
-
-void Estimator::ResidentRing(const MomentArgs &ma) {
-  const unsigned seq = ++res_seq_;
-  const double sd = double(seq);
-  for (int f = 0; f < res_nframes_; ++f) {
-    double *d = h_res_door_ + f * LIO_RES_DOOR;
-    const MomentFrame &fr = ma.fr[f];
-    // payload first, the sequence slot of each cache line last (x86 keeps the order of stores; the GPU reads a line at a time)
-    for (int k = 0; k < 7; ++k) d[k] = fr.R[k];
-    __atomic_store_n(reinterpret_cast<unsigned long long *>(d + 7), *reinterpret_cast<const unsigned long long *>(&sd), __ATOMIC_RELEASE);
-    d[8] = fr.R[7]; d[9] = fr.R[8]; d[10] = fr.t[0]; d[11] = fr.t[1]; d[12] = fr.t[2]; d[13] = 0.0; d[14] = 0.0;
-    __atomic_store_n(reinterpret_cast<unsigned long long *>(d + 15), *reinterpret_cast<const unsigned long long *>(&sd), __ATOMIC_RELEASE);
-  }
-}
-
-// Waits for frame f's completion word of the pass in flight.  A relay timeout (this host thread was held up for > 200 ms before
-// it rang) can only show while NO frame of the pass has been posted: the relay gives up between passes, and a pass that was
-// started is posted whole.
-void Estimator::ResidentAwaitWord(int f) {
-  const unsigned seq = res_seq_;
-  const volatile unsigned *w = h_res_words_;
-  for (unsigned long it = 1;; ++it) {
-    if (__atomic_load_n(w + f, __ATOMIC_ACQUIRE) == seq) return;
-    if (__atomic_load_n(w + LIO_MAX_FRAMES, __ATOMIC_ACQUIRE) == LIO_RES_EXPIRED) {
-      if (__atomic_load_n(w + f, __ATOMIC_ACQUIRE) == seq) return;
-      if (f > 0 && __atomic_load_n(w + 0, __ATOMIC_ACQUIRE) == seq) throw DeviceError("resident moments kernel gave up in the middle of a pass");
-      // let that launch drain and start a new one for the pass that is pending; its doorbell is still rung.  Twice at most: a
-      // kernel that keeps expiring is not being scheduled whole (its blocks are not co-resident) and no retry will change that.
-      LIO_HIP(hipStreamSynchronize(stream_));
-      if (++res_relaunches_ > 2) throw DeviceError("resident moments kernel expired three times within one solve (its blocks are not co-resident?)");
-      h_res_words_[LIO_MAX_FRAMES] = 0;
-      // The expired relay left ITS stop value in the HBM copy of the doorbell.  If that launch never served a pass, the one that
-      // replaces it starts at the same sequence number and has the same stop value: clear the copy, or the new workers leave on it
-      // before the new relay republishes the pending pass.
-      LIO_HIP(hipMemsetAsync(d_res_relay_.p, 0, sizeof(double) * LIO_MAX_FRAMES * LIO_RES_DOOR, stream_));
-      ResidentLaunchKernel(seq);
-      continue;
-    }
-    __builtin_ia32_pause();
-    if ((it & 0xFFFFu) == 0) {
-      const hipError_t e = hipStreamQuery(stream_);
-      if (e != hipErrorNotReady && e != hipSuccess) throw DeviceError(std::string("resident moments pass failed: ") + hipGetErrorString(e));
-      if (e == hipSuccess && h_res_words_[LIO_MAX_FRAMES] != LIO_RES_EXPIRED && __atomic_load_n(w + f, __ATOMIC_ACQUIRE) != seq)
-        throw DeviceError("resident moments kernel ended without posting its pass");   // the kernel is gone although nobody stopped it
-    }
-  }
-}
-
-void Estimator::ResidentUnpackFrame(int f, FrameMoments &fm) {
-  // the device posts the upper triangle of the 13 x 13 tile (it is symmetric bit for bit); S is the padded 16 x 16 tile
-  static const struct TriMap { int at[256]; TriMap() { for (int i = 0; i < 16; ++i) for (int j = 0; j < 16; ++j) { const int a = std::min(i, j), b = std::max(i, j); at[i * 16 + j] = (b < 13) ? a * 13 - a * (a - 1) / 2 + (b - a) : -1; } } } tri;
-  const double *rec = h_res_out_ + size_t(f) * LIO_RES_OUT;
-  for (int k = 0; k < 256; ++k) fm.S[k] = tri.at[k] >= 0 ? rec[tri.at[k]] : 0.0;
-  fm.cost = rec[LIO_RES_NTRI]; fm.count = rec[LIO_RES_NTRI + 1];
-  double *o = h_moment_out_ + size_t(f) * LIO_MOMENT_OUT;   // the landing zone of the launch path doubles as "the last moments"
-  o[256] = fm.cost; o[257] = fm.count;
-}
-
-// bookkeeping of a finished pass (all frames in): device-side phase stamps, busy time, algorithmic bytes
-void Estimator::ResidentPassDone() {
-  const int nf = res_nframes_;
-  double busy = 0, polls = 0;
-  for (int f = 0; f < nf; ++f) {
-    const double *rec = h_res_out_ + size_t(f) * LIO_RES_OUT;
-    for (int q = 0; q < 4; ++q) res_diag_us_[q] += rec[258 + q] * res_tick_us_ / nf;
-    polls += rec[262] / nf;
-    res_relay_us_ += rec[263] * res_tick_us_ / nf;
-    busy = std::max(busy, rec[261]);
-  }
-  res_busy_us_ += busy * res_tick_us_;   // doorbell copy seen -> sums posted, slowest frame
-  { double nres = 0; for (int f = 0; f < nf; ++f) nres += res_args_.fr[f].nslots; res_bytes_ += 60.0 * nres; }   // 60 B per lidar residual
-  res_polls_ += polls; ++res_passes_; ++res_passes_total_;
-}
-
-void Estimator::ResidentWaitFrame(int f, FrameMoments &fm) {
-  ResidentAwaitWord(f);
-  ResidentUnpackFrame(f, fm);
-  if (f == res_nframes_ - 1) ResidentPassDone();
-}
-
-void Estimator::ResidentWait(std::vector<FrameMoments> &m) {
-  for (int f = 0; f < res_nframes_; ++f) ResidentAwaitWord(f);
-  for (int f = 0; f < res_nframes_; ++f) ResidentUnpackFrame(f, m[f + 1]);
-  ResidentPassDone();
-}
-
-void Estimator::ResidentEnd() {
-  res_allowed_ = false;
-  if (!res_active_) return;
-  const double stop = LIO_RES_STOP(res_launch_seq_);
-  const unsigned long long bits = *reinterpret_cast<const unsigned long long *>(&stop);
-  for (int f = 0; f < res_nframes_; ++f) {
-    __atomic_store_n(reinterpret_cast<unsigned long long *>(h_res_door_ + f * LIO_RES_DOOR + 7), bits, __ATOMIC_RELEASE);
-    __atomic_store_n(reinterpret_cast<unsigned long long *>(h_res_door_ + f * LIO_RES_DOOR + 15), bits, __ATOMIC_RELEASE);
-  }
-  res_active_ = false;   // the kernel leaves within one poll; whatever is enqueued on stream_ next is ordered behind it
-  g_resident_moments.fetch_sub(1);
-  if (res_time_launch_ && !res_launch_events_.empty()) (void)hipEventRecord(res_launch_events_.back().second, stream_);
 }
 
 void Estimator::LidarLaunch(const WindowParams &P) {
@@ -864,14 +669,10 @@ void Estimator::LidarLaunch(const WindowParams &P) {
 void Estimator::LidarLaunchMoments(const MomentArgs &ma, bool reduce) {
   const double t_dbg0 = now_ms();
   struct DbgAcc { Estimator *e; double t0; ~DbgAcc() { e->dbg_eval_ms_ += now_ms() - t0; } } dbg_acc{this, t_dbg0};
-  if (res_active_ || ResidentBegin(ma)) {
-    res_t_ring_ = now_ms();
-    ResidentRing(ma);
-    if (g_debug_timing) {   // ring -> the relay's echo of the sequence number: the inbound PCIe leg + one word back
-      const volatile unsigned *echo = h_res_words_ + LIO_MAX_FRAMES + 1;
-      for (unsigned long it = 0; it < 2000000ul && __atomic_load_n(echo, __ATOMIC_ACQUIRE) != res_seq_; ++it) __builtin_ia32_pause();
-      res_echo_ms_ += now_ms() - res_t_ring_;
-    }
+  // the resident form serves the pass unless something only this side knows rules it out (g_active_solves above)
+  if (resident_.active() || resident_.Begin(ma, host_signal_ && !timers_.on && !Sharded() && !rccl_comm_ && g_active_solves.load(std::memory_order_relaxed) <= 1,
+                                            f_valid_.p, f_coef_.p, stream_)) {
+    resident_.Ring(ma);
     return;
   }
   d_moment_partials_.reserve(size_t(ma.nframes) * ma.blocks_per_frame * LIO_MOMENT_OUT);
@@ -886,14 +687,14 @@ void Estimator::LidarLaunchMoments(const MomentArgs &ma, bool reduce) {
     // same stream, then the 10 KB result goes to the pinned landing zone
     launch_lidar_moments(ma, f_valid_.p, f_coef_.p, d_moment_partials_.p, d_moment_out_.p, stream_);
     if (reduce) rccl_all_reduce_sum_f64(rccl_comm_, d_moment_out_.p, size_t(Wo_) * LIO_MOMENT_OUT, stream_);
-    LIO_HIP(hipMemcpyAsync(h_moment_out_, d_moment_out_.p, sizeof(double) * Wo_ * LIO_MOMENT_OUT, hipMemcpyDeviceToHost, stream_));
+    LIO_HIP(hipMemcpyAsync(h_moment_out_.p, d_moment_out_.p, sizeof(double) * Wo_ * LIO_MOMENT_OUT, hipMemcpyDeviceToHost, stream_));
   } else {
     moment_signal_ = HostSignal();
     if (host_signal_ && !timers_.on) {
       // one completion word per block of the kernel that writes the result: k_moment_reduce's (frames, 3) grid
-      moment_signal_.flag = h_signal_; moment_signal_.seq = ++signal_seq_[0]; moment_signal_.nslots = 3 * ma.nframes;
+      moment_signal_.flag = h_signal_.p; moment_signal_.seq = ++signal_seq_[0]; moment_signal_.nslots = 3 * ma.nframes;
     }
-    launch_lidar_moments(ma, f_valid_.p, f_coef_.p, d_moment_partials_.p, h_moment_out_, stream_, moment_signal_);
+    launch_lidar_moments(ma, f_valid_.p, f_coef_.p, d_moment_partials_.p, h_moment_out_.p, stream_, moment_signal_);
   }
   timers_.end(th, stream_);
 }
@@ -901,9 +702,9 @@ void Estimator::LidarLaunchMoments(const MomentArgs &ma, bool reduce) {
 int Estimator::EvalLidarMoments(int n_passes, const double *Rt, double *out) {
   if (feat_batch_) return -1;   // the slot layout is the batch's (its arrays, not f_valid_ / f_coef_): lio_est_build_local_map first
   // the guards of SolveOptimizationHost: one solve scope, so that with the resident form the passes are passes 1 .. n of one launch
-  struct ActiveSolve { ActiveSolve() { g_active_solves.fetch_add(1); } ~ActiveSolve() { g_active_solves.fetch_sub(1); } } active_solve;
-  struct ResidentScope { Estimator *e; ~ResidentScope() { e->ResidentEnd(); } } resident_scope{this};
-  res_allowed_ = true;
+  ActiveSolve active_solve;
+  ResidentScope resident_scope{this};
+  resident_.Open();
   MomentArgs ma;
   int max_slots = 0;
   FillMomentArgs(ma, max_slots);
@@ -916,7 +717,7 @@ int Estimator::EvalLidarMoments(int n_passes, const double *Rt, double *out) {
       for (int k = 0; k < 3; ++k) ma.fr[f].t[k] = src[9 + k];
     }
     LidarLaunchMoments(ma, false);
-    path = res_active_ ? 2 : 0;
+    path = resident_.active() ? 2 : 0;
     LidarWait(m, false);
     for (int f = 0; f < Wo_; ++f) {
       double *dst = out + (size_t(p) * Wo_ + f) * 258;
@@ -979,29 +780,36 @@ bool Estimator::BenchBatchedMoments(int B, int reps, double *avg_ms, double *byt
 
 // Frame i (1-based) of the pass in flight, as soon as its completion word is in — only the resident kernel posts per frame.
 bool Estimator::LidarWaitFrame(int i, FrameMoments &fm) {
-  if (!res_active_) return false;
+  if (!resident_.active()) return false;
   const double t_dbg0 = now_ms();
-  ResidentWaitFrame(i - 1, fm);
+  resident_.WaitFrame(i - 1, fm, stream_);
+  double *o = h_moment_out_.p + size_t(i - 1) * LIO_MOMENT_OUT;   // the landing zone of the launch path doubles as "the last moments"
+  o[256] = fm.cost; o[257] = fm.count;
   const double t1 = now_ms();
   dbg_eval_ms_ += t1 - t_dbg0; dbg_sync_ms_ += t1 - t_dbg0;
-  if (i == res_nframes_) { ++dbg_eval_n_; res_ring_to_done_ms_ += t1 - res_t_ring_; }
+  if (i == resident_.nframes()) ++dbg_eval_n_;
   return true;
 }
 
 void Estimator::LidarWait(std::vector<FrameMoments> &m, bool reduce) {
   const double t_dbg0 = now_ms();
   struct DbgAcc { Estimator *e; double t0; ~DbgAcc() { e->dbg_eval_ms_ += now_ms() - t0; e->dbg_eval_n_++; } } dbg_acc{this, t_dbg0};
-  if (res_active_) { ResidentWait(m); dbg_sync_ms_ += now_ms() - t_dbg0; res_ring_to_done_ms_ += now_ms() - res_t_ring_; return; }
+  if (resident_.active()) {
+    resident_.Wait(m, stream_);
+    for (int i = 1; i <= Wo_; ++i) { double *o = h_moment_out_.p + size_t(i - 1) * LIO_MOMENT_OUT; o[256] = m[i].cost; o[257] = m[i].count; }   // as in LidarWaitFrame
+    dbg_sync_ms_ += now_ms() - t_dbg0;
+    return;
+  }
   if (moment_signal_.flag && !rccl_comm_) wait_host_signal(moment_signal_, stream_);
   else LIO_HIP(hipStreamSynchronize(stream_));
   dbg_sync_ms_ += now_ms() - t_dbg0;
   timers_.resolve();
   if (reduce && shard_world_ > 1 && allreduce_ && !rccl_comm_) {
     // per-shard moments -> whole-window moments through the caller's callback (gloo on CPU hosts; the RCCL form never gets here)
-    if (allreduce_(h_moment_out_, Wo_ * LIO_MOMENT_OUT, allreduce_user_) != 0) throw std::runtime_error("factor-sharding all-reduce failed");
+    if (allreduce_(h_moment_out_.p, Wo_ * LIO_MOMENT_OUT, allreduce_user_) != 0) throw std::runtime_error("factor-sharding all-reduce failed");
   }
   for (int i = 1; i <= Wo_; ++i) {
-    const double *src = h_moment_out_ + size_t(i - 1) * LIO_MOMENT_OUT;
+    const double *src = h_moment_out_.p + size_t(i - 1) * LIO_MOMENT_OUT;
     std::memcpy(m[i].S, src, 256 * sizeof(double));
     m[i].cost = src[256]; m[i].count = src[257];
   }
@@ -1014,11 +822,11 @@ bool Estimator::SolveOptimizationHost(lio_solve_report *rep) {
   lio_solve_report &R = rep ? *rep : local;
   std::memset(&R, 0, sizeof(R));
   bool turn_off = true;
-  struct ActiveSolve { ActiveSolve() { g_active_solves.fetch_add(1); } ~ActiveSolve() { g_active_solves.fetch_sub(1); } } active_solve;
+  ActiveSolve active_solve;
   BuildLocalMap(&R);
   // from here to the end of the solve the lidar passes may come from ONE resident kernel (begun by the first LidarLaunch)
-  struct ResidentScope { Estimator *e; ~ResidentScope() { e->ResidentEnd(); } } resident_scope{this};
-  res_allowed_ = true;
+  ResidentScope resident_scope{this};
+  resident_.Open();
   const double t_prep0 = now_ms();
   const int pivot = W_ - Wo_;
   WindowParams P;
@@ -1118,7 +926,7 @@ bool Estimator::SolveOptimizationHost(lio_solve_report *rep) {
   // residual count of the last device evaluation (valid feature slots of frames 1..Wo)
   {
     double cnt = 0;
-    for (int i = 1; i <= Wo_; ++i) cnt += h_moment_out_[size_t(i - 1) * LIO_MOMENT_OUT + 257];
+    for (int i = 1; i <= Wo_; ++i) cnt += h_moment_out_.p[size_t(i - 1) * LIO_MOMENT_OUT + 257];
     R.n_lidar_residuals = cfg_.point_distance_factor ? int(cnt) : 0;
   }
   R.ms_total = now_ms() - t_total0;
@@ -1126,15 +934,7 @@ bool Estimator::SolveOptimizationHost(lio_solve_report *rep) {
     std::fprintf(stderr, "[lio_hip timing] total %.3f map %.3f feat %.3f opt %.3f marg %.3f | lidar_eval %d calls %.3f ms (%.1f us each)\n", R.ms_total,
                  R.ms_build_map, R.ms_features, R.ms_opt, R.ms_marg, dbg_eval_n_, dbg_eval_ms_, dbg_eval_n_ ? 1e3 * dbg_eval_ms_ / dbg_eval_n_ : 0.0);
   }
-  if (g_debug_timing && res_passes_) {
-    std::fprintf(stderr, "[lio_hip timing] resident moments: %d passes; folding block, from the doorbell copy seen (us): accumulated %.2f, parked %.2f, all flags in %.2f, sums posted %.2f; relay detect -> copy seen %.2f; host ring -> moments unpacked %.2f; HBM polls %.1f; %d worker blocks\n",
-                 res_passes_, res_diag_us_[0] / res_passes_, res_diag_us_[1] / res_passes_, res_diag_us_[2] / res_passes_, res_diag_us_[3] / res_passes_,
-                 res_relay_us_ / res_passes_, 1e3 * res_ring_to_done_ms_ / res_passes_, res_polls_ / res_passes_, res_bpf_ * res_nframes_);
-    std::fprintf(stderr, "[lio_hip timing] resident moments: host ring -> relay's echo seen %.2f us (the host waits for it only under LIO_DEBUG_TIMING)\n",
-                 1e3 * res_echo_ms_ / res_passes_);
-    res_echo_ms_ = 0;
-    res_diag_us_[0] = res_diag_us_[1] = res_diag_us_[2] = res_diag_us_[3] = res_polls_ = res_relay_us_ = res_ring_to_done_ms_ = 0; res_passes_ = 0;
-  }
+  resident_.PrintDebugTiming();
   if (g_debug_timing) std::fprintf(stderr, "[lio_hip timing] of which hipStreamSynchronize %.3f ms\n", dbg_sync_ms_);
   dbg_eval_ms_ = 0; dbg_eval_n_ = 0; dbg_sync_ms_ = 0;
   return true;

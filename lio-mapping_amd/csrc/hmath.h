@@ -399,41 +399,4 @@ LIO_HD void sym_eig3_top_closed(const float *Ain, float *evals, double *vtop) {
   else { vtop[0] = 1.0; vtop[1] = 0.0; vtop[2] = 0.0; }
 }
 
-// Cyclic-Jacobi eigenvalues of a symmetric NxN (N <= 6) matrix, ascending.  Accumulates in double.
-template <int N>
-LIO_HD void sym_eigvals(const float *Ain, float *evals) {
-  double A[N * N];
-  for (int i = 0; i < N * N; ++i) A[i] = double(Ain[i]);
-  for (int sweep = 0; sweep < 60; ++sweep) {
-    double off = 0, dg = 0;
-    for (int i = 0; i < N; ++i) { dg += A[i * N + i] * A[i * N + i]; for (int j = i + 1; j < N; ++j) off += A[i * N + j] * A[i * N + j]; }
-    if (off <= 1e-30 * dg) break;  // eigenvalues converged to ~1e-15 relative (quadratic convergence)
-    for (int p = 0; p < N; ++p)
-      for (int q = p + 1; q < N; ++q) {
-        double apq = A[p * N + q];
-        if (apq == 0.0) continue;
-        double app = A[p * N + p], aqq = A[q * N + q];
-        double tau = (aqq - app) / (2.0 * apq);
-        double t = (tau >= 0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-        double c = 1.0 / sqrt(1.0 + t * t), s = t * c;
-        for (int k = 0; k < N; ++k) {
-          double akp = A[k * N + p], akq = A[k * N + q];
-          A[k * N + p] = c * akp - s * akq;
-          A[k * N + q] = s * akp + c * akq;
-        }
-        for (int k = 0; k < N; ++k) {
-          double apk = A[p * N + k], aqk = A[q * N + k];
-          A[p * N + k] = c * apk - s * aqk;
-          A[q * N + k] = s * apk + c * aqk;
-        }
-      }
-  }
-  double d[N];
-  for (int i = 0; i < N; ++i) d[i] = A[i * N + i];
-  for (int i = 0; i < N; ++i)
-    for (int j = i + 1; j < N; ++j)
-      if (d[j] < d[i]) { double t = d[i]; d[i] = d[j]; d[j] = t; }
-  for (int i = 0; i < N; ++i) evals[i] = float(d[i]);
-}
-
 }  // namespace lio

@@ -59,7 +59,7 @@ class KfBatchDev {
   DBuf<uint32_t> order_, qkeys_, qkeys2_, qvals2_, qhist_;
   DBuf<SegDesc> d_qseg_;
   bool order_valid_ = false;
-  int *h_nconv_ = nullptr;  // pinned
+  HostBuf<int> h_nconv_;
   bool md_dirty_ = true, kf_dirty_ = true;
   int max_Mc_ = 0, max_Ms_ = 0, max_nb_ = 1, total_nb_ = 0, n_gated_ = 0;
 };

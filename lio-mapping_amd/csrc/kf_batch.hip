@@ -16,13 +16,12 @@ KfBatchDev::KfBatchDev(const lio_map_config &cfg) : cfg_(cfg) {
   LIO_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
   LIO_HIP(hipEventCreate(&ev0_));
   LIO_HIP(hipEventCreate(&ev1_));
-  LIO_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_nconv_), sizeof(int), hipHostMallocDefault));
+  h_nconv_.alloc(1, hipHostMallocDefault);
   d_nconv_.reserve(1);
 }
 
 KfBatchDev::~KfBatchDev() {
   if (stream_) (void)hipStreamSynchronize(stream_);
-  if (h_nconv_) (void)hipHostFree(h_nconv_);
   if (ev0_) (void)hipEventDestroy(ev0_);
   if (ev1_) (void)hipEventDestroy(ev1_);
   if (stream_) (void)hipStreamDestroy(stream_);
@@ -175,9 +174,9 @@ void KfBatchDev::Refine() {
     ++rounds_;
     // most keyframes converge in 5-7 rounds; converged keyframes cost nothing in later rounds, so peek sparsely
     if (iter + 1 >= 5 && (iter + 1) % 2 == 1 && iter + 1 < max_it) {
-      LIO_HIP(hipMemcpyAsync(h_nconv_, d_nconv_.p, sizeof(int), hipMemcpyDeviceToHost, s));
+      LIO_HIP(hipMemcpyAsync(h_nconv_.p, d_nconv_.p, sizeof(int), hipMemcpyDeviceToHost, s));
       LIO_HIP(hipStreamSynchronize(s));
-      if (*h_nconv_ + n_gated_ >= B) break;
+      if (*h_nconv_.p + n_gated_ >= B) break;
     }
   }
   LIO_HIP(hipEventRecord(ev1_, s));

@@ -81,8 +81,8 @@ class MappingDev {
     VoxelGridDev vox;
     DBuf<float4> in, stack_raw, stack_ds;
     size_t n_stack = 0;
-    MapCounters *h_counters = nullptr;  // pinned
-    VoxParams *h_bounds = nullptr;      // pinned
+    HostBuf<MapCounters> h_counters;
+    HostBuf<VoxParams> h_bounds;
   };
 
   MapValidSet MakeValidSet(const uint32_t *valid_idx, size_t n, const int cen_of_idx[3]) const;
@@ -103,7 +103,8 @@ class MappingDev {
   DBuf<float4> f_coef_, f_abs_;
   DBuf<OdomState> d_state_;
   DBuf<double> d_partials_;
-  OdomState *h_state_ = nullptr;  // pinned, coherent: the state's mailbox
+  HostBuf<char> h_mail_;          // pinned, coherent: the state's mailbox
+  OdomState *h_state_ = nullptr;  // ... the state in it
   unsigned *h_flag_ = nullptr;    // its completion word
   unsigned seq_ = 0;
   size_t n_score_slots_ = 0;

@@ -2,7 +2,6 @@
 // kernel or a rocPRIM primitive; the host only does the 6-DoF bookkeeping (transform algebra, cube-window shift,
 // FOV test of <= 125 cubes).
 #include <cstring>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 
@@ -20,8 +19,6 @@
 namespace lio {
 
 namespace {
-
-inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 __host__ __device__ inline uint32_t pack_cube(int ai, int aj, int ak) {
   return (uint32_t(ai + 512) << 20) | (uint32_t(aj + 512) << 10) | uint32_t(ak + 512);
@@ -243,13 +240,6 @@ inline Vec3<double> r2ypr_deg(const Mat3<double> &R) {
 }
 inline Mat3<double> to_double(const Mat3<float> &m) { Mat3<double> r; for (int k = 0; k < 9; ++k) r.m[k] = double(m.m[k]); return r; }
 
-template <typename T> T *pinned_alloc() {
-  T *p = nullptr;
-  LIO_HIP(hipHostMalloc(reinterpret_cast<void **>(&p), sizeof(T), hipHostMallocDefault));
-  std::memset(p, 0, sizeof(T));
-  return p;
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -262,26 +252,21 @@ MappingDev::MappingDev(const lio_map_config &cfg) : cfg_(cfg) {
   LIO_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
   LIO_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
   for (ClassMap &m : cls_) {
-    m.h_counters = pinned_alloc<MapCounters>();
-    m.h_bounds = pinned_alloc<VoxParams>();
+    m.h_counters.alloc(1, hipHostMallocDefault, true);
+    m.h_bounds.alloc(1, hipHostMallocDefault, true);
     m.counters.reserve(1);
     m.bounds.reserve(1);
     m.cube_bounds.reserve(LIO_MAP_MAX_VALID * 6);
   }
   // coherent: the update kernel posts the state and a completion word here (dev.h: HostSignal)
-  LIO_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_state_), 128, hipHostMallocCoherent));
+  h_mail_.alloc(128, hipHostMallocCoherent, true);
   static_assert(sizeof(OdomState) <= 64, "mailbox layout");
-  std::memset(h_state_, 0, 128);
-  h_flag_ = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(h_state_) + 64);
+  h_state_ = reinterpret_cast<OdomState *>(h_mail_.p);
+  h_flag_ = reinterpret_cast<unsigned *>(h_mail_.p + 64);
   d_state_.reserve(1);
 }
 
 MappingDev::~MappingDev() {
-  for (ClassMap &m : cls_) {
-    if (m.h_counters) (void)hipHostFree(m.h_counters);
-    if (m.h_bounds) (void)hipHostFree(m.h_bounds);
-  }
-  if (h_state_) (void)hipHostFree(h_state_);
   if (ev_fork_) (void)hipEventDestroy(ev_fork_);
   if (ev_join_) (void)hipEventDestroy(ev_join_);
   if (stream2_) (void)hipStreamDestroy(stream2_);
@@ -319,7 +304,7 @@ bool MappingDev::LayoutMatches(const ClassMap &m, const MapValidSet &vs) const {
 
 void MappingDev::LayoutLaunch(ClassMap &m, const MapValidSet &vs) {
   hipStream_t s = stream_;
-  std::memset(m.h_counters, 0, sizeof(MapCounters));
+  std::memset(m.h_counters.p, 0, sizeof(MapCounters));
   if (m.n == 0) return;
   const size_t n = m.n;
   const int ni = int(n);
@@ -334,7 +319,7 @@ void MappingDev::LayoutLaunch(ClassMap &m, const MapValidSet &vs) {
   hipLaunchKernelGGL(k_map_gather, dim3(cdiv(ni, 256)), dim3(256), 0, s, m.pool.p, m.pkey.p, m.rk2.p, m.vals2.p, ni, m.counters.p, m.pool2.p,
                      m.pkey2.p, m.vrank.p);
   LIO_HIP(hipGetLastError());
-  LIO_HIP(hipMemcpyAsync(m.h_counters, m.counters.p, sizeof(MapCounters), hipMemcpyDeviceToHost, s));
+  LIO_HIP(hipMemcpyAsync(m.h_counters.p, m.counters.p, sizeof(MapCounters), hipMemcpyDeviceToHost, s));
 }
 
 void MappingDev::LayoutFinish(ClassMap &m, const MapValidSet &vs) {
@@ -342,8 +327,8 @@ void MappingDev::LayoutFinish(ClassMap &m, const MapValidSet &vs) {
     std::swap(m.pool, m.pool2);
     std::swap(m.pkey, m.pkey2);
   }
-  m.n_valid = size_t(m.h_counters->n_valid);
-  m.n_rest = size_t(m.h_counters->n_rest);
+  m.n_valid = size_t(m.h_counters.p->n_valid);
+  m.n_rest = size_t(m.h_counters.p->n_rest);
   m.n = m.n_valid + m.n_rest;
   m.layout_ok = true;
   m.layout_keys.assign(vs.key, vs.key + vs.n);
@@ -353,9 +338,9 @@ void MappingDev::LayoutFinish(ClassMap &m, const MapValidSet &vs) {
 // pool must already be laid out for vs.  new_sensor_pts: device, sensor frame.
 void MappingDev::UpdateLaunch(ClassMap &m, const float4 *new_sensor_pts, size_t n_new, const MapValidSet &vs, const Rigid<float> &T, float leaf) {
   hipStream_t s = stream_;
-  std::memset(m.h_counters, 0, sizeof(MapCounters));
+  std::memset(m.h_counters.p, 0, sizeof(MapCounters));
   const size_t nV = m.n_valid, nU = nV + n_new;
-  m.h_counters->n_out = int(nV);
+  m.h_counters.p->n_out = int(nV);
   if (nU == 0) return;
   m.pool.reserve(m.n_rest + n_new + nU, s, true, m.n);
   m.pkey.reserve(m.n_rest + n_new + nU, s, true, m.n);
@@ -394,12 +379,12 @@ void MappingDev::UpdateLaunch(ClassMap &m, const float4 *new_sensor_pts, size_t 
   hipLaunchKernelGGL(k_cube_centroids, dim3(cdiv(nu, 256)), dim3(256), 0, s, m.u_pts.p, reinterpret_cast<unsigned long long *>(m.k64b.p), m.vals2.p,
                      m.flags.p, m.pos.p, nu, vs, int(m.n_rest), m.counters.p, m.pool.p, m.pkey.p, m.vrank.p);
   LIO_HIP(hipGetLastError());
-  LIO_HIP(hipMemcpyAsync(m.h_counters, m.counters.p, sizeof(MapCounters), hipMemcpyDeviceToHost, s));
+  LIO_HIP(hipMemcpyAsync(m.h_counters.p, m.counters.p, sizeof(MapCounters), hipMemcpyDeviceToHost, s));
 }
 
 void MappingDev::UpdateFinish(ClassMap &m) {
-  m.n_rest += size_t(m.h_counters->n_new_rest);
-  m.n_valid = size_t(m.h_counters->n_out);
+  m.n_rest += size_t(m.h_counters.p->n_new_rest);
+  m.n_valid = size_t(m.h_counters.p->n_out);
   m.n = m.n_rest + m.n_valid;
 }
 
@@ -566,11 +551,11 @@ void MappingDev::Optimize(bool four_dof) {
   ClassMap *cm[2] = {&mc, &ms};
   for (ClassMap *m : cm) {
     launch_cloud_bounds(m->pool.p + m->n_rest, int(m->n_valid), m->partial, m->bounds.p, s);
-    LIO_HIP(hipMemcpyAsync(m->h_bounds, m->bounds.p, sizeof(VoxParams), hipMemcpyDeviceToHost, s));
+    LIO_HIP(hipMemcpyAsync(m->h_bounds.p, m->bounds.p, sizeof(VoxParams), hipMemcpyDeviceToHost, s));
   }
   LIO_HIP(hipStreamSynchronize(s));
   const float cell = std::sqrt(cfg_.min_match_sq_dis) * 1.0001f;
-  for (ClassMap *m : cm) m->grid.build(m->pool.p + m->n_rest, m->n_valid, m->h_bounds->mn, m->h_bounds->mx, cell, s);
+  for (ClassMap *m : cm) m->grid.build(m->pool.p + m->n_rest, m->n_valid, m->h_bounds.p->mn, m->h_bounds.p->mx, cell, s);
 
   const int Mc = int(mc.n_stack), Ms = int(ms.n_stack), M = Mc + Ms;
   if (M == 0) {  // every round has < 50 rows: the loop runs dry, then TransformUpdate

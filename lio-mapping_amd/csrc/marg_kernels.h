@@ -25,7 +25,7 @@ class MargSchurDev {
   int device_;
   hipStream_t stream_ = nullptr;
   double *d_in_ = nullptr, *d_out_ = nullptr;   // [A | b], [lin_jac | lin_res | evals | info]
-  double *h_io_ = nullptr;                      // pinned staging for both
+  HostBuf<double> h_io_;                        // pinned staging for both
   double last_ms_ = 0;
 };
 

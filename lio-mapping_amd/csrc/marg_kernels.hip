@@ -578,11 +578,10 @@ MargSchurDev::MargSchurDev(int device) : device_(device) {
   const size_t N = MARG_MAX_M + MARG_MAX_N;
   LIO_HIP(hipMalloc(reinterpret_cast<void **>(&d_in_), (N * N + N) * sizeof(double)));
   LIO_HIP(hipMalloc(reinterpret_cast<void **>(&d_out_), (size_t(MARG_MAX_N) * MARG_MAX_N + 2 * MARG_MAX_N + 8) * sizeof(double)));
-  LIO_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_io_), (N * N + N + size_t(MARG_MAX_N) * MARG_MAX_N + 2 * MARG_MAX_N + 8) * sizeof(double)));
+  h_io_.alloc(N * N + N + size_t(MARG_MAX_N) * MARG_MAX_N + 2 * MARG_MAX_N + 8, hipHostMallocDefault);
   LIO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_marg_schur), hipFuncAttributeMaxDynamicSharedMemorySize, int(marg_lds_bytes(MARG_MAX_N))));
 }
 MargSchurDev::~MargSchurDev() {
-  if (h_io_) (void)hipHostFree(h_io_);
   if (d_in_) (void)hipFree(d_in_);
   if (d_out_) (void)hipFree(d_out_);
   if (stream_) (void)hipStreamDestroy(stream_);
@@ -593,13 +592,13 @@ bool MargSchurDev::Run(const double *A, const double *b, int m, int n, double ep
   const auto t0 = std::chrono::steady_clock::now();
   LIO_HIP(hipSetDevice(device_));   // the caller is the estimator's worker thread: the current device is per thread
   const size_t N = size_t(m) + n, n_in = N * N + N, n_out = size_t(n) * n + 2 * size_t(n) + 2;
-  std::memcpy(h_io_, A, N * N * sizeof(double));
-  std::memcpy(h_io_ + N * N, b, N * sizeof(double));
-  LIO_HIP(hipMemcpyAsync(d_in_, h_io_, n_in * sizeof(double), hipMemcpyHostToDevice, stream_));
+  std::memcpy(h_io_.p, A, N * N * sizeof(double));
+  std::memcpy(h_io_.p + N * N, b, N * sizeof(double));
+  LIO_HIP(hipMemcpyAsync(d_in_, h_io_.p, n_in * sizeof(double), hipMemcpyHostToDevice, stream_));
   double *d_jac = d_out_, *d_res = d_out_ + size_t(n) * n, *d_ev = d_res + n, *d_info = d_ev + n;
   hipLaunchKernelGGL(k_marg_schur, dim3(1), dim3(MARG_THREADS), marg_lds_bytes(n), stream_, d_in_, d_in_ + N * N, m, n, eps, d_jac, d_res, d_ev, d_info);
   LIO_HIP(hipGetLastError());
-  double *h_out = h_io_ + n_in;
+  double *h_out = h_io_.p + n_in;
   LIO_HIP(hipMemcpyAsync(h_out, d_out_, n_out * sizeof(double), hipMemcpyDeviceToHost, stream_));
   LIO_HIP(hipStreamSynchronize(stream_));
   std::memcpy(lin_jac, h_out, size_t(n) * n * sizeof(double));

@@ -36,8 +36,9 @@ class OdometryDev {
   KnnGrid grid_c_, grid_s_;
   DBuf<float> partial_c_, partial_s_;
   DBuf<VoxParams> bounds_;
-  VoxParams *h_bounds_ = nullptr;  // pinned
-  OdomState *h_state_ = nullptr;   // pinned, coherent: the state's mailbox
+  HostBuf<VoxParams> h_bounds_;    // allocated on first use
+  HostBuf<char> h_mail_;           // pinned, coherent, allocated on first use: the state's mailbox
+  OdomState *h_state_ = nullptr;   // ... the state in it
   unsigned *h_flag_ = nullptr;     // its completion word
   unsigned seq_ = 0;
 };

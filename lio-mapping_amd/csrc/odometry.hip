@@ -358,8 +358,6 @@ OdometryDev::OdometryDev(float scan_period, int io_ratio, int max_iter, bool no_
   d_state_.reserve(1);
 }
 OdometryDev::~OdometryDev() {
-  if (h_bounds_) (void)hipHostFree(h_bounds_);
-  if (h_state_) (void)hipHostFree(h_state_);
   if (stream_) (void)hipStreamDestroy(stream_);
 }
 
@@ -367,14 +365,14 @@ OdometryDev::~OdometryDev() {
 void OdometryDev::BuildGrids() {
   hipStream_t s = stream_;
   bounds_.reserve(2);
-  if (!h_bounds_) LIO_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_bounds_), 2 * sizeof(VoxParams), hipHostMallocDefault));
+  if (!h_bounds_.p) h_bounds_.alloc(2, hipHostMallocDefault);
   launch_cloud_bounds(last_corner_.p, int(n_last_corner_), partial_c_, bounds_.p, s);
   launch_cloud_bounds(last_surf_.p, int(n_last_surf_), partial_s_, bounds_.p + 1, s);
-  LIO_HIP(hipMemcpyAsync(h_bounds_, bounds_.p, 2 * sizeof(VoxParams), hipMemcpyDeviceToHost, s));
+  LIO_HIP(hipMemcpyAsync(h_bounds_.p, bounds_.p, 2 * sizeof(VoxParams), hipMemcpyDeviceToHost, s));
   LIO_HIP(hipStreamSynchronize(s));
   const float cell = 5.0f * 1.0001f;
-  grid_c_.build(last_corner_.p, n_last_corner_, h_bounds_[0].mn, h_bounds_[0].mx, cell, s);
-  grid_s_.build(last_surf_.p, n_last_surf_, h_bounds_[1].mn, h_bounds_[1].mx, cell, s);
+  grid_c_.build(last_corner_.p, n_last_corner_, h_bounds_.p[0].mn, h_bounds_.p[0].mx, cell, s);
+  grid_s_.build(last_surf_.p, n_last_surf_, h_bounds_.p[1].mn, h_bounds_.p[1].mx, cell, s);
 }
 
 static void upload(DBuf<float4> &b, const float *src, size_t n, hipStream_t s) {
@@ -397,10 +395,10 @@ void OdometryDev::Process(const float *sharp, size_t n_sharp, const float *less_
   }
   if (enable_odom_) {
     if (!h_state_) {   // coherent: k_odo_update posts the state and its completion word here (dev.h: HostSignal)
-      LIO_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_state_), 128, hipHostMallocCoherent));
+      h_mail_.alloc(128, hipHostMallocCoherent, true);
       static_assert(sizeof(OdomState) <= 64, "mailbox layout");
-      std::memset(h_state_, 0, 128);
-      h_flag_ = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(h_state_) + 64);
+      h_state_ = reinterpret_cast<OdomState *>(h_mail_.p);
+      h_flag_ = reinterpret_cast<unsigned *>(h_mail_.p + 64);
     }
     OdomState st{};
     st.T[0] = transform_es_.rot.x; st.T[1] = transform_es_.rot.y; st.T[2] = transform_es_.rot.z; st.T[3] = transform_es_.rot.w;

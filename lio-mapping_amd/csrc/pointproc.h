@@ -93,6 +93,7 @@ class PointProcessorDev {
   PPDeviceCounts counts_{};            // of the selected sweep
   std::vector<int> ring_offsets_;      // of the selected sweep
   // pinned landing zone: the state records of all sweeps, then three floats per sweep (start-azimuth probe x 2, the value used)
+  HostBuf<char> h_block_;
   int *h_state_ = nullptr;
   float *h_ori_ = nullptr;
   const float4 **h_ptr_ = nullptr;     // staging of the table of input pointers (sweeps already in device memory)

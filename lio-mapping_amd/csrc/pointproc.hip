@@ -821,14 +821,14 @@ PointProcessorDev::PointProcessorDev(float lower, float upper, int rings, const 
 }
 PointProcessorDev::~PointProcessorDev() {
   if (stream_) (void)hipStreamSynchronize(stream_);
-  if (h_state_) (void)hipHostFree(h_state_);
   if (stream_) (void)hipStreamDestroy(stream_);
 }
 void PointProcessorDev::ReserveHost(int B) {
   if (B <= h_cap_sweeps_) return;
-  if (h_state_) { LIO_HIP(hipStreamSynchronize(stream_)); (void)hipHostFree(h_state_); h_state_ = nullptr; }
+  if (h_block_.p) { LIO_HIP(hipStreamSynchronize(stream_)); h_block_.release(); h_state_ = nullptr; }
   const size_t ints = size_t(B) * state_stride_;
-  LIO_HIP(hipHostMalloc(reinterpret_cast<void **>(&h_state_), ints * sizeof(int) + size_t(4) * B * sizeof(float) + size_t(B) * sizeof(const float4 *)));
+  h_block_.alloc(ints * sizeof(int) + size_t(4) * B * sizeof(float) + size_t(B) * sizeof(const float4 *), hipHostMallocDefault);
+  h_state_ = reinterpret_cast<int *>(h_block_.p);
   h_ori_ = reinterpret_cast<float *>(h_state_ + ints);
   h_ptr_ = reinterpret_cast<const float4 **>(h_ori_ + size_t(4) * B);   // (4 B floats behind a multiple-of-4 int count: 8-byte aligned)
   h_cap_sweeps_ = B;

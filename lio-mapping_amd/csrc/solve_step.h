@@ -3,14 +3,14 @@
 //
 // One dogleg iteration is two launches on the estimator's stream, with no host round trip between them:
 //
-//   A  k_lidar_moments_dev   (solve_kernels.hip)   S_i = sum rho' z z^T of the lidar factors at the CANDIDATE poses held in
+//   A  k_bw_moments, k_bw_aux (solve_kernels.hip)  S_i = sum rho' z z^T of the lidar factors at the CANDIDATE poses held in
 //                                                   device memory, per-block partials; one extra grid row evaluates, in
 //                                                   parallel with it, everything that depends on the candidate but not on
 //                                                   the points: the Wo ImuFactor blocks (ImuFactor.h:53-168) whitened and
 //                                                   squared (30x30 each), the marginalization prior's gradient and cost
 //                                                   (MarginalizationFactor.cc:343-393), the extrinsic PriorFactor
 //                                                   (PriorFactor.cc:35-67) and the 18x13 lidar linear maps L_i;
-//   B  k_solve_step           (solve_device.hip)   ONE workgroup: folds the partials, expands L S L^T, assembles H and g in
+//   B  k_bw_solve_step        (solve_kernels.hip)  ONE workgroup: folds the partials, expands L S L^T, assembles H and g in
 //                                                   LDS, decides on the pending candidate (step quality, radius, mu:
 //                                                   Ceres' TrustRegionMinimizer), factors H + mu D^2 = L D L^T in LDS
 //                                                   (16-wide panels: a register-resident diagonal block on one wave,
