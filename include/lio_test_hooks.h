@@ -34,6 +34,25 @@ int lio_est_force_moments_per_lane(lio_est *, int per_lane);
  * The oracle returns zeros. */
 int lio_est_batch_get_moments(lio_est_batch *, int window, double *out, double *Rt);
 
+/* The five-nearest-neighbour walk every lidar residual of the product starts from (csrc/cloud_device.h: knn_scan_group<5, LPQ>, the body
+ * CalculateFeatures, CalculateLaserOdom, the batched windows, scan-to-map and the keyframe batch all call), on its own.
+ * Product: uploads map and queries (xyzi, 4 floats per point), builds the cell grid over the map's own bounds with cell size `cell`
+ * (lio_knn's grid at cell = sqrt(radius_sq) * 1.0001f + 1e-6f) and runs the walk in one launch of 256-thread blocks with
+ * LPQ = lanes_per_query lanes per query: 1, 4 or 8, the forms the product launches; any other value is LIO_ERR_ARG, as are a null
+ * pointer and a cell that is not a positive finite number.
+ * The WHOLE list comes back, with no radius cut (the product cuts later, in the plane fit):
+ *   idx_out[m * 5]          original map indices, ascending by (squared distance, index); a missing entry is -1
+ *   sqd_out[m * 5]          the fp32 squared distances (d = dx*dx; d += dy*dy; d += dz*dz); a missing entry is +inf
+ *   nbr_xyz_out[m * 5 * 3]  the coordinates the walk's POSITIONS in the cell-sorted map point at (what the plane fit would load);
+ *                           a missing entry is zeros
+ * What is searched: with c(v) = int(floorf(v * (1.0f / cell))) in fp32 per axis, the grid spans cells c(min) - 1 .. c(max) + 1 of the
+ * map's finite bounds (an empty map: bounds 0); a query whose cell lies in the grid sees every map point whose cell is within +-1 of
+ * its own on every axis; a query outside the grid, or with a NaN / inf coordinate, finds nothing (all -1 / +inf / zeros) and does
+ * not disturb the other queries of its wave.  Map points are expected finite.
+ * The oracle states the same contract as a serial loop over cells; it checks lanes_per_query and otherwise ignores it. */
+int lio_knn_walk(const float *map_xyzi, size_t n_map, const float *query_xyzi, size_t m, float cell, int lanes_per_query,
+                 int32_t *idx_out, float *sqd_out, float *nbr_xyz_out);
+
 #ifdef __cplusplus
 }
 #endif

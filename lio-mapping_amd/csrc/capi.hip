@@ -521,7 +521,7 @@ struct Scratch {
   DBuf<float4> coef;
   DBuf<float> score, tf;
   DBuf<int32_t> idx;
-  DBuf<float> sqd;
+  DBuf<float> sqd, nbr;
   DBuf<float> bounds;
 };
 static Scratch &scratch() {
@@ -557,6 +557,7 @@ int lio_voxel_grid(const float *xyzi, size_t n, float leaf, float *out, size_t *
 int lio_knn(const float *map, size_t n_map, const float *query, size_t m, int k, float radius_sq, int32_t *idx, float *sqd) {
   if ((!map && n_map) || (!query && m) || !(k == 1 || k == 5) || !idx || !sqd) return LIO_ERR_ARG;
   if (!(radius_sq > 0)) return LIO_ERR_ARG;  // the GPU search is radius-bounded by construction
+  if (m > size_t(INT_MAX) / 8 || n_map > size_t(INT_MAX)) return LIO_ERR_CAPACITY;   // eight lanes per query, int thread ids
   return guarded([&] {
     Scratch &sc = scratch();
     sc.a.reserve(std::max<size_t>(n_map, 1)); sc.b.reserve(std::max<size_t>(m, 1));
@@ -571,6 +572,32 @@ int lio_knn(const float *map, size_t n_map, const float *query, size_t m, int k,
     if (m) {
       LIO_HIP(hipMemcpyAsync(idx, sc.idx.p, m * k * sizeof(int32_t), hipMemcpyDeviceToHost, sc.s));
       LIO_HIP(hipMemcpyAsync(sqd, sc.sqd.p, m * k * sizeof(float), hipMemcpyDeviceToHost, sc.s));
+    }
+    LIO_HIP(hipStreamSynchronize(sc.s));
+    return LIO_OK;
+  });
+}
+
+int lio_knn_walk(const float *map, size_t n_map, const float *query, size_t m, float cell, int lanes_per_query, int32_t *idx, float *sqd,
+                 float *nbr_xyz) {
+  if ((!map && n_map) || (!query && m) || !idx || !sqd || !nbr_xyz || !(cell > 0) || !std::isfinite(cell)) return LIO_ERR_ARG;
+  if (!(lanes_per_query == 1 || lanes_per_query == 4 || lanes_per_query == 8)) return LIO_ERR_ARG;   // the forms the product launches
+  if (m > size_t(INT_MAX) / 8 || n_map > size_t(INT_MAX)) return LIO_ERR_CAPACITY;
+  return guarded([&] {
+    Scratch &sc = scratch();
+    sc.a.reserve(std::max<size_t>(n_map, 1)); sc.b.reserve(std::max<size_t>(m, 1));
+    sc.idx.reserve(std::max<size_t>(m * 5, 1)); sc.sqd.reserve(std::max<size_t>(m * 5, 1)); sc.nbr.reserve(std::max<size_t>(m * 15, 1));
+    if (n_map) LIO_HIP(hipMemcpyAsync(sc.a.p, map, n_map * sizeof(float4), hipMemcpyHostToDevice, sc.s));
+    if (m) LIO_HIP(hipMemcpyAsync(sc.b.p, query, m * sizeof(float4), hipMemcpyHostToDevice, sc.s));
+    float mn[3], mx[3];
+    host_bounds(map, n_map, mn, mx);
+    if (n_map == 0) { mn[0] = mn[1] = mn[2] = 0; mx[0] = mx[1] = mx[2] = 0; }
+    sc.grid.build(sc.a.p, n_map, mn, mx, cell, sc.s);
+    launch_knn_walk(sc.b.p, int(m), lanes_per_query, sc.grid.sorted(), sc.grid.cells(), sc.grid.desc(), sc.idx.p, sc.sqd.p, sc.nbr.p, sc.s);
+    if (m) {
+      LIO_HIP(hipMemcpyAsync(idx, sc.idx.p, m * 5 * sizeof(int32_t), hipMemcpyDeviceToHost, sc.s));
+      LIO_HIP(hipMemcpyAsync(sqd, sc.sqd.p, m * 5 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
+      LIO_HIP(hipMemcpyAsync(nbr_xyz, sc.nbr.p, m * 15 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
     }
     LIO_HIP(hipStreamSynchronize(sc.s));
     return LIO_OK;

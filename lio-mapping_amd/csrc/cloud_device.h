@@ -15,6 +15,7 @@
 namespace lio {
 
 __device__ inline bool finite3(const float4 &p) { return isfinite(p.x) && isfinite(p.y) && isfinite(p.z); }
+__device__ inline bool finite3(const Vec3<float> &p) { return isfinite(p.x) && isfinite(p.y) && isfinite(p.z); }
 
 
 __device__ inline int cell_coord(float v, float inv_cell) { return int(floorf(v * inv_cell)); }
@@ -71,7 +72,9 @@ __device__ inline void knn_scan_group(const Vec3<float> &q, bool active, int sub
   int cx = cell_coord(q.x, g.inv_cell) - g.origin[0];
   int cy = cell_coord(q.y, g.inv_cell) - g.origin[1];
   int cz = cell_coord(q.z, g.inv_cell) - g.origin[2];
-  if (cx < 0 || cy < 0 || cz < 0 || cx >= g.dims[0] || cy >= g.dims[1] || cz >= g.dims[2]) active = false;
+  // a query with a NaN / inf coordinate has no cell (the float -> int conversion above is not defined for it): like a query outside
+  // the grid it finds nothing and only takes part in the shuffles below
+  if (!finite3(q) || cx < 0 || cy < 0 || cz < 0 || cx >= g.dims[0] || cy >= g.dims[1] || cz >= g.dims[2]) active = false;
   if (active) {
     // cells x-1..x+1 have consecutive ids => their points are one contiguous run of the cell-sorted array
     const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dims[0] - 1);

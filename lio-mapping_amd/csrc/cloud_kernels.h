@@ -109,9 +109,14 @@ struct FeatArgs {
 void launch_features(const FeatArgs &a, const float *transforms, const float4 *map_sorted, const int *cells, const GridDesc &g,
                      uint8_t *valid, float4 *coef, float *score, const int *skip_flag, hipStream_t s, float4 *abs_coef = nullptr);
 
-// stateless K-NN (lio_knn entry point): idx/sqd are m*k
+// stateless K-NN (lio_knn entry point): the product's walk (knn_scan_group, 8 lanes per query), k = 1 or 5, entries at or beyond
+// radius_sq come back as -1 / +inf; idx / sqd are m * k
 void launch_knn(const float4 *query, int m, int k, float radius_sq, const float4 *map_sorted, const int *cells, const GridDesc &g,
                 int32_t *idx, float *sqd, hipStream_t s);
+// the same walk with 1, 4 or 8 lanes per query and no radius cut (lio_knn_walk, include/lio_test_hooks.h): idx / sqd are m * 5,
+// nbr_xyz (m * 5 * 3) the coordinates at the positions the walk hands to the plane fit
+void launch_knn_walk(const float4 *query, int m, int lanes_per_query, const float4 *map_sorted, const int *cells, const GridDesc &g,
+                     int32_t *idx, float *sqd, float *nbr_xyz, hipStream_t s);
 
 // Both branches of one scan-to-map round in a single launch (surf: FeatArgs with one frame, mapping_mode 1 or 2; corner: the
 // first Mc points of the concatenated stack, slots [0, Mc)).

@@ -478,75 +478,57 @@ void KnnGrid::build(const float4 *pts, size_t n, const float mn[3], const float 
   cnt_dirty_ = false;
 }
 
-// K nearest (K <= 5 kept in registers) over the 27 neighbouring cells; total order (d2, original index).
-template <int K>
-__device__ inline void knn_scan(const Vec3<float> &q, const float4 *__restrict__ map, const int *__restrict__ cells, const GridDesc &g,
-                                float (&bd)[K], int (&bi)[K], int (&bj)[K]) {
+// The walk of the product, knn_scan_group (cloud_device.h), on its own: LPQ lanes per query in a 256-thread block, like the feature and
+// round kernels; sub-lane 0 writes the query's list.  lio_knn (K = 1 / 5, 8 lanes, entries at or beyond radius_sq cut) and the test hook
+// lio_knn_walk (K = 5, 1 / 4 / 8 lanes, the whole list and the points at sorted[bj[k]], the ones the plane fit loads) both run it.
+#define KNN_WALK_THREADS 256
+template <int K, int LPQ>
+__global__ void __launch_bounds__(KNN_WALK_THREADS) k_nn_walk(const float4 *__restrict__ query, int m, int cut, float radius_sq,
+                                                              const float4 *__restrict__ map, const int *__restrict__ cells, GridDesc g,
+                                                              int32_t *__restrict__ idx, float *__restrict__ sqd, float *__restrict__ nbr) {
+  const int gt = blockIdx.x * blockDim.x + threadIdx.x;   // m * LPQ < 2^31: checked by the callers
+  const int i = gt / LPQ, sub = gt % LPQ;
+  const bool active = i < m;
+  const float4 q4 = active ? query[i] : make_float4(0, 0, 0, 0);
+  float bd[K]; int bi[K], bj[K];
+  knn_scan_group<K, LPQ>(Vec3<float>(q4.x, q4.y, q4.z), active, sub, map, cells, g, bd, bi, bj);
+  if (!active || sub != 0) return;
 #pragma unroll
-  for (int k = 0; k < K; ++k) { bd[k] = INFINITY; bi[k] = INT_MAX; bj[k] = 0; }
-  int cx = cell_coord(q.x, g.inv_cell) - g.origin[0];
-  int cy = cell_coord(q.y, g.inv_cell) - g.origin[1];
-  int cz = cell_coord(q.z, g.inv_cell) - g.origin[2];
-  if (cx < 0 || cy < 0 || cz < 0 || cx >= g.dims[0] || cy >= g.dims[1] || cz >= g.dims[2]) return;
-  for (int dz = -1; dz <= 1; ++dz) {
-    int z = cz + dz;
-    if (z < 0 || z >= g.dims[2]) continue;
-    for (int dy = -1; dy <= 1; ++dy) {
-      int y = cy + dy;
-      if (y < 0 || y >= g.dims[1]) continue;
-      int row = g.dims[0] * (y + g.dims[1] * z);
-      for (int dx = -1; dx <= 1; ++dx) {
-        int x = cx + dx;
-        if (x < 0 || x >= g.dims[0]) continue;
-        const int c0 = cells[row + x], c1 = cells[row + x + 1];
-        for (int j = c0; j < c1; ++j) {
-          float4 p = map[j];
-          float ddx = p.x - q.x, ddy = p.y - q.y, ddz = p.z - q.z;
-          float d = ddx * ddx;
-          d += ddy * ddy;
-          d += ddz * ddz;
-          int idx = __float_as_int(p.w);
-          if (d < bd[K - 1] || (d == bd[K - 1] && idx < bi[K - 1])) {
-            // sorted insertion, fully unrolled so the arrays stay in registers
-            bd[K - 1] = d; bi[K - 1] = idx; bj[K - 1] = j;
-#pragma unroll
-            for (int k = K - 1; k > 0; --k) {
-              bool sw = bd[k - 1] > bd[k] || (bd[k - 1] == bd[k] && bi[k - 1] > bi[k]);
-              float td = sw ? bd[k - 1] : bd[k];
-              int ti = sw ? bi[k - 1] : bi[k];
-              int tj = sw ? bj[k - 1] : bj[k];
-              bd[k - 1] = sw ? bd[k] : bd[k - 1];
-              bi[k - 1] = sw ? bi[k] : bi[k - 1];
-              bj[k - 1] = sw ? bj[k] : bj[k - 1];
-              bd[k] = td; bi[k] = ti; bj[k] = tj;
-            }
-          }
-        }
-      }
+  for (int k = 0; k < K; ++k) {
+    const bool ok = bi[k] != INT_MAX && !(cut && !(bd[k] < radius_sq));
+    const size_t o = size_t(i) * K + k;
+    idx[o] = ok ? bi[k] : -1;
+    sqd[o] = ok ? bd[k] : INFINITY;
+    if (nbr) {
+      const float4 p = ok ? map[bj[k]] : make_float4(0, 0, 0, 0);
+      nbr[3 * o + 0] = p.x; nbr[3 * o + 1] = p.y; nbr[3 * o + 2] = p.z;
     }
   }
 }
 
-template <int K>
-__global__ void k_knn(const float4 *__restrict__ query, int m, float radius_sq, const float4 *__restrict__ map,
-                      const int *__restrict__ cells, GridDesc g, int32_t *__restrict__ idx, float *__restrict__ sqd, int kout) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
-  float4 q4 = query[i];
-  float bd[K]; int bi[K], bj[K];
-  knn_scan<K>(Vec3<float>(q4.x, q4.y, q4.z), map, cells, g, bd, bi, bj);
-  for (int k = 0; k < kout; ++k) {
-    bool ok = bi[k] != INT_MAX && bd[k] < radius_sq;
-    idx[i * kout + k] = ok ? bi[k] : -1;
-    sqd[i * kout + k] = ok ? bd[k] : INFINITY;
-  }
+template <int K, int LPQ>
+static void launch_knn_walk_as(const float4 *query, int m, int cut, float radius_sq, const float4 *map_sorted, const int *cells, const GridDesc &g,
+                               int32_t *idx, float *sqd, float *nbr, hipStream_t s) {
+  hipLaunchKernelGGL((k_nn_walk<K, LPQ>), dim3(cdiv((long long)m * LPQ, KNN_WALK_THREADS)), dim3(KNN_WALK_THREADS), 0, s, query, m, cut, radius_sq,
+                     map_sorted, cells, g, idx, sqd, nbr);
 }
 
 void launch_knn(const float4 *query, int m, int k, float radius_sq, const float4 *map_sorted, const int *cells, const GridDesc &g,
                 int32_t *idx, float *sqd, hipStream_t s) {
   if (m <= 0) return;
-  if (k == 1) hipLaunchKernelGGL(k_knn<1>, dim3(cdiv(m, 128)), dim3(128), 0, s, query, m, radius_sq, map_sorted, cells, g, idx, sqd, k);
-  else hipLaunchKernelGGL(k_knn<5>, dim3(cdiv(m, 128)), dim3(128), 0, s, query, m, radius_sq, map_sorted, cells, g, idx, sqd, k);
+  if (k == 1) launch_knn_walk_as<1, 8>(query, m, 1, radius_sq, map_sorted, cells, g, idx, sqd, nullptr, s);
+  else if (k == 5) launch_knn_walk_as<5, 8>(query, m, 1, radius_sq, map_sorted, cells, g, idx, sqd, nullptr, s);
+  else throw DeviceError("launch_knn: k is 1 or 5");
+  LIO_HIP(hipGetLastError());
+}
+
+void launch_knn_walk(const float4 *query, int m, int lanes_per_query, const float4 *map_sorted, const int *cells, const GridDesc &g,
+                     int32_t *idx, float *sqd, float *nbr_xyz, hipStream_t s) {
+  if (m <= 0) return;
+  if (lanes_per_query == 1) launch_knn_walk_as<5, 1>(query, m, 0, 0.f, map_sorted, cells, g, idx, sqd, nbr_xyz, s);
+  else if (lanes_per_query == 4) launch_knn_walk_as<5, 4>(query, m, 0, 0.f, map_sorted, cells, g, idx, sqd, nbr_xyz, s);
+  else if (lanes_per_query == 8) launch_knn_walk_as<5, 8>(query, m, 0, 0.f, map_sorted, cells, g, idx, sqd, nbr_xyz, s);
+  else throw DeviceError("launch_knn_walk: lanes per query is 1, 4 or 8");
   LIO_HIP(hipGetLastError());
 }
 

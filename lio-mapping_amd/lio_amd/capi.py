@@ -265,6 +265,7 @@ _TEST_SIGS = {
     "lio_est_eval_lidar_moments": (C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p, C.POINTER(C.c_int)]),
     "lio_est_force_moments_per_lane": (C.c_int, [C.c_void_p, C.c_int]),
     "lio_est_batch_get_moments": (C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
+    "lio_knn_walk": (C.c_int, [c_float_p, C.c_size_t, c_float_p, C.c_size_t, C.c_float, C.c_int, c_int32_p, c_float_p, c_float_p]),
 }
 
 
@@ -397,6 +398,18 @@ class LioLib:
             self.dll.lio_knn(_fp(m_), m_.shape[0], _fp(q_), q_.shape[0], k, radius_sq, idx.ctypes.data_as(c_int32_p), _fp(sqd)), "lio_knn"
         )
         return idx, sqd
+
+    def knn_walk(self, map_xyzi, query_xyzi, cell, lanes_per_query):
+        """the product's five-nearest walk on its own (include/lio_test_hooks.h: lio_knn_walk), no radius cut ->
+        (idx (m, 5) int32, -1 = missing; sqd (m, 5) fp32, +inf = missing; nbr_xyz (m, 5, 3) the points the plane fit would load)"""
+        m_ = _f32(map_xyzi).reshape(-1, 4)
+        q_ = _f32(query_xyzi).reshape(-1, 4)
+        idx = np.zeros((q_.shape[0], 5), dtype=np.int32)
+        sqd = np.zeros((q_.shape[0], 5), dtype=np.float32)
+        nbr = np.zeros((q_.shape[0], 5, 3), dtype=np.float32)
+        _chk(self.dll.lio_knn_walk(_fp(m_), m_.shape[0], _fp(q_), q_.shape[0], float(cell), int(lanes_per_query),
+                                   idx.ctypes.data_as(c_int32_p), _fp(sqd), _fp(nbr)), "lio_knn_walk")
+        return idx, sqd, nbr
 
     def calculate_features(self, map_xyzi, stack_xyzi, T: TransformF, min_match_sq_dis=1.0, min_plane_dis=0.2):
         m_ = _f32(map_xyzi).reshape(-1, 4)

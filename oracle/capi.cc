@@ -1,7 +1,13 @@
 // oracle/capi.cc — TEST INFRASTRUCTURE ONLY (CPU oracle).  Not part of the product.
 // Implements include/lio_c.h on top of the CPU restatement so tests/ can drive both back ends
 // through the same symbols.  Built by oracle/Makefile into oracle/liblio_oracle.so.
+#include <algorithm>
+#include <cmath>
 #include <cstring>
+#include <limits>
+#include <map>
+#include <utility>
+#include <vector>
 #include <new>
 
 #include "../include/lio_c.h"
@@ -400,6 +406,71 @@ int lio_knn(const float *map, size_t n_map, const float *query, size_t m, int k,
       bool ok = j < f && !(radius_sq > 0 && !(sd[j] < radius_sq));
       idx[i * k + j] = ok ? id[j] : -1;
       sqd[i * k + j] = ok ? sd[j] : std::numeric_limits<float>::infinity();
+    }
+  }
+  return LIO_OK;
+}
+// lio_knn_walk (include/lio_test_hooks.h): the contract of the product's cell walk as a plain serial loop.  Points are binned by
+// int(floorf(v * inv_cell)) in fp32; a query sees the points of the 27 cells around its own, ranks them by (fp32 distance, index).
+int lio_knn_walk(const float *map, size_t n_map, const float *query, size_t m, float cell, int lanes_per_query, int32_t *idx, float *sqd,
+                 float *nbr_xyz) {
+  if ((!map && n_map) || (!query && m) || !idx || !sqd || !nbr_xyz || !(cell > 0) || !std::isfinite(cell)) return LIO_ERR_ARG;
+  if (!(lanes_per_query == 1 || lanes_per_query == 4 || lanes_per_query == 8)) return LIO_ERR_ARG;
+  const float inv_cell = 1.0f / cell;
+  auto coord = [&](float v) { return int(std::floor(v * inv_cell)); };
+  int lo[3], dims[3];
+  for (int d = 0; d < 3; ++d) {
+    float mn = 3.4e38f, mx = -3.4e38f;
+    for (size_t i = 0; i < n_map; ++i) { const float v = map[4 * i + d]; if (std::isfinite(v)) { mn = std::min(mn, v); mx = std::max(mx, v); } }
+    if (n_map == 0) mn = mx = 0.f;
+    lo[d] = coord(mn) - 1;
+    dims[d] = coord(mx) + 1 - lo[d] + 1;
+  }
+  auto cell_id = [&](const int c[3]) { return (long long)c[0] + (long long)dims[0] * ((long long)c[1] + (long long)dims[1] * (long long)c[2]); };
+  std::map<long long, std::vector<int>> bins;
+  for (size_t i = 0; i < n_map; ++i) {
+    int c[3];
+    for (int d = 0; d < 3; ++d) c[d] = std::min(std::max(coord(map[4 * i + d]) - lo[d], 0), dims[d] - 1);
+    bins[cell_id(c)].push_back(int(i));
+  }
+  std::vector<std::pair<uint32_t, int>> cand;
+  for (size_t i = 0; i < m; ++i) {
+    const float *q = query + 4 * i;
+    cand.clear();
+    int c[3] = {0, 0, 0};
+    bool in = std::isfinite(q[0]) && std::isfinite(q[1]) && std::isfinite(q[2]);
+    for (int d = 0; d < 3 && in; ++d) { c[d] = coord(q[d]) - lo[d]; in = c[d] >= 0 && c[d] < dims[d]; }
+    if (in)
+      for (int z = std::max(c[2] - 1, 0); z <= std::min(c[2] + 1, dims[2] - 1); ++z)
+        for (int y = std::max(c[1] - 1, 0); y <= std::min(c[1] + 1, dims[1] - 1); ++y)
+          for (int x = std::max(c[0] - 1, 0); x <= std::min(c[0] + 1, dims[0] - 1); ++x) {
+            const int cc[3] = {x, y, z};
+            auto it = bins.find(cell_id(cc));
+            if (it == bins.end()) continue;
+            for (int j : it->second) {
+              const float dx = map[4 * j] - q[0], dy = map[4 * j + 1] - q[1], dz = map[4 * j + 2] - q[2];
+              float d = dx * dx;
+              d += dy * dy;
+              d += dz * dz;
+              uint32_t bits;
+              std::memcpy(&bits, &d, 4);
+              if (bits <= 0x7f800000u) cand.emplace_back(bits, j);   // a NaN distance (overflow of a far-off point) ranks nowhere
+            }
+          }
+    const size_t keep = std::min<size_t>(5, cand.size());
+    std::partial_sort(cand.begin(), cand.begin() + keep, cand.end());
+    for (size_t k = 0; k < 5; ++k) {
+      const size_t o = i * 5 + k;
+      if (k < keep) {
+        const int j = cand[k].second;
+        idx[o] = j;
+        std::memcpy(&sqd[o], &cand[k].first, 4);
+        for (int d = 0; d < 3; ++d) nbr_xyz[3 * o + d] = map[4 * j + d];
+      } else {
+        idx[o] = -1;
+        sqd[o] = std::numeric_limits<float>::infinity();
+        for (int d = 0; d < 3; ++d) nbr_xyz[3 * o + d] = 0.f;
+      }
     }
   }
   return LIO_OK;

@@ -78,7 +78,7 @@ def _declared_test_hooks():
 def test_each_test_hook_is_bound_and_exported_by_both_libraries(oracle):
     """include/lio_test_hooks.h: every hook bound in Python and exported by the product and the oracle"""
     hooks = _declared_test_hooks()
-    assert len(hooks) >= 3
+    assert len(hooks) >= 4 and "lio_knn_walk" in hooks
     assert set(hooks) == set(capi._TEST_SIGS.keys())
     assert not set(hooks) & set(_declared_symbols())
     dll = ctypes.CDLL(capi.HIP_LIB_PATH)
@@ -101,6 +101,21 @@ def test_test_hook_header_is_plain_c_and_links(tmp_path, oracle, lib):
                    "  if (lio_est_eval_lidar_moments(NULL, 1, NULL, NULL, &path) != LIO_ERR_ARG || path != 7) return 1;\n"
                    "  if (lio_est_batch_get_moments(NULL, 0, NULL, NULL) != LIO_ERR_ARG) return 2;\n"
                    "  if (lio_est_force_moments_per_lane(NULL, 0) != LIO_ERR_ARG) return 3;\n"
+                   "  {\n"
+                   "    float map[8] = {0, 0, 0, 0, 1, 1, 1, 0}, q[4] = {0, 0, 0, 0}, sqd[5] = {7, 7, 7, 7, 7}, nbr[15];\n"
+                   "    int32_t idx[5] = {7, 7, 7, 7, 7};\n"
+                   "    if (lio_knn_walk(NULL, 2, q, 1, 1.0f, 8, idx, sqd, nbr) != LIO_ERR_ARG) return 4;\n"
+                   "    if (lio_knn_walk(map, 2, NULL, 1, 1.0f, 8, idx, sqd, nbr) != LIO_ERR_ARG) return 5;\n"
+                   "    if (lio_knn_walk(map, 2, q, 1, 1.0f, 8, NULL, sqd, nbr) != LIO_ERR_ARG) return 6;\n"
+                   "    if (lio_knn_walk(map, 2, q, 1, 1.0f, 8, idx, NULL, nbr) != LIO_ERR_ARG) return 7;\n"
+                   "    if (lio_knn_walk(map, 2, q, 1, 1.0f, 8, idx, sqd, NULL) != LIO_ERR_ARG) return 8;\n"
+                   "    if (lio_knn_walk(map, 2, q, 1, 1.0f, 2, idx, sqd, nbr) != LIO_ERR_ARG) return 9;\n"
+                   "    if (lio_knn_walk(map, 2, q, 1, 1.0f, 0, idx, sqd, nbr) != LIO_ERR_ARG) return 10;\n"
+                   "    if (lio_knn_walk(map, 2, q, 1, 1.0f, 16, idx, sqd, nbr) != LIO_ERR_ARG) return 11;\n"
+                   "    if (lio_knn_walk(map, 2, q, 1, 0.0f, 8, idx, sqd, nbr) != LIO_ERR_ARG) return 12;\n"
+                   "    if (lio_knn_walk(map, 2, q, 1, -1.0f, 8, idx, sqd, nbr) != LIO_ERR_ARG) return 13;\n"
+                   "    if (idx[0] != 7 || sqd[4] != 7) return 14;   /* refused before anything is written */\n"
+                   "  }\n"
                    '  puts("hooks ok");\n  return 0;\n}\n')
     exe = tmp_path / "hooks"
     libdir, libname = os.path.dirname(path), os.path.basename(path)
