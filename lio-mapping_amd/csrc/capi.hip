@@ -567,7 +567,7 @@ int lio_knn(const float *map, size_t n_map, const float *query, size_t m, int k,
     float mn[3], mx[3];
     host_bounds(map, n_map, mn, mx);
     if (n_map == 0) { mn[0] = mn[1] = mn[2] = 0; mx[0] = mx[1] = mx[2] = 0; }
-    sc.grid.build(sc.a.p, n_map, mn, mx, std::sqrt(radius_sq) * 1.0001f + 1e-6f, sc.s);
+    sc.grid.build(sc.a.p, n_map, mn, mx, knn_cell_edge(radius_sq), sc.s);
     launch_knn(sc.b.p, int(m), k, radius_sq, sc.grid.sorted(), sc.grid.cells(), sc.grid.desc(), sc.idx.p, sc.sqd.p, sc.s);
     if (m) {
       LIO_HIP(hipMemcpyAsync(idx, sc.idx.p, m * k * sizeof(int32_t), hipMemcpyDeviceToHost, sc.s));
@@ -618,7 +618,7 @@ int lio_calculate_features(const float *map, size_t n_map, const float *stack, s
     float mn[3], mx[3];
     host_bounds(map, n_map, mn, mx);
     if (n_map == 0) { mn[0] = mn[1] = mn[2] = 0; mx[0] = mx[1] = mx[2] = 0; }
-    sc.grid.build(sc.a.p, n_map, mn, mx, std::sqrt(mm) * 1.0001f + 1e-6f, sc.s);
+    sc.grid.build(sc.a.p, n_map, mn, mx, knn_cell_edge(mm), sc.s);
     FeatArgs fa{};
     fa.nframes = 1; fa.max_M = int(m); fa.min_match_sq_dis = mm; fa.min_plane_dis = mp;
     fa.fr[0].stack = sc.b.p; fa.fr[0].M = int(m); fa.fr[0].slot_off = 0; fa.fr[0].tf_index = 0;

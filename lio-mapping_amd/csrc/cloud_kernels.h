@@ -5,6 +5,7 @@
 //   laser-odom rows/update      : Estimator::CalculateLaserOdom (Estimator.cc:1242-1359)
 //   deskew                      : TransformToEnd (Estimator.cc:62-103)
 #pragma once
+#include <cmath>
 #include <cstdint>
 
 #include "dev.h"
@@ -71,6 +72,21 @@ struct GridDesc {
   float inv_cell;
   int n_points;
 };
+
+// Cell edge >= sqrt(min_match_sq_dis): the 27-cell neighbourhood then holds every point that can pass the d2[4] < min_match_sq_dis
+// gate (Estimator.cc:1021).  mapping.hip, kf_batch.hip and odometry.hip size their grids by an expression of their own (no + 1e-6f).
+inline float knn_cell_edge(float min_match_sq_dis) { return std::sqrt(min_match_sq_dis) * 1.0001f + 1e-6f; }
+// inv_cell, origin, dims of the grid over [mn, mx] with one border cell on every side; returns the number of cells
+inline size_t grid_extent(GridDesc &g, const float mn[3], const float mx[3], float cell) {
+  g.inv_cell = 1.0f / cell;
+  size_t ncells = 1;
+  for (int d = 0; d < 3; ++d) {
+    const int lo = int(std::floor(mn[d] * g.inv_cell)) - 1, hi = int(std::floor(mx[d] * g.inv_cell)) + 1;
+    g.origin[d] = lo; g.dims[d] = hi - lo + 1;
+    ncells *= size_t(g.dims[d]);
+  }
+  return ncells;
+}
 
 class KnnGrid {
  public:

@@ -449,16 +449,8 @@ __global__ void k_cell_place(const float4 *__restrict__ pts, const uint32_t *__r
 }
 
 void KnnGrid::build(const float4 *pts, size_t n, const float mn[3], const float mx[3], float cell, hipStream_t s) {
-  desc_.inv_cell = 1.0f / cell;
   desc_.n_points = int(n);
-  size_t ncells = 1;
-  for (int d = 0; d < 3; ++d) {
-    int lo = int(std::floor(mn[d] * desc_.inv_cell)) - 1;
-    int hi = int(std::floor(mx[d] * desc_.inv_cell)) + 1;
-    desc_.origin[d] = lo;
-    desc_.dims[d] = hi - lo + 1;
-    ncells *= size_t(desc_.dims[d]);
-  }
+  const size_t ncells = grid_extent(desc_, mn, mx, cell);
   if (ncells > (size_t(1) << 30)) throw DeviceError("KnnGrid: cell table too large");
   cells_.reserve(ncells + 1);
   if (cnt_.cap < ncells + 1 || cnt_dirty_) {   // a fresh table starts zeroed; after that k_cell_place leaves it zeroed (no fill per build)

@@ -62,8 +62,9 @@ class EstimatorBatch {
   // (S 16 x 16 row-major, cost, count) — and the T_{pivot<-i} of that point (Wo x 12: R row-major, t).  false: the window was not
   // solved on the device.  Waits for the batch.
   bool GetMoments(int w, double *out, double *Rt);
-  // lio_est_get_features of a member whose last Solve() ran on the device: its feature slots live in the batch's arrays
-  size_t GetFeatures(int w, int frame, double *pt, double *co, double *sc);
+  // lio_est_get_features of a member whose last Solve() ran on the device: its feature slots live in the batch's arrays, at the
+  // window's own slot offsets behind these pointers.  Waits for the batch.
+  void FeatureSlots(int w, const uint8_t **valid, const float4 **coef, const float **score);
   hipStream_t stream() const { return stream_; }
   // execution choices (batch_kernels.h: BatchKnobs) by name: lanes_per_query, loop_groups, aux_threads, finish_threads, time_kernels;
   // false: unknown name or a value the knob does not take

@@ -269,26 +269,10 @@ bool EstimatorBatch::GetMoments(int w, double *out, double *Rt) {
   return true;
 }
 
-size_t EstimatorBatch::GetFeatures(int w, int frame, double *pt, double *co, double *sc) {
-  const Estimator *e = win_[size_t(w)].e;
-  if (frame < 0 || frame > e->W_ || e->nslots_[frame] == 0) return 0;
+void EstimatorBatch::FeatureSlots(int w, const uint8_t **valid, const float4 **coef, const float **score) {
   Sync();
-  const size_t off = size_t(h_win_.p[w].slot_base) + size_t(e->slot_off_[frame]), ns = size_t(e->nslots_[frame]);
-  const size_t M = e->stacks_[frame].n;
-  const std::vector<uint8_t> v = fetch(valid_all_.p + off, ns);
-  const std::vector<float4> c = fetch(coef_all_.p + off, ns);
-  const std::vector<float> s = fetch(score_all_.p + off, ns);
-  const std::vector<float4> p = fetch(e->stacks_[frame].buf.p, M);
-  size_t k = 0;
-  for (size_t i = 0; i < ns; ++i) {
-    if (!v[i]) continue;
-    const float4 &pp = p[i % M];
-    if (pt) { pt[3 * k] = pp.x; pt[3 * k + 1] = pp.y; pt[3 * k + 2] = pp.z; }
-    if (co) { co[4 * k] = c[i].x; co[4 * k + 1] = c[i].y; co[4 * k + 2] = c[i].z; co[4 * k + 3] = c[i].w; }
-    if (sc) sc[k] = s[i];
-    ++k;
-  }
-  return k;
+  const size_t off = size_t(h_win_.p[w].slot_base);
+  *valid = valid_all_.p + off; *coef = coef_all_.p + off; *score = score_all_.p + off;
 }
 
 int EstimatorBatch::Solve(lio_solve_report *reps) {
@@ -312,7 +296,7 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
     Wn.prior_used.reset();
     if (Wn.device) {
       e->JoinMarg(false);
-      e->BatchDescribe(bw);
+      Wn.max_slots = e->BatchDescribe(bw);
     } else {
       std::memset(&bw, 0, sizeof(bw));
       bw.inv_leaf = 1.f;
@@ -389,13 +373,7 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
     }
     if (Wn.device && (vo.params.overflow || vo.range_overflow)) Wn.device = false;   // PCL's own index / "leaf too small" / keys beyond the passes: the single-window path has those forms
     if (Wn.device && vo.count > 0) {
-      const float cell = std::sqrt(Wn.e->cfg_.min_match_sq_dis) * 1.0001f + 1e-6f;
-      G.g.inv_cell = 1.0f / cell;
-      for (int d = 0; d < 3; ++d) {
-        const int lo = int(std::floor(vo.params.mn[d] * G.g.inv_cell)) - 1, hi = int(std::floor(vo.params.mx[d] * G.g.inv_cell)) + 1;
-        G.g.origin[d] = lo; G.g.dims[d] = hi - lo + 1;
-        ncells *= size_t(G.g.dims[d]);
-      }
+      ncells = grid_extent(G.g, vo.params.mn, vo.params.mx, knn_cell_edge(Wn.e->cfg_.min_match_sq_dis));
       if (ncells > (size_t(1) << 28)) { Wn.device = false; ncells = 1; G.g.dims[0] = G.g.dims[1] = G.g.dims[2] = 1; }
       else { G.n_filtered = vo.count; G.g.n_points = vo.count; }
     }
@@ -455,11 +433,8 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
     Win &Wn = win_[w];
     if (!Wn.device) continue;
     Estimator *e = Wn.e;
-    int ms = 0;
-    for (int i = e->W_ - e->Wo_ + 1; i <= e->W_; ++i) ms = std::max(ms, e->nslots_[i]);
-    Wn.max_slots = ms;
-    Wn.bpf = batch_blocks_per_frame(ms);
-    if (e->total_slots_ == 0 || !e->BatchPackProblem(Wn.bpf, h_pb_.p[w], h_st_.p[w], &Wn.prior_used)) { Wn.device = false; continue; }
+    Wn.bpf = batch_blocks_per_frame(Wn.max_slots);
+    if (h_win_.p[w].n_slots == 0 || !e->BatchPackProblem(Wn.bpf, h_pb_.p[w], h_st_.p[w], &Wn.prior_used)) { Wn.device = false; continue; }
     Wn.part_off = part_total;
     part_total += size_t(e->Wo_) * Wn.bpf * LIO_MOMENT_OUT;
     max_bpf = std::max(max_bpf, Wn.bpf); max_wo = std::max(max_wo, e->Wo_); max_npad = std::max(max_npad, h_pb_.p[w].n_pad);
@@ -515,16 +490,10 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
     S.marg = d_mg_.p + w;
     if (!Wn.device) continue;
     Estimator *e = Wn.e;
-    e->BatchSetOdom(h_odom_.p[w]);
-    const int pivot = e->W_ - e->Wo_;
+    e->ApplyOdomState(h_odom_.p[w]);
     double *slab = slab_.p + size_t(w) * lay_.total;
     S.active = 1; S.nframes = e->Wo_; S.bpf = Wn.bpf;
-    for (int i = 1; i <= e->Wo_; ++i) {
-      MomentFrame &f = S.fr[i - 1];
-      const int idx = pivot + i;
-      f.stack = e->stacks_[idx].buf.p; f.M = std::max<int>(1, int(e->stacks_[idx].n));
-      f.slot_off = h_win_.p[w].slot_base + e->slot_off_[idx]; f.nslots = e->nslots_[idx]; f.slot_begin = 0; f.slot_end = f.nslots;
-    }
+    e->FillMomentFrames(S.fr, h_win_.p[w].slot_base);   // (BatchEligible: not sharded)
     S.pb = d_pb_.p + w; S.st = d_st_.p + w;
     S.prior_mats = slab + lay_.prior[Wn.cur]; S.next_prior_mats = slab + lay_.prior[1 - Wn.cur];
     S.partials = partials_.p + Wn.part_off;

@@ -35,7 +35,7 @@ struct EstConfig {
   double max_solver_time = 0.10;
   int extrinsic_stage = 2;
   int init_window_factor = 3;
-  // execution switches (lio_est_config's trailing block; environment overrides are applied in the constructor)
+  // execution switches (lio_est_config's trailing block)
   bool device_solve = false, inline_marg = false, stream_sync = false;
   int resident_moments = 0;
 };
@@ -153,6 +153,16 @@ class MargWorker {
 
 class EstimatorBatch;
 
+// One window as BOTH solve paths read it (Estimator::PlanWindow): the single-window path fills ConcatArgs / SolveSetup / FeatArgs from
+// it, the batched path BatchWin.  The slot layout it goes with is the estimator's slot_off_ / nslots_ / total_slots_.
+struct WindowPlan {
+  int pivot, keep_mult;            // keep_mult: slots per point of the newest frame (10 rounds' features kept, else 1)
+  ConcatSeg seg[LIO_MAX_FRAMES];   // local map (Estimator.cc:1480-1507): the pivot's cloud as it is, frames pivot+1 .. W-1 transformed, intensity = frame index
+  int nseg, n_local;
+  float tf[LIO_MAX_FRAMES][8];     // local transform of frame i >= first_frame (qx qy qz qw px py pz 0)
+  int max_slots;                   // largest nslots_ of frames pivot+1 .. W (the newest frame's is an upper bound until the rounds are done)
+};
+
 class Estimator {
  public:
   explicit Estimator(const EstConfig &cfg);
@@ -179,15 +189,18 @@ class Estimator {
   // stage over all windows of the batch)
   bool BatchEligible() const;
   // host half of BuildLocalMap (Estimator.cc:1361-1646): segments of the local map, frames, local transforms, slot layout.
-  // Offsets are the window's own (from 0); the batch shifts them to its arrays.
-  void BatchDescribe(BatchWin &bw);
+  // Offsets are the window's own (from 0); the batch shifts them to its arrays.  Returns WindowPlan::max_slots.
+  int BatchDescribe(BatchWin &bw);
   // the problem of Estimator.cc:1660-1921 as the device loop reads it; *prior = the marginalization prior the problem uses.
   // false: this window's problem does not fit the device loop.
   bool BatchPackProblem(int bpf, DevProblem &pb, DevState &st, std::shared_ptr<MargPrior> *prior);
   // after the device loop: DoubleToVector, the report, convergence_flag_.  true: the window marginalises now — mg is filled
   // (linearisation point, layout) and *shell is the new prior without its matrices (they are computed on the device).
   bool BatchFinish(const DevState &st, const std::shared_ptr<MargPrior> &prior_used, lio_solve_report &R, DevMarg &mg, std::shared_ptr<MargPrior> *shell);
-  void BatchSetOdom(const OdomState &st);   // CalculateLaserOdom's outcome as the rounds left it (Estimator.cc:1242-1359)
+  void ApplyOdomState(const OdomState &st);   // CalculateLaserOdom's outcome as the rounds left it (Estimator.cc:1242-1359)
+  // frames pivot+1 .. W as the moments kernels read them (this rank's share of the slots when sharded); R, t are the caller's.
+  // Returns the largest frame's slot count.
+  int FillMomentFrames(MomentFrame *fr, int slot_base) const;
 
   // test hooks
   void SetWindow(const double *Ps, const double *Rs, const double *Vs, const double *Bas, const double *Bgs, const double g[3]);
@@ -261,12 +274,15 @@ class Estimator {
   hipStream_t stream() const { return stream_; }
 
  private:
-  friend class EstimatorBatch;
+  friend class EstimatorBatch;   // the adoption handshake only: device_id_, AdoptStream / ReleaseAdoptedStream, feat_batch_ / feat_batch_w_
   struct ResidentScope { Estimator *e; ~ResidentScope() { e->resident_.End(e->stream_); } };   // closes a solve scope on every exit path
   void Init(), Close() noexcept;
   struct HostState;  // snapshot payload
   Rigidd LidarPose(int i, const Rigidd &lb) const;
   Rigidf RelTransform(int i, const Rigidd &T_pivot, const Rigidd &lb) const;
+  bool KeepFeatures() const { return cfg_.keep_features && cfg_.imu_factor; }
+  WindowPlan PlanWindow(int first_frame);   // also writes the slot layout
+  void AssembleSystem(WindowParams &P, WindowSystem &sys) const;   // the problem of Estimator.cc:1660-1921 without the lidar callbacks
   void VectorToParams(WindowParams &P) const;
   void ParamsToVector(const WindowParams &P);
   void FillMomentArgs(MomentArgs &ma, int &max_slots) const;

@@ -220,16 +220,17 @@ size_t Estimator::GetLocalMap(float *out) {
 }
 
 size_t Estimator::GetFeatures(int frame, double *pt, double *co, double *sc) {
-  if (feat_batch_) return feat_batch_->GetFeatures(feat_batch_w_, frame, pt, co, sc);   // the last solve ran in a batch, on the device
   if (frame < 0 || frame > W_ || nslots_[frame] == 0) return 0;
+  const uint8_t *valid = f_valid_.p; const float4 *coef = f_coef_.p; const float *score = f_score_.p;
+  if (feat_batch_) feat_batch_->FeatureSlots(feat_batch_w_, &valid, &coef, &score);   // the last solve ran in a batch: the slots are in its arrays
   const int off = slot_off_[frame], ns = nslots_[frame];
   const size_t M = stacks_[frame].n;
   std::vector<uint8_t> v(ns);
   std::vector<float4> c(ns), p(M);
   std::vector<float> s(ns);
-  LIO_HIP(hipMemcpyAsync(v.data(), f_valid_.p + off, ns, hipMemcpyDeviceToHost, stream_));
-  LIO_HIP(hipMemcpyAsync(c.data(), f_coef_.p + off, ns * sizeof(float4), hipMemcpyDeviceToHost, stream_));
-  LIO_HIP(hipMemcpyAsync(s.data(), f_score_.p + off, ns * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  LIO_HIP(hipMemcpyAsync(v.data(), valid + off, ns, hipMemcpyDeviceToHost, stream_));
+  LIO_HIP(hipMemcpyAsync(c.data(), coef + off, ns * sizeof(float4), hipMemcpyDeviceToHost, stream_));
+  LIO_HIP(hipMemcpyAsync(s.data(), score + off, ns * sizeof(float), hipMemcpyDeviceToHost, stream_));
   LIO_HIP(hipMemcpyAsync(p.data(), stacks_[frame].buf.p, M * sizeof(float4), hipMemcpyDeviceToHost, stream_));
   LIO_HIP(hipStreamSynchronize(stream_));
   size_t k = 0;
@@ -430,27 +431,42 @@ void Estimator::FusePivotOnce() {
   init_local_map_ = true;
 }
 
+WindowPlan Estimator::PlanWindow(int first_frame) {
+  WindowPlan pl{};
+  const int pivot = pl.pivot = W_ - Wo_;
+  const Rigidd lb = toDouble(transform_lb_);
+  const Rigidd T_pivot = LidarPose(pivot, lb);
+  pl.keep_mult = KeepFeatures() ? 10 : 1;
+  total_slots_ = 0;
+  for (int i = 0; i <= W_; ++i) {
+    slot_off_[i] = int(total_slots_);
+    nslots_[i] = 0;
+    if (i > pivot) { nslots_[i] = int(stacks_[i].n) * ((i == W_) ? pl.keep_mult : 1); total_slots_ += size_t(nslots_[i]); }
+    pl.max_slots = std::max(pl.max_slots, nslots_[i]);
+    if (i < first_frame) continue;
+    const Rigidf tf = RelTransform(i, T_pivot, lb);
+    const Rigidf T = fromAffine(linearOf(tf), tf.pos);
+    float *o = pl.tf[i];
+    o[0] = T.rot.x; o[1] = T.rot.y; o[2] = T.rot.z; o[3] = T.rot.w; o[4] = T.pos.x; o[5] = T.pos.y; o[6] = T.pos.z;
+    if (i < pivot || i == W_) continue;
+    ConcatSeg &sg = pl.seg[pl.nseg++];
+    sg.src = stacks_[i].buf.p; sg.n = int(stacks_[i].n); sg.dst_off = pl.n_local;
+    if (i == pivot) { sg.identity = 1; sg.set_intensity = 0; sg.intensity = 0; }
+    else { sg.identity = 0; sg.set_intensity = 1; sg.intensity = float(i); sg.tf = affineOf(tf); }
+    pl.n_local += sg.n;
+  }
+  return pl;
+}
+
 void Estimator::BuildLocalMap(lio_solve_report *rep) {
   const double t0 = now_ms();
   feat_batch_ = nullptr; feat_batch_w_ = -1;   // the feature slots are this handle's own again
-  const int pivot = W_ - Wo_;
-  const Rigidd lb = toDouble(transform_lb_);
-  const Rigidd T_pivot = LidarPose(pivot, lb);
   FusePivotOnce();
-  std::vector<Rigidf> local_transforms(W_ + 1);
+  const WindowPlan pl = PlanWindow(0);
+  const int pivot = pl.pivot, total = pl.n_local, keep_mult = pl.keep_mult;
   ConcatArgs ca{};
-  int total = 0;
-  for (int i = 0; i <= W_; ++i) {
-    Rigidf tf = RelTransform(i, T_pivot, lb);
-    local_transforms[i] = fromAffine(linearOf(tf), tf.pos);
-    if (i < pivot || i == W_) continue;
-    ConcatSeg &sg = ca.seg[ca.nseg++];
-    sg.src = stacks_[i].buf.p; sg.n = int(stacks_[i].n); sg.dst_off = total;
-    if (i == pivot) { sg.identity = 1; sg.set_intensity = 0; sg.intensity = 0; }
-    else { sg.identity = 0; sg.set_intensity = 1; sg.intensity = float(i); sg.tf = affineOf(tf); }
-    total += sg.n;
-  }
-  ca.total = total;
+  std::copy(pl.seg, pl.seg + pl.nseg, ca.seg);
+  ca.nseg = pl.nseg; ca.total = total;
   local_.buf.reserve(std::max(total, 1));
   int th = timers_.begin(KT_CONCAT, 32.0 * total, stream_);
   launch_transform_concat(ca, local_.buf.p, stream_);
@@ -461,34 +477,17 @@ void Estimator::BuildLocalMap(lio_solve_report *rep) {
   local_filtered_.n = vox_.run(local_.buf.p, local_.n, cfg_.surf_filter_size, local_filtered_.buf, stream_, &vp);
   timers_.end(th, stream_);
   const double t1 = now_ms();
-  // K-NN grid: cell edge >= sqrt(min_match_sq_dis) so the 27-cell neighbourhood holds every point that can
-  // pass the d2[4] < min_match_sq_dis gate (Estimator.cc:1021); beyond it the reference rejects anyway.
-  const float cell = std::sqrt(cfg_.min_match_sq_dis) * 1.0001f + 1e-6f;
   th = timers_.begin(KT_KNN_GRID, 32.0 * double(local_filtered_.n), stream_);
-  grid_.build(local_filtered_.buf.p, local_filtered_.n, vp.mn, vp.mx, cell, stream_);
+  grid_.build(local_filtered_.buf.p, local_filtered_.n, vp.mn, vp.mx, knn_cell_edge(cfg_.min_match_sq_dis), stream_);
   timers_.end(th, stream_);
-  // slot layout
-  const int keep_mult = (cfg_.keep_features && cfg_.imu_factor) ? 10 : 1;
-  total_slots_ = 0;
-  for (int i = 0; i <= W_; ++i) {
-    slot_off_[i] = int(total_slots_);
-    nslots_[i] = 0;
-    if (i > pivot) { nslots_[i] = int(stacks_[i].n) * ((i == W_) ? keep_mult : 1); total_slots_ += size_t(nslots_[i]); }
-  }
   f_valid_.reserve(std::max<size_t>(total_slots_, 1)); f_coef_.reserve(std::max<size_t>(total_slots_, 1)); f_score_.reserve(std::max<size_t>(total_slots_, 1));
   // feature flags cleared, local transforms and the newest frame's state on the device: one launch (cloud_kernels.h: SolveSetup)
-  std::vector<float> tfs(size_t(W_ + 1) * 8, 0.f);
   SolveSetup su{};
   su.ntf = W_ + 1;
-  for (int i = 0; i <= W_; ++i) {
-    const Rigidf &T = local_transforms[i];
-    float *o = &tfs[size_t(i) * 8];
-    o[0] = T.rot.x; o[1] = T.rot.y; o[2] = T.rot.z; o[3] = T.rot.w; o[4] = T.pos.x; o[5] = T.pos.y; o[6] = T.pos.z;
-    std::memcpy(su.tf[i], o, 8 * sizeof(float));
-  }
-  std::memcpy(su.odom_T, &tfs[size_t(W_) * 8], 8 * sizeof(float));
+  std::memcpy(su.tf, pl.tf, sizeof(float) * 8 * size_t(W_ + 1));
+  std::memcpy(su.odom_T, pl.tf[W_], 8 * sizeof(float));
   su.set_odom = cfg_.imu_factor ? 1 : 0;
-  d_transforms_.reserve(tfs.size());
+  d_transforms_.reserve(size_t(W_ + 1) * 8);
   launch_solve_setup(su, d_transforms_.p, d_odom_.p, f_valid_.p, total_slots_, stream_);
   // frames pivot+1 .. W-1 (and W when the IMU factor is off): one batched launch
   FeatArgs fa{};
@@ -521,7 +520,7 @@ void Estimator::BuildLocalMap(lio_solve_report *rep) {
     // transform and the convergence flag; later launches turn into no-ops)
     OdomState st{};
     bool have_state = false;  // a converged peek already brought the final state to the host
-    std::memcpy(st.T, &tfs[size_t(W_) * 8], 8 * sizeof(float));   // (on the device since launch_solve_setup)
+    std::memcpy(st.T, pl.tf[W_], 8 * sizeof(float));   // (on the device since launch_solve_setup)
     const int M = int(stacks_[W_].n);
     const bool mail = host_signal_ && !timers_.on;
     HostSignal sig{};
@@ -571,10 +570,7 @@ void Estimator::BuildLocalMap(lio_solve_report *rep) {
       st = *h_odom_.p;
       timers_.resolve();
     }
-    laser_odom_iters_ = st.iters;
-    laser_odom_kz_ = st.degenerate ? st.kz : 0;
-    laser_odom_transform_ = Rigidf(Quat<float>(st.T[3], st.T[0], st.T[1], st.T[2]), Vec3<float>(st.T[4], st.T[5], st.T[6]));
-    if (keep_mult > 1) nslots_[W_] = int(stacks_[W_].n) * std::max(1, st.iters);
+    ApplyOdomState(st);
   } else {
     LIO_HIP(hipStreamSynchronize(stream_));
     timers_.resolve();
@@ -635,14 +631,12 @@ void Estimator::LidarEval(const WindowParams &P, std::vector<FrameMoments> &m) {
   LidarWait(m);
 }
 
-void Estimator::FillMomentArgs(MomentArgs &ma, int &max_slots) const {
-  const int pivot = W_ - Wo_;
-  ma = MomentArgs{};
-  max_slots = 0;
+int Estimator::FillMomentFrames(MomentFrame *fr, int slot_base) const {
+  int max_slots = 0;
   for (int i = 1; i <= Wo_; ++i) {
-    MomentFrame &f = ma.fr[ma.nframes++];
-    const int idx = pivot + i;
-    f.stack = stacks_[idx].buf.p; f.M = std::max<int>(1, int(stacks_[idx].n)); f.slot_off = slot_off_[idx]; f.nslots = nslots_[idx];
+    MomentFrame &f = fr[i - 1];
+    const int idx = W_ - Wo_ + i;
+    f.stack = stacks_[idx].buf.p; f.M = std::max<int>(1, int(stacks_[idx].n)); f.slot_off = slot_base + slot_off_[idx]; f.nslots = nslots_[idx];
     f.slot_begin = 0; f.slot_end = f.nslots;
     if (Sharded()) {  // contiguous share of this frame's factor slots
       f.slot_begin = int((long long)f.nslots * shard_rank_ / shard_world_);
@@ -650,6 +644,13 @@ void Estimator::FillMomentArgs(MomentArgs &ma, int &max_slots) const {
     }
     max_slots = std::max(max_slots, f.nslots);
   }
+  return max_slots;
+}
+
+void Estimator::FillMomentArgs(MomentArgs &ma, int &max_slots) const {
+  ma = MomentArgs{};
+  ma.nframes = Wo_;
+  max_slots = FillMomentFrames(ma.fr, 0);
   ma.blocks_per_frame = moment_blocks_per_frame(max_slots);
   // With the resident form configured, BOTH paths use its partition (blocks per frame so that a lane holds <= per_lane
   // 64-slot chunks per wave, fp64-MFMA form): the launch path — taken when a pass cannot use the resident kernel (kernel timing, factor
@@ -730,31 +731,29 @@ int Estimator::EvalLidarMoments(int n_passes, const double *Rt, double *out) {
 
 bool Estimator::BenchBatchedMoments(int B, int reps, double *avg_ms, double *bytes) {
   if (B < 1 || reps < 1 || total_slots_ == 0 || !init_local_map_) return false;
-  const int pivot = W_ - Wo_;
   WindowParams P;
   VectorToParams(P);
   // replicate the feature slots and the stacks B times (distinct addresses: no cache reuse across windows)
   DBuf<uint8_t> valid_b; DBuf<float4> coef_b, stack_b;
   size_t stack_pts = 0;
-  for (int i = pivot + 1; i <= W_; ++i) stack_pts += stacks_[i].n;
+  for (int i = W_ - Wo_ + 1; i <= W_; ++i) stack_pts += stacks_[i].n;
   valid_b.reserve(size_t(B) * total_slots_); coef_b.reserve(size_t(B) * total_slots_); stack_b.reserve(std::max<size_t>(size_t(B) * stack_pts, 1));
-  std::vector<MomentFrame> frames;
+  std::vector<MomentFrame> frames(size_t(B) * Wo_, MomentFrame{});
   int max_slots = 0;
   double nres = 0;
   for (int b = 0; b < B; ++b) {
     LIO_HIP(hipMemcpyAsync(valid_b.p + size_t(b) * total_slots_, f_valid_.p, total_slots_, hipMemcpyDeviceToDevice, stream_));
     LIO_HIP(hipMemcpyAsync(coef_b.p + size_t(b) * total_slots_, f_coef_.p, total_slots_ * sizeof(float4), hipMemcpyDeviceToDevice, stream_));
     size_t off = size_t(b) * stack_pts;
+    MomentFrame *fr = frames.data() + size_t(b) * Wo_;
+    max_slots = FillMomentFrames(fr, int(size_t(b) * total_slots_));
     for (int i = 1; i <= Wo_; ++i) {
-      const int idx = pivot + i;
-      if (stacks_[idx].n) LIO_HIP(hipMemcpyAsync(stack_b.p + off, stacks_[idx].buf.p, stacks_[idx].n * sizeof(float4), hipMemcpyDeviceToDevice, stream_));
-      MomentFrame f{};
-      f.stack = stack_b.p + off; f.M = std::max<int>(1, int(stacks_[idx].n)); f.slot_off = int(size_t(b) * total_slots_) + slot_off_[idx];
-      f.nslots = nslots_[idx]; f.slot_begin = 0; f.slot_end = f.nslots;
+      MomentFrame &f = fr[i - 1];
+      const size_t n = stacks_[W_ - Wo_ + i].n;
+      if (n) LIO_HIP(hipMemcpyAsync(stack_b.p + off, f.stack, n * sizeof(float4), hipMemcpyDeviceToDevice, stream_));
+      f.stack = stack_b.p + off;
       relative_lidar_pose(P.pose[0].data(), P.pose[i].data(), P.ex.data(), f.R, f.t);
-      frames.push_back(f);
-      off += stacks_[idx].n;
-      max_slots = std::max(max_slots, f.nslots);
+      off += n;
       nres += f.nslots;
     }
   }
@@ -830,24 +829,9 @@ bool Estimator::SolveOptimizationHost(lio_solve_report *rep) {
   const double t_prep0 = now_ms();
   const int pivot = W_ - Wo_;
   WindowParams P;
-  VectorToParams(P);
-  P.ex_constant = (cfg_.extrinsic_stage == 0 || !cfg_.opt_extrinsic);
   WindowSystem sys;
-  sys.Wo = Wo_;
-  sys.use_lidar = cfg_.point_distance_factor;
-  sys.pim.assign(Wo_, nullptr);
-  if (cfg_.imu_factor)
-    for (int i = 0; i < Wo_; ++i) {
-      auto &pi = pre_integrations_[pivot + i + 1];
-      if (pi && pi->sum_dt <= 10.0) sys.pim[i] = pi;
-    }
   JoinMarg();  // the previous solve's marginalization has had the map + feature stages to finish
-  if (cfg_.marginalization_factor && last_marg_) sys.prior = last_marg_;
-  if (cfg_.prior_factor) {
-    sys.use_prior_factor = true;
-    Rigidd t = toDouble(transform_lb_);
-    sys.prior_pos = t.pos; sys.prior_rot = t.rot;
-  }
+  AssembleSystem(P, sys);
   sys.lidar_eval = [this](const WindowParams &Pq, std::vector<FrameMoments> &m) { LidarEval(Pq, m); };
   sys.lidar_launch = [this](const WindowParams &Pq) { LidarLaunch(Pq); };
   sys.lidar_wait = [this](std::vector<FrameMoments> &m) { LidarWait(m); };
@@ -938,6 +922,25 @@ bool Estimator::SolveOptimizationHost(lio_solve_report *rep) {
   if (g_debug_timing) std::fprintf(stderr, "[lio_hip timing] of which hipStreamSynchronize %.3f ms\n", dbg_sync_ms_);
   dbg_eval_ms_ = 0; dbg_eval_n_ = 0; dbg_sync_ms_ = 0;
   return true;
+}
+
+void Estimator::AssembleSystem(WindowParams &P, WindowSystem &sys) const {
+  VectorToParams(P);
+  P.ex_constant = (cfg_.extrinsic_stage == 0 || !cfg_.opt_extrinsic);
+  sys.Wo = Wo_;
+  sys.use_lidar = cfg_.point_distance_factor;
+  sys.pim.assign(Wo_, nullptr);
+  if (cfg_.imu_factor)
+    for (int i = 0; i < Wo_; ++i) {
+      auto &pi = pre_integrations_[W_ - Wo_ + i + 1];
+      if (pi && pi->sum_dt <= 10.0) sys.pim[i] = pi;
+    }
+  if (cfg_.marginalization_factor && last_marg_) sys.prior = last_marg_;   // (the caller has joined the marginalization)
+  if (cfg_.prior_factor) {
+    sys.use_prior_factor = true;
+    Rigidd t = toDouble(transform_lb_);
+    sys.prior_pos = t.pos; sys.prior_rot = t.rot;
+  }
 }
 
 void Estimator::SlideWindow() {
@@ -1034,7 +1037,7 @@ bool Estimator::Restore() {
 // Batched solve: the per-window host halves (est_batch.hip drives them)
 // ================================================================================================
 bool Estimator::BatchEligible() const {
-  if (!inited_ || cir_buf_count_ < W_ || false) return false;
+  if (!inited_ || cir_buf_count_ < W_) return false;
   if (!cfg_.imu_factor || !cfg_.point_distance_factor || Sharded() || rccl_comm_) return false;
   if (Wo_ < 1 || Wo_ > DS_MAX_WO || Wo_ > LIO_BW_MAX_STATIC + 1 || Wo_ > LIO_BW_MAX_SEG) return false;
   const int dim = 15 * (Wo_ + 1) + 6;
@@ -1042,71 +1045,41 @@ bool Estimator::BatchEligible() const {
   return true;
 }
 
-void Estimator::BatchDescribe(BatchWin &bw) {
+int Estimator::BatchDescribe(BatchWin &bw) {
   FusePivotOnce();
-  const int pivot = W_ - Wo_;
-  const Rigidd lb = toDouble(transform_lb_);
-  const Rigidd T_pivot = LidarPose(pivot, lb);
+  const WindowPlan pl = PlanWindow(W_ - Wo_);
   std::memset(&bw, 0, sizeof(bw));
   bw.inv_leaf = 1.0f / cfg_.surf_filter_size;
   bw.min_match_sq_dis = cfg_.min_match_sq_dis; bw.min_plane_dis = cfg_.min_plane_dis;
-  const int keep_mult = cfg_.keep_features ? 10 : 1;
-  bw.keep = cfg_.keep_features ? 1 : 0;
-  int total = 0;
-  total_slots_ = 0;
-  for (int i = 0; i <= W_; ++i) { slot_off_[i] = 0; nslots_[i] = 0; }
-  for (int i = pivot; i <= W_; ++i) {
-    const Rigidf tf = RelTransform(i, T_pivot, lb);
-    const Rigidf lt = fromAffine(linearOf(tf), tf.pos);
-    if (i < W_) {   // a segment of the local map (Estimator.cc:1480-1507)
-      BwSeg &sg = bw.seg[bw.nseg++];
-      sg.src = stacks_[i].buf.p; sg.n = int(stacks_[i].n); sg.dst_off = total;
-      if (i == pivot) { sg.identity = 1; sg.set_intensity = 0; sg.intensity = 0; }
-      else { sg.identity = 0; sg.set_intensity = 1; sg.intensity = float(i); sg.tf = affineOf(tf); }
-      total += sg.n;
-    }
-    if (i == pivot) continue;
+  bw.keep = pl.keep_mult > 1 ? 1 : 0;
+  for (; bw.nseg < pl.nseg; ++bw.nseg) {
+    const ConcatSeg &c = pl.seg[bw.nseg];
+    bw.seg[bw.nseg] = BwSeg{c.src, c.n, c.dst_off, c.identity, c.set_intensity, c.intensity, c.tf};
+  }
+  for (int i = pl.pivot + 1; i <= W_; ++i) {
     const int k = (i == W_) ? LIO_BW_MAX_STATIC : bw.nstatic;
-    float *o = bw.tf[k];
-    o[0] = lt.rot.x; o[1] = lt.rot.y; o[2] = lt.rot.z; o[3] = lt.rot.w; o[4] = lt.pos.x; o[5] = lt.pos.y; o[6] = lt.pos.z; o[7] = 0.f;
-    slot_off_[i] = int(total_slots_);
-    nslots_[i] = int(stacks_[i].n) * ((i == W_) ? keep_mult : 1);
-    total_slots_ += size_t(nslots_[i]);
+    std::memcpy(bw.tf[k], pl.tf[i], sizeof(bw.tf[k]));
     FeatFrame &f = (i == W_) ? bw.newest : bw.fr[bw.nstatic];
     f.stack = stacks_[i].buf.p; f.M = int(stacks_[i].n); f.slot_off = slot_off_[i]; f.tf_index = k;
     if (i < W_) ++bw.nstatic;
   }
-  bw.n_local = total;
+  bw.n_local = pl.n_local;
   bw.n_slots = int(total_slots_);
   bw.nb_round = bw.newest.M > 0 ? bw_round_blocks(bw.newest.M) : 0;
+  return pl.max_slots;
 }
 
-void Estimator::BatchSetOdom(const OdomState &st) {
+void Estimator::ApplyOdomState(const OdomState &st) {
   laser_odom_iters_ = st.iters;
   laser_odom_kz_ = st.degenerate ? st.kz : 0;
   laser_odom_transform_ = Rigidf(Quat<float>(st.T[3], st.T[0], st.T[1], st.T[2]), Vec3<float>(st.T[4], st.T[5], st.T[6]));
-  if (cfg_.keep_features) nslots_[W_] = int(stacks_[W_].n) * std::max(1, st.iters);
+  if (KeepFeatures()) nslots_[W_] = int(stacks_[W_].n) * std::max(1, st.iters);
 }
 
 bool Estimator::BatchPackProblem(int bpf, DevProblem &pb, DevState &st, std::shared_ptr<MargPrior> *prior) {
-  const int pivot = W_ - Wo_;
   WindowParams P;
-  VectorToParams(P);
-  P.ex_constant = (cfg_.extrinsic_stage == 0 || !cfg_.opt_extrinsic);
   WindowSystem sys;
-  sys.Wo = Wo_;
-  sys.use_lidar = cfg_.point_distance_factor;
-  sys.pim.assign(Wo_, nullptr);
-  for (int i = 0; i < Wo_; ++i) {
-    auto &pi = pre_integrations_[pivot + i + 1];
-    if (pi && pi->sum_dt <= 10.0) sys.pim[i] = pi;
-  }
-  if (cfg_.marginalization_factor && last_marg_) sys.prior = last_marg_;
-  if (cfg_.prior_factor) {
-    sys.use_prior_factor = true;
-    Rigidd t = toDouble(transform_lb_);
-    sys.prior_pos = t.pos; sys.prior_rot = t.rot;
-  }
+  AssembleSystem(P, sys);
   if (prior) *prior = sys.prior;
   if (!ds_pack_problem(sys, P, cfg_.max_num_iterations, bpf, convergence_flag_, cfg_.imu_factor, pb, nullptr)) return false;
   if (ds_lds_doubles(pb.n_pad, Wo_) * sizeof(double) > 160 * 1024) return false;
@@ -1134,41 +1107,11 @@ bool Estimator::BatchFinish(const DevState &st, const std::shared_ptr<MargPrior>
   R.laser_odom_iterations = laser_odom_iters_; R.laser_odom_kz = laser_odom_kz_;
   std::memset(&mg, 0, sizeof(mg));
   if (!cfg_.marginalization_factor || turn_off) return false;
-  // MarginalizationInfo::{AddResidualBlockInfo, PreMarginalize, Marginalize} (host_solver.h: marginalize): the layout
   WindowParams M;
   VectorToParams(M);
-  ds_pack_params(M, mg.x);
   auto &pi = pre_integrations_[pivot + 1];
-  const bool has_imu = pi && pi->sum_dt < 10.0 && pi->sqrt_info() != nullptr;
-  const bool sb0_present = has_imu || prior != nullptr;
-  mg.active = 1; mg.Wo = Wo_; mg.has_imu = has_imu ? 1 : 0; mg.have_prior = prior ? 1 : 0;
-  for (int i = 0; i <= DS_MAX_WO; ++i) mg.pose_col[i] = -1;
-  mg.sb_col[0] = mg.sb_col[1] = -1;
-  int pos = 0;
-  mg.pose_col[0] = pos; pos += 6;
-  if (sb0_present) { mg.sb_col[0] = pos; pos += 9; }
-  const int m = pos;
-  std::vector<KeepBlock> keep;
-  mg.pose_col[1] = pos; keep.push_back({0, 0, 7, pos - m}); pos += 6;
-  if (has_imu) { mg.sb_col[1] = pos; keep.push_back({1, 0, 9, pos - m}); pos += 9; }
-  for (int i = 2; i <= Wo_; ++i) { mg.pose_col[i] = pos; keep.push_back({0, i - 1, 7, pos - m}); pos += 6; }
-  mg.ex_col = pos; keep.push_back({2, 0, 7, pos - m}); pos += 6;
-  mg.m = m; mg.n = pos - m;
-  for (int i = 0; i < DS_MAX_NPAD; ++i) mg.prior_col[i] = -1;
-  if (prior) {
-    for (const KeepBlock &kb : prior->keep) {
-      const int col = kb.kind == 0 ? mg.pose_col[kb.index] : (kb.kind == 1 ? (kb.index < 2 ? mg.sb_col[kb.index] : -1) : mg.ex_col);
-      if (col < 0) continue;
-      const int la = kb.size == 7 ? 6 : kb.size;
-      for (int i = 0; i < la; ++i) mg.prior_col[col + i] = kb.idx + i;
-    }
-  }
-  auto pr = std::make_shared<MargPrior>();
-  pr->n = mg.n; pr->keep = keep;
-  for (const KeepBlock &kb : keep) {
-    const double *src = kb.kind == 0 ? M.pose[kb.index + 1].data() : (kb.kind == 1 ? M.sb[kb.index + 1].data() : M.ex.data());
-    pr->x0.emplace_back(src, src + kb.size);
-  }
+  const bool has_imu = pi && pi->sum_dt < 10.0 && pi->sqrt_info() != nullptr;   // (the host path takes the pre-integration alone)
+  std::shared_ptr<MargPrior> pr = ds_pack_marg(M, has_imu, prior.get(), mg);
   if (shell) *shell = pr;
   R.marginalized = 1;
   return true;

@@ -764,28 +764,46 @@ inline SolveSummary solve_dogleg(WindowSystem &sys, WindowParams &P, int max_ite
   return sum;
 }
 
+// The marginalization's column layout (MarginalizationFactor.cc:185-311): pose 0 [+ speed-bias 0] are dropped (the first m
+// columns), pose 1 [+ speed-bias 1], poses 2 .. Wo and the extrinsic are kept (n columns; KeepBlock::idx counts from m).
+// The caller decides has_imu: the host takes pim[0] != nullptr, the device path also needs its square-root information.
+struct MargLayout { Layout lay; int m = 0, n = 0; std::vector<KeepBlock> keep; };
+inline MargLayout marg_layout(int Wo, bool has_imu, bool have_prior) {
+  MargLayout L;
+  Layout &lay = L.lay;
+  lay.pose.assign(Wo + 1, -1); lay.sb.assign(Wo + 1, -1);
+  int pos = 0;
+  lay.pose[0] = pos; pos += 6;
+  if (has_imu || have_prior) { lay.sb[0] = pos; pos += 9; }
+  const int m = pos;
+  lay.pose[1] = pos; L.keep.push_back({0, 0, 7, pos - m}); pos += 6;
+  if (has_imu) { lay.sb[1] = pos; L.keep.push_back({1, 0, 9, pos - m}); pos += 9; }
+  for (int i = 2; i <= Wo; ++i) { lay.pose[i] = pos; L.keep.push_back({0, i - 1, 7, pos - m}); pos += 6; }
+  lay.ex = pos; L.keep.push_back({2, 0, 7, pos - m}); pos += 6;
+  lay.dim = pos;
+  L.m = m; L.n = pos - m;
+  return L;
+}
+// the kept blocks' linearisation point: block `index` of the NEXT window is block index + 1 of this one
+inline std::vector<std::vector<double>> marg_x0(const std::vector<KeepBlock> &keep, const WindowParams &P) {
+  std::vector<std::vector<double>> x0;
+  for (const KeepBlock &kb : keep) {
+    const double *src = kb.kind == 0 ? P.pose[kb.index + 1].data() : (kb.kind == 1 ? P.sb[kb.index + 1].data() : P.ex.data());
+    x0.emplace_back(src, src + kb.size);
+  }
+  return x0;
+}
+
 // MarginalizationInfo::{PreMarginalize, Marginalize, GetParameterBlocks}.  `sys` must carry the OLD prior,
 // pim[0] (or null) and the lidar evaluator; P are the parameters after DoubleToVector/VectorToDouble.
 inline std::shared_ptr<MargPrior> marginalize(WindowSystem &sys, const WindowParams &Pin) {
   const double eps = 1e-8;
-  const int Wo = Pin.Wo;
   WindowParams P = Pin;
   P.ex_constant = false;
-  const bool has_imu = sys.pim[0] != nullptr;
-  const bool sb0_present = has_imu || sys.prior != nullptr;
-  Layout lay;
-  lay.pose.assign(Wo + 1, -1); lay.sb.assign(Wo + 1, -1);
-  int pos = 0;
-  lay.pose[0] = pos; pos += 6;
-  if (sb0_present) { lay.sb[0] = pos; pos += 9; }
-  const int m = pos;
-  std::vector<KeepBlock> keep;
-  lay.pose[1] = pos; keep.push_back({0, 0, 7, pos - m}); pos += 6;
-  if (has_imu) { lay.sb[1] = pos; keep.push_back({1, 0, 9, pos - m}); pos += 9; }
-  for (int i = 2; i <= Wo; ++i) { lay.pose[i] = pos; keep.push_back({0, i - 1, 7, pos - m}); pos += 6; }
-  lay.ex = pos; keep.push_back({2, 0, 7, pos - m}); pos += 6;
-  lay.dim = pos;
-  const int n = pos - m;
+  const MargLayout L = marg_layout(Pin.Wo, sys.pim[0] != nullptr, sys.prior != nullptr);
+  const Layout &lay = L.lay;
+  const std::vector<KeepBlock> &keep = L.keep;
+  const int m = L.m, n = L.n;
   DMat A; std::vector<double> b;
   bool saved = sys.use_prior_factor;
   sys.use_prior_factor = false;
@@ -795,10 +813,7 @@ inline std::shared_ptr<MargPrior> marginalize(WindowSystem &sys, const WindowPar
   pr->n = n; pr->keep = keep;
   pr->lin_jac = DMat(n, n); pr->lin_res.assign(n, 0.0);
   auto finish = [&] {
-    for (const KeepBlock &kb : keep) {
-      const double *src = kb.kind == 0 ? Pin.pose[kb.index + 1].data() : (kb.kind == 1 ? Pin.sb[kb.index + 1].data() : Pin.ex.data());
-      pr->x0.emplace_back(src, src + kb.size);
-    }
+    pr->x0 = marg_x0(keep, Pin);
     pr->finalize();
     return pr;
   };

@@ -1064,6 +1064,15 @@ LIO_HD void solve_step(const X &x, const DevProblem &pb, DevState &st, const Ste
 // WindowSystem / WindowParams (host_solver.h) -> the POD problem the kernels read.  false: the problem does not fit the
 // device-resident path (too many optimised frames for the LDS-resident factorisation, no lidar factors) -> host solver.
 // prior_mats == nullptr: the caller already holds the prior's matrices on the device
+// column of `lay` -> column of the prior's kept blocks (entries of blocks that `lay` does not hold stay as they are)
+inline void ds_prior_cols(const MargPrior &pr, const Layout &lay, int *prior_col) {
+  for (const KeepBlock &kb : pr.keep) {
+    const int col = kb.kind == 0 ? lay.pose[kb.index] : (kb.kind == 1 ? lay.sb[kb.index] : lay.ex);
+    if (col < 0) continue;
+    const int la = kb.size == 7 ? 6 : kb.size;
+    for (int i = 0; i < la; ++i) prior_col[col + i] = kb.idx + i;
+  }
+}
 inline bool ds_pack_problem(const WindowSystem &sys, const WindowParams &P, int max_iterations, int bpf, bool conv_flag_in, bool imu_on,
                             DevProblem &pb, std::vector<double> *prior_mats) {
   const Layout lay = WindowSystem::solve_layout(P);
@@ -1085,11 +1094,8 @@ inline bool ds_pack_problem(const WindowSystem &sys, const WindowParams &P, int 
       pb.keep_kind[b] = kb.kind; pb.keep_index[b] = kb.index; pb.keep_size[b] = kb.size; pb.keep_idx[b] = kb.idx; pb.keep_x0[b] = off;
       for (int k = 0; k < kb.size; ++k) pb.prior_x0[off + k] = pr.x0[b][k];
       off += kb.size;
-      const int col = kb.kind == 0 ? lay.pose[kb.index] : (kb.kind == 1 ? lay.sb[kb.index] : lay.ex);
-      if (col < 0) continue;
-      const int la = kb.size == 7 ? 6 : kb.size;
-      for (int i = 0; i < la; ++i) pb.prior_col[col + i] = kb.idx + i;
     }
+    ds_prior_cols(pr, lay, pb.prior_col);
     if (prior_mats) {
       const size_t np = size_t(pr.n);
       prior_mats->resize(ds_prior_mats_size(pr.n));
@@ -1131,6 +1137,22 @@ inline void ds_unpack_params(const DevParams &d, WindowParams &P) {
     for (int k = 0; k < 9; ++k) P.sb[i][k] = d.sb[i][k];
   }
   for (int k = 0; k < 7; ++k) P.ex[k] = d.ex[k];
+}
+// MarginalizationInfo::{AddResidualBlockInfo, PreMarginalize, Marginalize} for the device (marg_kernels.hip): linearisation point M,
+// the layout of marginalize() (host_solver.h: marg_layout) as columns, the old prior's columns in it.  Returns the new prior
+// without its matrices (they are computed on the device).
+inline std::shared_ptr<MargPrior> ds_pack_marg(const WindowParams &M, bool has_imu, const MargPrior *prior, DevMarg &mg) {
+  std::memset(&mg, 0, sizeof(mg));
+  ds_pack_params(M, mg.x);
+  const MargLayout L = marg_layout(M.Wo, has_imu, prior != nullptr);
+  mg.active = 1; mg.Wo = M.Wo; mg.m = L.m; mg.n = L.n; mg.has_imu = has_imu ? 1 : 0; mg.have_prior = prior ? 1 : 0;
+  for (int i = 0; i <= DS_MAX_WO; ++i) mg.pose_col[i] = i <= M.Wo ? L.lay.pose[i] : -1;
+  mg.sb_col[0] = L.lay.sb[0]; mg.sb_col[1] = L.lay.sb[1]; mg.ex_col = L.lay.ex;
+  for (int i = 0; i < DS_MAX_NPAD; ++i) mg.prior_col[i] = -1;
+  if (prior) ds_prior_cols(*prior, L.lay, mg.prior_col);
+  auto pr = std::make_shared<MargPrior>();
+  pr->n = L.n; pr->keep = L.keep; pr->x0 = marg_x0(L.keep, M);
+  return pr;
 }
 // state before launch A_0: the initial point is its own first "candidate"
 inline void ds_init_state(const WindowParams &P, DevState &st) {

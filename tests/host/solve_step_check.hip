@@ -208,6 +208,67 @@ int compare(const char *name, Window &w, int max_it, bool conv_in) {
   if (st.need_host) bad = 1;
   return bad;
 }
+
+// The marginalization's layout, stated once (host_solver.h: marg_layout) and read by marginalize() on the host and by ds_pack_marg for
+// the device: both against each other and against (m, n, ex_col) written out by hand — m = 6 + 9 [has_imu or have_prior],
+// n = 6 Wo + 9 has_imu + 6, the extrinsic in the last six columns.  Exact integer comparisons.
+int check_marg_layout(const PimNoise &noise) {
+  struct Case { int Wo, has_imu, have_prior, m, n, ex_col; };
+  const Case cases[12] = {{1, 0, 0, 6, 12, 12},  {1, 0, 1, 15, 12, 21}, {1, 1, 0, 15, 21, 30}, {1, 1, 1, 15, 21, 30},
+                          {5, 0, 0, 6, 36, 36},  {5, 0, 1, 15, 36, 45}, {5, 1, 0, 15, 45, 54}, {5, 1, 1, 15, 45, 54},
+                          {7, 0, 0, 6, 48, 48},  {7, 0, 1, 15, 48, 57}, {7, 1, 0, 15, 57, 66}, {7, 1, 1, 15, 57, 66}};
+  int bad = 0;
+  for (const Case &c : cases) {
+    std::vector<std::shared_ptr<Preintegration>> pims;
+    Truth T = make_truth(c.Wo + 3, pims, noise);
+    // the old prior: window 0 marginalised with its IMU factor; the case is the slid window
+    Window w0 = make_window(T, pims, 0, c.Wo, 60, true, 0.0, 0.0);
+    w0.sys.lidar_eval = [&w0](const WindowParams &P, std::vector<FrameMoments> &m) { eval_lidar(w0, P, m); };
+    for (int i = 1; i < c.Wo; ++i) w0.sys.pim[i] = nullptr;
+    const std::shared_ptr<MargPrior> old_prior = marginalize(w0.sys, w0.P);
+    Window w = make_window(T, pims, 1, c.Wo, 60, true, 0.0, 0.0);
+    w.sys.lidar_eval = [&w](const WindowParams &P, std::vector<FrameMoments> &m) { eval_lidar(w, P, m); };
+    for (int i = 0; i < c.Wo; ++i) w.sys.pim[i] = (i == 0 && c.has_imu) ? pims[2] : nullptr;
+    w.sys.prior = c.have_prior ? old_prior : nullptr;
+    const std::shared_ptr<MargPrior> host = marginalize(w.sys, w.P);
+    DevMarg mg;
+    const std::shared_ptr<MargPrior> shell = ds_pack_marg(w.P, c.has_imu != 0, w.sys.prior.get(), mg);
+    int err = 0;
+    // the hand-written table
+    if (mg.m != c.m || mg.n != c.n || mg.ex_col != c.ex_col || host->n != c.n) err |= 1;
+    if (mg.Wo != c.Wo || mg.active != 1 || mg.has_imu != c.has_imu || mg.have_prior != c.have_prior) err |= 1;
+    // the shell against marginalize(): keep and x0
+    if (shell->n != host->n || shell->keep.size() != host->keep.size() || shell->x0 != host->x0) err |= 2;
+    for (size_t b = 0; b < host->keep.size() && b < shell->keep.size(); ++b) {
+      const KeepBlock &x = shell->keep[b], &y = host->keep[b];
+      if (x.kind != y.kind || x.index != y.index || x.size != y.size || x.idx != y.idx) err |= 2;
+    }
+    // the columns against marginalize()'s kept blocks: block b sits at column m + idx
+    std::vector<int> pose_col(DS_MAX_WO + 1, -1);
+    int sb_col[2] = {(c.has_imu || c.have_prior) ? 6 : -1, -1}, ex_col = -1;
+    pose_col[0] = 0;
+    for (const KeepBlock &kb : host->keep) {
+      if (kb.kind == 0) pose_col[kb.index + 1] = c.m + kb.idx;
+      else if (kb.kind == 1) sb_col[kb.index + 1] = c.m + kb.idx;
+      else ex_col = c.m + kb.idx;
+    }
+    for (int i = 0; i <= DS_MAX_WO; ++i) if (mg.pose_col[i] != pose_col[i]) err |= 4;
+    if (mg.sb_col[0] != sb_col[0] || mg.sb_col[1] != sb_col[1] || mg.ex_col != ex_col) err |= 4;
+    if ((sb_col[1] >= 0) != (c.has_imu != 0)) err |= 4;
+    // the old prior's columns: its block (kind, index) is block (kind, index) of this window
+    std::vector<int> prior_col(DS_MAX_NPAD, -1);
+    if (c.have_prior)
+      for (const KeepBlock &kb : old_prior->keep) {
+        const int col = kb.kind == 0 ? pose_col[kb.index] : (kb.kind == 1 ? sb_col[kb.index] : ex_col);
+        for (int i = 0; col >= 0 && i < (kb.size == 7 ? 6 : kb.size); ++i) prior_col[col + i] = kb.idx + i;
+      }
+    for (int i = 0; i < DS_MAX_NPAD; ++i) if (mg.prior_col[i] != prior_col[i]) err |= 8;
+    std::printf("marg layout Wo=%d has_imu=%d have_prior=%d: m=%d n=%d ex_col=%d keep=%zu %s\n", c.Wo, c.has_imu, c.have_prior, mg.m, mg.n, mg.ex_col,
+                shell->keep.size(), err ? "MISMATCH" : "equal");
+    if (err) { std::printf("  mismatch bits %d (1 table, 2 keep/x0, 4 columns, 8 prior_col)\n", err); bad = 1; }
+  }
+  return bad;
+}
 }  // namespace
 
 int main() {
@@ -255,6 +316,7 @@ int main() {
     std::printf("conv_flag_in=0, ex free: need_host=%d conv_out=%d turn_off=%d\n", dr.st.need_host, dr.st.conv_flag_out, dr.st.turn_off);
     if (!(dr.st.need_host == 1 || dr.st.conv_flag_out == 1)) bad = 1;
   }
+  bad |= check_marg_layout(noise);
   std::printf(bad ? "FAIL\n" : "OK\n");
   return bad;
 }
