@@ -53,6 +53,24 @@ int lio_est_batch_get_moments(lio_est_batch *, int window, double *out, double *
 int lio_knn_walk(const float *map_xyzi, size_t n_map, const float *query_xyzi, size_t m, float cell, int lanes_per_query,
                  int32_t *idx_out, float *sqd_out, float *nbr_xyz_out);
 
+/* The fit that turns a query's five neighbours into a residual's coefficients and decides whether the residual exists, on
+ * caller-given neighbours (csrc/cloud_device.h: features_fit<MAPPING>, the body CalculateFeatures, CalculateLaserOdom, the batched
+ * windows, scan-to-map, MapBuilder and the keyframe batch call; csrc/cloud_kernels.hip: line_features_fit, the corner branch of
+ * scan-to-map and of the keyframe batch).
+ *   form             0 plane fit of the estimator; 1 plane fit of PointMapping (sign follows pd2); 2 plane fit of MapBuilder (fitted
+ *                    sign kept); 3 line fit.  Any other value: LIO_ERR_ARG, as is a null pointer.
+ *   nbr_xyz[m*5*3]   the five neighbours of every query, in the order the walk returns them
+ *   fifth_sqd[m]     what the walk reports as the fifth squared distance; +inf stands for "fewer than five found"
+ *   stack_xyzi[m*4]  the queries in the sensor frame; the fit sees sel = rotate(T.q, p) + T.p
+ *   fixed_pz[3]      the FOV apex point of forms 1 - 3 (form 0 uses rotate(T.q, (0, 0, 10)) + T.p and ignores it)
+ * Out, m entries each: valid, coeff (4 floats), score (forms 1 - 3: 0), abs_coeff (4 floats; forms 0 and 3: 0).  An invalid query
+ * returns zeros in all of them.  m == 0 is fine.
+ * Product: uploads, then ONE launch with a query per lane that calls the same device functions the production kernels call, with the
+ * uploaded neighbours as the map and positions 5 i .. 5 i + 4.  Oracle: the fit functions its own loops call, serially. */
+int lio_fit_five(int form, const float *nbr_xyz, const float *fifth_sqd, const float *stack_xyzi, size_t m, const lio_transform_f *T,
+                 const float *fixed_pz, float min_match_sq_dis, float min_plane_dis, uint8_t *valid, float *coeff, float *score,
+                 float *abs_coeff);
+
 #ifdef __cplusplus
 }
 #endif

@@ -518,7 +518,7 @@ struct Scratch {
   VoxelGridDev vox;
   KnnGrid grid;
   DBuf<uint8_t> valid;
-  DBuf<float4> coef;
+  DBuf<float4> coef, abs_coef;
   DBuf<float> score, tf;
   DBuf<int32_t> idx;
   DBuf<float> sqd, nbr;
@@ -600,6 +600,36 @@ int lio_knn_walk(const float *map, size_t n_map, const float *query, size_t m, f
       LIO_HIP(hipMemcpyAsync(nbr_xyz, sc.nbr.p, m * 15 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
     }
     LIO_HIP(hipStreamSynchronize(sc.s));
+    return LIO_OK;
+  });
+}
+
+int lio_fit_five(int form, const float *nbr_xyz, const float *fifth_sqd, const float *stack, size_t m, const lio_transform_f *T,
+                 const float *fixed_pz, float mm, float mp, uint8_t *valid, float *coeff, float *score, float *abs_coeff) {
+  if (form < 0 || form > 3 || ((!nbr_xyz || !fifth_sqd || !stack) && m) || !T || !fixed_pz || !valid || !coeff || !score || !abs_coeff) return LIO_ERR_ARG;
+  if (m > size_t(INT_MAX) / 5) return LIO_ERR_CAPACITY;   // positions 5 i .. 5 i + 4 are ints
+  return guarded([&] {
+    Scratch &sc = scratch();
+    sc.a.reserve(std::max<size_t>(m * 5, 1)); sc.b.reserve(std::max<size_t>(m, 1)); sc.sqd.reserve(std::max<size_t>(m, 1));
+    sc.valid.reserve(std::max<size_t>(m, 1)); sc.coef.reserve(std::max<size_t>(m, 1)); sc.score.reserve(std::max<size_t>(m, 1));
+    sc.abs_coef.reserve(std::max<size_t>(m, 1)); sc.tf.reserve(8);
+    std::vector<float4> nb(m * 5);   // the fits load float4 map points; .w (the original index) is not read by them
+    for (size_t k = 0; k < m * 5; ++k) nb[k] = make_float4(nbr_xyz[3 * k], nbr_xyz[3 * k + 1], nbr_xyz[3 * k + 2], 0.f);
+    const float tf[8] = {T->q[0], T->q[1], T->q[2], T->q[3], T->p[0], T->p[1], T->p[2], 0.f};
+    LIO_HIP(hipMemcpyAsync(sc.tf.p, tf, sizeof(tf), hipMemcpyHostToDevice, sc.s));
+    if (m) {
+      LIO_HIP(hipMemcpyAsync(sc.a.p, nb.data(), m * 5 * sizeof(float4), hipMemcpyHostToDevice, sc.s));
+      LIO_HIP(hipMemcpyAsync(sc.b.p, stack, m * sizeof(float4), hipMemcpyHostToDevice, sc.s));
+      LIO_HIP(hipMemcpyAsync(sc.sqd.p, fifth_sqd, m * sizeof(float), hipMemcpyHostToDevice, sc.s));
+    }
+    launch_fit_five(form, mm, mp, fixed_pz, sc.tf.p, sc.b.p, int(m), sc.a.p, sc.sqd.p, sc.valid.p, sc.coef.p, sc.score.p, sc.abs_coef.p, sc.s);
+    if (m) {
+      LIO_HIP(hipMemcpyAsync(valid, sc.valid.p, m, hipMemcpyDeviceToHost, sc.s));
+      LIO_HIP(hipMemcpyAsync(coeff, sc.coef.p, m * sizeof(float4), hipMemcpyDeviceToHost, sc.s));
+      LIO_HIP(hipMemcpyAsync(score, sc.score.p, m * sizeof(float), hipMemcpyDeviceToHost, sc.s));
+      LIO_HIP(hipMemcpyAsync(abs_coeff, sc.abs_coef.p, m * sizeof(float4), hipMemcpyDeviceToHost, sc.s));
+    }
+    LIO_HIP(hipStreamSynchronize(sc.s));   // also keeps nb and tf alive until the uploads have read them
     return LIO_OK;
   });
 }

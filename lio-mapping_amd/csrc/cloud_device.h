@@ -230,7 +230,7 @@ __device__ __forceinline__ FeatResult features_fit(const FeatScalars &a, int slo
     bool plane_valid = true;
 #pragma unroll
     for (int j = 0; j < 5; ++j)
-      if (fabsf(pa * nx[j] + pb * ny[j] + pc * nz[j] + pd) > a.min_plane_dis) plane_valid = false;
+      if (!(fabsf(pa * nx[j] + pb * ny[j] + pc * nz[j] + pd) <= a.min_plane_dis)) plane_valid = false;   // a NaN distance (0 * NaN: a NaN coordinate in a column the rank cut dropped) is no plane
     if (plane_valid) {
       float pd2 = pa * sel.x + pb * sel.y + pc * sel.z + pd;
       float s = 1 - 0.9f * fabsf(pd2) / sqrtf(sqrtf(sel.x * sel.x + sel.y * sel.y + sel.z * sel.z));

@@ -134,6 +134,11 @@ void launch_knn(const float4 *query, int m, int k, float radius_sq, const float4
 void launch_knn_walk(const float4 *query, int m, int lanes_per_query, const float4 *map_sorted, const int *cells, const GridDesc &g,
                      int32_t *idx, float *sqd, float *nbr_xyz, hipStream_t s);
 
+// the plane fit (form 0 estimator, 1 PointMapping, 2 MapBuilder) or the line fit (form 3) of the product on caller-given neighbours, one
+// query per lane (lio_fit_five, include/lio_test_hooks.h): nbr is m * 5 points, fifth_sqd m; every output is m entries, zeros where invalid
+void launch_fit_five(int form, float min_match_sq_dis, float min_plane_dis, const float fixed_pz[3], const float *transform, const float4 *stack,
+                     int m, const float4 *nbr, const float *fifth_sqd, uint8_t *valid, float4 *coef, float *score, float4 *abs_coef, hipStream_t s);
+
 // Both branches of one scan-to-map round in a single launch (surf: FeatArgs with one frame, mapping_mode 1 or 2; corner: the
 // first Mc points of the concatenated stack, slots [0, Mc)).
 void launch_map_round(const FeatArgs &surf, const float4 *corner_stack, int Mc, const float *transform, const float4 *corner_map,

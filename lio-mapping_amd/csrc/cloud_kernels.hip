@@ -534,30 +534,15 @@ __global__ void __launch_bounds__(FEAT_THREADS) k_features(FeatArgs a, const flo
   features_block<MAPPING, LPQ>(a.fr[blockIdx.y], feat_scalars(a), int(blockIdx.x), transforms, map, cells, g, valid, coef, score, abs_coef);
 }
 
-// Corner branch of the scan-to-map step (PointMapping::OptimizeTransformTobeMapped, PointMapping.cc:377-517): one query per
-// FEAT_LPQ lanes, 5-NN, covariance of the 5 neighbours, line direction = eigenvector of the largest eigenvalue (accepted when
-// it dominates 3x the middle one).
-template <int LPQ = FEAT_LPQ>
-__device__ __forceinline__ void line_features_body(int block_x, const float4 *__restrict__ stack, int M, int slot_off, const float *__restrict__ tp,
-                                                   const Vec3<float> &pz, float min_match_sq_dis, const float4 *__restrict__ map,
-                                                   const int *__restrict__ cells, const GridDesc &g, uint8_t *__restrict__ valid,
-                                                   float4 *__restrict__ coef, const uint32_t *__restrict__ order = nullptr) {
-  const int gt = block_x * blockDim.x + threadIdx.x;
-  const int it = gt / LPQ, sub = gt % LPQ;
-  const bool active = it < M;
-  const int i = (active && order) ? int(order[it]) - slot_off : it;   // (processing order: FeatFrame::order)
-  Quat<float> q(tp[3], tp[0], tp[1], tp[2]);
-  Vec3<float> t(tp[4], tp[5], tp[6]);
-  float4 po = active ? stack[i] : make_float4(0, 0, 0, 0);
-  Vec3<float> r = rotate(q, Vec3<float>(po.x, po.y, po.z));
-  Vec3<float> sel(r.x + t.x, r.y + t.y, r.z + t.z);
-  float bd[5]; int bi[5], bj[5];
-  knn_scan_group<5, LPQ>(sel, active, sub, map, cells, g, bd, bi, bj);
-  if (!active || sub != 0) return;
-  const int slot = slot_off + i;
+// The fit half of a corner feature (PointMapping.cc:399-517) for ONE query whose five nearest map points are known: covariance of
+// the five, line direction = eigenvector of the largest eigenvalue (accepted when it dominates 3x the middle one), point-to-line
+// coefficients, score, FOV.  t: the frame's translation; pz: the FOV apex point; sel: the query's image; bd4 / bi4: distance and
+// original index of the fifth neighbour; bj: positions of the five in `map`.  Returns ok; c is zeros when not ok.
+__device__ __forceinline__ uint8_t line_features_fit(const Vec3<float> &t, const Vec3<float> &pz, const Vec3<float> &sel, float min_match_sq_dis,
+                                                     float bd4, int bi4, const int (&bj)[5], const float4 *__restrict__ map, float4 &c) {
   uint8_t ok = 0;
-  float4 c = make_float4(0, 0, 0, 0);
-  if (bi[4] != INT_MAX && bd[4] < min_match_sq_dis) {
+  c = make_float4(0, 0, 0, 0);
+  if (bi4 != INT_MAX && bd4 < min_match_sq_dis) {
     float nx[5], ny[5], nz[5];
     Vec3<float> vc(0.f, 0.f, 0.f);
 #pragma unroll
@@ -602,7 +587,67 @@ __device__ __forceinline__ void line_features_body(int block_x, const float4 *__
       }
     }
   }
+  return ok;
+}
+
+// Corner branch of the scan-to-map step (PointMapping::OptimizeTransformTobeMapped, PointMapping.cc:377-517): one query per
+// FEAT_LPQ lanes, 5-NN, then line_features_fit.
+template <int LPQ = FEAT_LPQ>
+__device__ __forceinline__ void line_features_body(int block_x, const float4 *__restrict__ stack, int M, int slot_off, const float *__restrict__ tp,
+                                                   const Vec3<float> &pz, float min_match_sq_dis, const float4 *__restrict__ map,
+                                                   const int *__restrict__ cells, const GridDesc &g, uint8_t *__restrict__ valid,
+                                                   float4 *__restrict__ coef, const uint32_t *__restrict__ order = nullptr) {
+  const int gt = block_x * blockDim.x + threadIdx.x;
+  const int it = gt / LPQ, sub = gt % LPQ;
+  const bool active = it < M;
+  const int i = (active && order) ? int(order[it]) - slot_off : it;   // (processing order: FeatFrame::order)
+  Quat<float> q(tp[3], tp[0], tp[1], tp[2]);
+  Vec3<float> t(tp[4], tp[5], tp[6]);
+  float4 po = active ? stack[i] : make_float4(0, 0, 0, 0);
+  Vec3<float> r = rotate(q, Vec3<float>(po.x, po.y, po.z));
+  Vec3<float> sel(r.x + t.x, r.y + t.y, r.z + t.z);
+  float bd[5]; int bi[5], bj[5];
+  knn_scan_group<5, LPQ>(sel, active, sub, map, cells, g, bd, bi, bj);
+  if (!active || sub != 0) return;
+  const int slot = slot_off + i;
+  float4 c;
+  const uint8_t ok = line_features_fit(t, pz, sel, min_match_sq_dis, bd[4], bi[4], bj, map, c);
   valid[slot] = ok; coef[slot] = c;
+}
+
+// The two fit bodies on caller-given neighbours (lio_fit_five, include/lio_test_hooks.h): one query per lane, `nbr` holds the five
+// neighbours of query i at 5 i .. 5 i + 4 and stands in for the cell-sorted map, fifth_sqd[i] for the walk's bd[4] (+inf: fewer than
+// five found).  form 0 features_fit<false>, 1 / 2 features_fit<true> with mapping_mode 1 / 2, 3 line_features_fit.
+__global__ void __launch_bounds__(256) k_fit_five(int form, FeatScalars fs, const float *__restrict__ tp, const float4 *__restrict__ stack, int m,
+                                                  const float4 *__restrict__ nbr, const float *__restrict__ fifth_sqd, uint8_t *__restrict__ valid,
+                                                  float4 *__restrict__ coef, float *__restrict__ score, float4 *__restrict__ abs_coef) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const Quat<float> q(tp[3], tp[0], tp[1], tp[2]);
+  const Vec3<float> t(tp[4], tp[5], tp[6]);
+  const float4 po = stack[i];
+  const Vec3<float> r = rotate(q, Vec3<float>(po.x, po.y, po.z));
+  const Vec3<float> sel(r.x + t.x, r.y + t.y, r.z + t.z);
+  const float bd4 = fifth_sqd[i];
+  const int bi4 = bd4 == INFINITY ? INT_MAX : 0;
+  const int bj[5] = {5 * i, 5 * i + 1, 5 * i + 2, 5 * i + 3, 5 * i + 4};
+  uint8_t ok; float4 c, ab = make_float4(0, 0, 0, 0); float sc = 0;
+  if (form == 3) {
+    ok = line_features_fit(t, Vec3<float>(fs.fixed_pz[0], fs.fixed_pz[1], fs.fixed_pz[2]), sel, fs.min_match_sq_dis, bd4, bi4, bj, nbr, c);
+  } else {
+    const FeatResult res = form == 0 ? features_fit<false>(fs, i, q, t, po, sel, bd4, bi4, bj, nbr) : features_fit<true>(fs, i, q, t, po, sel, bd4, bi4, bj, nbr);
+    ok = res.ok; c = res.c; sc = form == 0 ? res.sc : 0.f; ab = res.abs;   // the mapping forms have no score output (their kernels pass no score array)
+  }
+  valid[i] = ok; coef[i] = c; score[i] = sc; abs_coef[i] = ab;
+}
+
+void launch_fit_five(int form, float min_match_sq_dis, float min_plane_dis, const float fixed_pz[3], const float *transform, const float4 *stack,
+                     int m, const float4 *nbr, const float *fifth_sqd, uint8_t *valid, float4 *coef, float *score, float4 *abs_coef, hipStream_t s) {
+  if (m <= 0) return;
+  if (form < 0 || form > 3) throw DeviceError("launch_fit_five: form is 0 .. 3");
+  const FeatScalars fs{min_match_sq_dis, min_plane_dis, form == 3 ? 0 : form, {fixed_pz[0], fixed_pz[1], fixed_pz[2]}};
+  hipLaunchKernelGGL(k_fit_five, dim3(cdiv(m, 256)), dim3(256), 0, s, form, fs, transform, stack, m, nbr, fifth_sqd, valid, coef, score, abs_coef);
+  LIO_HIP(hipGetLastError());
 }
 
 // One round of the scan-to-map search in ONE launch: blockIdx.y = 0 runs the corner (line) branch against the corner map,

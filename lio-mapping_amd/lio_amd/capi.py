@@ -266,6 +266,8 @@ _TEST_SIGS = {
     "lio_est_force_moments_per_lane": (C.c_int, [C.c_void_p, C.c_int]),
     "lio_est_batch_get_moments": (C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
     "lio_knn_walk": (C.c_int, [c_float_p, C.c_size_t, c_float_p, C.c_size_t, C.c_float, C.c_int, c_int32_p, c_float_p, c_float_p]),
+    "lio_fit_five": (C.c_int, [C.c_int, c_float_p, c_float_p, c_float_p, C.c_size_t, C.POINTER(TransformF), c_float_p, C.c_float, C.c_float,
+                               c_uint8_p, c_float_p, c_float_p, c_float_p]),
 }
 
 
@@ -410,6 +412,22 @@ class LioLib:
         _chk(self.dll.lio_knn_walk(_fp(m_), m_.shape[0], _fp(q_), q_.shape[0], float(cell), int(lanes_per_query),
                                    idx.ctypes.data_as(c_int32_p), _fp(sqd), _fp(nbr)), "lio_knn_walk")
         return idx, sqd, nbr
+
+    def fit_five(self, form, nbr_xyz, fifth_sqd, stack_xyzi, T: TransformF, fixed_pz=(0.0, 0.0, 0.0), min_match_sq_dis=1.0, min_plane_dis=0.2):
+        """the plane fit (form 0 estimator, 1 PointMapping, 2 MapBuilder) or the line fit (form 3) on caller-given neighbours
+        (include/lio_test_hooks.h: lio_fit_five) -> (valid (m,) uint8, coeff (m, 4), score (m,), abs_coeff (m, 4)), zeros where invalid"""
+        s_ = _f32(stack_xyzi).reshape(-1, 4)
+        m = s_.shape[0]
+        n_ = _f32(nbr_xyz).reshape(m, 5, 3)
+        f_ = _f32(fifth_sqd).reshape(m)
+        pz = _f32(fixed_pz).reshape(3)
+        valid = np.zeros(m, dtype=np.uint8)
+        coeff = np.zeros((m, 4), dtype=np.float32)
+        score = np.zeros(m, dtype=np.float32)
+        abs_coeff = np.zeros((m, 4), dtype=np.float32)
+        _chk(self.dll.lio_fit_five(int(form), _fp(n_), _fp(f_), _fp(s_), m, C.byref(T), _fp(pz), float(min_match_sq_dis), float(min_plane_dis),
+                                   valid.ctypes.data_as(c_uint8_p), _fp(coeff), _fp(score), _fp(abs_coeff)), "lio_fit_five")
+        return valid, coeff, score, abs_coeff
 
     def calculate_features(self, map_xyzi, stack_xyzi, T: TransformF, min_match_sq_dis=1.0, min_plane_dis=0.2):
         m_ = _f32(map_xyzi).reshape(-1, 4)

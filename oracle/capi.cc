@@ -488,6 +488,42 @@ int lio_calculate_features(const float *map, size_t n_map, const float *stack, s
   for (size_t i = 0; i < m; ++i) { valid[i] = v[i]; for (int k = 0; k < 4; ++k) coeff[4 * i + k] = raw[i][k]; score[i] = raw[i][4]; }
   return LIO_OK;
 }
+// lio_fit_five (include/lio_test_hooks.h): the fit halves of Estimator::CalculateFeatures and of the surf / corner branches of
+// PointMapping::OptimizeTransformTobeMapped on caller-given neighbours, serially.
+int lio_fit_five(int form, const float *nbr_xyz, const float *fifth_sqd, const float *stack, size_t m, const lio_transform_f *T,
+                 const float *fixed_pz, float mm, float mp, uint8_t *valid, float *coeff, float *score, float *abs_coeff) {
+  if (form < 0 || form > 3 || ((!nbr_xyz || !fifth_sqd || !stack) && m) || !T || !fixed_pz || !valid || !coeff || !score || !abs_coeff) return LIO_ERR_ARG;
+  const Transformf Tf = toT(*T);
+  MappingConfig mc;
+  mc.min_match_sq_dis = mm; mc.min_plane_dis = mp;
+  PointMapping pm(mc);
+  pm.point_on_z_axis = P4{fixed_pz[0], fixed_pz[1], fixed_pz[2], 0.f};
+  const P4 tpos{Tf.pos.x, Tf.pos.y, Tf.pos.z, 0};
+  for (size_t i = 0; i < m; ++i) {
+    const float *nb = nbr_xyz + 15 * i;
+    const float sq4 = fifth_sqd[i];   // +inf (fewer than five found) fails every sq4 < min_match_sq_dis
+    const P4 po{stack[4 * i], stack[4 * i + 1], stack[4 * i + 2], stack[4 * i + 3]};
+    valid[i] = 0; score[i] = 0.f;
+    for (int k = 0; k < 4; ++k) coeff[4 * i + k] = abs_coeff[4 * i + k] = 0.f;
+    if (form == 0) {
+      const V3<float> sel = AssociateToMap(V3<float>(po.x, po.y, po.z), Tf);
+      std::array<float, 5> raw;
+      if (!Estimator::FitPlaneFeature(nb, sq4, sel, Tf, mm, mp, raw)) continue;
+      valid[i] = 1;
+      for (int k = 0; k < 4; ++k) coeff[4 * i + k] = raw[size_t(k)];
+      score[i] = raw[4];
+    } else {
+      const P4 ps = PointMapping::ToMap(po, Tf);
+      P4 c, ab{0, 0, 0, 0};
+      const bool ok = form == 3 ? pm.FitLineFeature(nb, sq4, ps, tpos, c) : pm.FitPlaneFeature(nb, sq4, ps, tpos, form == 2, c, ab);
+      if (!ok) continue;
+      valid[i] = 1;
+      coeff[4 * i] = c.x; coeff[4 * i + 1] = c.y; coeff[4 * i + 2] = c.z; coeff[4 * i + 3] = c.i;
+      abs_coeff[4 * i] = ab.x; abs_coeff[4 * i + 1] = ab.y; abs_coeff[4 * i + 2] = ab.z; abs_coeff[4 * i + 3] = ab.i;
+    }
+  }
+  return LIO_OK;
+}
 
 // ---------------------------------------------------------------- pre-integration
 lio_pim *lio_pim_create(const double acc0[3], const double gyr0[3], const double ba[3], const double bg[3], double acc_n, double gyr_n,

@@ -301,6 +301,44 @@ struct Estimator {
     return Twist<double>(rot, pos);
   }
 
+  // ---- Estimator.cc:1021-1097: the fit half of a surf feature, for one query whose five nearest map points nb (x, y, z each, in the
+  // order of the search) and fifth squared distance sq4 are known.  True and raw = {coeffs, score} when the feature exists.  Shared with
+  // the test hook lio_fit_five.
+  static bool FitPlaneFeature(const float nb[15], float sq4, const V3<float> &sel, const Transformf &T, float min_match_sq_dis, float min_plane_dis,
+                              std::array<float, 5> &raw) {
+    if (sq4 < min_match_sq_dis) {
+      float A[15], B[5] = {-1, -1, -1, -1, -1}, X[3];
+      for (int j = 0; j < 5; ++j) { A[j * 3 + 0] = nb[j * 3 + 0]; A[j * 3 + 1] = nb[j * 3 + 1]; A[j * 3 + 2] = nb[j * 3 + 2]; }
+      colpiv_qr_solve<float>(5, 3, A, B, X);
+      float pa = X[0], pb = X[1], pc = X[2], pd = 1;
+      float ps = std::sqrt(pa * pa + pb * pb + pc * pc);
+      pa /= ps; pb /= ps; pc /= ps; pd /= ps;
+      bool planeValid = true;
+      for (int j = 0; j < 5; ++j) {
+        // !(<=), not >: a NaN distance (0 * NaN: a NaN coordinate in a column the rank cut dropped) is no plane
+        if (!(std::fabs(pa * nb[j * 3 + 0] + pb * nb[j * 3 + 1] + pc * nb[j * 3 + 2] + pd) <= min_plane_dis)) { planeValid = false; break; }
+      }
+      if (!planeValid) return false;
+      float pd2 = pa * sel.x + pb * sel.y + pc * sel.z + pd;
+      float s = 1 - 0.9f * std::fabs(pd2) / std::sqrt(std::sqrt(sel.x * sel.x + sel.y * sel.y + sel.z * sel.z));
+      float c0 = s * pa, c1 = s * pb, c2 = s * pc, c3 = s * pd;
+      bool in_fov = false;
+      V3<float> pz = AssociateToMap(V3<float>(0.f, 0.f, 10.f), T);
+      float dx1 = T.pos.x - sel.x, dy1 = T.pos.y - sel.y, dz1 = T.pos.z - sel.z;
+      float side1 = dx1 * dx1 + dy1 * dy1 + dz1 * dz1;
+      float dx2 = pz.x - sel.x, dy2 = pz.y - sel.y, dz2 = pz.z - sel.z;
+      float side2 = dx2 * dx2 + dy2 * dy2 + dz2 * dz2;
+      float check1 = 100.0f + side1 - side2 - 10.0f * std::sqrt(3.0f) * std::sqrt(side1);
+      float check2 = 100.0f + side1 - side2 + 10.0f * std::sqrt(3.0f) * std::sqrt(side1);
+      if (check1 < 0 && check2 > 0) in_fov = true;
+      if (s > 0.1 && in_fov) {
+        raw = {c0, c1, c2, c3, s};
+        return true;
+      }
+    }
+    return false;
+  }
+
   // ---- Estimator.cc:970-1097, surf branch.  Shared with the stateless C entry point.
   static void CalculateFeatures(const KdTree &tree, const Cloud &map, const Cloud &stack, const Transformf &T, float min_match_sq_dis,
                                 float min_plane_dis, bool keep, std::vector<PlaneFeature> &features, std::vector<uint8_t> *valid_out = nullptr,
@@ -315,40 +353,17 @@ struct Estimator {
       int idx[5]; float sq[5];
       int found = tree.Search(q, 5, idx, sq);
       if (found < 5) continue;
-      if (sq[4] < min_match_sq_dis) {
-        float A[15], B[5] = {-1, -1, -1, -1, -1}, X[3];
-        for (int j = 0; j < 5; ++j) { A[j * 3 + 0] = map[idx[j]].x; A[j * 3 + 1] = map[idx[j]].y; A[j * 3 + 2] = map[idx[j]].z; }
-        colpiv_qr_solve<float>(5, 3, A, B, X);
-        float pa = X[0], pb = X[1], pc = X[2], pd = 1;
-        float ps = std::sqrt(pa * pa + pb * pb + pc * pc);
-        pa /= ps; pb /= ps; pc /= ps; pd /= ps;
-        bool planeValid = true;
-        for (int j = 0; j < 5; ++j) {
-          if (std::fabs(pa * map[idx[j]].x + pb * map[idx[j]].y + pc * map[idx[j]].z + pd) > min_plane_dis) { planeValid = false; break; }
-        }
-        if (!planeValid) continue;
-        float pd2 = pa * sel.x + pb * sel.y + pc * sel.z + pd;
-        float s = 1 - 0.9f * std::fabs(pd2) / std::sqrt(std::sqrt(sel.x * sel.x + sel.y * sel.y + sel.z * sel.z));
-        float c0 = s * pa, c1 = s * pb, c2 = s * pc, c3 = s * pd;
-        bool in_fov = false;
-        V3<float> pz = AssociateToMap(V3<float>(0.f, 0.f, 10.f), T);
-        float dx1 = T.pos.x - sel.x, dy1 = T.pos.y - sel.y, dz1 = T.pos.z - sel.z;
-        float side1 = dx1 * dx1 + dy1 * dy1 + dz1 * dz1;
-        float dx2 = pz.x - sel.x, dy2 = pz.y - sel.y, dz2 = pz.z - sel.z;
-        float side2 = dx2 * dx2 + dy2 * dy2 + dz2 * dz2;
-        float check1 = 100.0f + side1 - side2 - 10.0f * std::sqrt(3.0f) * std::sqrt(side1);
-        float check2 = 100.0f + side1 - side2 + 10.0f * std::sqrt(3.0f) * std::sqrt(side1);
-        if (check1 < 0 && check2 > 0) in_fov = true;
-        if (s > 0.1 && in_fov) {
-          PlaneFeature f;
-          f.score = s;
-          f.point = V3d(po.x, po.y, po.z);
-          f.coeffs[0] = c0; f.coeffs[1] = c1; f.coeffs[2] = c2; f.coeffs[3] = c3;
-          features.push_back(f);
-          if (valid_out) (*valid_out)[i] = 1;
-          if (raw_out) (*raw_out)[i] = {c0, c1, c2, c3, s};
-        }
-      }
+      float nb[15];
+      for (int j = 0; j < 5; ++j) { nb[j * 3 + 0] = map[idx[j]].x; nb[j * 3 + 1] = map[idx[j]].y; nb[j * 3 + 2] = map[idx[j]].z; }
+      std::array<float, 5> raw;
+      if (!FitPlaneFeature(nb, sq[4], sel, T, min_match_sq_dis, min_plane_dis, raw)) continue;
+      PlaneFeature f;
+      f.score = raw[4];
+      f.point = V3d(po.x, po.y, po.z);
+      f.coeffs[0] = raw[0]; f.coeffs[1] = raw[1]; f.coeffs[2] = raw[2]; f.coeffs[3] = raw[3];
+      features.push_back(f);
+      if (valid_out) (*valid_out)[i] = 1;
+      if (raw_out) (*raw_out)[i] = raw;
     }
   }
 

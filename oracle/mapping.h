@@ -200,6 +200,60 @@ struct PointMapping {
     if (!imu_inited) UpdateMapDatabase(corner_stack_ds, surf_stack_ds, valid_idx, transform_tobe_mapped, cen);
   }
 
+  // The fit half of a corner feature (PointMapping.cc:399-517) for one query ps whose five nearest corner-map points nb (x, y, z each, in
+  // the order of the search) and fifth squared distance sq4 are known: covariance, line direction, point-to-line coefficients, score,
+  // FOV.  True and coeff when the feature exists.  Shared with the test hook lio_fit_five.
+  bool FitLineFeature(const float nb[15], float sq4, const P4 &ps, const P4 &tpos, P4 &coeff) const {
+    if (!(sq4 < cfg.min_match_sq_dis)) return false;
+    V3<float> vc(0, 0, 0);
+    for (int j = 0; j < 5; ++j) { vc.x += nb[j * 3 + 0]; vc.y += nb[j * 3 + 1]; vc.z += nb[j * 3 + 2]; }
+    vc.x /= 5.0f; vc.y /= 5.0f; vc.z /= 5.0f;
+    float a00 = 0, a10 = 0, a20 = 0, a11 = 0, a21 = 0, a22 = 0;
+    for (int j = 0; j < 5; ++j) {
+      float ax = nb[j * 3 + 0] - vc.x, ay = nb[j * 3 + 1] - vc.y, az = nb[j * 3 + 2] - vc.z;
+      a00 += ax * ax; a10 += ax * ay; a20 += ax * az; a11 += ay * ay; a21 += ay * az; a22 += az * az;
+    }
+    a00 /= 5.0f; a10 /= 5.0f; a20 /= 5.0f; a11 /= 5.0f; a21 /= 5.0f; a22 /= 5.0f;
+    float A1[9] = {a00, a10, a20, a10, a11, a21, a20, a21, a22};  // solver reads the lower triangle
+    float D1[3], V1[9];
+    sym_eigen<float>(3, A1, D1, V1);
+    if (!(D1[2] > 3 * D1[1])) return false;
+    float x0 = ps.x, y0 = ps.y, z0 = ps.z;
+    float x1 = float(double(vc.x) + 0.1 * double(V1[0 * 3 + 2])), y1 = float(double(vc.y) + 0.1 * double(V1[1 * 3 + 2])),
+          z1 = float(double(vc.z) + 0.1 * double(V1[2 * 3 + 2]));
+    float x2 = float(double(vc.x) - 0.1 * double(V1[0 * 3 + 2])), y2 = float(double(vc.y) - 0.1 * double(V1[1 * 3 + 2])),
+          z2 = float(double(vc.z) - 0.1 * double(V1[2 * 3 + 2]));
+    V3<float> X0(x0, y0, z0), X1(x1, y1, z1), X2(x2, y2, z2);
+    V3<float> a012_vec = (X0 - X1).cross(X0 - X2);
+    V3<float> ntp = (X1 - X2).cross(a012_vec).normalized();
+    float a012 = a012_vec.norm(), l12 = (X1 - X2).norm();
+    float la = ntp.x, lb = ntp.y, lc = ntp.z, ld2 = a012 / l12;
+    float s = 1 - 0.9f * std::fabs(ld2);
+    coeff = P4{s * la, s * lb, s * lc, s * ld2};
+    return s > 0.1 && InFov(tpos, ps);
+  }
+  // The fit half of a surf feature (PointMapping.cc:519-619; four_dof: MapBuilder.cc:786-789 keeps the fitted sign), same arguments.
+  bool FitPlaneFeature(const float nb[15], float sq4, const P4 &ps, const P4 &tpos, bool four_dof, P4 &coeff, P4 &abs_coeff) const {
+    if (!(sq4 < cfg.min_match_sq_dis)) return false;
+    float A[15], B[5] = {-1, -1, -1, -1, -1}, X[3];
+    for (int j = 0; j < 5; ++j) { A[j * 3 + 0] = nb[j * 3 + 0]; A[j * 3 + 1] = nb[j * 3 + 1]; A[j * 3 + 2] = nb[j * 3 + 2]; }
+    colpiv_qr_solve<float>(5, 3, A, B, X);
+    float pa = X[0], pb = X[1], pc = X[2], pd = 1;
+    float pn = std::sqrt(pa * pa + pb * pb + pc * pc);
+    pa /= pn; pb /= pn; pc /= pn; pd /= pn;
+    bool plane_valid = true;
+    for (int j = 0; j < 5; ++j) {
+      // !(<=), not >: a NaN distance (0 * NaN: a NaN coordinate in a column the rank cut dropped) is no plane
+      if (!(std::fabs(pa * nb[j * 3 + 0] + pb * nb[j * 3 + 1] + pc * nb[j * 3 + 2] + pd) <= cfg.min_plane_dis)) { plane_valid = false; break; }
+    }
+    if (!plane_valid) return false;
+    float pd2 = pa * ps.x + pb * ps.y + pc * ps.z + pd;
+    float s = 1 - 0.9f * std::fabs(pd2) / std::sqrt(std::sqrt(ps.x * ps.x + ps.y * ps.y + ps.z * ps.z));
+    if (pd2 > 0 || four_dof) { coeff = P4{s * pa, s * pb, s * pc, s * pd2}; abs_coeff = P4{pa, pb, pc, pd}; }
+    else { coeff = P4{-s * pa, -s * pb, -s * pc, -s * pd2}; abs_coeff = P4{-pa, -pb, -pc, -pd}; }
+    return s > 0.1 && InFov(tpos, ps);
+  }
+
   // four_dof = MapBuilder::OptimizeMap (MapBuilder.cc:624-1014): no sign flip of the plane coefficients, rotation
   // Jacobian in the map frame weighted diag(5e-3, 5e-3, 1), left-multiplied rotation update, no score list
   void OptimizeTransformTobeMapped(bool four_dof) {
@@ -224,58 +278,19 @@ struct PointMapping {
         P4 ps = ToMap(po, T);
         int idx[5]; float sq[5];
         if (tree_corner.Search(ps, 5, idx, sq) < 5) continue;
-        if (!(sq[4] < cfg.min_match_sq_dis)) continue;
-        V3<float> vc(0, 0, 0);
-        for (int j = 0; j < 5; ++j) { const P4 &m = corner_from_map[idx[j]]; vc.x += m.x; vc.y += m.y; vc.z += m.z; }
-        vc.x /= 5.0f; vc.y /= 5.0f; vc.z /= 5.0f;
-        float a00 = 0, a10 = 0, a20 = 0, a11 = 0, a21 = 0, a22 = 0;
-        for (int j = 0; j < 5; ++j) {
-          const P4 &m = corner_from_map[idx[j]];
-          float ax = m.x - vc.x, ay = m.y - vc.y, az = m.z - vc.z;
-          a00 += ax * ax; a10 += ax * ay; a20 += ax * az; a11 += ay * ay; a21 += ay * az; a22 += az * az;
-        }
-        a00 /= 5.0f; a10 /= 5.0f; a20 /= 5.0f; a11 /= 5.0f; a21 /= 5.0f; a22 /= 5.0f;
-        float A1[9] = {a00, a10, a20, a10, a11, a21, a20, a21, a22};  // solver reads the lower triangle
-        float D1[3], V1[9];
-        sym_eigen<float>(3, A1, D1, V1);
-        if (!(D1[2] > 3 * D1[1])) continue;
-        float x0 = ps.x, y0 = ps.y, z0 = ps.z;
-        float x1 = float(double(vc.x) + 0.1 * double(V1[0 * 3 + 2])), y1 = float(double(vc.y) + 0.1 * double(V1[1 * 3 + 2])),
-              z1 = float(double(vc.z) + 0.1 * double(V1[2 * 3 + 2]));
-        float x2 = float(double(vc.x) - 0.1 * double(V1[0 * 3 + 2])), y2 = float(double(vc.y) - 0.1 * double(V1[1 * 3 + 2])),
-              z2 = float(double(vc.z) - 0.1 * double(V1[2 * 3 + 2]));
-        V3<float> X0(x0, y0, z0), X1(x1, y1, z1), X2(x2, y2, z2);
-        V3<float> a012_vec = (X0 - X1).cross(X0 - X2);
-        V3<float> ntp = (X1 - X2).cross(a012_vec).normalized();
-        float a012 = a012_vec.norm(), l12 = (X1 - X2).norm();
-        float la = ntp.x, lb = ntp.y, lc = ntp.z, ld2 = a012 / l12;
-        float s = 1 - 0.9f * std::fabs(ld2);
-        P4 coeff{s * la, s * lb, s * lc, s * ld2};
-        if (s > 0.1 && InFov(tpos, ps)) sel.push_back({po, coeff});
+        float nb[15];
+        for (int j = 0; j < 5; ++j) { const P4 &m = corner_from_map[idx[j]]; nb[j * 3 + 0] = m.x; nb[j * 3 + 1] = m.y; nb[j * 3 + 2] = m.z; }
+        P4 coeff;
+        if (FitLineFeature(nb, sq[4], ps, tpos, coeff)) sel.push_back({po, coeff});
       }
       for (const P4 &po : surf_stack_ds) {
         P4 ps = ToMap(po, T);
         int idx[5]; float sq[5];
         if (tree_surf.Search(ps, 5, idx, sq) < 5) continue;
-        if (!(sq[4] < cfg.min_match_sq_dis)) continue;
-        float A[15], B[5] = {-1, -1, -1, -1, -1}, X[3];
-        for (int j = 0; j < 5; ++j) { A[j * 3 + 0] = surf_from_map[idx[j]].x; A[j * 3 + 1] = surf_from_map[idx[j]].y; A[j * 3 + 2] = surf_from_map[idx[j]].z; }
-        colpiv_qr_solve<float>(5, 3, A, B, X);
-        float pa = X[0], pb = X[1], pc = X[2], pd = 1;
-        float pn = std::sqrt(pa * pa + pb * pb + pc * pc);
-        pa /= pn; pb /= pn; pc /= pn; pd /= pn;
-        bool plane_valid = true;
-        for (int j = 0; j < 5; ++j) {
-          const P4 &m = surf_from_map[idx[j]];
-          if (std::fabs(pa * m.x + pb * m.y + pc * m.z + pd) > cfg.min_plane_dis) { plane_valid = false; break; }
-        }
-        if (!plane_valid) continue;
-        float pd2 = pa * ps.x + pb * ps.y + pc * ps.z + pd;
-        float s = 1 - 0.9f * std::fabs(pd2) / std::sqrt(std::sqrt(ps.x * ps.x + ps.y * ps.y + ps.z * ps.z));
+        float nb[15];
+        for (int j = 0; j < 5; ++j) { const P4 &m = surf_from_map[idx[j]]; nb[j * 3 + 0] = m.x; nb[j * 3 + 1] = m.y; nb[j * 3 + 2] = m.z; }
         P4 coeff, abs_coeff;
-        if (pd2 > 0 || four_dof) { coeff = P4{s * pa, s * pb, s * pc, s * pd2}; abs_coeff = P4{pa, pb, pc, pd}; }
-        else { coeff = P4{-s * pa, -s * pb, -s * pc, -s * pd2}; abs_coeff = P4{-pa, -pb, -pc, -pd}; }
-        if (s > 0.1 && InFov(tpos, ps)) {
+        if (FitPlaneFeature(nb, sq[4], ps, tpos, four_dof, coeff, abs_coeff)) {
           sel.push_back({po, coeff});
           spc.push_back({0.f, po, abs_coeff});
           spc_coeff.push_back(coeff);

@@ -78,7 +78,7 @@ def _declared_test_hooks():
 def test_each_test_hook_is_bound_and_exported_by_both_libraries(oracle):
     """include/lio_test_hooks.h: every hook bound in Python and exported by the product and the oracle"""
     hooks = _declared_test_hooks()
-    assert len(hooks) >= 4 and "lio_knn_walk" in hooks
+    assert len(hooks) >= 5 and "lio_knn_walk" in hooks and "lio_fit_five" in hooks
     assert set(hooks) == set(capi._TEST_SIGS.keys())
     assert not set(hooks) & set(_declared_symbols())
     dll = ctypes.CDLL(capi.HIP_LIB_PATH)
