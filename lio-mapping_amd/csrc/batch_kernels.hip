@@ -12,6 +12,7 @@
 namespace lio {
 
 #define BW_THREADS 256
+static_assert(BW_THREADS == VOX_TILE, "the filter bodies of cloud_device.h work on 256-entry tiles");
 
 int bw_round_blocks(int M) { return std::max(1, cdiv(M, 64)); }
 
@@ -51,70 +52,22 @@ __global__ void __launch_bounds__(BW_THREADS) k_bw_concat_keys(const BatchWin *_
     if (finite3(o)) {
       cnt = 1.f;
       mn[0] = mx[0] = o.x; mn[1] = mx[1] = o.y; mn[2] = mx[2] = o.z;
-      const float cx = floorf(o.x * W.inv_leaf), cy = floorf(o.y * W.inv_leaf), cz = floorf(o.z * W.inv_leaf);
-      // PCL's voxel index in ABSOLUTE cells, z 9 bits | y 11 | x 11 (+-102 m of height at a 0.4 m leaf; a window beyond that takes the
-      // single-window path); the sort runs on the key relative to the window's bounds (seg_sort.h: KeyLayout)
-      if (fabsf(cx) < 1024.f && fabsf(cy) < 1024.f && fabsf(cz) < 255.f) key = (uint32_t(int(cz) + 256) << 22) | (uint32_t(int(cy) + 1024) << 11) | uint32_t(int(cx) + 1024);
-      else range_overflow[w] = 1;
+      // z 9 bits (+-102 m of height at a 0.4 m leaf; a window beyond that takes the single-window path); the sort runs on the key relative
+      // to the window's bounds (seg_sort.h: KeyLayout)
+      if (!vox_abs_key<9>(o, W.inv_leaf, key)) range_overflow[w] = 1;
     }
     keys[W.loc_off + gid] = key;
   }
-  __shared__ float sm[7][BW_THREADS / 64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    for (int d = 0; d < 3; ++d) { mn[d] = fminf(mn[d], __shfl_xor(mn[d], o, 64)); mx[d] = fmaxf(mx[d], __shfl_xor(mx[d], o, 64)); }
-    cnt += __shfl_xor(cnt, o, 64);
-  }
-  if (lane == 0) { for (int d = 0; d < 3; ++d) { sm[d][wv] = mn[d]; sm[3 + d][wv] = mx[d]; } sm[6][wv] = cnt; }
-  __syncthreads();
-  if (threadIdx.x < 7) {
-    const int t = threadIdx.x;
-    float v = sm[t][0];
-    for (int q = 1; q < BW_THREADS / 64; ++q) v = t < 3 ? fminf(v, sm[t][q]) : (t < 6 ? fmaxf(v, sm[t][q]) : v + sm[t][q]);
-    partial[(size_t(W.loc_off / BW_THREADS) + blockIdx.x) * 8 + t] = v;
-  }
+  vox_block_partial(mn, mx, cnt, partial + (size_t(W.loc_off / BW_THREADS) + blockIdx.x) * 8);
 }
 
-// the window's bounds folded into VoxParams exactly as the single-window filter does, and from them how the sort sees the keys: one block
-// per window
-__device__ __forceinline__ int bits_for(int extent) { int b = 0; while ((1 << b) < extent) ++b; return b; }
+// the window's bounds folded into VoxParams (cloud_device.h: vox_fold_bounds), and from them how the sort sees the keys: one block per window
 __global__ void __launch_bounds__(BW_THREADS) k_bw_key_layout(const BatchWin *__restrict__ win, const float *__restrict__ partial, VoxParams *__restrict__ params,
                                                              KeyLayout *__restrict__ layout, int *__restrict__ range_overflow, int max_bits) {
   const int w = blockIdx.x;
   const BatchWin &W = win[w];
-  const int ntiles = W.loc_cap / BW_THREADS;
-  __shared__ float sm[7][BW_THREADS];
-  const int t = threadIdx.x;
-  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-  float cnt = 0;
-  const float *pw = partial + size_t(W.loc_off / BW_THREADS) * 8;
-  for (int b = t; b < ntiles; b += BW_THREADS) {
-    for (int d = 0; d < 3; ++d) { mn[d] = fminf(mn[d], pw[size_t(b) * 8 + d]); mx[d] = fmaxf(mx[d], pw[size_t(b) * 8 + 3 + d]); }
-    cnt += pw[size_t(b) * 8 + 6];   // integers below 2^24: exact in any order
-  }
-  for (int d = 0; d < 3; ++d) { sm[d][t] = mn[d]; sm[3 + d][t] = mx[d]; }
-  sm[6][t] = cnt;
-  __syncthreads();
-  for (int st = BW_THREADS / 2; st > 0; st >>= 1) {
-    if (t < st) {
-      for (int d = 0; d < 3; ++d) { sm[d][t] = fminf(sm[d][t], sm[d][t + st]); sm[3 + d][t] = fmaxf(sm[3 + d][t], sm[3 + d][t + st]); }
-      sm[6][t] += sm[6][t + st];
-    }
-    __syncthreads();
-  }
-  if (t != 0) return;
   VoxParams v;
-  long long dd[3];
-  for (int d = 0; d < 3; ++d) {
-    v.mn[d] = sm[d][0]; v.mx[d] = sm[3 + d][0];
-    dd[d] = (long long)((v.mx[d] - v.mn[d]) * W.inv_leaf) + 1;
-    v.minb[d] = int(floorf(v.mn[d] * W.inv_leaf));
-    const int maxb = int(floorf(v.mx[d] * W.inv_leaf));
-    v.divb[d] = maxb - v.minb[d] + 1;
-  }
-  v.overflow = (sm[6][0] > 0 && dd[0] * dd[1] * dd[2] > (long long)INT_MAX) ? 1 : 0;
-  v.n_valid = int(sm[6][0]);
+  if (!vox_fold_bounds(partial + size_t(W.loc_off / BW_THREADS) * 8, W.loc_cap / BW_THREADS, W.inv_leaf, v)) return;
   params[w] = v;
   KeyLayout L{0, 0, 0, 0, 0, 0};
   if (v.n_valid > 0 && !range_overflow[w]) {
@@ -140,23 +93,10 @@ void launch_bw_concat_keys(const BatchWin *win, int B, int max_local, float4 *lo
 // run is added up in sorted order, i.e. in ascending original index (the sort is stable), the order the oracle fixes.  Keys: the sort's
 // relative keys, all ones = no point (sorted last); positions from n_local on hold nothing.
 // ------------------------------------------------------------------------------------------------
-#define BW_SORTED_NONE 0xFFFFFFFFu
-__device__ __forceinline__ bool bw_is_head(const uint32_t *__restrict__ wkeys, int i, uint32_t k) {   // wkeys: the window's sorted keys, i < n_local
-  return k != BW_SORTED_NONE && (i == 0 || wkeys[i - 1] != k);
-}
 __global__ void __launch_bounds__(BW_THREADS) k_bw_vox_heads(const BatchWin *__restrict__ win, const uint32_t *__restrict__ keys, int *__restrict__ tile_heads) {
-  const int w = blockIdx.y;
-  const BatchWin &W = win[w];
-  const int ntiles = W.loc_cap / BW_THREADS;
-  if (int(blockIdx.x) >= ntiles) return;
-  __shared__ int swave[BW_THREADS / 64];
-  const int i = int(blockIdx.x) * BW_THREADS + threadIdx.x;
-  const uint32_t *wk = keys + W.loc_off;
-  const uint32_t k = i < W.n_local ? wk[i] : BW_SORTED_NONE;
-  const unsigned long long b = __ballot(bw_is_head(wk, i, k));
-  if ((threadIdx.x & 63) == 0) swave[threadIdx.x >> 6] = __popcll(b);
-  __syncthreads();
-  if (threadIdx.x == 0) tile_heads[W.loc_off / BW_THREADS + blockIdx.x] = (swave[0] + swave[1]) + (swave[2] + swave[3]);
+  const BatchWin &W = win[blockIdx.y];
+  if (int(blockIdx.x) >= W.loc_cap / BW_THREADS) return;
+  vox_tile_head_count(keys + W.loc_off, W.n_local, blockIdx.x, tile_heads + W.loc_off / BW_THREADS + blockIdx.x);
 }
 
 __global__ void __launch_bounds__(BW_THREADS) k_bw_vox_centroids(const BatchWin *__restrict__ win, const float4 *__restrict__ pts, const uint32_t *__restrict__ keys,
@@ -167,48 +107,16 @@ __global__ void __launch_bounds__(BW_THREADS) k_bw_vox_centroids(const BatchWin 
   const BatchWin &W = win[w];
   const int ntiles = W.loc_cap / BW_THREADS;
   if (int(blockIdx.x) >= ntiles) return;
-  __shared__ float4 sp[BW_THREADS];
-  __shared__ uint32_t sk[BW_THREADS];
-  __shared__ int swave[BW_THREADS / 64], sbase[BW_THREADS / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int base_i = int(blockIdx.x) * BW_THREADS, i = base_i + tid;
-  const uint32_t *wk = keys + W.loc_off;
-  const uint32_t *wvals = vals + W.loc_off;
-  const int *th = tile_heads + W.loc_off / BW_THREADS;
-  int before = 0;
-  for (int b = tid; b < int(blockIdx.x); b += BW_THREADS) before += th[b];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
-  const uint32_t k = i < W.n_local ? wk[i] : BW_SORTED_NONE;
-  const bool real = k != BW_SORTED_NONE;
-  sk[tid] = k;
-  if (real) sp[tid] = pts[wvals[i]];
-  const bool head = bw_is_head(wk, i, k);
-  const unsigned long long hb = __ballot(head);
-  if (lane == 0) { swave[wv] = __popcll(hb); sbase[wv] = before; }
-  __syncthreads();
-  int pos = (sbase[0] + sbase[1]) + (sbase[2] + sbase[3]);
-  for (int q = 0; q < wv; ++q) pos += swave[q];
-  pos += __popcll(hb & ((1ull << lane) - 1ull));
-  if (int(blockIdx.x) == ntiles - 1 && tid == BW_THREADS - 1) {   // the window's last tile knows the total
+  // (vals index the batch's point array: pts is not shifted)
+  const VoxSlot r = vox_centroid_tile(pts, keys + W.loc_off, vals + W.loc_off, tile_heads + W.loc_off / BW_THREADS, W.n_local, blockIdx.x, out + W.loc_off);
+  if (int(blockIdx.x) == ntiles - 1 && threadIdx.x == BW_THREADS - 1) {   // the window's last tile knows the total
     BwVoxOut o;
-    o.count = pos + (head ? 1 : 0);
+    o.count = r.pos + (r.head ? 1 : 0);
     o.params = params[w];
     o.range_overflow = range_overflow[w];
     range_overflow[w] = 0;   // clear for the next solve (no fill command in front of it)
     vout[w] = o;
   }
-  if (!head) return;
-  float ax = 0, ay = 0, az = 0, ai = 0;
-  int e = tid;
-  while (e < BW_THREADS && sk[e] == k) { const float4 p = sp[e]; ax += p.x; ay += p.y; az += p.z; ai += p.w; ++e; }
-  int cnt = e - tid;
-  if (e == BW_THREADS) {
-    int g = base_i + BW_THREADS;
-    while (g < W.n_local && wk[g] == k) { const float4 p = pts[wvals[g]]; ax += p.x; ay += p.y; az += p.z; ai += p.w; ++g; ++cnt; }
-  }
-  const float c = float(cnt);
-  out[W.loc_off + pos] = make_float4(ax / c, ay / c, az / c, ai / c);
 }
 
 void launch_bw_vox_finish(const BatchWin *win, int B, int max_cap, const float4 *local_all, const uint32_t *keys_sorted, const uint32_t *vals_sorted, int *tile_heads,
@@ -229,21 +137,10 @@ __global__ void __launch_bounds__(BW_THREADS) k_bw_setup(const BatchWin *__restr
                                                         int *__restrict__ n_converged) {
   const int w = blockIdx.y;
   const BatchWin &W = win[w];
-  const size_t i = (size_t(blockIdx.x) * BW_THREADS + threadIdx.x) * 16;
-  uint8_t *valid = valid_all + W.slot_base;   // slot_base is a multiple of 16
-  const size_t n = size_t(W.n_slots);
-  if (i + 16 <= n) *reinterpret_cast<uint4 *>(valid + i) = make_uint4(0, 0, 0, 0);
-  else for (size_t k = i; k < n; ++k) valid[k] = 0;
+  clear_valid_block(valid_all + W.slot_base, size_t(W.n_slots));   // slot_base is a multiple of 16
   if (blockIdx.x == 0) {
-    unsigned *o = reinterpret_cast<unsigned *>(odom + w);
-    const int nw = int(sizeof(OdomState) / 4);
-    const float *T = W.tf[LIO_BW_MAX_STATIC];
     const bool none = W.newest.M <= 0;
-    if (int(threadIdx.x) < nw) {
-      unsigned v = threadIdx.x < 8 ? __float_as_uint(T[threadIdx.x]) : 0u;
-      if (none && threadIdx.x == offsetof(OdomState, converged) / 4) v = 1u;
-      o[threadIdx.x] = v;
-    }
+    odom_state_init(odom + w, W.tf[LIO_BW_MAX_STATIC], none);
     if (none && threadIdx.x == 0) atomicAdd(n_converged, 1);
   }
 }
@@ -267,13 +164,7 @@ __global__ void __launch_bounds__(BW_THREADS) k_bw_cell_keys(const BatchWin *__r
   const int i = int(blockIdx.x) * BW_THREADS + threadIdx.x;
   if (i >= G.n_filtered) return;
   const int gi = win[w].loc_off + i;
-  const float4 p = filtered_all[gi];
-  const GridDesc &g = G.g;
-  int cx = cell_coord(p.x, g.inv_cell) - g.origin[0];
-  int cy = cell_coord(p.y, g.inv_cell) - g.origin[1];
-  int cz = cell_coord(p.z, g.inv_cell) - g.origin[2];
-  cx = min(max(cx, 0), g.dims[0] - 1); cy = min(max(cy, 0), g.dims[1] - 1); cz = min(max(cz, 0), g.dims[2] - 1);
-  keys[gi] = uint32_t(cx + g.dims[0] * (cy + g.dims[1] * cz));
+  keys[gi] = cell_key_clamped(filtered_all[gi], G.g);
 }
 // behind the sort by cell: the cell-sorted points, and the table — entry c = position of the first point whose cell is >= c (an empty cell
 // holds the start of the next occupied one, entry n_cells the end), every entry written here: no histogram, no scan, no clearing.

@@ -1,7 +1,10 @@
 // cloud_device.h — device-side bodies shared by the single-window kernels (cloud_kernels.hip) and the batched-window kernels
 // (batch_kernels.hip): the K-NN walk over the cell grid, the plane fit of CalculateFeatures (Estimator.cc:1014-1097), the rows and
 // the 6x6 step of CalculateLaserOdom (Estimator.cc:1242-1359).  One definition, so a window solved alone and a window solved inside
-// a batch run the same instructions.
+// a batch run the same instructions.  The map stage in front of them is here too: the voxel filter's bounds, keys, run heads and centroid
+// tile (pcl::VoxelGrid, Estimator.cc:1518-1519), the cell key of a point and what a solve's feature stage starts from.  Every body takes
+// pointers already shifted to the window's range (a kernel argument + an offset: global to the compiler, dev.h); the kernels keep what
+// differs — where a window's range starts, and what the last tile posts.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,6 +22,172 @@ __device__ inline bool finite3(const Vec3<float> &p) { return isfinite(p.x) && i
 
 
 __device__ inline int cell_coord(float v, float inv_cell) { return int(floorf(v * inv_cell)); }
+// the cell of (x, y, z) relative to the grid's origin; true when it lies inside the grid
+__device__ __forceinline__ bool cell_of(float x, float y, float z, const GridDesc &g, int &cx, int &cy, int &cz) {
+  cx = cell_coord(x, g.inv_cell) - g.origin[0];
+  cy = cell_coord(y, g.inv_cell) - g.origin[1];
+  cz = cell_coord(z, g.inv_cell) - g.origin[2];
+  return cx >= 0 && cy >= 0 && cz >= 0 && cx < g.dims[0] && cy < g.dims[1] && cz < g.dims[2];
+}
+__device__ __forceinline__ uint32_t cell_index(int cx, int cy, int cz, const GridDesc &g) { return uint32_t(cx + g.dims[0] * (cy + g.dims[1] * cz)); }
+// the cell a map point is filed under: points outside the grid go to the border cells
+__device__ __forceinline__ uint32_t cell_key_clamped(const float4 &p, const GridDesc &g) {
+  int cx, cy, cz;
+  cell_of(p.x, p.y, p.z, g, cx, cy, cz);
+  cx = min(max(cx, 0), g.dims[0] - 1); cy = min(max(cy, 0), g.dims[1] - 1); cz = min(max(cz, 0), g.dims[2] - 1);
+  return cell_index(cx, cy, cz, g);
+}
+
+// ------------------------------------------------------------------------------------------------
+// pcl::VoxelGrid
+// ------------------------------------------------------------------------------------------------
+#define VOX_TILE 256                 // threads of every filter kernel = entries of a tile of the sorted keys
+#define VOX_KEY_NONE 0xFFFFFFFFu     // sorted key of an entry that holds no point (non-finite): behind every real key
+
+// PCL's voxel index in ABSOLUTE cells floor(p * inverse_leaf), z ZBITS bits | y 11 | x 11, each with a fixed offset: it orders the voxels
+// like PCL's own index (cells relative to the cloud's minimum).  False: the point leaves the key's range (`key` is left as it is).
+template <int ZBITS>
+__device__ __forceinline__ bool vox_abs_key(const float4 &p, float inv_leaf, uint32_t &key) {
+  constexpr int ZOFF = 1 << (ZBITS - 1);
+  const float cx = floorf(p.x * inv_leaf), cy = floorf(p.y * inv_leaf), cz = floorf(p.z * inv_leaf);
+  if (!(fabsf(cx) < 1024.f && fabsf(cy) < 1024.f && fabsf(cz) < float(ZOFF - 1))) return false;
+  key = (uint32_t(int(cz) + ZOFF) << 22) | (uint32_t(int(cy) + 1024) << 11) | uint32_t(int(cx) + 1024);
+  return true;
+}
+
+// the block's bounds and count of finite points from every lane's (mn, mx, cnt) -> row[0 .. 6]: wave shuffles, then the four waves through LDS
+__device__ __forceinline__ void vox_block_partial(float (&mn)[3], float (&mx)[3], float cnt, float *__restrict__ row) {
+  __shared__ float sm[7][VOX_TILE / 64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    for (int d = 0; d < 3; ++d) { mn[d] = fminf(mn[d], __shfl_xor(mn[d], o, 64)); mx[d] = fmaxf(mx[d], __shfl_xor(mx[d], o, 64)); }
+    cnt += __shfl_xor(cnt, o, 64);
+  }
+  if (lane == 0) { for (int d = 0; d < 3; ++d) { sm[d][wv] = mn[d]; sm[3 + d][wv] = mx[d]; } sm[6][wv] = cnt; }
+  __syncthreads();
+  if (threadIdx.x < 7) {
+    const int t = threadIdx.x;
+    float v = sm[t][0];
+    for (int w = 1; w < VOX_TILE / 64; ++w) v = t < 3 ? fminf(v, sm[t][w]) : (t < 6 ? fmaxf(v, sm[t][w]) : v + sm[t][w]);
+    row[t] = v;
+  }
+}
+
+// `nb` rows of partials (eight floats each) folded by a VOX_TILE-thread block into the cloud's VoxParams: min, max, PCL's cell bounds and its
+// "leaf size too small" guard.  True on thread 0, which holds the result.
+__device__ __forceinline__ bool vox_fold_bounds(const float *__restrict__ partial, int nb, float inv_leaf, VoxParams &v) {
+  __shared__ float sm[7][VOX_TILE];
+  const int t = threadIdx.x;
+  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+  float cnt = 0;
+  for (int b = t; b < nb; b += VOX_TILE) {
+    for (int d = 0; d < 3; ++d) { mn[d] = fminf(mn[d], partial[size_t(b) * 8 + d]); mx[d] = fmaxf(mx[d], partial[size_t(b) * 8 + 3 + d]); }
+    cnt += partial[size_t(b) * 8 + 6];   // integers below 2^24: exact in any order
+  }
+  for (int d = 0; d < 3; ++d) { sm[d][t] = mn[d]; sm[3 + d][t] = mx[d]; }
+  sm[6][t] = cnt;
+  __syncthreads();
+  for (int st = VOX_TILE / 2; st > 0; st >>= 1) {
+    if (t < st) {
+      for (int d = 0; d < 3; ++d) { sm[d][t] = fminf(sm[d][t], sm[d][t + st]); sm[3 + d][t] = fmaxf(sm[3 + d][t], sm[3 + d][t + st]); }
+      sm[6][t] += sm[6][t + st];
+    }
+    __syncthreads();
+  }
+  if (t != 0) return false;
+  long long dd[3];
+  for (int d = 0; d < 3; ++d) {
+    v.mn[d] = sm[d][0]; v.mx[d] = sm[3 + d][0];
+    dd[d] = (long long)((v.mx[d] - v.mn[d]) * inv_leaf) + 1;
+    v.minb[d] = int(floorf(v.mn[d] * inv_leaf));
+    const int maxb = int(floorf(v.mx[d] * inv_leaf));
+    v.divb[d] = maxb - v.minb[d] + 1;
+  }
+  v.overflow = (sm[6][0] > 0 && dd[0] * dd[1] * dd[2] > (long long)INT_MAX) ? 1 : 0;
+  v.n_valid = int(sm[6][0]);
+  return true;
+}
+
+// entry i (key k) of a window's sorted keys opens a run of equal keys
+__device__ __forceinline__ bool vox_is_head(const uint32_t *__restrict__ keys, int i, uint32_t k) {
+  return k != VOX_KEY_NONE && (i == 0 || keys[i - 1] != k);
+}
+// heads in tile `tile` of the n sorted keys -> *count
+__device__ __forceinline__ void vox_tile_head_count(const uint32_t *__restrict__ keys, int n, int tile, int *__restrict__ count) {
+  __shared__ int swave[VOX_TILE / 64];
+  const int i = tile * VOX_TILE + threadIdx.x;
+  const uint32_t k = i < n ? keys[i] : VOX_KEY_NONE;
+  const unsigned long long b = __ballot(vox_is_head(keys, i, k));
+  if ((threadIdx.x & 63) == 0) swave[threadIdx.x >> 6] = __popcll(b);
+  __syncthreads();
+  if (threadIdx.x == 0) *count = (swave[0] + swave[1]) + (swave[2] + swave[3]);
+}
+
+// Centroids of the sorted runs that start in tile `tile`.  The tile's points are gathered into LDS by all lanes at once; the thread of a
+// run's first entry then adds the run up in sorted order (stable sort => ascending original index inside a voxel: the within-voxel order
+// the oracle fixes) out of LDS, and out of global memory only for the part of a run that leaves the tile.  One thread per run walking
+// global memory was a chain of dependent gathers: 57 us on the 150 k-point local map against 4 us like this.
+// The output slot of a run = heads in the tiles before this one + heads before it in the tile.  Handed back: this thread's slot and
+// whether it opened a run — the last thread of the last tile knows the total, pos + head.
+struct VoxSlot { int pos; bool head; };
+__device__ __forceinline__ VoxSlot vox_centroid_tile(const float4 *__restrict__ pts, const uint32_t *__restrict__ keys, const uint32_t *__restrict__ vals,
+                                                     const int *__restrict__ tile_heads, int n, int tile, float4 *__restrict__ out) {
+  __shared__ float4 sp[VOX_TILE];
+  __shared__ uint32_t sk[VOX_TILE];
+  __shared__ int swave[VOX_TILE / 64], sbase[VOX_TILE / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int base_i = tile * VOX_TILE, i = base_i + tid;
+  int before = 0;
+  for (int b = tid; b < tile; b += VOX_TILE) before += tile_heads[b];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
+  const uint32_t k = i < n ? keys[i] : VOX_KEY_NONE;
+  sk[tid] = k;
+  if (k != VOX_KEY_NONE) sp[tid] = pts[vals[i]];
+  const bool head = vox_is_head(keys, i, k);
+  const unsigned long long hb = __ballot(head);
+  if (lane == 0) { swave[wv] = __popcll(hb); sbase[wv] = before; }
+  __syncthreads();
+  int pos = (sbase[0] + sbase[1]) + (sbase[2] + sbase[3]);
+  for (int w = 0; w < wv; ++w) pos += swave[w];
+  pos += __popcll(hb & ((1ull << lane) - 1ull));
+  if (head) {
+    float ax = 0, ay = 0, az = 0, ai = 0;
+    int e = tid;
+    while (e < VOX_TILE && sk[e] == k) { const float4 p = sp[e]; ax += p.x; ay += p.y; az += p.z; ai += p.w; ++e; }
+    int cnt = e - tid;
+    if (e == VOX_TILE) {
+      int g = base_i + VOX_TILE;
+      while (g < n && keys[g] == k) { const float4 p = pts[vals[g]]; ax += p.x; ay += p.y; az += p.z; ai += p.w; ++g; ++cnt; }
+    }
+    const float c = float(cnt);
+    out[pos] = make_float4(ax / c, ay / c, az / c, ai / c);
+  }
+  return VoxSlot{pos, head};
+}
+
+// ------------------------------------------------------------------------------------------------
+// what a solve's feature stage starts from
+// ------------------------------------------------------------------------------------------------
+// feature flags valid[0, n) <- 0, sixteen bytes per lane of a VOX_TILE-thread block (valid is 16-byte aligned)
+__device__ __forceinline__ void clear_valid_block(uint8_t *__restrict__ valid, size_t n) {
+  const size_t i = (size_t(blockIdx.x) * VOX_TILE + threadIdx.x) * 16;
+  if (i + 16 <= n) *reinterpret_cast<uint4 *>(valid + i) = make_uint4(0, 0, 0, 0);
+  else for (size_t k = i; k < n; ++k) valid[k] = 0;
+}
+// the newest frame's Gauss-Newton state = its local transform T (eight floats), every other word zero, by the block's first lanes;
+// converged: the state of a frame that has nothing to iterate on
+__device__ __forceinline__ void odom_state_init(OdomState *__restrict__ st, const float *__restrict__ T, bool converged) {
+  static_assert(offsetof(OdomState, T) == 0 && sizeof(OdomState) <= VOX_TILE * 4, "state layout: T first, the rest zero");
+  unsigned *o = reinterpret_cast<unsigned *>(st);
+  const int nw = int(sizeof(OdomState) / 4);
+  if (int(threadIdx.x) < nw) {
+    unsigned v = threadIdx.x < 8 ? __float_as_uint(T[threadIdx.x]) : 0u;
+    if (converged && threadIdx.x == offsetof(OdomState, converged) / 4) v = 1u;
+    o[threadIdx.x] = v;
+  }
+}
 
 
 // ------------------------------------------------------------------------------------------------
@@ -69,11 +238,11 @@ __device__ inline void knn_scan_group(const Vec3<float> &q, bool active, int sub
   unsigned long long bk[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) { bk[k] = knn_key(INFINITY, INT_MAX); bj[k] = 0; }
-  int cx = cell_coord(q.x, g.inv_cell) - g.origin[0];
-  int cy = cell_coord(q.y, g.inv_cell) - g.origin[1];
-  int cz = cell_coord(q.z, g.inv_cell) - g.origin[2];
+  int cx, cy, cz;
+  cell_of(q.x, q.y, q.z, g, cx, cy, cz);
   // a query with a NaN / inf coordinate has no cell (the float -> int conversion above is not defined for it): like a query outside
-  // the grid it finds nothing and only takes part in the shuffles below
+  // the grid it finds nothing and only takes part in the shuffles below.  (cell_of's own inside test, written out in one chain with the
+  // finite test: taken from its return value, the one-lane search kernels compile to 5-8 % more instructions.)
   if (!finite3(q) || cx < 0 || cy < 0 || cz < 0 || cx >= g.dims[0] || cy >= g.dims[1] || cz >= g.dims[2]) active = false;
   if (active) {
     // cells x-1..x+1 have consecutive ids => their points are one contiguous run of the cell-sorted array

@@ -103,39 +103,8 @@ __global__ void k_bounds_partial(const float4 *__restrict__ pts, int n, float *_
 }
 
 __global__ void __launch_bounds__(256) k_bounds_final(const float *__restrict__ partial, int nb, float inv_leaf, VoxParams *out) {
-  __shared__ float sm[7][256];
-  const int t = threadIdx.x;
-  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-  float cnt = 0;
-  for (int b = t; b < nb; b += 256) {
-    for (int d = 0; d < 3; ++d) { mn[d] = fminf(mn[d], partial[b * 8 + d]); mx[d] = fmaxf(mx[d], partial[b * 8 + 3 + d]); }
-    cnt += partial[b * 8 + 6];
-  }
-  for (int d = 0; d < 3; ++d) { sm[d][t] = mn[d]; sm[3 + d][t] = mx[d]; }
-  sm[6][t] = cnt;
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if (t < st) {
-      for (int d = 0; d < 3; ++d) { sm[d][t] = fminf(sm[d][t], sm[d][t + st]); sm[3 + d][t] = fmaxf(sm[3 + d][t], sm[3 + d][t + st]); }
-      sm[6][t] += sm[6][t + st];
-    }
-    __syncthreads();
-  }
-  if (t != 0) return;
-  for (int d = 0; d < 3; ++d) { mn[d] = sm[d][0]; mx[d] = sm[3 + d][0]; }
-  cnt = sm[6][0];
   VoxParams v;
-  long long dd[3];
-  for (int d = 0; d < 3; ++d) {
-    v.mn[d] = mn[d]; v.mx[d] = mx[d];
-    dd[d] = (long long)((mx[d] - mn[d]) * inv_leaf) + 1;
-    v.minb[d] = int(floorf(mn[d] * inv_leaf));
-    int maxb = int(floorf(mx[d] * inv_leaf));
-    v.divb[d] = maxb - v.minb[d] + 1;
-  }
-  v.overflow = (cnt > 0 && dd[0] * dd[1] * dd[2] > (long long)INT_MAX) ? 1 : 0;
-  v.n_valid = int(cnt);
-  *out = v;
+  if (vox_fold_bounds(partial, nb, inv_leaf, v)) *out = v;
 }
 
 __global__ void k_vox_keys(const float4 *__restrict__ pts, int n, float inv_leaf, const VoxParams *__restrict__ vp,
@@ -143,7 +112,7 @@ __global__ void k_vox_keys(const float4 *__restrict__ pts, int n, float inv_leaf
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float4 p = pts[i];
-  uint32_t key = 0xFFFFFFFFu;
+  uint32_t key = VOX_KEY_NONE;
   if (finite3(p)) {
     int i0 = int(floorf(p.x * inv_leaf) - float(vp->minb[0]));
     int i1 = int(floorf(p.y * inv_leaf) - float(vp->minb[1]));
@@ -160,128 +129,51 @@ __global__ void k_vox_keys(const float4 *__restrict__ pts, int n, float inv_leaf
 // 0.4 m leaf).  A cloud that leaves that range raises `range_overflow` and the filter reruns with PCL's own index (exact path
 // below).  The same pass leaves the per-block bounds the later kernels and the host need (VoxParams); they are folded by the
 // extra block of k_vox_tile_heads, after the sort, so nothing waits for them.
-#define VOX_KEY_THREADS 256
-__global__ void __launch_bounds__(VOX_KEY_THREADS) k_vox_keys_abs(const float4 *__restrict__ pts, int n, float inv_leaf, uint32_t *__restrict__ keys,
-                                                                 uint32_t *__restrict__ vals, float *__restrict__ partial, int *__restrict__ range_overflow) {
-  const int i = blockIdx.x * VOX_KEY_THREADS + threadIdx.x;
+__global__ void __launch_bounds__(VOX_TILE) k_vox_keys_abs(const float4 *__restrict__ pts, int n, float inv_leaf, uint32_t *__restrict__ keys,
+                                                          uint32_t *__restrict__ vals, float *__restrict__ partial, int *__restrict__ range_overflow) {
+  const int i = blockIdx.x * VOX_TILE + threadIdx.x;
   float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
   float cnt = 0;
   if (i < n) {
     const float4 p = pts[i];
-    uint32_t key = 0xFFFFFFFFu;
+    uint32_t key = VOX_KEY_NONE;
     if (finite3(p)) {
       cnt = 1.f;
       mn[0] = mx[0] = p.x; mn[1] = mx[1] = p.y; mn[2] = mx[2] = p.z;
-      const float cx = floorf(p.x * inv_leaf), cy = floorf(p.y * inv_leaf), cz = floorf(p.z * inv_leaf);
-      if (fabsf(cx) < 1024.f && fabsf(cy) < 1024.f && fabsf(cz) < 511.f) key = (uint32_t(int(cz) + 512) << 22) | (uint32_t(int(cy) + 1024) << 11) | uint32_t(int(cx) + 1024);
-      else *range_overflow = 1;
+      if (!vox_abs_key<10>(p, inv_leaf, key)) *range_overflow = 1;
     }
     keys[i] = key;
     vals[i] = uint32_t(i);
   }
-  __shared__ float sm[7][VOX_KEY_THREADS / 64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    for (int d = 0; d < 3; ++d) { mn[d] = fminf(mn[d], __shfl_xor(mn[d], o, 64)); mx[d] = fmaxf(mx[d], __shfl_xor(mx[d], o, 64)); }
-    cnt += __shfl_xor(cnt, o, 64);
-  }
-  if (lane == 0) { for (int d = 0; d < 3; ++d) { sm[d][wv] = mn[d]; sm[3 + d][wv] = mx[d]; } sm[6][wv] = cnt; }
-  __syncthreads();
-  if (threadIdx.x < 7) {
-    const int t = threadIdx.x;
-    float v = sm[t][0];
-    for (int w = 1; w < VOX_KEY_THREADS / 64; ++w) v = t < 3 ? fminf(v, sm[t][w]) : (t < 6 ? fmaxf(v, sm[t][w]) : v + sm[t][w]);
-    partial[size_t(blockIdx.x) * 8 + t] = v;
-  }
+  vox_block_partial(mn, mx, cnt, partial + size_t(blockIdx.x) * 8);
 }
 
 // heads (first entry of a run of equal keys) in each VOX_TILE-entry tile of the sorted keys
-#define VOX_TILE 256
-__device__ __forceinline__ bool vox_is_head(const uint32_t *__restrict__ keys, int i, int n, uint32_t k) {
-  return i < n && k != 0xFFFFFFFFu && (i == 0 || keys[i - 1] != k);
-}
 __global__ void __launch_bounds__(VOX_TILE) k_vox_tile_heads(const uint32_t *__restrict__ keys, int n, int *__restrict__ tile_heads,
                                                              const float *__restrict__ partial, int npartial, float inv_leaf, VoxParams *__restrict__ params) {
   if (blockIdx.x == gridDim.x - 1) {
     // the extra block (fast path only: npartial > 0): bounds of the cloud from k_vox_keys_abs's per-block partials -> VoxParams
     if (npartial <= 0) return;
-    __shared__ float sm[7][VOX_TILE];
-    const int t = threadIdx.x;
-    float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    float cnt = 0;
-    for (int b = t; b < npartial; b += VOX_TILE) {
-      for (int d = 0; d < 3; ++d) { mn[d] = fminf(mn[d], partial[size_t(b) * 8 + d]); mx[d] = fmaxf(mx[d], partial[size_t(b) * 8 + 3 + d]); }
-      cnt += partial[size_t(b) * 8 + 6];   // integers below 2^24: exact in any order
-    }
-    for (int d = 0; d < 3; ++d) { sm[d][t] = mn[d]; sm[3 + d][t] = mx[d]; }
-    sm[6][t] = cnt;
-    __syncthreads();
-    for (int st = VOX_TILE / 2; st > 0; st >>= 1) {
-      if (t < st) {
-        for (int d = 0; d < 3; ++d) { sm[d][t] = fminf(sm[d][t], sm[d][t + st]); sm[3 + d][t] = fmaxf(sm[3 + d][t], sm[3 + d][t + st]); }
-        sm[6][t] += sm[6][t + st];
-      }
-      __syncthreads();
-    }
-    if (t != 0) return;
     VoxParams v;
-    long long dd[3];
-    for (int d = 0; d < 3; ++d) {
-      v.mn[d] = sm[d][0]; v.mx[d] = sm[3 + d][0];
-      dd[d] = (long long)((v.mx[d] - v.mn[d]) * inv_leaf) + 1;
-      v.minb[d] = int(floorf(v.mn[d] * inv_leaf));
-      const int maxb = int(floorf(v.mx[d] * inv_leaf));
-      v.divb[d] = maxb - v.minb[d] + 1;
-    }
-    v.overflow = (sm[6][0] > 0 && dd[0] * dd[1] * dd[2] > (long long)INT_MAX) ? 1 : 0;
-    v.n_valid = int(sm[6][0]);
-    *params = v;
+    if (vox_fold_bounds(partial, npartial, inv_leaf, v)) *params = v;
     return;
   }
-  __shared__ int swave[VOX_TILE / 64];
-  const int i = blockIdx.x * VOX_TILE + threadIdx.x;
-  const uint32_t k = i < n ? keys[i] : 0xFFFFFFFFu;
-  const unsigned long long b = __ballot(vox_is_head(keys, i, n, k));
-  if ((threadIdx.x & 63) == 0) swave[threadIdx.x >> 6] = __popcll(b);
-  __syncthreads();
-  if (threadIdx.x == 0) tile_heads[blockIdx.x] = (swave[0] + swave[1]) + (swave[2] + swave[3]);
+  vox_tile_head_count(keys, n, blockIdx.x, tile_heads + blockIdx.x);
 }
 
-// Centroids of the sorted runs.  The tile's points are gathered into LDS by all lanes at once; the thread of a run's first
-// entry then adds the run up in sorted order (stable sort => ascending original index inside a voxel: the within-voxel order
-// the oracle fixes) out of LDS, and out of global memory only for the part of a run that leaves the tile.  One thread per run
-// walking global memory was a chain of dependent gathers: 57 us on the 150 k-point local map against 4 us like this.
-// The output slot of a run = heads in the tiles before this one + heads before it in the tile.  The last tile's block knows
-// the total and posts it (with the bounds) to the host's mailbox.
+// Centroids of the sorted runs (cloud_device.h: vox_centroid_tile).  The last tile's block knows the total and posts it (with the
+// bounds) to the host's mailbox.
 struct VoxMail { int count; VoxParams params; int range_overflow; };
 __global__ void __launch_bounds__(VOX_TILE) k_vox_centroids(const float4 *__restrict__ pts, const uint32_t *__restrict__ keys,
                                                             const uint32_t *__restrict__ vals, const int *__restrict__ tile_heads, int n,
                                                             float4 *__restrict__ out, int *__restrict__ count, const VoxParams *__restrict__ params,
                                                             int *__restrict__ range_overflow, VoxMail *mail, HostSignal sig) {
-  __shared__ float4 sp[VOX_TILE];
-  __shared__ uint32_t sk[VOX_TILE];
-  __shared__ int swave[VOX_TILE / 64], sbase[VOX_TILE / 64];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int base_i = blockIdx.x * VOX_TILE, i = base_i + tid;
-  int before = 0;
-  for (int b = tid; b < int(blockIdx.x); b += VOX_TILE) before += tile_heads[b];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
-  const uint32_t k = i < n ? keys[i] : 0xFFFFFFFFu;
-  sk[tid] = k;
-  if (k != 0xFFFFFFFFu) sp[tid] = pts[vals[i]];
-  const bool head = vox_is_head(keys, i, n, k);
-  const unsigned long long hb = __ballot(head);
-  if (lane == 0) { swave[wv] = __popcll(hb); sbase[wv] = before; }
-  __syncthreads();
-  int pos = (sbase[0] + sbase[1]) + (sbase[2] + sbase[3]);
-  for (int w = 0; w < wv; ++w) pos += swave[w];
-  pos += __popcll(hb & ((1ull << lane) - 1ull));
+  const VoxSlot r = vox_centroid_tile(pts, keys, vals, tile_heads, n, blockIdx.x, out);
   if (blockIdx.x == gridDim.x - 1) {   // the last tile knows the total
     __shared__ VoxMail smail;
+    const int tid = threadIdx.x;
     if (tid == VOX_TILE - 1) {
-      const int total = pos + (head ? 1 : 0);
+      const int total = r.pos + (r.head ? 1 : 0);
       *count = total;
       smail.count = total; smail.params = *params; smail.range_overflow = *range_overflow;
       if (sig.flag) *range_overflow = 0;   // the mail carries it: leave the flag clear for the next run (no fill command in front of it)
@@ -291,17 +183,6 @@ __global__ void __launch_bounds__(VOX_TILE) k_vox_centroids(const float4 *__rest
       if (tid < 64) post_host_mail(sig, mail, &smail, int(sizeof(VoxMail) / 4), tid);
     }
   }
-  if (!head) return;
-  float ax = 0, ay = 0, az = 0, ai = 0;
-  int e = tid;
-  while (e < VOX_TILE && sk[e] == k) { const float4 p = sp[e]; ax += p.x; ay += p.y; az += p.z; ai += p.w; ++e; }
-  int cnt = e - tid;
-  if (e == VOX_TILE) {
-    int g = base_i + VOX_TILE;
-    while (g < n && keys[g] == k) { const float4 p = pts[vals[g]]; ax += p.x; ay += p.y; az += p.z; ai += p.w; ++g; ++cnt; }
-  }
-  const float c = float(cnt);
-  out[pos] = make_float4(ax / c, ay / c, az / c, ai / c);
 }
 
 void launch_cloud_bounds(const float4 *pts, int n, DBuf<float> &partial, VoxParams *d_out, hipStream_t s) {
@@ -329,7 +210,7 @@ void VoxelGridDev::enqueue(bool exact) {
   hipStream_t s = p_stream_;
   const int ni = int(n);
   const float inv_leaf = 1.0f / p_leaf_;
-  const int nkb = cdiv(ni, VOX_KEY_THREADS);
+  const int nkb = cdiv(ni, VOX_TILE);
   partial_.reserve(size_t(std::max(nkb, 512)) * 8);
   params_.reserve(1);
   keys_.reserve(n); keys2_.reserve(n); vals_.reserve(n); vals2_.reserve(n);
@@ -352,7 +233,7 @@ void VoxelGridDev::enqueue(bool exact) {
     hipLaunchKernelGGL(k_bounds_final, dim3(1), dim3(256), 0, s, partial_.p, nb, inv_leaf, params_.p);
     hipLaunchKernelGGL(k_vox_keys, dim3(cdiv(ni, 256)), dim3(256), 0, s, in, ni, inv_leaf, params_.p, keys_.p, vals_.p);
   } else {
-    hipLaunchKernelGGL(k_vox_keys_abs, dim3(nkb), dim3(VOX_KEY_THREADS), 0, s, in, ni, inv_leaf, keys_.p, vals_.p, partial_.p, d_range);
+    hipLaunchKernelGGL(k_vox_keys_abs, dim3(nkb), dim3(VOX_TILE), 0, s, in, ni, inv_leaf, keys_.p, vals_.p, partial_.p, d_range);
     npartial = nkb;
   }
   size_t tmp_bytes = 0;
@@ -425,12 +306,7 @@ __global__ void k_cell_count(const float4 *__restrict__ pts, int n, GridDesc g, 
                              int *__restrict__ cnt) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  float4 p = pts[i];
-  int cx = cell_coord(p.x, g.inv_cell) - g.origin[0];
-  int cy = cell_coord(p.y, g.inv_cell) - g.origin[1];
-  int cz = cell_coord(p.z, g.inv_cell) - g.origin[2];
-  cx = min(max(cx, 0), g.dims[0] - 1); cy = min(max(cy, 0), g.dims[1] - 1); cz = min(max(cz, 0), g.dims[2] - 1);
-  const uint32_t c = uint32_t(cx + g.dims[0] * (cy + g.dims[1] * cz));
+  const uint32_t c = cell_key_clamped(pts[i], g);
   keys[i] = c;
   slot[i] = uint32_t(atomicAdd(&cnt[c], 1));
 }
@@ -792,20 +668,13 @@ __global__ void __launch_bounds__(1024) k_odom_update_wide(const double *__restr
 }
 __global__ void __launch_bounds__(256) k_solve_setup(SolveSetup a, float *__restrict__ d_transforms, OdomState *__restrict__ d_odom, uint8_t *__restrict__ valid,
                                                      size_t n_valid) {
-  const size_t i = (size_t(blockIdx.x) * 256 + threadIdx.x) * 16;
-  if (i + 16 <= n_valid) *reinterpret_cast<uint4 *>(valid + i) = make_uint4(0, 0, 0, 0);
-  else for (size_t k = i; k < n_valid; ++k) valid[k] = 0;
+  clear_valid_block(valid, n_valid);
   if (blockIdx.x == 0) {
     for (int k = threadIdx.x; k < a.ntf * 8; k += 256) d_transforms[k] = a.tf[k >> 3][k & 7];
-    if (a.set_odom) {
-      unsigned *o = reinterpret_cast<unsigned *>(d_odom);
-      const int nw = int(sizeof(OdomState) / 4);
-      if (int(threadIdx.x) < nw) o[threadIdx.x] = threadIdx.x < 8 ? __float_as_uint(a.odom_T[threadIdx.x]) : 0u;
-    }
+    if (a.set_odom) odom_state_init(d_odom, a.odom_T, false);
   }
 }
 void launch_solve_setup(const SolveSetup &a, float *d_transforms, OdomState *d_odom, uint8_t *valid, size_t n_valid, hipStream_t s) {
-  static_assert(offsetof(OdomState, T) == 0 && sizeof(OdomState) <= 256 * 4, "state layout: T first, the rest zero");
   const int nb = std::max(1, cdiv((long long)n_valid, 256 * 16));
   hipLaunchKernelGGL(k_solve_setup, dim3(nb), dim3(256), 0, s, a, d_transforms, d_odom, valid, n_valid);
   LIO_HIP(hipGetLastError());
@@ -903,10 +772,9 @@ __global__ void __launch_bounds__(256) k_kf_query_keys(const KfDesc *__restrict_
   const Quat<float> q(tp[3], tp[0], tp[1], tp[2]);
   const float4 po = stack_all[slot];
   const Vec3<float> r = rotate(q, Vec3<float>(po.x, po.y, po.z));
-  const int cx = cell_coord(r.x + tp[4], g.inv_cell) - g.origin[0], cy = cell_coord(r.y + tp[5], g.inv_cell) - g.origin[1],
-            cz = cell_coord(r.z + tp[6], g.inv_cell) - g.origin[2];
-  const bool in = cx >= 0 && cy >= 0 && cz >= 0 && cx < g.dims[0] && cy < g.dims[1] && cz < g.dims[2];
-  keys[slot] = in ? uint32_t(cx + g.dims[0] * (cy + g.dims[1] * cz)) : 0xFFFFFFFFu;
+  int cx, cy, cz;
+  const bool in = cell_of(r.x + tp[4], r.y + tp[5], r.z + tp[6], g, cx, cy, cz);
+  keys[slot] = in ? cell_index(cx, cy, cz, g) : 0xFFFFFFFFu;
 }
 void launch_kf_query_keys(const KfDesc *kd, const KfMapDesc *md, const OdomState *st, int n_keyframes, int max_Mc, int max_Ms, const float4 *stack_all, uint32_t *keys,
                           hipStream_t s) {

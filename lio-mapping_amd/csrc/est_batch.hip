@@ -339,15 +339,9 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
     const SegSortPlan plan = seg_sort_plan(seg, B, SS_MAX_BITS);
     sort_hist_.reserve(std::max<size_t>(plan.hist_entries, 1), s);
     LIO_HIP(hipMemcpyAsync(d_seg_.p, seg, sizeof(SegDesc) * B, hipMemcpyHostToDevice, s));
-    const uint32_t *ki = ckeys_.p, *vi = nullptr;
-    uint32_t *ko = keys_.p, *vo = vals_.p, *ko2 = keysb_.p, *vo2 = valsb_.p;
-    for (int p = 0; p < vox_passes; ++p) {
-      const int shift = p * SS_MAX_BITS, bits = std::min(SS_MAX_BITS, 32 - shift);
-      seg_sort_pass(d_seg_.p, B, plan, ki, vi, ko, vo, sort_hist_.p, shift, bits, p == 0 ? d_layout_.p : nullptr, s);
-      ki = ko; vi = vo;
-      std::swap(ko, ko2); std::swap(vo, vo2);
-    }
-    keys_sorted = ki; vals_sorted = vi;
+    const SegSortPair sorted = seg_sort_passes(d_seg_.p, B, plan, ckeys_.p, nullptr, {keys_.p, vals_.p}, {keysb_.p, valsb_.p}, sort_hist_.p, SS_MAX_BITS, vox_passes,
+                                               d_layout_.p, s);
+    keys_sorted = sorted.keys; vals_sorted = sorted.vals;
   }
   launch_bw_vox_finish(d_win_.p, B, max_cap, local_all_.p, keys_sorted, vals_sorted, tile_heads_.p, filtered_all_.p, vparams_.p, range_overflow_.p, d_vout_.p, s);
   LIO_HIP(hipMemcpyAsync(h_vout_.p, d_vout_.p, sizeof(BwVoxOut) * B, hipMemcpyDeviceToHost, s));
@@ -367,8 +361,7 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
     G.g.dims[0] = G.g.dims[1] = G.g.dims[2] = 1;
     G.g.inv_cell = 1.f;
     {   // what the window's relative keys took: the next solve's guess for the number of sort passes
-      int kb = 0;
-      for (int d = 0; d < 3; ++d) { int b = 0; while ((1 << b) < vo.params.divb[d]) ++b; kb += b; }
+      const int kb = bits_for(vo.params.divb[0]) + bits_for(vo.params.divb[1]) + bits_for(vo.params.divb[2]);
       Wn.key_bits = vo.params.n_valid > 0 ? std::max(kb, 1) : Wn.key_bits;
     }
     if (Wn.device && (vo.params.overflow || vo.range_overflow)) Wn.device = false;   // PCL's own index / "leaf too small" / keys beyond the passes: the single-window path has those forms
@@ -392,21 +385,15 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
     int bits = 1;
     for (int w = 0; w < B; ++w) {
       seg[w] = SegDesc{h_win_.p[w].loc_off, h_grid_.p[w].n_filtered, 0};
-      const long long nc = (long long)h_grid_.p[w].g.dims[0] * h_grid_.p[w].g.dims[1] * h_grid_.p[w].g.dims[2];
-      while ((1ll << bits) < nc) ++bits;
+      bits = std::max(bits, bits_for(h_grid_.p[w].g.dims[0] * h_grid_.p[w].g.dims[1] * h_grid_.p[w].g.dims[2]));   // (at most 2^28 cells: checked above)
     }
     const int passes = std::max(1, (bits + SS_MAX_BITS - 1) / SS_MAX_BITS);
     const SegSortPlan plan = seg_sort_plan(seg, B, SS_MAX_BITS);
     sort_hist_.reserve(std::max<size_t>(plan.hist_entries, 1), s);
     LIO_HIP(hipMemcpyAsync(d_seg_.p + B, seg, sizeof(SegDesc) * B, hipMemcpyHostToDevice, s));
-    const uint32_t *ki = ckeys_.p, *vi = nullptr;
-    uint32_t *ko = keys_.p, *vo = vals_.p, *ko2 = keysb_.p, *vo2 = valsb_.p;
-    for (int p = 0; p < passes; ++p) {
-      seg_sort_pass(d_seg_.p + B, B, plan, ki, vi, ko, vo, sort_hist_.p, p * SS_MAX_BITS, SS_MAX_BITS, nullptr, s);
-      ki = ko; vi = vo;
-      std::swap(ko, ko2); std::swap(vo, vo2);
-    }
-    launch_bw_cell_table(d_win_.p, d_grid_.p, B, max_filtered, filtered_all_.p, ki, vi, cells_all_.p, sorted_all_.p, s);
+    const SegSortPair sorted = seg_sort_passes(d_seg_.p + B, B, plan, ckeys_.p, nullptr, {keys_.p, vals_.p}, {keysb_.p, valsb_.p}, sort_hist_.p, SS_MAX_BITS, passes,
+                                               nullptr, s);
+    launch_bw_cell_table(d_win_.p, d_grid_.p, B, max_filtered, filtered_all_.p, sorted.keys, sorted.vals, cells_all_.p, sorted_all_.p, s);
   }
   LIO_HIP(hipEventRecord(ev_[2], s));
   launch_bw_features(d_win_.p, d_grid_.p, B, max_M, max_static, q_static, knobs_, sorted_all_.p, cells_all_.p, valid_all_.p, coef_all_.p, score_all_.p, s);

@@ -115,10 +115,7 @@ void KfBatchDev::BuildQueryOrder(hipStream_t s) {
   }
   int bits = 1;
   for (const KfMapDesc &m : h_md_)
-    for (const GridDesc *g : {&m.corner_grid, &m.surf_grid}) {
-      const long long nc = (long long)g->dims[0] * g->dims[1] * g->dims[2];
-      while ((1ll << bits) < nc) ++bits;
-    }
+    for (const GridDesc *g : {&m.corner_grid, &m.surf_grid}) bits = std::max(bits, bits_for(g->dims[0] * g->dims[1] * g->dims[2]));   // (KnnGrid::build: at most 2^30 cells)
   const int passes = std::max(1, (bits + SS_MAX_BITS - 1) / SS_MAX_BITS);
   const SegSortPlan plan = seg_sort_plan(seg.data(), 2 * B, SS_MAX_BITS);
   qhist_.reserve(std::max<size_t>(plan.hist_entries, 1));
@@ -126,13 +123,10 @@ void KfBatchDev::BuildQueryOrder(hipStream_t s) {
   LIO_HIP(hipMemcpyAsync(d_qseg_.p, seg.data(), seg.size() * sizeof(SegDesc), hipMemcpyHostToDevice, s));
   for (int off = 0; off < B; off += kChunk)
     launch_kf_query_keys(d_kd_.p + off, d_md_.p, d_st_.p + off, std::min(kChunk, B - off), max_Mc_, max_Ms_, d_stack_.p, qkeys_.p, s);
-  // ping-pong so that the last pass lands in order_ (queries outside the grid sort last: their keys keep the bits above the passes)
-  const uint32_t *ki = qkeys_.p, *vi = nullptr;
-  uint32_t *kb[2] = {qkeys2_.p, qkeys_.p}, *vb[2] = {(passes & 1) ? order_.p : qvals2_.p, (passes & 1) ? qvals2_.p : order_.p};
-  for (int p = 0; p < passes; ++p) {
-    seg_sort_pass(d_qseg_.p, 2 * B, plan, ki, vi, kb[p & 1], vb[p & 1], qhist_.p, p * SS_MAX_BITS, SS_MAX_BITS, nullptr, s);
-    ki = kb[p & 1]; vi = vb[p & 1];
-  }
+  // the buffers chosen so that the last pass lands in order_ (queries outside the grid sort last: their keys keep the bits above the passes)
+  const bool odd = passes & 1;
+  seg_sort_passes(d_qseg_.p, 2 * B, plan, qkeys_.p, nullptr, {qkeys2_.p, odd ? order_.p : qvals2_.p}, {qkeys_.p, odd ? qvals2_.p : order_.p}, qhist_.p, SS_MAX_BITS,
+                  passes, nullptr, s);
   LIO_HIP(hipStreamSynchronize(s));   // (seg is a local)
   order_valid_ = true;
 }

@@ -17,6 +17,8 @@
 
 #include <cstdint>
 
+#include "hmath.h"
+
 namespace lio {
 
 #define SS_ITEMS 16        // elements per thread
@@ -32,6 +34,8 @@ struct SegDesc {
 // cells, z (9 bits, + 256) | y (11, + 1024) | x (11, + 1024), all ones = no point; the sort runs on the key relative to the window's
 // own bounds, z' | y' | x' packed to the bits the window uses (KeyLayout), and writes THAT key out.
 struct KeyLayout { int mx, my, mz; int bx, by; int bits; };   // mins in the stored key's offset space; shifts; total bits (> 27: not sortable in three 9-bit passes)
+// bits a key takes to number `extent` values (a window's cells along an axis, the cells of a grid)
+LIO_HD int bits_for(int extent) { int b = 0; while ((1 << b) < extent) ++b; return b; }
 
 struct SegSortPlan {
   int threads;          // 256 or 512 per block: tile = threads * SS_ITEMS
@@ -41,13 +45,18 @@ struct SegSortPlan {
 // tile size by the size of the launch; fills desc[k].hist_off.  sizes[k] = elements of segment k.
 SegSortPlan seg_sort_plan(SegDesc *desc, int nseg, int bits_per_pass);
 
-// per device, before the first seg_sort_pass on it (the current device)
+// per device, before the first seg_sort_passes on it (the current device)
 void prepare_seg_sort_kernels();
 
-// One pass on digit [shift, shift + bits) of the keys.  layout != nullptr: mode 1 (per-segment layouts, device array); vals_in == nullptr:
-// the values are the elements' own positions in the array (first pass).  hist: plan.hist_entries uint32 of scratch.
-void seg_sort_pass(const SegDesc *d_desc, int nseg, const SegSortPlan &plan, const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out, uint32_t *vals_out,
-                   uint32_t *hist, int shift, int bits, const KeyLayout *layout, hipStream_t s);
+// The sort: `passes` (>= 1) passes of `bits` bits each from the lowest bit up (a last pass that would reach beyond bit 32 is as narrow as
+// what is left).  Pass 0 reads (keys_in, vals_in) and writes pair a, pass 1 reads a and writes b, pass 2 writes a again ...; returned:
+// the pair the last pass wrote, i.e. the sorted keys and values — a caller that wants them in a buffer of its choice makes that one `a`
+// for an odd number of passes and `b` for an even one.  b may share its buffers with the input.
+// layout0 != nullptr: pass 0 sees the keys in mode 1 (per-segment layouts, device array); vals_in == nullptr: the values are the elements'
+// own positions in the array.  hist: plan.hist_entries uint32 of scratch.
+struct SegSortPair { uint32_t *keys, *vals; };
+SegSortPair seg_sort_passes(const SegDesc *d_desc, int nseg, const SegSortPlan &plan, const uint32_t *keys_in, const uint32_t *vals_in, SegSortPair a, SegSortPair b,
+                            uint32_t *hist, int bits, int passes, const KeyLayout *layout0, hipStream_t s);
 
 // test hook (lio_seg_sort_pairs): sorts host arrays through `passes` passes of `bits` bits; returns false on bad arguments
 bool seg_sort_host_test(const uint32_t *keys, const uint32_t *vals_or_null, size_t n_total, const int *seg_off, const int *seg_n, int nseg, int bits, int passes,

@@ -212,8 +212,9 @@ void prepare_seg_sort_kernels() {   // (the 512-thread scatter's 75.8 KB need th
   LIO_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ss_scatter<512>), hipFuncAttributeMaxDynamicSharedMemorySize, int(ss_scatter_lds_bytes(512))));
 }
 
-void seg_sort_pass(const SegDesc *d_desc, int nseg, const SegSortPlan &plan, const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out, uint32_t *vals_out,
-                   uint32_t *hist, int shift, int bits, const KeyLayout *layout, hipStream_t s) {
+// one pass on digit [shift, shift + bits) of the keys
+static void seg_sort_pass(const SegDesc *d_desc, int nseg, const SegSortPlan &plan, const uint32_t *keys_in, const uint32_t *vals_in, uint32_t *keys_out,
+                          uint32_t *vals_out, uint32_t *hist, int shift, int bits, const KeyLayout *layout, hipStream_t s) {
   if (nseg <= 0 || plan.max_tiles <= 0) return;
   if (bits < 1 || bits > SS_MAX_BITS) throw DeviceError("seg_sort_pass: digit width out of range");
   const dim3 grid(plan.max_tiles, nseg);
@@ -227,6 +228,18 @@ void seg_sort_pass(const SegDesc *d_desc, int nseg, const SegSortPlan &plan, con
     hipLaunchKernelGGL(k_ss_scatter<256>, grid, dim3(256), ss_scatter_lds_bytes(256), s, d_desc, keys_in, vals_in, keys_out, vals_out, hist, shift, bits, layout);
   }
   LIO_HIP(hipGetLastError());
+}
+
+SegSortPair seg_sort_passes(const SegDesc *d_desc, int nseg, const SegSortPlan &plan, const uint32_t *keys_in, const uint32_t *vals_in, SegSortPair a, SegSortPair b,
+                            uint32_t *hist, int bits, int passes, const KeyLayout *layout0, hipStream_t s) {
+  if (passes < 1) throw DeviceError("seg_sort_passes: no pass");
+  for (int p = 0; p < passes; ++p) {
+    const SegSortPair &o = (p & 1) ? b : a;
+    const int shift = p * bits;
+    seg_sort_pass(d_desc, nseg, plan, keys_in, vals_in, o.keys, o.vals, hist, shift, std::min(bits, 32 - shift), p == 0 ? layout0 : nullptr, s);
+    keys_in = o.keys; vals_in = o.vals;
+  }
+  return (passes & 1) ? a : b;
 }
 
 bool seg_sort_host_test(const uint32_t *keys, const uint32_t *vals, size_t n_total, const int *seg_off, const int *seg_n, int nseg, int bits, int passes,
@@ -249,14 +262,10 @@ bool seg_sort_host_test(const uint32_t *keys, const uint32_t *vals, size_t n_tot
   if (vals) { LIO_HIP(hipMemcpy(v0.p, vals, n_total * sizeof(uint32_t), hipMemcpyHostToDevice)); LIO_HIP(hipMemcpy(v1.p, vals, n_total * sizeof(uint32_t), hipMemcpyHostToDevice)); }
   else { LIO_HIP(hipMemset(v0.p, 0, n * sizeof(uint32_t))); LIO_HIP(hipMemset(v1.p, 0, n * sizeof(uint32_t))); }
   LIO_HIP(hipMemcpy(dd.p, desc.data(), sizeof(SegDesc) * size_t(nseg), hipMemcpyHostToDevice));
-  uint32_t *ki = k0.p, *ko = k1.p, *vi = v0.p, *vo = v1.p;
-  for (int p = 0; p < passes; ++p) {
-    seg_sort_pass(dd.p, nseg, plan, ki, (p == 0 && !vals) ? nullptr : vi, ko, vo, hist.p, p * bits, bits, nullptr, s);
-    std::swap(ki, ko); std::swap(vi, vo);
-  }
+  const SegSortPair sorted = seg_sort_passes(dd.p, nseg, plan, k0.p, vals ? v0.p : nullptr, {k1.p, v1.p}, {k0.p, v0.p}, hist.p, bits, passes, nullptr, s);
   LIO_HIP(hipDeviceSynchronize());
-  LIO_HIP(hipMemcpy(keys_out, ki, n_total * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  LIO_HIP(hipMemcpy(vals_out, vi, n_total * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  LIO_HIP(hipMemcpy(keys_out, sorted.keys, n_total * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  LIO_HIP(hipMemcpy(vals_out, sorted.vals, n_total * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return true;
 }
 

@@ -39,6 +39,51 @@ def test_voxel_grid_matches_oracle(hip, oracle, n, leaf):
     np.testing.assert_array_equal(a, b)
 
 
+def _tile_edge_clouds():
+    """Clouds at the edges of the filter's 256-entry tiles of sorted keys (csrc/cloud_device.h: vox_tile_head_count, vox_centroid_tile)."""
+    rng = np.random.default_rng(256)
+    clouds = {f"n{n}": _random_cloud(rng, n) for n in (256, 257, 512, 513)}   # a last tile that is exactly full / holds a single point
+    # ~700 of ~1500 points inside ONE 0.4 m voxel (cell 2, 2, 2), ~400 in voxels that sort before it (lower z) and ~400 behind it: the run
+    # crosses tile boundaries, whole tiles hold no head, and the head's thread walks on through global memory
+    n_dense, n_side = 700, 400
+    dense = np.empty((n_dense, 4), np.float32)
+    dense[:, :3] = rng.uniform(0.85, 1.15, (n_dense, 3))
+    dense[:, 3] = rng.uniform(0, 64, n_dense)
+    side = _random_cloud(rng, 2 * n_side, 10.0)
+    side[:n_side, 2] = rng.uniform(-2.0, 0.75, n_side)
+    side[n_side:, 2] = rng.uniform(1.25, 4.0, n_side)
+    perm = rng.permutation(n_dense + 2 * n_side)
+    one_voxel = np.concatenate([dense, side])[perm]
+    clouds["one_voxel"] = one_voxel
+    # the same cloud with that voxel's points non-finite except two: "no point" keys fill the end of the sorted keys, past a tile boundary
+    holes = one_voxel.copy()
+    rows = np.flatnonzero(perm < n_dense)[2:]
+    holes[rows[0::2], 0] = np.nan
+    holes[rows[1::2], 2] = np.inf
+    clouds["one_voxel_non_finite"] = holes
+    # the minimum of x is -0.0f with +0.0f also present (in other waves and blocks): the bounds' fold sees both zeros
+    zeros = _random_cloud(rng, 600, 5.0)
+    zeros[:, 0] = np.abs(zeros[:, 0])
+    zeros[[3, 70, 300, 555], 0] = -0.0
+    zeros[[0, 64, 129, 256, 599], 0] = 0.0
+    clouds["minus_zero"] = zeros
+    return clouds
+
+
+_TILE_EDGE_CLOUDS = _tile_edge_clouds()
+
+
+@pytest.mark.parametrize("name", list(_TILE_EDGE_CLOUDS))
+def test_voxel_grid_at_tile_edges_matches_oracle(hip, oracle, name):
+    """Shapes at which the tile bodies shared by the single-window and the batched filter can go wrong: full and one-point last tiles,
+    a run longer than two tiles, "no point" keys at the end of a tile, a -0.0f minimum.  The oracle's ascending-index sums are the
+    definition: the clouds are equal bit for bit."""
+    pts = _TILE_EDGE_CLOUDS[name]
+    a, b = hip.voxel_grid(pts, 0.4), oracle.voxel_grid(pts, 0.4)
+    assert a.shape == b.shape
+    np.testing.assert_array_equal(a, b)
+
+
 @pytest.mark.parametrize("extent,leaf", [(450.0, 0.4), (60.0, 0.05), (3000.0, 0.4)])
 def test_voxel_grid_beyond_the_fast_key_range(hip, oracle, extent, leaf):
     """The filter's fast path packs absolute cells into 10 + 11 + 11 bits; clouds that leave that range (|cell| >= 1024 in
