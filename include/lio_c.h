@@ -412,8 +412,9 @@ int lio_est_process_laser_odom(lio_est *, const lio_transform_f *transform_in, c
  * transform_tobe_mapped_ from the IMU-propagated body motion (:780-803), then ProcessLaserOdom with
  * transform_aft_mapped_.  transform_to_init_out (may be null) receives that transform.  After initialisation the
  * caller switches the scan-to-scan odometry to its packer mode (lio_odom_enable(.., 0); the reference does it
- * through the /enable_odom service, :549-558).  Not reproduced: the post-init map-database refresh (:703-708),
- * which only feeds the published surround map. */
+ * through the /enable_odom service, :549-558).  The post-initialisation map-database refresh (:703-708), which feeds
+ * the published surround map, is reproduced under lio_est_set_map_refresh (lio_ext.h, the product only; off by default:
+ * without it the map stops at the initialising step). */
 int lio_est_process_compact(lio_est *, const float *compact_xyzi, size_t n_points, double stamp,
                             lio_transform_f *transform_to_init_out, lio_solve_report *report_or_null);
 /* stage_flag_ (0 NOT_INITED, 1 INITED), cir_buf_count_, extrinsic_stage_, what the last ProcessLaserOdom did

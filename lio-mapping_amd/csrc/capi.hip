@@ -7,6 +7,7 @@
 
 #include "../../include/lio_c.h"
 #include "../../include/lio_test_hooks.h"
+#include "../../include/lio_ext.h"
 #include "est_batch.h"
 #include "seg_sort.h"
 #include "estimator.h"
@@ -25,7 +26,8 @@ using namespace lio;
 
 struct lio_pim { std::shared_ptr<Preintegration> p; };
 // (members are destroyed in reverse order: the batch of one that serves lio_est_config.device_solve goes before the estimator it adopted)
-struct lio_est { std::unique_ptr<Estimator> e; EstConfig cfg; std::unique_ptr<MappingDev> map; lio_map_config map_cfg; std::unique_ptr<EstimatorBatch> solo; bool adopted = false; struct lio_est_batch *owner = nullptr; };
+struct lio_map { std::unique_ptr<MappingDev> m; bool borrowed = false; };   // borrowed: the member of a lio_est (lio_est_map), not for lio_map_destroy
+struct lio_est { std::unique_ptr<Estimator> e; EstConfig cfg; lio_map map; lio_map_config map_cfg; std::unique_ptr<EstimatorBatch> solo; bool adopted = false; struct lio_est_batch *owner = nullptr; };
 // A batch of at least kBatchSplitFrom windows is TWO EstimatorBatch objects (the first and the second half of the windows) solved side by
 // side from two host threads: one part's host phases (describe, pack, write-back), syncs and latency-bound stages fill with the other
 // part's kernels (tools/batches_in_flight.py: 2 x 256 windows 20.1 k solves/s against 19.0 k for 1 x 512, 2 x 64 17.4 k against 16.1 k).
@@ -46,7 +48,6 @@ static constexpr int kBatchSplitFrom = 96;    // measured (profiles/r6_n_batch_p
 struct lio_pp_pool { PointProcessorDev pp; std::mutex mu; unsigned long gen = 0; lio_pp_pool(float lo, float up, int r, const lio_pp_config &c) : pp(lo, up, r, c) {} };
 struct lio_pp { std::unique_ptr<PointProcessorDev> pp; std::shared_ptr<lio_pp_pool> pool; int pool_sweep = -1; unsigned long pool_gen = 0; };
 struct lio_odom { std::unique_ptr<OdometryDev> o; };
-struct lio_map { std::unique_ptr<MappingDev> m; };
 
 static V3d v3(const double *p) { return V3d(p[0], p[1], p[2]); }
 static Rigidf toT(const lio_transform_f &t) { return Rigidf(Quat<float>(t.q[3], t.q[0], t.q[1], t.q[2]), Vec3<float>(t.p[0], t.p[1], t.p[2])); }
@@ -355,7 +356,10 @@ lio_map *lio_map_create(const lio_map_config *c) {
   if (rc != LIO_OK) { delete h; return nullptr; }
   return h;
 }
-void lio_map_destroy(lio_map *h) { delete h; }
+void lio_map_destroy(lio_map *h) {
+  if (h && h->borrowed) { std::fprintf(stderr, "[lio_hip] lio_map_destroy: the handle belongs to a lio_est (lio_est_map); ignored\n"); return; }
+  delete h;
+}
 int lio_map_process(lio_map *h, const float *corner, size_t nc, const float *surf, size_t ns, const lio_transform_f *Tsum, lio_transform_f *Taft,
                     int *iters, int *nsel) {
   if (!h || !Tsum || (!corner && nc) || (!surf && ns)) return LIO_ERR_ARG;
@@ -796,8 +800,14 @@ int lio_est_process_laser_odom(lio_est *h, const lio_transform_f *T, const float
   if (!h || !T || (!surf && ns) || (!corner && nc)) return LIO_ERR_ARG;
   return guarded([&] { return h->e->ProcessLaserOdom(toT(*T), surf, ns, corner, nc, stamp, rep) ? LIO_OK : LIO_ERR_STATE; });
 }
-// ProcessCompactData (Estimator.cc:776-856).  The post-initialisation map-database refresh (:703-708) only feeds the
-// published surround map and is not reproduced.
+// the estimator's PointMapping base, created on first use (Estimator.cc:189-194: configured from the estimator's own sizes)
+static MappingDev &est_map(lio_est *h) {
+  if (!h->map.m) { h->map.m.reset(new MappingDev(h->map_cfg)); h->map.borrowed = true; }
+  h->e->map_ = h->map.m.get();
+  return *h->map.m;
+}
+// ProcessCompactData (Estimator.cc:776-856).  The post-initialisation map-database refresh (:703-708), which feeds the published
+// surround map, runs inside ProcessLaserOdom under lio_est_set_map_refresh (include/lio_ext.h); it is off by default.
 int lio_est_process_compact(lio_est *h, const float *data, size_t n, double stamp, lio_transform_f *T_out, lio_solve_report *rep) {
   if (!h || !data) return LIO_ERR_ARG;
   lio_transform_f Tsum;
@@ -807,8 +817,7 @@ int lio_est_process_compact(lio_est *h, const float *data, size_t n, double stam
   return guarded([&] {
     Estimator &e = *h->e;
     if (e.inited_ && !e.cfg_.imu_factor) return LIO_ERR_STATE;  // LOAM-only operation after init is not part of this path
-    if (!h->map) h->map.reset(new MappingDev(h->map_cfg));
-    MappingDev &m = *h->map;
+    MappingDev &m = est_map(h);
     const float *corner = data + 4 * 3, *surf = data + 4 * (3 + nc);
     if (e.inited_) {  // :780-803: predict transform_tobe_mapped_ with the IMU-propagated body motion
       const int W = e.W_;
@@ -826,11 +835,55 @@ int lio_est_process_compact(lio_est *h, const float *data, size_t n, double stam
     const Rigidf T_to_init = m.transform_aft_mapped_;
     if (T_out) fromT(T_to_init, T_out);
     const bool was_inited = e.inited_;
-    const bool ok = was_inited ? e.ProcessLaserOdom(T_to_init, reinterpret_cast<const float4 *>(surf), ns, false, stamp, rep)
-                               : e.ProcessLaserOdom(T_to_init, m.StackDevice(1), m.StackSize(1), true, stamp, rep);
+    const bool ok = was_inited ? e.ProcessLaserOdom(T_to_init, reinterpret_cast<const float4 *>(surf), ns, false, stamp, rep,
+                                                    reinterpret_cast<const float4 *>(corner), nc, false)
+                               : e.ProcessLaserOdom(T_to_init, m.StackDevice(1), m.StackSize(1), true, stamp, rep, m.StackDevice(0), m.StackSize(0), true);
     if (!ok) return LIO_ERR_STATE;
     if (!was_inited && e.inited_) m.imu_inited_ = true;  // SetInitFlag(true) (:545)
     return LIO_OK;
+  });
+}
+// ---------------------------------------------------------------- include/lio_ext.h: the map refresh and the surround map
+lio_map *lio_est_map(lio_est *h) {
+  if (!h) return nullptr;
+  const int rc = guarded([&] { est_map(h); return LIO_OK; });
+  return rc == LIO_OK ? &h->map : nullptr;
+}
+int lio_est_set_map_refresh(lio_est *h, int on) {
+  if (!h || (on != 0 && on != 1)) return LIO_ERR_ARG;
+  return guarded([&] { h->e->SetMapRefresh(on != 0, &est_map(h)); return LIO_OK; });
+}
+int lio_est_refresh_map(lio_est *h) {
+  if (!h) return LIO_ERR_ARG;
+  if (!h->e->inited_) return LIO_ERR_STATE;
+  return guarded([&] { est_map(h); return h->e->RefreshMap(); });
+}
+size_t lio_map_get_surround(lio_map *h, float leaf, float *xyzi_or_null) {
+  if (!h || !h->m || !(leaf > 0)) return 0;
+  size_t n = 0;
+  guarded([&] { n = h->m->GetSurround(leaf, xyzi_or_null); return LIO_OK; });
+  return n;
+}
+int lio_est_get_last_map_refresh(const lio_est *h, int *applied, lio_transform_f *T, int cube_center[3], uint32_t *valid_idx, int *n_valid,
+                                 size_t *n_corner, float *corner_xyzi_or_null, size_t *n_surf, float *surf_xyzi_or_null) {
+  if (!h) return LIO_ERR_ARG;
+  const MapRefreshRecord &r = h->e->last_refresh();
+  if (!r.have) return LIO_ERR_STATE;
+  return guarded([&] {
+    Estimator &e = *h->e;
+    const OptSlot &sl = r.slot;
+    const DeviceCloud *surf = sl.surf_frame == OptSlot::kNoFrame ? nullptr : e.OptSurfCloud(sl.surf_frame);
+    if (sl.surf_frame != OptSlot::kNoFrame && !surf) return int(LIO_ERR_STATE);   // the frame has left the window since
+    if (applied) *applied = r.applied;
+    if (T) fromT(sl.transform, T);
+    if (cube_center) for (int d = 0; d < 3; ++d) cube_center[d] = sl.cen[d];
+    if (valid_idx) for (size_t k = 0; k < sl.valid_idx.size(); ++k) valid_idx[k] = sl.valid_idx[k];
+    if (n_valid) *n_valid = int(sl.valid_idx.size());
+    const size_t nc = e.CopyCloudToHost(sl.corner.get(), corner_xyzi_or_null);
+    const size_t ns = e.CopyCloudToHost(surf, surf_xyzi_or_null);
+    if (n_corner) *n_corner = nc;
+    if (n_surf) *n_surf = ns;
+    return int(LIO_OK);
   });
 }
 int lio_est_get_stage(const lio_est *h, int *stage, int *cir_buf_count, int *extrinsic_stage, int *last_event, double *R_WI, double *g_vec) {

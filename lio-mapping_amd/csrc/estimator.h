@@ -3,6 +3,7 @@
 // BuildLocalMap, SolveOptimization, SlideWindow.  Clouds live in HBM for the life of the window;
 // the host keeps only the (W+1) x {P,R,V,Ba,Bg} states, the pre-integrations and the prior.
 #pragma once
+#include <climits>
 #include <condition_variable>
 #include <exception>
 #include <functional>
@@ -54,6 +55,28 @@ struct DeviceCloud {
 };
 
 struct StampedPose { double time; Rigidf T; };
+
+class MappingDev;
+
+// One slot of the optimisation-window buffers (Estimator.cc:177-183; pushed at :467-485): opt_point_coeff_mask_, opt_cube_centers_,
+// opt_valid_idx_, opt_transforms_, opt_surf_stack_, opt_corner_stack_.  The reference's stacks are shared pointers: a slot's surf
+// cloud IS a window frame's cloud, later in-place edits included (the pivot fusion :1434, SlideWindow :2615), so the slot names the
+// frame (by its push number) and the cloud is looked up in the window when it is read.  Corner clouds are never edited: shared, immutable.
+struct OptSlot {
+  bool mask = false;
+  int cen[3] = {0, 0, 0};
+  std::vector<uint32_t> valid_idx;
+  Rigidf transform;
+  static constexpr long kNoFrame = LONG_MIN;
+  long surf_frame = kNoFrame;             // push number of the frame whose surf stack the slot holds (negative: a frame SetWindow injected)
+  std::shared_ptr<DeviceCloud> corner;    // null: no corner cloud (a frame from before the refresh was enabled)
+};
+// the arguments of the last RefreshMap (lio_est_get_last_map_refresh)
+struct MapRefreshRecord {
+  bool have = false;
+  int applied = 0;
+  OptSlot slot;
+};
 
 // HIP-event kernel timing on the estimator's stream (lio_est_enable_kernel_timing)
 enum { KT_FEATURES = 0, KT_ODOM_FEATURES, KT_ODOM_ROWS, KT_ODOM_UPDATE, KT_MOMENTS, KT_VOXEL, KT_KNN_GRID, KT_CONCAT, KT_COUNT };
@@ -172,9 +195,22 @@ class Estimator {
   bool ProcessLaserOdom(const Rigidf &transform_in, const float *surf, size_t n_surf, const float *corner, size_t n_corner, double stamp,
                         lio_solve_report *rep);
   // surf_on_device: the surf cloud already lives in HBM (the scan-to-map stage's down-sampled stack before initialisation)
-  bool ProcessLaserOdom(const Rigidf &transform_in, const float4 *surf, size_t n_surf, bool surf_on_device, double stamp, lio_solve_report *rep);
+  // corner: read only while the map refresh is on (PushFrame)
+  bool ProcessLaserOdom(const Rigidf &transform_in, const float4 *surf, size_t n_surf, bool surf_on_device, double stamp, lio_solve_report *rep,
+                        const float4 *corner = nullptr, size_t n_corner = 0, bool corner_on_device = false);
   bool PushFrame(const Rigidf &transform_in, const float *surf, size_t n_surf, const float *corner, size_t n_corner, double stamp,
-                 bool surf_on_device = false);
+                 bool surf_on_device = false, bool corner_on_device = false);
+  // ---- the map-database refresh (Estimator.cc:703-708), off unless SetMapRefresh(true, map): PushFrame then keeps the optimisation-window
+  // buffers (and the corner clouds they need), ProcessLaserOdom refreshes between SolveOptimization and SlideWindow
+  void SetMapRefresh(bool on, MappingDev *map);
+  bool map_refresh() const { return map_refresh_; }
+  // after a solve, before the slide.  1: the map was updated; 0: slot 0 is masked or the ring is not full (:626)
+  int RefreshMap();
+  const MapRefreshRecord &last_refresh() const { return last_refresh_; }
+  // the surf cloud an optimisation-window slot holds, where it is now (nullptr: the frame has left the window)
+  const DeviceCloud *OptSurfCloud(long surf_frame) const;
+  size_t CopyCloudToHost(const DeviceCloud *c, float *out);
+  MappingDev *map_ = nullptr;   // the PointMapping base (owned by the C handle); read by PushFrame and RefreshMap only while the refresh is on
   bool RunInitialization();
   void SetStatesFromLaser();
   // Estimator.cc:1648-2438.  With a hook installed (lio_est_config.device_solve: a batch of one window, est_batch.h) the whole
@@ -334,6 +370,20 @@ class Estimator {
   bool frames_dirty_ = true;
   std::unique_ptr<HostState> snap_;
   std::vector<DeviceCloud> snap_stacks_;
+  // ---- map refresh state (all empty while the refresh is off)
+  bool map_refresh_ = false;
+  std::vector<OptSlot> opt_ring_;               // CircularBuffer of Wo + 1 slots, oldest first
+  long frame_seq_ = 0;                          // frames pushed so far: window slot i holds frame frame_seq_ - 1 - (n_frames_ - 1 - i)
+  std::shared_ptr<DeviceCloud> corner_last_;    // corner_stack_.last()
+  std::vector<std::shared_ptr<DeviceCloud>> corner_pool_;   // every corner cloud made; one nobody else holds is reused
+  std::shared_ptr<DeviceCloud> AcquireCornerCloud();
+  // W == Wo with de-skew on: slot 0's frame has just left the window when it is read (the reference's shared pointer keeps it alive)
+  DeviceCloud opt_evicted_, snap_opt_evicted_;
+  long opt_evicted_frame_ = -1;
+  DeviceCloud upload_corner_;
+  VoxelGridDev vox_corner_;
+  MapRefreshRecord last_refresh_;
+  Rigidf OptPose0() const;                      // Estimator.cc:2282-2286
 };
 
 }  // namespace lio

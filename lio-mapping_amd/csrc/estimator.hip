@@ -3,6 +3,7 @@
 // :1648-2438 (SolveOptimization), :2440-2568 (VectorToDouble/DoubleToVector), :2570-2666 (SlideWindow).
 #include "estimator.h"
 #include "est_batch.h"
+#include "mapping.h"
 #include "marg_kernels.h"
 #include "rccl_comm.h"
 
@@ -59,6 +60,11 @@ struct Estimator::HostState {
   std::shared_ptr<Preintegration> tmp_pre_integration;
   std::vector<size_t> size_surf_stack;
   std::vector<StampedPose> imu_stamped;
+  // the optimisation-window buffers of the map refresh (corner clouds shared: they are immutable)
+  std::vector<OptSlot> opt_ring;
+  long frame_seq;
+  std::shared_ptr<DeviceCloud> corner_last;
+  long opt_evicted_frame;
 };
 
 Estimator::Estimator(const EstConfig &cfg) : cfg_(cfg), W_(cfg.W), Wo_(cfg.Wo) {
@@ -98,6 +104,7 @@ void Estimator::Init() {
   h_odom_.alloc(1, hipHostMallocCoherent);
   h_signal_.alloc(256, hipHostMallocCoherent, true);
   vox_.set_host_signal(host_signal_);
+  vox_corner_.set_host_signal(host_signal_);
   LIO_HIP(hipGetDevice(&device_id_));
 }
 
@@ -262,16 +269,18 @@ void Estimator::PushCloud(DeviceCloud &&c, size_t n, int n_before) {
 
 bool Estimator::ProcessLaserOdom(const Rigidf &transform_in, const float *surf, size_t n_surf, const float *corner, size_t n_corner,
                                  double stamp, lio_solve_report *rep) {
-  (void)corner; (void)n_corner;
-  return ProcessLaserOdom(transform_in, reinterpret_cast<const float4 *>(surf), n_surf, false, stamp, rep);
+  return ProcessLaserOdom(transform_in, reinterpret_cast<const float4 *>(surf), n_surf, false, stamp, rep, reinterpret_cast<const float4 *>(corner), n_corner,
+                          false);
 }
 
 // Estimator.cc:430-774
 bool Estimator::ProcessLaserOdom(const Rigidf &transform_in, const float4 *surf, size_t n_surf, bool surf_on_device, double stamp,
-                                 lio_solve_report *rep) {
+                                 lio_solve_report *rep, const float4 *corner, size_t n_corner, bool corner_on_device) {
   ++laser_odom_recv_count_;
   if (!inited_ && laser_odom_recv_count_ % cfg_.init_window_factor != 0) { last_event_ = EV_SKIPPED; return true; }  // :436-439
-  if (!PushFrame(transform_in, reinterpret_cast<const float *>(surf), n_surf, nullptr, 0, stamp, surf_on_device)) return false;
+  if (!PushFrame(transform_in, reinterpret_cast<const float *>(surf), n_surf, reinterpret_cast<const float *>(corner), n_corner, stamp, surf_on_device,
+                 corner_on_device))
+    return false;
   if (!inited_) {
     if (cir_buf_count_ == W_) {
       bool init_result = false;
@@ -299,9 +308,11 @@ bool Estimator::ProcessLaserOdom(const Rigidf &transform_in, const float4 *surf,
       ++cir_buf_count_;
       last_event_ = EV_FILLING;
     }
+    if (map_refresh_ && !opt_ring_.empty()) opt_ring_.back().mask = true;   // :616, the initialising step included: it does not refresh (:590-618)
     return true;
   }
   bool ok = SolveOptimization(rep);
+  if (map_refresh_) RefreshMap();   // :703-708
   SlideWindow();
   last_event_ = EV_SOLVED;
   return ok;
@@ -348,8 +359,15 @@ bool Estimator::RunInitialization() {
   return init_result;
 }
 
-bool Estimator::PushFrame(const Rigidf &transform_in, const float *surf, size_t n_surf, const float * /*corner*/, size_t /*n_corner*/,
-                          double stamp, bool surf_on_device) {
+std::shared_ptr<DeviceCloud> Estimator::AcquireCornerCloud() {
+  for (auto &c : corner_pool_)
+    if (c.use_count() == 1) return c;   // neither the ring, corner_last_ nor a snapshot holds it any more
+  corner_pool_.push_back(std::make_shared<DeviceCloud>());
+  return corner_pool_.back();
+}
+
+bool Estimator::PushFrame(const Rigidf &transform_in, const float *surf, size_t n_surf, const float *corner, size_t n_corner, double stamp,
+                          bool surf_on_device, bool corner_on_device) {
   frames_dirty_ = true;
   // every precondition is checked BEFORE the window is touched: a refused frame leaves the estimator as it was
   if (inited_ && (cfg_.enable_deskew || cfg_.cutoff_deskew) && !cfg_.cutoff_deskew && imu_stamped_.empty()) return false;
@@ -360,7 +378,38 @@ bool Estimator::PushFrame(const Rigidf &transform_in, const float *surf, size_t 
   tmp_pre_integration_ = std::make_shared<Preintegration>(acc_last_, gyr_last_, Bas_[cir_buf_count_], Bgs_[cir_buf_count_], cfg_.pim);
   const int n_before = n_frames_;
   if (n_frames_ < W_ + 1) ++n_frames_;
+  // the stacks are pushed as they come before initialisation and with both de-skew switches off (:474-480), else de-skewed and filtered (:678-693)
+  const bool as_is = !inited_ || !(cfg_.enable_deskew || cfg_.cutoff_deskew);
+  std::shared_ptr<DeviceCloud> corner_cloud;
+  if (map_refresh_) {
+    // Estimator.cc:467-471 and :484-485.  The stacks of :484-485 are surf_stack_.last() / corner_stack_.last() AT THAT LINE: this frame's
+    // when :474-480 has just pushed them, but the PREVIOUS frame's when the de-skewed stacks are only pushed at :689-693
+    OptSlot sl;
+    sl.mask = false;
+    for (int d = 0; d < 3; ++d) sl.cen[d] = map_->cen_[d];
+    sl.valid_idx = map_->valid_idx_;
+    sl.transform = transform_in;
+    sl.surf_frame = as_is ? frame_seq_ : frame_seq_ - 1;
+    corner_cloud = AcquireCornerCloud();
+    corner_cloud->id = ++g_content_id;
+    if (!as_is) sl.corner = corner_last_;
+    else sl.corner = corner_cloud;
+    if (int(opt_ring_.size()) == Wo_ + 1) opt_ring_.erase(opt_ring_.begin());
+    opt_ring_.push_back(std::move(sl));
+    corner_last_ = corner_cloud;
+    if (n_before == W_ + 1 && W_ == Wo_) {   // the frame leaving the window may still be slot 0's at the next refresh
+      std::swap(stacks_[0], opt_evicted_);
+      opt_evicted_frame_ = frame_seq_ - 1 - W_;
+    }
+  }
+  ++frame_seq_;
   DeviceCloud fresh = std::move(stacks_[n_before < W_ + 1 ? n_before : 0]);  // recycle the buffer of the slot being (re)written
+  if (as_is && corner_cloud) {
+    corner_cloud->buf.reserve(std::max<size_t>(n_corner, 1));
+    if (n_corner)
+      LIO_HIP(hipMemcpyAsync(corner_cloud->buf.p, corner, n_corner * sizeof(float4), corner_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
+    corner_cloud->n = n_corner;
+  }
   if (!inited_) {  // :474-481: the stacks are the scan-to-map stage's down-sampled clouds, pushed as they are
     fresh.buf.reserve(std::max<size_t>(n_surf, 1));
     if (n_surf)
@@ -377,6 +426,7 @@ bool Estimator::PushFrame(const Rigidf &transform_in, const float *surf, size_t 
     LIO_HIP(hipMemcpyAsync(upload_.buf.p, surf, n_surf * sizeof(float4), surf_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
   upload_.n = n_surf;
   if (cfg_.enable_deskew || cfg_.cutoff_deskew) {
+    float q[4] = {0.f, 0.f, 0.f, 1.f}, p[3] = {0.f, 0.f, 0.f};
     if (!cfg_.cutoff_deskew) {
       double time_e = imu_stamped_.back().time;
       Rigidf T_e = imu_stamped_.back().T;
@@ -393,10 +443,20 @@ bool Estimator::PushFrame(const Rigidf &transform_in, const float *surf, size_t 
       body_es.rot = slerp(qid, s, body_es.rot, FLT_EPSILON);
       body_es.pos = s * body_es.pos;
       Rigidf tes = compose(compose(transform_lb_, body_es), rinverse(transform_lb_));
-      float q[4] = {tes.rot.x, tes.rot.y, tes.rot.z, tes.rot.w}, p[3] = {tes.pos.x, tes.pos.y, tes.pos.z};
+      q[0] = tes.rot.x; q[1] = tes.rot.y; q[2] = tes.rot.z; q[3] = tes.rot.w; p[0] = tes.pos.x; p[1] = tes.pos.y; p[2] = tes.pos.z;
       launch_deskew_to_end(upload_.buf.p, int(n_surf), q, p, 10.f, stream_);
     }
-    // corner clouds are only consumed under USE_CORNER (off in the shipped build, Estimator.h:55): not processed
+    // corner clouds are only consumed under USE_CORNER (off in the shipped build, Estimator.h:55) and by the map refresh: processed
+    // for the refresh's ring only (:670, :684-687, :692)
+    if (corner_cloud) {
+      upload_corner_.buf.reserve(std::max<size_t>(n_corner, 1));
+      if (n_corner)
+        LIO_HIP(hipMemcpyAsync(upload_corner_.buf.p, corner, n_corner * sizeof(float4), corner_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                               stream_));
+      upload_corner_.n = n_corner;
+      if (!cfg_.cutoff_deskew) launch_deskew_to_end(upload_corner_.buf.p, int(n_corner), q, p, 10.f, stream_);
+      corner_cloud->n = vox_corner_.run(upload_corner_.buf.p, n_corner, cfg_.corner_filter_size, corner_cloud->buf, stream_);
+    }
     fresh.n = vox_.run(upload_.buf.p, n_surf, cfg_.surf_filter_size, fresh.buf, stream_);
   } else {
     fresh.buf.reserve(std::max<size_t>(n_surf, 1));
@@ -407,6 +467,62 @@ bool Estimator::PushFrame(const Rigidf &transform_in, const float *surf, size_t 
   fresh.id = ++g_content_id;
   PushCloud(std::move(fresh), nfresh, n_before);
   return true;
+}
+
+// ---- the map-database refresh
+void Estimator::SetMapRefresh(bool on, MappingDev *map) {
+  map_ = map;
+  if (on == map_refresh_) return;
+  map_refresh_ = on;
+  if (!on) {   // nothing is held while it is off
+    opt_ring_.clear(); corner_last_.reset(); corner_pool_.clear();
+    opt_evicted_ = DeviceCloud(); opt_evicted_frame_ = -1; upload_corner_ = DeviceCloud();
+    last_refresh_ = MapRefreshRecord();
+  }
+}
+
+const DeviceCloud *Estimator::OptSurfCloud(long surf_frame) const {
+  const long newest = frame_seq_ - 1;
+  const long idx = long(n_frames_ - 1) - (newest - surf_frame);
+  if (idx >= 0 && idx < long(stacks_.size())) return &stacks_[size_t(idx)];
+  if (surf_frame == opt_evicted_frame_) return &opt_evicted_;
+  return nullptr;
+}
+
+size_t Estimator::CopyCloudToHost(const DeviceCloud *c, float *out) {
+  if (!c) return 0;
+  if (out && c->n) {
+    LIO_HIP(hipMemcpyAsync(out, c->buf.p, c->n * sizeof(float4), hipMemcpyDeviceToHost, stream_));
+    LIO_HIP(hipStreamSynchronize(stream_));
+  }
+  return c->n;
+}
+
+// Estimator.cc:2282-2286 (update_laser_imu, which every shipped configuration sets): the optimised lidar pose of frame W - Wo, in double, cast to float
+Rigidf Estimator::OptPose0() const {
+  const Rigidd lb = toDouble(transform_lb_);
+  const int opt_0 = W_ - Wo_;
+  const Qd rot_l0 = fromRot(Rs_[opt_0] * toRot(normalized(conj(lb.rot))));
+  const V3d pos_l0 = Ps_[opt_0] - rotate(rot_l0, lb.pos);
+  return toFloat(Rigidd(rot_l0, pos_l0));
+}
+
+int Estimator::RefreshMap() {
+  if (!map_) throw std::runtime_error("RefreshMap: the estimator has no map");
+  last_refresh_ = MapRefreshRecord();
+  last_refresh_.have = true;
+  if (opt_ring_.empty()) return 0;
+  OptSlot &s0 = opt_ring_.front();
+  s0.transform = OptPose0();   // :2286 runs at the end of EVERY solve; slot 0 is read by nothing else before the next one
+  last_refresh_.slot = s0;
+  if (int(opt_ring_.size()) != Wo_ + 1 || s0.mask) return 0;   // :626, :703
+  const DeviceCloud *surf = OptSurfCloud(s0.surf_frame);
+  if (!surf) throw std::runtime_error("RefreshMap: slot 0's surf stack has left the window");
+  const DeviceCloud *cor = s0.corner.get();
+  map_->UpdateMapDatabase(cor ? cor->buf.p : nullptr, cor ? cor->n : 0, surf->buf.p, surf->n, s0.valid_idx.data(), s0.valid_idx.size(), s0.transform,
+                          s0.cen, stream_);
+  last_refresh_.applied = 1;
+  return 1;
 }
 
 void Estimator::FusePivotOnce() {
@@ -977,7 +1093,12 @@ void Estimator::Snapshot() {
                             convergence_flag_, cir_buf_count_, all_laser_transforms_, n_state_, n_frames_, laser_odom_recv_count_,
                             extrinsic_stage_, last_event_, initial_time_, R_WI_, last_marg_, pre_integrations_,
                             tmp_pre_integration_ ? std::make_shared<Preintegration>(*tmp_pre_integration_) : nullptr, size_surf_stack_,
-                            imu_stamped_});
+                            imu_stamped_, opt_ring_, frame_seq_, corner_last_, opt_evicted_frame_});
+  if (opt_evicted_.n) {
+    snap_opt_evicted_.buf.reserve(opt_evicted_.n);
+    LIO_HIP(hipMemcpyAsync(snap_opt_evicted_.buf.p, opt_evicted_.buf.p, opt_evicted_.n * sizeof(float4), hipMemcpyDeviceToDevice, stream_));
+  }
+  snap_opt_evicted_.n = opt_evicted_.n; snap_opt_evicted_.id = opt_evicted_.id;
   snap_stacks_.resize(stacks_.size());
   for (size_t i = 0; i < stacks_.size(); ++i) {
     snap_stacks_[i].buf.reserve(std::max<size_t>(stacks_[i].n, 1));
@@ -1002,6 +1123,11 @@ bool Estimator::CopySnapshotOf(Estimator &src) {
     snap_stacks_[i].n = c.n;
     snap_stacks_[i].id = ++g_content_id;
   }
+  if (src.snap_opt_evicted_.n) {
+    snap_opt_evicted_.buf.reserve(src.snap_opt_evicted_.n, stream_);
+    LIO_HIP(hipMemcpyAsync(snap_opt_evicted_.buf.p, src.snap_opt_evicted_.buf.p, src.snap_opt_evicted_.n * sizeof(float4), hipMemcpyDeviceToDevice, stream_));
+  }
+  snap_opt_evicted_.n = src.snap_opt_evicted_.n; snap_opt_evicted_.id = ++g_content_id;
   LIO_HIP(hipStreamSynchronize(stream_));
   return true;
 }
@@ -1029,6 +1155,17 @@ bool Estimator::Restore() {
       LIO_HIP(hipMemcpyAsync(stacks_[i].buf.p, snap_stacks_[i].buf.p, snap_stacks_[i].n * sizeof(float4), hipMemcpyDeviceToDevice, stream_));
     stacks_[i].n = snap_stacks_[i].n;
   }
+  if (map_refresh_ || !h.opt_ring.empty()) {   // the ring: host bookkeeping and shared (immutable) corner clouds; the evicted frame by content id
+    opt_ring_ = h.opt_ring; corner_last_ = h.corner_last; opt_evicted_frame_ = h.opt_evicted_frame;
+    if (opt_evicted_.id != snap_opt_evicted_.id || opt_evicted_.n != snap_opt_evicted_.n) {
+      opt_evicted_.id = snap_opt_evicted_.id;
+      opt_evicted_.buf.reserve(std::max<size_t>(snap_opt_evicted_.n, 1));
+      if (snap_opt_evicted_.n)
+        LIO_HIP(hipMemcpyAsync(opt_evicted_.buf.p, snap_opt_evicted_.buf.p, snap_opt_evicted_.n * sizeof(float4), hipMemcpyDeviceToDevice, stream_));
+      opt_evicted_.n = snap_opt_evicted_.n;
+    }
+  }
+  frame_seq_ = h.frame_seq;
   // no host wait: every consumer of the stacks is ordered behind these copies on stream_ (or behind an event recorded on it)
   return true;
 }

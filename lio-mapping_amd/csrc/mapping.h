@@ -14,6 +14,7 @@
 #include "../../include/lio_c.h"
 #include "cloud_kernels.h"
 #include "hmath.h"
+#include "seg_sort.h"
 
 namespace lio {
 
@@ -26,6 +27,13 @@ struct MapValidSet {
   int n;
   int lo[3], hi[3];                 // absolute cube range [lo, hi) of the current 21x21x11 window
 };
+
+// the 5x5x5 surround of the last Process (PointMapping.cc:927,984) as packed absolute cube keys; ascending == list order (i-major)
+struct MapSurroundSet {
+  uint32_t key[LIO_MAP_MAX_VALID];
+  int n;
+};
+#define LIO_MAP_SURROUND_DROP 255u   // bin of a point outside the surround; kept points have bin 2 * slot + class (< 250)
 
 struct MapCounters { int n_valid, n_rest, n_new_valid, n_new_rest, n_out, pad[3]; };
 
@@ -41,6 +49,13 @@ class MappingDev {
   void Process(const float *corner_last, size_t n_corner, const float *surf_last, size_t n_surf, const Rigid<float> &transform_sum);
   void UpdateMapDatabase(const float *corner_ds, size_t n_corner, const float *surf_ds, size_t n_surf, const uint32_t *valid_idx, size_t n_valid,
                          const Rigid<float> &T, const int cube_center[3]);
+  // the same with the stacks where they live (HBM, sensor frame): no cloud crosses PCIe.  producer: the stream that wrote them (the
+  // update waits for it through an event; nullptr: they are complete).  Returns after the update has read them.
+  void UpdateMapDatabase(const float4 *d_corner_ds, size_t n_corner, const float4 *d_surf_ds, size_t n_surf, const uint32_t *valid_idx, size_t n_valid,
+                         const Rigid<float> &T, const int cube_center[3], hipStream_t producer);
+  // laser_cloud_surround_downsampled_ (PointMapping.cc:1223-1234): the cubes of surround_idx_ in list order, corner then surf points
+  // of each, through the VoxelGrid at `leaf`.  Returns the count; copies the points when out != nullptr.  0 before the first Process.
+  size_t GetSurround(float leaf, float *out);
   size_t GetCloud(int which, float *out);
   size_t GetCube(int cls, uint32_t cube_idx, float *out);
   size_t GetScorePointCoeff(float *score, float *point, float *coeff);
@@ -53,6 +68,7 @@ class MappingDev {
   bool imu_inited_ = false;
   int cen_[3] = {10, 10, 5};  // laser_cloud_cen_length_/width_/height_ (:76-78)
   std::vector<uint32_t> valid_idx_;
+  std::vector<uint32_t> surround_idx_;   // laser_cloud_surround_idx_: every in-range cube of the 5x5x5 neighbourhood, FOV or not
   int iterations_ = 0, num_selected_ = 0;
   bool degenerate_ = false;
   int kz_ = 0;   // leading update components masked by round 0's degeneracy test (PointMapping.cc:650-680)
@@ -111,6 +127,14 @@ class MappingDev {
   bool score_ready_ = false;
   size_t n_from_map_[2] = {0, 0};  // sizes of laser_cloud_{corner,surf}_from_map_ of the last Process
   bool from_map_in_u_ = false;      // the map update moved them into the work list
+  // surround-map assembly: bin per point of [corner pool | surf pool], one 8-bit seg_sort pass over it, gather
+  DBuf<uint32_t> sur_bin_, sur_bin2_, sur_src_, sur_hist_;
+  DBuf<SegDesc> sur_desc_;
+  DBuf<int> sur_count_;
+  HostBuf<int> h_sur_count_;
+  HostBuf<SegDesc> h_sur_desc_;
+  DBuf<float4> sur_cloud_, sur_out_;
+  VoxelGridDev sur_vox_;
   bool system_init_ = false;        // MapBuilder.h:65
   int odom_count_ = 0;              // MapBuilder.h:69
 };

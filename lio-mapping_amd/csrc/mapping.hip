@@ -231,6 +231,41 @@ __global__ void k_stack_roundtrip(const float4 *__restrict__ in, int n, Quat<flo
   out[i] = make_float4(r.x, r.y, r.z, p.w);
 }
 
+// Surround map, step 1: the bin of every point of [corner pool | surf pool].  A point of surround cube `slot` (list order) and class
+// c gets bin 2 * slot + c, so ascending bins are PointMapping.cc:1225-1229's order (cube by cube, corner cloud then surf cloud); a point
+// of any other cube gets LIO_MAP_SURROUND_DROP, which sorts behind every kept one.  The kept points are counted per wave.
+__global__ void __launch_bounds__(256) k_surround_bins(const uint32_t *__restrict__ pkey_c, int n_c, const uint32_t *__restrict__ pkey_s, int n_s,
+                                                       MapSurroundSet ss, uint32_t *__restrict__ bin, int *__restrict__ n_kept) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in = i < n_c + n_s;
+  uint32_t b = LIO_MAP_SURROUND_DROP;
+  if (in) {
+    const uint32_t cls = i >= n_c ? 1u : 0u;
+    const uint32_t key = cls ? pkey_s[i - n_c] : pkey_c[i];
+    int lo = 0, hi = ss.n;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (ss.key[mid] < key) lo = mid + 1; else hi = mid;
+    }
+    if (lo < ss.n && ss.key[lo] == key) b = 2u * uint32_t(lo) + cls;
+    bin[i] = b;
+  }
+  const unsigned long long kept = __ballot(in && b != LIO_MAP_SURROUND_DROP);
+  if ((threadIdx.x & 63) == 0 && kept) atomicAdd(n_kept, __popcll(kept));
+}
+
+// step 3 (step 2 is the stable 8-bit seg_sort pass on the bins): the kept points, which the sort left in front, in sorted order
+__global__ void __launch_bounds__(256) k_surround_gather(const float4 *__restrict__ pool_c, int n_c, const float4 *__restrict__ pool_s, int n_s,
+                                                         const uint32_t *__restrict__ bin_sorted, const uint32_t *__restrict__ src_sorted,
+                                                         float4 *__restrict__ out) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n_c + n_s) return;
+  if (bin_sorted[s] == LIO_MAP_SURROUND_DROP) return;
+  const uint32_t src = src_sorted[s];
+  if (src >= uint32_t(n_c + n_s)) return;
+  out[s] = src < uint32_t(n_c) ? pool_c[src] : pool_s[src - uint32_t(n_c)];
+}
+
 // math_utils.h:186-203 (degrees)
 inline Vec3<double> r2ypr_deg(const Mat3<double> &R) {
   const double y = std::atan2(R(1, 0), R(0, 0));
@@ -264,6 +299,10 @@ MappingDev::MappingDev(const lio_map_config &cfg) : cfg_(cfg) {
   h_state_ = reinterpret_cast<OdomState *>(h_mail_.p);
   h_flag_ = reinterpret_cast<unsigned *>(h_mail_.p + 64);
   d_state_.reserve(1);
+  sur_count_.reserve(1); sur_desc_.reserve(1);
+  h_sur_count_.alloc(1, hipHostMallocDefault, true);
+  h_sur_desc_.alloc(1, hipHostMallocDefault, true);
+  prepare_seg_sort_kernels();
 }
 
 MappingDev::~MappingDev() {
@@ -390,7 +429,23 @@ void MappingDev::UpdateFinish(ClassMap &m) {
 
 void MappingDev::UpdateMapDatabase(const float *corner_ds, size_t n_corner, const float *surf_ds, size_t n_surf, const uint32_t *valid_idx,
                                    size_t n_valid, const Rigid<float> &T, const int cube_center[3]) {
+  const float *src[2] = {corner_ds, surf_ds};
+  const size_t cnt[2] = {n_corner, n_surf};
+  for (int c = 0; c < 2; ++c) {
+    if (!cnt[c]) continue;
+    cls_[c].in.reserve(cnt[c]);
+    LIO_HIP(hipMemcpyAsync(cls_[c].in.p, src[c], cnt[c] * sizeof(float4), hipMemcpyHostToDevice, stream_));
+  }
+  UpdateMapDatabase(cls_[0].in.p, n_corner, cls_[1].in.p, n_surf, valid_idx, n_valid, T, cube_center, nullptr);
+}
+
+void MappingDev::UpdateMapDatabase(const float4 *d_corner_ds, size_t n_corner, const float4 *d_surf_ds, size_t n_surf, const uint32_t *valid_idx,
+                                   size_t n_valid, const Rigid<float> &T, const int cube_center[3], hipStream_t producer) {
   hipStream_t s = stream_;
+  if (producer && producer != s) {
+    LIO_HIP(hipEventRecord(ev_fork_, producer));
+    LIO_HIP(hipStreamWaitEvent(s, ev_fork_, 0));
+  }
   const MapValidSet vs = MakeValidSet(valid_idx, n_valid, cube_center);
   bool relayout[2];
   for (int c = 0; c < 2; ++c) {
@@ -399,19 +454,58 @@ void MappingDev::UpdateMapDatabase(const float *corner_ds, size_t n_corner, cons
   }
   if (relayout[0] || relayout[1]) LIO_HIP(hipStreamSynchronize(s));
   for (int c = 0; c < 2; ++c) if (relayout[c]) LayoutFinish(cls_[c], vs);
-  const float *src[2] = {corner_ds, surf_ds};
+  const float4 *src[2] = {d_corner_ds, d_surf_ds};
   const size_t cnt[2] = {n_corner, n_surf};
   const float leaf[2] = {cfg_.corner_filter_size, cfg_.surf_filter_size};
-  for (int c = 0; c < 2; ++c) {
-    ClassMap &m = cls_[c];
-    if (cnt[c]) {
-      m.in.reserve(cnt[c]);
-      LIO_HIP(hipMemcpyAsync(m.in.p, src[c], cnt[c] * sizeof(float4), hipMemcpyHostToDevice, s));
-    }
-    UpdateLaunch(m, m.in.p, cnt[c], vs, T, leaf[c]);
-  }
+  for (int c = 0; c < 2; ++c) UpdateLaunch(cls_[c], src[c], cnt[c], vs, T, leaf[c]);
   LIO_HIP(hipStreamSynchronize(s));
   for (int c = 0; c < 2; ++c) UpdateFinish(cls_[c]);
+}
+
+// PointMapping.cc:1223-1234
+size_t MappingDev::GetSurround(float leaf, float *out) {
+  hipStream_t s = stream_;
+  if (surround_idx_.empty()) return 0;   // before the first Process
+  const size_t n_c = cls_[0].n, n_s = cls_[1].n, n = n_c + n_s;
+  if (n == 0) return 0;
+  if (n > size_t(INT_MAX)) throw std::runtime_error("PointMapping: map pools beyond 2^31 points");
+  MapSurroundSet ss;
+  std::memset(&ss, 0, sizeof(ss));
+  {
+    std::vector<uint32_t> keys;
+    for (uint32_t idx : surround_idx_) {   // FromIndex (PointMapping.h:153-160); cen_ only moves in Process, which also rewrites the list
+      const int residual = int(idx % uint32_t(L * Wd));
+      const int ck = int(idx / uint32_t(L * Wd)), cj = residual / L, ci = residual % L;
+      keys.push_back(pack_cube(ci - cen_[0], cj - cen_[1], ck - cen_[2]));
+    }
+    std::sort(keys.begin(), keys.end());   // (the list is i-major already: ascending keys)
+    keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+    if (keys.size() > LIO_MAP_MAX_VALID) throw std::runtime_error("PointMapping: more than 125 surround cubes");
+    ss.n = int(keys.size());
+    for (int k = 0; k < ss.n; ++k) ss.key[k] = keys[size_t(k)];
+  }
+  const int nc = int(n_c), ns = int(n_s), ni = int(n);
+  SegDesc desc{0, ni, 0};
+  const SegSortPlan plan = seg_sort_plan(&desc, 1, 8);
+  *h_sur_desc_.p = desc;
+  sur_bin_.reserve(n); sur_bin2_.reserve(n); sur_src_.reserve(n); sur_hist_.reserve(std::max<size_t>(plan.hist_entries, 1)); sur_cloud_.reserve(n);
+  LIO_HIP(hipMemcpyAsync(sur_desc_.p, h_sur_desc_.p, sizeof(SegDesc), hipMemcpyHostToDevice, s));
+  LIO_HIP(hipMemsetAsync(sur_count_.p, 0, sizeof(int), s));
+  hipLaunchKernelGGL(k_surround_bins, dim3(cdiv(ni, 256)), dim3(256), 0, s, cls_[0].pkey.p, nc, cls_[1].pkey.p, ns, ss, sur_bin_.p, sur_count_.p);
+  // a stable multi-split into <= 250 bins IS one 8-bit pass of the segmented sort over one segment (values: the points' positions)
+  const SegSortPair sorted = seg_sort_passes(sur_desc_.p, 1, plan, sur_bin_.p, nullptr, {sur_bin2_.p, sur_src_.p}, {sur_bin_.p, sur_src_.p}, sur_hist_.p, 8, 1, nullptr, s);
+  hipLaunchKernelGGL(k_surround_gather, dim3(cdiv(ni, 256)), dim3(256), 0, s, cls_[0].pool.p, nc, cls_[1].pool.p, ns, sorted.keys, sorted.vals, sur_cloud_.p);
+  LIO_HIP(hipGetLastError());
+  LIO_HIP(hipMemcpyAsync(h_sur_count_.p, sur_count_.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  LIO_HIP(hipStreamSynchronize(s));   // the one wait of the assembly: the VoxelGrid is launched over the kept points
+  const size_t n_kept = size_t(*h_sur_count_.p);
+  if (n_kept == 0) return 0;
+  const size_t m = sur_vox_.run(sur_cloud_.p, n_kept, leaf, sur_out_, s);
+  if (out && m) {
+    LIO_HIP(hipMemcpyAsync(out, sur_out_.p, m * sizeof(float4), hipMemcpyDeviceToHost, s));
+    LIO_HIP(hipStreamSynchronize(s));
+  }
+  return m;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -471,6 +565,7 @@ void MappingDev::Process(const float *corner_last, size_t n_corner, const float 
   }
   // cubes of the 5x5x5 neighbourhood with a corner inside the +-60 deg cone (:938-989)
   valid_idx_.clear();
+  surround_idx_.clear();
   auto sqdiff = [](const float a[3], const float b[3]) {
     float dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
     return dx * dx + dy * dy + dz * dz;
@@ -491,6 +586,7 @@ void MappingDev::Process(const float *corner_last, size_t n_corner, const float 
               if (check1 < 0 && check2 > 0) fov = true;
             }
         if (fov) valid_idx_.push_back(uint32_t(i + L * j + L * Wd * k));
+        surround_idx_.push_back(uint32_t(i + L * j + L * Wd * k));   // :984
       }
   const MapValidSet vs = MakeValidSet(valid_idx_.data(), valid_idx_.size(), cen_);
 

@@ -269,6 +269,16 @@ _TEST_SIGS = {
     "lio_fit_five": (C.c_int, [C.c_int, c_float_p, c_float_p, c_float_p, C.c_size_t, C.POINTER(TransformF), c_float_p, C.c_float, C.c_float,
                                c_uint8_p, c_float_p, c_float_p, c_float_p]),
 }
+# include/lio_ext.h: the product's entry points beyond the shared ABI (the map refresh and the surround map).  Attached to the HIP
+# library only: the oracle does not implement them, and loading it must keep working
+_EXT_SIGS = {
+    "lio_est_map": (C.c_void_p, [C.c_void_p]),
+    "lio_est_set_map_refresh": (C.c_int, [C.c_void_p, C.c_int]),
+    "lio_est_refresh_map": (C.c_int, [C.c_void_p]),
+    "lio_map_get_surround": (C.c_size_t, [C.c_void_p, C.c_float, c_float_p]),
+    "lio_est_get_last_map_refresh": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(TransformF), C.POINTER(C.c_int), C.POINTER(C.c_uint32),
+                                               C.POINTER(C.c_int), C.POINTER(C.c_size_t), c_float_p, C.POINTER(C.c_size_t), c_float_p]),
+}
 
 
 def _dp(a):
@@ -317,6 +327,12 @@ class LioLib:
             fn.restype = res
             fn.argtypes = args
         self.backend = self.dll.lio_backend().decode()
+        self.has_ext = self.backend.startswith("hip")
+        if self.has_ext:
+            for name, (res, args) in _EXT_SIGS.items():
+                fn = getattr(self.dll, name)
+                fn.restype = res
+                fn.argtypes = args
 
     # ---- ImuInitializer (host math)
     @staticmethod
@@ -661,10 +677,26 @@ class PointMapping:
         if not self.h:
             raise LioError("lio_map_create failed")
 
+    @classmethod
+    def borrowed(cls, lib: LioLib, handle, owner):
+        """The lio_map of an estimator (lio_est_map): owned by `owner`, which this object keeps alive; never destroyed here."""
+        m = cls.__new__(cls)
+        m.lib, m.cfg, m.h, m.owner = lib, None, handle, owner
+        return m
+
     def __del__(self):
-        if getattr(self, "h", None):
+        if getattr(self, "h", None) and getattr(self, "owner", None) is None:
             self.lib.dll.lio_map_destroy(self.h)
-            self.h = None
+        self.h = None
+
+    def surround(self, leaf=0.6):
+        """lio_map_get_surround (include/lio_ext.h): the down-sampled 5 x 5 x 5 surround map, PointMapping.cc:1223-1234."""
+        n = self.lib.dll.lio_map_get_surround(self.h, leaf, None)
+        out = np.zeros((n, 4), dtype=np.float32)
+        if n:
+            m = self.lib.dll.lio_map_get_surround(self.h, leaf, _fp(out))
+            assert m == n
+        return out
 
     def process(self, corner_last, surf_last, T_sum):
         c, s = _f32(corner_last).reshape(-1, 4), _f32(surf_last).reshape(-1, 4)
@@ -928,6 +960,41 @@ class Estimator:
 
     def slide(self):
         _chk(self.lib.dll.lio_est_slide_window(self.h), "lio_est_slide_window")
+
+    # ---- include/lio_ext.h (the product only)
+    def map(self):
+        """The estimator's PointMapping base as a PointMapping object (borrowed: it lives as long as this estimator)."""
+        h = self.lib.dll.lio_est_map(self.h)
+        if not h:
+            raise LioError("lio_est_map failed")
+        return PointMapping.borrowed(self.lib, h, self)
+
+    def set_map_refresh(self, on):
+        _chk(self.lib.dll.lio_est_set_map_refresh(self.h, 1 if on else 0), "lio_est_set_map_refresh")
+
+    def refresh_map(self):
+        """Estimator.cc:703-708 after a solve, before the slide -> 1 the map was updated, 0 masked / ring not full."""
+        rc = self.lib.dll.lio_est_refresh_map(self.h)
+        if rc < 0:
+            raise LioError(f"lio_est_refresh_map failed with code {rc}")
+        return rc
+
+    def last_map_refresh(self):
+        """The arguments of the last refresh_map (test hook) or None before the first one."""
+        ap, nv = C.c_int(0), C.c_int(0)
+        T = TransformF()
+        cen = (C.c_int * 3)()
+        valid = np.zeros(125, dtype=np.uint32)
+        nc, ns = C.c_size_t(0), C.c_size_t(0)
+        vp = valid.ctypes.data_as(C.POINTER(C.c_uint32))
+        fn = self.lib.dll.lio_est_get_last_map_refresh
+        rc = fn(self.h, C.byref(ap), C.byref(T), cen, vp, C.byref(nv), C.byref(nc), None, C.byref(ns), None)
+        if rc != 0:
+            return None
+        corner, surf = np.zeros((nc.value, 4), np.float32), np.zeros((ns.value, 4), np.float32)
+        _chk(fn(self.h, None, None, None, None, None, None, _fp(corner) if nc.value else None, None, _fp(surf) if ns.value else None),
+             "lio_est_get_last_map_refresh")
+        return dict(applied=ap.value, T=T.to_np(), cube_center=list(cen), valid_idx=valid[:nv.value].copy(), corner=corner, surf=surf)
 
     def sync(self):
         """Wait for the handle's deferred work (the marginalization worker of the product)."""

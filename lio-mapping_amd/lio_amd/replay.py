@@ -20,11 +20,15 @@ from .capi import Estimator, EstConfig, LioLib, PointOdometry, PointProcessor, T
 
 class Replay:
     tap = None   # (class default: subclasses that build only the pairing buffers need not set it)
-    def __init__(self, lib: LioLib, cfg: EstConfig, lidar, odom_io: int = 2, msg_time_delay: float = 0.0, scan_period: float = 0.1, tap=None):
+    def __init__(self, lib: LioLib, cfg: EstConfig, lidar, odom_io: int = 2, msg_time_delay: float = 0.0, scan_period: float = 0.1, tap=None,
+                 map_refresh: bool = False):
         self.lib = lib
         self.pp = PointProcessor(lib, lidar.lower_deg, lidar.upper_deg, lidar.rings)
         self.od = PointOdometry(lib, scan_period, odom_io, 25, False)
         self.est = Estimator(lib, cfg)
+        self.map_refresh = bool(map_refresh)
+        if self.map_refresh:    # the map-database refresh after every solved window (Estimator.cc:703-708); self.est.map().surround() serves the map
+            self.est.set_map_refresh(True)
         self.cfg = cfg
         self.odom_io = odom_io
         self.delay = msg_time_delay
