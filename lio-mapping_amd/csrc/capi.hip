@@ -8,6 +8,7 @@
 #include "../../include/lio_c.h"
 #include "../../include/lio_test_hooks.h"
 #include "../../include/lio_ext.h"
+#include "../../include/lio_full_cloud.h"
 #include "est_batch.h"
 #include "seg_sort.h"
 #include "estimator.h"
@@ -819,6 +820,10 @@ int lio_est_process_compact(lio_est *h, const float *data, size_t n, double stam
     if (e.inited_ && !e.cfg_.imu_factor) return LIO_ERR_STATE;  // LOAM-only operation after init is not part of this path
     MappingDev &m = est_map(h);
     const float *corner = data + 4 * 3, *surf = data + 4 * (3 + nc);
+    if (e.full_cloud()) {
+      if (nf > size_t(INT_MAX) - 255) return LIO_ERR_CAPACITY;
+      m.SetFullCloud(data + 4 * (3 + nc + ns), nf);
+    }   // CompactDataHandler's third block (PointMapping.cc:212-224)
     if (e.inited_) {  // :780-803: predict transform_tobe_mapped_ with the IMU-propagated body motion
       const int W = e.W_;
       auto bodyPose = [&](int i) {
@@ -886,6 +891,78 @@ int lio_est_get_last_map_refresh(const lio_est *h, int *applied, lio_transform_f
     return int(LIO_OK);
   });
 }
+// ---------------------------------------------------------------- include/lio_full_cloud.h: the full-resolution sweep
+// int thread ids, one point per lane in workgroups of 256: the last workgroup's tail lanes must not pass INT_MAX
+static constexpr size_t kMaxCloudPoints = size_t(INT_MAX) - 255;
+// PointOdometry.cc:261-292 at :725-730
+int lio_odom_full_to_end(lio_odom *h, const float *xyzi, size_t n, float *xyzi_out) {
+  if (!h || (n && (!xyzi || !xyzi_out))) return LIO_ERR_ARG;
+  if (n > kMaxCloudPoints) return LIO_ERR_CAPACITY;
+  return guarded([&] { h->o->FullToEnd(xyzi, n, xyzi_out); return LIO_OK; });
+}
+// PointMapping.cc:212-224
+int lio_map_set_full_cloud(lio_map *h, const float *xyzi, size_t n) {
+  if (!h || !h->m || (!xyzi && n)) return LIO_ERR_ARG;
+  if (n > kMaxCloudPoints) return LIO_ERR_CAPACITY;
+  return guarded([&] { h->m->SetFullCloud(xyzi, n); return LIO_OK; });
+}
+// PointMapping.cc:1244-1251
+size_t lio_map_get_full_cloud(const lio_map *h, float *xyzi_or_null) {
+  if (!h || !h->m) return 0;
+  size_t n = 0;
+  guarded([&] { n = h->m->GetFullCloud(xyzi_or_null); return LIO_OK; });
+  return n;
+}
+// Estimator.cc:482, :2355-2420
+int lio_est_set_full_cloud(lio_est *h, int on) {
+  if (!h || (on != 0 && on != 1)) return LIO_ERR_ARG;
+  return guarded([&] { h->e->SetFullCloud(on != 0, &est_map(h)); return LIO_OK; });
+}
+// Estimator.cc:2372-2375
+size_t lio_est_get_full_stack(const lio_est *h, int frame, float *xyzi_or_null, int *state_or_null) {
+  if (!h) return 0;
+  const FullEntry *e = h->e->FullEntryOf(frame);
+  if (!e) return 0;
+  size_t n = 0;
+  if (guarded([&] { n = h->e->CopyCloudToHost(&e->cloud, xyzi_or_null); return LIO_OK; }) != LIO_OK) return 0;
+  if (state_or_null) *state_or_null = e->state;
+  return n;
+}
+// Estimator.cc:2284-2286, :2293-2295, :2311 and PointMapping.cc:303-314
+int lio_est_get_registered_full(const lio_est *h, int frame, lio_transform_f *T_out_or_null, size_t *n_out, float *xyzi_or_null) {
+  if (!h) return LIO_ERR_ARG;
+  return guarded([&] {
+    Rigidf T;
+    size_t n = 0;
+    if (!h->e->RegisteredFull(frame, &T, &n, xyzi_or_null)) return int(LIO_ERR_STATE);
+    if (T_out_or_null) fromT(T, T_out_or_null);
+    if (n_out) *n_out = n;
+    return int(LIO_OK);
+  });
+}
+int lio_est_get_full_transform_es(const lio_est *h, int frame, lio_transform_f *T_es) {
+  if (!h || !T_es) return LIO_ERR_ARG;
+  const FullEntry *e = h->e->FullEntryOf(frame);
+  if (!e) return LIO_ERR_STATE;
+  fromT(e->tes, T_es);
+  return LIO_OK;
+}
+// Estimator.cc:62-103
+int lio_deskew_to_end(const float *xyzi, size_t n, const lio_transform_f *T_es, float time_factor, int keep_intensity, float *xyzi_out) {
+  if (!T_es || (keep_intensity != 0 && keep_intensity != 1) || (n && (!xyzi || !xyzi_out))) return LIO_ERR_ARG;
+  if (n > kMaxCloudPoints) return LIO_ERR_CAPACITY;
+  if (!n) return LIO_OK;
+  return guarded([&] {
+    Scratch &sc = scratch();
+    sc.a.reserve(n);
+    LIO_HIP(hipMemcpyAsync(sc.a.p, xyzi, n * sizeof(float4), hipMemcpyHostToDevice, sc.s));
+    launch_deskew_to_end(sc.a.p, int(n), T_es->q, T_es->p, time_factor, sc.s, keep_intensity != 0);
+    LIO_HIP(hipMemcpyAsync(xyzi_out, sc.a.p, n * sizeof(float4), hipMemcpyDeviceToHost, sc.s));
+    LIO_HIP(hipStreamSynchronize(sc.s));
+    return LIO_OK;
+  });
+}
+
 int lio_est_get_stage(const lio_est *h, int *stage, int *cir_buf_count, int *extrinsic_stage, int *last_event, double *R_WI, double *g_vec) {
   if (!h) return LIO_ERR_ARG;
   const Estimator &e = *h->e;

@@ -21,6 +21,27 @@ __device__ inline bool finite3(const float4 &p) { return isfinite(p.x) && isfini
 __device__ inline bool finite3(const Vec3<float> &p) { return isfinite(p.x) && isfinite(p.y) && isfinite(p.z); }
 
 
+// TransformToEnd of one point, x y z only: q_e * (slerp(id, s, q_e).conjugate() * (p - s t)) + t.  Stated once for its two forms:
+// the estimator's (Estimator.cc:62-103) normalises the conjugate (:88), the odometry's (PointOdometry.cc:261-292) does not.  What a
+// form does with the intensity (strip the ring, strip the fraction, keep both) is the calling kernel's; .w is returned as it came.
+template <bool NORMALISE_CONJ>
+__device__ __forceinline__ float4 to_end_point(float4 p, float s, const Quat<float> &qe, const Vec3<float> &te) {
+  p.x -= s * te.x; p.y -= s * te.y; p.z -= s * te.z;
+  Quat<float> qid;
+  Quat<float> qs = slerp(qid, s, qe, FLT_EPSILON);
+  Quat<float> qc = conj(qs);
+  if (NORMALISE_CONJ) qc = normalized(qc);
+  Vec3<float> v = rotate(qc, Vec3<float>(p.x, p.y, p.z));
+  v = rotate(qe, v);
+  p.x = v.x + te.x; p.y = v.y + te.y; p.z = v.z + te.z;
+  return p;
+}
+// PointAssociateToMap (PointMapping.cc:303-314): rot * p + pos in the operation order of rotate (hmath.h), intensity kept
+__device__ __forceinline__ float4 rigid_map_point(float4 p, const Quat<float> &q, const Vec3<float> &t) {
+  const Vec3<float> v = rotate(q, Vec3<float>(p.x, p.y, p.z));
+  return make_float4(v.x + t.x, v.y + t.y, v.z + t.z, p.w);
+}
+
 __device__ inline int cell_coord(float v, float inv_cell) { return int(floorf(v * inv_cell)); }
 // the cell of (x, y, z) relative to the grid's origin; true when it lies inside the grid
 __device__ __forceinline__ bool cell_of(float x, float y, float z, const GridDesc &g, int &cx, int &cy, int &cz) {

@@ -28,8 +28,11 @@ struct ConcatArgs { ConcatSeg seg[LIO_MAX_FRAMES]; int nseg; int total; };
 // dst[seg.dst_off + k] = tf * src[k] (or src[k] when identity); intensity optionally overwritten
 void launch_transform_concat(const ConcatArgs &a, float4 *dst, hipStream_t s);
 
-// TransformToEnd (Estimator.cc:62-103) in place; tes = q(xyzw), p
-void launch_deskew_to_end(float4 *pts, int n, const float q[4], const float p[3], float time_factor, hipStream_t s);
+// TransformToEnd (Estimator.cc:62-103) in place; tes = q(xyzw), p.  keep_intensity (:79): the form SolveOptimization runs on the
+// full-resolution cloud (:2355-2420); x y z are the same bits in both forms
+void launch_deskew_to_end(float4 *pts, int n, const float q[4], const float p[3], float time_factor, hipStream_t s, bool keep_intensity = false);
+// out = rot * in + pos, intensity kept (PointAssociateToMap, PointMapping.cc:303-314); out of place
+void launch_rigid_map(const float4 *in, int n, const float q[4], const float p[3], float4 *out, hipStream_t s);
 
 // min/max (VoxParams.mn/.mx, n_valid) of a device cloud; `partial` is scratch.  No host sync.
 void launch_cloud_bounds(const float4 *pts, int n, DBuf<float> &partial, VoxParams *d_out, hipStream_t s);

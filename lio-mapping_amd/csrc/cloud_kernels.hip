@@ -53,24 +53,35 @@ void launch_transform_concat(const ConcatArgs &a, float4 *dst, hipStream_t s) {
 // ------------------------------------------------------------------------------------------------
 // deskew (TransformToEnd)
 // ------------------------------------------------------------------------------------------------
-__global__ void k_deskew_to_end(float4 *pts, int n, Quat<float> qe, Vec3<float> te, float time_factor) {
+// One point per lane: one 16-byte load, one 16-byte store, 256 lanes per workgroup, cdiv(n, 256) workgroups (an HDL-64E sweep of 130 k
+// points: 508, one launch).  KEEP: the intensity (ring + rel_time) is carried through (keep_intensity, :79); else the ring is stripped.
+template <bool KEEP>
+__global__ void __launch_bounds__(256) k_deskew_to_end(float4 *pts, int n, Quat<float> qe, Vec3<float> te, float time_factor) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float4 p = pts[i];
   float s = time_factor * (p.w - int(p.w));
-  p.x -= s * te.x; p.y -= s * te.y; p.z -= s * te.z;
-  p.w -= int(p.w);
-  Quat<float> qid;
-  Quat<float> qs = slerp(qid, s, qe, FLT_EPSILON);
-  Vec3<float> v = rotate(normalized(conj(qs)), Vec3<float>(p.x, p.y, p.z));
-  v = rotate(qe, v);
-  p.x = v.x + te.x; p.y = v.y + te.y; p.z = v.z + te.z;
-  pts[i] = p;
+  if (!KEEP) p.w -= int(p.w);
+  pts[i] = to_end_point<true>(p, s, qe, te);
 }
-void launch_deskew_to_end(float4 *pts, int n, const float q[4], const float p[3], float time_factor, hipStream_t s) {
+void launch_deskew_to_end(float4 *pts, int n, const float q[4], const float p[3], float time_factor, hipStream_t s, bool keep_intensity) {
   if (n <= 0) return;
-  hipLaunchKernelGGL(k_deskew_to_end, dim3(cdiv(n, 256)), dim3(256), 0, s, pts, n, Quat<float>(q[3], q[0], q[1], q[2]),
-                     Vec3<float>(p[0], p[1], p[2]), time_factor);
+  const Quat<float> qe(q[3], q[0], q[1], q[2]);
+  const Vec3<float> te(p[0], p[1], p[2]);
+  if (keep_intensity) hipLaunchKernelGGL(k_deskew_to_end<true>, dim3(cdiv(n, 256)), dim3(256), 0, s, pts, n, qe, te, time_factor);
+  else hipLaunchKernelGGL(k_deskew_to_end<false>, dim3(cdiv(n, 256)), dim3(256), 0, s, pts, n, qe, te, time_factor);
+  LIO_HIP(hipGetLastError());
+}
+
+// out[i] = rot * in[i] + pos, intensity kept (PointAssociateToMap, PointMapping.cc:303-314); out of place, in != out
+__global__ void __launch_bounds__(256) k_rigid_map(const float4 *__restrict__ in, int n, Quat<float> q, Vec3<float> t, float4 *__restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = rigid_map_point(in[i], q, t);
+}
+void launch_rigid_map(const float4 *in, int n, const float q[4], const float p[3], float4 *out, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_rigid_map, dim3(cdiv(n, 256)), dim3(256), 0, s, in, n, Quat<float>(q[3], q[0], q[1], q[2]), Vec3<float>(p[0], p[1], p[2]), out);
   LIO_HIP(hipGetLastError());
 }
 

@@ -635,6 +635,8 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
   // ------------------------------------------------------------------------------------------------ windows the device loop did not take
   for (int w = 0; w < B; ++w) ok_[size_t(w)] = 1;
   for (int w : host_path) ok_[size_t(w)] = win_[w].e->SolveOptimizationHost(&reps[w]) ? 1 : 0;
+  for (int w = 0; w < B; ++w)   // the end of SolveOptimization for a window the device loop solved (the host path does it itself)
+    if (win_[w].device && win_[w].e->full_cloud()) win_[w].e->CorrectNewestFull();
   const double t6 = now_ms();
   clk_.fallback = t6 - t5;
   clk_.total = t6 - t0;

@@ -78,6 +78,16 @@ struct MapRefreshRecord {
   OptSlot slot;
 };
 
+// One entry of full_stack_ (Estimator.cc:482; include/lio_full_cloud.h): the full-resolution sweep of a window frame, the transform_es_ its
+// frame was pushed with (identity under cutoff_deskew and with both de-skew switches off) and where it stands.  The states are
+// LIO_FULL_* of the header.
+enum { FULL_NONE = 0, FULL_MAP_FRAME = 1, FULL_SENSOR_RAW = 2, FULL_SENSOR_END = 3 };
+struct FullEntry {
+  DeviceCloud cloud;
+  int state = FULL_NONE;
+  Rigidf tes;
+};
+
 // HIP-event kernel timing on the estimator's stream (lio_est_enable_kernel_timing)
 enum { KT_FEATURES = 0, KT_ODOM_FEATURES, KT_ODOM_ROWS, KT_ODOM_UPDATE, KT_MOMENTS, KT_VOXEL, KT_KNN_GRID, KT_CONCAT, KT_COUNT };
 struct KernelTimers {
@@ -210,7 +220,16 @@ class Estimator {
   // the surf cloud an optimisation-window slot holds, where it is now (nullptr: the frame has left the window)
   const DeviceCloud *OptSurfCloud(long surf_frame) const;
   size_t CopyCloudToHost(const DeviceCloud *c, float *out);
-  MappingDev *map_ = nullptr;   // the PointMapping base (owned by the C handle); read by PushFrame and RefreshMap only while the refresh is on
+  MappingDev *map_ = nullptr;   // the PointMapping base (owned by the C handle); read by PushFrame and RefreshMap only while the refresh or the full cloud is on
+  // ---- the full-resolution sweep (include/lio_full_cloud.h), off unless SetFullCloud(true, map): PushFrame then copies the map's full
+  // cloud into a ring of W + 1 that moves with the window, every completed solve corrects the newest entry once
+  void SetFullCloud(bool on, MappingDev *map);
+  bool full_cloud() const { return full_cloud_; }
+  void CorrectNewestFull();                       // Estimator.cc:2355-2420 (update_laser_imu): TransformToEnd(full_stack_.last(), transform_es_, 10, true)
+  const FullEntry *FullEntryOf(int frame) const;  // nullptr: the frame has no entry
+  Rigidf OptPose(int i) const;                    // the lidar pose of window frame i (Estimator.cc:2284-2286, :2293-2295): in double, cast to float
+  // a FULL_SENSOR_END entry mapped by its frame's lidar pose, out of place; false for any other state
+  bool RegisteredFull(int frame, Rigidf *T, size_t *n, float *out);
   bool RunInitialization();
   void SetStatesFromLaser();
   // Estimator.cc:1648-2438.  With a hook installed (lio_est_config.device_solve: a batch of one window, est_batch.h) the whole
@@ -383,7 +402,13 @@ class Estimator {
   DeviceCloud upload_corner_;
   VoxelGridDev vox_corner_;
   MapRefreshRecord last_refresh_;
-  Rigidf OptPose0() const;                      // Estimator.cc:2282-2286
+  Rigidf OptPose0() const { return OptPose(W_ - Wo_); }   // Estimator.cc:2282-2286
+  // ---- full-cloud state (empty while the switch is off)
+  bool full_cloud_ = false;
+  std::vector<FullEntry> full_ring_;            // CircularBuffer of W + 1 entries, oldest first; the newest belongs to the window's newest frame
+  DBuf<float4> full_out_;                       // RegisteredFull's output before it goes to the host
+  void PushFull(const Rigidf &tes);
+  void DropFullRing();
 };
 
 }  // namespace lio

@@ -416,10 +416,12 @@ bool Estimator::PushFrame(const Rigidf &transform_in, const float *surf, size_t 
       LIO_HIP(hipMemcpyAsync(fresh.buf.p, surf, n_surf * sizeof(float4), surf_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
     fresh.n = n_surf;
     fresh.id = ++g_content_id;
+    PushFull(Rigidf());
     LIO_HIP(hipStreamSynchronize(stream_));  // the source may be reused by the caller right after the call
     PushCloud(std::move(fresh), n_surf, n_before);
     return true;
   }
+  Rigidf full_tes;   // transform_es_ as SolveOptimization meets it (:2355): identity unless this push computes it
   // host -> HBM (the only PCIe traffic of the step besides the small state/moment exchanges)
   upload_.buf.reserve(std::max<size_t>(n_surf, 1));
   if (n_surf)
@@ -444,6 +446,7 @@ bool Estimator::PushFrame(const Rigidf &transform_in, const float *surf, size_t 
       body_es.pos = s * body_es.pos;
       Rigidf tes = compose(compose(transform_lb_, body_es), rinverse(transform_lb_));
       q[0] = tes.rot.x; q[1] = tes.rot.y; q[2] = tes.rot.z; q[3] = tes.rot.w; p[0] = tes.pos.x; p[1] = tes.pos.y; p[2] = tes.pos.z;
+      full_tes = tes;
       launch_deskew_to_end(upload_.buf.p, int(n_surf), q, p, 10.f, stream_);
     }
     // corner clouds are only consumed under USE_CORNER (off in the shipped build, Estimator.h:55) and by the map refresh: processed
@@ -466,6 +469,69 @@ bool Estimator::PushFrame(const Rigidf &transform_in, const float *surf, size_t 
   size_t nfresh = fresh.n;
   fresh.id = ++g_content_id;
   PushCloud(std::move(fresh), nfresh, n_before);
+  PushFull(full_tes);
+  return true;
+}
+
+// ---- the full-resolution sweep
+void Estimator::SetFullCloud(bool on, MappingDev *map) {
+  map_ = map;
+  if (on == full_cloud_) return;
+  full_cloud_ = on;
+  full_ring_.clear();   // nothing is held while it is off
+  if (!on) { full_ring_.shrink_to_fit(); full_out_.release(); }
+}
+void Estimator::DropFullRing() { full_ring_.clear(); }
+// full_stack_.push(full_cloud_) (Estimator.cc:482): the map's current full cloud, device to device, behind its registration
+void Estimator::PushFull(const Rigidf &tes) {
+  if (!full_cloud_) return;
+  FullEntry e;
+  if (int(full_ring_.size()) == W_ + 1) {   // the oldest entry goes; its buffer is recycled
+    e = std::move(full_ring_.front());
+    full_ring_.erase(full_ring_.begin());
+  }
+  const size_t n = map_ ? map_->FullSize() : 0;
+  e.cloud.buf.reserve(std::max<size_t>(n, 1));
+  if (n) {
+    map_->FullWaitOn(stream_);
+    LIO_HIP(hipMemcpyAsync(e.cloud.buf.p, map_->FullDevice(), n * sizeof(float4), hipMemcpyDeviceToDevice, stream_));
+    map_->FullReadBy(stream_);
+  }
+  e.cloud.n = n;
+  e.cloud.id = ++g_content_id;
+  e.state = inited_ ? FULL_SENSOR_RAW : FULL_MAP_FRAME;   // before initialisation PublishResults has registered it (PointMapping.cc:1244-1248)
+  e.tes = tes;
+  full_ring_.push_back(std::move(e));
+}
+// A map-frame entry is left alone: on the initialising step (:575) transform_es_ is the constructed identity and the intensities are
+// integral, which makes the reference's call there an exact no-op.  The state keeps a second solve of the same window from correcting twice.
+void Estimator::CorrectNewestFull() {
+  if (full_ring_.empty()) return;
+  FullEntry &e = full_ring_.back();
+  if (e.state != FULL_SENSOR_RAW) return;
+  const float q[4] = {e.tes.rot.x, e.tes.rot.y, e.tes.rot.z, e.tes.rot.w}, p[3] = {e.tes.pos.x, e.tes.pos.y, e.tes.pos.z};
+  launch_deskew_to_end(e.cloud.buf.p, int(e.cloud.n), q, p, 10.f, stream_, true);
+  e.state = FULL_SENSOR_END;
+}
+const FullEntry *Estimator::FullEntryOf(int frame) const {
+  // the ring's newest entry belongs to the window's newest frame; a frame older than the ring's oldest entry has none
+  const int idx = frame - (n_frames_ - int(full_ring_.size()));
+  if (frame < 0 || frame >= n_frames_ || idx < 0 || idx >= int(full_ring_.size())) return nullptr;
+  return &full_ring_[size_t(idx)];
+}
+bool Estimator::RegisteredFull(int frame, Rigidf *T, size_t *n, float *out) {
+  const FullEntry *e = FullEntryOf(frame);
+  if (!inited_ || !e || e->state != FULL_SENSOR_END) return false;
+  const Rigidf pose = OptPose(frame);
+  if (T) *T = pose;
+  if (n) *n = e->cloud.n;
+  if (out && e->cloud.n) {
+    const float q[4] = {pose.rot.x, pose.rot.y, pose.rot.z, pose.rot.w}, p[3] = {pose.pos.x, pose.pos.y, pose.pos.z};
+    full_out_.reserve(e->cloud.n);
+    launch_rigid_map(e->cloud.buf.p, int(e->cloud.n), q, p, full_out_.p, stream_);
+    LIO_HIP(hipMemcpyAsync(out, full_out_.p, e->cloud.n * sizeof(float4), hipMemcpyDeviceToHost, stream_));
+    LIO_HIP(hipStreamSynchronize(stream_));
+  }
   return true;
 }
 
@@ -498,13 +564,13 @@ size_t Estimator::CopyCloudToHost(const DeviceCloud *c, float *out) {
   return c->n;
 }
 
-// Estimator.cc:2282-2286 (update_laser_imu, which every shipped configuration sets): the optimised lidar pose of frame W - Wo, in double, cast to float
-Rigidf Estimator::OptPose0() const {
+// Estimator.cc:2282-2286 for frame W - Wo, :2293-2295 for the others (update_laser_imu, which every shipped configuration sets): the
+// optimised lidar pose of a window frame, in double, cast to float
+Rigidf Estimator::OptPose(int i) const {
   const Rigidd lb = toDouble(transform_lb_);
-  const int opt_0 = W_ - Wo_;
-  const Qd rot_l0 = fromRot(Rs_[opt_0] * toRot(normalized(conj(lb.rot))));
-  const V3d pos_l0 = Ps_[opt_0] - rotate(rot_l0, lb.pos);
-  return toFloat(Rigidd(rot_l0, pos_l0));
+  const Qd rot_li = fromRot(Rs_[i] * toRot(normalized(conj(lb.rot))));
+  const V3d pos_li = Ps_[i] - rotate(rot_li, lb.pos);
+  return toFloat(Rigidd(rot_li, pos_li));
 }
 
 int Estimator::RefreshMap() {
@@ -1037,6 +1103,7 @@ bool Estimator::SolveOptimizationHost(lio_solve_report *rep) {
   resident_.PrintDebugTiming();
   if (g_debug_timing) std::fprintf(stderr, "[lio_hip timing] of which hipStreamSynchronize %.3f ms\n", dbg_sync_ms_);
   dbg_eval_ms_ = 0; dbg_eval_n_ = 0; dbg_sync_ms_ = 0;
+  CorrectNewestFull();
   return true;
 }
 
@@ -1113,6 +1180,7 @@ void Estimator::Snapshot() {
 bool Estimator::CopySnapshotOf(Estimator &src) {
   if (!src.snap_ || src.W_ != W_ || src.Wo_ != Wo_ || &src == this) return false;
   JoinMarg();
+  if (full_cloud_) DropFullRing();   // snapshots do not carry full clouds
   frames_dirty_ = true;
   snap_.reset(new HostState(*src.snap_));   // pre-integrations and the prior are immutable once pushed: shared
   snap_stacks_.resize(src.snap_stacks_.size());
@@ -1134,6 +1202,7 @@ bool Estimator::CopySnapshotOf(Estimator &src) {
 
 bool Estimator::Restore() {
   if (!snap_) return false;
+  if (full_cloud_) DropFullRing();   // snapshots do not carry full clouds
   ++marg_epoch_;  // a marginalization still in flight belongs to the state being discarded: its result is dropped at the next join
   const HostState &h = *snap_;
   Ps_ = h.Ps; Vs_ = h.Vs; Bas_ = h.Bas; Bgs_ = h.Bgs; Rs_ = h.Rs; g_vec_ = h.g_vec; acc_last_ = h.acc_last; gyr_last_ = h.gyr_last;

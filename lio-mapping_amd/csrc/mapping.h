@@ -57,6 +57,15 @@ class MappingDev {
   // of each, through the VoxelGrid at `leaf`.  Returns the count; copies the points when out != nullptr.  0 before the first Process.
   size_t GetSurround(float leaf, float *out);
   size_t GetCloud(int which, float *out);
+  // full_cloud_ (PointMapping.cc:212-224): the full-resolution sweep, sensor frame until a Process with the init flag off has mapped it
+  // in place with the transform_tobe_mapped_ it ended with (PublishResults, :1244-1248) — once per set.  n = 0 clears it.
+  void SetFullCloud(const float *xyzi, size_t n);
+  size_t GetFullCloud(float *out);
+  const float4 *FullDevice() const { return full_.p; }
+  size_t FullSize() const { return n_full_; }
+  void FullWaitOn(hipStream_t consumer);
+  void FullReadBy(hipStream_t consumer);
+  hipStream_t stream() const { return stream_; }
   size_t GetCube(int cls, uint32_t cube_idx, float *out);
   size_t GetScorePointCoeff(float *score, float *point, float *coeff);
   // laser_cloud_{corner,surf}_stack_downsampled_ where they live (HBM), for the estimator's pre-initialisation pushes
@@ -111,7 +120,8 @@ class MappingDev {
 
   lio_map_config cfg_;
   hipStream_t stream_ = nullptr, stream2_ = nullptr;   // stream2_: the surf stack's VoxelGrid beside the corner one
-  hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr;
+  hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr, ev_full_ = nullptr, ev_full_read_ = nullptr;   // ev_full_: recorded behind the full cloud's registration
+  bool full_event_ = false, full_read_ = false;   // ev_full_read_: behind another stream's copy out of it
   ClassMap cls_[2];  // 0 corner, 1 surf
   float pz_[3] = {0, 0, 10};
   DBuf<float4> stack_all_;
@@ -135,6 +145,9 @@ class MappingDev {
   HostBuf<SegDesc> h_sur_desc_;
   DBuf<float4> sur_cloud_, sur_out_;
   VoxelGridDev sur_vox_;
+  DBuf<float4> full_, full_in_;     // full_cloud_ and the sensor-frame upload the registration reads (it writes out of place)
+  size_t n_full_ = 0;
+  bool full_mapped_ = false;        // this set has been through PublishResults
   bool system_init_ = false;        // MapBuilder.h:65
   int odom_count_ = 0;              // MapBuilder.h:69
 };

@@ -286,6 +286,8 @@ MappingDev::MappingDev(const lio_map_config &cfg) : cfg_(cfg) {
   LIO_HIP(hipStreamCreateWithFlags(&stream2_, hipStreamNonBlocking));
   LIO_HIP(hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
   LIO_HIP(hipEventCreateWithFlags(&ev_join_, hipEventDisableTiming));
+  LIO_HIP(hipEventCreateWithFlags(&ev_full_, hipEventDisableTiming));
+  LIO_HIP(hipEventCreateWithFlags(&ev_full_read_, hipEventDisableTiming));
   for (ClassMap &m : cls_) {
     m.h_counters.alloc(1, hipHostMallocDefault, true);
     m.h_bounds.alloc(1, hipHostMallocDefault, true);
@@ -308,6 +310,8 @@ MappingDev::MappingDev(const lio_map_config &cfg) : cfg_(cfg) {
 MappingDev::~MappingDev() {
   if (ev_fork_) (void)hipEventDestroy(ev_fork_);
   if (ev_join_) (void)hipEventDestroy(ev_join_);
+  if (ev_full_) (void)hipEventDestroy(ev_full_);
+  if (ev_full_read_) (void)hipEventDestroy(ev_full_read_);
   if (stream2_) (void)hipStreamDestroy(stream2_);
   if (stream_) (void)hipStreamDestroy(stream_);
 }
@@ -508,6 +512,31 @@ size_t MappingDev::GetSurround(float leaf, float *out) {
   return m;
 }
 
+void MappingDev::SetFullCloud(const float *xyzi, size_t n) {
+  n_full_ = n; full_mapped_ = false; full_event_ = false;
+  if (!n) return;
+  full_.reserve(n);
+  if (full_read_) LIO_HIP(hipStreamWaitEvent(stream_, ev_full_read_, 0));
+  LIO_HIP(hipMemcpyAsync(full_.p, xyzi, n * sizeof(float4), hipMemcpyHostToDevice, stream_));
+  LIO_HIP(hipStreamSynchronize(stream_));   // the caller may reuse the source right after the call
+}
+// a reader of FullDevice() on another stream is ordered behind the registration: no host wait
+void MappingDev::FullWaitOn(hipStream_t consumer) {
+  if (full_event_) LIO_HIP(hipStreamWaitEvent(consumer, ev_full_, 0));
+}
+// ... and the next writer of the buffers behind that reader's copy
+void MappingDev::FullReadBy(hipStream_t consumer) {
+  LIO_HIP(hipEventRecord(ev_full_read_, consumer));
+  full_read_ = true;
+}
+size_t MappingDev::GetFullCloud(float *out) {
+  if (out && n_full_) {
+    LIO_HIP(hipMemcpyAsync(out, full_.p, n_full_ * sizeof(float4), hipMemcpyDeviceToHost, stream_));
+    LIO_HIP(hipStreamSynchronize(stream_));
+  }
+  return n_full_;
+}
+
 // ------------------------------------------------------------------------------------------------
 void MappingDev::Process(const float *corner_last, size_t n_corner, const float *surf_last, size_t n_surf, const Rigid<float> &sum) {
   hipStream_t s = stream_;
@@ -631,6 +660,16 @@ void MappingDev::Process(const float *corner_last, size_t n_corner, const float 
     LIO_HIP(hipStreamSynchronize(s));
     for (int c = 0; c < 2; ++c) UpdateFinish(cls_[c]);
     from_map_in_u_ = true;
+  }
+  if (!imu_inited_ && n_full_ && !full_mapped_) {   // PublishResults (:1105 -> :1244-1248): PointAssociateToMap on full_cloud_, in place
+    const Rigid<float> &T = transform_tobe_mapped_;
+    const float q[4] = {T.rot.x, T.rot.y, T.rot.z, T.rot.w}, p[3] = {T.pos.x, T.pos.y, T.pos.z};
+    std::swap(full_, full_in_);
+    full_.reserve(n_full_);
+    if (full_read_) LIO_HIP(hipStreamWaitEvent(s, ev_full_read_, 0));
+    launch_rigid_map(full_in_.p, int(n_full_), q, p, full_.p, s);
+    LIO_HIP(hipEventRecord(ev_full_, s));
+    full_mapped_ = true; full_event_ = true;
   }
   if (dbg)
     std::fprintf(stderr, "[lio_hip map timing] upload+layout %.3f  stack voxel %.3f  optimise %.3f (%d rounds)  map update %.3f  total %.3f ms\n", tt1 - tt0,

@@ -13,6 +13,8 @@ class OdometryDev {
   void Process(const float *sharp, size_t n_sharp, const float *less_sharp, size_t n_ls, const float *flat, size_t n_flat, const float *less_flat,
                size_t n_lf);
   size_t GetLastCloud(int which, float *out);
+  // TransformToEnd(full_cloud_) with the last Process's transform_es_ (:725-730); a byte copy while the odometry is disabled
+  void FullToEnd(const float *xyzi, size_t n, float *out);
 
   Rigid<float> transform_es_, transform_sum_;
   int iterations_done_ = 0, last_num_sel_ = 0;
@@ -25,7 +27,8 @@ class OdometryDev {
   int io_ratio_, max_iter_;
   bool no_deskew_, inited_ = false;
   hipStream_t stream_ = nullptr;
-  DBuf<float4> sharp_, flat_, less_sharp_, less_flat_, last_corner_, last_surf_;
+  DBuf<float4> sharp_, flat_, less_sharp_, less_flat_, last_corner_, last_surf_, full_;
+  bool to_end_ready_ = false;  // a Process has run TransformToEnd: d_state_ holds the transform_es_ it used
   size_t n_last_corner_ = 0, n_last_surf_ = 0;
   DBuf<int> idx_;              // 2*nc + 3*ns correspondence indices
   DBuf<OdomState> d_state_;

@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "odometry.h"
+#include "cloud_device.h"
 
 namespace lio {
 
@@ -330,22 +331,17 @@ __device__ __forceinline__ void odo_update_step(const double *ssum, OdomState *s
   if (double(delta_r) < 0.1 && double(delta_t) < 0.1) st->converged = 1;
 }
 
-__global__ void k_odo_to_end(float4 *pts, int n, const OdomState *__restrict__ st, float time_factor, int no_deskew) {
+// TransformToEnd (:261-292) with the transform_es_ the iterations left on the device; out == in: in place
+__global__ void __launch_bounds__(256) k_odo_to_end(const float4 *in, float4 *out, int n, const OdomState *__restrict__ st, float time_factor, int no_deskew) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   Quat<float> qe(st->T[3], st->T[0], st->T[1], st->T[2]);
   Vec3<float> te(st->T[4], st->T[5], st->T[6]);
-  float4 p = pts[i];
+  float4 p = in[i];
   float s = time_factor * (p.w - int(p.w));
   if (no_deskew) s = 0;
-  p.x -= s * te.x; p.y -= s * te.y; p.z -= s * te.z;
   p.w = float(int(p.w));
-  Quat<float> qid;
-  Quat<float> qs = slerp(qid, s, qe, FLT_EPSILON);
-  Vec3<float> v = rotate(conj(qs), Vec3<float>(p.x, p.y, p.z));
-  v = rotate(qe, v);
-  p.x = v.x + te.x; p.y = v.y + te.y; p.z = v.z + te.z;
-  pts[i] = p;
+  out[i] = to_end_point<false>(p, s, qe, te);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -455,14 +451,32 @@ void OdometryDev::Process(const float *sharp, size_t n_sharp, const float *less_
     transform_es_ = Rigid<float>(Quat<float>(st.T[3], st.T[0], st.T[1], st.T[2]), Vec3<float>(st.T[4], st.T[5], st.T[6]));
     // :654-656 accumulate, :660-661 TransformToEnd, :663 normalise
     transform_sum_ = compose(transform_sum_, rinverse(transform_es_));
-    if (n_ls) hipLaunchKernelGGL(k_odo_to_end, dim3(cdiv(n_ls, 256)), dim3(256), 0, s, less_sharp_.p, int(n_ls), d_state_.p, time_factor_, no_deskew_ ? 1 : 0);
-    if (n_lf) hipLaunchKernelGGL(k_odo_to_end, dim3(cdiv(n_lf, 256)), dim3(256), 0, s, less_flat_.p, int(n_lf), d_state_.p, time_factor_, no_deskew_ ? 1 : 0);
+    if (n_ls) hipLaunchKernelGGL(k_odo_to_end, dim3(cdiv(n_ls, 256)), dim3(256), 0, s, less_sharp_.p, less_sharp_.p, int(n_ls), d_state_.p, time_factor_, no_deskew_ ? 1 : 0);
+    if (n_lf) hipLaunchKernelGGL(k_odo_to_end, dim3(cdiv(n_lf, 256)), dim3(256), 0, s, less_flat_.p, less_flat_.p, int(n_lf), d_state_.p, time_factor_, no_deskew_ ? 1 : 0);
     LIO_HIP(hipGetLastError());
     transform_es_.rot = normalized(transform_es_.rot);
+    to_end_ready_ = true;
   }
   LIO_HIP(hipStreamSynchronize(s));
   std::swap(last_corner_, less_sharp_); std::swap(last_surf_, less_flat_);
   n_last_corner_ = n_ls; n_last_surf_ = n_lf;
+}
+
+// TransformToEnd(full_cloud_) of a publishing step (:725-730): the same kernel and the same device-side transform_es_ as the
+// less-sharp / less-flat clouds of the last Process.  A byte copy while the odometry is disabled (:727) and before the first
+// publishing step: the first Process returns at :302-310 without publishing, so nothing has touched the cloud.
+void OdometryDev::FullToEnd(const float *xyzi, size_t n, float *out) {
+  if (!n) return;
+  if (!enable_odom_ || !to_end_ready_) {
+    if (out != xyzi) std::memmove(out, xyzi, n * sizeof(float4));
+    return;
+  }
+  hipStream_t s = stream_;
+  upload(full_, xyzi, n, s);
+  hipLaunchKernelGGL(k_odo_to_end, dim3(cdiv(n, 256)), dim3(256), 0, s, full_.p, full_.p, int(n), d_state_.p, time_factor_, no_deskew_ ? 1 : 0);
+  LIO_HIP(hipGetLastError());
+  LIO_HIP(hipMemcpyAsync(out, full_.p, n * sizeof(float4), hipMemcpyDeviceToHost, s));
+  LIO_HIP(hipStreamSynchronize(s));
 }
 
 size_t OdometryDev::GetLastCloud(int which, float *out) {

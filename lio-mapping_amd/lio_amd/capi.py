@@ -279,6 +279,18 @@ _EXT_SIGS = {
     "lio_est_get_last_map_refresh": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(TransformF), C.POINTER(C.c_int), C.POINTER(C.c_uint32),
                                                C.POINTER(C.c_int), C.POINTER(C.c_size_t), c_float_p, C.POINTER(C.c_size_t), c_float_p]),
 }
+# include/lio_full_cloud.h: the full-resolution sweep on the device (the product only, attached like _EXT_SIGS)
+_FULL_SIGS = {
+    "lio_odom_full_to_end": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, c_float_p]),
+    "lio_map_set_full_cloud": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t]),
+    "lio_map_get_full_cloud": (C.c_size_t, [C.c_void_p, c_float_p]),
+    "lio_est_set_full_cloud": (C.c_int, [C.c_void_p, C.c_int]),
+    "lio_est_get_full_stack": (C.c_size_t, [C.c_void_p, C.c_int, c_float_p, C.POINTER(C.c_int)]),
+    "lio_est_get_registered_full": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(TransformF), C.POINTER(C.c_size_t), c_float_p]),
+    "lio_est_get_full_transform_es": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(TransformF)]),
+    "lio_deskew_to_end": (C.c_int, [c_float_p, C.c_size_t, C.POINTER(TransformF), C.c_float, C.c_int, c_float_p]),
+}
+FULL_MAP_FRAME, FULL_SENSOR_RAW, FULL_SENSOR_END = 1, 2, 3   # LIO_FULL_* of include/lio_full_cloud.h
 
 
 def _dp(a):
@@ -329,10 +341,17 @@ class LioLib:
         self.backend = self.dll.lio_backend().decode()
         self.has_ext = self.backend.startswith("hip")
         if self.has_ext:
-            for name, (res, args) in _EXT_SIGS.items():
+            for name, (res, args) in list(_EXT_SIGS.items()) + list(_FULL_SIGS.items()):
                 fn = getattr(self.dll, name)
                 fn.restype = res
                 fn.argtypes = args
+
+    def deskew_to_end(self, xyzi, T_es: TransformF, time_factor=10.0, keep_intensity=False):
+        """lio_deskew_to_end (include/lio_full_cloud.h, test hook): the estimator's TransformToEnd, Estimator.cc:62-103."""
+        c = _f32(xyzi).reshape(-1, 4)
+        out = np.zeros_like(c)
+        _chk(self.dll.lio_deskew_to_end(_fp(c), c.shape[0], C.byref(T_es), time_factor, 1 if keep_intensity else 0, _fp(out)), "lio_deskew_to_end")
+        return out
 
     # ---- ImuInitializer (host math)
     @staticmethod
@@ -698,6 +717,20 @@ class PointMapping:
             assert m == n
         return out
 
+    def set_full_cloud(self, xyzi):
+        """lio_map_set_full_cloud (include/lio_full_cloud.h): full_cloud_, PointMapping.cc:212-224; an empty cloud clears it."""
+        c = _f32(xyzi).reshape(-1, 4)
+        _chk(self.lib.dll.lio_map_set_full_cloud(self.h, _fp(c), c.shape[0]), "lio_map_set_full_cloud")
+
+    def full_cloud(self):
+        """lio_map_get_full_cloud: full_cloud_ as it is now (/cloud_registered after a process with the init flag off)."""
+        n = self.lib.dll.lio_map_get_full_cloud(self.h, None)
+        out = np.zeros((n, 4), dtype=np.float32)
+        if n:
+            m = self.lib.dll.lio_map_get_full_cloud(self.h, _fp(out))
+            assert m == n
+        return out
+
     def process(self, corner_last, surf_last, T_sum):
         c, s = _f32(corner_last).reshape(-1, 4), _f32(surf_last).reshape(-1, 4)
         Ts = TransformF.make(*T_sum)
@@ -890,6 +923,13 @@ class PointOdometry:
     def enable(self, on):
         _chk(self.lib.dll.lio_odom_enable(self.h, 1 if on else 0), "lio_odom_enable")
 
+    def full_to_end(self, xyzi):
+        """lio_odom_full_to_end (include/lio_full_cloud.h): TransformToEnd(full_cloud_), PointOdometry.cc:261-292 at :725-730."""
+        c = _f32(xyzi).reshape(-1, 4)
+        out = np.zeros_like(c)
+        _chk(self.lib.dll.lio_odom_full_to_end(self.h, _fp(c), c.shape[0], _fp(out)), "lio_odom_full_to_end")
+        return out
+
     def last_cloud(self, which):
         n = self.lib.dll.lio_odom_get_last_cloud(self.h, which, None)
         out = np.zeros((n, 4), dtype=np.float32)
@@ -995,6 +1035,35 @@ class Estimator:
         _chk(fn(self.h, None, None, None, None, None, None, _fp(corner) if nc.value else None, None, _fp(surf) if ns.value else None),
              "lio_est_get_last_map_refresh")
         return dict(applied=ap.value, T=T.to_np(), cube_center=list(cen), valid_idx=valid[:nv.value].copy(), corner=corner, surf=surf)
+
+    # ---- include/lio_full_cloud.h (the product only)
+    def set_full_cloud(self, on):
+        _chk(self.lib.dll.lio_est_set_full_cloud(self.h, 1 if on else 0), "lio_est_set_full_cloud")
+
+    def full_stack(self, frame):
+        """lio_est_get_full_stack -> (points, LIO_FULL_* state) of window frame `frame`, or (empty, None) for a frame without an entry."""
+        st = C.c_int(0)
+        n = self.lib.dll.lio_est_get_full_stack(self.h, frame, None, C.byref(st))
+        out = np.zeros((n, 4), dtype=np.float32)
+        if n:
+            m = self.lib.dll.lio_est_get_full_stack(self.h, frame, _fp(out), None)
+            assert m == n
+        return out, (st.value or None)
+
+    def full_transform_es(self, frame):
+        """The transform_es_ kept with the entry (test hook) as (q xyzw, p)."""
+        T = TransformF()
+        _chk(self.lib.dll.lio_est_get_full_transform_es(self.h, frame, C.byref(T)), "lio_est_get_full_transform_es")
+        return T.to_np()
+
+    def registered_full(self, frame):
+        """lio_est_get_registered_full -> ((q xyzw, p) lidar pose of the frame, its corrected full cloud mapped into the world)."""
+        T, n = TransformF(), C.c_size_t(0)
+        _chk(self.lib.dll.lio_est_get_registered_full(self.h, frame, C.byref(T), C.byref(n), None), "lio_est_get_registered_full")
+        out = np.zeros((n.value, 4), dtype=np.float32)
+        if n.value:
+            _chk(self.lib.dll.lio_est_get_registered_full(self.h, frame, None, None, _fp(out)), "lio_est_get_registered_full")
+        return T.to_np(), out
 
     def sync(self):
         """Wait for the handle's deferred work (the marginalization worker of the product)."""

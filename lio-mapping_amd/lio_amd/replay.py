@@ -21,7 +21,7 @@ from .capi import Estimator, EstConfig, LioLib, PointOdometry, PointProcessor, T
 class Replay:
     tap = None   # (class default: subclasses that build only the pairing buffers need not set it)
     def __init__(self, lib: LioLib, cfg: EstConfig, lidar, odom_io: int = 2, msg_time_delay: float = 0.0, scan_period: float = 0.1, tap=None,
-                 map_refresh: bool = False):
+                 map_refresh: bool = False, full_cloud: bool = False):
         self.lib = lib
         self.pp = PointProcessor(lib, lidar.lower_deg, lidar.upper_deg, lidar.rings)
         self.od = PointOdometry(lib, scan_period, odom_io, 25, False)
@@ -29,6 +29,9 @@ class Replay:
         self.map_refresh = bool(map_refresh)
         if self.map_refresh:    # the map-database refresh after every solved window (Estimator.cc:703-708); self.est.map().surround() serves the map
             self.est.set_map_refresh(True)
+        self.full_cloud = bool(full_cloud)
+        if self.full_cloud:     # the full-resolution sweep rides in /compact_data and is kept per window frame (include/lio_full_cloud.h)
+            self.est.set_full_cloud(True)
         self.cfg = cfg
         self.odom_io = odom_io
         self.delay = msg_time_delay
@@ -54,7 +57,10 @@ class Replay:
         if self.odom_io < 2 or self.odom_frame_count % self.odom_io == 1:
             T = TransformF.make(*r["T_sum"])
             corner, surf = self.od.last_cloud(0), self.od.last_cloud(1)
-            full = np.zeros((0, 4), np.float32)  # full_cloud_ is only republished for display
+            if self.full_cloud:   # TransformToEnd(full_cloud_) before it is sent (PointOdometry.cc:725-730)
+                full = self.od.full_to_end(self.pp.cloud(PointProcessor.RINGS))
+            else:
+                full = np.zeros((0, 4), np.float32)  # full_cloud_ is only republished for display
             self.compact_buf.append((stamp, self.lib.compact_encode(T, corner, surf, full)))
             if self.tap:
                 self.tap("compact", stamp, self.compact_buf[-1][1])
