@@ -71,6 +71,36 @@ int lio_fit_five(int form, const float *nbr_xyz, const float *fifth_sqd, const f
                  const float *fixed_pz, float min_match_sq_dis, float min_plane_dis, uint8_t *valid, float *coeff, float *score,
                  float *abs_coeff);
 
+/* The correspondence search every scan-to-scan residual starts from (csrc/odometry.hip: k_odo_corr, one wave per query, launched by
+ * PointOdometry's Process at every fifth iteration), on its own and stateless: PointOdometry.cc:237-259 (TransformToStart), :342-385
+ * (corner: closest and second), :440-494 (surf: closest, second and third).  Clouds are xyzi, intensity = ring + relative time.
+ *   sel      TransformToStart of the query at transform_es: s = (1 / scan_period) * (intensity - int(intensity)), 0 with no_deskew;
+ *            a query with s < 0 or s > 1.001 passes through unchanged (and is searched for as it stands); otherwise
+ *            sel = conj(slerp(identity, s, q_es)) * (p - s t_es), the conjugate not normalised.
+ *   closest  the point of the previous cloud (last_corner for a sharp query, last_surf for a flat one) with the smallest fp32 squared
+ *            distance to sel (d = dx*dx; d += dy*dy; d += dz*dz); among equal distances the lower index; accepted only if d < 25.
+ *   window   with cs = int(intensity[closest]): j = closest + 1 .. upward until the first j with int(intensity[j]) > cs + 2.5 — nothing
+ *            at or behind that j is seen —, then j = closest - 1 .. 0 downward until the first int(intensity[j]) < cs - 2.5.
+ *   corner   second: upward candidates of ring > cs, downward candidates of ring < cs.
+ *   surf     second: upward ring <= cs, downward ring >= cs;  third: upward ring > cs, downward ring < cs.
+ *   a slot takes its candidate with the smallest distance below 25; among equal distances the first in walk order: any upward
+ *   candidate before any downward one, nearer to closest first.  A missing entry is -1; without closest all entries are -1.
+ * corner_idx: n_sharp x 2 (closest, second); surf_idx: n_flat x 3 (closest, second, third); sel_out: (n_sharp + n_flat) x 3, sharp first.
+ * The intensity of a query enters through s alone.  A query with a NaN or infinite coordinate, or (unless no_deskew) a NaN intensity,
+ * has no finite sel: it finds nothing (all -1; its sel_out row is not specified) and does not disturb the other queries.  An infinite
+ * intensity is a time ratio outside [0, 1.001] like any other (the query passes through); with no_deskew s = 0 whatever the intensity.
+ * The previous clouds are expected finite.  Empty previous clouds give all -1; n_sharp == n_flat == 0 is fine.  A null required pointer
+ * (a cloud pointer may be null when its count is 0) or a scan_period that is not positive and finite: LIO_ERR_ARG.  The > 10 / > 100
+ * size gate of Process (:335) is not applied.
+ * Product: uploads the clouds into a device object of its own, builds the two 5 m grids with the function Process uses
+ * (OdometryDev::BuildGrids), launches k_odo_corr ONCE through the launch statement Process uses, and fills sel_out from a separate
+ * one-query-per-lane kernel that calls the same odo_to_start.  Oracle: the functions its own Process loop calls, serially. */
+int lio_odom_correspondences(const float *sharp_xyzi, size_t n_sharp, const float *flat_xyzi, size_t n_flat,
+                             const float *last_corner_xyzi, size_t n_last_corner, const float *last_surf_xyzi, size_t n_last_surf,
+                             const lio_transform_f *transform_es, float scan_period, int no_deskew,
+                             int32_t *corner_idx /* n_sharp x 2 */, int32_t *surf_idx /* n_flat x 3 */,
+                             float *sel_out /* (n_sharp + n_flat) x 3, sharp first */);
+
 #ifdef __cplusplus
 }
 #endif

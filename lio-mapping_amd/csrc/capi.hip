@@ -639,6 +639,20 @@ int lio_fit_five(int form, const float *nbr_xyz, const float *fifth_sqd, const f
   });
 }
 
+int lio_odom_correspondences(const float *sharp, size_t n_sharp, const float *flat, size_t n_flat, const float *last_corner, size_t n_lc,
+                             const float *last_surf, size_t n_lsf, const lio_transform_f *T, float scan_period, int no_deskew,
+                             int32_t *corner_idx, int32_t *surf_idx, float *sel_out) {
+  if ((!sharp && n_sharp) || (!flat && n_flat) || (!last_corner && n_lc) || (!last_surf && n_lsf) || !T || !corner_idx || !surf_idx || !sel_out)
+    return LIO_ERR_ARG;
+  if (!(scan_period > 0) || !std::isfinite(scan_period)) return LIO_ERR_ARG;
+  if (n_sharp + n_flat > size_t(INT_MAX) / 4 || n_lc > size_t(1) << 24 || n_lsf > size_t(1) << 24) return LIO_ERR_CAPACITY;   // k_odo_corr's scan-order keys
+  return guarded([&] {
+    OdometryDev od(scan_period, 1, 1, no_deskew != 0);   // stateless: a device object of its own, gone on return
+    od.Correspondences(sharp, n_sharp, flat, n_flat, last_corner, n_lc, last_surf, n_lsf, toT(*T), corner_idx, surf_idx, sel_out);
+    return LIO_OK;
+  });
+}
+
 int lio_calculate_features(const float *map, size_t n_map, const float *stack, size_t m, const lio_transform_f *T, float mm, float mp,
                            uint8_t *valid, float *coeff, float *score) {
   if ((!map && n_map) || (!stack && m) || !T || !valid || !coeff || !score || !(mm > 0)) return LIO_ERR_ARG;

@@ -6,6 +6,8 @@
 
 namespace lio {
 
+struct OdoArgs;
+
 class OdometryDev {
  public:
   OdometryDev(float scan_period, int io_ratio, int max_iter, bool no_deskew);
@@ -15,6 +17,10 @@ class OdometryDev {
   size_t GetLastCloud(int which, float *out);
   // TransformToEnd(full_cloud_) with the last Process's transform_es_ (:725-730); a byte copy while the odometry is disabled
   void FullToEnd(const float *xyzi, size_t n, float *out);
+  // the correspondence search of one iteration on caller-given clouds and transform_es_ (lio_odom_correspondences,
+  // include/lio_test_hooks.h): corner_idx n_sharp x 2, surf_idx n_flat x 3, sel_out (n_sharp + n_flat) x 3
+  void Correspondences(const float *sharp, size_t n_sharp, const float *flat, size_t n_flat, const float *last_corner, size_t n_last_corner,
+                       const float *last_surf, size_t n_last_surf, const Rigid<float> &T, int32_t *corner_idx, int32_t *surf_idx, float *sel_out);
 
   Rigid<float> transform_es_, transform_sum_;
   int iterations_done_ = 0, last_num_sel_ = 0;
@@ -36,6 +42,8 @@ class OdometryDev {
   DBuf<float> d_trace_;        // 8 floats per iteration, written by k_odo_update
   std::vector<float> h_trace_;
   void BuildGrids();
+  OdoArgs Args(size_t n_sharp, size_t n_flat) const;
+  DBuf<float> d_sel_;          // 3 floats per query (Correspondences)
   KnnGrid grid_c_, grid_s_;
   DBuf<float> partial_c_, partial_s_;
   DBuf<VoxParams> bounds_;

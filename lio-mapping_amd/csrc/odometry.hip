@@ -9,6 +9,7 @@
 //                reduced to per-block partials.
 //   k_odo_update 6x6 solve, degeneracy mask (threshold 10, A.6), update, abort test (:573-650).
 //   k_odo_to_end TransformToEnd (:262-292).
+//   k_odo_sel    TransformToStart of every query on its own, one query per lane (the test hook lio_odom_correspondences).
 // The <= 25 rounds run without a host round trip except a convergence peek every 5 rounds.
 #include <hip/hip_runtime.h>
 
@@ -177,6 +178,24 @@ __global__ void __launch_bounds__(64) k_odo_corr(OdoArgs a, const OdomState *__r
     if (corner) { idx[2 * qi] = closest; idx[2 * qi + 1] = second; }
     else { int o = 2 * a.nc + 3 * (qi - a.nc); idx[o] = closest; idx[o + 1] = second; idx[o + 2] = third; }
   }
+}
+
+// The one statement of the correspondence launch: Process (every fifth iteration) and the test hook lio_odom_correspondences
+static void launch_odo_corr(const OdoArgs &a, const OdomState *st, int *idx, hipStream_t s) {
+  const int nq = a.nc + a.ns;
+  if (nq > 0) hipLaunchKernelGGL(k_odo_corr, dim3(nq), dim3(64), 0, s, a, st, idx);
+}
+
+// sel of every query (sharp first), as k_odo_corr and k_odo_rows see it: 3 floats per query
+__global__ void __launch_bounds__(256) k_odo_sel(OdoArgs a, const OdomState *__restrict__ st, float *__restrict__ sel_out) {
+  const int qi = blockIdx.x * blockDim.x + threadIdx.x;
+  if (qi >= a.nc + a.ns) return;
+  const float4 pi = qi < a.nc ? a.sharp[qi] : a.flat[qi - a.nc];
+  Quat<float> qe(st->T[3], st->T[0], st->T[1], st->T[2]);
+  Vec3<float> te(st->T[4], st->T[5], st->T[6]);
+  Vec3<float> sel;
+  odo_to_start(pi, qe, te, a.time_factor, a.no_deskew, sel);
+  sel_out[3 * qi] = sel.x; sel_out[3 * qi + 1] = sel.y; sel_out[3 * qi + 2] = sel.z;
 }
 
 #define ODO_ROW_THREADS 256
@@ -366,6 +385,10 @@ void OdometryDev::BuildGrids() {
   launch_cloud_bounds(last_surf_.p, int(n_last_surf_), partial_s_, bounds_.p + 1, s);
   LIO_HIP(hipMemcpyAsync(h_bounds_.p, bounds_.p, 2 * sizeof(VoxParams), hipMemcpyDeviceToHost, s));
   LIO_HIP(hipStreamSynchronize(s));
+  // a cloud without a finite point (the test hook allows empty ones; Process asks for > 10 and > 100 points) has no bounds
+  for (int k = 0; k < 2; ++k)
+    if (h_bounds_.p[k].n_valid == 0)
+      for (int d = 0; d < 3; ++d) h_bounds_.p[k].mn[d] = h_bounds_.p[k].mx[d] = 0.f;
   const float cell = 5.0f * 1.0001f;
   grid_c_.build(last_corner_.p, n_last_corner_, h_bounds_.p[0].mn, h_bounds_.p[0].mx, cell, s);
   grid_s_.build(last_surf_.p, n_last_surf_, h_bounds_.p[1].mn, h_bounds_.p[1].mx, cell, s);
@@ -374,6 +397,12 @@ void OdometryDev::BuildGrids() {
 static void upload(DBuf<float4> &b, const float *src, size_t n, hipStream_t s) {
   b.reserve(std::max<size_t>(n, 1));
   if (n) LIO_HIP(hipMemcpyAsync(b.p, src, n * sizeof(float4), hipMemcpyHostToDevice, s));
+}
+
+// the kernels' view of sharp_ / flat_ against the previous sweep's clouds and their grids (after BuildGrids)
+OdoArgs OdometryDev::Args(size_t n_sharp, size_t n_flat) const {
+  return OdoArgs{sharp_.p, int(n_sharp), flat_.p, int(n_flat), last_corner_.p, int(n_last_corner_), last_surf_.p, int(n_last_surf_), time_factor_,
+                 no_deskew_ ? 1 : 0, grid_c_.sorted(), grid_c_.cells(), grid_c_.desc(), grid_s_.sorted(), grid_s_.cells(), grid_s_.desc()};
 }
 
 void OdometryDev::Process(const float *sharp, size_t n_sharp, const float *less_sharp, size_t n_ls, const float *flat, size_t n_flat,
@@ -407,8 +436,7 @@ void OdometryDev::Process(const float *sharp, size_t n_sharp, const float *less_
       idx_.reserve(std::max<size_t>(2 * n_sharp + 3 * n_flat, 1));
       LIO_HIP(hipMemsetAsync(idx_.p, 0xFF, (2 * n_sharp + 3 * n_flat) * sizeof(int), s));
       BuildGrids();
-      OdoArgs a{sharp_.p, int(n_sharp), flat_.p, int(n_flat), last_corner_.p, int(n_last_corner_), last_surf_.p, int(n_last_surf_), time_factor_,
-                no_deskew_ ? 1 : 0, grid_c_.sorted(), grid_c_.cells(), grid_c_.desc(), grid_s_.sorted(), grid_s_.cells(), grid_s_.desc()};
+      const OdoArgs a = Args(n_sharp, n_flat);
       const int nb = std::max(1, std::min(cdiv(nq, ODO_ROW_THREADS), 64));
       d_partials_.reserve(size_t(nb) * 28);
       d_trace_.reserve(size_t(max_iter_) * 8);
@@ -420,7 +448,7 @@ void OdometryDev::Process(const float *sharp, size_t n_sharp, const float *less_
           st = *h_state_;
           if (st.converged) { have_state = true; break; }
         }
-        if (nq > 0 && iter % 5 == 0) hipLaunchKernelGGL(k_odo_corr, dim3(nq), dim3(64), 0, s, a, d_state_.p, idx_.p);
+        if (iter % 5 == 0) launch_odo_corr(a, d_state_.p, idx_.p, s);
         hipLaunchKernelGGL(k_odo_rows, dim3(nb), dim3(ODO_ROW_THREADS), 0, s, a, d_state_.p, idx_.p, iter, d_partials_.p);
         HostSignal sg{};
         if (iter % 5 == 4 || iter == max_iter_ - 1) { sig.flag = h_flag_; sig.seq = ++seq_; sg = sig; }
@@ -460,6 +488,38 @@ void OdometryDev::Process(const float *sharp, size_t n_sharp, const float *less_
   LIO_HIP(hipStreamSynchronize(s));
   std::swap(last_corner_, less_sharp_); std::swap(last_surf_, less_flat_);
   n_last_corner_ = n_ls; n_last_surf_ = n_lf;
+}
+
+// lio_odom_correspondences (include/lio_test_hooks.h): the given clouds as the previous sweep's, the grids Process builds, ONE launch of
+// k_odo_corr at the given transform_es_, and sel of every query from k_odo_sel.  Meant for a handle of its own: the clouds it leaves
+// behind are the caller's.
+void OdometryDev::Correspondences(const float *sharp, size_t n_sharp, const float *flat, size_t n_flat, const float *last_corner, size_t n_lc,
+                                  const float *last_surf, size_t n_lsf, const Rigid<float> &T, int32_t *corner_idx, int32_t *surf_idx,
+                                  float *sel_out) {
+  hipStream_t s = stream_;
+  upload(sharp_, sharp, n_sharp, s);
+  upload(flat_, flat, n_flat, s);
+  upload(last_corner_, last_corner, n_lc, s);
+  upload(last_surf_, last_surf, n_lsf, s);
+  n_last_corner_ = n_lc; n_last_surf_ = n_lsf;
+  OdomState st{};
+  st.T[0] = T.rot.x; st.T[1] = T.rot.y; st.T[2] = T.rot.z; st.T[3] = T.rot.w;
+  st.T[4] = T.pos.x; st.T[5] = T.pos.y; st.T[6] = T.pos.z;
+  LIO_HIP(hipMemcpyAsync(d_state_.p, &st, sizeof(st), hipMemcpyHostToDevice, s));
+  const size_t nq = n_sharp + n_flat, ni = 2 * n_sharp + 3 * n_flat;
+  idx_.reserve(std::max<size_t>(ni, 1));
+  if (ni) LIO_HIP(hipMemsetAsync(idx_.p, 0xFF, ni * sizeof(int), s));
+  BuildGrids();   // waits for the uploads: `st` and the caller's arrays have been read
+  const OdoArgs a = Args(n_sharp, n_flat);
+  launch_odo_corr(a, d_state_.p, idx_.p, s);
+  d_sel_.reserve(std::max<size_t>(3 * nq, 1));
+  if (nq) hipLaunchKernelGGL(k_odo_sel, dim3(cdiv(nq, 256)), dim3(256), 0, s, a, d_state_.p, d_sel_.p);
+  LIO_HIP(hipGetLastError());
+  static_assert(sizeof(int) == sizeof(int32_t), "index layout");
+  if (n_sharp) LIO_HIP(hipMemcpyAsync(corner_idx, idx_.p, 2 * n_sharp * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (n_flat) LIO_HIP(hipMemcpyAsync(surf_idx, idx_.p + 2 * n_sharp, 3 * n_flat * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (nq) LIO_HIP(hipMemcpyAsync(sel_out, d_sel_.p, 3 * nq * sizeof(float), hipMemcpyDeviceToHost, s));
+  LIO_HIP(hipStreamSynchronize(s));
 }
 
 // TransformToEnd(full_cloud_) of a publishing step (:725-730): the same kernel and the same device-side transform_es_ as the

@@ -268,6 +268,8 @@ _TEST_SIGS = {
     "lio_knn_walk": (C.c_int, [c_float_p, C.c_size_t, c_float_p, C.c_size_t, C.c_float, C.c_int, c_int32_p, c_float_p, c_float_p]),
     "lio_fit_five": (C.c_int, [C.c_int, c_float_p, c_float_p, c_float_p, C.c_size_t, C.POINTER(TransformF), c_float_p, C.c_float, C.c_float,
                                c_uint8_p, c_float_p, c_float_p, c_float_p]),
+    "lio_odom_correspondences": (C.c_int, [c_float_p, C.c_size_t, c_float_p, C.c_size_t, c_float_p, C.c_size_t, c_float_p, C.c_size_t,
+                                           C.POINTER(TransformF), C.c_float, C.c_int, c_int32_p, c_int32_p, c_float_p]),
 }
 # include/lio_ext.h: the product's entry points beyond the shared ABI (the map refresh and the surround map).  Attached to the HIP
 # library only: the oracle does not implement them, and loading it must keep working
@@ -463,6 +465,22 @@ class LioLib:
         _chk(self.dll.lio_fit_five(int(form), _fp(n_), _fp(f_), _fp(s_), m, C.byref(T), _fp(pz), float(min_match_sq_dis), float(min_plane_dis),
                                    valid.ctypes.data_as(c_uint8_p), _fp(coeff), _fp(score), _fp(abs_coeff)), "lio_fit_five")
         return valid, coeff, score, abs_coeff
+
+    def odom_correspondences(self, sharp, flat, last_corner, last_surf, T_es: TransformF, scan_period=0.1, no_deskew=False):
+        """the scan-to-scan correspondence search on its own (include/lio_test_hooks.h: lio_odom_correspondences) ->
+        (corner_idx (n_sharp, 2) int32, surf_idx (n_flat, 3) int32, -1 = missing; sel (n_sharp + n_flat, 3) fp32, sharp first)"""
+        cl = [_f32(c).reshape(-1, 4) for c in (sharp, flat, last_corner, last_surf)]
+        nc, ns = cl[0].shape[0], cl[1].shape[0]
+        corner_idx = np.zeros((nc, 2), dtype=np.int32)
+        surf_idx = np.zeros((ns, 3), dtype=np.int32)
+        sel = np.zeros((nc + ns, 3), dtype=np.float32)
+        args = []
+        for c in cl:
+            args += [_fp(c), c.shape[0]]
+        _chk(self.dll.lio_odom_correspondences(*args, C.byref(T_es), float(scan_period), 1 if no_deskew else 0,
+                                               corner_idx.ctypes.data_as(c_int32_p), surf_idx.ctypes.data_as(c_int32_p), _fp(sel)),
+             "lio_odom_correspondences")
+        return corner_idx, surf_idx, sel
 
     def calculate_features(self, map_xyzi, stack_xyzi, T: TransformF, min_match_sq_dis=1.0, min_plane_dis=0.2):
         m_ = _f32(map_xyzi).reshape(-1, 4)

@@ -475,6 +475,42 @@ int lio_knn_walk(const float *map, size_t n_map, const float *query, size_t m, f
   }
   return LIO_OK;
 }
+// lio_odom_correspondences (include/lio_test_hooks.h): TransformToStart and the two correspondence searches of PointOdometry::Process,
+// the functions its own loop calls, serially.  Non-finite queries are decided here, before any float -> int conversion sees them.
+int lio_odom_correspondences(const float *sharp, size_t n_sharp, const float *flat, size_t n_flat, const float *last_corner, size_t n_lc,
+                             const float *last_surf, size_t n_lsf, const lio_transform_f *T, float scan_period, int no_deskew,
+                             int32_t *corner_idx, int32_t *surf_idx, float *sel_out) {
+  if ((!sharp && n_sharp) || (!flat && n_flat) || (!last_corner && n_lc) || (!last_surf && n_lsf) || !T || !corner_idx || !surf_idx || !sel_out)
+    return LIO_ERR_ARG;
+  if (!(scan_period > 0) || !std::isfinite(scan_period)) return LIO_ERR_ARG;
+  PointOdometry od(scan_period, 1, 1, no_deskew != 0);
+  od.transform_es_ = toT(*T);
+  const Cloud lc = toCloud(last_corner, n_lc), ls = toCloud(last_surf, n_lsf);
+  KdTree kc, ks;
+  kc.Build(lc); ks.Build(ls);
+  for (size_t i = 0; i < n_sharp + n_flat; ++i) {
+    const bool corner = i < n_sharp;
+    const float *q = corner ? sharp + 4 * i : flat + 4 * (i - n_sharp);
+    const P4 pi{q[0], q[1], q[2], q[3]};
+    P4 sel = pi;
+    int closest = -1, second = -1, third = -1;
+    const bool xyz_ok = std::isfinite(pi.x) && std::isfinite(pi.y) && std::isfinite(pi.z);
+    // the intensity enters through the time ratio s alone: s = 0 with no_deskew whatever it is; else NaN gives a NaN sel, and an
+    // infinite one a ratio outside [0, 1.001], which passes through unchanged
+    P4 pin = pi;
+    if (no_deskew && !std::isfinite(pin.i)) pin.i = 0.f;
+    if (std::isfinite(pin.i)) od.TransformToStart(pin, sel);
+    else if (std::isnan(pin.i)) sel.x = sel.y = sel.z = std::numeric_limits<float>::quiet_NaN();
+    if (xyz_ok && std::isfinite(sel.x) && std::isfinite(sel.y) && std::isfinite(sel.z)) {
+      if (corner) PointOdometry::CornerCorrespondence(kc, lc, sel, closest, second);
+      else PointOdometry::SurfCorrespondence(ks, ls, sel, closest, second, third);
+    }
+    sel_out[3 * i] = sel.x; sel_out[3 * i + 1] = sel.y; sel_out[3 * i + 2] = sel.z;
+    if (corner) { corner_idx[2 * i] = closest; corner_idx[2 * i + 1] = second; }
+    else { const size_t k = i - n_sharp; surf_idx[3 * k] = closest; surf_idx[3 * k + 1] = second; surf_idx[3 * k + 2] = third; }
+  }
+  return LIO_OK;
+}
 int lio_calculate_features(const float *map, size_t n_map, const float *stack, size_t m, const lio_transform_f *T, float mm, float mp,
                            uint8_t *valid, float *coeff, float *score) {
   if ((!map && n_map) || (!stack && m) || !T || !valid || !coeff || !score) return LIO_ERR_ARG;

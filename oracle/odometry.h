@@ -65,6 +65,55 @@ struct PointOdometry {
     return dx * dx + dy * dy + dz * dz;
   }
 
+  // The two correspondence searches of an iteration with iter % 5 == 0, on the de-skewed query `sel` against the previous sweep's cloud
+  // `last` (kd built over it).  Shared by Process and the test hook lio_odom_correspondences (include/lio_test_hooks.h).
+  // :342-385 — closest by exact 1-NN inside the 25 m^2 gate, then the nearest point of ANOTHER ring within +-2.5 rings: upward in
+  // index until the first ring above the window, downward until the first below; first strictly smaller distance wins.
+  static void CornerCorrespondence(const KdTree &kd, const Cloud &last, const P4 &sel, int &closest, int &second) {
+    const int n = int(last.size());
+    int idx; float sq;
+    closest = -1; second = -1;
+    if (kd.Search(sel, 1, &idx, &sq) == 1 && sq < 25) {
+      closest = idx;
+      int cs = int(last[closest].i);
+      float d2, best = 25;
+      for (int j = closest + 1; j < n; ++j) {
+        if (int(last[j].i) > cs + 2.5) break;
+        d2 = SqDiff(last[j], sel);
+        if (int(last[j].i) > cs && d2 < best) { best = d2; second = j; }
+      }
+      for (int j = closest - 1; j >= 0; --j) {
+        if (int(last[j].i) < cs - 2.5) break;
+        d2 = SqDiff(last[j], sel);
+        if (int(last[j].i) < cs && d2 < best) { best = d2; second = j; }
+      }
+    }
+  }
+  // :440-494 — closest as above; second from the ring of closest or the side walked (<= cs upward, >= cs downward), third from the
+  // other rings of the window.
+  static void SurfCorrespondence(const KdTree &kd, const Cloud &last, const P4 &sel, int &closest, int &second, int &third) {
+    const int n = int(last.size());
+    int idx; float sq;
+    closest = -1; second = -1; third = -1;
+    if (kd.Search(sel, 1, &idx, &sq) == 1 && sq < 25) {
+      closest = idx;
+      int cs = int(last[closest].i);
+      float d2, b2 = 25, b3 = 25;
+      for (int j = closest + 1; j < n; ++j) {
+        if (int(last[j].i) > cs + 2.5) break;
+        d2 = SqDiff(last[j], sel);
+        if (int(last[j].i) <= cs) { if (d2 < b2) { b2 = d2; second = j; } }
+        else { if (d2 < b3) { b3 = d2; third = j; } }
+      }
+      for (int j = closest - 1; j >= 0; --j) {
+        if (int(last[j].i) < cs - 2.5) break;
+        d2 = SqDiff(last[j], sel);
+        if (int(last[j].i) >= cs) { if (d2 < b2) { b2 = d2; second = j; } }
+        else { if (d2 < b3) { b3 = d2; third = j; } }
+      }
+    }
+  }
+
   void Process(const Cloud &sharp, Cloud less_sharp, const Cloud &flat, Cloud less_flat) {
     iterations_done_ = 0; last_num_sel_ = 0; last_kz_ = 0; es_trace_.clear();
     if (!system_inited_) {
@@ -89,23 +138,8 @@ struct PointOdometry {
           for (size_t i = 0; i < nc; ++i) {
             TransformToStart(sharp[i], sel);
             if (iter % 5 == 0) {
-              int idx; float sq;
-              int closest = -1, second = -1;
-              if (kd_corner_.Search(sel, 1, &idx, &sq) == 1 && sq < 25) {
-                closest = idx;
-                int cs = int(last_corner_[closest].i);
-                float d2, best = 25;
-                for (int j = closest + 1; j < int(last_corner_size); ++j) {
-                  if (int(last_corner_[j].i) > cs + 2.5) break;
-                  d2 = SqDiff(last_corner_[j], sel);
-                  if (int(last_corner_[j].i) > cs && d2 < best) { best = d2; second = j; }
-                }
-                for (int j = closest - 1; j >= 0; --j) {
-                  if (int(last_corner_[j].i) < cs - 2.5) break;
-                  d2 = SqDiff(last_corner_[j], sel);
-                  if (int(last_corner_[j].i) < cs && d2 < best) { best = d2; second = j; }
-                }
-              }
+              int closest, second;
+              CornerCorrespondence(kd_corner_, last_corner_, sel, closest, second);
               ic1[i] = closest; ic2[i] = second;
             }
             if (ic2[i] >= 0) {
@@ -127,25 +161,8 @@ struct PointOdometry {
           for (size_t i = 0; i < ns; ++i) {
             TransformToStart(flat[i], sel);
             if (iter % 5 == 0) {
-              int idx; float sq;
-              int closest = -1, second = -1, third = -1;
-              if (kd_surf_.Search(sel, 1, &idx, &sq) == 1 && sq < 25) {
-                closest = idx;
-                int cs = int(last_surf_[closest].i);
-                float d2, b2 = 25, b3 = 25;
-                for (int j = closest + 1; j < int(last_surf_size); ++j) {
-                  if (int(last_surf_[j].i) > cs + 2.5) break;
-                  d2 = SqDiff(last_surf_[j], sel);
-                  if (int(last_surf_[j].i) <= cs) { if (d2 < b2) { b2 = d2; second = j; } }
-                  else { if (d2 < b3) { b3 = d2; third = j; } }
-                }
-                for (int j = closest - 1; j >= 0; --j) {
-                  if (int(last_surf_[j].i) < cs - 2.5) break;
-                  d2 = SqDiff(last_surf_[j], sel);
-                  if (int(last_surf_[j].i) >= cs) { if (d2 < b2) { b2 = d2; second = j; } }
-                  else { if (d2 < b3) { b3 = d2; third = j; } }
-                }
-              }
+              int closest, second, third;
+              SurfCorrespondence(kd_surf_, last_surf_, sel, closest, second, third);
               is1[i] = closest; is2[i] = second; is3[i] = third;
             }
             if (is2[i] >= 0 && is3[i] >= 0) {

@@ -78,7 +78,7 @@ def _declared_test_hooks():
 def test_each_test_hook_is_bound_and_exported_by_both_libraries(oracle):
     """include/lio_test_hooks.h: every hook bound in Python and exported by the product and the oracle"""
     hooks = _declared_test_hooks()
-    assert len(hooks) >= 5 and "lio_knn_walk" in hooks and "lio_fit_five" in hooks
+    assert len(hooks) >= 6 and "lio_knn_walk" in hooks and "lio_fit_five" in hooks and "lio_odom_correspondences" in hooks
     assert set(hooks) == set(capi._TEST_SIGS.keys())
     assert not set(hooks) & set(_declared_symbols())
     dll = ctypes.CDLL(capi.HIP_LIB_PATH)
@@ -115,6 +115,18 @@ def test_test_hook_header_is_plain_c_and_links(tmp_path, oracle, lib):
                    "    if (lio_knn_walk(map, 2, q, 1, 0.0f, 8, idx, sqd, nbr) != LIO_ERR_ARG) return 12;\n"
                    "    if (lio_knn_walk(map, 2, q, 1, -1.0f, 8, idx, sqd, nbr) != LIO_ERR_ARG) return 13;\n"
                    "    if (idx[0] != 7 || sqd[4] != 7) return 14;   /* refused before anything is written */\n"
+                   "  }\n"
+                   "  {\n"
+                   "    float q[4] = {0, 0, 0, 0}, prev[8] = {0, 0, 0, 0, 1, 1, 1, 1}, sel[6] = {7, 7, 7, 7, 7, 7};\n"
+                   "    int32_t ci[2] = {7, 7}, si[3] = {7, 7, 7};\n"
+                   "    lio_transform_f T = {{0, 0, 0, 1}, {0, 0, 0}};\n"
+                   "    if (lio_odom_correspondences(NULL, 1, q, 1, prev, 2, prev, 2, &T, 0.1f, 0, ci, si, sel) != LIO_ERR_ARG) return 15;\n"
+                   "    if (lio_odom_correspondences(q, 1, q, 1, prev, 2, NULL, 2, &T, 0.1f, 0, ci, si, sel) != LIO_ERR_ARG) return 16;\n"
+                   "    if (lio_odom_correspondences(q, 1, q, 1, prev, 2, prev, 2, NULL, 0.1f, 0, ci, si, sel) != LIO_ERR_ARG) return 17;\n"
+                   "    if (lio_odom_correspondences(q, 1, q, 1, prev, 2, prev, 2, &T, 0.0f, 0, ci, si, sel) != LIO_ERR_ARG) return 18;\n"
+                   "    if (lio_odom_correspondences(q, 1, q, 1, prev, 2, prev, 2, &T, 0.1f, 0, NULL, si, sel) != LIO_ERR_ARG) return 19;\n"
+                   "    if (lio_odom_correspondences(q, 1, q, 1, prev, 2, prev, 2, &T, 0.1f, 0, ci, si, NULL) != LIO_ERR_ARG) return 20;\n"
+                   "    if (ci[0] != 7 || si[2] != 7 || sel[5] != 7) return 21;\n"
                    "  }\n"
                    '  puts("hooks ok");\n  return 0;\n}\n')
     exe = tmp_path / "hooks"

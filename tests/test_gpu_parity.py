@@ -541,8 +541,9 @@ def test_full_size_hdl64_window(hip, oracle):
 # ------------------------------------------------------------------------------------------------ scan-to-scan odometry
 @pytest.mark.parametrize("kind,n_sweeps", [("indoor", 4), ("outdoor", 3)])
 def test_point_odometry_matches_oracle(hip, oracle, kind, n_sweeps):
-    """BASELINE.json configs[1]: LOAM scan-to-scan step on motion-distorted sweeps.  Correspondence indices come out
-    of exact searches (bit-exact), coefficients use the CPU operation order; only the 6x6 normal-equation sums differ
+    """BASELINE.json configs[1]: LOAM scan-to-scan step on motion-distorted sweeps.  The correspondence indices come out
+    of exact searches; THIS test does not look at them — tests/test_gpu_odom_corr.py holds them, index by index, to the serial
+    references of tests/odom_corr_ref.py.  Coefficients use the CPU operation order; only the 6x6 normal-equation sums differ
     in summation order => transform_es_ within 1e-5, TransformToEnd clouds within 1e-4."""
     sweeps, pose_fn, lid = synth.make_sweeps(kind, n_sweeps)
     oa, ob = capi.PointOdometry(hip, 0.1, 2, 25, False), capi.PointOdometry(oracle, 0.1, 2, 25, False)
