@@ -76,7 +76,15 @@ lio_pp *lio_pp_create(float lower_deg, float upper_deg, int rings, const lio_pp_
  * PointProcessor.cc:685-732, accepts any quota; its defaults are 20 + 4).  The oracle has no such limit.  No device work. */
 int lio_pp_check_config(float lower_deg, float upper_deg, int rings, const lio_pp_config *config_or_null);
 void lio_pp_destroy(lio_pp *);
-/* SetInputCloud + PointToRing + ExtractFeaturePoints (PointProcessor.cc:96-100, test_point_processor.cc:103-106) */
+/* SetInputCloud + PointToRing + ExtractFeaturePoints (PointProcessor.cc:96-100, test_point_processor.cc:103-106).
+ * Two capacities of the product's per-ring kernels (a ring and its sort keys live in LDS); the reference and the oracle have neither:
+ *   - a ring keeps at most 4080 points (LIO_PP_MAX_RING_POINTS);
+ *   - a subregion of a ring of n kept points, the reference's own [sp, ep] of PointProcessor.cc:672-675 — about
+ *     (n - 2 num_curvature_regions) / num_scan_subregions points —, holds at most 512 (num_scan_subregions = 4 reaches that at
+ *     about 2060 points per ring).
+ * A sweep beyond either returns LIO_ERR_CAPACITY from lio_pp_process, lio_pp_process_rings, lio_pp_wait and the batch calls (the
+ * message on stderr names the limit, the ring and its size).  Nothing is served of such a call: every count of the handles involved —
+ * all handles of a batch that shared the launch chain — reads 0 until their next process call, which starts afresh. */
 int lio_pp_process(lio_pp *, const float *xyzi, size_t n);
 /* lio_pp_process in two halves, for hosts that keep several sweeps in flight (one handle per sweep in flight, each with its
  * own stream): _async enqueues upload + all kernels + the copy of the counts and returns; _wait blocks until they are done.

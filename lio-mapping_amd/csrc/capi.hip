@@ -64,6 +64,10 @@ template <typename F> static int guarded(F &&f) {
     std::snprintf(g_last_error, sizeof(g_last_error), "%s", e.what());
     std::fprintf(stderr, "[lio_hip] %s\n", e.what());
     return LIO_ERR_DEVICE;
+  } catch (const CapacityError &e) {
+    std::snprintf(g_last_error, sizeof(g_last_error), "%s", e.what());
+    std::fprintf(stderr, "[lio_hip] %s\n", e.what());
+    return LIO_ERR_CAPACITY;
   } catch (const std::exception &e) {
     std::snprintf(g_last_error, sizeof(g_last_error), "%s", e.what());
     std::fprintf(stderr, "[lio_hip] %s\n", e.what());

@@ -34,6 +34,10 @@ __device__ __forceinline__ U *rebase(T *base, U *p) {
 struct DeviceError : std::runtime_error {
   using std::runtime_error::runtime_error;
 };
+// a fixed capacity of the device path was exceeded by the data (LIO_ERR_CAPACITY at the C-ABI)
+struct CapacityError : std::runtime_error {
+  using std::runtime_error::runtime_error;
+};
 
 #define LIO_HIP(call)                                                                                         \
   do {                                                                                                        \

@@ -13,6 +13,7 @@
 
 #define LIO_PP_MAX_RINGS 128
 #define LIO_PP_MAX_RING_POINTS 4080   // 8 subregions of <= 512 sort slots each, ring resident in LDS
+#define LIO_PP_MAX_SUBREGION_POINTS 512   // sort slots of one wave of k_ring_pick (PP_SORT_SLOTS)
 
 namespace lio {
 
@@ -20,7 +21,7 @@ struct PPDeviceCounts {
   int n_ring_points;     // points kept by ring binning
   int n_less_flat;       // voxel-filtered less-flat points
   int n_class[4];        // [1] sharp, [2] less_sharp, [3] flat
-  int overflow;          // a ring exceeded LIO_PP_MAX_RING_POINTS
+  int overflow;          // a ring exceeded LIO_PP_MAX_RING_POINTS or a subregion LIO_PP_MAX_SUBREGION_POINTS: the sweep has no results
   int pad;
   long long pick_stamps[8];   // LIO_DEBUG_TIMING: wall-clock ticks of ring 0's block at the phase boundaries of k_ring_pick
 };
@@ -87,6 +88,7 @@ class PointProcessorDev {
   // sweeps of the last launch; the sweep the accessors read; elements per sweep of the point-indexed arrays, of one packed class list
   int nsw_ = 0, sel_ = 0;
   bool last_empty_ = false;            // the last launch had no point at all: nothing ran, every count reads zero
+  bool over_capacity_ = false;         // the last launch hit a capacity limit: no sweep of it has results, every count reads zero
   std::vector<size_t> n_sw_;           // input points of the last launch's sweeps
   size_t pts_stride_ = 0, cls_stride_ = 0;
   int state_stride_ = 0;   // ints per sweep of the state record: PPDeviceCounts | ring offsets [LIO_PP_MAX_RINGS + 1] | first_valid [2] | end_ori | pad

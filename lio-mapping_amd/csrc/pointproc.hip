@@ -21,7 +21,7 @@
 namespace lio {
 
 #define PP_PICK_THREADS 512
-#define PP_SORT_SLOTS 512
+#define PP_SORT_SLOTS LIO_PP_MAX_SUBREGION_POINTS
 #define PP_WMASK 576     // bytes of a private subregion mask: PP_SORT_SLOTS + 2 x nc (nc <= 15), rounded up to a multiple of 64
 #define PP_STAMP_RING 20   // the ring whose block stamps its phases (an HDL-64 ring that looks at the scene, not the sky)
 #define PP_WSEL 64       // ints per wave for its speculative picks: max_corner_less_sharp + max_surf_flat <= 64
@@ -857,6 +857,7 @@ void PointProcessorDev::ProcessLaunchBatch(const float *const *xyzi, const uint1
   for (int k = 0; k < B; ++k) n_max = std::max(n_max, n[k]);
   // nothing to do: every count reads zero; the start azimuth stays the last sweep's, as the reference's member does (PointProcessor.cc:261-264)
   last_empty_ = (B <= 0 || n_max == 0);
+  over_capacity_ = false;
   if (last_empty_) return;
   bool any_ring = false;
   for (int k = 0; k < B; ++k) any_ring = any_ring || (ring && ring[k] && n[k]);
@@ -1002,13 +1003,40 @@ void PointProcessorDev::ProcessFinish() {
     std::fprintf(stderr, "[lio_hip pp timing] k_ring_pick ring %d, 10 ns ticks: load %lld, PrepareRing+reach %lld, curvature+keys %lld, sort %lld, picks %lld, lists + mask merge %lld, write-back %lld\n",
                  PP_STAMP_RING, st[1] - st[0], st[2] - st[1], st[3] - st[2], st[4] - st[3], st[5] - st[4], st[6] - st[5], st[7] - st[6]);
   }
+  // a ring or a subregion beyond what k_ring_pick holds: the kernels flagged the sweep and left it unfinished.  Nothing of this launch
+  // is served (every count reads zero until the next launch), and the message says which limit it was, from the ring lengths
   for (int k = 0; k < nsw_; ++k)
-    if (reinterpret_cast<const PPDeviceCounts *>(h_record(k))->overflow) { SelectSweep(0); throw std::runtime_error("PointProcessor: a ring exceeds LIO_PP_MAX_RING_POINTS"); }
+    if (reinterpret_cast<const PPDeviceCounts *>(h_record(k))->overflow) {
+      over_capacity_ = true;
+      const int *off = h_record(k) + kCountInts;
+      const int nc = cfg_.num_curvature_regions, ns = cfg_.num_scan_subregions;
+      char msg[256];
+      std::snprintf(msg, sizeof(msg), "PointProcessor: sweep %d exceeds a capacity of the pick kernel", k);
+      for (int r = 0; r < rings_; ++r) {
+        const long long n = off[r + 1] - off[r];
+        if (n > LIO_PP_MAX_RING_POINTS) {
+          std::snprintf(msg, sizeof(msg), "PointProcessor: ring %d of sweep %d has %lld points, more than LIO_PP_MAX_RING_POINTS = %d", r, k, n, LIO_PP_MAX_RING_POINTS);
+          break;
+        }
+        long long widest = 0;
+        for (int j = 0; j < ns && n > 2 * nc + 1; ++j) {   // PointProcessor.cc:672-675
+          const long long sp = (nc * (ns - j) + (n - nc) * j) / ns, ep = (nc * (ns - 1 - j) + (n - nc) * (j + 1)) / ns - 1;
+          widest = std::max(widest, ep - sp + 1);
+        }
+        if (widest > LIO_PP_MAX_SUBREGION_POINTS) {
+          std::snprintf(msg, sizeof(msg), "PointProcessor: ring %d of sweep %d (%lld points, %d subregions) has a subregion of %lld points, more than "
+                        "LIO_PP_MAX_SUBREGION_POINTS = %d", r, k, n, ns, widest, LIO_PP_MAX_SUBREGION_POINTS);
+          break;
+        }
+      }
+      SelectSweep(0);
+      throw CapacityError(msg);
+    }
   SelectSweep(0);
 }
 
 void PointProcessorDev::SelectSweep(int k) {
-  if (last_empty_) {   // (a batch of empty sweeps launched nothing)
+  if (last_empty_ || over_capacity_) {   // (a batch of empty sweeps launched nothing; one over a capacity limit finished nothing)
     std::memset(&counts_, 0, sizeof(counts_));
     std::fill(ring_offsets_.begin(), ring_offsets_.end(), 0);
     return;
