@@ -9,6 +9,7 @@
 #include "../../include/lio_test_hooks.h"
 #include "../../include/lio_ext.h"
 #include "../../include/lio_full_cloud.h"
+#include "../../include/lio_odom_batch.h"
 #include "est_batch.h"
 #include "seg_sort.h"
 #include "estimator.h"
@@ -18,6 +19,7 @@
 #include <mutex>
 #include <thread>
 #include <atomic>
+#include <algorithm>
 
 #include "mapping.h"
 #include "odometry.h"
@@ -280,6 +282,31 @@ int lio_odom_process(lio_odom *h, const float *sharp, size_t n_sharp, const floa
     if (iters) *iters = h->o->iterations_done_;
     if (nsel) *nsel = h->o->last_num_sel_;
     return LIO_OK;
+  });
+}
+// include/lio_odom_batch.h.  Every check comes before any device work and before any handle changes.
+int lio_odom_process_batch(lio_odom *const *handles, int n_sensors, const float *const *sharp, const size_t *n_sharp, const float *const *less_sharp,
+                           const size_t *n_ls, const float *const *flat, const size_t *n_flat, const float *const *less_flat, const size_t *n_lf,
+                           lio_transform_f *Tsum, lio_transform_f *Tes, int32_t *iters, int32_t *nsel) {
+  if (!handles || n_sensors < 1 || !sharp || !n_sharp || !less_sharp || !n_ls || !flat || !n_flat || !less_flat || !n_lf) return LIO_ERR_ARG;
+  if (n_sensors > LIO_ODOM_BATCH_MAX_SENSORS) return LIO_ERR_CAPACITY;
+  for (int k = 0; k < n_sensors; ++k)
+    if (!handles[k] || (!sharp[k] && n_sharp[k]) || (!less_sharp[k] && n_ls[k]) || (!flat[k] && n_flat[k]) || (!less_flat[k] && n_lf[k])) return LIO_ERR_ARG;
+  return guarded([&] {
+    std::vector<OdometryDev *> o;
+    for (int k = 0; k < n_sensors; ++k) o.push_back(handles[k]->o.get());
+    std::vector<OdometryDev *> sorted = o;
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return int(LIO_ERR_ARG);   // the same handle twice
+    OdometryDev::ProcessBatch(o.data(), n_sensors, sharp, n_sharp, less_sharp, n_ls, flat, n_flat, less_flat, n_lf);
+    for (int k = 0; k < n_sensors; ++k) {
+      const OdometryDev &d = *o[size_t(k)];
+      if (Tsum) fromT(d.transform_sum_, &Tsum[k]);
+      if (Tes) fromT(d.transform_es_, &Tes[k]);
+      if (iters) iters[k] = d.iterations_done_;
+      if (nsel) nsel[k] = d.last_num_sel_;
+    }
+    return int(LIO_OK);
   });
 }
 int lio_odom_get_iteration_trace(const lio_odom *h, lio_transform_f *trace, int capacity, int *kz) {

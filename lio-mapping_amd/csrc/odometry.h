@@ -1,12 +1,15 @@
 // odometry.h — PointOdometry (LOAM scan-to-scan step) on the GPU.
 // Reference: src/point_processor/PointOdometry.cc:237-292 (TransformToStart/End), :294-683 (Process).
 #pragma once
+#include <memory>
+
 #include "cloud_kernels.h"
 #include "hmath.h"
 
 namespace lio {
 
 struct OdoArgs;
+struct OdoBatchScratch;
 
 class OdometryDev {
  public:
@@ -14,6 +17,11 @@ class OdometryDev {
   ~OdometryDev();
   void Process(const float *sharp, size_t n_sharp, const float *less_sharp, size_t n_ls, const float *flat, size_t n_flat, const float *less_flat,
                size_t n_lf);
+  // Process for n independent sensors, one sweep each, through one launch chain on o[0]'s stream (lio_odom_process_batch,
+  // include/lio_odom_batch.h): array k of every argument belongs to o[k]; every sensor ends in the state Process alone leaves, bit for
+  // bit.  The chain's scratch stays with o[0].  Sensors whose max_iter differ are processed one after the other.
+  static void ProcessBatch(OdometryDev *const *o, int n, const float *const *sharp, const size_t *n_sharp, const float *const *less_sharp,
+                           const size_t *n_ls, const float *const *flat, const size_t *n_flat, const float *const *less_flat, const size_t *n_lf);
   size_t GetLastCloud(int which, float *out);
   // TransformToEnd(full_cloud_) with the last Process's transform_es_ (:725-730); a byte copy while the odometry is disabled
   void FullToEnd(const float *xyzi, size_t n, float *out);
@@ -42,6 +50,8 @@ class OdometryDev {
   DBuf<float> d_trace_;        // 8 floats per iteration, written by k_odo_update
   std::vector<float> h_trace_;
   void BuildGrids();
+  void Accumulate(const OdomState &st);   // the host's end of a step that ran with the odometry enabled (:654-663)
+  std::unique_ptr<OdoBatchScratch> batch_;   // ProcessBatch with this handle first: argument table, partials, indices, traces, mailbox
   OdoArgs Args(size_t n_sharp, size_t n_flat) const;
   DBuf<float> d_sel_;          // 3 floats per query (Correspondences)
   KnnGrid grid_c_, grid_s_;

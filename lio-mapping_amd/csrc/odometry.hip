@@ -60,9 +60,11 @@ __device__ inline void wave_argmin(float &d, int &key) {
   }
 }
 
-__global__ void __launch_bounds__(64) k_odo_corr(OdoArgs a, const OdomState *__restrict__ st, int *__restrict__ idx) {
+// The device bodies below are stated once: the k_odo_* kernels run them for one sensor, the k_ob_* kernels for the sensors of a batch
+// (lio_odom_process_batch), each sensor with its own arguments, state and slices, so that a sensor computes the same bits either way.
+// query qi of one sensor by one wavefront (lane = 0 .. 63)
+__device__ __forceinline__ void odo_corr_body(const OdoArgs &a, const OdomState *__restrict__ st, int *__restrict__ idx, const int qi, const int lane) {
   if (st->converged) return;
-  const int qi = blockIdx.x, lane = threadIdx.x;
   const bool corner = qi < a.nc;
   const float4 pi = corner ? a.sharp[qi] : a.flat[qi - a.nc];
   const float4 *cloud = corner ? a.lastc : a.lasts;
@@ -180,6 +182,10 @@ __global__ void __launch_bounds__(64) k_odo_corr(OdoArgs a, const OdomState *__r
   }
 }
 
+__global__ void __launch_bounds__(64) k_odo_corr(OdoArgs a, const OdomState *__restrict__ st, int *__restrict__ idx) {
+  odo_corr_body(a, st, idx, blockIdx.x, threadIdx.x);
+}
+
 // The one statement of the correspondence launch: Process (every fifth iteration) and the test hook lio_odom_correspondences
 static void launch_odo_corr(const OdoArgs &a, const OdomState *st, int *idx, hipStream_t s) {
   const int nq = a.nc + a.ns;
@@ -200,8 +206,9 @@ __global__ void __launch_bounds__(256) k_odo_sel(OdoArgs a, const OdomState *__r
 
 #define ODO_ROW_THREADS 256
 
-__global__ void __launch_bounds__(ODO_ROW_THREADS) k_odo_rows(OdoArgs a, const OdomState *__restrict__ st, const int *__restrict__ idx, int iter,
-                                                              double *__restrict__ partials) {
+// block `block` of the `nblocks` (ODO_ROW_THREADS threads each) that share one sensor's queries; 28 doubles to partials[block * 28 ...]
+__device__ __forceinline__ void odo_rows_body(const OdoArgs &a, const OdomState *__restrict__ st, const int *__restrict__ idx, int iter,
+                                              double *__restrict__ partials, const int block, const int nblocks) {
   if (st->converged) return;
   Quat<float> qe(st->T[3], st->T[0], st->T[1], st->T[2]);
   Vec3<float> te(st->T[4], st->T[5], st->T[6]);
@@ -210,7 +217,7 @@ __global__ void __launch_bounds__(ODO_ROW_THREADS) k_odo_rows(OdoArgs a, const O
 #pragma unroll
   for (int k = 0; k < 28; ++k) acc[k] = 0;
   const int total = a.nc + a.ns;
-  for (int qi = blockIdx.x * blockDim.x + threadIdx.x; qi < total; qi += gridDim.x * blockDim.x) {
+  for (int qi = block * ODO_ROW_THREADS + threadIdx.x; qi < total; qi += nblocks * ODO_ROW_THREADS) {
     const bool corner = qi < a.nc;
     const float4 pi = corner ? a.sharp[qi] : a.flat[qi - a.nc];
     Vec3<float> sel;
@@ -285,16 +292,21 @@ __global__ void __launch_bounds__(ODO_ROW_THREADS) k_odo_rows(OdoArgs a, const O
   if (threadIdx.x < 28) {
     double v = 0;
     for (int w = 0; w < ODO_ROW_THREADS / 64; ++w) v += sm[w][threadIdx.x];
-    partials[blockIdx.x * 28 + threadIdx.x] = v;
+    partials[block * 28 + threadIdx.x] = v;
   }
+}
+__global__ void __launch_bounds__(ODO_ROW_THREADS) k_odo_rows(OdoArgs a, const OdomState *__restrict__ st, const int *__restrict__ idx, int iter,
+                                                              double *__restrict__ partials) {
+  odo_rows_body(a, st, idx, iter, partials, blockIdx.x, gridDim.x);
 }
 
 // the serial 6x6 step of one iteration (thread 0); see k_odo_update
 __device__ __forceinline__ void odo_update_step(const double *ssum, OdomState *st, int iter);
 // mail / sig: at the iterations where the host looks at the convergence flag (every fifth) the state is posted to its mailbox
 // (dev.h: HostSignal) instead of being fetched with a copy + stream synchronisation
-__global__ void k_odo_update(const double *__restrict__ partials, int nblocks, OdomState *st, int iter, OdomState *mail, HostSignal sig,
-                             float *__restrict__ trace) {
+// one 256-thread block
+__device__ __forceinline__ void odo_update_body(const double *__restrict__ partials, int nblocks, OdomState *st, int iter, OdomState *mail,
+                                                const HostSignal &sig, float *__restrict__ trace) {
   if (!st->converged) {
     __shared__ double ssum[28];
     reduce_partials28(partials, nblocks, ssum);
@@ -308,6 +320,10 @@ __global__ void k_odo_update(const double *__restrict__ partials, int nblocks, O
     __syncthreads();
     if (threadIdx.x < 64) post_host_mail(sig, mail, st, int(sizeof(OdomState) / 4), threadIdx.x);
   }
+}
+__global__ void k_odo_update(const double *__restrict__ partials, int nblocks, OdomState *st, int iter, OdomState *mail, HostSignal sig,
+                             float *__restrict__ trace) {
+  odo_update_body(partials, nblocks, st, iter, mail, sig, trace);
 }
 __device__ __forceinline__ void odo_update_step(const double *ssum, OdomState *st, int iter) {
   double sum[28];
@@ -351,9 +367,8 @@ __device__ __forceinline__ void odo_update_step(const double *ssum, OdomState *s
 }
 
 // TransformToEnd (:261-292) with the transform_es_ the iterations left on the device; out == in: in place
-__global__ void __launch_bounds__(256) k_odo_to_end(const float4 *in, float4 *out, int n, const OdomState *__restrict__ st, float time_factor, int no_deskew) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+__device__ __forceinline__ void odo_to_end_body(const float4 *in, float4 *out, const int i, const OdomState *__restrict__ st, float time_factor,
+                                                int no_deskew) {
   Quat<float> qe(st->T[3], st->T[0], st->T[1], st->T[2]);
   Vec3<float> te(st->T[4], st->T[5], st->T[6]);
   float4 p = in[i];
@@ -362,6 +377,75 @@ __global__ void __launch_bounds__(256) k_odo_to_end(const float4 *in, float4 *ou
   p.w = float(int(p.w));
   out[i] = to_end_point<false>(p, s, qe, te);
 }
+__global__ void __launch_bounds__(256) k_odo_to_end(const float4 *in, float4 *out, int n, const OdomState *__restrict__ st, float time_factor, int no_deskew) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  odo_to_end_body(in, out, i, st, time_factor, no_deskew);
+}
+
+// ---- the batch (lio_odom_process_batch): the same bodies, every sensor with its own record of a device table
+// One sensor of a batch.  Iterating sensors come first in the table (the k_ob_corr / k_ob_rows / k_ob_update launches cover only them);
+// behind them those that only carry their clouds to the sweep's end (previous clouds too small to iterate: `a` holds time_factor and
+// no_deskew alone).
+struct OdoBatchRec {
+  OdoArgs a;
+  OdomState *st;              // the handle's own state
+  float4 *ls; int n_ls;       // its less-sharp / less-flat clouds of this sweep (k_ob_to_end, in place)
+  float4 *lf; int n_lf;
+  int idx_off;                // first of its 2 * nc + 3 * ns entries in the batch's index table
+  int nb;                     // its row blocks: max(1, min(cdiv(nq, ODO_ROW_THREADS), 64)), the partition it has alone
+  int part_off;               // its first row (28 doubles each) of the batch's partials
+  int trace_off;              // its first float of the batch's trace table (8 per iteration)
+};
+#define ODO_MAIL_STRIDE 64    // bytes per sensor in the batch's mailbox
+
+// grid (max nq, sensors) x 64: one wavefront per query; the blocks beyond a sensor's own queries leave at once
+__global__ void __launch_bounds__(64) k_ob_corr(const OdoBatchRec *__restrict__ recs, int *__restrict__ idx_all) {
+  const OdoBatchRec &r = recs[blockIdx.y];
+  if (int(blockIdx.x) >= r.a.nc + r.a.ns) return;
+  odo_corr_body(r.a, r.st, idx_all + r.idx_off, blockIdx.x, threadIdx.x);
+}
+// grid (max nb, sensors): sensor k is served by its first nb_k blocks with the stride nb_k * ODO_ROW_THREADS — its partition alone, NOT the
+// grid's width: the order in which a thread adds its rows, and so every bit of the sums, hangs on it
+__global__ void __launch_bounds__(ODO_ROW_THREADS) k_ob_rows(const OdoBatchRec *__restrict__ recs, const int *__restrict__ idx_all, int iter,
+                                                             double *__restrict__ partials_all) {
+  const OdoBatchRec &r = recs[blockIdx.y];
+  if (int(blockIdx.x) >= r.nb) return;
+  odo_rows_body(r.a, r.st, idx_all + r.idx_off, iter, partials_all + size_t(r.part_off) * 28, blockIdx.x, r.nb);
+}
+// one 256-thread block per sensor; at the iterations the host looks at, every sensor (a converged one too) posts its state to its own
+// mailbox slot and then stores sig.seq into its own completion word
+__global__ void k_ob_update(const OdoBatchRec *__restrict__ recs, const double *__restrict__ partials_all, int iter, char *mail, HostSignal sig,
+                            float *__restrict__ trace_all) {
+  const OdoBatchRec &r = recs[blockIdx.x];
+  HostSignal mine = sig;
+  if (sig.flag) mine.flag = sig.flag + blockIdx.x;
+  odo_update_body(partials_all + size_t(r.part_off) * 28, r.nb, r.st, iter, reinterpret_cast<OdomState *>(mail + size_t(blockIdx.x) * ODO_MAIL_STRIDE), mine,
+                  trace_all + r.trace_off);
+}
+// grid (cdiv(max(n_ls + n_lf), 256), sensors): the less-sharp points of a sensor, then its less-flat points, each in place
+__global__ void __launch_bounds__(256) k_ob_to_end(const OdoBatchRec *__restrict__ recs) {
+  const OdoBatchRec &r = recs[blockIdx.y];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= r.n_ls + r.n_lf) return;
+  float4 *c = i < r.n_ls ? r.ls : r.lf;
+  odo_to_end_body(c, c, i < r.n_ls ? i : i - r.n_ls, r.st, r.a.time_factor, r.a.no_deskew);
+}
+
+// The chain's scratch, kept by the first handle of a batch.  No results live here: the states, clouds and grids are the handles' own.
+struct OdoBatchScratch {
+  std::vector<OdoBatchRec> h_recs;
+  DBuf<OdoBatchRec> d_recs;
+  DBuf<int> d_idx;
+  DBuf<double> d_partials;
+  DBuf<float> d_trace;
+  std::vector<float> h_trace;
+  DBuf<VoxParams> d_bounds;
+  HostBuf<VoxParams> h_bounds;
+  HostBuf<char> h_mail;       // pinned, coherent: mail_cap states of ODO_MAIL_STRIDE bytes, then mail_cap completion words
+  size_t mail_cap = 0;
+  unsigned seq = 0;
+};
 
 // ------------------------------------------------------------------------------------------------
 OdometryDev::OdometryDev(float scan_period, int io_ratio, int max_iter, bool no_deskew)
@@ -403,6 +487,18 @@ static void upload(DBuf<float4> &b, const float *src, size_t n, hipStream_t s) {
 OdoArgs OdometryDev::Args(size_t n_sharp, size_t n_flat) const {
   return OdoArgs{sharp_.p, int(n_sharp), flat_.p, int(n_flat), last_corner_.p, int(n_last_corner_), last_surf_.p, int(n_last_surf_), time_factor_,
                  no_deskew_ ? 1 : 0, grid_c_.sorted(), grid_c_.cells(), grid_c_.desc(), grid_s_.sorted(), grid_s_.cells(), grid_s_.desc()};
+}
+
+// What the host keeps of the state the iterations ended with: :654-656 accumulate, :663 normalise.  TransformToEnd (:660-661) runs on the
+// device with the state's own, not normalised transform_es_.
+void OdometryDev::Accumulate(const OdomState &st) {
+  iterations_done_ = st.iters;
+  last_kz_ = st.degenerate ? st.kz : 0;
+  last_num_sel_ = int(st.T[7]);
+  transform_es_ = Rigid<float>(Quat<float>(st.T[3], st.T[0], st.T[1], st.T[2]), Vec3<float>(st.T[4], st.T[5], st.T[6]));
+  transform_sum_ = compose(transform_sum_, rinverse(transform_es_));
+  transform_es_.rot = normalized(transform_es_.rot);
+  to_end_ready_ = true;
 }
 
 void OdometryDev::Process(const float *sharp, size_t n_sharp, const float *less_sharp, size_t n_ls, const float *flat, size_t n_flat,
@@ -473,21 +569,174 @@ void OdometryDev::Process(const float *sharp, size_t n_sharp, const float *less_
       LIO_HIP(hipStreamSynchronize(s));
       st = *h_state_;
     }
-    iterations_done_ = st.iters;
-    last_kz_ = st.degenerate ? st.kz : 0;
-    last_num_sel_ = int(st.T[7]);
-    transform_es_ = Rigid<float>(Quat<float>(st.T[3], st.T[0], st.T[1], st.T[2]), Vec3<float>(st.T[4], st.T[5], st.T[6]));
-    // :654-656 accumulate, :660-661 TransformToEnd, :663 normalise
-    transform_sum_ = compose(transform_sum_, rinverse(transform_es_));
+    Accumulate(st);
+    // :660-661 TransformToEnd
     if (n_ls) hipLaunchKernelGGL(k_odo_to_end, dim3(cdiv(n_ls, 256)), dim3(256), 0, s, less_sharp_.p, less_sharp_.p, int(n_ls), d_state_.p, time_factor_, no_deskew_ ? 1 : 0);
     if (n_lf) hipLaunchKernelGGL(k_odo_to_end, dim3(cdiv(n_lf, 256)), dim3(256), 0, s, less_flat_.p, less_flat_.p, int(n_lf), d_state_.p, time_factor_, no_deskew_ ? 1 : 0);
     LIO_HIP(hipGetLastError());
-    transform_es_.rot = normalized(transform_es_.rot);
-    to_end_ready_ = true;
   }
   LIO_HIP(hipStreamSynchronize(s));
   std::swap(last_corner_, less_sharp_); std::swap(last_surf_, less_flat_);
   n_last_corner_ = n_ls; n_last_surf_ = n_lf;
+}
+
+void OdometryDev::ProcessBatch(OdometryDev *const *o, int n, const float *const *sharp, const size_t *n_sharp, const float *const *less_sharp,
+                               const size_t *n_ls, const float *const *flat, const size_t *n_flat, const float *const *less_flat, const size_t *n_lf) {
+  OdometryDev &lead = *o[0];
+  for (int k = 1; k < n; ++k)
+    if (o[k]->max_iter_ != lead.max_iter_) {   // no common iteration count: no common chain
+      for (int j = 0; j < n; ++j) o[j]->Process(sharp[j], n_sharp[j], less_sharp[j], n_ls[j], flat[j], n_flat[j], less_flat[j], n_lf[j]);
+      return;
+    }
+  const int max_iter = lead.max_iter_;
+  hipStream_t s = lead.stream_;   // the other handles are idle: every entry point returns synchronised
+  if (!lead.batch_) lead.batch_.reset(new OdoBatchScratch);
+  OdoBatchScratch &sc = *lead.batch_;
+
+  // ---- uploads, per sensor; who iterates (`act`), who only carries its clouds to the end (`idle`), who only stores them (neither)
+  std::vector<int> act, idle;
+  std::vector<OdomState> st(size_t(n), OdomState{});
+  for (int k = 0; k < n; ++k) {
+    OdometryDev &d = *o[k];
+    d.iterations_done_ = 0; d.last_num_sel_ = 0; d.last_kz_ = 0; d.es_trace_.clear();
+    upload(d.less_sharp_, less_sharp[k], n_ls[k], s);
+    upload(d.less_flat_, less_flat[k], n_lf[k], s);
+    if (!d.inited_ || !d.enable_odom_) continue;   // :302-310; the packer
+    OdomState &t = st[size_t(k)];
+    t.T[0] = d.transform_es_.rot.x; t.T[1] = d.transform_es_.rot.y; t.T[2] = d.transform_es_.rot.z; t.T[3] = d.transform_es_.rot.w;
+    t.T[4] = d.transform_es_.pos.x; t.T[5] = d.transform_es_.pos.y; t.T[6] = d.transform_es_.pos.z;
+    LIO_HIP(hipMemcpyAsync(d.d_state_.p, &t, sizeof(t), hipMemcpyHostToDevice, s));
+    if (d.n_last_corner_ > 10 && d.n_last_surf_ > 100) {
+      upload(d.sharp_, sharp[k], n_sharp[k], s);
+      upload(d.flat_, flat[k], n_flat[k], s);
+      act.push_back(k);
+    } else {
+      idle.push_back(k);
+    }
+  }
+  const int nA = int(act.size()), nE = nA + int(idle.size());
+
+  if (nE) {
+    // ---- the table: offsets first, then (after the grids, whose buffers may move while they are built) the kernels' arguments
+    sc.h_recs.assign(size_t(nE), OdoBatchRec{});
+    size_t idx_total = 0, part_total = 0;
+    int max_nq = 0, max_nb = 0, max_np = 0;
+    for (int j = 0; j < nE; ++j) {
+      const int k = j < nA ? act[size_t(j)] : idle[size_t(j - nA)];
+      OdometryDev &d = *o[k];
+      OdoBatchRec &r = sc.h_recs[size_t(j)];
+      r.a.time_factor = d.time_factor_; r.a.no_deskew = d.no_deskew_ ? 1 : 0;
+      r.st = d.d_state_.p;
+      r.ls = d.less_sharp_.p; r.n_ls = int(n_ls[k]); r.lf = d.less_flat_.p; r.n_lf = int(n_lf[k]);
+      if (n_ls[k] + n_lf[k] > size_t(INT_MAX)) throw CapacityError("lio_odom_process_batch: a sensor's clouds exceed 2^31 points");
+      max_np = std::max(max_np, r.n_ls + r.n_lf);
+      if (j >= nA) continue;
+      if (n_sharp[k] + n_flat[k] > (size_t(1) << 25)) throw CapacityError("lio_odom_process_batch: a sensor's queries exceed 2^25");   // one 64-thread block each
+      const int nq = int(n_sharp[k] + n_flat[k]);
+      r.idx_off = int(idx_total); r.part_off = int(part_total); r.trace_off = j * max_iter * 8;
+      r.nb = std::max(1, std::min(cdiv(nq, ODO_ROW_THREADS), 64));
+      idx_total += 2 * n_sharp[k] + 3 * n_flat[k]; part_total += size_t(r.nb);
+      if (idx_total > size_t(INT_MAX)) throw CapacityError("lio_odom_process_batch: the batch's index table exceeds 2^31 entries");
+      max_nq = std::max(max_nq, nq); max_nb = std::max(max_nb, r.nb);
+    }
+    if (nA) {
+      // ---- the bounds of all 2 * nA previous clouds with one read-back and one wait, then every sensor's own grids, back to back
+      sc.d_bounds.reserve(size_t(2 * nA));
+      if (sc.h_bounds.n < size_t(2 * nA)) sc.h_bounds.alloc(size_t(2 * nA) + size_t(nA), hipHostMallocDefault);
+      for (int j = 0; j < nA; ++j) {
+        OdometryDev &d = *o[act[size_t(j)]];
+        launch_cloud_bounds(d.last_corner_.p, int(d.n_last_corner_), d.partial_c_, sc.d_bounds.p + 2 * j, s);
+        launch_cloud_bounds(d.last_surf_.p, int(d.n_last_surf_), d.partial_s_, sc.d_bounds.p + 2 * j + 1, s);
+      }
+      LIO_HIP(hipMemcpyAsync(sc.h_bounds.p, sc.d_bounds.p, size_t(2 * nA) * sizeof(VoxParams), hipMemcpyDeviceToHost, s));
+      LIO_HIP(hipStreamSynchronize(s));
+      const float cell = 5.0f * 1.0001f;
+      for (int j = 0; j < nA; ++j) {
+        const int k = act[size_t(j)];
+        OdometryDev &d = *o[k];
+        VoxParams *b = sc.h_bounds.p + 2 * j;
+        for (int c = 0; c < 2; ++c)
+          if (b[c].n_valid == 0)
+            for (int e = 0; e < 3; ++e) b[c].mn[e] = b[c].mx[e] = 0.f;
+        d.grid_c_.build(d.last_corner_.p, d.n_last_corner_, b[0].mn, b[0].mx, cell, s);
+        d.grid_s_.build(d.last_surf_.p, d.n_last_surf_, b[1].mn, b[1].mx, cell, s);
+        sc.h_recs[size_t(j)].a = d.Args(n_sharp[k], n_flat[k]);
+      }
+      sc.d_idx.reserve(std::max<size_t>(idx_total, 1));
+      if (idx_total) LIO_HIP(hipMemsetAsync(sc.d_idx.p, 0xFF, idx_total * sizeof(int), s));
+      sc.d_partials.reserve(part_total * 28);
+      sc.d_trace.reserve(size_t(nA) * size_t(max_iter) * 8);
+      if (sc.mail_cap < size_t(nA)) {   // (the stream is idle between calls: nobody still posts to the old one)
+        const size_t cap = size_t(nA) + size_t(nA) / 2;
+        sc.h_mail.alloc(cap * (ODO_MAIL_STRIDE + sizeof(unsigned)), hipHostMallocCoherent, true);
+        sc.mail_cap = cap;
+      }
+    }
+    sc.d_recs.reserve(size_t(nE));
+    LIO_HIP(hipMemcpyAsync(sc.d_recs.p, sc.h_recs.data(), size_t(nE) * sizeof(OdoBatchRec), hipMemcpyHostToDevice, s));
+
+    if (nA) {
+      // ---- OdometryDev::Process's loop over the table: a peek where iter % 5 == 0 ends it only when EVERY sensor has converged (one that
+      // converged earlier stays frozen: its kernels leave at once)
+      static_assert(sizeof(OdomState) <= ODO_MAIL_STRIDE, "mailbox layout");
+      char *mail = sc.h_mail.p;
+      unsigned *flags = reinterpret_cast<unsigned *>(sc.h_mail.p + sc.mail_cap * ODO_MAIL_STRIDE);
+      std::vector<OdomState> got(static_cast<size_t>(nA), OdomState{});
+      auto read_mail = [&] {
+        bool all = true;
+        for (int j = 0; j < nA; ++j) {
+          got[size_t(j)] = *reinterpret_cast<const OdomState *>(mail + size_t(j) * ODO_MAIL_STRIDE);
+          all = all && got[size_t(j)].converged;
+        }
+        return all;
+      };
+      HostSignal sig{};
+      sig.nslots = nA;
+      bool have_state = false;
+      for (int iter = 0; iter < max_iter; ++iter) {
+        if (iter > 0 && iter % 5 == 0) {
+          wait_host_signal(sig, s);
+          if (read_mail()) { have_state = true; break; }
+        }
+        if (iter % 5 == 0 && max_nq > 0) hipLaunchKernelGGL(k_ob_corr, dim3(max_nq, nA), dim3(64), 0, s, sc.d_recs.p, sc.d_idx.p);
+        hipLaunchKernelGGL(k_ob_rows, dim3(max_nb, nA), dim3(ODO_ROW_THREADS), 0, s, sc.d_recs.p, sc.d_idx.p, iter, sc.d_partials.p);
+        HostSignal sg{};
+        if (iter % 5 == 4 || iter == max_iter - 1) { sig.flag = flags; sig.seq = ++sc.seq; sg = sig; }
+        hipLaunchKernelGGL(k_ob_update, dim3(nA), dim3(256), 0, s, sc.d_recs.p, sc.d_partials.p, iter, mail, sg, sc.d_trace.p);
+      }
+      LIO_HIP(hipGetLastError());
+      if (!have_state) {   // the last iteration posted (max_iter >= 1)
+        wait_host_signal(sig, s);
+        read_mail();
+      }
+      // every sensor's records in one copy (every launch behind them is complete: the states came back; iters >= 1 for each)
+      sc.h_trace.resize(size_t(nA) * size_t(max_iter) * 8);
+      LIO_HIP(hipMemcpyAsync(sc.h_trace.data(), sc.d_trace.p, sc.h_trace.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+      LIO_HIP(hipStreamSynchronize(s));
+      for (int j = 0; j < nA; ++j) {
+        const int k = act[size_t(j)];
+        st[size_t(k)] = got[size_t(j)];
+        for (int i = 0; i < got[size_t(j)].iters; ++i) {
+          const float *T = &sc.h_trace[size_t(sc.h_recs[size_t(j)].trace_off) + size_t(i) * 8];
+          o[k]->es_trace_.push_back(Rigid<float>(Quat<float>(T[3], T[0], T[1], T[2]), Vec3<float>(T[4], T[5], T[6])));
+        }
+      }
+    }
+    // (a sensor of `idle` keeps the state it was given: nothing ran on it)
+    for (int j = 0; j < nE; ++j) {
+      const int k = j < nA ? act[size_t(j)] : idle[size_t(j - nA)];
+      o[k]->Accumulate(st[size_t(k)]);
+    }
+    if (max_np) hipLaunchKernelGGL(k_ob_to_end, dim3(cdiv(max_np, 256), nE), dim3(256), 0, s, sc.d_recs.p);
+    LIO_HIP(hipGetLastError());
+  }
+  LIO_HIP(hipStreamSynchronize(s));
+  for (int k = 0; k < n; ++k) {
+    OdometryDev &d = *o[k];
+    std::swap(d.last_corner_, d.less_sharp_); std::swap(d.last_surf_, d.less_flat_);
+    d.n_last_corner_ = n_ls[k]; d.n_last_surf_ = n_lf[k];
+    d.inited_ = true;
+  }
 }
 
 // lio_odom_correspondences (include/lio_test_hooks.h): the given clouds as the previous sweep's, the grids Process builds, ONE launch of

@@ -293,6 +293,13 @@ _FULL_SIGS = {
     "lio_deskew_to_end": (C.c_int, [c_float_p, C.c_size_t, C.POINTER(TransformF), C.c_float, C.c_int, c_float_p]),
 }
 FULL_MAP_FRAME, FULL_SENSOR_RAW, FULL_SENSOR_END = 1, 2, 3   # LIO_FULL_* of include/lio_full_cloud.h
+# include/lio_odom_batch.h: the scan-to-scan odometry of many sensors through one launch chain (the product only, attached like _EXT_SIGS)
+_c_float_pp, _c_size_p = C.POINTER(c_float_p), C.POINTER(C.c_size_t)
+_ODOM_BATCH_SIGS = {
+    "lio_odom_process_batch": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, _c_float_pp, _c_size_p, _c_float_pp, _c_size_p, _c_float_pp, _c_size_p,
+                                         _c_float_pp, _c_size_p, C.POINTER(TransformF), C.POINTER(TransformF), c_int32_p, c_int32_p]),
+}
+ODOM_BATCH_MAX_SENSORS = 1024   # LIO_ODOM_BATCH_MAX_SENSORS
 
 
 def _dp(a):
@@ -343,7 +350,7 @@ class LioLib:
         self.backend = self.dll.lio_backend().decode()
         self.has_ext = self.backend.startswith("hip")
         if self.has_ext:
-            for name, (res, args) in list(_EXT_SIGS.items()) + list(_FULL_SIGS.items()):
+            for name, (res, args) in list(_EXT_SIGS.items()) + list(_FULL_SIGS.items()) + list(_ODOM_BATCH_SIGS.items()):
                 fn = getattr(self.dll, name)
                 fn.restype = res
                 fn.argtypes = args
@@ -937,6 +944,35 @@ class PointOdometry:
             raise LioError(f"lio_odom_get_iteration_trace -> {n}")
         trace = np.frombuffer(tr, dtype=np.float32).reshape(-1, 7)[:n].copy()   # rows: q xyzw, p
         return dict(T_sum=Ts.to_np(), T_es=Te.to_np(), iterations=it.value, num_selected=ns.value, trace=trace, kz=kz.value)
+
+    @staticmethod
+    def process_batch(handles, clouds):
+        """lio_odom_process_batch (include/lio_odom_batch.h): one sweep of every PointOdometry of `handles` through one launch chain;
+        clouds[k] = (sharp, less_sharp, flat, less_flat) of sensor k.  -> list of the dicts process() returns, without trace and kz
+        (ask iteration_trace() of the handle)."""
+        n = len(handles)
+        if n < 1 or len(clouds) != n:
+            raise LioError("process_batch: one set of four clouds per handle, at least one handle")
+        lib = handles[0].lib
+        cl = [[_f32(c).reshape(-1, 4) for c in four] for four in clouds]   # (kept alive until the call returns)
+        H = (C.c_void_p * n)(*[h.h for h in handles])
+        args = []
+        for w in range(4):
+            args += [(c_float_p * n)(*[_fp(cl[k][w]) for k in range(n)]), (C.c_size_t * n)(*[cl[k][w].shape[0] for k in range(n)])]
+        Ts, Te = (TransformF * n)(), (TransformF * n)()
+        it, ns = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        _chk(lib.dll.lio_odom_process_batch(H, n, *args, Ts, Te, it.ctypes.data_as(c_int32_p), ns.ctypes.data_as(c_int32_p)), "lio_odom_process_batch")
+        return [dict(T_sum=Ts[k].to_np(), T_es=Te[k].to_np(), iterations=int(it[k]), num_selected=int(ns[k])) for k in range(n)]
+
+    def iteration_trace(self):
+        """lio_odom_get_iteration_trace: transform_es_ after every iteration of the last step (rows: q xyzw, p) and kz."""
+        n = self.lib.dll.lio_odom_get_iteration_trace(self.h, None, 0, None)
+        if n < 0:
+            raise LioError(f"lio_odom_get_iteration_trace -> {n}")
+        tr = (TransformF * max(n, 1))()
+        kz = C.c_int(0)
+        n = self.lib.dll.lio_odom_get_iteration_trace(self.h, tr, max(n, 1), C.byref(kz))
+        return np.frombuffer(tr, dtype=np.float32).reshape(-1, 7)[:n].copy(), kz.value
 
     def enable(self, on):
         _chk(self.lib.dll.lio_odom_enable(self.h, 1 if on else 0), "lio_odom_enable")

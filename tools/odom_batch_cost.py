@@ -1,0 +1,144 @@
+"""What lio_odom_process_batch buys over a loop of lio_odom_process (docs/odom_batch.md).
+
+B copies of one sensor step through the same sweeps twice: one set of handles by a loop of lio_odom_process, one set by ONE
+lio_odom_process_batch, alternating step by step with the order swapped every step.  The sweeps are a pair (indoor VLP-16, outdoor
+HDL-64E; feature clouds from the product's PointProcessor) stepped to and fro, so every step is a real motion against the previous sweep
+and runs its full iterations.  Both calls end synchronised, so the host clock around them is the latency the caller pays.  Medians with
+min - max over the steps after the warm-up; a GPU is required.
+
+    python tools/odom_batch_cost.py [--steps 12] [--batches 1,8,64] [--kinds indoor,outdoor] [--out FILE.json]
+
+--parent-lib PATH additionally times lio_odom_process ALONE of this tree against another build of the product (the parent commit's
+liblio_hip.so) on the same sweeps, alternating, the order swapped every pair: what the shared device bodies cost the single path.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "lio-mapping_amd"))
+
+WARMUP = 3   # the first steps grow the buffers and load the code objects
+
+
+def _ms(fn):
+    t = time.perf_counter()
+    r = fn()
+    return r, (time.perf_counter() - t) * 1e3
+
+
+def _stats(v):
+    return dict(median=round(float(np.median(v)), 4), min=round(float(np.min(v)), 4), max=round(float(np.max(v)), 4))
+
+
+def sweep_pair(hip, kind):
+    from lio_amd import capi, synth
+
+    sweeps, _, lid = synth.make_sweeps(kind, 2)
+    out = []
+    for sw in sweeps:
+        pp = capi.PointProcessor(hip, lid.lower_deg, lid.upper_deg, lid.rings)
+        pp.process(sw)
+        out.append([pp.cloud(w) for w in (1, 2, 3, 4)])
+    return out
+
+
+def _sensors(lib, pair, n):
+    from lio_amd import capi
+
+    ods = [capi.PointOdometry(lib, 0.1, 2, 25, False) for _ in range(n)]
+    for od in ods:
+        od.process(*pair[0])
+    return ods
+
+
+def measure_batch(hip, kind, pair, B, steps):
+    from lio_amd import capi
+
+    loop, batch = _sensors(hip, pair, B), _sensors(hip, pair, B)
+    t_loop, t_batch, its = [], [], []
+    for k in range(WARMUP + steps):
+        cl = pair[(k + 1) % 2]
+
+        def run_loop():
+            return [od.process(*cl) for od in loop]
+
+        def run_batch():
+            return capi.PointOdometry.process_batch(batch, [cl] * B)
+
+        if k % 2:
+            (ra, a), (rb, b) = _ms(run_loop), _ms(run_batch)
+        else:
+            (rb, b), (ra, a) = _ms(run_batch), _ms(run_loop)
+        for x, y in zip(ra, rb):   # the batch's contract, at the size that is timed
+            assert x["T_es"][0].tobytes() == y["T_es"][0].tobytes() and x["T_es"][1].tobytes() == y["T_es"][1].tobytes() and x["iterations"] == y["iterations"]
+        if k >= WARMUP:
+            t_loop.append(a), t_batch.append(b), its.append(ra[0]["iterations"])
+    return dict(what="batch", kind=kind, B=B, steps_measured=steps, queries=int(len(pair[1][0]) + len(pair[1][2])), iterations=int(np.median(its)),
+                loop_ms=_stats(t_loop), batch_ms=_stats(t_batch), loop_per_sensor_us=round(float(np.median(t_loop)) / B * 1e3, 2),
+                batch_per_sensor_us=round(float(np.median(t_batch)) / B * 1e3, 2), ratio=round(float(np.median(t_loop) / np.median(t_batch)), 3))
+
+
+def measure_parent(hip, parent, kind, pair, steps):
+    here, there = _sensors(hip, pair, 1)[0], _sensors(parent, pair, 1)[0]
+    t_here, t_there = [], []
+    for k in range(WARMUP + steps):
+        cl = pair[(k + 1) % 2]
+        if k % 2:
+            (ra, a), (rb, b) = _ms(lambda: here.process(*cl)), _ms(lambda: there.process(*cl))
+        else:
+            (rb, b), (ra, a) = _ms(lambda: there.process(*cl)), _ms(lambda: here.process(*cl))
+        assert ra["T_es"][0].tobytes() == rb["T_es"][0].tobytes() and ra["T_es"][1].tobytes() == rb["T_es"][1].tobytes()   # same results as the parent
+        if k >= WARMUP:
+            t_here.append(a), t_there.append(b)
+    return dict(what="single_vs_parent", kind=kind, steps_measured=steps, this_tree_ms=_stats(t_here), parent_ms=_stats(t_there))
+
+
+def load_parent(path):
+    """another build of the product, which may lack lio_odom_process_batch"""
+    from lio_amd import capi
+
+    sigs = dict(capi._ODOM_BATCH_SIGS)
+    capi._ODOM_BATCH_SIGS.clear()
+    try:
+        return capi.LioLib(path)
+    finally:
+        capi._ODOM_BATCH_SIGS.update(sigs)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=12)
+    ap.add_argument("--batches", default="1,8,64")
+    ap.add_argument("--kinds", default="indoor,outdoor")
+    ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    assert args.steps >= 8, "medians over at least 8 steps"
+    import torch  # noqa: F401  (before the product library, as in __graft_entry__.py)
+
+    assert torch.cuda.is_available(), "needs a GPU"
+    from lio_amd import capi
+
+    hip = capi.load_hip()
+    parent = load_parent(args.parent_lib) if args.parent_lib else None
+    results = []
+    for kind in args.kinds.split(","):
+        pair = sweep_pair(hip, kind)
+        for B in [int(b) for b in args.batches.split(",") if b]:
+            results.append(measure_batch(hip, kind, pair, B, args.steps))
+            print(json.dumps(results[-1]), flush=True)
+        if parent is not None:
+            results.append(measure_parent(hip, parent, kind, pair, max(args.steps, 24)))
+            print(json.dumps(results[-1]), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(results, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
