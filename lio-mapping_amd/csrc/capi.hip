@@ -10,6 +10,7 @@
 #include "../../include/lio_ext.h"
 #include "../../include/lio_full_cloud.h"
 #include "../../include/lio_odom_batch.h"
+#include "../../include/lio_frontend_batch.h"
 #include "est_batch.h"
 #include "seg_sort.h"
 #include "estimator.h"
@@ -301,6 +302,57 @@ int lio_odom_process_batch(lio_odom *const *handles, int n_sensors, const float 
     OdometryDev::ProcessBatch(o.data(), n_sensors, sharp, n_sharp, less_sharp, n_ls, flat, n_flat, less_flat, n_lf);
     for (int k = 0; k < n_sensors; ++k) {
       const OdometryDev &d = *o[size_t(k)];
+      if (Tsum) fromT(d.transform_sum_, &Tsum[k]);
+      if (Tes) fromT(d.transform_es_, &Tes[k]);
+      if (iters) iters[k] = d.iterations_done_;
+      if (nsel) nsel[k] = d.last_num_sel_;
+    }
+    return int(LIO_OK);
+  });
+}
+// include/lio_frontend_batch.h.  Every pp[k] is resolved to (processor, sweep) as pp_read resolves it; the shared processors stay locked
+// until the chain, which reads their clouds, has returned synchronised.
+int lio_odom_process_batch_from_pp(lio_odom *const *handles, lio_pp *const *pp, int n_sensors, lio_transform_f *Tsum, lio_transform_f *Tes,
+                                   int32_t *iters, int32_t *nsel) {
+  if (!handles || !pp || n_sensors < 1) return LIO_ERR_ARG;
+  if (n_sensors > LIO_ODOM_BATCH_MAX_SENSORS) return LIO_ERR_CAPACITY;
+  for (int k = 0; k < n_sensors; ++k)
+    if (!handles[k] || !pp[k]) return LIO_ERR_ARG;
+  return guarded([&] {
+    const size_t n = size_t(n_sensors);
+    std::vector<OdometryDev *> o;
+    for (size_t k = 0; k < n; ++k) o.push_back(handles[k]->o.get());
+    std::vector<OdometryDev *> sorted = o;
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return int(LIO_ERR_ARG);   // the same handle twice
+    std::vector<lio_pp_pool *> pools;
+    for (size_t k = 0; k < n; ++k)
+      if (pp[k]->pool && pp[k]->pool_sweep >= 0) pools.push_back(pp[k]->pool.get());
+    std::sort(pools.begin(), pools.end());   // (one order for every caller)
+    pools.erase(std::unique(pools.begin(), pools.end()), pools.end());
+    std::vector<std::unique_lock<std::mutex>> locks;
+    for (lio_pp_pool *p : pools) locks.emplace_back(p->mu);
+    // the host table: four (source, count) pairs per sensor
+    std::vector<const float *> src[4];
+    std::vector<size_t> cnt[4];
+    for (int c = 0; c < 4; ++c) { src[c].resize(n); cnt[c].resize(n); }
+    for (size_t k = 0; k < n; ++k) {
+      const lio_pp *h = pp[k];
+      const bool pooled = h->pool && h->pool_sweep >= 0;
+      if (pooled && h->pool_gen != h->pool->gen)
+        throw std::runtime_error("lio_odom_process_batch_from_pp: a processor's batch results were overwritten by a later lio_pp_process_batch on the storage it shared");
+      PointProcessorDev &p = pooled ? h->pool->pp : *h->pp;
+      try { p.ProcessFinish(); }   // a sweep still in flight (lio_pp_process_async) is waited for
+      catch (const CapacityError &e) { throw std::runtime_error(e.what()); }
+      if (!p.has_results()) throw std::runtime_error("lio_odom_process_batch_from_pp: a processor has no completed sweep");
+      const float4 *s4[4]; size_t n4[4];
+      p.DeviceClouds(pooled ? h->pool_sweep : 0, s4, n4);
+      for (int c = 0; c < 4; ++c) { src[c][k] = reinterpret_cast<const float *>(s4[c]); cnt[c][k] = n4[c]; }
+    }
+    OdometryDev::ProcessBatch(o.data(), n_sensors, src[0].data(), cnt[0].data(), src[1].data(), cnt[1].data(), src[2].data(), cnt[2].data(), src[3].data(),
+                              cnt[3].data(), true);
+    for (size_t k = 0; k < n; ++k) {
+      const OdometryDev &d = *o[k];
       if (Tsum) fromT(d.transform_sum_, &Tsum[k]);
       if (Tes) fromT(d.transform_es_, &Tes[k]);
       if (iters) iters[k] = d.iterations_done_;

@@ -59,6 +59,58 @@ __device__ __forceinline__ uint32_t cell_key_clamped(const float4 &p, const Grid
   return cell_index(cx, cy, cz, g);
 }
 
+// The counting sort by cell of KnnGrid::build, per point, stated once for a grid built alone (k_cell_count, k_cell_place) and for the grids
+// of a batch built side by side (odometry.hip: k_ob_cell_count, k_ob_cell_place).  Point i takes a slot inside its cell ...
+__device__ __forceinline__ void cell_count_point(const float4 *__restrict__ pts, int i, const GridDesc &g, uint32_t *__restrict__ keys,
+                                                 uint32_t *__restrict__ slot, int *__restrict__ cnt) {
+  const uint32_t c = cell_key_clamped(pts[i], g);
+  keys[i] = c;
+  slot[i] = uint32_t(atomicAdd(&cnt[c], 1));
+}
+// ... and, once the counts have been scanned into `starts`, goes to its place with its index in .w and puts its cell's count back to zero
+__device__ __forceinline__ void cell_place_point(const float4 *__restrict__ pts, const uint32_t *__restrict__ keys, const uint32_t *__restrict__ slot, int i,
+                                                 const int *__restrict__ starts, float4 *__restrict__ sorted, int *__restrict__ cnt) {
+  float4 p = pts[i];
+  p.w = __int_as_float(i);
+  const uint32_t c = keys[i];
+  sorted[starts[c] + int(slot[i])] = p;
+  cnt[c] = 0;
+}
+
+// out[i] = base + in[0] + ... + in[i - 1] for i < n, by ONE workgroup of SEG_SCAN_THREADS threads that walks the table in chunks of
+// SEG_SCAN_THREADS * SEG_SCAN_ITEMS entries: a thread adds its own entries, the wavefront scans the threads' sums with shuffles, the
+// wavefronts' totals and the carry from chunk to chunk go through LDS.  Nothing outside the workgroup is waited for.  in != out.
+#define SEG_SCAN_THREADS 1024
+#define SEG_SCAN_ITEMS 4
+__device__ __forceinline__ void block_exclusive_scan(const int *__restrict__ in, int *__restrict__ out, int n, int base) {
+  __shared__ int wsum[SEG_SCAN_THREADS / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  int carry = base;
+  for (int c0 = 0; c0 < n; c0 += SEG_SCAN_THREADS * SEG_SCAN_ITEMS) {   // (uniform: every thread of the block takes every chunk)
+    const int i0 = c0 + tid * SEG_SCAN_ITEMS;
+    int v[SEG_SCAN_ITEMS], tsum = 0;
+#pragma unroll
+    for (int k = 0; k < SEG_SCAN_ITEMS; ++k) { v[k] = i0 + k < n ? in[i0 + k] : 0; tsum += v[k]; }
+    int inc = tsum;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int u = __shfl_up(inc, off, 64);
+      if (lane >= off) inc += u;
+    }
+    if (lane == 63) wsum[wv] = inc;
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < SEG_SCAN_THREADS / 64; ++w) { const int t = wsum[w]; if (w < wv) before += t; total += t; }
+    int run = carry + before + inc - tsum;
+#pragma unroll
+    for (int k = 0; k < SEG_SCAN_ITEMS; ++k)
+      if (i0 + k < n) { out[i0 + k] = run; run += v[k]; }
+    carry += total;
+    __syncthreads();   // the next chunk rewrites wsum
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // pcl::VoxelGrid
 // ------------------------------------------------------------------------------------------------

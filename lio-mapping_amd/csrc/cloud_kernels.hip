@@ -317,9 +317,7 @@ __global__ void k_cell_count(const float4 *__restrict__ pts, int n, GridDesc g, 
                              int *__restrict__ cnt) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const uint32_t c = cell_key_clamped(pts[i], g);
-  keys[i] = c;
-  slot[i] = uint32_t(atomicAdd(&cnt[c], 1));
+  cell_count_point(pts, i, g, keys, slot, cnt);
 }
 
 // cnt: the histogram of k_cell_count, already scanned into `starts`; every point puts its cell's count back to zero (plain
@@ -328,11 +326,7 @@ __global__ void k_cell_place(const float4 *__restrict__ pts, const uint32_t *__r
                              const int *__restrict__ starts, float4 *__restrict__ sorted, int *__restrict__ cnt) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  float4 p = pts[i];
-  p.w = __int_as_float(i);
-  const uint32_t c = keys[i];
-  sorted[starts[c] + int(slot[i])] = p;
-  cnt[c] = 0;
+  cell_place_point(pts, keys, slot, i, starts, sorted, cnt);
 }
 
 void KnnGrid::build(const float4 *pts, size_t n, const float mn[3], const float mx[3], float cell, hipStream_t s) {

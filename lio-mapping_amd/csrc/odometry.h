@@ -20,8 +20,11 @@ class OdometryDev {
   // Process for n independent sensors, one sweep each, through one launch chain on o[0]'s stream (lio_odom_process_batch,
   // include/lio_odom_batch.h): array k of every argument belongs to o[k]; every sensor ends in the state Process alone leaves, bit for
   // bit.  The chain's scratch stays with o[0].  Sensors whose max_iter differ are processed one after the other.
+  // on_device (lio_odom_process_batch_from_pp, include/lio_frontend_batch.h): the clouds lie in device memory, complete and left alone until
+  // the call returns; one launch copies them and sets every sensor's starting state, no copy per sensor.
   static void ProcessBatch(OdometryDev *const *o, int n, const float *const *sharp, const size_t *n_sharp, const float *const *less_sharp,
-                           const size_t *n_ls, const float *const *flat, const size_t *n_flat, const float *const *less_flat, const size_t *n_lf);
+                           const size_t *n_ls, const float *const *flat, const size_t *n_flat, const float *const *less_flat, const size_t *n_lf,
+                           bool on_device = false);
   size_t GetLastCloud(int which, float *out);
   // TransformToEnd(full_cloud_) with the last Process's transform_es_ (:725-730); a byte copy while the odometry is disabled
   void FullToEnd(const float *xyzi, size_t n, float *out);
@@ -50,6 +53,8 @@ class OdometryDev {
   DBuf<float> d_trace_;        // 8 floats per iteration, written by k_odo_update
   std::vector<float> h_trace_;
   void BuildGrids();
+  void ProcessFrom(const float *sharp, size_t n_sharp, const float *less_sharp, size_t n_ls, const float *flat, size_t n_flat, const float *less_flat,
+                   size_t n_lf, bool on_device);
   void Accumulate(const OdomState &st);   // the host's end of a step that ran with the odometry enabled (:654-663)
   std::unique_ptr<OdoBatchScratch> batch_;   // ProcessBatch with this handle first: argument table, partials, indices, traces, mailbox
   OdoArgs Args(size_t n_sharp, size_t n_flat) const;

@@ -18,6 +18,7 @@
 #include <cstring>
 
 #include "odometry.h"
+#include "../../include/lio_frontend_batch.h"
 #include "cloud_device.h"
 
 namespace lio {
@@ -396,6 +397,10 @@ struct OdoBatchRec {
   int nb;                     // its row blocks: max(1, min(cdiv(nq, ODO_ROW_THREADS), 64)), the partition it has alone
   int part_off;               // its first row (28 doubles each) of the batch's partials
   int trace_off;              // its first float of the batch's trace table (8 per iteration)
+  // the segmented build of its two grids over a.lastc (0) and a.lasts (1): the batch's tables hold every sensor's grids one behind the other
+  int b_nb[2], b_off[2];      // bounds: its blocks over the cloud (launch_cloud_bounds's count), its first row of the batch's bounds partials
+  int g_pt[2];                // the cloud's first entry in the batch's keys / slot / sorted arrays; < 0: this grid is built by KnnGrid::build
+  int g_cell[2], g_ncells[2]; // its slice (g_ncells + 1 entries) of the batch's count and cell tables
 };
 #define ODO_MAIL_STRIDE 64    // bytes per sensor in the batch's mailbox
 
@@ -432,7 +437,78 @@ __global__ void __launch_bounds__(256) k_ob_to_end(const OdoBatchRec *__restrict
   odo_to_end_body(c, c, i < r.n_ls ? i : i - r.n_ls, r.st, r.a.time_factor, r.a.no_deskew);
 }
 
-// The chain's scratch, kept by the first handle of a batch.  No results live here: the states, clouds and grids are the handles' own.
+// ---- the segmented grid build: launch_cloud_bounds and KnnGrid::build of all 2 * nA previous clouds in five launches.  Grid `y` of a launch is
+// cloud y & 1 of sensor y >> 1.  The bounds are folded by the device code of the single path's (vox_block_partial, vox_fold_bounds: min and
+// max do not hang on the order, the count is an exact float sum), the cells are keyed and the points placed by k_cell_count's and
+// k_cell_place's bodies.  A grid's run starts are offsets into the batch's ONE sorted array, which is all odo_corr_body asks of them.
+__global__ void __launch_bounds__(VOX_TILE) k_ob_bounds(const OdoBatchRec *__restrict__ recs, float *__restrict__ partial_all) {
+  const OdoBatchRec &r = recs[blockIdx.y >> 1];
+  const int w = blockIdx.y & 1, nb = r.b_nb[w];
+  if (int(blockIdx.x) >= nb) return;
+  const float4 *pts = w ? r.a.lasts : r.a.lastc;
+  const int n = w ? r.a.nls : r.a.nlc;
+  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+  float cnt = 0;
+  for (int i = blockIdx.x * VOX_TILE + threadIdx.x; i < n; i += nb * VOX_TILE) {
+    const float4 p = pts[i];
+    if (!finite3(p)) continue;
+    cnt += 1.f;
+    mn[0] = fminf(mn[0], p.x); mn[1] = fminf(mn[1], p.y); mn[2] = fminf(mn[2], p.z);
+    mx[0] = fmaxf(mx[0], p.x); mx[1] = fmaxf(mx[1], p.y); mx[2] = fmaxf(mx[2], p.z);
+  }
+  vox_block_partial(mn, mx, cnt, partial_all + (size_t(r.b_off[w]) + blockIdx.x) * 8);
+}
+// one block per cloud: out[2 * sensor + cloud]
+__global__ void __launch_bounds__(VOX_TILE) k_ob_bounds_fold(const OdoBatchRec *__restrict__ recs, const float *__restrict__ partial_all,
+                                                             VoxParams *__restrict__ out) {
+  const OdoBatchRec &r = recs[blockIdx.x >> 1];
+  const int w = blockIdx.x & 1;
+  VoxParams v;
+  if (vox_fold_bounds(partial_all + size_t(r.b_off[w]) * 8, r.b_nb[w], 1.0f, v)) out[blockIdx.x] = v;
+}
+// grid (cdiv(max points, 256), grids)
+__global__ void __launch_bounds__(256) k_ob_cell_count(const OdoBatchRec *__restrict__ recs, uint32_t *__restrict__ keys, uint32_t *__restrict__ slot,
+                                                       int *__restrict__ cnt) {
+  const OdoBatchRec &r = recs[blockIdx.y >> 1];
+  const int w = blockIdx.y & 1, off = r.g_pt[w];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (off < 0 || i >= (w ? r.a.nls : r.a.nlc)) return;
+  cell_count_point(w ? r.a.lasts : r.a.lastc, i, w ? r.a.gs : r.a.gc, keys + off, slot + off, cnt + r.g_cell[w]);
+}
+// one workgroup per grid walks the grid's own count table: no block waits for another
+__global__ void __launch_bounds__(SEG_SCAN_THREADS) k_ob_cell_scan(const OdoBatchRec *__restrict__ recs, const int *__restrict__ cnt, int *__restrict__ cells) {
+  const OdoBatchRec &r = recs[blockIdx.x >> 1];
+  const int w = blockIdx.x & 1;
+  if (r.g_pt[w] < 0) return;
+  block_exclusive_scan(cnt + r.g_cell[w], cells + r.g_cell[w], r.g_ncells[w] + 1, r.g_pt[w]);
+}
+__global__ void __launch_bounds__(256) k_ob_cell_place(const OdoBatchRec *__restrict__ recs, const uint32_t *__restrict__ keys, const uint32_t *__restrict__ slot,
+                                                       const int *__restrict__ cells, float4 *__restrict__ sorted, int *__restrict__ cnt) {
+  const OdoBatchRec &r = recs[blockIdx.y >> 1];
+  const int w = blockIdx.y & 1, off = r.g_pt[w];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (off < 0 || i >= (w ? r.a.nls : r.a.nlc)) return;
+  cell_place_point(w ? r.a.lasts : r.a.lastc, keys + off, slot + off, i, cells + r.g_cell[w], sorted, cnt + r.g_cell[w]);
+}
+
+// ---- the hand-over from the feature extraction (lio_odom_process_batch_from_pp): one sensor's four clouds, where the processor left them on
+// the device, into the handle's sharp_ / less_sharp_ / flat_ / less_flat_, and the state its iterations start from
+struct OdoTakeRec {
+  const float4 *src[4]; float4 *dst[4]; int n[4];   // sharp, less sharp, flat, less flat; n = 0: not taken
+  OdomState *st;                                    // null: the sensor only stores or packs its clouds
+  OdomState init;
+};
+// grid (cdiv(max n, 256), 4, sensors): one float4 per thread
+__global__ void __launch_bounds__(256) k_ob_take(const OdoTakeRec *__restrict__ recs) {
+  const OdoTakeRec &r = recs[blockIdx.z];
+  const int c = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (blockIdx.x == 0 && c == 0 && r.st && threadIdx.x < sizeof(OdomState) / 4)
+    reinterpret_cast<int *>(r.st)[threadIdx.x] = reinterpret_cast<const int *>(&r.init)[threadIdx.x];
+  if (i < r.n[c]) r.dst[c][i] = r.src[c][i];
+}
+
+// The chain's scratch, kept by the first handle of a batch.  No results live here: the states and clouds are the handles' own, and the grids
+// of a call are rebuilt by every call from the handles' previous clouds.
 struct OdoBatchScratch {
   std::vector<OdoBatchRec> h_recs;
   DBuf<OdoBatchRec> d_recs;
@@ -445,6 +521,14 @@ struct OdoBatchScratch {
   HostBuf<char> h_mail;       // pinned, coherent: mail_cap states of ODO_MAIL_STRIDE bytes, then mail_cap completion words
   size_t mail_cap = 0;
   unsigned seq = 0;
+  // the segmented grid build: bounds partials, and the grids' keys, slots, counts, run starts and cell-sorted points, one grid behind the other
+  DBuf<float> d_bpartial;
+  DBuf<uint32_t> g_keys, g_slot;
+  DBuf<int> g_cnt, g_cells;
+  DBuf<float4> g_sorted;
+  bool g_cnt_dirty = false;   // KnnGrid's invariant for g_cnt: all zeros between builds (k_ob_cell_place puts them back)
+  std::vector<OdoTakeRec> h_take;
+  DBuf<OdoTakeRec> d_take;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -478,9 +562,9 @@ void OdometryDev::BuildGrids() {
   grid_s_.build(last_surf_.p, n_last_surf_, h_bounds_.p[1].mn, h_bounds_.p[1].mx, cell, s);
 }
 
-static void upload(DBuf<float4> &b, const float *src, size_t n, hipStream_t s) {
+static void upload(DBuf<float4> &b, const float *src, size_t n, hipStream_t s, hipMemcpyKind kind = hipMemcpyHostToDevice) {
   b.reserve(std::max<size_t>(n, 1));
-  if (n) LIO_HIP(hipMemcpyAsync(b.p, src, n * sizeof(float4), hipMemcpyHostToDevice, s));
+  if (n) LIO_HIP(hipMemcpyAsync(b.p, src, n * sizeof(float4), kind, s));
 }
 
 // the kernels' view of sharp_ / flat_ against the previous sweep's clouds and their grids (after BuildGrids)
@@ -503,10 +587,16 @@ void OdometryDev::Accumulate(const OdomState &st) {
 
 void OdometryDev::Process(const float *sharp, size_t n_sharp, const float *less_sharp, size_t n_ls, const float *flat, size_t n_flat,
                           const float *less_flat, size_t n_lf) {
+  ProcessFrom(sharp, n_sharp, less_sharp, n_ls, flat, n_flat, less_flat, n_lf, false);
+}
+// on_device: the four clouds lie in device memory (a batch from the feature extraction that has no common chain)
+void OdometryDev::ProcessFrom(const float *sharp, size_t n_sharp, const float *less_sharp, size_t n_ls, const float *flat, size_t n_flat,
+                              const float *less_flat, size_t n_lf, bool on_device) {
+  const hipMemcpyKind up = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   iterations_done_ = 0; last_num_sel_ = 0; last_kz_ = 0; es_trace_.clear();
   hipStream_t s = stream_;
-  upload(less_sharp_, less_sharp, n_ls, s);
-  upload(less_flat_, less_flat, n_lf, s);
+  upload(less_sharp_, less_sharp, n_ls, s, up);
+  upload(less_flat_, less_flat, n_lf, s, up);
   if (!inited_) {  // :302-310
     LIO_HIP(hipStreamSynchronize(s));
     std::swap(last_corner_, less_sharp_); std::swap(last_surf_, less_flat_);
@@ -526,8 +616,8 @@ void OdometryDev::Process(const float *sharp, size_t n_sharp, const float *less_
     st.T[4] = transform_es_.pos.x; st.T[5] = transform_es_.pos.y; st.T[6] = transform_es_.pos.z;
     LIO_HIP(hipMemcpyAsync(d_state_.p, &st, sizeof(st), hipMemcpyHostToDevice, s));
     if (n_last_corner_ > 10 && n_last_surf_ > 100) {
-      upload(sharp_, sharp, n_sharp, s);
-      upload(flat_, flat, n_flat, s);
+      upload(sharp_, sharp, n_sharp, s, up);
+      upload(flat_, flat, n_flat, s, up);
       const int nq = int(n_sharp + n_flat);
       idx_.reserve(std::max<size_t>(2 * n_sharp + 3 * n_flat, 1));
       LIO_HIP(hipMemsetAsync(idx_.p, 0xFF, (2 * n_sharp + 3 * n_flat) * sizeof(int), s));
@@ -581,11 +671,12 @@ void OdometryDev::Process(const float *sharp, size_t n_sharp, const float *less_
 }
 
 void OdometryDev::ProcessBatch(OdometryDev *const *o, int n, const float *const *sharp, const size_t *n_sharp, const float *const *less_sharp,
-                               const size_t *n_ls, const float *const *flat, const size_t *n_flat, const float *const *less_flat, const size_t *n_lf) {
+                               const size_t *n_ls, const float *const *flat, const size_t *n_flat, const float *const *less_flat, const size_t *n_lf,
+                               bool on_device) {
   OdometryDev &lead = *o[0];
   for (int k = 1; k < n; ++k)
     if (o[k]->max_iter_ != lead.max_iter_) {   // no common iteration count: no common chain
-      for (int j = 0; j < n; ++j) o[j]->Process(sharp[j], n_sharp[j], less_sharp[j], n_ls[j], flat[j], n_flat[j], less_flat[j], n_lf[j]);
+      for (int j = 0; j < n; ++j) o[j]->ProcessFrom(sharp[j], n_sharp[j], less_sharp[j], n_ls[j], flat[j], n_flat[j], less_flat[j], n_lf[j], on_device);
       return;
     }
   const int max_iter = lead.max_iter_;
@@ -593,31 +684,50 @@ void OdometryDev::ProcessBatch(OdometryDev *const *o, int n, const float *const 
   if (!lead.batch_) lead.batch_.reset(new OdoBatchScratch);
   OdoBatchScratch &sc = *lead.batch_;
 
-  // ---- uploads, per sensor; who iterates (`act`), who only carries its clouds to the end (`idle`), who only stores them (neither)
+  // ---- the clouds and the starting state, per sensor: uploads from the host, or (on_device) one record of the take table each; who
+  // iterates (`act`), who only carries its clouds to the end (`idle`), who only stores them (neither)
   std::vector<int> act, idle;
   std::vector<OdomState> st(size_t(n), OdomState{});
+  if (on_device) sc.h_take.assign(size_t(n), OdoTakeRec{});
+  size_t max_take = 0;
+  // cloud c of sensor k: sharp, less sharp, flat, less flat
+  auto take = [&](int k, int c, DBuf<float4> &b, const float *src, size_t cnt) {
+    if (!on_device) { upload(b, src, cnt, s); return; }
+    if (cnt > size_t(INT_MAX)) throw CapacityError("lio_odom_process_batch_from_pp: a cloud exceeds 2^31 points");
+    b.reserve(std::max<size_t>(cnt, 1));
+    OdoTakeRec &r = sc.h_take[size_t(k)];
+    r.src[c] = reinterpret_cast<const float4 *>(src); r.dst[c] = b.p; r.n[c] = int(cnt);
+    max_take = std::max(max_take, cnt);
+  };
   for (int k = 0; k < n; ++k) {
     OdometryDev &d = *o[k];
     d.iterations_done_ = 0; d.last_num_sel_ = 0; d.last_kz_ = 0; d.es_trace_.clear();
-    upload(d.less_sharp_, less_sharp[k], n_ls[k], s);
-    upload(d.less_flat_, less_flat[k], n_lf[k], s);
+    take(k, 1, d.less_sharp_, less_sharp[k], n_ls[k]);
+    take(k, 3, d.less_flat_, less_flat[k], n_lf[k]);
     if (!d.inited_ || !d.enable_odom_) continue;   // :302-310; the packer
     OdomState &t = st[size_t(k)];
     t.T[0] = d.transform_es_.rot.x; t.T[1] = d.transform_es_.rot.y; t.T[2] = d.transform_es_.rot.z; t.T[3] = d.transform_es_.rot.w;
     t.T[4] = d.transform_es_.pos.x; t.T[5] = d.transform_es_.pos.y; t.T[6] = d.transform_es_.pos.z;
-    LIO_HIP(hipMemcpyAsync(d.d_state_.p, &t, sizeof(t), hipMemcpyHostToDevice, s));
+    if (on_device) { sc.h_take[size_t(k)].st = d.d_state_.p; sc.h_take[size_t(k)].init = t; }
+    else LIO_HIP(hipMemcpyAsync(d.d_state_.p, &t, sizeof(t), hipMemcpyHostToDevice, s));
     if (d.n_last_corner_ > 10 && d.n_last_surf_ > 100) {
-      upload(d.sharp_, sharp[k], n_sharp[k], s);
-      upload(d.flat_, flat[k], n_flat[k], s);
+      take(k, 0, d.sharp_, sharp[k], n_sharp[k]);
+      take(k, 2, d.flat_, flat[k], n_flat[k]);
       act.push_back(k);
     } else {
       idle.push_back(k);
     }
   }
+  if (on_device) {   // every sensor's clouds and state in one launch behind one upload
+    sc.d_take.reserve(size_t(n));
+    LIO_HIP(hipMemcpyAsync(sc.d_take.p, sc.h_take.data(), size_t(n) * sizeof(OdoTakeRec), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_ob_take, dim3(std::max(1, cdiv(max_take, 256)), 4, n), dim3(256), 0, s, sc.d_take.p);
+    LIO_HIP(hipGetLastError());
+  }
   const int nA = int(act.size()), nE = nA + int(idle.size());
 
   if (nE) {
-    // ---- the table: offsets first, then (after the grids, whose buffers may move while they are built) the kernels' arguments
+    // ---- the table: offsets first, then the previous clouds (for their bounds), then the grids (for their build and for the chain)
     sc.h_recs.assign(size_t(nE), OdoBatchRec{});
     size_t idx_total = 0, part_total = 0;
     int max_nq = 0, max_nb = 0, max_np = 0;
@@ -639,28 +749,78 @@ void OdometryDev::ProcessBatch(OdometryDev *const *o, int n, const float *const 
       if (idx_total > size_t(INT_MAX)) throw CapacityError("lio_odom_process_batch: the batch's index table exceeds 2^31 entries");
       max_nq = std::max(max_nq, nq); max_nb = std::max(max_nb, r.nb);
     }
+    sc.d_recs.reserve(size_t(nE));
+    bool any_shared = false;
+    int max_pts = 0;
     if (nA) {
-      // ---- the bounds of all 2 * nA previous clouds with one read-back and one wait, then every sensor's own grids, back to back
-      sc.d_bounds.reserve(size_t(2 * nA));
-      if (sc.h_bounds.n < size_t(2 * nA)) sc.h_bounds.alloc(size_t(2 * nA) + size_t(nA), hipHostMallocDefault);
-      for (int j = 0; j < nA; ++j) {
-        OdometryDev &d = *o[act[size_t(j)]];
-        launch_cloud_bounds(d.last_corner_.p, int(d.n_last_corner_), d.partial_c_, sc.d_bounds.p + 2 * j, s);
-        launch_cloud_bounds(d.last_surf_.p, int(d.n_last_surf_), d.partial_s_, sc.d_bounds.p + 2 * j + 1, s);
-      }
-      LIO_HIP(hipMemcpyAsync(sc.h_bounds.p, sc.d_bounds.p, size_t(2 * nA) * sizeof(VoxParams), hipMemcpyDeviceToHost, s));
-      LIO_HIP(hipStreamSynchronize(s));
-      const float cell = 5.0f * 1.0001f;
+      // ---- the bounds of all 2 * nA previous clouds: two launches over the table (which so far names the clouds alone), one read-back, one wait
+      size_t bpart_total = 0, pt_total = 0;
+      int max_bnb = 0;
       for (int j = 0; j < nA; ++j) {
         const int k = act[size_t(j)];
         OdometryDev &d = *o[k];
+        OdoBatchRec &r = sc.h_recs[size_t(j)];
+        if (d.n_last_corner_ + d.n_last_surf_ > size_t(INT_MAX)) throw CapacityError("lio_odom_process_batch: a sensor's previous clouds exceed 2^31 points");
+        r.a.sharp = d.sharp_.p; r.a.nc = int(n_sharp[k]); r.a.flat = d.flat_.p; r.a.ns = int(n_flat[k]);
+        r.a.lastc = d.last_corner_.p; r.a.nlc = int(d.n_last_corner_); r.a.lasts = d.last_surf_.p; r.a.nls = int(d.n_last_surf_);
+        for (int c = 0; c < 2; ++c) {
+          const int np = c ? r.a.nls : r.a.nlc;
+          r.b_nb[c] = std::max(1, std::min(cdiv(np, 256), 512));   // (launch_cloud_bounds)
+          r.b_off[c] = int(bpart_total);
+          bpart_total += size_t(r.b_nb[c]);
+          max_bnb = std::max(max_bnb, r.b_nb[c]); max_pts = std::max(max_pts, np);
+          pt_total += size_t(np);
+        }
+      }
+      if (pt_total > size_t(INT_MAX)) throw CapacityError("lio_odom_process_batch: the batch's previous clouds exceed 2^31 points");
+      sc.d_bounds.reserve(size_t(2 * nA));
+      if (sc.h_bounds.n < size_t(2 * nA)) sc.h_bounds.alloc(size_t(2 * nA) + size_t(nA), hipHostMallocDefault);
+      sc.d_bpartial.reserve(bpart_total * 8);
+      LIO_HIP(hipMemcpyAsync(sc.d_recs.p, sc.h_recs.data(), size_t(nA) * sizeof(OdoBatchRec), hipMemcpyHostToDevice, s));
+      hipLaunchKernelGGL(k_ob_bounds, dim3(max_bnb, 2 * nA), dim3(VOX_TILE), 0, s, sc.d_recs.p, sc.d_bpartial.p);
+      hipLaunchKernelGGL(k_ob_bounds_fold, dim3(2 * nA), dim3(VOX_TILE), 0, s, sc.d_recs.p, sc.d_bpartial.p, sc.d_bounds.p);
+      LIO_HIP(hipGetLastError());
+      LIO_HIP(hipMemcpyAsync(sc.h_bounds.p, sc.d_bounds.p, size_t(2 * nA) * sizeof(VoxParams), hipMemcpyDeviceToHost, s));
+      LIO_HIP(hipStreamSynchronize(s));
+      // ---- the grids: every grid of at most LIO_ODOM_BATCH_GRID_CELLS_MAX cells gets a slice of the batch's tables and is built by the three
+      // launches below; a larger one is built by its sensor's own KnnGrid, as lio_odom_process builds it
+      const float cell = 5.0f * 1.0001f;
+      size_t cell_total = 0, pt_off = 0;
+      for (int j = 0; j < nA; ++j) {
+        OdometryDev &d = *o[act[size_t(j)]];
+        OdoBatchRec &r = sc.h_recs[size_t(j)];
         VoxParams *b = sc.h_bounds.p + 2 * j;
-        for (int c = 0; c < 2; ++c)
+        for (int c = 0; c < 2; ++c) {
           if (b[c].n_valid == 0)
             for (int e = 0; e < 3; ++e) b[c].mn[e] = b[c].mx[e] = 0.f;
-        d.grid_c_.build(d.last_corner_.p, d.n_last_corner_, b[0].mn, b[0].mx, cell, s);
-        d.grid_s_.build(d.last_surf_.p, d.n_last_surf_, b[1].mn, b[1].mx, cell, s);
-        sc.h_recs[size_t(j)].a = d.Args(n_sharp[k], n_flat[k]);
+          GridDesc &g = c ? r.a.gs : r.a.gc;
+          const int np = c ? r.a.nls : r.a.nlc;
+          g.n_points = np;
+          const size_t ncells = grid_extent(g, b[c].mn, b[c].mx, cell);
+          if (ncells > size_t(LIO_ODOM_BATCH_GRID_CELLS_MAX)) {
+            KnnGrid &own = c ? d.grid_s_ : d.grid_c_;
+            own.build(c ? r.a.lasts : r.a.lastc, size_t(np), b[c].mn, b[c].mx, cell, s);
+            r.g_pt[c] = -1;
+            continue;
+          }
+          r.g_pt[c] = int(pt_off); r.g_cell[c] = int(cell_total); r.g_ncells[c] = int(ncells);
+          pt_off += size_t(np); cell_total += ncells + 1;
+          any_shared = true;
+        }
+      }
+      if (cell_total > size_t(INT_MAX)) throw CapacityError("lio_odom_process_batch: the batch's cell tables exceed 2^31 entries");
+      sc.g_cells.reserve(std::max<size_t>(cell_total, 1));
+      if (sc.g_cnt.cap < cell_total || sc.g_cnt_dirty) {   // a fresh table starts zeroed; after that k_ob_cell_place leaves it zeroed
+        sc.g_cnt.reserve(std::max<size_t>(cell_total, 1));
+        LIO_HIP(hipMemsetAsync(sc.g_cnt.p, 0, sc.g_cnt.cap * sizeof(int), s));
+      }
+      sc.g_keys.reserve(std::max<size_t>(pt_off, 1)); sc.g_slot.reserve(std::max<size_t>(pt_off, 1)); sc.g_sorted.reserve(std::max<size_t>(pt_off, 1));
+      // (every buffer is in place: a grid's arguments are its slice of the cell table and the base of the shared sorted array)
+      for (int j = 0; j < nA; ++j) {
+        OdometryDev &d = *o[act[size_t(j)]];
+        OdoBatchRec &r = sc.h_recs[size_t(j)];
+        r.a.gc_sorted = r.g_pt[0] < 0 ? d.grid_c_.sorted() : sc.g_sorted.p; r.a.gc_cells = r.g_pt[0] < 0 ? d.grid_c_.cells() : sc.g_cells.p + r.g_cell[0];
+        r.a.gs_sorted = r.g_pt[1] < 0 ? d.grid_s_.sorted() : sc.g_sorted.p; r.a.gs_cells = r.g_pt[1] < 0 ? d.grid_s_.cells() : sc.g_cells.p + r.g_cell[1];
       }
       sc.d_idx.reserve(std::max<size_t>(idx_total, 1));
       if (idx_total) LIO_HIP(hipMemsetAsync(sc.d_idx.p, 0xFF, idx_total * sizeof(int), s));
@@ -672,8 +832,16 @@ void OdometryDev::ProcessBatch(OdometryDev *const *o, int n, const float *const 
         sc.mail_cap = cap;
       }
     }
-    sc.d_recs.reserve(size_t(nE));
     LIO_HIP(hipMemcpyAsync(sc.d_recs.p, sc.h_recs.data(), size_t(nE) * sizeof(OdoBatchRec), hipMemcpyHostToDevice, s));
+    if (any_shared) {   // count, scan, place: one launch each over all grids
+      sc.g_cnt_dirty = true;   // until k_ob_cell_place has been enqueued
+      hipLaunchKernelGGL(k_ob_cell_count, dim3(cdiv(max_pts, 256), 2 * nA), dim3(256), 0, s, sc.d_recs.p, sc.g_keys.p, sc.g_slot.p, sc.g_cnt.p);
+      hipLaunchKernelGGL(k_ob_cell_scan, dim3(2 * nA), dim3(SEG_SCAN_THREADS), 0, s, sc.d_recs.p, sc.g_cnt.p, sc.g_cells.p);
+      hipLaunchKernelGGL(k_ob_cell_place, dim3(cdiv(max_pts, 256), 2 * nA), dim3(256), 0, s, sc.d_recs.p, sc.g_keys.p, sc.g_slot.p, sc.g_cells.p, sc.g_sorted.p,
+                         sc.g_cnt.p);
+      LIO_HIP(hipGetLastError());
+      sc.g_cnt_dirty = false;
+    }
 
     if (nA) {
       // ---- OdometryDev::Process's loop over the table: a peek where iter % 5 == 0 ends it only when EVERY sensor has converged (one that

@@ -6,6 +6,7 @@
 #pragma once
 #include <chrono>
 #include <cstdint>
+#include <stdexcept>
 #include <vector>
 
 #include "../../include/lio_c.h"
@@ -78,6 +79,20 @@ class PointProcessorDev {
   // device-resident results (valid until the next Process)
   const float4 *d_less_flat() const { return less_flat_.p + size_t(sel_) * pts_stride_; }
   size_t n_less_flat() const { return size_t(counts_.n_less_flat); }
+  // a process call has completed and its sweeps have results (false: never processed, or the last launch ended over capacity)
+  bool has_results() const { return launched_ && !in_flight_ && !over_capacity_; }
+  // sweep k's sharp, less-sharp, flat and less-flat clouds where the last launch left them on the device, and their counts (what
+  // Count / GetCloud answer once SelectSweep(k) has run); nothing of the processor changes
+  void DeviceClouds(int k, const float4 *src[4], size_t n[4]) const {
+    for (int c = 0; c < 4; ++c) { src[c] = nullptr; n[c] = 0; }
+    if (last_empty_ || over_capacity_ || !processed_) return;   // (SelectSweep: every count reads zero)
+    if (k < 0 || k >= nsw_) throw std::runtime_error("PointProcessor: no such sweep in the last batch");
+    const PPDeviceCounts &c = *reinterpret_cast<const PPDeviceCounts *>(h_record(k));
+    for (int w = 1; w <= 3; ++w) { src[w - 1] = class_cloud_[w].p + size_t(k) * cls_stride_; n[w - 1] = size_t(c.n_class[w]); }
+    src[3] = less_flat_.p + size_t(k) * pts_stride_; n[3] = size_t(c.n_less_flat);
+    for (int w = 0; w < 4; ++w)
+      if (n[w] > (w < 3 ? cls_stride_ : pts_stride_)) throw std::runtime_error("PointProcessor: a cloud's count exceeds its storage");
+  }
   float StartOri();   // start_ori_ of the selected sweep of the last Process (one small D2H unless infer_start_ori already fetched it)
 
  private:
@@ -107,6 +122,7 @@ class PointProcessorDev {
   DBuf<float> azi_, curv_, start_ori_dev_;   // start_ori_dev_: 2 probes per sweep, then one override per sweep
   StartOriFilter start_ori_filter_;
   bool processed_ = false, start_ori_known_ = false, in_flight_ = false;
+  bool launched_ = false;              // a launch has been made (an empty one too: it completes with every count zero)
   std::chrono::steady_clock::time_point t_begin_{};
   DBuf<uint32_t> keys_;
   DBuf<int> ring_total_;

@@ -851,6 +851,7 @@ void PointProcessorDev::ProcessLaunch(const float *xyzi, size_t n, const uint16_
 void PointProcessorDev::ProcessLaunchBatch(const float *const *xyzi, const uint16_t *const *ring, const size_t *n, int B, bool on_device,
                                            StartOriFilter *const *filters) {
   if (in_flight_) ProcessFinish();
+  launched_ = true;
   std::memset(&counts_, 0, sizeof(counts_));
   std::fill(ring_offsets_.begin(), ring_offsets_.end(), 0);
   size_t n_max = 0;

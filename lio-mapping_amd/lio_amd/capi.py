@@ -300,6 +300,11 @@ _ODOM_BATCH_SIGS = {
                                          _c_float_pp, _c_size_p, C.POINTER(TransformF), C.POINTER(TransformF), c_int32_p, c_int32_p]),
 }
 ODOM_BATCH_MAX_SENSORS = 1024   # LIO_ODOM_BATCH_MAX_SENSORS
+# include/lio_frontend_batch.h: the batched odometry fed from the feature extraction on the device (the product only, attached like _EXT_SIGS)
+_FRONTEND_SIGS = {
+    "lio_odom_process_batch_from_pp": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.POINTER(TransformF), C.POINTER(TransformF),
+                                                 c_int32_p, c_int32_p]),
+}
 
 
 def _dp(a):
@@ -350,7 +355,7 @@ class LioLib:
         self.backend = self.dll.lio_backend().decode()
         self.has_ext = self.backend.startswith("hip")
         if self.has_ext:
-            for name, (res, args) in list(_EXT_SIGS.items()) + list(_FULL_SIGS.items()) + list(_ODOM_BATCH_SIGS.items()):
+            for name, (res, args) in list(_EXT_SIGS.items()) + list(_FULL_SIGS.items()) + list(_ODOM_BATCH_SIGS.items()) + list(_FRONTEND_SIGS.items()):
                 fn = getattr(self.dll, name)
                 fn.restype = res
                 fn.argtypes = args
@@ -962,6 +967,23 @@ class PointOdometry:
         Ts, Te = (TransformF * n)(), (TransformF * n)()
         it, ns = np.zeros(n, np.int32), np.zeros(n, np.int32)
         _chk(lib.dll.lio_odom_process_batch(H, n, *args, Ts, Te, it.ctypes.data_as(c_int32_p), ns.ctypes.data_as(c_int32_p)), "lio_odom_process_batch")
+        return [dict(T_sum=Ts[k].to_np(), T_es=Te[k].to_np(), iterations=int(it[k]), num_selected=int(ns[k])) for k in range(n)]
+
+    @staticmethod
+    def process_batch_from_pp(handles, processors):
+        """lio_odom_process_batch_from_pp (include/lio_frontend_batch.h): process_batch with the four clouds of handles[k] taken on the
+        device from the last sweep of the PointProcessor processors[k] (one processor may feed several handles).  -> what process_batch
+        returns."""
+        n = len(handles)
+        if n < 1 or len(processors) != n:
+            raise LioError("process_batch_from_pp: one processor per handle, at least one handle")
+        lib = handles[0].lib
+        H = (C.c_void_p * n)(*[h.h for h in handles])
+        P = (C.c_void_p * n)(*[p.h for p in processors])
+        Ts, Te = (TransformF * n)(), (TransformF * n)()
+        it, ns = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        _chk(lib.dll.lio_odom_process_batch_from_pp(H, P, n, Ts, Te, it.ctypes.data_as(c_int32_p), ns.ctypes.data_as(c_int32_p)),
+             "lio_odom_process_batch_from_pp")
         return [dict(T_sum=Ts[k].to_np(), T_es=Te[k].to_np(), iterations=int(it[k]), num_selected=int(ns[k])) for k in range(n)]
 
     def iteration_trace(self):

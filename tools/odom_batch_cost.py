@@ -10,6 +10,14 @@ min - max over the steps after the warm-up; a GPU is required.
 
 --parent-lib PATH additionally times lio_odom_process ALONE of this tree against another build of the product (the parent commit's
 liblio_hip.so) on the same sweeps, alternating, the order swapped every pair: what the shared device bodies cost the single path.
+
+--frontend times instead what feeding the batch from the PointProcessor on the device buys (include/lio_frontend_batch.h).  B processors
+take the sweep of the step through ONE lio_pp_process_batch (not timed); then, alternating as above and with equal bits asserted at
+every step:
+  (a) lio_pp_get_cloud x 4 per sensor, then lio_odom_process_batch      the route without the hand-over
+  (b) lio_odom_process_batch_from_pp
+and, with --parent-lib,
+  (c) the host-fed lio_odom_process_batch of this tree against the other build's: what the segmented grid build changes for it.
 """
 import argparse
 import json
@@ -98,16 +106,88 @@ def measure_parent(hip, parent, kind, pair, steps):
     return dict(what="single_vs_parent", kind=kind, steps_measured=steps, this_tree_ms=_stats(t_here), parent_ms=_stats(t_there))
 
 
-def load_parent(path):
-    """another build of the product, which may lack lio_odom_process_batch"""
+def measure_frontend(hip, kind, B, steps):
+    """routes (a) and (b) on B sensors that read B pooled processors"""
+    from lio_amd import capi, synth
+
+    sweeps, _, lid = synth.make_sweeps(kind, 2)
+    pps = [capi.PointProcessor(hip, lid.lower_deg, lid.upper_deg, lid.rings) for _ in range(B)]
+
+    def feed(k):
+        if B > 1:
+            capi.PointProcessor.process_batch(pps, [sweeps[k % 2]] * B)
+        else:
+            pps[0].process(sweeps[k % 2])
+
+    def fetch():
+        return [[pp.cloud(w) for w in (1, 2, 3, 4)] for pp in pps]
+
+    feed(0)
+    first = fetch()
+    via_host, via_dev = [[capi.PointOdometry(hip, 0.1, 2, 25, False) for _ in range(B)] for _ in range(2)]
+    for od, cl in zip(via_host + via_dev, first + first):
+        od.process(*cl)
+    t_a, t_b, its = [], [], []
+    for k in range(WARMUP + steps):
+        feed(k + 1)
+
+        def run_a():
+            return capi.PointOdometry.process_batch(via_host, fetch())
+
+        def run_b():
+            return capi.PointOdometry.process_batch_from_pp(via_dev, pps)
+
+        if k % 2:
+            (ra, a), (rb, b) = _ms(run_a), _ms(run_b)
+        else:
+            (rb, b), (ra, a) = _ms(run_b), _ms(run_a)
+        for x, y in zip(ra, rb):
+            assert x["T_es"][0].tobytes() == y["T_es"][0].tobytes() and x["T_es"][1].tobytes() == y["T_es"][1].tobytes() and x["iterations"] == y["iterations"]
+            assert x["T_sum"][0].tobytes() == y["T_sum"][0].tobytes() and x["T_sum"][1].tobytes() == y["T_sum"][1].tobytes()
+        if k >= WARMUP:
+            t_a.append(a), t_b.append(b), its.append(ra[0]["iterations"])
+    return dict(what="frontend", kind=kind, B=B, steps_measured=steps, queries=int(len(first[0][0]) + len(first[0][2])), iterations=int(np.median(its)),
+                get_cloud_then_batch_ms=_stats(t_a), from_pp_ms=_stats(t_b), ratio=round(float(np.median(t_a) / np.median(t_b)), 3))
+
+
+def measure_batch_parent(hip, parent, kind, pair, B, steps):
+    """route (c): one host-fed lio_odom_process_batch of B sensors, this tree against another build"""
     from lio_amd import capi
 
-    sigs = dict(capi._ODOM_BATCH_SIGS)
-    capi._ODOM_BATCH_SIGS.clear()
+    here, there = _sensors(hip, pair, B), _sensors(parent, pair, B)
+    t_here, t_there = [], []
+    for k in range(WARMUP + steps):
+        cl = [pair[(k + 1) % 2]] * B
+        if k % 2:
+            (ra, a), (rb, b) = _ms(lambda: capi.PointOdometry.process_batch(here, cl)), _ms(lambda: capi.PointOdometry.process_batch(there, cl))
+        else:
+            (rb, b), (ra, a) = _ms(lambda: capi.PointOdometry.process_batch(there, cl)), _ms(lambda: capi.PointOdometry.process_batch(here, cl))
+        for x, y in zip(ra, rb):
+            assert x["T_es"][0].tobytes() == y["T_es"][0].tobytes() and x["T_es"][1].tobytes() == y["T_es"][1].tobytes() and x["iterations"] == y["iterations"]
+        if k >= WARMUP:
+            t_here.append(a), t_there.append(b)
+    return dict(what="batch_vs_parent", kind=kind, B=B, steps_measured=steps, this_tree_ms=_stats(t_here), parent_ms=_stats(t_there))
+
+
+def load_parent(path):
+    """another build of the product, which may lack the calls of the product-only headers that came after it"""
+    import ctypes
+
+    from lio_amd import capi
+
+    dll = ctypes.CDLL(path)
+    tables = [capi._ODOM_BATCH_SIGS, capi._FRONTEND_SIGS]
+    saved = [dict(t) for t in tables]
+    for t in tables:
+        for name in list(t):
+            if not hasattr(dll, name):
+                del t[name]
     try:
         return capi.LioLib(path)
     finally:
-        capi._ODOM_BATCH_SIGS.update(sigs)
+        for t, s in zip(tables, saved):
+            t.clear()
+            t.update(s)
 
 
 def main():
@@ -116,6 +196,7 @@ def main():
     ap.add_argument("--batches", default="1,8,64")
     ap.add_argument("--kinds", default="indoor,outdoor")
     ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--frontend", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert args.steps >= 8, "medians over at least 8 steps"
@@ -127,7 +208,15 @@ def main():
     hip = capi.load_hip()
     parent = load_parent(args.parent_lib) if args.parent_lib else None
     results = []
-    for kind in args.kinds.split(","):
+    for kind in args.kinds.split(",") if args.frontend else []:
+        pair = sweep_pair(hip, kind)
+        for B in [int(b) for b in args.batches.split(",") if b]:
+            results.append(measure_frontend(hip, kind, B, args.steps))
+            print(json.dumps(results[-1]), flush=True)
+            if parent is not None:
+                results.append(measure_batch_parent(hip, parent, kind, pair, B, args.steps))
+                print(json.dumps(results[-1]), flush=True)
+    for kind in args.kinds.split(",") if not args.frontend else []:
         pair = sweep_pair(hip, kind)
         for B in [int(b) for b in args.batches.split(",") if b]:
             results.append(measure_batch(hip, kind, pair, B, args.steps))
