@@ -101,6 +101,94 @@ int lio_odom_correspondences(const float *sharp_xyzi, size_t n_sharp, const floa
                              int32_t *corner_idx /* n_sharp x 2 */, int32_t *surf_idx /* n_flat x 3 */,
                              float *sel_out /* (n_sharp + n_flat) x 3, sharp first */);
 
+/* ---- The 6x6 Gauss-Newton loops from the rows onward.  Every pose of the product passes through one of three loops — scan-to-scan
+ * odometry (csrc/odometry.hip: k_odo_rows, k_odo_update, and the batch's k_ob_*), scan-to-map and the keyframe batch
+ * (csrc/cloud_kernels.hip: k_odom_rows / k_kf_rows with k_odom_update / k_kf_update) and the estimator's newest-frame loop (k_odom_round,
+ * k_odom_update_wide, and k_bw_odom_round / k_bw_odom_update of the batched windows) — and all of them form fp32 rows (A | b) per selected
+ * residual, add a_i a_j, a_i b and a count into 28 fp64 sums through a chain of folds, and run one serial step on the sums.  The sums
+ * are laid out as the upper triangle of A^T A row by row (21), A^T b (6), the row count (1). */
+
+/* The state a step works on: csrc/cloud_kernels.h OdomState, word for word. */
+typedef struct {
+  float T[8];          /* qx qy qz qw px py pz, and a pad; the scan-to-scan step (family 1) leaves float(rows selected) in the pad */
+  int32_t converged;   /* set by the abort test; never cleared */
+  int32_t iters;       /* iter + 1 after every step, also after one that had too few rows */
+  int32_t degenerate;  /* kz > 0, decided at iter 0 and carried */
+  int32_t kz;          /* eigenvalues of A^T A below the family's threshold at iter 0: the leading kz components of the step are masked */
+  int32_t nsel;        /* rows selected: int(sums[27]) */
+} lio_gn_state;
+
+/* The rows of the scan-to-map family (csrc/cloud_device.h: odom_row_form, the function odom_row_accumulate — k_odom_rows, k_kf_rows,
+ * k_odom_round and the batched windows — forms every row with) and the partials of ONE production rows launch.
+ *   form            the production `b_from_coef`: 0 estimator (b = -(w . (R p + t) + c.w)), 1 scan-to-map (b = -c.w), 2 MapBuilder
+ *                   (b = -c.w and the rotation columns times R^-1 diag(5e-3, 5e-3, 1)).  Any other value: LIO_ERR_ARG.
+ *   stack_xyzi      m queries in the sensor frame (intensity unused); valid[m]; coeff[m * 4] = (w, c.w) as a fit returns them
+ *   T               the pose the rows are formed at; a non-finite component is LIO_ERR_ARG
+ *   ok_out[m]       1 where a row exists: valid != 0
+ *   rows_out[m * 7] a0 .. a5, b in fp32; zeros where ok is 0.  a = (-(w^T R skew(p)) [form 2: R^-1 diag(5e-3, 5e-3, 1)], w)
+ *   nb_out          odom_rows_blocks(m), the block count production launches with
+ *   partials_out    nb x 28 doubles; nb never exceeds 256, and the caller provides 256 x 28 (m == 0: one row of zeros)
+ * Product: ONE launch through launch_odom_rows with the production block count; rows_out comes from a separate one-query-per-lane
+ * kernel that calls the same odom_row_form.  Oracle: the row function its own loops (Estimator::CalculateLaserOdom,
+ * PointMapping::OptimizeTransformTobeMapped) call, serially; nb_out = 1 and its partial is one row of plain fp64 sums of the fp32
+ * products.  A null required pointer (an input may be null when m is 0): LIO_ERR_ARG. */
+int lio_gn_rows_map(int form, const float *stack_xyzi, size_t m, const uint8_t *valid, const float *coeff, const lio_transform_f *T,
+                    uint8_t *ok_out, float *rows_out, int32_t *nb_out, double *partials_out);
+
+/* The rows of the scan-to-scan loop (csrc/odometry.hip: odo_row_coeff and odo_row_of, the two functions k_odo_rows and the batch's k_ob_rows form every row
+ * with) and the partials of ONE production rows launch, on caller-given clouds and correspondences: PointOdometry.cc:391-435 (edge
+ * coefficients), :497-531 (plane coefficients), A.7 (the weight s, 1 before iteration 5), :548-571 (the row).  Clouds, transform_es,
+ * scan_period and no_deskew as in lio_odom_correspondences; corner_idx (n_sharp x 2) and surf_idx (n_flat x 3) as it returns them or as
+ * the caller states them.
+ *   a sharp query has a row when its second index is >= 0, s > 0.1 and the distance ld2 != 0; a flat query when its second and third
+ *   are >= 0, s > 0.1 and pd2 != 0 (a collinear triple gives a non-finite pd2, which passes `!= 0`, and a non-finite row: the
+ *   behaviour of the reference program, kept)
+ *   ok_out[n_sharp + n_flat], rows_out[(n_sharp + n_flat) * 7] (r0 .. r5, b; zeros where ok is 0), sharp first
+ *   nb_out = max(1, min(ceil(nq / 256), 64)), partials_out nb x 28 doubles; the caller provides 64 x 28
+ * An index outside [-1, size of its cloud), a second or third index without a closest one (the search never returns that, and the rows
+ * read the closest point whenever the others exist; so -1 in the closest slot is a case only together with -1 in the others, never on
+ * its own), a null required pointer, a non-finite transform, a scan_period that is not positive
+ * and finite, or a negative iter: LIO_ERR_ARG.
+ * Product: uploads into a device object of its own, launches k_odo_rows ONCE through the statement Process uses; rows_out comes from a
+ * separate one-query-per-lane kernel that calls the same two functions.  Oracle: the functions its own Process loop calls, serially;
+ * nb_out = 1 and one partial of plain fp64 sums of the fp32 products. */
+int lio_gn_rows_odom(const float *sharp_xyzi, size_t n_sharp, const float *flat_xyzi, size_t n_flat, const float *last_corner_xyzi,
+                     size_t n_last_corner, const float *last_surf_xyzi, size_t n_last_surf, const int32_t *corner_idx, const int32_t *surf_idx,
+                     const lio_transform_f *transform_es, float scan_period, int no_deskew, int iter, uint8_t *ok_out, float *rows_out,
+                     int32_t *nb_out, double *partials_out);
+
+/* The fixed-order fold of `nblocks` partials (28 doubles each) into sums_out[28].
+ *   wide 0   reduce_partials28 (csrc/cloud_kernels.h) on a 256-thread block: k_odom_update, k_kf_update, k_odo_update, k_ob_update
+ *   wide 1   fold_partials28_wide (csrc/cloud_device.h) on a 1024-thread block: k_odom_update_wide, k_bw_odom_update
+ * One launch that calls the production function and copies the 28 shared sums out.  nblocks == 0 gives zeros.  The oracle adds the rows
+ * serially, ascending.  A null pointer (partials may be null when nblocks is 0), a negative nblocks or another `wide`: LIO_ERR_ARG. */
+int lio_gn_fold(const double *partials, int nblocks, int wide, double *sums_out);
+
+/* The serial step behind the sums: fp32 A^T A, A^T b <- sums; qr_solve<float, 6, 6>; at iter 0 kz = count_eigs_below(threshold) and
+ * degenerate = kz > 0; the leading kz components of X masked; t += X[3..5], q = q * deltaQ(X[0..2]) (left_update: deltaQ * q); a
+ * non-finite t component resets to 0; converged when the rotation in degrees and 100 |X[3..5]| are both below the abort value.
+ *   family 0   odom_update_from_sums (csrc/cloud_device.h): threshold 100, abort at 0.05; a step with min_rows > 0 and fewer rows leaves
+ *              T untouched and sets nsel and iters alone
+ *   family 1   odo_update_step (csrc/odometry.hip): threshold 10, abort at 0.1, fewer than 10 rows leave T untouched; min_rows and
+ *              left_update must be 0; T[7] = float(rows), which the hook also reports in nsel
+ * Product: one launch, thread 0 calls the production function on a copy of state_in.  Oracle: the statements after the sums of its
+ * own loops (GaussNewtonStep, oracle/liomath.h), which accumulate in fp32 and so take float(sums).  Null pointers, another family, a
+ * negative iter or min_rows, or a non-finite state_in->T[0..6]: LIO_ERR_ARG (non-finite SUMS are a case, not an error). */
+int lio_gn_step(int family, const double *sums, const lio_gn_state *state_in, int iter, int min_rows, int left_update,
+                lio_gn_state *state_out);
+
+/* Round 0, keep 0, of the estimator's newest-frame loop through launch_odom_round: search + fit + rows per block (k_odom_round<4> or
+ * <8>) and fold + step (k_odom_update_wide).  The grid is built over the map as lio_calculate_features builds it.
+ *   lanes_per_query   4 or 8 (what the product launches); anything else is LIO_ERR_ARG
+ *   nb_out            odom_round_blocks(m, lanes_per_query) = max(1, ceil(m * lanes_per_query / 256)); partials_out holds nb x 28
+ *                     doubles, and the caller provides that many
+ *   state_out         the state after k_odom_update_wide, started from T with every other word zero
+ * The oracle runs one pass of its own loop body (CalculateFeatures, rows, GaussNewtonStep): nb_out = 1, one partial.  m == 0 launches
+ * nothing: state_out is the initial state and nb_out = 0.  Rounds with kept features (keep = 1, round > 0) are covered end to end only
+ * (tests/test_gpu_parity.py).  Null required pointers, a non-finite T or thresholds that are not positive and finite: LIO_ERR_ARG. */
+int lio_gn_round(const float *map_xyzi, size_t n_map, const float *stack_xyzi, size_t m, const lio_transform_f *T, float min_match_sq_dis,
+                 float min_plane_dis, int lanes_per_query, int32_t *nb_out, double *partials_out, lio_gn_state *state_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -611,6 +611,9 @@ struct Scratch {
   DBuf<int32_t> idx;
   DBuf<float> sqd, nbr;
   DBuf<float> bounds;
+  DBuf<double> gn_partials, gn_sums;   // the Gauss-Newton hooks
+  DBuf<OdomState> gn_state;
+  DBuf<float> gn_rows;
 };
 static Scratch &scratch() {
   static thread_local Scratch sc;
@@ -732,6 +735,145 @@ int lio_odom_correspondences(const float *sharp, size_t n_sharp, const float *fl
   return guarded([&] {
     OdometryDev od(scan_period, 1, 1, no_deskew != 0);   // stateless: a device object of its own, gone on return
     od.Correspondences(sharp, n_sharp, flat, n_flat, last_corner, n_lc, last_surf, n_lsf, toT(*T), corner_idx, surf_idx, sel_out);
+    return LIO_OK;
+  });
+}
+
+// ---- the Gauss-Newton hooks (include/lio_test_hooks.h)
+static_assert(sizeof(lio_gn_state) == sizeof(OdomState) && offsetof(lio_gn_state, nsel) == offsetof(OdomState, nsel), "lio_gn_state is OdomState");
+static bool finite_T(const lio_transform_f *T) {
+  for (int k = 0; k < 4; ++k) if (!std::isfinite(T->q[k])) return false;
+  for (int k = 0; k < 3; ++k) if (!std::isfinite(T->p[k])) return false;
+  return true;
+}
+static OdomState state_at(const lio_transform_f *T) {
+  OdomState st{};
+  for (int k = 0; k < 4; ++k) st.T[k] = T->q[k];
+  for (int k = 0; k < 3; ++k) st.T[4 + k] = T->p[k];
+  return st;
+}
+
+int lio_gn_rows_map(int form, const float *stack, size_t m, const uint8_t *valid, const float *coeff, const lio_transform_f *T, uint8_t *ok_out,
+                    float *rows_out, int32_t *nb_out, double *partials_out) {
+  if (form < 0 || form > 2 || ((!stack || !valid || !coeff || !ok_out || !rows_out) && m) || !T || !nb_out || !partials_out) return LIO_ERR_ARG;
+  if (!finite_T(T)) return LIO_ERR_ARG;
+  if (m > size_t(INT_MAX) / 8) return LIO_ERR_CAPACITY;
+  return guarded([&] {
+    Scratch &sc = scratch();
+    const int M = int(m), nb = odom_rows_blocks(M);
+    sc.b.reserve(std::max<size_t>(m, 1)); sc.valid.reserve(std::max<size_t>(m, 1)); sc.coef.reserve(std::max<size_t>(m, 1));
+    sc.idx.reserve(std::max<size_t>((m + 3) / 4, 1));   // ok_out, as bytes
+    sc.gn_rows.reserve(std::max<size_t>(m * 7, 1)); sc.gn_partials.reserve(size_t(nb) * 28); sc.gn_state.reserve(1);
+    const OdomState st = state_at(T);
+    LIO_HIP(hipMemcpyAsync(sc.gn_state.p, &st, sizeof(st), hipMemcpyHostToDevice, sc.s));
+    LIO_HIP(hipMemsetAsync(sc.gn_partials.p, 0, size_t(nb) * 28 * sizeof(double), sc.s));
+    if (m) {
+      LIO_HIP(hipMemcpyAsync(sc.b.p, stack, m * sizeof(float4), hipMemcpyHostToDevice, sc.s));
+      LIO_HIP(hipMemcpyAsync(sc.valid.p, valid, m, hipMemcpyHostToDevice, sc.s));
+      LIO_HIP(hipMemcpyAsync(sc.coef.p, coeff, m * sizeof(float4), hipMemcpyHostToDevice, sc.s));
+      // what production launches: M slots over the M points, odom_rows_blocks(M) blocks (csrc/mapping.hip, csrc/estimator.hip)
+      launch_odom_rows(sc.b.p, M, M, sc.valid.p, sc.coef.p, sc.gn_state.p, sc.gn_partials.p, nb, sc.s, form);
+      uint8_t *ok_dev = reinterpret_cast<uint8_t *>(sc.idx.p);
+      launch_gn_rows_map(sc.b.p, M, sc.valid.p, sc.coef.p, sc.gn_state.p, form, ok_dev, sc.gn_rows.p, sc.s);
+      LIO_HIP(hipMemcpyAsync(ok_out, ok_dev, m, hipMemcpyDeviceToHost, sc.s));
+      LIO_HIP(hipMemcpyAsync(rows_out, sc.gn_rows.p, m * 7 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
+    }
+    LIO_HIP(hipMemcpyAsync(partials_out, sc.gn_partials.p, size_t(nb) * 28 * sizeof(double), hipMemcpyDeviceToHost, sc.s));
+    LIO_HIP(hipStreamSynchronize(sc.s));
+    *nb_out = nb;
+    return LIO_OK;
+  });
+}
+
+// every stated correspondence lies in its cloud, and a second / third entry comes with a closest one (the search gives all -1 without it; the
+// rows read the closest point whenever the others exist)
+static bool gn_indices_ok(const int32_t *idx, size_t n, int per, size_t n_last) {
+  for (size_t i = 0; i < n; ++i) {
+    bool others = false;
+    for (int k = 0; k < per; ++k) {
+      const int32_t v = idx[i * per + k];
+      if (v < -1 || (v >= 0 && size_t(v) >= n_last)) return false;
+      if (k > 0 && v >= 0) others = true;
+    }
+    if (others && idx[i * per] < 0) return false;
+  }
+  return true;
+}
+int lio_gn_rows_odom(const float *sharp, size_t n_sharp, const float *flat, size_t n_flat, const float *last_corner, size_t n_lc, const float *last_surf,
+                     size_t n_lsf, const int32_t *corner_idx, const int32_t *surf_idx, const lio_transform_f *T, float scan_period, int no_deskew, int iter,
+                     uint8_t *ok_out, float *rows_out, int32_t *nb_out, double *partials_out) {
+  if ((!sharp && n_sharp) || (!flat && n_flat) || (!last_corner && n_lc) || (!last_surf && n_lsf) || (!corner_idx && n_sharp) || (!surf_idx && n_flat) ||
+      ((!ok_out || !rows_out) && (n_sharp + n_flat)) || !T || !nb_out || !partials_out || iter < 0)
+    return LIO_ERR_ARG;
+  if (!(scan_period > 0) || !std::isfinite(scan_period) || !finite_T(T)) return LIO_ERR_ARG;
+  if (n_sharp + n_flat > size_t(INT_MAX) / 8 || n_lc > size_t(INT_MAX) || n_lsf > size_t(INT_MAX)) return LIO_ERR_CAPACITY;
+  if (!gn_indices_ok(corner_idx, n_sharp, 2, n_lc) || !gn_indices_ok(surf_idx, n_flat, 3, n_lsf)) return LIO_ERR_ARG;
+  return guarded([&] {
+    OdometryDev od(scan_period, 1, 1, no_deskew != 0);   // stateless: a device object of its own, gone on return
+    od.Rows(sharp, n_sharp, flat, n_flat, last_corner, n_lc, last_surf, n_lsf, corner_idx, surf_idx, toT(*T), iter, ok_out, rows_out, nb_out, partials_out);
+    return LIO_OK;
+  });
+}
+
+int lio_gn_fold(const double *partials, int nblocks, int wide, double *sums_out) {
+  if (nblocks < 0 || (!partials && nblocks) || !(wide == 0 || wide == 1) || !sums_out) return LIO_ERR_ARG;
+  if (nblocks > INT_MAX / 32) return LIO_ERR_CAPACITY;   // reduce_partials28 indexes b * 28 + c in int
+  return guarded([&] {
+    Scratch &sc = scratch();
+    sc.gn_partials.reserve(std::max<size_t>(size_t(nblocks) * 28, 1)); sc.gn_sums.reserve(28);
+    if (nblocks) LIO_HIP(hipMemcpyAsync(sc.gn_partials.p, partials, size_t(nblocks) * 28 * sizeof(double), hipMemcpyHostToDevice, sc.s));
+    launch_gn_fold(sc.gn_partials.p, nblocks, wide, sc.gn_sums.p, sc.s);
+    LIO_HIP(hipMemcpyAsync(sums_out, sc.gn_sums.p, 28 * sizeof(double), hipMemcpyDeviceToHost, sc.s));
+    LIO_HIP(hipStreamSynchronize(sc.s));
+    return LIO_OK;
+  });
+}
+
+int lio_gn_step(int family, const double *sums, const lio_gn_state *state_in, int iter, int min_rows, int left_update, lio_gn_state *state_out) {
+  if (!(family == 0 || family == 1) || !sums || !state_in || !state_out || iter < 0 || min_rows < 0) return LIO_ERR_ARG;
+  if (family == 1 && (min_rows != 0 || left_update != 0)) return LIO_ERR_ARG;
+  for (int k = 0; k < 7; ++k) if (!std::isfinite(state_in->T[k])) return LIO_ERR_ARG;
+  return guarded([&] {
+    Scratch &sc = scratch();
+    sc.gn_sums.reserve(28); sc.gn_state.reserve(1);
+    LIO_HIP(hipMemcpyAsync(sc.gn_sums.p, sums, 28 * sizeof(double), hipMemcpyHostToDevice, sc.s));
+    LIO_HIP(hipMemcpyAsync(sc.gn_state.p, state_in, sizeof(OdomState), hipMemcpyHostToDevice, sc.s));
+    if (family == 0) launch_gn_step(sc.gn_sums.p, sc.gn_state.p, iter, min_rows, left_update ? 1 : 0, sc.s);
+    else launch_gn_odo_step(sc.gn_sums.p, sc.gn_state.p, iter, sc.s);
+    LIO_HIP(hipMemcpyAsync(state_out, sc.gn_state.p, sizeof(OdomState), hipMemcpyDeviceToHost, sc.s));
+    LIO_HIP(hipStreamSynchronize(sc.s));
+    return LIO_OK;
+  });
+}
+
+int lio_gn_round(const float *map, size_t n_map, const float *stack, size_t m, const lio_transform_f *T, float mm, float mp, int lpq, int32_t *nb_out,
+                 double *partials_out, lio_gn_state *state_out) {
+  if ((!map && n_map) || (!stack && m) || !T || !nb_out || !partials_out || !state_out || !(lpq == 4 || lpq == 8)) return LIO_ERR_ARG;
+  if (!finite_T(T) || !(mm > 0) || !std::isfinite(mm) || !(mp > 0) || !std::isfinite(mp)) return LIO_ERR_ARG;
+  if (m > size_t(INT_MAX) / 8 || n_map > size_t(INT_MAX)) return LIO_ERR_CAPACITY;
+  return guarded([&] {
+    Scratch &sc = scratch();
+    const int M = int(m), nb = M > 0 ? odom_round_blocks(M, lpq) : 0;
+    sc.a.reserve(std::max<size_t>(n_map, 1)); sc.b.reserve(std::max<size_t>(m, 1));
+    sc.valid.reserve(std::max<size_t>(m, 1)); sc.coef.reserve(std::max<size_t>(m, 1)); sc.score.reserve(std::max<size_t>(m, 1));
+    sc.gn_partials.reserve(std::max<size_t>(size_t(nb) * 28, 1)); sc.gn_state.reserve(1);
+    if (n_map) LIO_HIP(hipMemcpyAsync(sc.a.p, map, n_map * sizeof(float4), hipMemcpyHostToDevice, sc.s));
+    if (m) LIO_HIP(hipMemcpyAsync(sc.b.p, stack, m * sizeof(float4), hipMemcpyHostToDevice, sc.s));
+    const OdomState st = state_at(T);
+    LIO_HIP(hipMemcpyAsync(sc.gn_state.p, &st, sizeof(st), hipMemcpyHostToDevice, sc.s));
+    float mn[3], mx[3];   // the grid of lio_calculate_features
+    host_bounds(map, n_map, mn, mx);
+    if (n_map == 0) { mn[0] = mn[1] = mn[2] = 0; mx[0] = mx[1] = mx[2] = 0; }
+    sc.grid.build(sc.a.p, n_map, mn, mx, knn_cell_edge(mm), sc.s);
+    FeatArgs fa{};
+    fa.nframes = 1; fa.max_M = M; fa.min_match_sq_dis = mm; fa.min_plane_dis = mp;
+    fa.fr[0].stack = sc.b.p; fa.fr[0].M = M; fa.fr[0].slot_off = 0; fa.fr[0].tf_index = 0;
+    launch_odom_round(fa, 0, 0, 0, sc.gn_state.p, sc.grid.sorted(), sc.grid.cells(), sc.grid.desc(), sc.valid.p, sc.coef.p, sc.score.p, sc.gn_partials.p, sc.s,
+                      nullptr, HostSignal(), lpq);
+    if (nb) LIO_HIP(hipMemcpyAsync(partials_out, sc.gn_partials.p, size_t(nb) * 28 * sizeof(double), hipMemcpyDeviceToHost, sc.s));
+    LIO_HIP(hipMemcpyAsync(state_out, sc.gn_state.p, sizeof(OdomState), hipMemcpyDeviceToHost, sc.s));
+    LIO_HIP(hipStreamSynchronize(sc.s));
+    *nb_out = nb;
     return LIO_OK;
   });
 }

@@ -582,12 +582,11 @@ __device__ __forceinline__ void features_block(const FeatFrame fr, const FeatSca
   if (MAPPING && abs_coef && res.ok) abs_coef[res.slot] = res.abs;
 }
 
-// one row of (mat_A | mat_B) of a selected feature, added to the 21 + 6 + 1 running sums (Estimator.cc:1272-1301)
-__device__ __forceinline__ void odom_row_accumulate(const float4 po, const float4 c, const Quat<float> &q, const Vec3<float> &t, const Mat3<float> &Rm,
-                                                    const Mat3<float> &Rinv, int b_from_coef, double (&acc)[28]) {
+// one row of (mat_A | mat_B) of a selected feature (Estimator.cc:1272-1301): a[6] and b.  Also called by the test hook lio_gn_rows_map.
+__device__ __forceinline__ void odom_row_form(const float4 po, const float4 c, const Quat<float> &q, const Vec3<float> &t, const Mat3<float> &Rm,
+                                              const Mat3<float> &Rinv, int b_from_coef, float (&a)[6], float &bb) {
   Vec3<float> p(po.x, po.y, po.z), w(c.x, c.y, c.z);
   Mat3<float> RS = Rm * skew(p);
-  float a[6];
   a[0] = -(w.x * RS(0, 0) + w.y * RS(1, 0) + w.z * RS(2, 0));
   a[1] = -(w.x * RS(0, 1) + w.y * RS(1, 1) + w.z * RS(2, 1));
   a[2] = -(w.x * RS(0, 2) + w.y * RS(1, 2) + w.z * RS(2, 2));
@@ -600,7 +599,10 @@ __device__ __forceinline__ void odom_row_accumulate(const float4 po, const float
   a[3] = w.x; a[4] = w.y; a[5] = w.z;
   Vec3<float> rp = rotate(q, p);
   float d2 = w.x * (rp.x + t.x) + w.y * (rp.y + t.y) + w.z * (rp.z + t.z) + c.w;
-  float bb = b_from_coef ? -c.w : -d2;
+  bb = b_from_coef ? -c.w : -d2;
+}
+// a row added to the 21 + 6 + 1 running sums
+__device__ __forceinline__ void odom_row_add(const float (&a)[6], const float bb, double (&acc)[28]) {
   int k = 0;
 #pragma unroll
   for (int r = 0; r < 6; ++r)
@@ -609,6 +611,12 @@ __device__ __forceinline__ void odom_row_accumulate(const float4 po, const float
 #pragma unroll
   for (int r = 0; r < 6; ++r) acc[21 + r] += double(a[r] * bb);
   acc[27] += 1.0;
+}
+__device__ __forceinline__ void odom_row_accumulate(const float4 po, const float4 c, const Quat<float> &q, const Vec3<float> &t, const Mat3<float> &Rm,
+                                                    const Mat3<float> &Rinv, int b_from_coef, double (&acc)[28]) {
+  float a[6], bb;
+  odom_row_form(po, c, q, t, Rm, Rinv, b_from_coef, a, bb);
+  odom_row_add(a, bb, acc);
 }
 
 
@@ -739,17 +747,9 @@ __device__ __forceinline__ double odom_round_block(const FeatScalars fs, FeatFra
 
 
 // fold of `nblocks` 28-double partials by a 1024-thread block (32 groups of rows b = g mod 32, ascending, then the group sums
-// ascending), followed by the update of odom_update_body
-// mail: a copy of the state in coherent pinned host memory, posted with the round's sequence number after every round (also
-// by the no-op rounds behind convergence), so the host's look at the convergence flag is a read of its own memory.
-__device__ __forceinline__ void odom_update_wide_block(const double *__restrict__ partials, int nblocks, OdomState *st, int iter, int min_rows,
-                                                      int left_update, OdomState *mail, const HostSignal &sig) {
-  if (st->converged) {
-    if (sig.flag && threadIdx.x < 64) post_host_mail(sig, mail, st, int(sizeof(OdomState) / 4), threadIdx.x);
-    return;
-  }
+// ascending) into ssum[0..27]; ends with a barrier.  Also called by the test hook lio_gn_fold.
+__device__ __forceinline__ void fold_partials28_wide(const double *__restrict__ partials, int nblocks, double *ssum /* shared, >= 28 */) {
   __shared__ double part[32][32];
-  __shared__ double ssum[28];
   const int c = threadIdx.x & 31, gq = threadIdx.x >> 5;
   double v0 = 0, v1 = 0, v2 = 0, v3 = 0;
   if (c < 28) {
@@ -787,6 +787,19 @@ __device__ __forceinline__ void odom_update_wide_block(const double *__restrict_
     ssum[threadIdx.x] = s2;
   }
   __syncthreads();
+}
+
+// fold_partials28_wide followed by the update of odom_update_from_sums
+// mail: a copy of the state in coherent pinned host memory, posted with the round's sequence number after every round (also
+// by the no-op rounds behind convergence), so the host's look at the convergence flag is a read of its own memory.
+__device__ __forceinline__ void odom_update_wide_block(const double *__restrict__ partials, int nblocks, OdomState *st, int iter, int min_rows,
+                                                      int left_update, OdomState *mail, const HostSignal &sig) {
+  if (st->converged) {
+    if (sig.flag && threadIdx.x < 64) post_host_mail(sig, mail, st, int(sizeof(OdomState) / 4), threadIdx.x);
+    return;
+  }
+  __shared__ double ssum[28];
+  fold_partials28_wide(partials, nblocks, ssum);
   odom_update_from_sums(ssum, st, iter, min_rows, left_update);
   if (sig.flag) {
     __syncthreads();   // thread 0's update of *st is visible to wave 0

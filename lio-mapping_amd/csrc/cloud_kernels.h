@@ -188,6 +188,15 @@ void launch_odom_round(const FeatArgs &a, int base_slot, int round, int keep, Od
                        uint8_t *valid, float4 *coef, float *score, double *partials, hipStream_t s, OdomState *mail = nullptr,
                        const HostSignal &sig = HostSignal(), int lpq = 8);
 
+// ---- the Gauss-Newton test hooks (include/lio_test_hooks.h)
+// the row of every slot on its own (7 floats: a0 .. a5, b; zeros where valid is 0), one query per lane through the row function of the rows kernels
+void launch_gn_rows_map(const float4 *stack, int m, const uint8_t *valid, const float4 *coef, const OdomState *st, int b_from_coef, uint8_t *ok_out,
+                        float *rows_out, hipStream_t s);
+// sums_out[28] (device) = reduce_partials28 on 256 threads (wide == 0) or fold_partials28_wide on 1024
+void launch_gn_fold(const double *partials, int nblocks, int wide, double *sums_out, hipStream_t s);
+// odom_update_from_sums on device sums and a device state, in place
+void launch_gn_step(const double *sums, OdomState *st, int iter, int min_rows, int left_update, hipStream_t s);
+
 // ---- batched keyframe refinement (config 5: B independent OptimizeMap / OptimizeTransformTobeMapped loops, MapBuilder.cc:624-1014,
 // PointMapping.cc:325-753).  Slots of keyframe k = [slot_off, slot_off + Mc) corner, then Ms surf, in one concatenated stack.
 struct KfDesc {

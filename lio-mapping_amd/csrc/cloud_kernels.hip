@@ -699,6 +699,57 @@ void launch_odom_round(const FeatArgs &a, int base_slot, int round, int keep, Od
   LIO_HIP(hipGetLastError());
 }
 
+// ---- the Gauss-Newton test hooks (include/lio_test_hooks.h): small kernels around the production device functions
+// lio_gn_rows_map: the row of every slot on its own, one query per lane, through the odom_row_form the rows kernels call; 7 floats per slot
+// (a0 .. a5, b), zeros and ok = 0 where valid is 0
+__global__ void __launch_bounds__(256) k_gn_rows_map(const float4 *__restrict__ stack, int m, const uint8_t *__restrict__ valid, const float4 *__restrict__ coef,
+                                                     const OdomState *__restrict__ st, int b_from_coef, uint8_t *__restrict__ ok_out,
+                                                     float *__restrict__ rows_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  Quat<float> q(st->T[3], st->T[0], st->T[1], st->T[2]);
+  Vec3<float> t(st->T[4], st->T[5], st->T[6]);
+  Mat3<float> Rm = toRot(q);
+  Mat3<float> Rinv = toRot(qinverse(q));
+  float a[6] = {0, 0, 0, 0, 0, 0}, bb = 0;
+  const bool ok = valid[i] != 0;
+  if (ok) odom_row_form(stack[i], coef[i], q, t, Rm, Rinv, b_from_coef, a, bb);
+  ok_out[i] = ok ? 1 : 0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) rows_out[size_t(i) * 7 + k] = a[k];
+  rows_out[size_t(i) * 7 + 6] = bb;
+}
+void launch_gn_rows_map(const float4 *stack, int m, const uint8_t *valid, const float4 *coef, const OdomState *st, int b_from_coef, uint8_t *ok_out,
+                        float *rows_out, hipStream_t s) {
+  if (m <= 0) return;
+  hipLaunchKernelGGL(k_gn_rows_map, dim3(cdiv(m, 256)), dim3(256), 0, s, stack, m, valid, coef, st, b_from_coef, ok_out, rows_out);
+  LIO_HIP(hipGetLastError());
+}
+// lio_gn_fold: one block of the size production folds with; the 28 shared sums go out as they stand
+__global__ void __launch_bounds__(256) k_gn_fold(const double *__restrict__ partials, int nblocks, double *__restrict__ sums_out) {
+  __shared__ double ssum[28];
+  reduce_partials28(partials, nblocks, ssum);
+  if (threadIdx.x < 28) sums_out[threadIdx.x] = ssum[threadIdx.x];
+}
+__global__ void __launch_bounds__(1024) k_gn_fold_wide(const double *__restrict__ partials, int nblocks, double *__restrict__ sums_out) {
+  __shared__ double ssum[28];
+  fold_partials28_wide(partials, nblocks, ssum);
+  if (threadIdx.x < 28) sums_out[threadIdx.x] = ssum[threadIdx.x];
+}
+void launch_gn_fold(const double *partials, int nblocks, int wide, double *sums_out, hipStream_t s) {
+  if (wide) hipLaunchKernelGGL(k_gn_fold_wide, dim3(1), dim3(1024), 0, s, partials, nblocks, sums_out);
+  else hipLaunchKernelGGL(k_gn_fold, dim3(1), dim3(256), 0, s, partials, nblocks, sums_out);
+  LIO_HIP(hipGetLastError());
+}
+// lio_gn_step, family 0: thread 0 of one wave runs odom_update_from_sums on the state in place
+__global__ void __launch_bounds__(64) k_gn_step(const double *__restrict__ sums, OdomState *st, int iter, int min_rows, int left_update) {
+  odom_update_from_sums(sums, st, iter, min_rows, left_update);
+}
+void launch_gn_step(const double *sums, OdomState *st, int iter, int min_rows, int left_update, hipStream_t s) {
+  hipLaunchKernelGGL(k_gn_step, dim3(1), dim3(64), 0, s, sums, st, iter, min_rows, left_update);
+  LIO_HIP(hipGetLastError());
+}
+
 // ------------------------------------------------------------------------------------------------
 // Batched keyframe refinement: B independent scan-to-map loops advance together, one launch per stage per round
 // ------------------------------------------------------------------------------------------------

@@ -32,6 +32,11 @@ class OdometryDev {
   // include/lio_test_hooks.h): corner_idx n_sharp x 2, surf_idx n_flat x 3, sel_out (n_sharp + n_flat) x 3
   void Correspondences(const float *sharp, size_t n_sharp, const float *flat, size_t n_flat, const float *last_corner, size_t n_last_corner,
                        const float *last_surf, size_t n_last_surf, const Rigid<float> &T, int32_t *corner_idx, int32_t *surf_idx, float *sel_out);
+  // the rows of one iteration on caller-given clouds, correspondences and transform_es_ (lio_gn_rows_odom, include/lio_test_hooks.h): ok_out
+  // n_sharp + n_flat, rows_out x 7, partials_out nb x 28 with nb <= 64
+  void Rows(const float *sharp, size_t n_sharp, const float *flat, size_t n_flat, const float *last_corner, size_t n_last_corner, const float *last_surf,
+            size_t n_last_surf, const int32_t *corner_idx, const int32_t *surf_idx, const Rigid<float> &T, int iter, uint8_t *ok_out, float *rows_out,
+            int32_t *nb_out, double *partials_out);
 
   Rigid<float> transform_es_, transform_sum_;
   int iterations_done_ = 0, last_num_sel_ = 0;
@@ -68,5 +73,8 @@ class OdometryDev {
   unsigned *h_flag_ = nullptr;     // its completion word
   unsigned seq_ = 0;
 };
+
+// the scan-to-scan step (odo_update_step) on device sums and a device state, in place (lio_gn_step family 1, include/lio_test_hooks.h)
+void launch_gn_odo_step(const double *sums, OdomState *st, int iter, hipStream_t s);
 
 }  // namespace lio

@@ -207,6 +207,71 @@ __global__ void __launch_bounds__(256) k_odo_sel(OdoArgs a, const OdomState *__r
 
 #define ODO_ROW_THREADS 256
 
+// The row of query qi (sharp first) at transform_es_ = (qe, te) on the correspondences `idx`, in the two halves the loop of odo_rows_body has
+// around its `continue`; the test hook lio_gn_rows_odom calls the same two.
+// odo_row_coeff: TransformToStart, edge / plane coefficients (:391-435, :497-531) and weight (A.7).  false: the query has no row.
+__device__ __forceinline__ bool odo_row_coeff(const OdoArgs &a, const Quat<float> &qe, const Vec3<float> &te, const int *__restrict__ idx, int iter, int qi,
+                                              float4 &pi_out, float4 &c_out) {
+  const bool corner = qi < a.nc;
+  const float4 pi = corner ? a.sharp[qi] : a.flat[qi - a.nc];
+  Vec3<float> sel;
+  odo_to_start(pi, qe, te, a.time_factor, a.no_deskew, sel);
+  float c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+  bool ok = false;
+  if (corner) {
+    int i1 = idx[2 * qi], i2 = idx[2 * qi + 1];
+    if (i2 >= 0) {
+      float4 t1 = a.lastc[i1], t2 = a.lastc[i2];
+      float x0 = sel.x, y0 = sel.y, z0 = sel.z, x1 = t1.x, y1 = t1.y, z1 = t1.z, x2 = t2.x, y2 = t2.y, z2 = t2.z;
+      float a012 = sqrtf(((x0 - x1) * (y0 - y2) - (x0 - x2) * (y0 - y1)) * ((x0 - x1) * (y0 - y2) - (x0 - x2) * (y0 - y1)) +
+                         ((x0 - x1) * (z0 - z2) - (x0 - x2) * (z0 - z1)) * ((x0 - x1) * (z0 - z2) - (x0 - x2) * (z0 - z1)) +
+                         ((y0 - y1) * (z0 - z2) - (y0 - y2) * (z0 - z1)) * ((y0 - y1) * (z0 - z2) - (y0 - y2) * (z0 - z1)));
+      float l12 = sqrtf((x1 - x2) * (x1 - x2) + (y1 - y2) * (y1 - y2) + (z1 - z2) * (z1 - z2));
+      float la = ((y1 - y2) * ((x0 - x1) * (y0 - y2) - (x0 - x2) * (y0 - y1)) + (z1 - z2) * ((x0 - x1) * (z0 - z2) - (x0 - x2) * (z0 - z1))) / a012 / l12;
+      float lb = -((x1 - x2) * ((x0 - x1) * (y0 - y2) - (x0 - x2) * (y0 - y1)) - (z1 - z2) * ((y0 - y1) * (z0 - z2) - (y0 - y2) * (z0 - z1))) / a012 / l12;
+      float lc = -((x1 - x2) * ((x0 - x1) * (z0 - z2) - (x0 - x2) * (z0 - z1)) + (y1 - y2) * ((y0 - y1) * (z0 - z2) - (y0 - y2) * (z0 - z1))) / a012 / l12;
+      float ld2 = a012 / l12;
+      float s = 1;
+      if (iter >= 5) s = 1 - 1.8f * fabsf(ld2);
+      if (double(s) > 0.1 && ld2 != 0) { ok = true; c0 = s * la; c1 = s * lb; c2 = s * lc; c3 = s * ld2; }
+    }
+  } else {
+    int o = 2 * a.nc + 3 * (qi - a.nc);
+    int i1 = idx[o], i2 = idx[o + 1], i3 = idx[o + 2];
+    if (i2 >= 0 && i3 >= 0) {
+      float4 t1 = a.lasts[i1], t2 = a.lasts[i2], t3 = a.lasts[i3];
+      float pa = (t2.y - t1.y) * (t3.z - t1.z) - (t3.y - t1.y) * (t2.z - t1.z);
+      float pb = (t2.z - t1.z) * (t3.x - t1.x) - (t3.z - t1.z) * (t2.x - t1.x);
+      float pc = (t2.x - t1.x) * (t3.y - t1.y) - (t3.x - t1.x) * (t2.y - t1.y);
+      float pd = -(pa * t1.x + pb * t1.y + pc * t1.z);
+      float ps = sqrtf(pa * pa + pb * pb + pc * pc);
+      pa /= ps; pb /= ps; pc /= ps; pd /= ps;
+      float pd2 = pa * sel.x + pb * sel.y + pc * sel.z + pd;
+      float s = 1;
+      if (iter >= 5) s = 1 - 1.8f * fabsf(pd2) / sqrtf(sqrtf(sel.x * sel.x + sel.y * sel.y + sel.z * sel.z));
+      if (double(s) > 0.1 && pd2 != 0) { ok = true; c0 = s * pa; c1 = s * pb; c2 = s * pc; c3 = s * pd2; }
+    }
+  }
+  pi_out = pi; c_out = make_float4(c0, c1, c2, c3);
+  return ok;
+}
+// odo_row_of: r[6] and b of a selected query (:548-571), Rt = R(qe)^T
+__device__ __forceinline__ void odo_row_of(const float4 pi, const float4 c, const Quat<float> &qe, const Vec3<float> &te, const Mat3<float> &Rt, float (&r)[6],
+                                           float &bb) {
+  const float c0 = c.x, c1 = c.y, c2 = c.z, c3 = c.w;
+  Vec3<float> p(pi.x, pi.y, pi.z), w(c0, c1, c2);
+  Vec3<float> pmt = p - te;
+  Vec3<float> cc = rotate(conj(qe), pmt);
+  Mat3<float> S = skew(cc);
+  r[0] = w.x * S(0, 0) + w.y * S(1, 0) + w.z * S(2, 0);
+  r[1] = w.x * S(0, 1) + w.y * S(1, 1) + w.z * S(2, 1);
+  r[2] = w.x * S(0, 2) + w.y * S(1, 2) + w.z * S(2, 2);
+  r[3] = -(w.x * Rt(0, 0) + w.y * Rt(1, 0) + w.z * Rt(2, 0));
+  r[4] = -(w.x * Rt(0, 1) + w.y * Rt(1, 1) + w.z * Rt(2, 1));
+  r[5] = -(w.x * Rt(0, 2) + w.y * Rt(1, 2) + w.z * Rt(2, 2));
+  bb = float(-0.1 * double(c3));
+}
+
 // block `block` of the `nblocks` (ODO_ROW_THREADS threads each) that share one sensor's queries; 28 doubles to partials[block * 28 ...]
 __device__ __forceinline__ void odo_rows_body(const OdoArgs &a, const OdomState *__restrict__ st, const int *__restrict__ idx, int iter,
                                               double *__restrict__ partials, const int block, const int nblocks) {
@@ -219,59 +284,10 @@ __device__ __forceinline__ void odo_rows_body(const OdoArgs &a, const OdomState 
   for (int k = 0; k < 28; ++k) acc[k] = 0;
   const int total = a.nc + a.ns;
   for (int qi = block * ODO_ROW_THREADS + threadIdx.x; qi < total; qi += nblocks * ODO_ROW_THREADS) {
-    const bool corner = qi < a.nc;
-    const float4 pi = corner ? a.sharp[qi] : a.flat[qi - a.nc];
-    Vec3<float> sel;
-    odo_to_start(pi, qe, te, a.time_factor, a.no_deskew, sel);
-    float c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-    bool ok = false;
-    if (corner) {
-      int i1 = idx[2 * qi], i2 = idx[2 * qi + 1];
-      if (i2 >= 0) {
-        float4 t1 = a.lastc[i1], t2 = a.lastc[i2];
-        float x0 = sel.x, y0 = sel.y, z0 = sel.z, x1 = t1.x, y1 = t1.y, z1 = t1.z, x2 = t2.x, y2 = t2.y, z2 = t2.z;
-        float a012 = sqrtf(((x0 - x1) * (y0 - y2) - (x0 - x2) * (y0 - y1)) * ((x0 - x1) * (y0 - y2) - (x0 - x2) * (y0 - y1)) +
-                           ((x0 - x1) * (z0 - z2) - (x0 - x2) * (z0 - z1)) * ((x0 - x1) * (z0 - z2) - (x0 - x2) * (z0 - z1)) +
-                           ((y0 - y1) * (z0 - z2) - (y0 - y2) * (z0 - z1)) * ((y0 - y1) * (z0 - z2) - (y0 - y2) * (z0 - z1)));
-        float l12 = sqrtf((x1 - x2) * (x1 - x2) + (y1 - y2) * (y1 - y2) + (z1 - z2) * (z1 - z2));
-        float la = ((y1 - y2) * ((x0 - x1) * (y0 - y2) - (x0 - x2) * (y0 - y1)) + (z1 - z2) * ((x0 - x1) * (z0 - z2) - (x0 - x2) * (z0 - z1))) / a012 / l12;
-        float lb = -((x1 - x2) * ((x0 - x1) * (y0 - y2) - (x0 - x2) * (y0 - y1)) - (z1 - z2) * ((y0 - y1) * (z0 - z2) - (y0 - y2) * (z0 - z1))) / a012 / l12;
-        float lc = -((x1 - x2) * ((x0 - x1) * (z0 - z2) - (x0 - x2) * (z0 - z1)) + (y1 - y2) * ((y0 - y1) * (z0 - z2) - (y0 - y2) * (z0 - z1))) / a012 / l12;
-        float ld2 = a012 / l12;
-        float s = 1;
-        if (iter >= 5) s = 1 - 1.8f * fabsf(ld2);
-        if (double(s) > 0.1 && ld2 != 0) { ok = true; c0 = s * la; c1 = s * lb; c2 = s * lc; c3 = s * ld2; }
-      }
-    } else {
-      int o = 2 * a.nc + 3 * (qi - a.nc);
-      int i1 = idx[o], i2 = idx[o + 1], i3 = idx[o + 2];
-      if (i2 >= 0 && i3 >= 0) {
-        float4 t1 = a.lasts[i1], t2 = a.lasts[i2], t3 = a.lasts[i3];
-        float pa = (t2.y - t1.y) * (t3.z - t1.z) - (t3.y - t1.y) * (t2.z - t1.z);
-        float pb = (t2.z - t1.z) * (t3.x - t1.x) - (t3.z - t1.z) * (t2.x - t1.x);
-        float pc = (t2.x - t1.x) * (t3.y - t1.y) - (t3.x - t1.x) * (t2.y - t1.y);
-        float pd = -(pa * t1.x + pb * t1.y + pc * t1.z);
-        float ps = sqrtf(pa * pa + pb * pb + pc * pc);
-        pa /= ps; pb /= ps; pc /= ps; pd /= ps;
-        float pd2 = pa * sel.x + pb * sel.y + pc * sel.z + pd;
-        float s = 1;
-        if (iter >= 5) s = 1 - 1.8f * fabsf(pd2) / sqrtf(sqrtf(sel.x * sel.x + sel.y * sel.y + sel.z * sel.z));
-        if (double(s) > 0.1 && pd2 != 0) { ok = true; c0 = s * pa; c1 = s * pb; c2 = s * pc; c3 = s * pd2; }
-      }
-    }
-    if (!ok) continue;
-    Vec3<float> p(pi.x, pi.y, pi.z), w(c0, c1, c2);
-    Vec3<float> pmt = p - te;
-    Vec3<float> cc = rotate(conj(qe), pmt);
-    Mat3<float> S = skew(cc);
-    float r[6];
-    r[0] = w.x * S(0, 0) + w.y * S(1, 0) + w.z * S(2, 0);
-    r[1] = w.x * S(0, 1) + w.y * S(1, 1) + w.z * S(2, 1);
-    r[2] = w.x * S(0, 2) + w.y * S(1, 2) + w.z * S(2, 2);
-    r[3] = -(w.x * Rt(0, 0) + w.y * Rt(1, 0) + w.z * Rt(2, 0));
-    r[4] = -(w.x * Rt(0, 1) + w.y * Rt(1, 1) + w.z * Rt(2, 1));
-    r[5] = -(w.x * Rt(0, 2) + w.y * Rt(1, 2) + w.z * Rt(2, 2));
-    float bb = float(-0.1 * double(c3));
+    float4 pi, c;
+    if (!odo_row_coeff(a, qe, te, idx, iter, qi, pi, c)) continue;
+    float r[6], bb;
+    odo_row_of(pi, c, qe, te, Rt, r, bb);
     int k = 0;
 #pragma unroll
     for (int i = 0; i < 6; ++i)
@@ -299,6 +315,30 @@ __device__ __forceinline__ void odo_rows_body(const OdoArgs &a, const OdomState 
 __global__ void __launch_bounds__(ODO_ROW_THREADS) k_odo_rows(OdoArgs a, const OdomState *__restrict__ st, const int *__restrict__ idx, int iter,
                                                               double *__restrict__ partials) {
   odo_rows_body(a, st, idx, iter, partials, blockIdx.x, gridDim.x);
+}
+
+// The one statement of the rows launch: Process (every iteration) and the test hook lio_gn_rows_odom
+static int odo_rows_blocks(int nq) { return std::max(1, std::min(cdiv(nq, ODO_ROW_THREADS), 64)); }
+static void launch_odo_rows(const OdoArgs &a, const OdomState *st, const int *idx, int iter, double *partials, int nb, hipStream_t s) {
+  hipLaunchKernelGGL(k_odo_rows, dim3(nb), dim3(ODO_ROW_THREADS), 0, s, a, st, idx, iter, partials);
+}
+// the row of every query on its own (lio_gn_rows_odom): one query per lane through odo_row_coeff and odo_row_of; 7 floats (r0 .. r5, b), zeros and ok = 0
+// where the query has no row
+__global__ void __launch_bounds__(256) k_gn_rows_odom(OdoArgs a, const OdomState *__restrict__ st, const int *__restrict__ idx, int iter,
+                                                      uint8_t *__restrict__ ok_out, float *__restrict__ rows_out) {
+  const int qi = blockIdx.x * blockDim.x + threadIdx.x;
+  if (qi >= a.nc + a.ns) return;
+  Quat<float> qe(st->T[3], st->T[0], st->T[1], st->T[2]);
+  Vec3<float> te(st->T[4], st->T[5], st->T[6]);
+  Mat3<float> Rt = transpose(toRot(qe));
+  float4 pi, c;
+  float r[6] = {0, 0, 0, 0, 0, 0}, bb = 0;
+  const bool ok = odo_row_coeff(a, qe, te, idx, iter, qi, pi, c);
+  if (ok) odo_row_of(pi, c, qe, te, Rt, r, bb);
+  ok_out[qi] = ok ? 1 : 0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) rows_out[size_t(qi) * 7 + k] = ok ? r[k] : 0.f;
+  rows_out[size_t(qi) * 7 + 6] = ok ? bb : 0.f;
 }
 
 // the serial 6x6 step of one iteration (thread 0); see k_odo_update
@@ -365,6 +405,18 @@ __device__ __forceinline__ void odo_update_step(const double *ssum, OdomState *s
   double dt0 = double(X[3] * 100), dt1 = double(X[4] * 100), dt2 = double(X[5] * 100);
   float delta_t = float(sqrt(dt0 * dt0 + dt1 * dt1 + dt2 * dt2));
   if (double(delta_r) < 0.1 && double(delta_t) < 0.1) st->converged = 1;
+}
+
+// lio_gn_step, family 1 (include/lio_test_hooks.h): thread 0 runs odo_update_step on the state in place; the row count it leaves in the pad
+// slot is also written to nsel
+__global__ void __launch_bounds__(64) k_gn_odo_step(const double *__restrict__ sums, OdomState *st, int iter) {
+  if (threadIdx.x != 0) return;
+  odo_update_step(sums, st, iter);
+  st->nsel = int(st->T[7]);
+}
+void launch_gn_odo_step(const double *sums, OdomState *st, int iter, hipStream_t s) {
+  hipLaunchKernelGGL(k_gn_odo_step, dim3(1), dim3(64), 0, s, sums, st, iter);
+  LIO_HIP(hipGetLastError());
 }
 
 // TransformToEnd (:261-292) with the transform_es_ the iterations left on the device; out == in: in place
@@ -623,7 +675,7 @@ void OdometryDev::ProcessFrom(const float *sharp, size_t n_sharp, const float *l
       LIO_HIP(hipMemsetAsync(idx_.p, 0xFF, (2 * n_sharp + 3 * n_flat) * sizeof(int), s));
       BuildGrids();
       const OdoArgs a = Args(n_sharp, n_flat);
-      const int nb = std::max(1, std::min(cdiv(nq, ODO_ROW_THREADS), 64));
+      const int nb = odo_rows_blocks(nq);
       d_partials_.reserve(size_t(nb) * 28);
       d_trace_.reserve(size_t(max_iter_) * 8);
       HostSignal sig{};
@@ -635,7 +687,7 @@ void OdometryDev::ProcessFrom(const float *sharp, size_t n_sharp, const float *l
           if (st.converged) { have_state = true; break; }
         }
         if (iter % 5 == 0) launch_odo_corr(a, d_state_.p, idx_.p, s);
-        hipLaunchKernelGGL(k_odo_rows, dim3(nb), dim3(ODO_ROW_THREADS), 0, s, a, d_state_.p, idx_.p, iter, d_partials_.p);
+        launch_odo_rows(a, d_state_.p, idx_.p, iter, d_partials_.p, nb, s);
         HostSignal sg{};
         if (iter % 5 == 4 || iter == max_iter_ - 1) { sig.flag = h_flag_; sig.seq = ++seq_; sg = sig; }
         hipLaunchKernelGGL(k_odo_update, dim3(1), dim3(256), 0, s, d_partials_.p, nb, d_state_.p, iter, h_state_, sg, d_trace_.p);
@@ -937,6 +989,45 @@ void OdometryDev::Correspondences(const float *sharp, size_t n_sharp, const floa
   if (n_flat) LIO_HIP(hipMemcpyAsync(surf_idx, idx_.p + 2 * n_sharp, 3 * n_flat * sizeof(int), hipMemcpyDeviceToHost, s));
   if (nq) LIO_HIP(hipMemcpyAsync(sel_out, d_sel_.p, 3 * nq * sizeof(float), hipMemcpyDeviceToHost, s));
   LIO_HIP(hipStreamSynchronize(s));
+}
+
+// lio_gn_rows_odom (include/lio_test_hooks.h): the given clouds and correspondences, ONE launch of k_odo_rows through the statement Process
+// uses at the given transform_es_ and iteration, and the row of every query from k_gn_rows_odom.  Meant for a handle of its own.  The
+// caller has checked the indices against the clouds' sizes.
+void OdometryDev::Rows(const float *sharp, size_t n_sharp, const float *flat, size_t n_flat, const float *last_corner, size_t n_lc,
+                       const float *last_surf, size_t n_lsf, const int32_t *corner_idx, const int32_t *surf_idx, const Rigid<float> &T, int iter,
+                       uint8_t *ok_out, float *rows_out, int32_t *nb_out, double *partials_out) {
+  hipStream_t s = stream_;
+  upload(sharp_, sharp, n_sharp, s);
+  upload(flat_, flat, n_flat, s);
+  upload(last_corner_, last_corner, n_lc, s);
+  upload(last_surf_, last_surf, n_lsf, s);
+  n_last_corner_ = n_lc; n_last_surf_ = n_lsf;
+  OdomState st{};
+  st.T[0] = T.rot.x; st.T[1] = T.rot.y; st.T[2] = T.rot.z; st.T[3] = T.rot.w;
+  st.T[4] = T.pos.x; st.T[5] = T.pos.y; st.T[6] = T.pos.z;
+  LIO_HIP(hipMemcpyAsync(d_state_.p, &st, sizeof(st), hipMemcpyHostToDevice, s));
+  const size_t nq = n_sharp + n_flat, ni = 2 * n_sharp + 3 * n_flat;
+  static_assert(sizeof(int) == sizeof(int32_t), "index layout");
+  idx_.reserve(std::max<size_t>(ni, 1));
+  if (n_sharp) LIO_HIP(hipMemcpyAsync(idx_.p, corner_idx, 2 * n_sharp * sizeof(int), hipMemcpyHostToDevice, s));
+  if (n_flat) LIO_HIP(hipMemcpyAsync(idx_.p + 2 * n_sharp, surf_idx, 3 * n_flat * sizeof(int), hipMemcpyHostToDevice, s));
+  const OdoArgs a = Args(n_sharp, n_flat);   // the grids are not built: the rows kernels read the clouds and the indices alone
+  const int nb = odo_rows_blocks(int(nq));
+  d_partials_.reserve(size_t(nb) * 28);
+  launch_odo_rows(a, d_state_.p, idx_.p, iter, d_partials_.p, nb, s);
+  d_sel_.reserve(std::max<size_t>(7 * nq, 1));
+  DBuf<uint8_t> ok_dev;
+  ok_dev.reserve(std::max<size_t>(nq, 1));
+  if (nq) hipLaunchKernelGGL(k_gn_rows_odom, dim3(cdiv(nq, 256)), dim3(256), 0, s, a, d_state_.p, idx_.p, iter, ok_dev.p, d_sel_.p);
+  LIO_HIP(hipGetLastError());
+  if (nq) {
+    LIO_HIP(hipMemcpyAsync(ok_out, ok_dev.p, nq, hipMemcpyDeviceToHost, s));
+    LIO_HIP(hipMemcpyAsync(rows_out, d_sel_.p, 7 * nq * sizeof(float), hipMemcpyDeviceToHost, s));
+  }
+  LIO_HIP(hipMemcpyAsync(partials_out, d_partials_.p, size_t(nb) * 28 * sizeof(double), hipMemcpyDeviceToHost, s));
+  LIO_HIP(hipStreamSynchronize(s));   // `st` and the caller's arrays have been read
+  *nb_out = nb;
 }
 
 // TransformToEnd(full_cloud_) of a publishing step (:725-730): the same kernel and the same device-side transform_es_ as the

@@ -270,7 +270,18 @@ _TEST_SIGS = {
                                c_uint8_p, c_float_p, c_float_p, c_float_p]),
     "lio_odom_correspondences": (C.c_int, [c_float_p, C.c_size_t, c_float_p, C.c_size_t, c_float_p, C.c_size_t, c_float_p, C.c_size_t,
                                            C.POINTER(TransformF), C.c_float, C.c_int, c_int32_p, c_int32_p, c_float_p]),
+    "lio_gn_rows_map": (C.c_int, [C.c_int, c_float_p, C.c_size_t, c_uint8_p, c_float_p, C.POINTER(TransformF), c_uint8_p, c_float_p, c_int32_p,
+                                  c_double_p]),
+    "lio_gn_rows_odom": (C.c_int, [c_float_p, C.c_size_t, c_float_p, C.c_size_t, c_float_p, C.c_size_t, c_float_p, C.c_size_t, c_int32_p, c_int32_p,
+                                   C.POINTER(TransformF), C.c_float, C.c_int, C.c_int, c_uint8_p, c_float_p, c_int32_p, c_double_p]),
+    "lio_gn_fold": (C.c_int, [c_double_p, C.c_int, C.c_int, c_double_p]),
+    "lio_gn_step": (C.c_int, [C.c_int, c_double_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "lio_gn_round": (C.c_int, [c_float_p, C.c_size_t, c_float_p, C.c_size_t, C.POINTER(TransformF), C.c_float, C.c_float, C.c_int, c_int32_p,
+                               c_double_p, C.c_void_p]),
 }
+# lio_gn_state of include/lio_test_hooks.h as a numpy record: 13 words
+GN_STATE = np.dtype([("T", np.float32, 8), ("converged", np.int32), ("iters", np.int32), ("degenerate", np.int32), ("kz", np.int32),
+                     ("nsel", np.int32)])
 # include/lio_ext.h: the product's entry points beyond the shared ABI (the map refresh and the surround map).  Attached to the HIP
 # library only: the oracle does not implement them, and loading it must keep working
 _EXT_SIGS = {
@@ -493,6 +504,70 @@ class LioLib:
                                                corner_idx.ctypes.data_as(c_int32_p), surf_idx.ctypes.data_as(c_int32_p), _fp(sel)),
              "lio_odom_correspondences")
         return corner_idx, surf_idx, sel
+
+    def gn_rows_map(self, form, stack_xyzi, valid, coeff, T: TransformF):
+        """the rows of the scan-to-map family and the partials of one production rows launch (include/lio_test_hooks.h: lio_gn_rows_map) ->
+        (ok (m,) uint8, rows (m, 7) fp32 = a0 .. a5, b, partials (nb, 28) fp64)"""
+        s_ = _f32(stack_xyzi).reshape(-1, 4)
+        m = s_.shape[0]
+        v_ = np.ascontiguousarray(valid, dtype=np.uint8).reshape(m)
+        c_ = _f32(coeff).reshape(m, 4)
+        ok = np.zeros(m, dtype=np.uint8)
+        rows = np.zeros((m, 7), dtype=np.float32)
+        nb = np.zeros(1, dtype=np.int32)
+        partials = np.zeros((256, 28), dtype=np.float64)
+        _chk(self.dll.lio_gn_rows_map(int(form), _fp(s_), m, v_.ctypes.data_as(c_uint8_p), _fp(c_), C.byref(T), ok.ctypes.data_as(c_uint8_p),
+                                      _fp(rows), nb.ctypes.data_as(c_int32_p), partials.ctypes.data_as(c_double_p)), "lio_gn_rows_map")
+        return ok, rows, partials[: int(nb[0])].copy()
+
+    def gn_rows_odom(self, sharp, flat, last_corner, last_surf, corner_idx, surf_idx, T_es: TransformF, iter, scan_period=0.1, no_deskew=False):
+        """the rows of the scan-to-scan loop and the partials of one production rows launch, on given correspondences
+        (include/lio_test_hooks.h: lio_gn_rows_odom) -> (ok (nq,) uint8, rows (nq, 7) fp32, partials (nb, 28) fp64), sharp first"""
+        cl = [_f32(c).reshape(-1, 4) for c in (sharp, flat, last_corner, last_surf)]
+        nc, ns = cl[0].shape[0], cl[1].shape[0]
+        ci = np.ascontiguousarray(corner_idx, dtype=np.int32).reshape(nc, 2)
+        si = np.ascontiguousarray(surf_idx, dtype=np.int32).reshape(ns, 3)
+        ok = np.zeros(nc + ns, dtype=np.uint8)
+        rows = np.zeros((nc + ns, 7), dtype=np.float32)
+        nb = np.zeros(1, dtype=np.int32)
+        partials = np.zeros((64, 28), dtype=np.float64)
+        args = []
+        for c in cl:
+            args += [_fp(c), c.shape[0]]
+        _chk(self.dll.lio_gn_rows_odom(*args, ci.ctypes.data_as(c_int32_p), si.ctypes.data_as(c_int32_p), C.byref(T_es), float(scan_period),
+                                       1 if no_deskew else 0, int(iter), ok.ctypes.data_as(c_uint8_p), _fp(rows), nb.ctypes.data_as(c_int32_p),
+                                       partials.ctypes.data_as(c_double_p)), "lio_gn_rows_odom")
+        return ok, rows, partials[: int(nb[0])].copy()
+
+    def gn_fold(self, partials, wide):
+        """the fixed-order fold of (nblocks, 28) partials (include/lio_test_hooks.h: lio_gn_fold) -> sums (28,) fp64"""
+        p_ = np.ascontiguousarray(partials, dtype=np.float64).reshape(-1, 28)
+        sums = np.zeros(28, dtype=np.float64)
+        _chk(self.dll.lio_gn_fold(p_.ctypes.data_as(c_double_p), p_.shape[0], int(wide), sums.ctypes.data_as(c_double_p)), "lio_gn_fold")
+        return sums
+
+    def gn_step(self, family, sums, state_in, iter, min_rows=0, left_update=0):
+        """the serial 6x6 step behind the sums (include/lio_test_hooks.h: lio_gn_step); state_in / the result: records of GN_STATE"""
+        s_ = np.ascontiguousarray(sums, dtype=np.float64).reshape(28)
+        si = np.array(state_in, dtype=GN_STATE).reshape(1)
+        so = np.zeros(1, dtype=GN_STATE)
+        _chk(self.dll.lio_gn_step(int(family), s_.ctypes.data_as(c_double_p), si.ctypes.data, int(iter), int(min_rows), int(left_update),
+                                  so.ctypes.data), "lio_gn_step")
+        return so[0]
+
+    def gn_round(self, map_xyzi, stack_xyzi, T: TransformF, lanes_per_query, min_match_sq_dis=1.0, min_plane_dis=0.2):
+        """round 0 of the newest-frame loop through the production launch pair (include/lio_test_hooks.h: lio_gn_round) ->
+        (partials (nb, 28) fp64, state: a record of GN_STATE)"""
+        m_ = _f32(map_xyzi).reshape(-1, 4)
+        s_ = _f32(stack_xyzi).reshape(-1, 4)
+        m = s_.shape[0]
+        nb = np.zeros(1, dtype=np.int32)
+        partials = np.zeros((max(1, -(-m * int(lanes_per_query) // 256)), 28), dtype=np.float64)
+        so = np.zeros(1, dtype=GN_STATE)
+        _chk(self.dll.lio_gn_round(_fp(m_), m_.shape[0], _fp(s_), m, C.byref(T), float(min_match_sq_dis), float(min_plane_dis),
+                                   int(lanes_per_query), nb.ctypes.data_as(c_int32_p), partials.ctypes.data_as(c_double_p), so.ctypes.data),
+             "lio_gn_round")
+        return partials[: int(nb[0])].copy(), so[0]
 
     def calculate_features(self, map_xyzi, stack_xyzi, T: TransformF, min_match_sq_dis=1.0, min_plane_dis=0.2):
         m_ = _f32(map_xyzi).reshape(-1, 4)

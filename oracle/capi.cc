@@ -561,6 +561,165 @@ int lio_fit_five(int form, const float *nbr_xyz, const float *fifth_sqd, const f
   return LIO_OK;
 }
 
+// ---- the Gauss-Newton hooks (include/lio_test_hooks.h): the row and step functions the oracle's own loops call (oracle/liomath.h)
+static bool finite_T(const lio_transform_f *T) {
+  for (int k = 0; k < 4; ++k) if (!std::isfinite(T->q[k])) return false;
+  for (int k = 0; k < 3; ++k) if (!std::isfinite(T->p[k])) return false;
+  return true;
+}
+// a row added to one partial: plain fp64 sums of the fp32 products, upper triangle row by row, A^T b, count
+static void gn_add_row(const float a[6], float bb, double *part) {
+  int k = 0;
+  for (int r = 0; r < 6; ++r) for (int c = r; c < 6; ++c) part[k++] += double(a[r] * a[c]);
+  for (int r = 0; r < 6; ++r) part[21 + r] += double(a[r] * bb);
+  part[27] += 1.0;
+}
+int lio_gn_rows_map(int form, const float *stack, size_t m, const uint8_t *valid, const float *coeff, const lio_transform_f *T, uint8_t *ok_out,
+                    float *rows_out, int32_t *nb_out, double *partials_out) {
+  if (form < 0 || form > 2 || ((!stack || !valid || !coeff || !ok_out || !rows_out) && m) || !T || !nb_out || !partials_out) return LIO_ERR_ARG;
+  if (!finite_T(T)) return LIO_ERR_ARG;
+  const Transformf Tf = toT(*T);
+  const M3<float> Rm = Tf.rot.toRotationMatrix(), Rinv = Tf.rot.inverse().toRotationMatrix();
+  for (int k = 0; k < 28; ++k) partials_out[k] = 0.0;
+  for (size_t i = 0; i < m; ++i) {
+    float a[6] = {0, 0, 0, 0, 0, 0}, bb = 0.f;
+    ok_out[i] = valid[i] ? 1 : 0;
+    if (valid[i]) {
+      const V3<float> p(stack[4 * i], stack[4 * i + 1], stack[4 * i + 2]), w(coeff[4 * i], coeff[4 * i + 1], coeff[4 * i + 2]);
+      GaussNewtonMapRow(form, p, w, coeff[4 * i + 3], Tf, Rm, Rinv, a, bb);
+      gn_add_row(a, bb, partials_out);
+    }
+    for (int k = 0; k < 6; ++k) rows_out[7 * i + k] = a[k];
+    rows_out[7 * i + 6] = bb;
+  }
+  *nb_out = 1;
+  return LIO_OK;
+}
+static bool gn_indices_ok(const int32_t *idx, size_t n, int per, size_t n_last) {
+  for (size_t i = 0; i < n; ++i) {
+    bool others = false;
+    for (int k = 0; k < per; ++k) {
+      const int32_t v = idx[i * per + k];
+      if (v < -1 || (v >= 0 && size_t(v) >= n_last)) return false;
+      if (k > 0 && v >= 0) others = true;
+    }
+    if (others && idx[i * per] < 0) return false;
+  }
+  return true;
+}
+// lio_gn_rows_odom: TransformToStart, the coefficient functions and the row function of PointOdometry::Process, serially, on the stated indices
+int lio_gn_rows_odom(const float *sharp, size_t n_sharp, const float *flat, size_t n_flat, const float *last_corner, size_t n_lc, const float *last_surf,
+                     size_t n_lsf, const int32_t *corner_idx, const int32_t *surf_idx, const lio_transform_f *T, float scan_period, int no_deskew, int iter,
+                     uint8_t *ok_out, float *rows_out, int32_t *nb_out, double *partials_out) {
+  if ((!sharp && n_sharp) || (!flat && n_flat) || (!last_corner && n_lc) || (!last_surf && n_lsf) || (!corner_idx && n_sharp) || (!surf_idx && n_flat) ||
+      ((!ok_out || !rows_out) && (n_sharp + n_flat)) || !T || !nb_out || !partials_out || iter < 0)
+    return LIO_ERR_ARG;
+  if (!(scan_period > 0) || !std::isfinite(scan_period) || !finite_T(T)) return LIO_ERR_ARG;
+  if (!gn_indices_ok(corner_idx, n_sharp, 2, n_lc) || !gn_indices_ok(surf_idx, n_flat, 3, n_lsf)) return LIO_ERR_ARG;
+  PointOdometry od(scan_period, 1, 1, no_deskew != 0);
+  od.transform_es_ = toT(*T);
+  const Cloud lc = toCloud(last_corner, n_lc), ls = toCloud(last_surf, n_lsf);
+  const M3<float> Rt = od.transform_es_.rot.toRotationMatrix().transpose();
+  for (int k = 0; k < 28; ++k) partials_out[k] = 0.0;
+  for (size_t i = 0; i < n_sharp + n_flat; ++i) {
+    const bool corner = i < n_sharp;
+    const float *q = corner ? sharp + 4 * i : flat + 4 * (i - n_sharp);
+    const P4 pi{q[0], q[1], q[2], q[3]};
+    P4 sel, c;
+    od.TransformToStart(pi, sel);
+    bool ok = false;
+    if (corner) {
+      const int32_t i1 = corner_idx[2 * i], i2 = corner_idx[2 * i + 1];
+      if (i2 >= 0) ok = PointOdometry::EdgeCoefficients(sel, lc[i1], lc[i2], size_t(iter), c);
+    } else {
+      const size_t k = i - n_sharp;
+      const int32_t i1 = surf_idx[3 * k], i2 = surf_idx[3 * k + 1], i3 = surf_idx[3 * k + 2];
+      if (i2 >= 0 && i3 >= 0) ok = PointOdometry::PlaneCoefficients(sel, ls[i1], ls[i2], ls[i3], size_t(iter), c);
+    }
+    float a[6] = {0, 0, 0, 0, 0, 0}, bb = 0.f;
+    if (ok) {
+      PointOdometry::OdometryRow(pi, c, od.transform_es_, Rt, a, bb);
+      gn_add_row(a, bb, partials_out);
+    }
+    ok_out[i] = ok ? 1 : 0;
+    for (int k = 0; k < 6; ++k) rows_out[7 * i + k] = a[k];
+    rows_out[7 * i + 6] = bb;
+  }
+  *nb_out = 1;
+  return LIO_OK;
+}
+int lio_gn_fold(const double *partials, int nblocks, int wide, double *sums_out) {
+  if (nblocks < 0 || (!partials && nblocks) || !(wide == 0 || wide == 1) || !sums_out) return LIO_ERR_ARG;
+  for (int k = 0; k < 28; ++k) sums_out[k] = 0.0;
+  for (int b = 0; b < nblocks; ++b) for (int k = 0; k < 28; ++k) sums_out[k] += partials[size_t(b) * 28 + k];
+  return LIO_OK;
+}
+int lio_gn_step(int family, const double *sums, const lio_gn_state *state_in, int iter, int min_rows, int left_update, lio_gn_state *state_out) {
+  if (!(family == 0 || family == 1) || !sums || !state_in || !state_out || iter < 0 || min_rows < 0) return LIO_ERR_ARG;
+  if (family == 1 && (min_rows != 0 || left_update != 0)) return LIO_ERR_ARG;
+  for (int k = 0; k < 7; ++k) if (!std::isfinite(state_in->T[k])) return LIO_ERR_ARG;
+  lio_gn_state st = *state_in;
+  const int nsel = int(sums[27]);
+  st.nsel = nsel;
+  st.iters = iter + 1;
+  if (family == 1) st.T[7] = float(nsel);
+  // the loops' own gates in front of the sums: `continue` (PointMapping.cc:623-626, PointOdometry.cc:535)
+  const bool too_few = family == 0 ? (min_rows > 0 && nsel < min_rows) : nsel < 10;
+  if (!too_few) {
+    // the loops accumulate in fp32: the sums enter as floats
+    float AtA[36], AtB[6], X[6];
+    int k = 0;
+    for (int r = 0; r < 6; ++r) for (int c = r; c < 6; ++c) { AtA[r * 6 + c] = float(sums[k]); AtA[c * 6 + r] = float(sums[k]); ++k; }
+    for (int r = 0; r < 6; ++r) AtB[r] = float(sums[21 + r]);
+    Transformf T(Q<float>(st.T[3], st.T[0], st.T[1], st.T[2]), V3<float>(st.T[4], st.T[5], st.T[6]));
+    bool is_degenerate = st.degenerate != 0;
+    int kz = st.kz;
+    const bool done = family == 0 ? GaussNewtonStep(AtA, AtB, size_t(iter), 100.f, true, left_update != 0, 0.05, 0.05, T, is_degenerate, kz, X)
+                                  : GaussNewtonStep(AtA, AtB, size_t(iter), 10.f, false, false, 0.1, 0.1, T, is_degenerate, kz, X);
+    st.T[0] = T.rot.x; st.T[1] = T.rot.y; st.T[2] = T.rot.z; st.T[3] = T.rot.w; st.T[4] = T.pos.x; st.T[5] = T.pos.y; st.T[6] = T.pos.z;
+    st.degenerate = is_degenerate ? 1 : 0; st.kz = kz;
+    if (done) st.converged = 1;
+  }
+  *state_out = st;
+  return LIO_OK;
+}
+int lio_gn_round(const float *map, size_t n_map, const float *stack, size_t m, const lio_transform_f *T, float mm, float mp, int lpq, int32_t *nb_out,
+                 double *partials_out, lio_gn_state *state_out) {
+  if ((!map && n_map) || (!stack && m) || !T || !nb_out || !partials_out || !state_out || !(lpq == 4 || lpq == 8)) return LIO_ERR_ARG;
+  if (!finite_T(T) || !(mm > 0) || !std::isfinite(mm) || !(mp > 0) || !std::isfinite(mp)) return LIO_ERR_ARG;
+  lio_gn_state st{};
+  for (int k = 0; k < 4; ++k) st.T[k] = T->q[k];
+  for (int k = 0; k < 3; ++k) st.T[4 + k] = T->p[k];
+  *nb_out = 0;
+  if (m == 0) { *state_out = st; return LIO_OK; }
+  // one pass of the body of Estimator::CalculateLaserOdom at iter 0
+  Cloud c = toCloud(map, n_map), s = toCloud(stack, m);
+  KdTree t;
+  t.Build(c);
+  std::vector<PlaneFeature> feats;
+  Transformf Tf = toT(*T);
+  Estimator::CalculateFeatures(t, c, s, Tf, mm, mp, false, feats, nullptr, nullptr);
+  float AtA[36] = {0}, AtB[6] = {0}, X[6];
+  const M3<float> Rm = Tf.rot.toRotationMatrix();
+  for (int k = 0; k < 28; ++k) partials_out[k] = 0.0;
+  for (const PlaneFeature &f : feats) {
+    V3<float> p{float(f.point.x), float(f.point.y), float(f.point.z)};
+    V3<float> w{float(f.coeffs[0]), float(f.coeffs[1]), float(f.coeffs[2])};
+    float a[6], bb;
+    GaussNewtonMapRow(0, p, w, float(f.coeffs[3]), Tf, Rm, Rm, a, bb);
+    for (int r = 0; r < 6; ++r) { for (int cc = 0; cc < 6; ++cc) AtA[r * 6 + cc] += a[r] * a[cc]; AtB[r] += a[r] * bb; }
+    gn_add_row(a, bb, partials_out);
+  }
+  bool is_degenerate = false;
+  int kz = 0;
+  const bool done = GaussNewtonStep(AtA, AtB, 0, 100.f, true, false, 0.05, 0.05, Tf, is_degenerate, kz, X);
+  st.T[0] = Tf.rot.x; st.T[1] = Tf.rot.y; st.T[2] = Tf.rot.z; st.T[3] = Tf.rot.w; st.T[4] = Tf.pos.x; st.T[5] = Tf.pos.y; st.T[6] = Tf.pos.z;
+  st.converged = done ? 1 : 0; st.iters = 1; st.degenerate = is_degenerate ? 1 : 0; st.kz = kz; st.nsel = int(feats.size());
+  *nb_out = 1;
+  *state_out = st;
+  return LIO_OK;
+}
+
 // ---------------------------------------------------------------- pre-integration
 lio_pim *lio_pim_create(const double acc0[3], const double gyr0[3], const double ba[3], const double bg[3], double acc_n, double gyr_n,
                         double acc_w, double gyr_w, double g_norm) {

@@ -370,14 +370,12 @@ struct Estimator {
   // ---- Estimator.cc:1242-1359
   void CalculateLaserOdom(const KdTree &tree, const Cloud &map, const Cloud &stack, Transformf &T, std::vector<PlaneFeature> &features) {
     bool is_degenerate = false;
-    float matP[36];
     laser_odom_iters = 0; laser_odom_kz = 0;
     for (size_t iter = 0; iter < 10; ++iter) {  // num_max_iterations_ = 10 (PointMapping.h:171)
       ++laser_odom_iters;
       CalculateFeatures(tree, map, stack, T, cfg.min_match_sq_dis, cfg.min_plane_dis, cfg.keep_features, features);
       size_t n = features.size();
       float AtA[36] = {0}, AtB[6] = {0};
-      Q<float> R0 = T.rot.normalized();  // SO3 ctor normalises (so3.hpp)
       M3<float> Rm = T.rot.toRotationMatrix();  // Quaternion * Matrix goes through toRotationMatrix()
       // Eigen evaluates mat_At * mat_A / mat_At * mat_B as GEMM/GEMV in float; the summation order inside
       // Eigen's kernels is unspecified — the oracle sums rows sequentially in float.
@@ -386,45 +384,15 @@ struct Estimator {
         V3<float> p{float(f.point.x), float(f.point.y), float(f.point.z)};
         V3<float> w{float(f.coeffs[0]), float(f.coeffs[1]), float(f.coeffs[2])};
         float ci = float(f.coeffs[3]);
-        M3<float> RS = Rm * Skew(p);
-        // J_r = -w^T (R skew(p))
-        float a[6];
-        a[0] = -(w.x * RS(0, 0) + w.y * RS(1, 0) + w.z * RS(2, 0));
-        a[1] = -(w.x * RS(0, 1) + w.y * RS(1, 1) + w.z * RS(2, 1));
-        a[2] = -(w.x * RS(0, 2) + w.y * RS(1, 2) + w.z * RS(2, 2));
-        a[3] = w.x; a[4] = w.y; a[5] = w.z;
-        V3<float> rp = T.rot * p;
-        float d2 = w.x * (rp.x + T.pos.x) + w.y * (rp.y + T.pos.y) + w.z * (rp.z + T.pos.z) + ci;
-        float bb = -d2;
+        float a[6], bb;
+        GaussNewtonMapRow(0, p, w, ci, T, Rm, Rm, a, bb);   // Rinv unused for form 0
         for (int r = 0; r < 6; ++r) { for (int c = 0; c < 6; ++c) AtA[r * 6 + c] += a[r] * a[c]; AtB[r] += a[r] * bb; }
       }
-      float Acopy[36], Bcopy[6], X[6];
-      std::memcpy(Acopy, AtA, sizeof(AtA)); std::memcpy(Bcopy, AtB, sizeof(AtB));
-      colpiv_qr_solve<float>(6, 6, Acopy, Bcopy, X);
-      if (iter == 0) {
-        float E[6], V[36];
-        sym_eigen<float>(6, AtA, E, V);
-        is_degenerate = false;
-        // A.6: matP = V2 * V^-1 with leading ROWS of V zeroed == diag(0..0,1..1)
-        for (int k = 0; k < 36; ++k) matP[k] = 0;
-        int kz = 0;
-        for (int i = 0; i < 6; ++i) { if (E[i] < 100.f) { ++kz; is_degenerate = true; } else break; }
-        for (int i = kz; i < 6; ++i) matP[i * 6 + i] = 1.f;
-        laser_odom_kz = kz;
-      }
-      if (is_degenerate) {
-        float X2[6];
-        for (int i = 0; i < 6; ++i) { float s = 0; for (int j = 0; j < 6; ++j) s += matP[i * 6 + j] * X[j]; X2[i] = s; }
-        std::memcpy(X, X2, sizeof(X));
-      }
-      T.pos.x += X[3]; T.pos.y += X[4]; T.pos.z += X[5];
-      T.rot = T.rot * DeltaQ(V3<float>(X[0], X[1], X[2]));
-      if (!std::isfinite(T.pos.x)) T.pos.x = 0;
-      if (!std::isfinite(T.pos.y)) T.pos.y = 0;
-      if (!std::isfinite(T.pos.z)) T.pos.z = 0;
-      float delta_r = RadToDeg(R0.angularDistance(T.rot));
-      float delta_t = std::sqrt(std::pow(X[3] * 100, 2) + std::pow(X[4] * 100, 2) + std::pow(X[5] * 100, 2));
-      if (delta_r < 0.05 && delta_t < 0.05) break;  // delta_*_abort_ doubles (PointMapping.cc:75-76)
+      float X[6];
+      int kz = laser_odom_kz;
+      const bool done = GaussNewtonStep(AtA, AtB, iter, 100.f, true, false, 0.05, 0.05, T, is_degenerate, kz, X);  // delta_*_abort_ doubles (PointMapping.cc:75-76)
+      laser_odom_kz = kz;
+      if (done) break;
     }
   }
 

@@ -468,4 +468,71 @@ inline void colpiv_qr_solve(int m, int n, T *A, T *b, T *x) {
   for (int j = 0; j < n; ++j) x[perm[j]] = y[j];
 }
 
+// ---- the 6x6 Gauss-Newton loops (Estimator::CalculateLaserOdom, PointMapping::OptimizeTransformTobeMapped, PointOdometry::Process): the
+// statements the three loops share, called by them and by the test hooks lio_gn_rows_map / lio_gn_step (include/lio_test_hooks.h)
+
+// One row of (mat_A | mat_B) of a point-to-plane / point-to-line residual with coefficients (w, ci) at the pose T, Rm = T.rot's matrix.
+// form 0 (Estimator.cc:1272-1301): b = -(w . (R p + t) + ci);  1 (PointMapping.cc:640-650): b = -ci;  2 (MapBuilder.cc:903-914): b = -ci and
+// the rotation columns times R^-1 diag(5e-3, 5e-3, 1) with Rinv = T.rot.inverse()'s matrix (unused otherwise)
+inline void GaussNewtonMapRow(int form, const V3<float> &p, const V3<float> &w, float ci, const Twist<float> &T, const M3<float> &Rm,
+                              const M3<float> &Rinv, float a[6], float &bb) {
+  M3<float> RS = Rm * Skew(p);
+  // J_r = -w^T (R skew(p))
+  a[0] = -(w.x * RS(0, 0) + w.y * RS(1, 0) + w.z * RS(2, 0));
+  a[1] = -(w.x * RS(0, 1) + w.y * RS(1, 1) + w.z * RS(2, 1));
+  a[2] = -(w.x * RS(0, 2) + w.y * RS(1, 2) + w.z * RS(2, 2));
+  if (form == 2) {  // (-w^T R skew(p)) R^-1 diag(5e-3, 5e-3, 1)
+    const float t0 = a[0], t1 = a[1], t2 = a[2];
+    a[0] = (t0 * Rinv(0, 0) + t1 * Rinv(1, 0) + t2 * Rinv(2, 0)) * 5e-3f;
+    a[1] = (t0 * Rinv(0, 1) + t1 * Rinv(1, 1) + t2 * Rinv(2, 1)) * 5e-3f;
+    a[2] = (t0 * Rinv(0, 2) + t1 * Rinv(1, 2) + t2 * Rinv(2, 2)) * 1.f;
+  }
+  a[3] = w.x; a[4] = w.y; a[5] = w.z;
+  if (form == 0) {
+    V3<float> rp = T.rot * p;
+    float d2 = w.x * (rp.x + T.pos.x) + w.y * (rp.y + T.pos.y) + w.z * (rp.z + T.pos.z) + ci;
+    bb = -d2;
+  } else {
+    bb = -ci;
+  }
+}
+
+// The statements behind the sums of one iteration: solve, degeneracy mask (decided at iter 0, carried in is_degenerate / kz), update of T,
+// abort test.  Returns true when the loop breaks.
+//   eig_threshold 100 / 10;  mask_by_matP: X = matP X with matP = diag(0 .. 0, 1 .. 1) (Estimator.cc:1308-1339, PointMapping.cc:650-680) instead
+//   of zeroing the leading kz components (PointOdometry.cc:584-615);  left_update: rot = DeltaQ(X) * rot (MapBuilder.cc:978-979)
+inline bool GaussNewtonStep(const float AtA[36], const float AtB[6], size_t iter, float eig_threshold, bool mask_by_matP, bool left_update, double abort_r,
+                            double abort_t, Twist<float> &T, bool &is_degenerate, int &kz, float X[6]) {
+  Q<float> R0 = T.rot.normalized();  // SO3 ctor normalises (so3.hpp)
+  float Ac[36], Bc[6];
+  std::memcpy(Ac, AtA, sizeof(Ac)); std::memcpy(Bc, AtB, sizeof(Bc));
+  colpiv_qr_solve<float>(6, 6, Ac, Bc, X);
+  if (iter == 0) {
+    float E[6], V[36];
+    sym_eigen<float>(6, AtA, E, V);
+    is_degenerate = false; kz = 0;
+    for (int i = 0; i < 6; ++i) { if (E[i] < eig_threshold) { ++kz; is_degenerate = true; } else break; }
+  }
+  if (is_degenerate) {
+    if (mask_by_matP) {
+      // A.6: matP = V2 * V^-1 with leading ROWS of V zeroed == diag(0..0,1..1)
+      float matP[36], X2[6];
+      for (int k = 0; k < 36; ++k) matP[k] = 0;
+      for (int i = kz; i < 6; ++i) matP[i * 6 + i] = 1.f;
+      for (int i = 0; i < 6; ++i) { float s = 0; for (int j = 0; j < 6; ++j) s += matP[i * 6 + j] * X[j]; X2[i] = s; }
+      std::memcpy(X, X2, sizeof(X2));
+    } else {
+      for (int i = 0; i < kz; ++i) X[i] = 0.f;  // matP = diag(0..0,1..1) (A.6)
+    }
+  }
+  T.pos.x += X[3]; T.pos.y += X[4]; T.pos.z += X[5];
+  T.rot = left_update ? DeltaQ(V3<float>(X[0], X[1], X[2])) * T.rot : T.rot * DeltaQ(V3<float>(X[0], X[1], X[2]));
+  if (!std::isfinite(T.pos.x)) T.pos.x = 0;
+  if (!std::isfinite(T.pos.y)) T.pos.y = 0;
+  if (!std::isfinite(T.pos.z)) T.pos.z = 0;
+  float delta_r = RadToDeg(R0.angularDistance(T.rot));
+  float delta_t = float(std::sqrt(std::pow(X[3] * 100, 2) + std::pow(X[4] * 100, 2) + std::pow(X[5] * 100, 2)));
+  return delta_r < abort_r && delta_t < abort_t;
+}
+
 }  // namespace orc

@@ -48,7 +48,6 @@ struct PointMapping {
   std::vector<size_t> valid_idx, surround_idx;
   std::vector<ScorePointCoeff> score_point_coeff;  // descending score, insertion order among equals
   P4 point_on_z_axis{0, 0, 0, 0};
-  float matP[36];
   int last_iterations = 0, last_selected = 0;
   bool last_degenerate = false;
   int last_kz = 0;   // leading update components masked (PointMapping.cc:650-680, MapBuilder.cc:930-960)
@@ -58,7 +57,6 @@ struct PointMapping {
   explicit PointMapping(const MappingConfig &c = MappingConfig()) : cfg(c) {
     corner_array.resize(size_t(L) * Wd * H);
     surf_array.resize(size_t(L) * Wd * H);
-    for (int i = 0; i < 36; ++i) matP[i] = (i % 7 == 0) ? 1.f : 0.f;
   }
 
   static size_t ToIndex(int i, int j, int k) { return size_t(i) + size_t(L) * j + size_t(L) * Wd * k; }
@@ -263,7 +261,6 @@ struct PointMapping {
     tree_corner.Build(corner_from_map);
     tree_surf.Build(surf_from_map);
     bool is_degenerate = false;
-    for (int i = 0; i < 36; ++i) matP[i] = (i % 7 == 0) ? 1.f : 0.f;
     Transformf &T = transform_tobe_mapped;
     struct Sel { P4 ori, coeff; };
     std::vector<Sel> sel;
@@ -299,54 +296,21 @@ struct PointMapping {
       last_selected = int(sel.size());
       if (sel.size() < 50) continue;
       float AtA[36] = {0}, AtB[6] = {0};
-      Q<float> R0 = T.rot.normalized();
       M3<float> Rm = T.rot.toRotationMatrix();
       M3<float> Rinv = T.rot.inverse().toRotationMatrix();
       for (const Sel &f : sel) {
         V3<float> p(f.ori.x, f.ori.y, f.ori.z), w(f.coeff.x, f.coeff.y, f.coeff.z);
-        M3<float> RS = Rm * Skew(p);
-        float a[6];
-        a[0] = -(w.x * RS(0, 0) + w.y * RS(1, 0) + w.z * RS(2, 0));
-        a[1] = -(w.x * RS(0, 1) + w.y * RS(1, 1) + w.z * RS(2, 1));
-        a[2] = -(w.x * RS(0, 2) + w.y * RS(1, 2) + w.z * RS(2, 2));
-        if (four_dof) {  // (-w^T R skew(p)) R^-1 diag(5e-3, 5e-3, 1)
-          const float t0 = a[0], t1 = a[1], t2 = a[2];
-          a[0] = (t0 * Rinv(0, 0) + t1 * Rinv(1, 0) + t2 * Rinv(2, 0)) * 5e-3f;
-          a[1] = (t0 * Rinv(0, 1) + t1 * Rinv(1, 1) + t2 * Rinv(2, 1)) * 5e-3f;
-          a[2] = (t0 * Rinv(0, 2) + t1 * Rinv(1, 2) + t2 * Rinv(2, 2)) * 1.f;
-        }
-        a[3] = w.x; a[4] = w.y; a[5] = w.z;
-        float bb = -f.coeff.i;
+        float a[6], bb;
+        GaussNewtonMapRow(four_dof ? 2 : 1, p, w, f.coeff.i, T, Rm, Rinv, a, bb);
         for (int r = 0; r < 6; ++r) { for (int c = 0; c < 6; ++c) AtA[r * 6 + c] += a[r] * a[c]; AtB[r] += a[r] * bb; }
       }
-      float Ac[36], Bc[6], X[6];
-      std::memcpy(Ac, AtA, sizeof(AtA)); std::memcpy(Bc, AtB, sizeof(AtB));
-      colpiv_qr_solve<float>(6, 6, Ac, Bc, X);
-      if (iter == 0) {
-        float E[6], V[36];
-        sym_eigen<float>(6, AtA, E, V);
-        is_degenerate = false;
-        for (int k = 0; k < 36; ++k) matP[k] = 0;
-        int kz = 0;
-        for (int i = 0; i < 6; ++i) { if (E[i] < 100.f) { ++kz; is_degenerate = true; } else break; }  // A.6
-        for (int i = kz; i < 6; ++i) matP[i * 6 + i] = 1.f;
-        last_kz = kz;
-      }
-      if (is_degenerate) {
-        float X2[6];
-        for (int i = 0; i < 6; ++i) { float s = 0; for (int j = 0; j < 6; ++j) s += matP[i * 6 + j] * X[j]; X2[i] = s; }
-        std::memcpy(X, X2, sizeof(X));
-      }
+      float X[6];
+      int kz = last_kz;
+      const bool done = GaussNewtonStep(AtA, AtB, size_t(iter), 100.f, true, four_dof, 0.05, 0.05, T, is_degenerate, kz, X);
+      last_kz = kz;
       last_degenerate = is_degenerate;
-      T.pos.x += X[3]; T.pos.y += X[4]; T.pos.z += X[5];
-      T.rot = four_dof ? DeltaQ(V3<float>(X[0], X[1], X[2])) * T.rot : T.rot * DeltaQ(V3<float>(X[0], X[1], X[2]));
-      if (!std::isfinite(T.pos.x)) T.pos.x = 0;
-      if (!std::isfinite(T.pos.y)) T.pos.y = 0;
-      if (!std::isfinite(T.pos.z)) T.pos.z = 0;
-      float delta_r = RadToDeg(R0.angularDistance(T.rot));
-      float delta_t = std::sqrt(std::pow(X[3] * 100, 2) + std::pow(X[4] * 100, 2) + std::pow(X[5] * 100, 2));
       if (std::getenv("LIO_ORACLE_DEBUG")) std::fprintf(stderr, "[map] it %d nsel %zu X %g %g %g | %g %g %g pos %g %g %g\n", iter, sel.size(), X[0], X[1], X[2], X[3], X[4], X[5], T.pos.x, T.pos.y, T.pos.z);
-      if (delta_r < 0.05 && delta_t < 0.05) break;
+      if (done) break;
     }
     TransformUpdate();
     if (!four_dof && spc.size() >= 50) {

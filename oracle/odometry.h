@@ -114,6 +114,53 @@ struct PointOdometry {
     }
   }
 
+  // The statements of an iteration that turn a query and its correspondences into a row, shared by Process and the test hook lio_gn_rows_odom
+  // (include/lio_test_hooks.h).  :391-435 — the edge through t1, t2 and the de-skewed query: unit normal of the line in the plane of the three
+  // points (la, lb, lc), distance ld2, weight s (A.7: 1 before iteration 5).  False: the residual is not selected.
+  static bool EdgeCoefficients(const P4 &sel, const P4 &t1, const P4 &t2, size_t iter, P4 &c) {
+    float x0 = sel.x, y0 = sel.y, z0 = sel.z, x1 = t1.x, y1 = t1.y, z1 = t1.z, x2 = t2.x, y2 = t2.y, z2 = t2.z;
+    float a012 = std::sqrt(((x0 - x1) * (y0 - y2) - (x0 - x2) * (y0 - y1)) * ((x0 - x1) * (y0 - y2) - (x0 - x2) * (y0 - y1)) +
+                           ((x0 - x1) * (z0 - z2) - (x0 - x2) * (z0 - z1)) * ((x0 - x1) * (z0 - z2) - (x0 - x2) * (z0 - z1)) +
+                           ((y0 - y1) * (z0 - z2) - (y0 - y2) * (z0 - z1)) * ((y0 - y1) * (z0 - z2) - (y0 - y2) * (z0 - z1)));
+    float l12 = std::sqrt((x1 - x2) * (x1 - x2) + (y1 - y2) * (y1 - y2) + (z1 - z2) * (z1 - z2));
+    float la = ((y1 - y2) * ((x0 - x1) * (y0 - y2) - (x0 - x2) * (y0 - y1)) + (z1 - z2) * ((x0 - x1) * (z0 - z2) - (x0 - x2) * (z0 - z1))) / a012 / l12;
+    float lb = -((x1 - x2) * ((x0 - x1) * (y0 - y2) - (x0 - x2) * (y0 - y1)) - (z1 - z2) * ((y0 - y1) * (z0 - z2) - (y0 - y2) * (z0 - z1))) / a012 / l12;
+    float lc = -((x1 - x2) * ((x0 - x1) * (z0 - z2) - (x0 - x2) * (z0 - z1)) + (y1 - y2) * ((y0 - y1) * (z0 - z2) - (y0 - y2) * (z0 - z1))) / a012 / l12;
+    float ld2 = a012 / l12;
+    float s = 1;
+    if (iter >= 5) s = 1 - 1.8f * std::fabs(ld2);
+    if (s > 0.1 && ld2 != 0) { c = {s * la, s * lb, s * lc, s * ld2}; return true; }
+    return false;
+  }
+  // :497-531 — the plane through t1, t2, t3
+  static bool PlaneCoefficients(const P4 &sel, const P4 &t1, const P4 &t2, const P4 &t3, size_t iter, P4 &c) {
+    float pa = (t2.y - t1.y) * (t3.z - t1.z) - (t3.y - t1.y) * (t2.z - t1.z);
+    float pb = (t2.z - t1.z) * (t3.x - t1.x) - (t3.z - t1.z) * (t2.x - t1.x);
+    float pc = (t2.x - t1.x) * (t3.y - t1.y) - (t3.x - t1.x) * (t2.y - t1.y);
+    float pd = -(pa * t1.x + pb * t1.y + pc * t1.z);
+    float ps = std::sqrt(pa * pa + pb * pb + pc * pc);
+    pa /= ps; pb /= ps; pc /= ps; pd /= ps;
+    float pd2 = pa * sel.x + pb * sel.y + pc * sel.z + pd;
+    float s = 1;
+    if (iter >= 5) s = 1 - 1.8f * std::fabs(pd2) / std::sqrt(std::sqrt(sel.x * sel.x + sel.y * sel.y + sel.z * sel.z));
+    if (s > 0.1 && pd2 != 0) { c = {s * pa, s * pb, s * pc, s * pd2}; return true; }
+    return false;
+  }
+  // :548-571 — the row of a selected residual (point po, coefficients co) at transform_es_ = T, Rt = R(T.rot)^T
+  static void OdometryRow(const P4 &po, const P4 &co, const Twist<float> &T, const M3<float> &Rt, float a[6], float &bb) {
+    V3<float> p(po.x, po.y, po.z), w(co.x, co.y, co.z);
+    V3<float> pmt = p - T.pos;
+    V3<float> c = T.rot.conjugate() * pmt;
+    M3<float> S = Skew(c);
+    a[0] = w.x * S(0, 0) + w.y * S(1, 0) + w.z * S(2, 0);
+    a[1] = w.x * S(0, 1) + w.y * S(1, 1) + w.z * S(2, 1);
+    a[2] = w.x * S(0, 2) + w.y * S(1, 2) + w.z * S(2, 2);
+    a[3] = -(w.x * Rt(0, 0) + w.y * Rt(1, 0) + w.z * Rt(2, 0));
+    a[4] = -(w.x * Rt(0, 1) + w.y * Rt(1, 1) + w.z * Rt(2, 1));
+    a[5] = -(w.x * Rt(0, 2) + w.y * Rt(1, 2) + w.z * Rt(2, 2));
+    bb = float(-0.1 * co.i);
+  }
+
   void Process(const Cloud &sharp, Cloud less_sharp, const Cloud &flat, Cloud less_flat) {
     iterations_done_ = 0; last_num_sel_ = 0; last_kz_ = 0; es_trace_.clear();
     if (!system_inited_) {
@@ -143,19 +190,8 @@ struct PointOdometry {
               ic1[i] = closest; ic2[i] = second;
             }
             if (ic2[i] >= 0) {
-              const P4 &t1 = last_corner_[ic1[i]], &t2 = last_corner_[ic2[i]];
-              float x0 = sel.x, y0 = sel.y, z0 = sel.z, x1 = t1.x, y1 = t1.y, z1 = t1.z, x2 = t2.x, y2 = t2.y, z2 = t2.z;
-              float a012 = std::sqrt(((x0 - x1) * (y0 - y2) - (x0 - x2) * (y0 - y1)) * ((x0 - x1) * (y0 - y2) - (x0 - x2) * (y0 - y1)) +
-                                     ((x0 - x1) * (z0 - z2) - (x0 - x2) * (z0 - z1)) * ((x0 - x1) * (z0 - z2) - (x0 - x2) * (z0 - z1)) +
-                                     ((y0 - y1) * (z0 - z2) - (y0 - y2) * (z0 - z1)) * ((y0 - y1) * (z0 - z2) - (y0 - y2) * (z0 - z1)));
-              float l12 = std::sqrt((x1 - x2) * (x1 - x2) + (y1 - y2) * (y1 - y2) + (z1 - z2) * (z1 - z2));
-              float la = ((y1 - y2) * ((x0 - x1) * (y0 - y2) - (x0 - x2) * (y0 - y1)) + (z1 - z2) * ((x0 - x1) * (z0 - z2) - (x0 - x2) * (z0 - z1))) / a012 / l12;
-              float lb = -((x1 - x2) * ((x0 - x1) * (y0 - y2) - (x0 - x2) * (y0 - y1)) - (z1 - z2) * ((y0 - y1) * (z0 - z2) - (y0 - y2) * (z0 - z1))) / a012 / l12;
-              float lc = -((x1 - x2) * ((x0 - x1) * (z0 - z2) - (x0 - x2) * (z0 - z1)) + (y1 - y2) * ((y0 - y1) * (z0 - z2) - (y0 - y2) * (z0 - z1))) / a012 / l12;
-              float ld2 = a012 / l12;
-              float s = 1;
-              if (iter >= 5) s = 1 - 1.8f * std::fabs(ld2);
-              if (s > 0.1 && ld2 != 0) { ori.push_back(sharp[i]); coef.push_back({s * la, s * lb, s * lc, s * ld2}); }
+              P4 c;
+              if (EdgeCoefficients(sel, last_corner_[ic1[i]], last_corner_[ic2[i]], iter, c)) { ori.push_back(sharp[i]); coef.push_back(c); }
             }
           }
           for (size_t i = 0; i < ns; ++i) {
@@ -166,60 +202,25 @@ struct PointOdometry {
               is1[i] = closest; is2[i] = second; is3[i] = third;
             }
             if (is2[i] >= 0 && is3[i] >= 0) {
-              const P4 &t1 = last_surf_[is1[i]], &t2 = last_surf_[is2[i]], &t3 = last_surf_[is3[i]];
-              float pa = (t2.y - t1.y) * (t3.z - t1.z) - (t3.y - t1.y) * (t2.z - t1.z);
-              float pb = (t2.z - t1.z) * (t3.x - t1.x) - (t3.z - t1.z) * (t2.x - t1.x);
-              float pc = (t2.x - t1.x) * (t3.y - t1.y) - (t3.x - t1.x) * (t2.y - t1.y);
-              float pd = -(pa * t1.x + pb * t1.y + pc * t1.z);
-              float ps = std::sqrt(pa * pa + pb * pb + pc * pc);
-              pa /= ps; pb /= ps; pc /= ps; pd /= ps;
-              float pd2 = pa * sel.x + pb * sel.y + pc * sel.z + pd;
-              float s = 1;
-              if (iter >= 5) s = 1 - 1.8f * std::fabs(pd2) / std::sqrt(std::sqrt(sel.x * sel.x + sel.y * sel.y + sel.z * sel.z));
-              if (s > 0.1 && pd2 != 0) { ori.push_back(flat[i]); coef.push_back({s * pa, s * pb, s * pc, s * pd2}); }
+              P4 c;
+              if (PlaneCoefficients(sel, last_surf_[is1[i]], last_surf_[is2[i]], last_surf_[is3[i]], iter, c)) { ori.push_back(flat[i]); coef.push_back(c); }
             }
           }
           const int nsel = int(ori.size());
           last_num_sel_ = nsel;
           if (nsel < 10) { es_trace_.push_back(transform_es_); continue; }
           float AtA[36] = {0}, AtB[6] = {0};
-          Q<float> R0 = transform_es_.rot.normalized();  // SO3 ctor normalises
           M3<float> Rt = transform_es_.rot.toRotationMatrix().transpose();
           for (int i = 0; i < nsel; ++i) {
-            V3<float> p(ori[i].x, ori[i].y, ori[i].z), w(coef[i].x, coef[i].y, coef[i].z);
-            V3<float> pmt = p - transform_es_.pos;
-            V3<float> c = transform_es_.rot.conjugate() * pmt;
-            M3<float> S = Skew(c);
-            float a[6];
-            a[0] = w.x * S(0, 0) + w.y * S(1, 0) + w.z * S(2, 0);
-            a[1] = w.x * S(0, 1) + w.y * S(1, 1) + w.z * S(2, 1);
-            a[2] = w.x * S(0, 2) + w.y * S(1, 2) + w.z * S(2, 2);
-            a[3] = -(w.x * Rt(0, 0) + w.y * Rt(1, 0) + w.z * Rt(2, 0));
-            a[4] = -(w.x * Rt(0, 1) + w.y * Rt(1, 1) + w.z * Rt(2, 1));
-            a[5] = -(w.x * Rt(0, 2) + w.y * Rt(1, 2) + w.z * Rt(2, 2));
-            float bb = float(-0.1 * coef[i].i);
+            float a[6], bb;
+            OdometryRow(ori[i], coef[i], transform_es_, Rt, a, bb);
             for (int r = 0; r < 6; ++r) { for (int cc = 0; cc < 6; ++cc) AtA[r * 6 + cc] += a[r] * a[cc]; AtB[r] += a[r] * bb; }
           }
-          float Ac[36], Bc[6], X[6];
-          std::memcpy(Ac, AtA, sizeof(Ac)); std::memcpy(Bc, AtB, sizeof(Bc));
-          colpiv_qr_solve<float>(6, 6, Ac, Bc, X);
-          if (iter == 0) {
-            float E[6], V[36];
-            sym_eigen<float>(6, AtA, E, V);
-            is_degenerate = false; kz = 0;
-            for (int i = 0; i < 6; ++i) { if (E[i] < 10.f) { ++kz; is_degenerate = true; } else break; }
-            last_kz_ = kz;
-          }
-          if (is_degenerate) for (int i = 0; i < kz; ++i) X[i] = 0.f;  // matP = diag(0..0,1..1) (A.6)
-          transform_es_.pos.x += X[3]; transform_es_.pos.y += X[4]; transform_es_.pos.z += X[5];
-          transform_es_.rot = transform_es_.rot * DeltaQ(V3<float>(X[0], X[1], X[2]));
-          if (!std::isfinite(transform_es_.pos.x)) transform_es_.pos.x = 0;
-          if (!std::isfinite(transform_es_.pos.y)) transform_es_.pos.y = 0;
-          if (!std::isfinite(transform_es_.pos.z)) transform_es_.pos.z = 0;
-          float delta_r = RadToDeg(R0.angularDistance(transform_es_.rot));
-          float delta_t = float(std::sqrt(std::pow(X[3] * 100, 2) + std::pow(X[4] * 100, 2) + std::pow(X[5] * 100, 2)));
+          float X[6];
+          const bool done = GaussNewtonStep(AtA, AtB, iter, 10.f, false, false, delta_r_abort_, delta_t_abort_, transform_es_, is_degenerate, kz, X);
+          if (iter == 0) last_kz_ = kz;
           es_trace_.push_back(transform_es_);
-          if (delta_r < delta_r_abort_ && delta_t < delta_t_abort_) break;
+          if (done) break;
         }
       }
       Twist<float> se = transform_es_.inverse();

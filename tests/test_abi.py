@@ -78,7 +78,8 @@ def _declared_test_hooks():
 def test_each_test_hook_is_bound_and_exported_by_both_libraries(oracle):
     """include/lio_test_hooks.h: every hook bound in Python and exported by the product and the oracle"""
     hooks = _declared_test_hooks()
-    assert len(hooks) >= 6 and "lio_knn_walk" in hooks and "lio_fit_five" in hooks and "lio_odom_correspondences" in hooks
+    assert len(hooks) >= 10 and "lio_knn_walk" in hooks and "lio_fit_five" in hooks and "lio_odom_correspondences" in hooks
+    assert {"lio_gn_rows_map", "lio_gn_rows_odom", "lio_gn_fold", "lio_gn_step", "lio_gn_round"} <= set(hooks)
     assert set(hooks) == set(capi._TEST_SIGS.keys())
     assert not set(hooks) & set(_declared_symbols())
     dll = ctypes.CDLL(capi.HIP_LIB_PATH)
@@ -127,6 +128,58 @@ def test_test_hook_header_is_plain_c_and_links(tmp_path, oracle, lib):
                    "    if (lio_odom_correspondences(q, 1, q, 1, prev, 2, prev, 2, &T, 0.1f, 0, NULL, si, sel) != LIO_ERR_ARG) return 19;\n"
                    "    if (lio_odom_correspondences(q, 1, q, 1, prev, 2, prev, 2, &T, 0.1f, 0, ci, si, NULL) != LIO_ERR_ARG) return 20;\n"
                    "    if (ci[0] != 7 || si[2] != 7 || sel[5] != 7) return 21;\n"
+                   "  }\n"
+                   "  {\n"
+                   "    float stack[4] = {1, 2, 3, 0}, coeff[4] = {0, 0, 1, -3}, rows[7] = {7, 7, 7, 7, 7, 7, 7};\n"
+                   "    uint8_t valid[1] = {1}, ok[1] = {7};\n"
+                   "    int32_t nb = 7;\n"
+                   "    double part[28], sums[28] = {0};\n"
+                   "    lio_transform_f T = {{0, 0, 0, 1}, {0, 0, 0}};\n"
+                   "    lio_gn_state st = {{0, 0, 0, 1, 0, 0, 0, 0}, 0, 0, 0, 0, 0}, out = {{7, 7, 7, 7, 7, 7, 7, 7}, 7, 7, 7, 7, 7};\n"
+                   "    part[0] = 7;\n"
+                   "    if (lio_gn_rows_map(3, stack, 1, valid, coeff, &T, ok, rows, &nb, part) != LIO_ERR_ARG) return 22;\n"
+                   "    if (lio_gn_rows_map(0, NULL, 1, valid, coeff, &T, ok, rows, &nb, part) != LIO_ERR_ARG) return 23;\n"
+                   "    if (lio_gn_rows_map(0, stack, 1, valid, coeff, NULL, ok, rows, &nb, part) != LIO_ERR_ARG) return 24;\n"
+                   "    if (lio_gn_rows_map(0, stack, 1, valid, coeff, &T, ok, rows, NULL, part) != LIO_ERR_ARG) return 25;\n"
+                   "    if (lio_gn_rows_map(0, stack, 1, valid, coeff, &T, ok, rows, &nb, NULL) != LIO_ERR_ARG) return 26;\n"
+                   "    if (ok[0] != 7 || rows[6] != 7 || nb != 7 || part[0] != 7) return 27;\n"
+                   "    if (lio_gn_fold(NULL, 2, 0, sums) != LIO_ERR_ARG) return 28;\n"
+                   "    if (lio_gn_fold(part, 1, 2, sums) != LIO_ERR_ARG) return 29;\n"
+                   "    if (lio_gn_fold(part, -1, 1, sums) != LIO_ERR_ARG) return 30;\n"
+                   "    if (lio_gn_fold(part, 1, 1, NULL) != LIO_ERR_ARG) return 31;\n"
+                   "    if (lio_gn_step(2, sums, &st, 0, 0, 0, &out) != LIO_ERR_ARG) return 32;\n"
+                   "    if (lio_gn_step(0, NULL, &st, 0, 0, 0, &out) != LIO_ERR_ARG) return 33;\n"
+                   "    if (lio_gn_step(0, sums, NULL, 0, 0, 0, &out) != LIO_ERR_ARG) return 34;\n"
+                   "    if (lio_gn_step(0, sums, &st, -1, 0, 0, &out) != LIO_ERR_ARG) return 35;\n"
+                   "    if (lio_gn_step(1, sums, &st, 0, 0, 1, &out) != LIO_ERR_ARG) return 36;\n"
+                   "    if (lio_gn_step(0, sums, &st, 0, 0, 0, NULL) != LIO_ERR_ARG) return 37;\n"
+                   "    if (out.T[0] != 7 || out.nsel != 7) return 38;\n"
+                   "    if (lio_gn_round(stack, 1, stack, 1, &T, 1.0f, 0.2f, 2, &nb, part, &out) != LIO_ERR_ARG) return 39;\n"
+                   "    if (lio_gn_round(NULL, 1, stack, 1, &T, 1.0f, 0.2f, 8, &nb, part, &out) != LIO_ERR_ARG) return 40;\n"
+                   "    if (lio_gn_round(stack, 1, stack, 1, NULL, 1.0f, 0.2f, 8, &nb, part, &out) != LIO_ERR_ARG) return 41;\n"
+                   "    if (lio_gn_round(stack, 1, stack, 1, &T, 0.0f, 0.2f, 8, &nb, part, &out) != LIO_ERR_ARG) return 42;\n"
+                   "    if (lio_gn_round(stack, 1, stack, 1, &T, 1.0f, 0.2f, 8, &nb, part, NULL) != LIO_ERR_ARG) return 43;\n"
+                   "    if (nb != 7 || part[0] != 7 || out.kz != 7) return 44;\n"
+                   "    {\n"
+                   "      float q4[4] = {0, 0, 0, 0}, prev[12] = {0, 0, 0, 0, 1, 1, 1, 1, 2, 0, 1, 2};\n"
+                   "      int32_t ci[2] = {0, 1}, si[3] = {0, 1, 2}, far[2] = {0, 3}, lone[3] = {-1, 1, 2};\n"
+                   "      if (lio_gn_rows_odom(NULL, 1, q4, 1, prev, 3, prev, 3, ci, si, &T, 0.1f, 1, 0, ok, rows, &nb, part) != LIO_ERR_ARG) return 45;\n"
+                   "      if (lio_gn_rows_odom(q4, 1, NULL, 1, prev, 3, prev, 3, ci, si, &T, 0.1f, 1, 0, ok, rows, &nb, part) != LIO_ERR_ARG) return 46;\n"
+                   "      if (lio_gn_rows_odom(q4, 1, q4, 1, NULL, 3, prev, 3, ci, si, &T, 0.1f, 1, 0, ok, rows, &nb, part) != LIO_ERR_ARG) return 47;\n"
+                   "      if (lio_gn_rows_odom(q4, 1, q4, 1, prev, 3, NULL, 3, ci, si, &T, 0.1f, 1, 0, ok, rows, &nb, part) != LIO_ERR_ARG) return 48;\n"
+                   "      if (lio_gn_rows_odom(q4, 1, q4, 1, prev, 3, prev, 3, NULL, si, &T, 0.1f, 1, 0, ok, rows, &nb, part) != LIO_ERR_ARG) return 49;\n"
+                   "      if (lio_gn_rows_odom(q4, 1, q4, 1, prev, 3, prev, 3, ci, NULL, &T, 0.1f, 1, 0, ok, rows, &nb, part) != LIO_ERR_ARG) return 50;\n"
+                   "      if (lio_gn_rows_odom(q4, 1, q4, 1, prev, 3, prev, 3, ci, si, NULL, 0.1f, 1, 0, ok, rows, &nb, part) != LIO_ERR_ARG) return 51;\n"
+                   "      if (lio_gn_rows_odom(q4, 1, q4, 1, prev, 3, prev, 3, ci, si, &T, 0.0f, 1, 0, ok, rows, &nb, part) != LIO_ERR_ARG) return 52;\n"
+                   "      if (lio_gn_rows_odom(q4, 1, q4, 1, prev, 3, prev, 3, ci, si, &T, 0.1f, 1, -1, ok, rows, &nb, part) != LIO_ERR_ARG) return 53;\n"
+                   "      if (lio_gn_rows_odom(q4, 1, q4, 1, prev, 3, prev, 3, ci, si, &T, 0.1f, 1, 0, NULL, rows, &nb, part) != LIO_ERR_ARG) return 54;\n"
+                   "      if (lio_gn_rows_odom(q4, 1, q4, 1, prev, 3, prev, 3, ci, si, &T, 0.1f, 1, 0, ok, NULL, &nb, part) != LIO_ERR_ARG) return 55;\n"
+                   "      if (lio_gn_rows_odom(q4, 1, q4, 1, prev, 3, prev, 3, ci, si, &T, 0.1f, 1, 0, ok, rows, NULL, part) != LIO_ERR_ARG) return 56;\n"
+                   "      if (lio_gn_rows_odom(q4, 1, q4, 1, prev, 3, prev, 3, ci, si, &T, 0.1f, 1, 0, ok, rows, &nb, NULL) != LIO_ERR_ARG) return 57;\n"
+                   "      if (lio_gn_rows_odom(q4, 1, q4, 1, prev, 3, prev, 3, far, si, &T, 0.1f, 1, 0, ok, rows, &nb, part) != LIO_ERR_ARG) return 58;\n"
+                   "      if (lio_gn_rows_odom(q4, 1, q4, 1, prev, 3, prev, 3, ci, lone, &T, 0.1f, 1, 0, ok, rows, &nb, part) != LIO_ERR_ARG) return 59;\n"
+                   "      if (ok[0] != 7 || rows[6] != 7 || nb != 7 || part[0] != 7) return 60;\n"
+                   "    }\n"
                    "  }\n"
                    '  puts("hooks ok");\n  return 0;\n}\n')
     exe = tmp_path / "hooks"
