@@ -71,7 +71,7 @@ int lio_fit_five(int form, const float *nbr_xyz, const float *fifth_sqd, const f
                  const float *fixed_pz, float min_match_sq_dis, float min_plane_dis, uint8_t *valid, float *coeff, float *score,
                  float *abs_coeff);
 
-/* The correspondence search every scan-to-scan residual starts from (csrc/odometry.hip: k_odo_corr, one wave per query, launched by
+/* The correspondence search every scan-to-scan residual starts from (csrc/odometry.hip: k_ob_corr, one wave per query, launched by
  * PointOdometry's Process at every fifth iteration), on its own and stateless: PointOdometry.cc:237-259 (TransformToStart), :342-385
  * (corner: closest and second), :440-494 (surf: closest, second and third).  Clouds are xyzi, intensity = ring + relative time.
  *   sel      TransformToStart of the query at transform_es: s = (1 / scan_period) * (intensity - int(intensity)), 0 with no_deskew;
@@ -92,8 +92,8 @@ int lio_fit_five(int form, const float *nbr_xyz, const float *fifth_sqd, const f
  * The previous clouds are expected finite.  Empty previous clouds give all -1; n_sharp == n_flat == 0 is fine.  A null required pointer
  * (a cloud pointer may be null when its count is 0) or a scan_period that is not positive and finite: LIO_ERR_ARG.  The > 10 / > 100
  * size gate of Process (:335) is not applied.
- * Product: uploads the clouds into a device object of its own, builds the two 5 m grids with the function Process uses
- * (OdometryDev::BuildGrids), launches k_odo_corr ONCE through the launch statement Process uses, and fills sel_out from a separate
+ * Product: uploads the clouds into a device object of its own, fills the one-sensor table and builds the two 5 m grids with the steps
+ * Process runs (OdoChain::FillTable, OdoChain::MakeGrids), launches k_ob_corr ONCE over that table, and fills sel_out from a separate
  * one-query-per-lane kernel that calls the same odo_to_start.  Oracle: the functions its own Process loop calls, serially. */
 int lio_odom_correspondences(const float *sharp_xyzi, size_t n_sharp, const float *flat_xyzi, size_t n_flat,
                              const float *last_corner_xyzi, size_t n_last_corner, const float *last_surf_xyzi, size_t n_last_surf,
@@ -102,7 +102,7 @@ int lio_odom_correspondences(const float *sharp_xyzi, size_t n_sharp, const floa
                              float *sel_out /* (n_sharp + n_flat) x 3, sharp first */);
 
 /* ---- The 6x6 Gauss-Newton loops from the rows onward.  Every pose of the product passes through one of three loops — scan-to-scan
- * odometry (csrc/odometry.hip: k_odo_rows, k_odo_update, and the batch's k_ob_*), scan-to-map and the keyframe batch
+ * odometry (csrc/odometry.hip: k_ob_rows, k_ob_update, for one sensor and for a batch), scan-to-map and the keyframe batch
  * (csrc/cloud_kernels.hip: k_odom_rows / k_kf_rows with k_odom_update / k_kf_update) and the estimator's newest-frame loop (k_odom_round,
  * k_odom_update_wide, and k_bw_odom_round / k_bw_odom_update of the batched windows) — and all of them form fp32 rows (A | b) per selected
  * residual, add a_i a_j, a_i b and a count into 28 fp64 sums through a chain of folds, and run one serial step on the sums.  The sums
@@ -135,7 +135,7 @@ typedef struct {
 int lio_gn_rows_map(int form, const float *stack_xyzi, size_t m, const uint8_t *valid, const float *coeff, const lio_transform_f *T,
                     uint8_t *ok_out, float *rows_out, int32_t *nb_out, double *partials_out);
 
-/* The rows of the scan-to-scan loop (csrc/odometry.hip: odo_row_coeff and odo_row_of, the two functions k_odo_rows and the batch's k_ob_rows form every row
+/* The rows of the scan-to-scan loop (csrc/odometry.hip: odo_row_coeff and odo_row_of, the two functions k_ob_rows forms every row
  * with) and the partials of ONE production rows launch, on caller-given clouds and correspondences: PointOdometry.cc:391-435 (edge
  * coefficients), :497-531 (plane coefficients), A.7 (the weight s, 1 before iteration 5), :548-571 (the row).  Clouds, transform_es,
  * scan_period and no_deskew as in lio_odom_correspondences; corner_idx (n_sharp x 2) and surf_idx (n_flat x 3) as it returns them or as
@@ -149,7 +149,7 @@ int lio_gn_rows_map(int form, const float *stack_xyzi, size_t m, const uint8_t *
  * read the closest point whenever the others exist; so -1 in the closest slot is a case only together with -1 in the others, never on
  * its own), a null required pointer, a non-finite transform, a scan_period that is not positive
  * and finite, or a negative iter: LIO_ERR_ARG.
- * Product: uploads into a device object of its own, launches k_odo_rows ONCE through the statement Process uses; rows_out comes from a
+ * Product: uploads into a device object of its own, launches k_ob_rows ONCE over the one-sensor table Process fills; rows_out comes from a
  * separate one-query-per-lane kernel that calls the same two functions.  Oracle: the functions its own Process loop calls, serially;
  * nb_out = 1 and one partial of plain fp64 sums of the fp32 products. */
 int lio_gn_rows_odom(const float *sharp_xyzi, size_t n_sharp, const float *flat_xyzi, size_t n_flat, const float *last_corner_xyzi,
@@ -158,7 +158,7 @@ int lio_gn_rows_odom(const float *sharp_xyzi, size_t n_sharp, const float *flat_
                      int32_t *nb_out, double *partials_out);
 
 /* The fixed-order fold of `nblocks` partials (28 doubles each) into sums_out[28].
- *   wide 0   reduce_partials28 (csrc/cloud_kernels.h) on a 256-thread block: k_odom_update, k_kf_update, k_odo_update, k_ob_update
+ *   wide 0   reduce_partials28 (csrc/cloud_kernels.h) on a 256-thread block: k_odom_update, k_kf_update, k_ob_update
  *   wide 1   fold_partials28_wide (csrc/cloud_device.h) on a 1024-thread block: k_odom_update_wide, k_bw_odom_update
  * One launch that calls the production function and copies the 28 shared sums out.  nblocks == 0 gives zeros.  The oracle adds the rows
  * serially, ascending.  A null pointer (partials may be null when nblocks is 0), a negative nblocks or another `wide`: LIO_ERR_ARG. */

@@ -273,15 +273,30 @@ lio_odom *lio_odom_create(float scan_period, int io_ratio, int max_iter, int no_
   return h;
 }
 void lio_odom_destroy(lio_odom *h) { delete h; }
+// the handles' devices in the caller's order; false: the same handle twice
+static bool odom_devices(lio_odom *const *handles, int n, std::vector<OdometryDev *> &o) {
+  for (int k = 0; k < n; ++k) o.push_back(handles[k]->o.get());
+  std::vector<OdometryDev *> sorted = o;
+  std::sort(sorted.begin(), sorted.end());
+  return std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end();
+}
+// what a step hands back per sensor; every array is optional
+static void odom_results(OdometryDev *const *o, int n, lio_transform_f *Tsum, lio_transform_f *Tes, int32_t *iters, int32_t *nsel) {
+  for (int k = 0; k < n; ++k) {
+    const OdometryDev &d = *o[k];
+    if (Tsum) fromT(d.transform_sum_, &Tsum[k]);
+    if (Tes) fromT(d.transform_es_, &Tes[k]);
+    if (iters) iters[k] = d.iterations_done_;
+    if (nsel) nsel[k] = d.last_num_sel_;
+  }
+}
 int lio_odom_process(lio_odom *h, const float *sharp, size_t n_sharp, const float *less_sharp, size_t n_ls, const float *flat, size_t n_flat,
                      const float *less_flat, size_t n_lf, lio_transform_f *Tsum, lio_transform_f *Tes, int *iters, int *nsel) {
   if (!h || (!sharp && n_sharp) || (!less_sharp && n_ls) || (!flat && n_flat) || (!less_flat && n_lf)) return LIO_ERR_ARG;
   return guarded([&] {
-    h->o->Process(sharp, n_sharp, less_sharp, n_ls, flat, n_flat, less_flat, n_lf);
-    if (Tsum) fromT(h->o->transform_sum_, Tsum);
-    if (Tes) fromT(h->o->transform_es_, Tes);
-    if (iters) *iters = h->o->iterations_done_;
-    if (nsel) *nsel = h->o->last_num_sel_;
+    OdometryDev *o = h->o.get();
+    o->Process(sharp, n_sharp, less_sharp, n_ls, flat, n_flat, less_flat, n_lf);
+    odom_results(&o, 1, Tsum, Tes, iters, nsel);
     return LIO_OK;
   });
 }
@@ -295,18 +310,9 @@ int lio_odom_process_batch(lio_odom *const *handles, int n_sensors, const float 
     if (!handles[k] || (!sharp[k] && n_sharp[k]) || (!less_sharp[k] && n_ls[k]) || (!flat[k] && n_flat[k]) || (!less_flat[k] && n_lf[k])) return LIO_ERR_ARG;
   return guarded([&] {
     std::vector<OdometryDev *> o;
-    for (int k = 0; k < n_sensors; ++k) o.push_back(handles[k]->o.get());
-    std::vector<OdometryDev *> sorted = o;
-    std::sort(sorted.begin(), sorted.end());
-    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return int(LIO_ERR_ARG);   // the same handle twice
+    if (!odom_devices(handles, n_sensors, o)) return int(LIO_ERR_ARG);
     OdometryDev::ProcessBatch(o.data(), n_sensors, sharp, n_sharp, less_sharp, n_ls, flat, n_flat, less_flat, n_lf);
-    for (int k = 0; k < n_sensors; ++k) {
-      const OdometryDev &d = *o[size_t(k)];
-      if (Tsum) fromT(d.transform_sum_, &Tsum[k]);
-      if (Tes) fromT(d.transform_es_, &Tes[k]);
-      if (iters) iters[k] = d.iterations_done_;
-      if (nsel) nsel[k] = d.last_num_sel_;
-    }
+    odom_results(o.data(), n_sensors, Tsum, Tes, iters, nsel);
     return int(LIO_OK);
   });
 }
@@ -321,10 +327,7 @@ int lio_odom_process_batch_from_pp(lio_odom *const *handles, lio_pp *const *pp, 
   return guarded([&] {
     const size_t n = size_t(n_sensors);
     std::vector<OdometryDev *> o;
-    for (size_t k = 0; k < n; ++k) o.push_back(handles[k]->o.get());
-    std::vector<OdometryDev *> sorted = o;
-    std::sort(sorted.begin(), sorted.end());
-    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return int(LIO_ERR_ARG);   // the same handle twice
+    if (!odom_devices(handles, n_sensors, o)) return int(LIO_ERR_ARG);
     std::vector<lio_pp_pool *> pools;
     for (size_t k = 0; k < n; ++k)
       if (pp[k]->pool && pp[k]->pool_sweep >= 0) pools.push_back(pp[k]->pool.get());
@@ -351,13 +354,7 @@ int lio_odom_process_batch_from_pp(lio_odom *const *handles, lio_pp *const *pp, 
     }
     OdometryDev::ProcessBatch(o.data(), n_sensors, src[0].data(), cnt[0].data(), src[1].data(), cnt[1].data(), src[2].data(), cnt[2].data(), src[3].data(),
                               cnt[3].data(), true);
-    for (size_t k = 0; k < n; ++k) {
-      const OdometryDev &d = *o[k];
-      if (Tsum) fromT(d.transform_sum_, &Tsum[k]);
-      if (Tes) fromT(d.transform_es_, &Tes[k]);
-      if (iters) iters[k] = d.iterations_done_;
-      if (nsel) nsel[k] = d.last_num_sel_;
-    }
+    odom_results(o.data(), n_sensors, Tsum, Tes, iters, nsel);
     return int(LIO_OK);
   });
 }
@@ -731,7 +728,7 @@ int lio_odom_correspondences(const float *sharp, size_t n_sharp, const float *fl
   if ((!sharp && n_sharp) || (!flat && n_flat) || (!last_corner && n_lc) || (!last_surf && n_lsf) || !T || !corner_idx || !surf_idx || !sel_out)
     return LIO_ERR_ARG;
   if (!(scan_period > 0) || !std::isfinite(scan_period)) return LIO_ERR_ARG;
-  if (n_sharp + n_flat > size_t(INT_MAX) / 4 || n_lc > size_t(1) << 24 || n_lsf > size_t(1) << 24) return LIO_ERR_CAPACITY;   // k_odo_corr's scan-order keys
+  if (n_sharp + n_flat > size_t(INT_MAX) / 4 || n_lc > size_t(1) << 24 || n_lsf > size_t(1) << 24) return LIO_ERR_CAPACITY;   // odo_corr_body's scan-order keys
   return guarded([&] {
     OdometryDev od(scan_period, 1, 1, no_deskew != 0);   // stateless: a device object of its own, gone on return
     od.Correspondences(sharp, n_sharp, flat, n_flat, last_corner, n_lc, last_surf, n_lsf, toT(*T), corner_idx, surf_idx, sel_out);

@@ -8,8 +8,7 @@
 
 namespace lio {
 
-struct OdoArgs;
-struct OdoBatchScratch;
+struct OdoChain;
 
 class OdometryDev {
  public:
@@ -17,9 +16,9 @@ class OdometryDev {
   ~OdometryDev();
   void Process(const float *sharp, size_t n_sharp, const float *less_sharp, size_t n_ls, const float *flat, size_t n_flat, const float *less_flat,
                size_t n_lf);
-  // Process for n independent sensors, one sweep each, through one launch chain on o[0]'s stream (lio_odom_process_batch,
-  // include/lio_odom_batch.h): array k of every argument belongs to o[k]; every sensor ends in the state Process alone leaves, bit for
-  // bit.  The chain's scratch stays with o[0].  Sensors whose max_iter differ are processed one after the other.
+  // n independent sensors, one sweep each, through one launch chain on o[0]'s stream (lio_odom_process_batch, include/lio_odom_batch.h):
+  // array k of every argument belongs to o[k].  Process is the chain of one, and every sensor of a batch ends in the state it leaves, bit
+  // for bit.  The chain's scratch stays with o[0].  Sensors whose max_iter differ are processed one after the other, a chain of one each.
   // on_device (lio_odom_process_batch_from_pp, include/lio_frontend_batch.h): the clouds lie in device memory, complete and left alone until
   // the call returns; one launch copies them and sets every sensor's starting state, no copy per sensor.
   static void ProcessBatch(OdometryDev *const *o, int n, const float *const *sharp, const size_t *n_sharp, const float *const *less_sharp,
@@ -45,6 +44,7 @@ class OdometryDev {
   bool enable_odom_ = true;
 
  private:
+  friend struct OdoChain;
   float scan_period_, time_factor_;
   int io_ratio_, max_iter_;
   bool no_deskew_, inited_ = false;
@@ -52,26 +52,15 @@ class OdometryDev {
   DBuf<float4> sharp_, flat_, less_sharp_, less_flat_, last_corner_, last_surf_, full_;
   bool to_end_ready_ = false;  // a Process has run TransformToEnd: d_state_ holds the transform_es_ it used
   size_t n_last_corner_ = 0, n_last_surf_ = 0;
-  DBuf<int> idx_;              // 2*nc + 3*ns correspondence indices
   DBuf<OdomState> d_state_;
-  DBuf<double> d_partials_;
-  DBuf<float> d_trace_;        // 8 floats per iteration, written by k_odo_update
-  std::vector<float> h_trace_;
-  void BuildGrids();
-  void ProcessFrom(const float *sharp, size_t n_sharp, const float *less_sharp, size_t n_ls, const float *flat, size_t n_flat, const float *less_flat,
-                   size_t n_lf, bool on_device);
   void Accumulate(const OdomState &st);   // the host's end of a step that ran with the odometry enabled (:654-663)
-  std::unique_ptr<OdoBatchScratch> batch_;   // ProcessBatch with this handle first: argument table, partials, indices, traces, mailbox
-  OdoArgs Args(size_t n_sharp, size_t n_flat) const;
-  DBuf<float> d_sel_;          // 3 floats per query (Correspondences)
-  KnnGrid grid_c_, grid_s_;
-  DBuf<float> partial_c_, partial_s_;
-  DBuf<VoxParams> bounds_;
-  HostBuf<VoxParams> h_bounds_;    // allocated on first use
-  HostBuf<char> h_mail_;           // pinned, coherent, allocated on first use: the state's mailbox
-  OdomState *h_state_ = nullptr;   // ... the state in it
-  unsigned *h_flag_ = nullptr;     // its completion word
-  unsigned seq_ = 0;
+  std::unique_ptr<OdoChain> chain_;       // the chain of the calls with this handle first (allocated on first use): table, indices, partials, traces, mailbox
+  OdoChain &Chain();
+  // the table and grids of a chain of this handle alone over caller-given clouds and transform_es_ (Correspondences, Rows)
+  OdoChain &HookTable(const float *sharp, size_t n_sharp, const float *flat, size_t n_flat, const float *last_corner, size_t n_last_corner,
+                      const float *last_surf, size_t n_last_surf, const Rigid<float> &T);
+  DBuf<float> d_sel_;          // 3 floats per query (Correspondences), 7 (Rows)
+  KnnGrid grid_c_, grid_s_;    // the grids over last_corner_ / last_surf_ that exceed LIO_ODOM_BATCH_GRID_CELLS_MAX cells
 };
 
 // the scan-to-scan step (odo_update_step) on device sums and a device state, in place (lio_gn_step family 1, include/lio_test_hooks.h)

@@ -1,16 +1,18 @@
-// odometry.hip — gfx950 kernels + host loop of the LOAM scan-to-scan step (see odometry.h).
+// odometry.hip — gfx950 kernels + host chain of the LOAM scan-to-scan step (see odometry.h).
 //
-//   k_odo_corr   one wavefront per feature point: TransformToStart, exact nearest neighbour over the previous
-//                sweep's cloud (lane-strided brute force: <= 40 k points, L2 resident), then the +-2.5-ring
-//                window scan of PointOdometry.cc:353-380 / :451-488 in 64-wide chunks.  The sequential
-//                "first strictly smaller wins" selection is reproduced as argmin over (distance, scan order);
-//                the early `break` on the ring bound is reproduced with a ballot inside the chunk.
-//   k_odo_rows   edge / plane coefficients (:391-435, :497-531), weights (A.7), rows of A and B (:548-571),
-//                reduced to per-block partials.
-//   k_odo_update 6x6 solve, degeneracy mask (threshold 10, A.6), update, abort test (:573-650).
-//   k_odo_to_end TransformToEnd (:262-292).
-//   k_odo_sel    TransformToStart of every query on its own, one query per lane (the test hook lio_odom_correspondences).
+// One launch chain serves one sensor and a batch of them alike: every sensor has a record of a device table (OdoBatchRec) with its own clouds,
+// state, grids and slices, and lio_odom_process is a batch of one.  The device bodies are stated once (odo_*_body); per iteration
+//   k_ob_corr    one wavefront per feature point: TransformToStart, exact nearest neighbour over the previous sweep's cloud (the 27 cells of
+//                a 5 m grid around the query), then the +-2.5-ring window scan of PointOdometry.cc:353-380 / :451-488 in 64-wide chunks.  The
+//                sequential "first strictly smaller wins" selection is reproduced as argmin over (distance, scan order); the early `break`
+//                on the ring bound is reproduced with a ballot inside the chunk.  Every fifth iteration.
+//   k_ob_rows    edge / plane coefficients (:391-435, :497-531), weights (A.7), rows of A and B (:548-571), reduced to per-block partials.
+//   k_ob_update  6x6 solve, degeneracy mask (threshold 10, A.6), update, abort test (:573-650).
+// and around them k_ob_take (the clouds from the feature extraction), k_ob_bounds .. k_ob_cell_place (the grids over the previous clouds, all
+// sensors' side by side) and k_ob_to_end (TransformToEnd, :262-292).  k_odo_to_end is TransformToEnd of a caller's cloud (FullToEnd).
 // The <= 25 rounds run without a host round trip except a convergence peek every 5 rounds.
+// The test hooks (include/lio_test_hooks.h) build the same table for one sensor and launch k_ob_corr or k_ob_rows once over it; k_odo_sel and
+// k_gn_rows_odom give them every query's sel and row on its own, k_gn_odo_step the 6x6 step on caller-given sums.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -61,8 +63,8 @@ __device__ inline void wave_argmin(float &d, int &key) {
   }
 }
 
-// The device bodies below are stated once: the k_odo_* kernels run them for one sensor, the k_ob_* kernels for the sensors of a batch
-// (lio_odom_process_batch), each sensor with its own arguments, state and slices, so that a sensor computes the same bits either way.
+// The device bodies below take one sensor's arguments, state and slices: the k_ob_* kernels run them for every sensor of a table, so a sensor
+// computes the same bits alone and in any batch.
 // query qi of one sensor by one wavefront (lane = 0 .. 63)
 __device__ __forceinline__ void odo_corr_body(const OdoArgs &a, const OdomState *__restrict__ st, int *__restrict__ idx, const int qi, const int lane) {
   if (st->converged) return;
@@ -183,17 +185,7 @@ __device__ __forceinline__ void odo_corr_body(const OdoArgs &a, const OdomState 
   }
 }
 
-__global__ void __launch_bounds__(64) k_odo_corr(OdoArgs a, const OdomState *__restrict__ st, int *__restrict__ idx) {
-  odo_corr_body(a, st, idx, blockIdx.x, threadIdx.x);
-}
-
-// The one statement of the correspondence launch: Process (every fifth iteration) and the test hook lio_odom_correspondences
-static void launch_odo_corr(const OdoArgs &a, const OdomState *st, int *idx, hipStream_t s) {
-  const int nq = a.nc + a.ns;
-  if (nq > 0) hipLaunchKernelGGL(k_odo_corr, dim3(nq), dim3(64), 0, s, a, st, idx);
-}
-
-// sel of every query (sharp first), as k_odo_corr and k_odo_rows see it: 3 floats per query
+// sel of every query (sharp first), as odo_corr_body and odo_row_coeff see it: 3 floats per query
 __global__ void __launch_bounds__(256) k_odo_sel(OdoArgs a, const OdomState *__restrict__ st, float *__restrict__ sel_out) {
   const int qi = blockIdx.x * blockDim.x + threadIdx.x;
   if (qi >= a.nc + a.ns) return;
@@ -312,16 +304,6 @@ __device__ __forceinline__ void odo_rows_body(const OdoArgs &a, const OdomState 
     partials[block * 28 + threadIdx.x] = v;
   }
 }
-__global__ void __launch_bounds__(ODO_ROW_THREADS) k_odo_rows(OdoArgs a, const OdomState *__restrict__ st, const int *__restrict__ idx, int iter,
-                                                              double *__restrict__ partials) {
-  odo_rows_body(a, st, idx, iter, partials, blockIdx.x, gridDim.x);
-}
-
-// The one statement of the rows launch: Process (every iteration) and the test hook lio_gn_rows_odom
-static int odo_rows_blocks(int nq) { return std::max(1, std::min(cdiv(nq, ODO_ROW_THREADS), 64)); }
-static void launch_odo_rows(const OdoArgs &a, const OdomState *st, const int *idx, int iter, double *partials, int nb, hipStream_t s) {
-  hipLaunchKernelGGL(k_odo_rows, dim3(nb), dim3(ODO_ROW_THREADS), 0, s, a, st, idx, iter, partials);
-}
 // the row of every query on its own (lio_gn_rows_odom): one query per lane through odo_row_coeff and odo_row_of; 7 floats (r0 .. r5, b), zeros and ok = 0
 // where the query has no row
 __global__ void __launch_bounds__(256) k_gn_rows_odom(OdoArgs a, const OdomState *__restrict__ st, const int *__restrict__ idx, int iter,
@@ -341,7 +323,7 @@ __global__ void __launch_bounds__(256) k_gn_rows_odom(OdoArgs a, const OdomState
   rows_out[size_t(qi) * 7 + 6] = ok ? bb : 0.f;
 }
 
-// the serial 6x6 step of one iteration (thread 0); see k_odo_update
+// the serial 6x6 step of one iteration (thread 0); see odo_update_body
 __device__ __forceinline__ void odo_update_step(const double *ssum, OdomState *st, int iter);
 // mail / sig: at the iterations where the host looks at the convergence flag (every fifth) the state is posted to its mailbox
 // (dev.h: HostSignal) instead of being fetched with a copy + stream synchronisation
@@ -361,10 +343,6 @@ __device__ __forceinline__ void odo_update_body(const double *__restrict__ parti
     __syncthreads();
     if (threadIdx.x < 64) post_host_mail(sig, mail, st, int(sizeof(OdomState) / 4), threadIdx.x);
   }
-}
-__global__ void k_odo_update(const double *__restrict__ partials, int nblocks, OdomState *st, int iter, OdomState *mail, HostSignal sig,
-                             float *__restrict__ trace) {
-  odo_update_body(partials, nblocks, st, iter, mail, sig, trace);
 }
 __device__ __forceinline__ void odo_update_step(const double *ssum, OdomState *st, int iter) {
   double sum[28];
@@ -436,8 +414,8 @@ __global__ void __launch_bounds__(256) k_odo_to_end(const float4 *in, float4 *ou
   odo_to_end_body(in, out, i, st, time_factor, no_deskew);
 }
 
-// ---- the batch (lio_odom_process_batch): the same bodies, every sensor with its own record of a device table
-// One sensor of a batch.  Iterating sensors come first in the table (the k_ob_corr / k_ob_rows / k_ob_update launches cover only them);
+// ---- the chain's kernels: the bodies above, every sensor with its own record of a device table
+// One sensor of a call (lio_odom_process: the only one).  Iterating sensors come first in the table (the k_ob_corr / k_ob_rows / k_ob_update launches cover only them);
 // behind them those that only carry their clouds to the sweep's end (previous clouds too small to iterate: `a` holds time_factor and
 // no_deskew alone).
 struct OdoBatchRec {
@@ -490,7 +468,7 @@ __global__ void __launch_bounds__(256) k_ob_to_end(const OdoBatchRec *__restrict
 }
 
 // ---- the segmented grid build: launch_cloud_bounds and KnnGrid::build of all 2 * nA previous clouds in five launches.  Grid `y` of a launch is
-// cloud y & 1 of sensor y >> 1.  The bounds are folded by the device code of the single path's (vox_block_partial, vox_fold_bounds: min and
+// cloud y & 1 of sensor y >> 1.  The bounds are folded by the device code of launch_cloud_bounds (vox_block_partial, vox_fold_bounds: min and
 // max do not hang on the order, the count is an exact float sum), the cells are keyed and the points placed by k_cell_count's and
 // k_cell_place's bodies.  A grid's run starts are offsets into the batch's ONE sorted array, which is all odo_corr_body asks of them.
 __global__ void __launch_bounds__(VOX_TILE) k_ob_bounds(const OdoBatchRec *__restrict__ recs, float *__restrict__ partial_all) {
@@ -559,9 +537,23 @@ __global__ void __launch_bounds__(256) k_ob_take(const OdoTakeRec *__restrict__ 
   if (i < r.n[c]) r.dst[c][i] = r.src[c][i];
 }
 
-// The chain's scratch, kept by the first handle of a batch.  No results live here: the states and clouds are the handles' own, and the grids
-// of a call are rebuilt by every call from the handles' previous clouds.
-struct OdoBatchScratch {
+// One call's chain over the table, and its scratch, kept by the first handle of the call.  No results live here: the states and clouds are the
+// handles' own, and the grids of a call are rebuilt by every call from the handles' previous clouds.  The steps run in the order they are
+// declared in; ProcessBatch runs all five, the test hooks the table and the grids in front of one launch of their own.
+struct OdoChain {
+  // ---- the call
+  OdometryDev *const *o = nullptr;   // its handles; the chain runs on o[0]'s stream (the other handles are idle: every entry point returns synchronised)
+  hipStream_t s = nullptr;
+  int max_iter = 0;
+  std::vector<int> act, idle;        // who iterates, and who only carries its clouds to the sweep's end; the table holds `act`, then `idle`
+  std::vector<OdomState> st, got;    // per handle: the state it starts from and ends with; per iterating sensor: the state its mailbox held
+  int max_nq = 0, max_nb = 0, max_np = 0, max_bnb = 0, max_pts = 0;   // the launches' widths: queries, row blocks, points to the end, bounds blocks, previous points
+  size_t idx_total = 0, part_total = 0, bpart_total = 0;
+  int nA() const { return int(act.size()); }
+  int nE() const { return int(act.size() + idle.size()); }
+  int who(int j) const { return j < nA() ? act[size_t(j)] : idle[size_t(j - nA())]; }   // the handle (index into o) of table record j
+  OdometryDev &dev(int j) const { return *o[who(j)]; }
+  // ---- the scratch
   std::vector<OdoBatchRec> h_recs;
   DBuf<OdoBatchRec> d_recs;
   DBuf<int> d_idx;
@@ -581,6 +573,15 @@ struct OdoBatchScratch {
   bool g_cnt_dirty = false;   // KnnGrid's invariant for g_cnt: all zeros between builds (k_ob_cell_place puts them back)
   std::vector<OdoTakeRec> h_take;
   DBuf<OdoTakeRec> d_take;
+
+  void Begin(OdometryDev *const *handles, int n);
+  void TakeClouds(int n, const float *const *sharp, const size_t *n_sharp, const float *const *less_sharp, const size_t *n_ls, const float *const *flat,
+                  const size_t *n_flat, const float *const *less_flat, const size_t *n_lf, bool on_device);
+  void FillTable(const size_t *n_sharp, const size_t *n_flat, const size_t *n_ls, const size_t *n_lf);
+  void ReadBounds();
+  void MakeGrids();
+  void Iterate();
+  void Finish();
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -595,34 +596,20 @@ OdometryDev::OdometryDev(float scan_period, int io_ratio, int max_iter, bool no_
 OdometryDev::~OdometryDev() {
   if (stream_) (void)hipStreamDestroy(stream_);
 }
-
-// kdtree_corner_last_ / kdtree_surf_last_->setInputCloud (PointOdometry.cc:673-676) as 5 m grids over the previous sweep
-void OdometryDev::BuildGrids() {
-  hipStream_t s = stream_;
-  bounds_.reserve(2);
-  if (!h_bounds_.p) h_bounds_.alloc(2, hipHostMallocDefault);
-  launch_cloud_bounds(last_corner_.p, int(n_last_corner_), partial_c_, bounds_.p, s);
-  launch_cloud_bounds(last_surf_.p, int(n_last_surf_), partial_s_, bounds_.p + 1, s);
-  LIO_HIP(hipMemcpyAsync(h_bounds_.p, bounds_.p, 2 * sizeof(VoxParams), hipMemcpyDeviceToHost, s));
-  LIO_HIP(hipStreamSynchronize(s));
-  // a cloud without a finite point (the test hook allows empty ones; Process asks for > 10 and > 100 points) has no bounds
-  for (int k = 0; k < 2; ++k)
-    if (h_bounds_.p[k].n_valid == 0)
-      for (int d = 0; d < 3; ++d) h_bounds_.p[k].mn[d] = h_bounds_.p[k].mx[d] = 0.f;
-  const float cell = 5.0f * 1.0001f;
-  grid_c_.build(last_corner_.p, n_last_corner_, h_bounds_.p[0].mn, h_bounds_.p[0].mx, cell, s);
-  grid_s_.build(last_surf_.p, n_last_surf_, h_bounds_.p[1].mn, h_bounds_.p[1].mx, cell, s);
+OdoChain &OdometryDev::Chain() {
+  if (!chain_) chain_.reset(new OdoChain);
+  return *chain_;
 }
 
-static void upload(DBuf<float4> &b, const float *src, size_t n, hipStream_t s, hipMemcpyKind kind = hipMemcpyHostToDevice) {
+static void upload(DBuf<float4> &b, const float *src, size_t n, hipStream_t s) {
   b.reserve(std::max<size_t>(n, 1));
-  if (n) LIO_HIP(hipMemcpyAsync(b.p, src, n * sizeof(float4), kind, s));
+  if (n) LIO_HIP(hipMemcpyAsync(b.p, src, n * sizeof(float4), hipMemcpyHostToDevice, s));
 }
-
-// the kernels' view of sharp_ / flat_ against the previous sweep's clouds and their grids (after BuildGrids)
-OdoArgs OdometryDev::Args(size_t n_sharp, size_t n_flat) const {
-  return OdoArgs{sharp_.p, int(n_sharp), flat_.p, int(n_flat), last_corner_.p, int(n_last_corner_), last_surf_.p, int(n_last_surf_), time_factor_,
-                 no_deskew_ ? 1 : 0, grid_c_.sorted(), grid_c_.cells(), grid_c_.desc(), grid_s_.sorted(), grid_s_.cells(), grid_s_.desc()};
+static OdomState state_at(const Rigid<float> &T) {
+  OdomState st{};
+  st.T[0] = T.rot.x; st.T[1] = T.rot.y; st.T[2] = T.rot.z; st.T[3] = T.rot.w;
+  st.T[4] = T.pos.x; st.T[5] = T.pos.y; st.T[6] = T.pos.z;
+  return st;
 }
 
 // What the host keeps of the state the iterations ended with: :654-656 accumulate, :663 normalise.  TransformToEnd (:660-661) runs on the
@@ -637,117 +624,25 @@ void OdometryDev::Accumulate(const OdomState &st) {
   to_end_ready_ = true;
 }
 
-void OdometryDev::Process(const float *sharp, size_t n_sharp, const float *less_sharp, size_t n_ls, const float *flat, size_t n_flat,
-                          const float *less_flat, size_t n_lf) {
-  ProcessFrom(sharp, n_sharp, less_sharp, n_ls, flat, n_flat, less_flat, n_lf, false);
-}
-// on_device: the four clouds lie in device memory (a batch from the feature extraction that has no common chain)
-void OdometryDev::ProcessFrom(const float *sharp, size_t n_sharp, const float *less_sharp, size_t n_ls, const float *flat, size_t n_flat,
-                              const float *less_flat, size_t n_lf, bool on_device) {
-  const hipMemcpyKind up = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  iterations_done_ = 0; last_num_sel_ = 0; last_kz_ = 0; es_trace_.clear();
-  hipStream_t s = stream_;
-  upload(less_sharp_, less_sharp, n_ls, s, up);
-  upload(less_flat_, less_flat, n_lf, s, up);
-  if (!inited_) {  // :302-310
-    LIO_HIP(hipStreamSynchronize(s));
-    std::swap(last_corner_, less_sharp_); std::swap(last_surf_, less_flat_);
-    n_last_corner_ = n_ls; n_last_surf_ = n_lf;
-    inited_ = true;
-    return;
-  }
-  if (enable_odom_) {
-    if (!h_state_) {   // coherent: k_odo_update posts the state and its completion word here (dev.h: HostSignal)
-      h_mail_.alloc(128, hipHostMallocCoherent, true);
-      static_assert(sizeof(OdomState) <= 64, "mailbox layout");
-      h_state_ = reinterpret_cast<OdomState *>(h_mail_.p);
-      h_flag_ = reinterpret_cast<unsigned *>(h_mail_.p + 64);
-    }
-    OdomState st{};
-    st.T[0] = transform_es_.rot.x; st.T[1] = transform_es_.rot.y; st.T[2] = transform_es_.rot.z; st.T[3] = transform_es_.rot.w;
-    st.T[4] = transform_es_.pos.x; st.T[5] = transform_es_.pos.y; st.T[6] = transform_es_.pos.z;
-    LIO_HIP(hipMemcpyAsync(d_state_.p, &st, sizeof(st), hipMemcpyHostToDevice, s));
-    if (n_last_corner_ > 10 && n_last_surf_ > 100) {
-      upload(sharp_, sharp, n_sharp, s, up);
-      upload(flat_, flat, n_flat, s, up);
-      const int nq = int(n_sharp + n_flat);
-      idx_.reserve(std::max<size_t>(2 * n_sharp + 3 * n_flat, 1));
-      LIO_HIP(hipMemsetAsync(idx_.p, 0xFF, (2 * n_sharp + 3 * n_flat) * sizeof(int), s));
-      BuildGrids();
-      const OdoArgs a = Args(n_sharp, n_flat);
-      const int nb = odo_rows_blocks(nq);
-      d_partials_.reserve(size_t(nb) * 28);
-      d_trace_.reserve(size_t(max_iter_) * 8);
-      HostSignal sig{};
-      bool have_state = false;
-      for (int iter = 0; iter < max_iter_; ++iter) {
-        if (iter > 0 && iter % 5 == 0) {  // look at the abort flag where the reference refreshes correspondences
-          wait_host_signal(sig, s);
-          st = *h_state_;
-          if (st.converged) { have_state = true; break; }
-        }
-        if (iter % 5 == 0) launch_odo_corr(a, d_state_.p, idx_.p, s);
-        launch_odo_rows(a, d_state_.p, idx_.p, iter, d_partials_.p, nb, s);
-        HostSignal sg{};
-        if (iter % 5 == 4 || iter == max_iter_ - 1) { sig.flag = h_flag_; sig.seq = ++seq_; sg = sig; }
-        hipLaunchKernelGGL(k_odo_update, dim3(1), dim3(256), 0, s, d_partials_.p, nb, d_state_.p, iter, h_state_, sg, d_trace_.p);
-      }
-      LIO_HIP(hipGetLastError());
-      if (!have_state) {   // the last iteration posted the state (max_iter_ >= 1)
-        wait_host_signal(sig, s);
-        st = *h_state_;
-      }
-      if (st.iters > 0) {   // the records of the iterations that ran (every launch behind them is complete: the state came back)
-        h_trace_.resize(size_t(st.iters) * 8);
-        LIO_HIP(hipMemcpyAsync(h_trace_.data(), d_trace_.p, size_t(st.iters) * 8 * sizeof(float), hipMemcpyDeviceToHost, s));
-        LIO_HIP(hipStreamSynchronize(s));
-        for (int k = 0; k < st.iters; ++k) {
-          const float *T = &h_trace_[size_t(k) * 8];
-          es_trace_.push_back(Rigid<float>(Quat<float>(T[3], T[0], T[1], T[2]), Vec3<float>(T[4], T[5], T[6])));
-        }
-      }
-    } else {
-      LIO_HIP(hipMemcpyAsync(h_state_, d_state_.p, sizeof(st), hipMemcpyDeviceToHost, s));
-      LIO_HIP(hipStreamSynchronize(s));
-      st = *h_state_;
-    }
-    Accumulate(st);
-    // :660-661 TransformToEnd
-    if (n_ls) hipLaunchKernelGGL(k_odo_to_end, dim3(cdiv(n_ls, 256)), dim3(256), 0, s, less_sharp_.p, less_sharp_.p, int(n_ls), d_state_.p, time_factor_, no_deskew_ ? 1 : 0);
-    if (n_lf) hipLaunchKernelGGL(k_odo_to_end, dim3(cdiv(n_lf, 256)), dim3(256), 0, s, less_flat_.p, less_flat_.p, int(n_lf), d_state_.p, time_factor_, no_deskew_ ? 1 : 0);
-    LIO_HIP(hipGetLastError());
-  }
-  LIO_HIP(hipStreamSynchronize(s));
-  std::swap(last_corner_, less_sharp_); std::swap(last_surf_, less_flat_);
-  n_last_corner_ = n_ls; n_last_surf_ = n_lf;
+void OdoChain::Begin(OdometryDev *const *handles, int n) {
+  o = handles; s = handles[0]->stream_; max_iter = handles[0]->max_iter_;
+  act.clear(); idle.clear();
+  st.assign(size_t(n), OdomState{});
 }
 
-void OdometryDev::ProcessBatch(OdometryDev *const *o, int n, const float *const *sharp, const size_t *n_sharp, const float *const *less_sharp,
-                               const size_t *n_ls, const float *const *flat, const size_t *n_flat, const float *const *less_flat, const size_t *n_lf,
-                               bool on_device) {
-  OdometryDev &lead = *o[0];
-  for (int k = 1; k < n; ++k)
-    if (o[k]->max_iter_ != lead.max_iter_) {   // no common iteration count: no common chain
-      for (int j = 0; j < n; ++j) o[j]->ProcessFrom(sharp[j], n_sharp[j], less_sharp[j], n_ls[j], flat[j], n_flat[j], less_flat[j], n_lf[j], on_device);
-      return;
-    }
-  const int max_iter = lead.max_iter_;
-  hipStream_t s = lead.stream_;   // the other handles are idle: every entry point returns synchronised
-  if (!lead.batch_) lead.batch_.reset(new OdoBatchScratch);
-  OdoBatchScratch &sc = *lead.batch_;
-
-  // ---- the clouds and the starting state, per sensor: uploads from the host, or (on_device) one record of the take table each; who
-  // iterates (`act`), who only carries its clouds to the end (`idle`), who only stores them (neither)
-  std::vector<int> act, idle;
-  std::vector<OdomState> st(size_t(n), OdomState{});
-  if (on_device) sc.h_take.assign(size_t(n), OdoTakeRec{});
+// ---- step 1: the clouds and the starting state, per sensor: uploads from the host, or (on_device) one record of the take table each; who
+// iterates (`act`: previous clouds of more than 10 corner and 100 surf points), who only carries its clouds to the end (`idle`), who
+// only stores them (neither: the first sweep, :302-310, and the packer)
+void OdoChain::TakeClouds(int n, const float *const *sharp, const size_t *n_sharp, const float *const *less_sharp, const size_t *n_ls,
+                          const float *const *flat, const size_t *n_flat, const float *const *less_flat, const size_t *n_lf, bool on_device) {
+  if (on_device) h_take.assign(size_t(n), OdoTakeRec{});
   size_t max_take = 0;
   // cloud c of sensor k: sharp, less sharp, flat, less flat
   auto take = [&](int k, int c, DBuf<float4> &b, const float *src, size_t cnt) {
     if (!on_device) { upload(b, src, cnt, s); return; }
     if (cnt > size_t(INT_MAX)) throw CapacityError("lio_odom_process_batch_from_pp: a cloud exceeds 2^31 points");
     b.reserve(std::max<size_t>(cnt, 1));
-    OdoTakeRec &r = sc.h_take[size_t(k)];
+    OdoTakeRec &r = h_take[size_t(k)];
     r.src[c] = reinterpret_cast<const float4 *>(src); r.dst[c] = b.p; r.n[c] = int(cnt);
     max_take = std::max(max_take, cnt);
   };
@@ -756,11 +651,10 @@ void OdometryDev::ProcessBatch(OdometryDev *const *o, int n, const float *const 
     d.iterations_done_ = 0; d.last_num_sel_ = 0; d.last_kz_ = 0; d.es_trace_.clear();
     take(k, 1, d.less_sharp_, less_sharp[k], n_ls[k]);
     take(k, 3, d.less_flat_, less_flat[k], n_lf[k]);
-    if (!d.inited_ || !d.enable_odom_) continue;   // :302-310; the packer
+    if (!d.inited_ || !d.enable_odom_) continue;
     OdomState &t = st[size_t(k)];
-    t.T[0] = d.transform_es_.rot.x; t.T[1] = d.transform_es_.rot.y; t.T[2] = d.transform_es_.rot.z; t.T[3] = d.transform_es_.rot.w;
-    t.T[4] = d.transform_es_.pos.x; t.T[5] = d.transform_es_.pos.y; t.T[6] = d.transform_es_.pos.z;
-    if (on_device) { sc.h_take[size_t(k)].st = d.d_state_.p; sc.h_take[size_t(k)].init = t; }
+    t = state_at(d.transform_es_);
+    if (on_device) { h_take[size_t(k)].st = d.d_state_.p; h_take[size_t(k)].init = t; }
     else LIO_HIP(hipMemcpyAsync(d.d_state_.p, &t, sizeof(t), hipMemcpyHostToDevice, s));
     if (d.n_last_corner_ > 10 && d.n_last_surf_ > 100) {
       take(k, 0, d.sharp_, sharp[k], n_sharp[k]);
@@ -771,186 +665,224 @@ void OdometryDev::ProcessBatch(OdometryDev *const *o, int n, const float *const 
     }
   }
   if (on_device) {   // every sensor's clouds and state in one launch behind one upload
-    sc.d_take.reserve(size_t(n));
-    LIO_HIP(hipMemcpyAsync(sc.d_take.p, sc.h_take.data(), size_t(n) * sizeof(OdoTakeRec), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_ob_take, dim3(std::max(1, cdiv(max_take, 256)), 4, n), dim3(256), 0, s, sc.d_take.p);
+    d_take.reserve(size_t(n));
+    LIO_HIP(hipMemcpyAsync(d_take.p, h_take.data(), size_t(n) * sizeof(OdoTakeRec), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_ob_take, dim3(std::max(1, cdiv(max_take, 256)), 4, n), dim3(256), 0, s, d_take.p);
     LIO_HIP(hipGetLastError());
   }
-  const int nA = int(act.size()), nE = nA + int(idle.size());
+}
 
-  if (nE) {
-    // ---- the table: offsets first, then the previous clouds (for their bounds), then the grids (for their build and for the chain)
-    sc.h_recs.assign(size_t(nE), OdoBatchRec{});
-    size_t idx_total = 0, part_total = 0;
-    int max_nq = 0, max_nb = 0, max_np = 0;
-    for (int j = 0; j < nE; ++j) {
-      const int k = j < nA ? act[size_t(j)] : idle[size_t(j - nA)];
-      OdometryDev &d = *o[k];
-      OdoBatchRec &r = sc.h_recs[size_t(j)];
-      r.a.time_factor = d.time_factor_; r.a.no_deskew = d.no_deskew_ ? 1 : 0;
-      r.st = d.d_state_.p;
-      r.ls = d.less_sharp_.p; r.n_ls = int(n_ls[k]); r.lf = d.less_flat_.p; r.n_lf = int(n_lf[k]);
-      if (n_ls[k] + n_lf[k] > size_t(INT_MAX)) throw CapacityError("lio_odom_process_batch: a sensor's clouds exceed 2^31 points");
-      max_np = std::max(max_np, r.n_ls + r.n_lf);
-      if (j >= nA) continue;
-      if (n_sharp[k] + n_flat[k] > (size_t(1) << 25)) throw CapacityError("lio_odom_process_batch: a sensor's queries exceed 2^25");   // one 64-thread block each
-      const int nq = int(n_sharp[k] + n_flat[k]);
-      r.idx_off = int(idx_total); r.part_off = int(part_total); r.trace_off = j * max_iter * 8;
-      r.nb = std::max(1, std::min(cdiv(nq, ODO_ROW_THREADS), 64));
-      idx_total += 2 * n_sharp[k] + 3 * n_flat[k]; part_total += size_t(r.nb);
-      if (idx_total > size_t(INT_MAX)) throw CapacityError("lio_odom_process_batch: the batch's index table exceeds 2^31 entries");
-      max_nq = std::max(max_nq, nq); max_nb = std::max(max_nb, r.nb);
+// ---- step 2: the table of `act` and `idle`, all of it but the grids (the host does not know the previous clouds' bounds yet), and the buffers
+// whose sizes it states.  Array k of every argument belongs to o[k]; the clouds themselves lie in the handles.
+void OdoChain::FillTable(const size_t *n_sharp, const size_t *n_flat, const size_t *n_ls, const size_t *n_lf) {
+  const int na = nA(), ne = nE();
+  h_recs.assign(size_t(ne), OdoBatchRec{});
+  idx_total = part_total = bpart_total = 0;
+  max_nq = max_nb = max_np = max_bnb = max_pts = 0;
+  size_t pt_total = 0;
+  for (int j = 0; j < ne; ++j) {
+    const int k = who(j);
+    OdometryDev &d = *o[k];
+    OdoBatchRec &r = h_recs[size_t(j)];
+    r.a.time_factor = d.time_factor_; r.a.no_deskew = d.no_deskew_ ? 1 : 0;
+    r.st = d.d_state_.p;
+    r.ls = d.less_sharp_.p; r.n_ls = int(n_ls[k]); r.lf = d.less_flat_.p; r.n_lf = int(n_lf[k]);
+    if (n_ls[k] + n_lf[k] > size_t(INT_MAX)) throw CapacityError("scan-to-scan odometry: a sensor's clouds exceed 2^31 points");
+    max_np = std::max(max_np, r.n_ls + r.n_lf);
+    if (j >= na) continue;
+    if (n_sharp[k] + n_flat[k] > (size_t(1) << 25)) throw CapacityError("scan-to-scan odometry: a sensor's queries exceed 2^25");   // one 64-thread block each
+    if (d.n_last_corner_ + d.n_last_surf_ > size_t(INT_MAX)) throw CapacityError("scan-to-scan odometry: a sensor's previous clouds exceed 2^31 points");
+    const int nq = int(n_sharp[k] + n_flat[k]);
+    r.idx_off = int(idx_total); r.part_off = int(part_total); r.trace_off = j * max_iter * 8;
+    r.nb = std::max(1, std::min(cdiv(nq, ODO_ROW_THREADS), 64));
+    idx_total += 2 * n_sharp[k] + 3 * n_flat[k]; part_total += size_t(r.nb);
+    if (idx_total > size_t(INT_MAX)) throw CapacityError("scan-to-scan odometry: the index table exceeds 2^31 entries");
+    max_nq = std::max(max_nq, nq); max_nb = std::max(max_nb, r.nb);
+    r.a.sharp = d.sharp_.p; r.a.nc = int(n_sharp[k]); r.a.flat = d.flat_.p; r.a.ns = int(n_flat[k]);
+    r.a.lastc = d.last_corner_.p; r.a.nlc = int(d.n_last_corner_); r.a.lasts = d.last_surf_.p; r.a.nls = int(d.n_last_surf_);
+    for (int c = 0; c < 2; ++c) {
+      const int np = c ? r.a.nls : r.a.nlc;
+      r.b_nb[c] = std::max(1, std::min(cdiv(np, 256), 512));   // (launch_cloud_bounds)
+      r.b_off[c] = int(bpart_total);
+      bpart_total += size_t(r.b_nb[c]);
+      max_bnb = std::max(max_bnb, r.b_nb[c]); max_pts = std::max(max_pts, np);
+      pt_total += size_t(np);
     }
-    sc.d_recs.reserve(size_t(nE));
-    bool any_shared = false;
-    int max_pts = 0;
-    if (nA) {
-      // ---- the bounds of all 2 * nA previous clouds: two launches over the table (which so far names the clouds alone), one read-back, one wait
-      size_t bpart_total = 0, pt_total = 0;
-      int max_bnb = 0;
-      for (int j = 0; j < nA; ++j) {
-        const int k = act[size_t(j)];
-        OdometryDev &d = *o[k];
-        OdoBatchRec &r = sc.h_recs[size_t(j)];
-        if (d.n_last_corner_ + d.n_last_surf_ > size_t(INT_MAX)) throw CapacityError("lio_odom_process_batch: a sensor's previous clouds exceed 2^31 points");
-        r.a.sharp = d.sharp_.p; r.a.nc = int(n_sharp[k]); r.a.flat = d.flat_.p; r.a.ns = int(n_flat[k]);
-        r.a.lastc = d.last_corner_.p; r.a.nlc = int(d.n_last_corner_); r.a.lasts = d.last_surf_.p; r.a.nls = int(d.n_last_surf_);
-        for (int c = 0; c < 2; ++c) {
-          const int np = c ? r.a.nls : r.a.nlc;
-          r.b_nb[c] = std::max(1, std::min(cdiv(np, 256), 512));   // (launch_cloud_bounds)
-          r.b_off[c] = int(bpart_total);
-          bpart_total += size_t(r.b_nb[c]);
-          max_bnb = std::max(max_bnb, r.b_nb[c]); max_pts = std::max(max_pts, np);
-          pt_total += size_t(np);
-        }
-      }
-      if (pt_total > size_t(INT_MAX)) throw CapacityError("lio_odom_process_batch: the batch's previous clouds exceed 2^31 points");
-      sc.d_bounds.reserve(size_t(2 * nA));
-      if (sc.h_bounds.n < size_t(2 * nA)) sc.h_bounds.alloc(size_t(2 * nA) + size_t(nA), hipHostMallocDefault);
-      sc.d_bpartial.reserve(bpart_total * 8);
-      LIO_HIP(hipMemcpyAsync(sc.d_recs.p, sc.h_recs.data(), size_t(nA) * sizeof(OdoBatchRec), hipMemcpyHostToDevice, s));
-      hipLaunchKernelGGL(k_ob_bounds, dim3(max_bnb, 2 * nA), dim3(VOX_TILE), 0, s, sc.d_recs.p, sc.d_bpartial.p);
-      hipLaunchKernelGGL(k_ob_bounds_fold, dim3(2 * nA), dim3(VOX_TILE), 0, s, sc.d_recs.p, sc.d_bpartial.p, sc.d_bounds.p);
-      LIO_HIP(hipGetLastError());
-      LIO_HIP(hipMemcpyAsync(sc.h_bounds.p, sc.d_bounds.p, size_t(2 * nA) * sizeof(VoxParams), hipMemcpyDeviceToHost, s));
-      LIO_HIP(hipStreamSynchronize(s));
-      // ---- the grids: every grid of at most LIO_ODOM_BATCH_GRID_CELLS_MAX cells gets a slice of the batch's tables and is built by the three
-      // launches below; a larger one is built by its sensor's own KnnGrid, as lio_odom_process builds it
-      const float cell = 5.0f * 1.0001f;
-      size_t cell_total = 0, pt_off = 0;
-      for (int j = 0; j < nA; ++j) {
-        OdometryDev &d = *o[act[size_t(j)]];
-        OdoBatchRec &r = sc.h_recs[size_t(j)];
-        VoxParams *b = sc.h_bounds.p + 2 * j;
-        for (int c = 0; c < 2; ++c) {
-          if (b[c].n_valid == 0)
-            for (int e = 0; e < 3; ++e) b[c].mn[e] = b[c].mx[e] = 0.f;
-          GridDesc &g = c ? r.a.gs : r.a.gc;
-          const int np = c ? r.a.nls : r.a.nlc;
-          g.n_points = np;
-          const size_t ncells = grid_extent(g, b[c].mn, b[c].mx, cell);
-          if (ncells > size_t(LIO_ODOM_BATCH_GRID_CELLS_MAX)) {
-            KnnGrid &own = c ? d.grid_s_ : d.grid_c_;
-            own.build(c ? r.a.lasts : r.a.lastc, size_t(np), b[c].mn, b[c].mx, cell, s);
-            r.g_pt[c] = -1;
-            continue;
-          }
-          r.g_pt[c] = int(pt_off); r.g_cell[c] = int(cell_total); r.g_ncells[c] = int(ncells);
-          pt_off += size_t(np); cell_total += ncells + 1;
-          any_shared = true;
-        }
-      }
-      if (cell_total > size_t(INT_MAX)) throw CapacityError("lio_odom_process_batch: the batch's cell tables exceed 2^31 entries");
-      sc.g_cells.reserve(std::max<size_t>(cell_total, 1));
-      if (sc.g_cnt.cap < cell_total || sc.g_cnt_dirty) {   // a fresh table starts zeroed; after that k_ob_cell_place leaves it zeroed
-        sc.g_cnt.reserve(std::max<size_t>(cell_total, 1));
-        LIO_HIP(hipMemsetAsync(sc.g_cnt.p, 0, sc.g_cnt.cap * sizeof(int), s));
-      }
-      sc.g_keys.reserve(std::max<size_t>(pt_off, 1)); sc.g_slot.reserve(std::max<size_t>(pt_off, 1)); sc.g_sorted.reserve(std::max<size_t>(pt_off, 1));
-      // (every buffer is in place: a grid's arguments are its slice of the cell table and the base of the shared sorted array)
-      for (int j = 0; j < nA; ++j) {
-        OdometryDev &d = *o[act[size_t(j)]];
-        OdoBatchRec &r = sc.h_recs[size_t(j)];
-        r.a.gc_sorted = r.g_pt[0] < 0 ? d.grid_c_.sorted() : sc.g_sorted.p; r.a.gc_cells = r.g_pt[0] < 0 ? d.grid_c_.cells() : sc.g_cells.p + r.g_cell[0];
-        r.a.gs_sorted = r.g_pt[1] < 0 ? d.grid_s_.sorted() : sc.g_sorted.p; r.a.gs_cells = r.g_pt[1] < 0 ? d.grid_s_.cells() : sc.g_cells.p + r.g_cell[1];
-      }
-      sc.d_idx.reserve(std::max<size_t>(idx_total, 1));
-      if (idx_total) LIO_HIP(hipMemsetAsync(sc.d_idx.p, 0xFF, idx_total * sizeof(int), s));
-      sc.d_partials.reserve(part_total * 28);
-      sc.d_trace.reserve(size_t(nA) * size_t(max_iter) * 8);
-      if (sc.mail_cap < size_t(nA)) {   // (the stream is idle between calls: nobody still posts to the old one)
-        const size_t cap = size_t(nA) + size_t(nA) / 2;
-        sc.h_mail.alloc(cap * (ODO_MAIL_STRIDE + sizeof(unsigned)), hipHostMallocCoherent, true);
-        sc.mail_cap = cap;
-      }
-    }
-    LIO_HIP(hipMemcpyAsync(sc.d_recs.p, sc.h_recs.data(), size_t(nE) * sizeof(OdoBatchRec), hipMemcpyHostToDevice, s));
-    if (any_shared) {   // count, scan, place: one launch each over all grids
-      sc.g_cnt_dirty = true;   // until k_ob_cell_place has been enqueued
-      hipLaunchKernelGGL(k_ob_cell_count, dim3(cdiv(max_pts, 256), 2 * nA), dim3(256), 0, s, sc.d_recs.p, sc.g_keys.p, sc.g_slot.p, sc.g_cnt.p);
-      hipLaunchKernelGGL(k_ob_cell_scan, dim3(2 * nA), dim3(SEG_SCAN_THREADS), 0, s, sc.d_recs.p, sc.g_cnt.p, sc.g_cells.p);
-      hipLaunchKernelGGL(k_ob_cell_place, dim3(cdiv(max_pts, 256), 2 * nA), dim3(256), 0, s, sc.d_recs.p, sc.g_keys.p, sc.g_slot.p, sc.g_cells.p, sc.g_sorted.p,
-                         sc.g_cnt.p);
-      LIO_HIP(hipGetLastError());
-      sc.g_cnt_dirty = false;
-    }
-
-    if (nA) {
-      // ---- OdometryDev::Process's loop over the table: a peek where iter % 5 == 0 ends it only when EVERY sensor has converged (one that
-      // converged earlier stays frozen: its kernels leave at once)
-      static_assert(sizeof(OdomState) <= ODO_MAIL_STRIDE, "mailbox layout");
-      char *mail = sc.h_mail.p;
-      unsigned *flags = reinterpret_cast<unsigned *>(sc.h_mail.p + sc.mail_cap * ODO_MAIL_STRIDE);
-      std::vector<OdomState> got(static_cast<size_t>(nA), OdomState{});
-      auto read_mail = [&] {
-        bool all = true;
-        for (int j = 0; j < nA; ++j) {
-          got[size_t(j)] = *reinterpret_cast<const OdomState *>(mail + size_t(j) * ODO_MAIL_STRIDE);
-          all = all && got[size_t(j)].converged;
-        }
-        return all;
-      };
-      HostSignal sig{};
-      sig.nslots = nA;
-      bool have_state = false;
-      for (int iter = 0; iter < max_iter; ++iter) {
-        if (iter > 0 && iter % 5 == 0) {
-          wait_host_signal(sig, s);
-          if (read_mail()) { have_state = true; break; }
-        }
-        if (iter % 5 == 0 && max_nq > 0) hipLaunchKernelGGL(k_ob_corr, dim3(max_nq, nA), dim3(64), 0, s, sc.d_recs.p, sc.d_idx.p);
-        hipLaunchKernelGGL(k_ob_rows, dim3(max_nb, nA), dim3(ODO_ROW_THREADS), 0, s, sc.d_recs.p, sc.d_idx.p, iter, sc.d_partials.p);
-        HostSignal sg{};
-        if (iter % 5 == 4 || iter == max_iter - 1) { sig.flag = flags; sig.seq = ++sc.seq; sg = sig; }
-        hipLaunchKernelGGL(k_ob_update, dim3(nA), dim3(256), 0, s, sc.d_recs.p, sc.d_partials.p, iter, mail, sg, sc.d_trace.p);
-      }
-      LIO_HIP(hipGetLastError());
-      if (!have_state) {   // the last iteration posted (max_iter >= 1)
-        wait_host_signal(sig, s);
-        read_mail();
-      }
-      // every sensor's records in one copy (every launch behind them is complete: the states came back; iters >= 1 for each)
-      sc.h_trace.resize(size_t(nA) * size_t(max_iter) * 8);
-      LIO_HIP(hipMemcpyAsync(sc.h_trace.data(), sc.d_trace.p, sc.h_trace.size() * sizeof(float), hipMemcpyDeviceToHost, s));
-      LIO_HIP(hipStreamSynchronize(s));
-      for (int j = 0; j < nA; ++j) {
-        const int k = act[size_t(j)];
-        st[size_t(k)] = got[size_t(j)];
-        for (int i = 0; i < got[size_t(j)].iters; ++i) {
-          const float *T = &sc.h_trace[size_t(sc.h_recs[size_t(j)].trace_off) + size_t(i) * 8];
-          o[k]->es_trace_.push_back(Rigid<float>(Quat<float>(T[3], T[0], T[1], T[2]), Vec3<float>(T[4], T[5], T[6])));
-        }
-      }
-    }
-    // (a sensor of `idle` keeps the state it was given: nothing ran on it)
-    for (int j = 0; j < nE; ++j) {
-      const int k = j < nA ? act[size_t(j)] : idle[size_t(j - nA)];
-      o[k]->Accumulate(st[size_t(k)]);
-    }
-    if (max_np) hipLaunchKernelGGL(k_ob_to_end, dim3(cdiv(max_np, 256), nE), dim3(256), 0, s, sc.d_recs.p);
-    LIO_HIP(hipGetLastError());
   }
+  if (pt_total > size_t(INT_MAX)) throw CapacityError("scan-to-scan odometry: the previous clouds exceed 2^31 points");
+  d_recs.reserve(size_t(ne));
+  if (!na) return;
+  d_idx.reserve(std::max<size_t>(idx_total, 1));
+  if (idx_total) LIO_HIP(hipMemsetAsync(d_idx.p, 0xFF, idx_total * sizeof(int), s));
+  d_partials.reserve(part_total * 28);
+}
+
+// ---- step 3: kdtree_corner_last_ / kdtree_surf_last_->setInputCloud (PointOdometry.cc:673-676) as 5 m grids over the previous clouds of `act`,
+// and the finished table on the device.
+// The bounds of all 2 * nA clouds -> h_bounds: two launches over the table (which so far names the clouds alone), one read-back, one wait
+void OdoChain::ReadBounds() {
+  const int na = nA();
+  d_bounds.reserve(size_t(2 * na));
+  if (h_bounds.n < size_t(2 * na)) h_bounds.alloc(size_t(2 * na) + size_t(na), hipHostMallocDefault);
+  d_bpartial.reserve(bpart_total * 8);
+  LIO_HIP(hipMemcpyAsync(d_recs.p, h_recs.data(), size_t(na) * sizeof(OdoBatchRec), hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(k_ob_bounds, dim3(max_bnb, 2 * na), dim3(VOX_TILE), 0, s, d_recs.p, d_bpartial.p);
+  hipLaunchKernelGGL(k_ob_bounds_fold, dim3(2 * na), dim3(VOX_TILE), 0, s, d_recs.p, d_bpartial.p, d_bounds.p);
+  LIO_HIP(hipGetLastError());
+  LIO_HIP(hipMemcpyAsync(h_bounds.p, d_bounds.p, size_t(2 * na) * sizeof(VoxParams), hipMemcpyDeviceToHost, s));
   LIO_HIP(hipStreamSynchronize(s));
+}
+// Every grid of at most LIO_ODOM_BATCH_GRID_CELLS_MAX cells gets a slice of the chain's tables and is built by count, scan and place, one
+// launch each over all of them; a larger one is built by its sensor's own KnnGrid.
+void OdoChain::MakeGrids() {
+  const int na = nA(), ne = nE();
+  bool any_shared = false;
+  if (na) {
+    ReadBounds();
+    const float cell = 5.0f * 1.0001f;
+    size_t cell_total = 0, pt_off = 0;
+    for (int j = 0; j < na; ++j) {
+      OdometryDev &d = dev(j);
+      OdoBatchRec &r = h_recs[size_t(j)];
+      VoxParams *b = h_bounds.p + 2 * j;
+      for (int c = 0; c < 2; ++c) {
+        if (b[c].n_valid == 0)   // a cloud without a finite point (the test hooks allow empty ones) has no bounds
+          for (int e = 0; e < 3; ++e) b[c].mn[e] = b[c].mx[e] = 0.f;
+        GridDesc &g = c ? r.a.gs : r.a.gc;
+        const int np = c ? r.a.nls : r.a.nlc;
+        g.n_points = np;
+        const size_t ncells = grid_extent(g, b[c].mn, b[c].mx, cell);
+        if (ncells > size_t(LIO_ODOM_BATCH_GRID_CELLS_MAX)) {
+          KnnGrid &own = c ? d.grid_s_ : d.grid_c_;
+          own.build(c ? r.a.lasts : r.a.lastc, size_t(np), b[c].mn, b[c].mx, cell, s);
+          r.g_pt[c] = -1;
+          continue;
+        }
+        r.g_pt[c] = int(pt_off); r.g_cell[c] = int(cell_total); r.g_ncells[c] = int(ncells);
+        pt_off += size_t(np); cell_total += ncells + 1;
+        any_shared = true;
+      }
+    }
+    if (cell_total > size_t(INT_MAX)) throw CapacityError("scan-to-scan odometry: the cell tables exceed 2^31 entries");
+    g_cells.reserve(std::max<size_t>(cell_total, 1));
+    if (g_cnt.cap < cell_total || g_cnt_dirty) {   // a fresh table starts zeroed; after that k_ob_cell_place leaves it zeroed
+      g_cnt.reserve(std::max<size_t>(cell_total, 1));
+      LIO_HIP(hipMemsetAsync(g_cnt.p, 0, g_cnt.cap * sizeof(int), s));
+    }
+    g_keys.reserve(std::max<size_t>(pt_off, 1)); g_slot.reserve(std::max<size_t>(pt_off, 1)); g_sorted.reserve(std::max<size_t>(pt_off, 1));
+    // (every buffer is in place: a grid's arguments are its slice of the cell table and the base of the shared sorted array)
+    for (int j = 0; j < na; ++j) {
+      OdometryDev &d = dev(j);
+      OdoBatchRec &r = h_recs[size_t(j)];
+      r.a.gc_sorted = r.g_pt[0] < 0 ? d.grid_c_.sorted() : g_sorted.p; r.a.gc_cells = r.g_pt[0] < 0 ? d.grid_c_.cells() : g_cells.p + r.g_cell[0];
+      r.a.gs_sorted = r.g_pt[1] < 0 ? d.grid_s_.sorted() : g_sorted.p; r.a.gs_cells = r.g_pt[1] < 0 ? d.grid_s_.cells() : g_cells.p + r.g_cell[1];
+    }
+  }
+  LIO_HIP(hipMemcpyAsync(d_recs.p, h_recs.data(), size_t(ne) * sizeof(OdoBatchRec), hipMemcpyHostToDevice, s));
+  if (any_shared) {
+    // no point at all (max_pts == 0, the hooks' empty previous clouds): nothing to count or place, and no launch of zero blocks; the scan
+    // still runs, so every cell's run starts (and ends) at its grid's base
+    const int pb = cdiv(max_pts, 256);
+    g_cnt_dirty = true;   // until k_ob_cell_place has been enqueued
+    if (pb) hipLaunchKernelGGL(k_ob_cell_count, dim3(pb, 2 * na), dim3(256), 0, s, d_recs.p, g_keys.p, g_slot.p, g_cnt.p);
+    hipLaunchKernelGGL(k_ob_cell_scan, dim3(2 * na), dim3(SEG_SCAN_THREADS), 0, s, d_recs.p, g_cnt.p, g_cells.p);
+    if (pb) hipLaunchKernelGGL(k_ob_cell_place, dim3(pb, 2 * na), dim3(256), 0, s, d_recs.p, g_keys.p, g_slot.p, g_cells.p, g_sorted.p, g_cnt.p);
+    LIO_HIP(hipGetLastError());
+    g_cnt_dirty = false;
+  }
+}
+
+// ---- step 4: the <= max_iter iterations of `act` (:325-651).  The host looks at the sensors' mailboxes where the reference refreshes the
+// correspondences (iter % 5 == 0); the look ends the loop only when EVERY sensor has converged (one that converged earlier stays frozen: its
+// kernels leave at once).  Leaves every sensor's last state in `got`.
+void OdoChain::Iterate() {
+  const int na = nA();
+  static_assert(sizeof(OdomState) <= ODO_MAIL_STRIDE, "mailbox layout");
+  d_trace.reserve(size_t(na) * size_t(max_iter) * 8);
+  if (mail_cap < size_t(na)) {   // (the stream is idle between calls: nobody still posts to the old one)
+    const size_t cap = size_t(na) + size_t(na) / 2;
+    h_mail.alloc(cap * (ODO_MAIL_STRIDE + sizeof(unsigned)), hipHostMallocCoherent, true);
+    mail_cap = cap;
+  }
+  char *mail = h_mail.p;
+  unsigned *flags = reinterpret_cast<unsigned *>(h_mail.p + mail_cap * ODO_MAIL_STRIDE);
+  got.assign(size_t(na), OdomState{});
+  auto read_mail = [&] {
+    bool all = true;
+    for (int j = 0; j < na; ++j) {
+      got[size_t(j)] = *reinterpret_cast<const OdomState *>(mail + size_t(j) * ODO_MAIL_STRIDE);
+      all = all && got[size_t(j)].converged;
+    }
+    return all;
+  };
+  HostSignal sig{};
+  sig.nslots = na;
+  bool have_state = false;
+  for (int iter = 0; iter < max_iter; ++iter) {
+    if (iter > 0 && iter % 5 == 0) {
+      wait_host_signal(sig, s);
+      if (read_mail()) { have_state = true; break; }
+    }
+    if (iter % 5 == 0 && max_nq > 0) hipLaunchKernelGGL(k_ob_corr, dim3(max_nq, na), dim3(64), 0, s, d_recs.p, d_idx.p);
+    hipLaunchKernelGGL(k_ob_rows, dim3(max_nb, na), dim3(ODO_ROW_THREADS), 0, s, d_recs.p, d_idx.p, iter, d_partials.p);
+    HostSignal sg{};
+    if (iter % 5 == 4 || iter == max_iter - 1) { sig.flag = flags; sig.seq = ++seq; sg = sig; }
+    hipLaunchKernelGGL(k_ob_update, dim3(na), dim3(256), 0, s, d_recs.p, d_partials.p, iter, mail, sg, d_trace.p);
+  }
+  LIO_HIP(hipGetLastError());
+  if (!have_state) {   // the last iteration posted (max_iter >= 1)
+    wait_host_signal(sig, s);
+    read_mail();
+  }
+}
+
+// ---- step 5: the iterations' records (lio_odom_get_iteration_trace), what the host keeps of the states (:654-663), TransformToEnd of the
+// less-sharp and less-flat clouds (:660-661)
+void OdoChain::Finish() {
+  const int na = nA(), ne = nE();
+  if (na) {
+    // every sensor's records in one copy (every launch behind them is complete: the states came back; iters >= 1 for each)
+    h_trace.resize(size_t(na) * size_t(max_iter) * 8);
+    LIO_HIP(hipMemcpyAsync(h_trace.data(), d_trace.p, h_trace.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+    LIO_HIP(hipStreamSynchronize(s));
+    for (int j = 0; j < na; ++j) {
+      st[size_t(act[size_t(j)])] = got[size_t(j)];
+      for (int i = 0; i < got[size_t(j)].iters; ++i) {
+        const float *T = &h_trace[size_t(h_recs[size_t(j)].trace_off) + size_t(i) * 8];
+        dev(j).es_trace_.push_back(Rigid<float>(Quat<float>(T[3], T[0], T[1], T[2]), Vec3<float>(T[4], T[5], T[6])));
+      }
+    }
+  }
+  // (a sensor of `idle` keeps the state it was given: nothing ran on it)
+  for (int j = 0; j < ne; ++j) dev(j).Accumulate(st[size_t(who(j))]);
+  if (max_np) hipLaunchKernelGGL(k_ob_to_end, dim3(cdiv(max_np, 256), ne), dim3(256), 0, s, d_recs.p);
+  LIO_HIP(hipGetLastError());
+}
+
+void OdometryDev::Process(const float *sharp, size_t n_sharp, const float *less_sharp, size_t n_ls, const float *flat, size_t n_flat,
+                          const float *less_flat, size_t n_lf) {
+  OdometryDev *self = this;
+  ProcessBatch(&self, 1, &sharp, &n_sharp, &less_sharp, &n_ls, &flat, &n_flat, &less_flat, &n_lf);
+}
+
+void OdometryDev::ProcessBatch(OdometryDev *const *o, int n, const float *const *sharp, const size_t *n_sharp, const float *const *less_sharp,
+                               const size_t *n_ls, const float *const *flat, const size_t *n_flat, const float *const *less_flat, const size_t *n_lf,
+                               bool on_device) {
+  for (int k = 1; k < n; ++k)
+    if (o[k]->max_iter_ != o[0]->max_iter_) {   // no common iteration count: no common chain, a chain of one per handle
+      for (int j = 0; j < n; ++j) ProcessBatch(o + j, 1, sharp + j, n_sharp + j, less_sharp + j, n_ls + j, flat + j, n_flat + j, less_flat + j, n_lf + j, on_device);
+      return;
+    }
+  OdoChain &ch = o[0]->Chain();
+  ch.Begin(o, n);
+  ch.TakeClouds(n, sharp, n_sharp, less_sharp, n_ls, flat, n_flat, less_flat, n_lf, on_device);
+  if (ch.nE()) {
+    ch.FillTable(n_sharp, n_flat, n_ls, n_lf);
+    ch.MakeGrids();
+    if (ch.nA()) ch.Iterate();
+    ch.Finish();
+  }
+  LIO_HIP(hipStreamSynchronize(ch.s));
   for (int k = 0; k < n; ++k) {
     OdometryDev &d = *o[k];
     std::swap(d.last_corner_, d.less_sharp_); std::swap(d.last_surf_, d.less_flat_);
@@ -959,74 +891,73 @@ void OdometryDev::ProcessBatch(OdometryDev *const *o, int n, const float *const 
   }
 }
 
-// lio_odom_correspondences (include/lio_test_hooks.h): the given clouds as the previous sweep's, the grids Process builds, ONE launch of
-// k_odo_corr at the given transform_es_, and sel of every query from k_odo_sel.  Meant for a handle of its own: the clouds it leaves
-// behind are the caller's.
+// The test hooks' table (include/lio_test_hooks.h): the given clouds as this handle's queries and previous clouds, the given transform_es_
+// as its state, and the table and grids of a chain of one that iterates — whatever the previous clouds' sizes: the gate on them is
+// TakeClouds's, for Process alone.  Meant for a handle of its own: the clouds it leaves behind are the caller's.  Returns synchronised (the
+// bounds' read-back): `T` and the caller's arrays have been read.
+OdoChain &OdometryDev::HookTable(const float *sharp, size_t n_sharp, const float *flat, size_t n_flat, const float *last_corner, size_t n_lc,
+                                 const float *last_surf, size_t n_lsf, const Rigid<float> &T) {
+  OdometryDev *self = this;
+  OdoChain &ch = Chain();
+  ch.Begin(&self, 1);
+  upload(sharp_, sharp, n_sharp, ch.s);
+  upload(flat_, flat, n_flat, ch.s);
+  upload(last_corner_, last_corner, n_lc, ch.s);
+  upload(last_surf_, last_surf, n_lsf, ch.s);
+  n_last_corner_ = n_lc; n_last_surf_ = n_lsf;
+  ch.st[0] = state_at(T);
+  LIO_HIP(hipMemcpyAsync(d_state_.p, &ch.st[0], sizeof(OdomState), hipMemcpyHostToDevice, ch.s));
+  ch.act.push_back(0);
+  const size_t none = 0;
+  ch.FillTable(&n_sharp, &n_flat, &none, &none);
+  ch.MakeGrids();
+  return ch;
+}
+
+// lio_odom_correspondences (include/lio_test_hooks.h): ONE launch of k_ob_corr over the hook's table, as the first iteration of Process
+// launches it, and sel of every query from k_odo_sel
 void OdometryDev::Correspondences(const float *sharp, size_t n_sharp, const float *flat, size_t n_flat, const float *last_corner, size_t n_lc,
                                   const float *last_surf, size_t n_lsf, const Rigid<float> &T, int32_t *corner_idx, int32_t *surf_idx,
                                   float *sel_out) {
-  hipStream_t s = stream_;
-  upload(sharp_, sharp, n_sharp, s);
-  upload(flat_, flat, n_flat, s);
-  upload(last_corner_, last_corner, n_lc, s);
-  upload(last_surf_, last_surf, n_lsf, s);
-  n_last_corner_ = n_lc; n_last_surf_ = n_lsf;
-  OdomState st{};
-  st.T[0] = T.rot.x; st.T[1] = T.rot.y; st.T[2] = T.rot.z; st.T[3] = T.rot.w;
-  st.T[4] = T.pos.x; st.T[5] = T.pos.y; st.T[6] = T.pos.z;
-  LIO_HIP(hipMemcpyAsync(d_state_.p, &st, sizeof(st), hipMemcpyHostToDevice, s));
-  const size_t nq = n_sharp + n_flat, ni = 2 * n_sharp + 3 * n_flat;
-  idx_.reserve(std::max<size_t>(ni, 1));
-  if (ni) LIO_HIP(hipMemsetAsync(idx_.p, 0xFF, ni * sizeof(int), s));
-  BuildGrids();   // waits for the uploads: `st` and the caller's arrays have been read
-  const OdoArgs a = Args(n_sharp, n_flat);
-  launch_odo_corr(a, d_state_.p, idx_.p, s);
+  OdoChain &ch = HookTable(sharp, n_sharp, flat, n_flat, last_corner, n_lc, last_surf, n_lsf, T);
+  hipStream_t s = ch.s;
+  const size_t nq = n_sharp + n_flat;
+  if (ch.max_nq > 0) hipLaunchKernelGGL(k_ob_corr, dim3(ch.max_nq, 1), dim3(64), 0, s, ch.d_recs.p, ch.d_idx.p);
   d_sel_.reserve(std::max<size_t>(3 * nq, 1));
-  if (nq) hipLaunchKernelGGL(k_odo_sel, dim3(cdiv(nq, 256)), dim3(256), 0, s, a, d_state_.p, d_sel_.p);
+  if (nq) hipLaunchKernelGGL(k_odo_sel, dim3(cdiv(nq, 256)), dim3(256), 0, s, ch.h_recs[0].a, d_state_.p, d_sel_.p);
   LIO_HIP(hipGetLastError());
   static_assert(sizeof(int) == sizeof(int32_t), "index layout");
-  if (n_sharp) LIO_HIP(hipMemcpyAsync(corner_idx, idx_.p, 2 * n_sharp * sizeof(int), hipMemcpyDeviceToHost, s));
-  if (n_flat) LIO_HIP(hipMemcpyAsync(surf_idx, idx_.p + 2 * n_sharp, 3 * n_flat * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (n_sharp) LIO_HIP(hipMemcpyAsync(corner_idx, ch.d_idx.p, 2 * n_sharp * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (n_flat) LIO_HIP(hipMemcpyAsync(surf_idx, ch.d_idx.p + 2 * n_sharp, 3 * n_flat * sizeof(int), hipMemcpyDeviceToHost, s));
   if (nq) LIO_HIP(hipMemcpyAsync(sel_out, d_sel_.p, 3 * nq * sizeof(float), hipMemcpyDeviceToHost, s));
   LIO_HIP(hipStreamSynchronize(s));
 }
 
-// lio_gn_rows_odom (include/lio_test_hooks.h): the given clouds and correspondences, ONE launch of k_odo_rows through the statement Process
-// uses at the given transform_es_ and iteration, and the row of every query from k_gn_rows_odom.  Meant for a handle of its own.  The
-// caller has checked the indices against the clouds' sizes.
+// lio_gn_rows_odom (include/lio_test_hooks.h): the given correspondences in the place of the search's, ONE launch of k_ob_rows over the hook's
+// table at the given iteration, as Process launches it, and the row of every query from k_gn_rows_odom.  The caller has checked the indices
+// against the clouds' sizes.
 void OdometryDev::Rows(const float *sharp, size_t n_sharp, const float *flat, size_t n_flat, const float *last_corner, size_t n_lc,
                        const float *last_surf, size_t n_lsf, const int32_t *corner_idx, const int32_t *surf_idx, const Rigid<float> &T, int iter,
                        uint8_t *ok_out, float *rows_out, int32_t *nb_out, double *partials_out) {
-  hipStream_t s = stream_;
-  upload(sharp_, sharp, n_sharp, s);
-  upload(flat_, flat, n_flat, s);
-  upload(last_corner_, last_corner, n_lc, s);
-  upload(last_surf_, last_surf, n_lsf, s);
-  n_last_corner_ = n_lc; n_last_surf_ = n_lsf;
-  OdomState st{};
-  st.T[0] = T.rot.x; st.T[1] = T.rot.y; st.T[2] = T.rot.z; st.T[3] = T.rot.w;
-  st.T[4] = T.pos.x; st.T[5] = T.pos.y; st.T[6] = T.pos.z;
-  LIO_HIP(hipMemcpyAsync(d_state_.p, &st, sizeof(st), hipMemcpyHostToDevice, s));
-  const size_t nq = n_sharp + n_flat, ni = 2 * n_sharp + 3 * n_flat;
+  OdoChain &ch = HookTable(sharp, n_sharp, flat, n_flat, last_corner, n_lc, last_surf, n_lsf, T);
+  hipStream_t s = ch.s;
+  const size_t nq = n_sharp + n_flat;
   static_assert(sizeof(int) == sizeof(int32_t), "index layout");
-  idx_.reserve(std::max<size_t>(ni, 1));
-  if (n_sharp) LIO_HIP(hipMemcpyAsync(idx_.p, corner_idx, 2 * n_sharp * sizeof(int), hipMemcpyHostToDevice, s));
-  if (n_flat) LIO_HIP(hipMemcpyAsync(idx_.p + 2 * n_sharp, surf_idx, 3 * n_flat * sizeof(int), hipMemcpyHostToDevice, s));
-  const OdoArgs a = Args(n_sharp, n_flat);   // the grids are not built: the rows kernels read the clouds and the indices alone
-  const int nb = odo_rows_blocks(int(nq));
-  d_partials_.reserve(size_t(nb) * 28);
-  launch_odo_rows(a, d_state_.p, idx_.p, iter, d_partials_.p, nb, s);
+  if (n_sharp) LIO_HIP(hipMemcpyAsync(ch.d_idx.p, corner_idx, 2 * n_sharp * sizeof(int), hipMemcpyHostToDevice, s));
+  if (n_flat) LIO_HIP(hipMemcpyAsync(ch.d_idx.p + 2 * n_sharp, surf_idx, 3 * n_flat * sizeof(int), hipMemcpyHostToDevice, s));
+  const int nb = ch.max_nb;
+  hipLaunchKernelGGL(k_ob_rows, dim3(nb, 1), dim3(ODO_ROW_THREADS), 0, s, ch.d_recs.p, ch.d_idx.p, iter, ch.d_partials.p);
   d_sel_.reserve(std::max<size_t>(7 * nq, 1));
   DBuf<uint8_t> ok_dev;
   ok_dev.reserve(std::max<size_t>(nq, 1));
-  if (nq) hipLaunchKernelGGL(k_gn_rows_odom, dim3(cdiv(nq, 256)), dim3(256), 0, s, a, d_state_.p, idx_.p, iter, ok_dev.p, d_sel_.p);
+  if (nq) hipLaunchKernelGGL(k_gn_rows_odom, dim3(cdiv(nq, 256)), dim3(256), 0, s, ch.h_recs[0].a, d_state_.p, ch.d_idx.p, iter, ok_dev.p, d_sel_.p);
   LIO_HIP(hipGetLastError());
   if (nq) {
     LIO_HIP(hipMemcpyAsync(ok_out, ok_dev.p, nq, hipMemcpyDeviceToHost, s));
     LIO_HIP(hipMemcpyAsync(rows_out, d_sel_.p, 7 * nq * sizeof(float), hipMemcpyDeviceToHost, s));
   }
-  LIO_HIP(hipMemcpyAsync(partials_out, d_partials_.p, size_t(nb) * 28 * sizeof(double), hipMemcpyDeviceToHost, s));
-  LIO_HIP(hipStreamSynchronize(s));   // `st` and the caller's arrays have been read
+  LIO_HIP(hipMemcpyAsync(partials_out, ch.d_partials.p, size_t(nb) * 28 * sizeof(double), hipMemcpyDeviceToHost, s));
+  LIO_HIP(hipStreamSynchronize(s));   // the caller's index arrays have been read
   *nb_out = nb;
 }
 

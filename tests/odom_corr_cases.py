@@ -1,5 +1,5 @@
 """The cases the scan-to-scan correspondence search is pinned on (tests/test_odom_corr.py on the CPU: oracle and references;
-tests/test_gpu_odom_corr.py: the product's k_odo_corr through lio_odom_correspondences).  Every case is seeded and small: at most about
+tests/test_gpu_odom_corr.py: the product's k_ob_corr through lio_odom_correspondences).  Every case is seeded and small: at most about
 45 k previous points and 2 k queries.  A case is the four clouds of one hook call, transform_es, and what the checks need to know about
 it: `lattice` (every fp32 distance exact: layer B leaves out nothing).  What each case must contain is asserted in
 tests/test_odom_corr.py::test_case_contains_what_it_claims.
@@ -16,7 +16,8 @@ import odom_corr_ref as ref
 
 CHUNK_COUNTS = (0, 1, 63, 64, 65, 255, 256, 257, 511, 512, 513)
 VIOLATION_OFFSETS = tuple(64 * q + l for q in range(4) for l in (0, 1, 63)) + (256, 512)
-CELL = np.float32(5.0) * np.float32(1.0001)       # OdometryDev::BuildGrids
+CELL = np.float32(5.0) * np.float32(1.0001)       # the grids of csrc/odometry.hip
+GRID_CELLS_MAX = 131072                           # LIO_ODOM_BATCH_GRID_CELLS_MAX (include/lio_frontend_batch.h)
 
 
 class Case:
@@ -278,6 +279,33 @@ def _grid_edges():
     return Case("grid_edges", qc, qs, lc, ls, no_deskew=True, n_outside=no, n_faces=nf)
 
 
+def grid_cells(cloud):
+    """cells of the 5 m grid the product lays over a previous cloud (csrc/cloud_kernels.h: grid_extent, one border cell on every side)"""
+    inv = np.float32(1.0) / CELL
+    lo = np.floor(cloud[:, :3].min(axis=0) * inv).astype(np.int64) - 1
+    hi = np.floor(cloud[:, :3].max(axis=0) * inv).astype(np.int64) + 1
+    return int(np.prod(hi - lo + 1))
+
+
+def _grid_oversize():
+    """two tight clusters 300 m apart along every axis: the grid over them has about 61^3 cells, more than GRID_CELLS_MAX, so the product
+    builds it by KnnGrid::build and not by the segmented build every other case's grids go through"""
+    rng = np.random.default_rng(31)
+    centres = np.array([[-150.0, -150.0, -150.0], [150.0, 150.0, 150.0]])
+
+    def cloud():
+        out = []
+        for c in centres:   # rings 0 .. 9 at heights 0.3 m apart, ten points each on a 3 m patch
+            ring = np.repeat(np.arange(10.0), 10)
+            xyz = c + np.concatenate([rng.uniform(-1.5, 1.5, (100, 2)), 0.3 * ring[:, None] + rng.normal(0, 0.02, (100, 1))], axis=1)
+            out.append(np.concatenate([xyz, ring[:, None]], axis=1))
+        return np.concatenate(out).astype(np.float32)
+
+    lc, ls = cloud(), cloud()
+    near = lambda cl: np.concatenate([_near_queries(rng, cl[:100], 64, 0.2), _near_queries(rng, cl[100:], 64, 0.2)])
+    return Case("grid_oversize", near(lc), near(ls), lc, ls, no_deskew=True)
+
+
 def _tiny(kind):
     rng = np.random.default_rng(27)
     q = np.concatenate([rng.normal(0, 2.0, (70, 3)), np.zeros((70, 1))], axis=1)
@@ -372,7 +400,7 @@ def _sweep(kind, it, oracle):
 _BUILDERS = {
     "chunk_edges": lambda o: _chunk_edges(False), "chunk_edges_swapped": lambda o: _chunk_edges(True),
     "violation_then_valid": lambda o: _violation_then_valid(), "ties": lambda o: _ties(), "gate": lambda o: _gate(),
-    "ring_rules": lambda o: _ring_rules(), "grid_edges": lambda o: _grid_edges(),
+    "ring_rules": lambda o: _ring_rules(), "grid_edges": lambda o: _grid_edges(), "grid_oversize": lambda o: _grid_oversize(),
     "prev_0": lambda o: _tiny("prev_0"), "prev_1": lambda o: _tiny("prev_1"), "prev_2": lambda o: _tiny("prev_2"),
     "prev_identical": lambda o: _tiny("prev_identical"), "bad_queries": lambda o: _bad_queries(), "deskew": lambda o: _deskew(),
     "sweep_vlp16_iter0": lambda o: _sweep("vlp16", 0, o), "sweep_vlp16_iter5": lambda o: _sweep("vlp16", 5, o),

@@ -1,4 +1,4 @@
-"""Plain references of the scan-to-scan correspondence search (csrc/odometry.hip: k_odo_corr; test hook lio_odom_correspondences of
+"""Plain references of the scan-to-scan correspondence search (csrc/odometry.hip: k_ob_corr; test hook lio_odom_correspondences of
 include/lio_test_hooks.h; PointOdometry.cc:237-259, :342-385, :440-494), written from the contract.  numpy only; no library of ours;
 every previous point is looked at for every query, one query after the other.
 
@@ -22,7 +22,7 @@ MARGIN = 1e-5
 
 # Worst |sel - to_start64|_inf / (2^-24 * (|p| + |t_es|)) of the ORACLE's lio_odom_correspondences over every case of
 # tests/odom_corr_cases.py, as tests/test_odom_corr.py::test_oracle_sel_within_k_start measures it on the CPU (the run printed 2.154, in
-# the case `deskew`), rounded up.  The product's k_odo_sel / k_odo_corr are held to GPU_BOUND_FACTOR x this, as the de-skew is to K_DESKEW
+# the case `deskew`), rounded up.  The product's k_odo_sel / k_ob_corr are held to GPU_BOUND_FACTOR x this, as the de-skew is to K_DESKEW
 # (device acos, sin and the division each differ from libm by a few ulps).  Not measured on the code under test.
 K_START = 2.2
 

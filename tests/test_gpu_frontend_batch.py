@@ -1,4 +1,4 @@
-"""lio_odom_process_batch_from_pp (include/lio_frontend_batch.h) against lio_odom_process alone.  The raw sweeps of
+"""lio_odom_process_batch_from_pp (include/lio_frontend_batch.h) against lio_odom_process alone (the same chain, host-fed, for a batch of one).  The raw sweeps of
 tests/frontend_batch_cases.py go through the product's PointProcessor ONCE per step; one set of odometry handles is then fed from the
 processors on the device, a twin set is fed what lio_pp_get_cloud returns through lio_odom_process, handle by handle.  Every comparison is
 bit for bit (uint32 views) over the state tests/test_gpu_odom_batch.py compares: T_es, T_sum, iterations, selected rows, the iteration

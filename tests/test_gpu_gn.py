@@ -50,7 +50,7 @@ def test_rows_hook_checks_its_arguments(hip):
 # ------------------------------------------------------------------------------------------------ rows of the scan-to-scan loop
 @pytest.mark.parametrize("name", gn_cases.ODOM_NAMES)
 def test_odom_rows_and_sums(hip, name):
-    """ONE launch of k_odo_rows through the statement Process uses: the count exactly, every other sum within the bound of any fp64 summation
+    """ONE launch of k_ob_rows over the one-sensor table Process fills: the count exactly, every other sum within the bound of any fp64 summation
     order of the fp32 products of the rows the one-query-per-lane kernel returns (with and without de-skewing)"""
     c = gn_cases.get_odom(name)
     ok, rows, part = c.run(hip)

@@ -1,7 +1,8 @@
 """lio_odom_process_batch (include/lio_odom_batch.h) against lio_odom_process alone: the same sweeps through fresh handles, every
 comparison bit for bit (uint32 views) — T_es, T_sum, iterations, selected rows, the whole iteration trace and kz, both last clouds and
-lio_odom_full_to_end of a 257-point cloud, per sensor and step.  No tolerance anywhere: the single-handle path is what the existing tests
-pin to the reference.  The sensors are those of tests/odom_batch_cases.py, which tests/test_odom_batch_abi.py checks on the oracle."""
+lio_odom_full_to_end of a 257-point cloud, per sensor and step.  No tolerance anywhere.  lio_odom_process is the same launch chain for a
+batch of one, so what is pinned here is that a sensor's result does not depend on its place in the table, its offsets or its neighbours;
+the single-handle results themselves are what the other tests pin to the reference.  The sensors are those of tests/odom_batch_cases.py, which tests/test_odom_batch_abi.py checks on the oracle."""
 import ctypes as C
 
 import numpy as np

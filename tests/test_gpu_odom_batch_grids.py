@@ -1,5 +1,6 @@
 """The segmented grid build of the batched odometry (one bounds pass, one count, one scan, one place over all previous clouds of a call)
-under the host-fed lio_odom_process_batch, against lio_odom_process alone, bit for bit.  The four sensors of
+under the host-fed lio_odom_process_batch, against lio_odom_process alone (the same build for a batch of one: the comparison pins the
+slices and offsets of the shared tables; the build itself is pinned to the serial search by tests/test_gpu_odom_corr.py), bit for bit.  The four sensors of
 frontend_batch_cases.grid_sensors sit side by side in every call: a plain cell table, one that spans many chunks of the scan, one above
 LIO_ODOM_BATCH_GRID_CELLS_MAX (built by the sensor's own KnnGrid) and one over an 11-point corner cloud.
 tests/test_frontend_batch_abi.py asserts the sides without a GPU; here the previous clouds each step really had are checked again."""

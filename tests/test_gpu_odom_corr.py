@@ -1,4 +1,5 @@
-"""The correspondence search the scan-to-scan odometry runs (csrc/odometry.hip: k_odo_corr, one wave per query, through the test hook
+"""The correspondence search the scan-to-scan odometry runs (csrc/odometry.hip: k_ob_corr, one wave per query, over the one-sensor table
+and the grids lio_odom_process builds — the segmented grid build on every case, KnnGrid::build on `grid_oversize` — through the test hook
 lio_odom_correspondences) against the plain references of tests/odom_corr_ref.py on the cases of tests/odom_corr_cases.py: equality with
 layer A (the contract in fp32, evaluated on the sel the product reports — no tolerance, no query left out), then layer B (fp64 on the same
 sel bits, slots within rounding left out, at most 1 % of a case's queries and none on a lattice), and sel itself within

@@ -2,7 +2,7 @@
 (include/lio_test_hooks.h; the functions its own PointOdometry::Process calls) equals layer A of tests/odom_corr_ref.py on every case of
 tests/odom_corr_cases.py, layer A satisfies layer B within the cap, every case contains what it claims, the comparison notices each
 planted error, and the oracle's sel lies within K_START of the fp64 TransformToStart.  tests/test_gpu_odom_corr.py holds the product's
-k_odo_corr to the same references."""
+k_ob_corr to the same references."""
 import numpy as np
 import pytest
 
@@ -126,6 +126,17 @@ def test_case_contains_what_it_claims(results):
         assert np.abs(cl[:, :2]).max() > 120 and cl[:, 0].min() < -115
         face = q[-c.n_faces:, :3] / float(cases.CELL)
         assert (np.abs(face - np.rint(face)).min(axis=1) < 1.01e-3).all() and (idx[-c.n_faces:, 0] >= 0).sum() > 0.9 * c.n_faces
+    # grid_oversize: both grids above the segmented build's limit (every other case's below it), and queries that find their closest, second
+    # and third points in both clusters
+    for name in cases.NAMES:
+        c, _ = results(name)
+        over = [cases.grid_cells(cl) > cases.GRID_CELLS_MAX for cl in (c.last_corner, c.last_surf) if cl.shape[0]]
+        assert all(over) if name == "grid_oversize" else not any(over), (name, over)
+    c, (ci, si, sel) = results("grid_oversize")
+    assert c.last_corner.shape[0] == 200 and c.last_surf.shape[0] == 200 and cases.grid_cells(c.last_corner) > 200000
+    for half in (slice(0, 64), slice(64, 128)):
+        assert (ci[half, 1] >= 0).sum() > 32 and ((si[half, 1] >= 0) & (si[half, 2] >= 0)).sum() > 32
+    assert (ci[:64][ci[:64, 0] >= 0, 0] < 100).all() and (ci[64:][ci[64:, 0] >= 0, 0] >= 100).all()
     for name, sizes in (("prev_0", (0, 0)), ("prev_1", (1, 2)), ("prev_2", (2, 1)), ("prev_identical", (200, 200))):
         c, (ci, si, sel) = results(name)
         assert (c.last_corner.shape[0], c.last_surf.shape[0]) == sizes

@@ -9,7 +9,7 @@ min - max over the steps after the warm-up; a GPU is required.
     python tools/odom_batch_cost.py [--steps 12] [--batches 1,8,64] [--kinds indoor,outdoor] [--out FILE.json]
 
 --parent-lib PATH additionally times lio_odom_process ALONE of this tree against another build of the product (the parent commit's
-liblio_hip.so) on the same sweeps, alternating, the order swapped every pair: what the shared device bodies cost the single path.
+liblio_hip.so) on the same sweeps, alternating, the order swapped every pair: what a change of the chain costs the one-sensor call.
 
 --frontend times instead what feeding the batch from the PointProcessor on the device buys (include/lio_frontend_batch.h).  B processors
 take the sweep of the step through ONE lio_pp_process_batch (not timed); then, alternating as above and with equal bits asserted at
