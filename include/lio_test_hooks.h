@@ -103,7 +103,7 @@ int lio_odom_correspondences(const float *sharp_xyzi, size_t n_sharp, const floa
 
 /* ---- The 6x6 Gauss-Newton loops from the rows onward.  Every pose of the product passes through one of three loops — scan-to-scan
  * odometry (csrc/odometry.hip: k_ob_rows, k_ob_update, for one sensor and for a batch), scan-to-map and the keyframe batch
- * (csrc/cloud_kernels.hip: k_odom_rows / k_kf_rows with k_odom_update / k_kf_update) and the estimator's newest-frame loop (k_odom_round,
+ * (csrc/cloud_kernels.hip: k_kf_rows with k_kf_update, over a batch of keyframes or the map handle's table of one) and the estimator's newest-frame loop (k_odom_round,
  * k_odom_update_wide, and k_bw_odom_round / k_bw_odom_update of the batched windows) — and all of them form fp32 rows (A | b) per selected
  * residual, add a_i a_j, a_i b and a count into 28 fp64 sums through a chain of folds, and run one serial step on the sums.  The sums
  * are laid out as the upper triangle of A^T A row by row (21), A^T b (6), the row count (1). */
@@ -118,7 +118,7 @@ typedef struct {
   int32_t nsel;        /* rows selected: int(sums[27]) */
 } lio_gn_state;
 
-/* The rows of the scan-to-map family (csrc/cloud_device.h: odom_row_form, the function odom_row_accumulate — k_odom_rows, k_kf_rows,
+/* The rows of the scan-to-map family (csrc/cloud_device.h: odom_row_form, the function odom_row_accumulate — k_kf_rows,
  * k_odom_round and the batched windows — forms every row with) and the partials of ONE production rows launch.
  *   form            the production `b_from_coef`: 0 estimator (b = -(w . (R p + t) + c.w)), 1 scan-to-map (b = -c.w), 2 MapBuilder
  *                   (b = -c.w and the rotation columns times R^-1 diag(5e-3, 5e-3, 1)).  Any other value: LIO_ERR_ARG.
@@ -128,7 +128,7 @@ typedef struct {
  *   rows_out[m * 7] a0 .. a5, b in fp32; zeros where ok is 0.  a = (-(w^T R skew(p)) [form 2: R^-1 diag(5e-3, 5e-3, 1)], w)
  *   nb_out          odom_rows_blocks(m), the block count production launches with
  *   partials_out    nb x 28 doubles; nb never exceeds 256, and the caller provides 256 x 28 (m == 0: one row of zeros)
- * Product: ONE launch through launch_odom_rows with the production block count; rows_out comes from a separate one-query-per-lane
+ * Product: ONE launch through launch_kf_rows over a table of one record with the production block count; rows_out comes from a separate one-query-per-lane
  * kernel that calls the same odom_row_form.  Oracle: the row function its own loops (Estimator::CalculateLaserOdom,
  * PointMapping::OptimizeTransformTobeMapped) call, serially; nb_out = 1 and its partial is one row of plain fp64 sums of the fp32
  * products.  A null required pointer (an input may be null when m is 0): LIO_ERR_ARG. */
@@ -158,7 +158,7 @@ int lio_gn_rows_odom(const float *sharp_xyzi, size_t n_sharp, const float *flat_
                      int32_t *nb_out, double *partials_out);
 
 /* The fixed-order fold of `nblocks` partials (28 doubles each) into sums_out[28].
- *   wide 0   reduce_partials28 (csrc/cloud_kernels.h) on a 256-thread block: k_odom_update, k_kf_update, k_ob_update
+ *   wide 0   reduce_partials28 (csrc/cloud_kernels.h) on a 256-thread block: k_kf_update, k_ob_update
  *   wide 1   fold_partials28_wide (csrc/cloud_device.h) on a 1024-thread block: k_odom_update_wide, k_bw_odom_update
  * One launch that calls the production function and copies the 28 shared sums out.  nblocks == 0 gives zeros.  The oracle adds the rows
  * serially, ascending.  A null pointer (partials may be null when nblocks is 0), a negative nblocks or another `wide`: LIO_ERR_ARG. */

@@ -610,6 +610,7 @@ struct Scratch {
   DBuf<float> bounds;
   DBuf<double> gn_partials, gn_sums;   // the Gauss-Newton hooks
   DBuf<OdomState> gn_state;
+  DBuf<KfDesc> gn_kd;
   DBuf<float> gn_rows;
 };
 static Scratch &scratch() {
@@ -621,11 +622,6 @@ static Scratch &scratch() {
     LIO_HIP(hipStreamCreate(&sc.s));
   }
   return sc;
-}
-static void host_bounds(const float *xyzi, size_t n, float mn[3], float mx[3]) {
-  for (int d = 0; d < 3; ++d) { mn[d] = 3.4e38f; mx[d] = -3.4e38f; }
-  for (size_t i = 0; i < n; ++i)
-    for (int d = 0; d < 3; ++d) { float v = xyzi[4 * i + d]; if (std::isfinite(v)) { mn[d] = std::min(mn[d], v); mx[d] = std::max(mx[d], v); } }
 }
 
 int lio_voxel_grid(const float *xyzi, size_t n, float leaf, float *out, size_t *n_out) {
@@ -653,8 +649,7 @@ int lio_knn(const float *map, size_t n_map, const float *query, size_t m, int k,
     if (n_map) LIO_HIP(hipMemcpyAsync(sc.a.p, map, n_map * sizeof(float4), hipMemcpyHostToDevice, sc.s));
     if (m) LIO_HIP(hipMemcpyAsync(sc.b.p, query, m * sizeof(float4), hipMemcpyHostToDevice, sc.s));
     float mn[3], mx[3];
-    host_bounds(map, n_map, mn, mx);
-    if (n_map == 0) { mn[0] = mn[1] = mn[2] = 0; mx[0] = mx[1] = mx[2] = 0; }
+    host_cloud_bounds(map, n_map, mn, mx);
     sc.grid.build(sc.a.p, n_map, mn, mx, knn_cell_edge(radius_sq), sc.s);
     launch_knn(sc.b.p, int(m), k, radius_sq, sc.grid.sorted(), sc.grid.cells(), sc.grid.desc(), sc.idx.p, sc.sqd.p, sc.s);
     if (m) {
@@ -678,8 +673,7 @@ int lio_knn_walk(const float *map, size_t n_map, const float *query, size_t m, f
     if (n_map) LIO_HIP(hipMemcpyAsync(sc.a.p, map, n_map * sizeof(float4), hipMemcpyHostToDevice, sc.s));
     if (m) LIO_HIP(hipMemcpyAsync(sc.b.p, query, m * sizeof(float4), hipMemcpyHostToDevice, sc.s));
     float mn[3], mx[3];
-    host_bounds(map, n_map, mn, mx);
-    if (n_map == 0) { mn[0] = mn[1] = mn[2] = 0; mx[0] = mx[1] = mx[2] = 0; }
+    host_cloud_bounds(map, n_map, mn, mx);
     sc.grid.build(sc.a.p, n_map, mn, mx, cell, sc.s);
     launch_knn_walk(sc.b.p, int(m), lanes_per_query, sc.grid.sorted(), sc.grid.cells(), sc.grid.desc(), sc.idx.p, sc.sqd.p, sc.nbr.p, sc.s);
     if (m) {
@@ -743,12 +737,6 @@ static bool finite_T(const lio_transform_f *T) {
   for (int k = 0; k < 3; ++k) if (!std::isfinite(T->p[k])) return false;
   return true;
 }
-static OdomState state_at(const lio_transform_f *T) {
-  OdomState st{};
-  for (int k = 0; k < 4; ++k) st.T[k] = T->q[k];
-  for (int k = 0; k < 3; ++k) st.T[4 + k] = T->p[k];
-  return st;
-}
 
 int lio_gn_rows_map(int form, const float *stack, size_t m, const uint8_t *valid, const float *coeff, const lio_transform_f *T, uint8_t *ok_out,
                     float *rows_out, int32_t *nb_out, double *partials_out) {
@@ -760,16 +748,19 @@ int lio_gn_rows_map(int form, const float *stack, size_t m, const uint8_t *valid
     const int M = int(m), nb = odom_rows_blocks(M);
     sc.b.reserve(std::max<size_t>(m, 1)); sc.valid.reserve(std::max<size_t>(m, 1)); sc.coef.reserve(std::max<size_t>(m, 1));
     sc.idx.reserve(std::max<size_t>((m + 3) / 4, 1));   // ok_out, as bytes
-    sc.gn_rows.reserve(std::max<size_t>(m * 7, 1)); sc.gn_partials.reserve(size_t(nb) * 28); sc.gn_state.reserve(1);
-    const OdomState st = state_at(T);
+    sc.gn_rows.reserve(std::max<size_t>(m * 7, 1)); sc.gn_partials.reserve(size_t(nb) * 28); sc.gn_state.reserve(1); sc.gn_kd.reserve(1);
+    const OdomState st = odom_state_at(toT(*T));
     LIO_HIP(hipMemcpyAsync(sc.gn_state.p, &st, sizeof(st), hipMemcpyHostToDevice, sc.s));
     LIO_HIP(hipMemsetAsync(sc.gn_partials.p, 0, size_t(nb) * 28 * sizeof(double), sc.s));
     if (m) {
       LIO_HIP(hipMemcpyAsync(sc.b.p, stack, m * sizeof(float4), hipMemcpyHostToDevice, sc.s));
       LIO_HIP(hipMemcpyAsync(sc.valid.p, valid, m, hipMemcpyHostToDevice, sc.s));
       LIO_HIP(hipMemcpyAsync(sc.coef.p, coeff, m * sizeof(float4), hipMemcpyHostToDevice, sc.s));
-      // what production launches: M slots over the M points, odom_rows_blocks(M) blocks (csrc/mapping.hip, csrc/estimator.hip)
-      launch_odom_rows(sc.b.p, M, M, sc.valid.p, sc.coef.p, sc.gn_state.p, sc.gn_partials.p, nb, sc.s, form);
+      // what production launches (csrc/mapping.hip, csrc/kf_batch.hip): the rows kernel over a keyframe table, here one record of M slots
+      // in odom_rows_blocks(M) blocks
+      const KfDesc kd{0, 0, M, 0, nb, 0, {0.f, 0.f, 0.f}};
+      LIO_HIP(hipMemcpyAsync(sc.gn_kd.p, &kd, sizeof(kd), hipMemcpyHostToDevice, sc.s));
+      launch_kf_rows(sc.gn_kd.p, sc.gn_state.p, 1, nb, sc.b.p, sc.valid.p, sc.coef.p, sc.gn_partials.p, form, sc.s);
       uint8_t *ok_dev = reinterpret_cast<uint8_t *>(sc.idx.p);
       launch_gn_rows_map(sc.b.p, M, sc.valid.p, sc.coef.p, sc.gn_state.p, form, ok_dev, sc.gn_rows.p, sc.s);
       LIO_HIP(hipMemcpyAsync(ok_out, ok_dev, m, hipMemcpyDeviceToHost, sc.s));
@@ -856,11 +847,10 @@ int lio_gn_round(const float *map, size_t n_map, const float *stack, size_t m, c
     sc.gn_partials.reserve(std::max<size_t>(size_t(nb) * 28, 1)); sc.gn_state.reserve(1);
     if (n_map) LIO_HIP(hipMemcpyAsync(sc.a.p, map, n_map * sizeof(float4), hipMemcpyHostToDevice, sc.s));
     if (m) LIO_HIP(hipMemcpyAsync(sc.b.p, stack, m * sizeof(float4), hipMemcpyHostToDevice, sc.s));
-    const OdomState st = state_at(T);
+    const OdomState st = odom_state_at(toT(*T));
     LIO_HIP(hipMemcpyAsync(sc.gn_state.p, &st, sizeof(st), hipMemcpyHostToDevice, sc.s));
     float mn[3], mx[3];   // the grid of lio_calculate_features
-    host_bounds(map, n_map, mn, mx);
-    if (n_map == 0) { mn[0] = mn[1] = mn[2] = 0; mx[0] = mx[1] = mx[2] = 0; }
+    host_cloud_bounds(map, n_map, mn, mx);
     sc.grid.build(sc.a.p, n_map, mn, mx, knn_cell_edge(mm), sc.s);
     FeatArgs fa{};
     fa.nframes = 1; fa.max_M = M; fa.min_match_sq_dis = mm; fa.min_plane_dis = mp;
@@ -887,8 +877,7 @@ int lio_calculate_features(const float *map, size_t n_map, const float *stack, s
     float tf[8] = {T->q[0], T->q[1], T->q[2], T->q[3], T->p[0], T->p[1], T->p[2], 0.f};
     LIO_HIP(hipMemcpyAsync(sc.tf.p, tf, sizeof(tf), hipMemcpyHostToDevice, sc.s));
     float mn[3], mx[3];
-    host_bounds(map, n_map, mn, mx);
-    if (n_map == 0) { mn[0] = mn[1] = mn[2] = 0; mx[0] = mx[1] = mx[2] = 0; }
+    host_cloud_bounds(map, n_map, mn, mx);
     sc.grid.build(sc.a.p, n_map, mn, mx, knn_cell_edge(mm), sc.s);
     FeatArgs fa{};
     fa.nframes = 1; fa.max_M = int(m); fa.min_match_sq_dis = mm; fa.min_plane_dis = mp;

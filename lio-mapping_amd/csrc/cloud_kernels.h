@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "dev.h"
+#include "hmath.h"
 
 namespace lio {
 
@@ -77,8 +78,24 @@ struct GridDesc {
 };
 
 // Cell edge >= sqrt(min_match_sq_dis): the 27-cell neighbourhood then holds every point that can pass the d2[4] < min_match_sq_dis
-// gate (Estimator.cc:1021).  mapping.hip, kf_batch.hip and odometry.hip size their grids by an expression of their own (no + 1e-6f).
+// gate (Estimator.cc:1021).  odometry.hip sizes its grids by an expression of its own.
 inline float knn_cell_edge(float min_match_sq_dis) { return std::sqrt(min_match_sq_dis) * 1.0001f + 1e-6f; }
+// ... and the edge the scan-to-map grids (mapping.hip, kf_batch.hip) have always had: no + 1e-6f, so a different partition of the same points
+inline float scan_to_map_cell_edge(float min_match_sq_dis) { return std::sqrt(min_match_sq_dis) * 1.0001f; }
+// min / max of the points of a host cloud (x y z i) that are finite in x, y and z; zeros when there is none
+inline void host_cloud_bounds(const float *xyzi, size_t n, float mn[3], float mx[3]) {
+  for (int d = 0; d < 3; ++d) { mn[d] = 0.f; mx[d] = 0.f; }
+  bool first = true;
+  for (size_t i = 0; i < n; ++i) {
+    const float *p = xyzi + 4 * i;
+    if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) continue;
+    for (int d = 0; d < 3; ++d) {
+      if (first || p[d] < mn[d]) mn[d] = p[d];
+      if (first || p[d] > mx[d]) mx[d] = p[d];
+    }
+    first = false;
+  }
+}
 // inv_cell, origin, dims of the grid over [mn, mx] with one border cell on every side; returns the number of cells
 inline size_t grid_extent(GridDesc &g, const float mn[3], const float mx[3], float cell) {
   g.inv_cell = 1.0f / cell;
@@ -118,15 +135,15 @@ struct FeatArgs {
   int nframes;
   int max_M;
   float min_match_sq_dis, min_plane_dis;
-  // scan-to-map variant (PointMapping.cc:519-619): coefficient sign follows pd2, coef.w = s*pd2, the FOV apex
-  // point_on_z_axis_ is the one fixed before the iterations (:803-806), abs_coeff is written when requested
-  int mapping_mode;   // 0 estimator, 1 PointMapping, 2 MapBuilder::OptimizeMap (no sign flip)
+  // 0 in every launch that takes a FeatArgs (the estimator's); the scan-to-map forms (1 PointMapping, 2 MapBuilder::OptimizeMap) reach the
+  // shared bodies as FeatScalars from the keyframe kernels below.  Both fields stay: they are part of these kernels' argument layout.
+  int mapping_mode;
   float fixed_pz[3];
 };
 // transforms: device array of 8 floats per entry (qx,qy,qz,qw,px,py,pz,pad).  skip_flag: optional device int;
 // when *skip_flag != 0 the launch is a no-op (converged laser-odom loop).
 void launch_features(const FeatArgs &a, const float *transforms, const float4 *map_sorted, const int *cells, const GridDesc &g,
-                     uint8_t *valid, float4 *coef, float *score, const int *skip_flag, hipStream_t s, float4 *abs_coef = nullptr);
+                     uint8_t *valid, float4 *coef, float *score, const int *skip_flag, hipStream_t s);
 
 // stateless K-NN (lio_knn entry point): the product's walk (knn_scan_group, 8 lanes per query), k = 1 or 5, entries at or beyond
 // radius_sq come back as -1 / +inf; idx / sqd are m * k
@@ -141,12 +158,6 @@ void launch_knn_walk(const float4 *query, int m, int lanes_per_query, const floa
 // query per lane (lio_fit_five, include/lio_test_hooks.h): nbr is m * 5 points, fifth_sqd m; every output is m entries, zeros where invalid
 void launch_fit_five(int form, float min_match_sq_dis, float min_plane_dis, const float fixed_pz[3], const float *transform, const float4 *stack,
                      int m, const float4 *nbr, const float *fifth_sqd, uint8_t *valid, float4 *coef, float *score, float4 *abs_coef, hipStream_t s);
-
-// Both branches of one scan-to-map round in a single launch (surf: FeatArgs with one frame, mapping_mode 1 or 2; corner: the
-// first Mc points of the concatenated stack, slots [0, Mc)).
-void launch_map_round(const FeatArgs &surf, const float4 *corner_stack, int Mc, const float *transform, const float4 *corner_map,
-                      const int *corner_cells, const GridDesc &corner_grid, const float4 *surf_map, const int *surf_cells,
-                      const GridDesc &surf_grid, uint8_t *valid, float4 *coef, float4 *abs_coef, const int *skip_flag, hipStream_t s);
 
 // What a solve's feature stage starts from, in ONE launch instead of a fill and two small uploads (each a command of its own in
 // the stream, the uploads staged through the runtime's pinned buffer): valid[0, n_valid) <- 0, the (W + 1) x 8 local transforms,
@@ -168,17 +179,19 @@ struct OdomState {
   int kz;            // number of leading components masked (A.6)
   int nsel;          // rows selected in the last round
 };
-// rows of mat_A / mat_B (Estimator.cc:1272-1301) over slots [0,nslots) of the newest frame, reduced to
-// per-block partials (28 doubles each).  Point of slot s = stack[s % M].
-// b_from_coef != 0: mat_B = -coef.w (the distance stored at feature time, PointMapping.cc:640,650); 2 additionally maps the
-// rotation columns into the map frame with the MapBuilder weights (MapBuilder.cc:903-914).
-void launch_odom_rows(const float4 *stack, int M, int nslots, const uint8_t *valid, const float4 *coef, const OdomState *st,
-                      double *partials, int nblocks, hipStream_t s, int b_from_coef = 0);
-// reduce + 6x6 solve + degeneracy mask + transform update + convergence test (Estimator.cc:1303-1357)
-// min_rows > 0: a round with fewer selected rows leaves the transform untouched (`continue`, PointMapping.cc:623-626).
-// left_update != 0: rot = DeltaQ(x) * rot (MapBuilder.cc:978-979) instead of rot * DeltaQ(x).
-void launch_odom_update(const double *partials, int nblocks, OdomState *st, int iter, hipStream_t s, int min_rows = 0, int left_update = 0,
-                        OdomState *mail = nullptr, const HostSignal &sig = HostSignal());
+// the state a Gauss-Newton loop starts from at pose T: no round run, nothing converged
+inline OdomState odom_state_at(const Rigid<float> &T) {
+  OdomState st{};
+  st.T[0] = T.rot.x; st.T[1] = T.rot.y; st.T[2] = T.rot.z; st.T[3] = T.rot.w;
+  st.T[4] = T.pos.x; st.T[5] = T.pos.y; st.T[6] = T.pos.z;
+  return st;
+}
+// point_on_z_axis_ of a pose (PointMapping.cc:803-806): the apex of the FOV test, fixed before the scan-to-map iterations
+inline void point_on_z_axis(const Rigid<float> &T, float pz[3]) {
+  const Vec3<float> z = rotate(T.rot, Vec3<float>(0.f, 0.f, 10.f));
+  pz[0] = z.x + T.pos.x; pz[1] = z.y + T.pos.y; pz[2] = z.z + T.pos.z;
+}
+// blocks of a row reduction over nslots slots (28 doubles of partials each)
 int odom_rows_blocks(int nslots);
 // One round of the newest frame's loop in two launches (search + plane fit + rows per block; fold + update).  a.fr[0] names the
 // stack; slots of round r start at base_slot (+ r * M with keep != 0: keep_features, Estimator.cc:978-980); partials holds
@@ -197,12 +210,20 @@ void launch_gn_fold(const double *partials, int nblocks, int wide, double *sums_
 // odom_update_from_sums on device sums and a device state, in place
 void launch_gn_step(const double *sums, OdomState *st, int iter, int min_rows, int left_update, hipStream_t s);
 
-// ---- batched keyframe refinement (config 5: B independent OptimizeMap / OptimizeTransformTobeMapped loops, MapBuilder.cc:624-1014,
-// PointMapping.cc:325-753).  Slots of keyframe k = [slot_off, slot_off + Mc) corner, then Ms surf, in one concatenated stack.
+// ---- the scan-to-map Gauss-Newton loop (OptimizeMap / OptimizeTransformTobeMapped, MapBuilder.cc:624-1014, PointMapping.cc:325-753) for a
+// table of keyframes: B independent loops in the batched refinement (config 5, kf_batch.hip), a table of one in the map handle (mapping.hip).
+// Slots of keyframe k = [slot_off, slot_off + Mc) corner, then Ms surf, in one concatenated stack.  Three launches per round:
+//   round  : corner line search + surf plane search (PointMapping.cc:377-619), blockIdx.y picks the branch
+//   rows   : mat_A / mat_B (Estimator.cc:1272-1301) reduced to nb partials of 28 doubles.  b_from_coef != 0: mat_B = -coef.w (the distance
+//            stored at feature time, PointMapping.cc:640,650); 2 additionally maps the rotation columns into the map frame with the
+//            MapBuilder weights (MapBuilder.cc:903-914)
+//   update : fold + 6x6 solve + degeneracy mask + transform update + convergence test (Estimator.cc:1303-1357).  min_rows > 0: a round with
+//            fewer selected rows leaves the transform untouched (`continue`, PointMapping.cc:623-626).  left_update != 0: rot = DeltaQ(x) * rot
+//            (MapBuilder.cc:978-979) instead of rot * DeltaQ(x)
 struct KfDesc {
   int slot_off, Mc, Ms;
   int map;          // index into the KfMapDesc array
-  int nb;           // row-reduction blocks of this keyframe (= odom_rows_blocks(Mc + Ms), as in the single-keyframe path)
+  int nb;           // row-reduction blocks of this keyframe (= odom_rows_blocks(Mc + Ms))
   int part_off;     // first partial row (28 doubles each)
   float pz[3];      // point_on_z_axis_ fixed before the iterations
 };
@@ -215,14 +236,17 @@ struct KfMapDesc {
 // queries behind them), e.g. sorted by map cell (launch_kf_query_keys + the segmented sort)
 void launch_kf_query_keys(const KfDesc *kd, const KfMapDesc *md, const OdomState *st, int n_keyframes, int max_Mc, int max_Ms, const float4 *stack_all, uint32_t *keys,
                           hipStream_t s);
-void launch_kf_round(const KfDesc *kd, const KfMapDesc *md, const OdomState *st, int n_keyframes, int max_Mc, int max_Ms, long long total_queries,
-                     const float4 *stack_all, const uint32_t *order_or_null, float min_match_sq_dis, float min_plane_dis, int mapping_mode, uint8_t *valid, float4 *coef,
-                     hipStream_t s);
+// lpq: lanes per query, 1, 4 or 8 (the result does not depend on it).  abs_coef_or_null: the unsigned plane of every valid surf query at
+// its slot (the map handle's score list, PointMapping.cc:572-592)
+void launch_kf_round(const KfDesc *kd, const KfMapDesc *md, const OdomState *st, int n_keyframes, int max_Mc, int max_Ms, int lpq, const float4 *stack_all,
+                     const uint32_t *order_or_null, float min_match_sq_dis, float min_plane_dis, int mapping_mode, uint8_t *valid, float4 *coef,
+                     float4 *abs_coef_or_null, hipStream_t s);
 void launch_kf_rows(const KfDesc *kd, const OdomState *st, int n_keyframes, int max_nb, const float4 *stack_all, const uint8_t *valid, const float4 *coef,
                     double *partials, int b_from_coef, hipStream_t s);
-// n_converged (device int) is incremented once per keyframe when it converges
+// n_converged (device int, optional) is incremented once per keyframe when it converges.  sig (a launch of ONE keyframe only): the block posts
+// the keyframe's state to the host's mailbox `mail` behind the update (dev.h: HostSignal), converged before this launch or not
 void launch_kf_update(const KfDesc *kd, OdomState *st, int n_keyframes, const double *partials, int iter, int min_rows, int left_update, int *n_converged,
-                      hipStream_t s);
+                      OdomState *mail, const HostSignal &sig, hipStream_t s);
 
 #if defined(__HIPCC__)
 // Fixed-order sum of `nblocks` rows of 28 doubles by a 256-thread block: 8 groups of 32 lanes take the rows b = g (mod 8)

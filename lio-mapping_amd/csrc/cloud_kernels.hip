@@ -531,51 +531,19 @@ void launch_fit_five(int form, float min_match_sq_dis, float min_plane_dis, cons
   LIO_HIP(hipGetLastError());
 }
 
-// One round of the scan-to-map search in ONE launch: blockIdx.y = 0 runs the corner (line) branch against the corner map,
-// blockIdx.y = 1 the surf (plane) branch against the surf map.  No cross-stream events, one dispatch.
-struct MapRoundArgs {
-  const float4 *corner_stack; int Mc;
-  const float4 *corner_map; const int *corner_cells; GridDesc corner_grid;
-  const float4 *surf_map; const int *surf_cells; GridDesc surf_grid;
-  int blocks_corner, blocks_surf;
-};
-__global__ void __launch_bounds__(128) k_map_round(FeatArgs a, MapRoundArgs m, const float *__restrict__ tp, uint8_t *__restrict__ valid,
-                                                  float4 *__restrict__ coef, float4 *__restrict__ abs_coef, const int *__restrict__ skip_flag) {
-  if (skip_flag && *skip_flag) return;
-  if (blockIdx.y == 0) {
-    if (int(blockIdx.x) >= m.blocks_corner) return;
-    line_features_body(blockIdx.x, m.corner_stack, m.Mc, 0, tp, Vec3<float>(a.fixed_pz[0], a.fixed_pz[1], a.fixed_pz[2]), a.min_match_sq_dis,
-                       m.corner_map, m.corner_cells, m.corner_grid, valid, coef);
-  } else {
-    if (int(blockIdx.x) >= m.blocks_surf) return;
-    features_body<true, 8>(a.fr[0], feat_scalars(a), blockIdx.x, tp, m.surf_map, m.surf_cells, m.surf_grid, valid, coef, nullptr, abs_coef);
-  }
-}
-
-void launch_map_round(const FeatArgs &surf, const float4 *corner_stack, int Mc, const float *transform, const float4 *corner_map,
-                      const int *corner_cells, const GridDesc &corner_grid, const float4 *surf_map, const int *surf_cells,
-                      const GridDesc &surf_grid, uint8_t *valid, float4 *coef, float4 *abs_coef, const int *skip_flag, hipStream_t s) {
-  MapRoundArgs m{corner_stack, Mc, corner_map, corner_cells, corner_grid, surf_map, surf_cells, surf_grid, cdiv((long long)Mc * FEAT_LPQ, 128),
-                 cdiv((long long)surf.max_M * 8, 128)};
-  const int bx = std::max(1, std::max(m.blocks_corner, m.blocks_surf));
-  hipLaunchKernelGGL(k_map_round, dim3(bx, 2), dim3(128), 0, s, surf, m, transform, valid, coef, abs_coef, skip_flag);
-  LIO_HIP(hipGetLastError());
-}
-
 void launch_features(const FeatArgs &a, const float *transforms, const float4 *map_sorted, const int *cells, const GridDesc &g,
-                     uint8_t *valid, float4 *coef, float *score, const int *skip_flag, hipStream_t s, float4 *abs_coef) {
+                     uint8_t *valid, float4 *coef, float *score, const int *skip_flag, hipStream_t s) {
   if (a.nframes <= 0 || a.max_M <= 0) return;
+  if (a.mapping_mode) throw DeviceError("launch_features: the scan-to-map forms run through launch_kf_round");
   // lanes per query: 8 when the launch is small (latency-bound: shorter per-lane candidate walks), 4 when it already fills
   // the GPU several times over (throughput-bound: fewer shuffle-merge rounds per query)
   const bool big = (long long)a.max_M * a.nframes >= 50000;
   const dim3 grid(cdiv((long long)a.max_M * (big ? 4 : 8), FEAT_THREADS), a.nframes);
-  if (a.mapping_mode)
-    hipLaunchKernelGGL((k_features<true, 8>), dim3(cdiv((long long)a.max_M * 8, FEAT_THREADS), a.nframes), dim3(FEAT_THREADS), 0, s, a, transforms, map_sorted,
-                       cells, g, valid, coef, score, skip_flag, abs_coef);
-  else if (big)
-    hipLaunchKernelGGL((k_features<false, 4>), grid, dim3(FEAT_THREADS), 0, s, a, transforms, map_sorted, cells, g, valid, coef, score, skip_flag, abs_coef);
+  float4 *const no_abs = nullptr;   // (the unsigned plane is an output of the scan-to-map forms only)
+  if (big)
+    hipLaunchKernelGGL((k_features<false, 4>), grid, dim3(FEAT_THREADS), 0, s, a, transforms, map_sorted, cells, g, valid, coef, score, skip_flag, no_abs);
   else
-    hipLaunchKernelGGL((k_features<false, 8>), grid, dim3(FEAT_THREADS), 0, s, a, transforms, map_sorted, cells, g, valid, coef, score, skip_flag, abs_coef);
+    hipLaunchKernelGGL((k_features<false, 8>), grid, dim3(FEAT_THREADS), 0, s, a, transforms, map_sorted, cells, g, valid, coef, score, skip_flag, no_abs);
   LIO_HIP(hipGetLastError());
 }
 
@@ -618,40 +586,12 @@ __device__ __forceinline__ void odom_rows_body(int block_x, int nblocks, const f
   }
 }
 
-__global__ void __launch_bounds__(ODOM_ROW_THREADS) k_odom_rows(const float4 *__restrict__ stack, int M, int nslots,
-                                                                const uint8_t *__restrict__ valid, const float4 *__restrict__ coef,
-                                                                const OdomState *__restrict__ st, double *__restrict__ partials,
-                                                                int b_from_coef) {
-  if (st->converged) return;
-  odom_rows_body(blockIdx.x, gridDim.x, stack, M, nslots, valid, coef, st, partials, b_from_coef);
-}
-
-void launch_odom_rows(const float4 *stack, int M, int nslots, const uint8_t *valid, const float4 *coef, const OdomState *st,
-                      double *partials, int nblocks, hipStream_t s, int b_from_coef) {
-  hipLaunchKernelGGL(k_odom_rows, dim3(nblocks), dim3(ODOM_ROW_THREADS), 0, s, stack, M, nslots, valid, coef, st, partials, b_from_coef);
-  LIO_HIP(hipGetLastError());
-}
-
 __device__ __forceinline__ void odom_update_body(const double *__restrict__ partials, int nblocks, OdomState *st, int iter, int min_rows,
                                                  int left_update) {
   // column k of the partials is summed by lane k (fixed order), then lane 0 runs the scalar 6x6 step
   __shared__ double ssum[28];
   reduce_partials28(partials, nblocks, ssum);
   odom_update_from_sums(ssum, st, iter, min_rows, left_update);
-}
-__global__ void k_odom_update(const double *__restrict__ partials, int nblocks, OdomState *st, int iter, int min_rows, int left_update, OdomState *mail,
-                              HostSignal sig) {
-  if (!st->converged) odom_update_body(partials, nblocks, st, iter, min_rows, left_update);
-  if (sig.flag) {   // the rounds at which the host looks at the convergence flag post the state to its mailbox (dev.h)
-    __syncthreads();
-    if (threadIdx.x < 64) post_host_mail(sig, mail, st, int(sizeof(OdomState) / 4), threadIdx.x);
-  }
-}
-
-void launch_odom_update(const double *partials, int nblocks, OdomState *st, int iter, hipStream_t s, int min_rows, int left_update, OdomState *mail,
-                        const HostSignal &sig) {
-  hipLaunchKernelGGL(k_odom_update, dim3(1), dim3(256), 0, s, partials, nblocks, st, iter, min_rows, left_update, mail, sig);
-  LIO_HIP(hipGetLastError());
 }
 
 template <int LPQ>
@@ -751,12 +691,13 @@ void launch_gn_step(const double *sums, OdomState *st, int iter, int min_rows, i
 }
 
 // ------------------------------------------------------------------------------------------------
-// Batched keyframe refinement: B independent scan-to-map loops advance together, one launch per stage per round
+// The scan-to-map loop over a table of keyframes: B independent loops advance together, one launch per stage per round (kf_batch.hip: a batch,
+// mapping.hip: a table of one).  blockIdx.y = 0 runs the corner (line) branch against the corner map, 1 the surf (plane) branch against the surf map.
 // ------------------------------------------------------------------------------------------------
 template <int LPQ>
 __device__ __forceinline__ void kf_round_body(const KfDesc *__restrict__ kd, const KfMapDesc *__restrict__ md, const OdomState *__restrict__ st,
                                                  const float4 *__restrict__ stack_all, const uint32_t *__restrict__ order, float min_match_sq_dis, float min_plane_dis,
-                                                 int mapping_mode, uint8_t *__restrict__ valid, float4 *__restrict__ coef) {
+                                                 int mapping_mode, uint8_t *__restrict__ valid, float4 *__restrict__ coef, float4 *__restrict__ abs_coef) {
   const int k = blockIdx.z;
   if (st[k].converged) return;
   const KfDesc d = kd[k];
@@ -772,23 +713,23 @@ __device__ __forceinline__ void kf_round_body(const KfDesc *__restrict__ kd, con
     const KfMapDesc &m = md[d.map];
     const FeatFrame fr{stack_all + d.slot_off + d.Mc, d.Ms, d.slot_off + d.Mc, 0, order ? order + d.slot_off + d.Mc : nullptr};
     const FeatScalars fs{min_match_sq_dis, min_plane_dis, mapping_mode, {d.pz[0], d.pz[1], d.pz[2]}};
-    features_body<true, LPQ>(fr, fs, blockIdx.x, tp, rebase(stack_all, m.surf_sorted), rebase(stack_all, m.surf_cells), m.surf_grid, valid, coef, nullptr, nullptr);
+    features_body<true, LPQ>(fr, fs, blockIdx.x, tp, rebase(stack_all, m.surf_sorted), rebase(stack_all, m.surf_cells), m.surf_grid, valid, coef, nullptr, abs_coef);
   }
 }
 
 template <int LPQ>
 __global__ void __launch_bounds__(128) k_kf_round(const KfDesc *__restrict__ kd, const KfMapDesc *__restrict__ md, const OdomState *__restrict__ st,
                                                  const float4 *__restrict__ stack_all, const uint32_t *__restrict__ order, float min_match_sq_dis, float min_plane_dis,
-                                                 int mapping_mode, uint8_t *__restrict__ valid, float4 *__restrict__ coef) {
-  kf_round_body<LPQ>(kd, md, st, stack_all, order, min_match_sq_dis, min_plane_dis, mapping_mode, valid, coef);
+                                                 int mapping_mode, uint8_t *__restrict__ valid, float4 *__restrict__ coef, float4 *__restrict__ abs_coef) {
+  kf_round_body<LPQ>(kd, md, st, stack_all, order, min_match_sq_dis, min_plane_dis, mapping_mode, valid, coef, abs_coef);
 }
 // the one-lane-per-query form is bound by gather latency: 8 waves per SIMD (64 VGPRs, the fit phase spills a little) beats
 // the 5 waves the default allocation gives by 15% (54.4 -> 46.1 ms at 1000 HDL-64 keyframes)
 __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(8, 8)))
 k_kf_round1_w8(const KfDesc *__restrict__ kd, const KfMapDesc *__restrict__ md, const OdomState *__restrict__ st,
                const float4 *__restrict__ stack_all, const uint32_t *__restrict__ order, float min_match_sq_dis, float min_plane_dis,
-               int mapping_mode, uint8_t *__restrict__ valid, float4 *__restrict__ coef) {
-  kf_round_body<1>(kd, md, st, stack_all, order, min_match_sq_dis, min_plane_dis, mapping_mode, valid, coef);
+               int mapping_mode, uint8_t *__restrict__ valid, float4 *__restrict__ coef, float4 *__restrict__ abs_coef) {
+  kf_round_body<1>(kd, md, st, stack_all, order, min_match_sq_dis, min_plane_dis, mapping_mode, valid, coef, abs_coef);
 }
 
 __global__ void __launch_bounds__(ODOM_ROW_THREADS) k_kf_rows(const KfDesc *__restrict__ kd, const OdomState *__restrict__ st,
@@ -804,12 +745,17 @@ __global__ void __launch_bounds__(ODOM_ROW_THREADS) k_kf_rows(const KfDesc *__re
 }
 
 __global__ void k_kf_update(const KfDesc *__restrict__ kd, OdomState *st, const double *__restrict__ partials, int iter, int min_rows, int left_update,
-                            int *n_converged) {
+                            int *n_converged, OdomState *mail, HostSignal sig) {
   const int k = blockIdx.x;
-  if (st[k].converged) return;
-  const KfDesc d = kd[k];
-  odom_update_body(partials + size_t(d.part_off) * 28, d.nb, st + k, iter, min_rows, left_update);
-  if (threadIdx.x == 0 && st[k].converged) atomicAdd(n_converged, 1);
+  if (!st[k].converged) {
+    const KfDesc d = kd[k];
+    odom_update_body(partials + size_t(d.part_off) * 28, d.nb, st + k, iter, min_rows, left_update);
+    if (n_converged && threadIdx.x == 0 && st[k].converged) atomicAdd(n_converged, 1);
+  }
+  if (sig.flag) {   // the rounds at which the host looks at the convergence flag post the state to its mailbox (dev.h); a launch of one keyframe
+    __syncthreads();
+    if (threadIdx.x < 64) post_host_mail(sig, mail, st + k, int(sizeof(OdomState) / 4), threadIdx.x);
+  }
 }
 
 // the map cell of every query under its keyframe's current transform: the key the queries' processing order is sorted by (all ones: outside
@@ -839,18 +785,15 @@ void launch_kf_query_keys(const KfDesc *kd, const KfMapDesc *md, const OdomState
   LIO_HIP(hipGetLastError());
 }
 
-void launch_kf_round(const KfDesc *kd, const KfMapDesc *md, const OdomState *st, int n_keyframes, int max_Mc, int max_Ms, long long total_queries,
-                     const float4 *stack_all, const uint32_t *order, float min_match_sq_dis, float min_plane_dis, int mapping_mode, uint8_t *valid, float4 *coef,
+void launch_kf_round(const KfDesc *kd, const KfMapDesc *md, const OdomState *st, int n_keyframes, int max_Mc, int max_Ms, int lpq, const float4 *stack_all,
+                     const uint32_t *order, float min_match_sq_dis, float min_plane_dis, int mapping_mode, uint8_t *valid, float4 *coef, float4 *abs_coef,
                      hipStream_t s) {
-  // lanes per query: a small batch is latency-bound (8 lanes shorten each query's dependent candidate walk); once the batch
-  // fills the GPU many times over, one lane per query wins 1.8x (no merge rounds, no idle lanes in the fit): measured
-  // 96 / 69 / 59 / 55 ms for 8 / 4 / 2 / 1 lanes at 1000 HDL-64 keyframes.  The result does not depend on the split.
-  const int lpq = total_queries >= 250000 ? 1 : total_queries >= 60000 ? 4 : 8;   // (round 6, flat candidate lists: 16 keyframes = 377 k queries 0.89 ms at one lane against 0.96 at four; 8 keyframes 0.62 against 0.55)
+  if (lpq != 1 && lpq != 4 && lpq != 8) throw DeviceError("launch_kf_round: lanes per query is 1, 4 or 8");
   const int bx = std::max(1, cdiv((long long)std::max(max_Mc, max_Ms) * lpq, 128));
   const dim3 grid(bx, 2, n_keyframes);
-  if (lpq == 1) hipLaunchKernelGGL(k_kf_round1_w8, grid, dim3(128), 0, s, kd, md, st, stack_all, order, min_match_sq_dis, min_plane_dis, mapping_mode, valid, coef);
-  else if (lpq == 4) hipLaunchKernelGGL(k_kf_round<4>, grid, dim3(128), 0, s, kd, md, st, stack_all, order, min_match_sq_dis, min_plane_dis, mapping_mode, valid, coef);
-  else hipLaunchKernelGGL(k_kf_round<8>, grid, dim3(128), 0, s, kd, md, st, stack_all, order, min_match_sq_dis, min_plane_dis, mapping_mode, valid, coef);
+  if (lpq == 1) hipLaunchKernelGGL(k_kf_round1_w8, grid, dim3(128), 0, s, kd, md, st, stack_all, order, min_match_sq_dis, min_plane_dis, mapping_mode, valid, coef, abs_coef);
+  else if (lpq == 4) hipLaunchKernelGGL(k_kf_round<4>, grid, dim3(128), 0, s, kd, md, st, stack_all, order, min_match_sq_dis, min_plane_dis, mapping_mode, valid, coef, abs_coef);
+  else hipLaunchKernelGGL(k_kf_round<8>, grid, dim3(128), 0, s, kd, md, st, stack_all, order, min_match_sq_dis, min_plane_dis, mapping_mode, valid, coef, abs_coef);
   LIO_HIP(hipGetLastError());
 }
 void launch_kf_rows(const KfDesc *kd, const OdomState *st, int n_keyframes, int max_nb, const float4 *stack_all, const uint8_t *valid, const float4 *coef,
@@ -859,8 +802,9 @@ void launch_kf_rows(const KfDesc *kd, const OdomState *st, int n_keyframes, int 
   LIO_HIP(hipGetLastError());
 }
 void launch_kf_update(const KfDesc *kd, OdomState *st, int n_keyframes, const double *partials, int iter, int min_rows, int left_update, int *n_converged,
-                      hipStream_t s) {
-  hipLaunchKernelGGL(k_kf_update, dim3(n_keyframes), dim3(256), 0, s, kd, st, partials, iter, min_rows, left_update, n_converged);
+                      OdomState *mail, const HostSignal &sig, hipStream_t s) {
+  if (sig.flag && n_keyframes != 1) throw DeviceError("launch_kf_update: only a launch of one keyframe posts to the host's mailbox");
+  hipLaunchKernelGGL(k_kf_update, dim3(n_keyframes), dim3(256), 0, s, kd, st, partials, iter, min_rows, left_update, n_converged, mail, sig);
   LIO_HIP(hipGetLastError());
 }
 

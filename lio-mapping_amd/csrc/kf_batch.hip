@@ -1,5 +1,5 @@
 // kf_batch.hip — host side of the batched keyframe refinement; the kernels are the scan-to-map stages of cloud_kernels.hip
-// indexed by keyframe.
+// indexed by keyframe, the ones the map handle (mapping.hip) runs on a table of one.
 #include "kf_batch.h"
 #include "rccl_comm.h"
 
@@ -27,24 +27,10 @@ KfBatchDev::~KfBatchDev() {
   if (stream_) (void)hipStreamDestroy(stream_);
 }
 
-static void host_bounds(const float *xyzi, size_t n, float mn[3], float mx[3]) {
-  for (int d = 0; d < 3; ++d) { mn[d] = 0.f; mx[d] = 0.f; }
-  bool first = true;
-  for (size_t i = 0; i < n; ++i) {
-    const float *p = xyzi + 4 * i;
-    if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) continue;
-    for (int d = 0; d < 3; ++d) {
-      if (first || p[d] < mn[d]) mn[d] = p[d];
-      if (first || p[d] > mx[d]) mx[d] = p[d];
-    }
-    first = false;
-  }
-}
-
 int KfBatchDev::AddMap(const float *corner, size_t nc, const float *surf, size_t ns) {
   std::unique_ptr<Map> m(new Map);
   m->nc = nc; m->ns = ns;
-  const float cell = std::sqrt(cfg_.min_match_sq_dis) * 1.0001f;
+  const float cell = scan_to_map_cell_edge(cfg_.min_match_sq_dis);
   const float *src[2] = {corner, surf};
   const size_t cnt[2] = {nc, ns};
   DBuf<float4> *dst[2] = {&m->corner, &m->surf};
@@ -52,7 +38,7 @@ int KfBatchDev::AddMap(const float *corner, size_t nc, const float *surf, size_t
   for (int c = 0; c < 2; ++c) {
     dst[c]->reserve(std::max<size_t>(cnt[c], 1));
     float mn[3], mx[3];
-    host_bounds(src[c], cnt[c], mn, mx);
+    host_cloud_bounds(src[c], cnt[c], mn, mx);
     if (cnt[c]) LIO_HIP(hipMemcpyAsync(dst[c]->p, src[c], cnt[c] * sizeof(float4), hipMemcpyHostToDevice, stream_));
     grid[c]->build(dst[c]->p, cnt[c], mn, mx, cell, stream_);
   }
@@ -74,15 +60,12 @@ int KfBatchDev::AddKeyframe(int map, const float *corner, size_t nc, const float
   d.nb = odom_rows_blocks(int(nc + ns));
   d.part_off = total_nb_;
   total_nb_ += d.nb;
-  const Vec3<float> z = rotate(T.rot, Vec3<float>(0.f, 0.f, 10.f));  // point_on_z_axis_ (PointMapping.cc:803-806)
-  d.pz[0] = z.x + T.pos.x; d.pz[1] = z.y + T.pos.y; d.pz[2] = z.z + T.pos.z;
+  point_on_z_axis(T, d.pz);
   const size_t base = h_stack_.size();
   h_stack_.resize(base + nc + ns);
   if (nc) std::memcpy(&h_stack_[base], corner, nc * sizeof(float4));
   if (ns) std::memcpy(&h_stack_[base + nc], surf, ns * sizeof(float4));
-  OdomState st;
-  std::memset(&st, 0, sizeof(st));
-  st.T[0] = T.rot.x; st.T[1] = T.rot.y; st.T[2] = T.rot.z; st.T[3] = T.rot.w; st.T[4] = T.pos.x; st.T[5] = T.pos.y; st.T[6] = T.pos.z;
+  OdomState st = odom_state_at(T);
   const Map &m = *maps_[size_t(map)];
   if (m.nc <= 10 || m.ns <= 100) { st.converged = 1; ++n_gated_; }  // the early return of :327-329: pose untouched, 0 iterations
   h_st0_.push_back(st);
@@ -156,14 +139,18 @@ void KfBatchDev::Refine() {
   const bool four_dof = cfg_.map_builder && cfg_.enable_4d;
   const int mode = four_dof ? 2 : 1;
   const int max_it = cfg_.num_max_iterations;
+  // lanes per query: a small batch is latency-bound (8 lanes shorten each query's dependent candidate walk); once the batch
+  // fills the GPU many times over, one lane per query wins 1.8x (no merge rounds, no idle lanes in the fit): measured
+  // 96 / 69 / 59 / 55 ms for 8 / 4 / 2 / 1 lanes at 1000 HDL-64 keyframes.  The result does not depend on the split.
+  const int lpq = n_queries_ >= 250000 ? 1 : n_queries_ >= 60000 ? 4 : 8;   // (round 6, flat candidate lists: 16 keyframes = 377 k queries 0.89 ms at one lane against 0.96 at four; 8 keyframes 0.62 against 0.55)
   LIO_HIP(hipEventRecord(ev0_, s));
   for (int iter = 0; iter < max_it; ++iter) {
     for (int off = 0; off < B; off += kChunk) {
       const int nk = std::min(kChunk, B - off);
-      launch_kf_round(d_kd_.p + off, d_md_.p, d_st_.p + off, nk, max_Mc_, max_Ms_, n_queries_, d_stack_.p, order_.p, cfg_.min_match_sq_dis, cfg_.min_plane_dis, mode, valid_.p,
-                      coef_.p, s);
+      launch_kf_round(d_kd_.p + off, d_md_.p, d_st_.p + off, nk, max_Mc_, max_Ms_, lpq, d_stack_.p, order_.p, cfg_.min_match_sq_dis, cfg_.min_plane_dis, mode, valid_.p,
+                      coef_.p, nullptr, s);
       launch_kf_rows(d_kd_.p + off, d_st_.p + off, nk, max_nb_, d_stack_.p, valid_.p, coef_.p, partials_.p, mode, s);
-      launch_kf_update(d_kd_.p + off, d_st_.p + off, nk, partials_.p, iter, 50, four_dof ? 1 : 0, d_nconv_.p, s);
+      launch_kf_update(d_kd_.p + off, d_st_.p + off, nk, partials_.p, iter, 50, four_dof ? 1 : 0, d_nconv_.p, nullptr, HostSignal(), s);
     }
     ++rounds_;
     // most keyframes converge in 5-7 rounds; converged keyframes cost nothing in later rounds, so peek sparsely

@@ -37,6 +37,9 @@ struct MapSurroundSet {
 
 struct MapCounters { int n_valid, n_rest, n_new_valid, n_new_rest, n_out, pad[3]; };
 
+// the keyframe table of one that Optimize runs the scan-to-map chain on (cloud_kernels.h): one record of each kind and the loop's state
+struct KfOne { KfMapDesc md; KfDesc kd; OdomState st; };
+
 class MappingDev {
  public:
   static constexpr int L = 21, Wd = 21, H = 11;  // laser_cloud_length_/width_/height_ (PointMapping.cc:79-81)
@@ -127,11 +130,12 @@ class MappingDev {
   DBuf<float4> stack_all_;
   DBuf<uint8_t> f_valid_;
   DBuf<float4> f_coef_, f_abs_;
-  DBuf<OdomState> d_state_;
+  DBuf<KfOne> d_one_;
   DBuf<double> d_partials_;
   HostBuf<char> h_mail_;          // pinned, coherent: the state's mailbox
   OdomState *h_state_ = nullptr;  // ... the state in it
   unsigned *h_flag_ = nullptr;    // its completion word
+  KfOne *h_one_ = nullptr;        // ... and the table of one that Optimize uploads
   unsigned seq_ = 0;
   size_t n_score_slots_ = 0;
   bool score_ready_ = false;

@@ -295,12 +295,13 @@ MappingDev::MappingDev(const lio_map_config &cfg) : cfg_(cfg) {
     m.bounds.reserve(1);
     m.cube_bounds.reserve(LIO_MAP_MAX_VALID * 6);
   }
-  // coherent: the update kernel posts the state and a completion word here (dev.h: HostSignal)
-  h_mail_.alloc(128, hipHostMallocCoherent, true);
+  // coherent: the update kernel posts the state and a completion word here (dev.h: HostSignal); behind them the table of one on its way up
+  h_mail_.alloc(128 + sizeof(KfOne), hipHostMallocCoherent, true);
   static_assert(sizeof(OdomState) <= 64, "mailbox layout");
   h_state_ = reinterpret_cast<OdomState *>(h_mail_.p);
   h_flag_ = reinterpret_cast<unsigned *>(h_mail_.p + 64);
-  d_state_.reserve(1);
+  h_one_ = reinterpret_cast<KfOne *>(h_mail_.p + 128);
+  d_one_.reserve(1);
   sur_count_.reserve(1); sur_desc_.reserve(1);
   h_sur_count_.alloc(1, hipHostMallocDefault, true);
   h_sur_desc_.alloc(1, hipHostMallocDefault, true);
@@ -579,10 +580,7 @@ void MappingDev::Process(const float *corner_last, size_t n_corner, const float 
     LIO_HIP(hipMemcpyAsync(m.in.p, src[c], cnt[c] * sizeof(float4), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_stack_roundtrip, dim3(cdiv(int(cnt[c]), 256)), dim3(256), 0, s, m.in.p, int(cnt[c]), T0.rot, T0.pos, m.stack_raw.p);
   }
-  {
-    Vec3<float> z = rotate(T0.rot, Vec3<float>(0.f, 0.f, 10.f));
-    pz_[0] = z.x + T0.pos.x; pz_[1] = z.y + T0.pos.y; pz_[2] = z.z + T0.pos.z;
-  }
+  point_on_z_axis(T0, pz_);
   // sensor cube and window shift (:808-925); absolute keys make the shift a change of cen_ only
   const float posv[3] = {T0.pos.x, T0.pos.y, T0.pos.z};
   const int dims[3] = {L, Wd, H};
@@ -689,7 +687,7 @@ void MappingDev::Optimize(bool four_dof) {
     LIO_HIP(hipMemcpyAsync(m->h_bounds.p, m->bounds.p, sizeof(VoxParams), hipMemcpyDeviceToHost, s));
   }
   LIO_HIP(hipStreamSynchronize(s));
-  const float cell = std::sqrt(cfg_.min_match_sq_dis) * 1.0001f;
+  const float cell = scan_to_map_cell_edge(cfg_.min_match_sq_dis);
   for (ClassMap *m : cm) m->grid.build(m->pool.p + m->n_rest, m->n_valid, m->h_bounds.p->mn, m->h_bounds.p->mx, cell, s);
 
   const int Mc = int(mc.n_stack), Ms = int(ms.n_stack), M = Mc + Ms;
@@ -701,26 +699,24 @@ void MappingDev::Optimize(bool four_dof) {
   stack_all_.reserve(size_t(M)); f_valid_.reserve(size_t(M)); f_coef_.reserve(size_t(M)); f_abs_.reserve(size_t(M));
   if (Mc) LIO_HIP(hipMemcpyAsync(stack_all_.p, mc.stack_ds.p, size_t(Mc) * sizeof(float4), hipMemcpyDeviceToDevice, s));
   if (Ms) LIO_HIP(hipMemcpyAsync(stack_all_.p + Mc, ms.stack_ds.p, size_t(Ms) * sizeof(float4), hipMemcpyDeviceToDevice, s));
-  OdomState st;
-  std::memset(&st, 0, sizeof(st));
-  const Rigid<float> &T = transform_tobe_mapped_;
-  st.T[0] = T.rot.x; st.T[1] = T.rot.y; st.T[2] = T.rot.z; st.T[3] = T.rot.w; st.T[4] = T.pos.x; st.T[5] = T.pos.y; st.T[6] = T.pos.z;
-  *h_state_ = st;
-  LIO_HIP(hipMemcpyAsync(d_state_.p, h_state_, sizeof(OdomState), hipMemcpyHostToDevice, s));
-  const float *d_T = reinterpret_cast<const float *>(d_state_.p);
-  const int *d_conv = reinterpret_cast<const int *>(reinterpret_cast<const char *>(d_state_.p) + offsetof(OdomState, converged));
+  // the loop is the keyframe chain of cloud_kernels.hip on a table of one: this window's two grids, the whole stack as one keyframe, the
+  // starting state — one upload
   const int nb = odom_rows_blocks(M);
   d_partials_.reserve(size_t(nb) * 28);
-  FeatArgs fa{};
-  fa.nframes = 1; fa.max_M = Ms;
-  fa.fr[0].stack = stack_all_.p + Mc; fa.fr[0].M = Ms; fa.fr[0].slot_off = Mc; fa.fr[0].tf_index = 0;
-  fa.min_match_sq_dis = cfg_.min_match_sq_dis; fa.min_plane_dis = cfg_.min_plane_dis;
-  fa.mapping_mode = four_dof ? 2 : 1;
-  for (int d = 0; d < 3; ++d) fa.fixed_pz[d] = pz_[d];
+  KfOne &one = *h_one_;
+  one.md = KfMapDesc{mc.grid.sorted(), mc.grid.cells(), mc.grid.desc(), ms.grid.sorted(), ms.grid.cells(), ms.grid.desc()};
+  one.kd = KfDesc{0, Mc, Ms, 0, nb, 0, {pz_[0], pz_[1], pz_[2]}};
+  one.st = odom_state_at(transform_tobe_mapped_);
+  *h_state_ = one.st;   // (what the loop's end reads when no round runs)
+  LIO_HIP(hipMemcpyAsync(d_one_.p, h_one_, sizeof(KfOne), hipMemcpyHostToDevice, s));
+  const KfMapDesc *d_md = &d_one_.p->md;
+  const KfDesc *d_kd = &d_one_.p->kd;
+  OdomState *d_st = &d_one_.p->st;
+  const int mode = four_dof ? 2 : 1;
   const int max_it = cfg_.num_max_iterations;
   int iter = 0;
   // Convergence is read back at these rounds only: a peek costs a sync + D2H + relaunch bubble (~35 us), a round that runs
-  // after convergence costs four no-op launches (~18 us), and the loop typically needs 5-7 rounds.
+  // after convergence costs three no-op launches (~18 us), and the loop typically needs 5-7 rounds.
   static const int kPeek[] = {6, 8, 10, 10};
   int peek_i = 0;
   bool done = false;
@@ -730,18 +726,17 @@ void MappingDev::Optimize(bool four_dof) {
     if (peek_i < 4) until = std::min(max_it, kPeek[peek_i]);
     HostSignal sig{};
     for (; iter < until; ++iter) {
-      // the corner (line) and surf (plane) searches of a round are independent: one launch, blockIdx.y picks the branch
-      launch_map_round(fa, stack_all_.p, Mc, d_T, mc.grid.sorted(), mc.grid.cells(), mc.grid.desc(), ms.grid.sorted(), ms.grid.cells(), ms.grid.desc(),
-                       f_valid_.p, f_coef_.p, f_abs_.p, d_conv, s);
-      launch_odom_rows(stack_all_.p, M, M, f_valid_.p, f_coef_.p, d_state_.p, d_partials_.p, nb, s, four_dof ? 2 : 1);
+      // eight lanes per query; no processing order (the stack is one sweep's, a few thousand queries)
+      launch_kf_round(d_kd, d_md, d_st, 1, Mc, Ms, 8, stack_all_.p, nullptr, cfg_.min_match_sq_dis, cfg_.min_plane_dis, mode, f_valid_.p, f_coef_.p, f_abs_.p, s);
+      launch_kf_rows(d_kd, d_st, 1, nb, stack_all_.p, f_valid_.p, f_coef_.p, d_partials_.p, mode, s);
       // the last round before a look at the convergence flag posts the state to the host's mailbox (dev.h: HostSignal)
       if (iter == until - 1) { sig.flag = h_flag_; sig.seq = ++seq_; }
-      launch_odom_update(d_partials_.p, nb, d_state_.p, iter, s, 50, four_dof ? 1 : 0, h_state_, sig);
+      launch_kf_update(d_kd, d_st, 1, d_partials_.p, iter, 50, four_dof ? 1 : 0, nullptr, h_state_, sig, s);
     }
     wait_host_signal(sig, s);   // until > iter: the inner loop ran and its last round posted sig
     if (h_state_->converged) done = true;
   }
-  st = *h_state_;
+  const OdomState st = *h_state_;
   transform_tobe_mapped_.rot = Quat<float>(st.T[3], st.T[0], st.T[1], st.T[2]);
   transform_tobe_mapped_.pos = Vec3<float>(st.T[4], st.T[5], st.T[6]);
   iterations_ = st.iters;

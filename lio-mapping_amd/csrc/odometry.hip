@@ -605,12 +605,6 @@ static void upload(DBuf<float4> &b, const float *src, size_t n, hipStream_t s) {
   b.reserve(std::max<size_t>(n, 1));
   if (n) LIO_HIP(hipMemcpyAsync(b.p, src, n * sizeof(float4), hipMemcpyHostToDevice, s));
 }
-static OdomState state_at(const Rigid<float> &T) {
-  OdomState st{};
-  st.T[0] = T.rot.x; st.T[1] = T.rot.y; st.T[2] = T.rot.z; st.T[3] = T.rot.w;
-  st.T[4] = T.pos.x; st.T[5] = T.pos.y; st.T[6] = T.pos.z;
-  return st;
-}
 
 // What the host keeps of the state the iterations ended with: :654-656 accumulate, :663 normalise.  TransformToEnd (:660-661) runs on the
 // device with the state's own, not normalised transform_es_.
@@ -653,7 +647,7 @@ void OdoChain::TakeClouds(int n, const float *const *sharp, const size_t *n_shar
     take(k, 3, d.less_flat_, less_flat[k], n_lf[k]);
     if (!d.inited_ || !d.enable_odom_) continue;
     OdomState &t = st[size_t(k)];
-    t = state_at(d.transform_es_);
+    t = odom_state_at(d.transform_es_);
     if (on_device) { h_take[size_t(k)].st = d.d_state_.p; h_take[size_t(k)].init = t; }
     else LIO_HIP(hipMemcpyAsync(d.d_state_.p, &t, sizeof(t), hipMemcpyHostToDevice, s));
     if (d.n_last_corner_ > 10 && d.n_last_surf_ > 100) {
@@ -905,7 +899,7 @@ OdoChain &OdometryDev::HookTable(const float *sharp, size_t n_sharp, const float
   upload(last_corner_, last_corner, n_lc, ch.s);
   upload(last_surf_, last_surf, n_lsf, ch.s);
   n_last_corner_ = n_lc; n_last_surf_ = n_lsf;
-  ch.st[0] = state_at(T);
+  ch.st[0] = odom_state_at(T);
   LIO_HIP(hipMemcpyAsync(d_state_.p, &ch.st[0], sizeof(OdomState), hipMemcpyHostToDevice, ch.s));
   ch.act.push_back(0);
   const size_t none = 0;

@@ -1,5 +1,5 @@
 """The Gauss-Newton rows, folds and step the product runs (csrc/cloud_device.h: odom_row_form, fold_partials28_wide, odom_update_from_sums;
-csrc/cloud_kernels.h: reduce_partials28; csrc/odometry.hip: odo_update_step; the production launches launch_odom_rows and launch_odom_round;
+csrc/cloud_kernels.h: reduce_partials28; csrc/odometry.hip: odo_update_step; the production launches launch_kf_rows and launch_odom_round;
 through the test hooks lio_gn_rows_map, lio_gn_fold, lio_gn_step and lio_gn_round) against the references of tests/gn_ref.py on the cases of
 tests/gn_cases.py — the same comparisons and constants the oracle meets in tests/test_gn.py, where the cases' contents and the comparisons'
 sensitivity are tested without a GPU — and against the oracle."""
@@ -19,7 +19,7 @@ STEPS = [n for n in gn_cases.STEP_NAMES if not n.startswith("nan")]
 # ------------------------------------------------------------------------------------------------ rows and their sums
 @pytest.mark.parametrize("name,form", gn_cases.MAP_RUNS, ids=MAP_IDS)
 def test_product_rows_and_sums(hip, name, form):
-    """ONE launch_odom_rows with the production block count: the rows against fp64, the count exactly, every other sum within the bound of
+    """ONE launch_kf_rows (a table of one record) with the production block count: the rows against fp64, the count exactly, every other sum within the bound of
     any fp64 summation order of the fp32 products of the rows"""
     c = gn_cases.get_map(name)
     ok, rows, part = c.run(hip, form)

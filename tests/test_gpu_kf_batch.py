@@ -60,24 +60,68 @@ def test_batch_matches_oracle_vlp16(hip, oracle, four_dof):
     np.testing.assert_array_equal(r1["q"][0], rh["q"][7])
 
 
-def test_batch_equals_single_keyframe_handle(hip, oracle):
-    """The batch stages are the lio_map stages indexed by keyframe: same inputs, same pose as the scan-to-map handle."""
-    from mapping_util import drifting_inputs
-    frames = drifting_inputs(oracle, "indoor", 3)
-    mh = capi.PointMapping(hip)
-    for corner, surf, T_sum, _ in frames[:2]:
-        mh.process(corner, surf, T_sum)
-    mh.set_init_flag(True)                     # keeps transform_tobe_mapped as the start pose, no map update
-    T0 = mh.transform_tobe_mapped()
-    corner, surf, T_sum, _ = frames[2]
-    r = mh.process(corner, surf, T_sum)
-    b = capi.KeyframeBatch(hip)
+def _assert_twin(hip, mh, r, T0, **batch_kw):
+    """the handle's last process against a batch of one keyframe built from the handle's own clouds and start pose: the same bits"""
+    b = capi.KeyframeBatch(hip, **batch_kw)
     b.add_map(mh.cloud(capi.PointMapping.CORNER_FROM_MAP), mh.cloud(capi.PointMapping.SURF_FROM_MAP))
     b.add_keyframe(0, mh.cloud(capi.PointMapping.CORNER_STACK_DS), mh.cloud(capi.PointMapping.SURF_STACK_DS), T0)
     rb = b.refine()
     assert rb["iterations"][0] == r["iterations"] and rb["rows"][0] == r["num_selected"]
     np.testing.assert_array_equal(rb["p"][0], r["T_aft"][1])
     np.testing.assert_array_equal(rb["q"][0], r["T_aft"][0])
+
+
+def test_batch_equals_single_keyframe_handle(hip, oracle):
+    """The scan-to-map handle runs the batch's launch chain on a table of one keyframe (csrc/mapping.hip: Optimize), so the two agree
+    by construction; what this still guards is everything around the chain — the handle's table (grids, stack, start state in one
+    upload), its mailbox peeks at rounds 6, 8 and 10, and the batch's query order, lane split and convergence count.  Three cuts of
+    the stacks: full; no corner point (the corner half of the round launch has no block to run); 3 corner + 20 surf points (fewer
+    than 50 rows every round: the loop runs dry through all three peeks and the start pose comes back untouched)."""
+    from mapping_util import drifting_inputs
+    frames = drifting_inputs(oracle, "indoor", 3)
+    mh = capi.PointMapping(hip)
+    for corner, surf, T_sum, _ in frames[:2]:
+        mh.process(corner, surf, T_sum)
+    mh.set_init_flag(True)                     # keeps transform_tobe_mapped as the start pose, no map update
+    corner, surf, T_sum, _ = frames[2]
+    max_it = mh.cfg.num_max_iterations
+    for name, c, s_ in [("full", corner, surf), ("no corner", corner[:0], surf), ("dry", corner[:3], surf[:20])]:
+        T0 = mh.transform_tobe_mapped()
+        r = mh.process(c, s_, T_sum)
+        print(f"twin {name}: stack {len(mh.cloud(0))} + {len(mh.cloud(1))}, iterations {r['iterations']}, rows {r['num_selected']}")
+        if name == "no corner":
+            assert len(mh.cloud(capi.PointMapping.CORNER_STACK_DS)) == 0 and r["num_selected"] >= 50
+        if name == "dry":
+            # iterations is the count the mailbox carried at the LAST peek (round 10); a loop that never converges passes the peeks at 6 and 8 first
+            assert r["iterations"] == max_it == 10 and r["num_selected"] < 50
+            np.testing.assert_array_equal(r["T_aft"][0], T0[0])
+            np.testing.assert_array_equal(r["T_aft"][1], T0[1])
+        _assert_twin(hip, mh, r, T0)
+
+
+def test_batch_equals_map_builder_handle_4dof(hip, oracle):
+    """The 4-DoF route (MapBuilder::OptimizeMap) against KeyframeBatch(map_builder=1, enable_4d=1).  A MapBuilder handle associates
+    transform_sum with the map at every process, so its start pose is read from a probe: a second handle with an EMPTY map brought to
+    the same (transform_bef_mapped, transform_tobe_mapped), which runs the same association on the same transform_sum and then returns
+    before the optimisation (<= 10 map points: no rounds, no TransformUpdate), leaving the start pose in transform_tobe_mapped."""
+    from mapping_util import drifting_inputs
+    kw = dict(map_builder=1, enable_4d=1, skip_count=1)
+    frames = drifting_inputs(oracle, "indoor", 3)
+    none = np.zeros((0, 4), np.float32)
+    mh, probe = capi.PointMapping(hip, **kw), capi.PointMapping(hip, **kw)
+    for corner, surf, T_sum, _ in frames[:2]:
+        r1 = mh.process(corner, surf, T_sum)
+    assert r1["iterations"] > 0                 # the second sweep was optimised: transform_bef_mapped = its transform_sum (TransformUpdate)
+    probe.process(none, none, frames[1][2])     # first call: transform_bef_mapped = transform_sum of sweep 1
+    probe.set_transform_tobe_mapped(*mh.transform_tobe_mapped())
+    corner, surf, T_sum, _ = frames[2]
+    rp = probe.process(none, none, T_sum)
+    assert rp["iterations"] == 0
+    T0 = probe.transform_tobe_mapped()
+    r = mh.process(corner, surf, T_sum)
+    print(f"twin 4-DoF: iterations {r['iterations']}, rows {r['num_selected']}")
+    assert r["iterations"] > 0 and r["num_selected"] >= 50
+    _assert_twin(hip, mh, r, T0, map_builder=1, enable_4d=1)
 
 
 def test_batch_edge_cases(hip, oracle):
