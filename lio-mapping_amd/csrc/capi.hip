@@ -11,6 +11,7 @@
 #include "../../include/lio_full_cloud.h"
 #include "../../include/lio_odom_batch.h"
 #include "../../include/lio_frontend_batch.h"
+#include "../../include/lio_map_batch.h"
 #include "est_batch.h"
 #include "seg_sort.h"
 #include "estimator.h"
@@ -450,6 +451,33 @@ int lio_map_process(lio_map *h, const float *corner, size_t nc, const float *sur
     if (iters) *iters = h->m->iterations_;
     if (nsel) *nsel = h->m->num_selected_;
     return LIO_OK;
+  });
+}
+// include/lio_map_batch.h.  Every check comes before any device work and before any handle changes.
+int lio_map_process_batch(lio_map *const *handles, int n_sensors, const float *const *corner, const size_t *nc, const float *const *surf, const size_t *ns,
+                          const lio_transform_f *Tsum, lio_transform_f *Taft, int32_t *iters, int32_t *nsel) {
+  if (!handles || n_sensors < 1 || !corner || !nc || !surf || !ns || !Tsum) return LIO_ERR_ARG;
+  if (n_sensors > LIO_MAP_BATCH_MAX_SENSORS) return LIO_ERR_CAPACITY;
+  for (int k = 0; k < n_sensors; ++k)
+    if (!handles[k] || (!corner[k] && nc[k]) || (!surf[k] && ns[k])) return LIO_ERR_ARG;
+  {
+    std::vector<const lio_map *> sorted(handles, handles + n_sensors);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return LIO_ERR_ARG;   // the same handle twice
+  }
+  for (int k = 0; k < n_sensors; ++k)
+    if (handles[k]->borrowed || !handles[k]->m) return LIO_ERR_STATE;   // an estimator's map (lio_est_map) is stepped by its estimator
+  return guarded([&] {
+    std::vector<MappingDev *> m;
+    std::vector<Rigidf> sums;
+    for (int k = 0; k < n_sensors; ++k) { m.push_back(handles[k]->m.get()); sums.push_back(toT(Tsum[k])); }
+    MappingDev::ProcessBatch(m.data(), n_sensors, corner, nc, surf, ns, sums.data());
+    for (int k = 0; k < n_sensors; ++k) {
+      if (Taft) fromT(m[size_t(k)]->transform_aft_mapped_, &Taft[k]);
+      if (iters) iters[k] = m[size_t(k)]->iterations_;
+      if (nsel) nsel[k] = m[size_t(k)]->num_selected_;
+    }
+    return int(LIO_OK);
   });
 }
 int lio_map_get_degeneracy(const lio_map *h, int *kz) {

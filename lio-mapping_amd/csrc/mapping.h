@@ -9,6 +9,7 @@
 // [rest | valid cubes in valid_idx order], so laser_cloud_*_from_map_ is a contiguous tail of the pool; the per-cube
 // VoxelGrid of UpdateMapDatabase is ONE segmented voxel pass with 64-bit (cube rank, voxel) keys.
 #pragma once
+#include <memory>
 #include <vector>
 
 #include "../../include/lio_c.h"
@@ -40,6 +41,8 @@ struct MapCounters { int n_valid, n_rest, n_new_valid, n_new_rest, n_out, pad[3]
 // the keyframe table of one that Optimize runs the scan-to-map chain on (cloud_kernels.h): one record of each kind and the loop's state
 struct KfOne { KfMapDesc md; KfDesc kd; OdomState st; };
 
+struct MapChain;   // mapping.hip: the launch chain of ProcessBatch and its scratch
+
 class MappingDev {
  public:
   static constexpr int L = 21, Wd = 21, H = 11;  // laser_cloud_length_/width_/height_ (PointMapping.cc:79-81)
@@ -50,6 +53,11 @@ class MappingDev {
   MappingDev &operator=(const MappingDev &) = delete;
 
   void Process(const float *corner_last, size_t n_corner, const float *surf_last, size_t n_surf, const Rigid<float> &transform_sum);
+  // include/lio_map_batch.h: Process of n distinct handles, one sweep each, with the phases lined up across the handles and the rounds of all
+  // of them in one launch chain.  Array k of every argument belongs to m[k].  Every handle ends in the state Process alone leaves, bit for
+  // bit.  Returns synchronised.
+  static void ProcessBatch(MappingDev *const *m, int n, const float *const *corner_last, const size_t *n_corner, const float *const *surf_last,
+                           const size_t *n_surf, const Rigid<float> *transform_sum);
   void UpdateMapDatabase(const float *corner_ds, size_t n_corner, const float *surf_ds, size_t n_surf, const uint32_t *valid_idx, size_t n_valid,
                          const Rigid<float> &T, const int cube_center[3]);
   // the same with the stacks where they live (HBM, sensor frame): no cloud crosses PCIe.  producer: the stream that wrote them (the
@@ -86,6 +94,7 @@ class MappingDev {
   int kz_ = 0;   // leading update components masked by round 0's degeneracy test (PointMapping.cc:650-680)
 
  private:
+  friend struct MapChain;
   struct ClassMap {
     DBuf<float4> pool, pool2;       // points in the map frame; pool2 = gather target (swapped in)
     DBuf<uint32_t> pkey, pkey2;     // packed absolute cube key per pool point
@@ -121,6 +130,31 @@ class MappingDev {
   void UpdateFinish(ClassMap &m);
   void Optimize(bool four_dof);
 
+  // ---- the phases of Process.  Process runs them one after the other on its own streams with the waits it has always had; ProcessBatch runs
+  // each phase for every handle before the next one starts, so that a wait is one pass over the handles instead of one stop per handle.
+  struct Step {            // what one Process carries between its phases
+    Rigid<float> T0;       // transform_tobe_mapped_ after the association: the stack's round trip, the window and the FOV test use it
+    MapValidSet vs;
+    size_t cnt[2];
+    bool relayout[2];
+  };
+  void StepBegin(const Rigid<float> &transform_sum, Step &st);           // the call's resets, TransformAssociateToMap / the 4-D one
+  void StepUpload(int c, const float *src, size_t n, Step &st);          // one stack cloud to in; stack_raw sized for its round trip
+  void StepWindow(Step &st);                                             // cube bookkeeping, valid set, surround set, LayoutLaunch where the layout changed
+  void StepLayoutFinish(Step &st);                                       // after a wait for stream_
+  void StepFilterLaunch(const Step &st);                                 // the two VoxelGrids, the surf one on stream2_, joined back into stream_
+  void StepFilterFinish();                                               // waits for the two counts
+  bool StepOptimizes();                                                  // MapBuilder's skip_count: false on a call that only updates the map (and does what that call does)
+  bool OptimizeGate();                                                   // Optimize's first lines: false when the from-map clouds are too small
+  void OptimizeDry();                                                    // ... an empty stack: the loop runs dry, then TransformUpdate
+  void OptimizeEnd(const OdomState &st, int M, bool four_dof);           // ... its last lines: the state the rounds ended with, TransformUpdate
+  bool StepUpdates() const { return cfg_.map_builder != 0 || !imu_inited_; }
+  void StepUpdateLaunch(const Step &st);                                 // UpdateLaunch of both classes
+  void StepUpdateFinish();                                               // after a wait for stream_
+  void StepRegisterFull();                                               // PublishResults on full_cloud_, once per set
+  bool FourDof() const { return cfg_.map_builder != 0 && cfg_.enable_4d != 0; }
+  MapChain &Chain();
+
   lio_map_config cfg_;
   hipStream_t stream_ = nullptr, stream2_ = nullptr;   // stream2_: the surf stack's VoxelGrid beside the corner one
   hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr, ev_full_ = nullptr, ev_full_read_ = nullptr;   // ev_full_: recorded behind the full cloud's registration
@@ -154,6 +188,7 @@ class MappingDev {
   bool full_mapped_ = false;        // this set has been through PublishResults
   bool system_init_ = false;        // MapBuilder.h:65
   int odom_count_ = 0;              // MapBuilder.h:69
+  std::unique_ptr<MapChain> chain_;  // ProcessBatch's scratch when this handle is the first of a call; no results live there
 };
 
 }  // namespace lio

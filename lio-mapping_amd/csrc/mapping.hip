@@ -15,6 +15,7 @@
 #include <cstddef>
 
 #include "mapping.h"
+#include "cloud_device.h"
 
 namespace lio {
 
@@ -220,15 +221,77 @@ __global__ void k_cube_centroids(const float4 *__restrict__ u_pts, const unsigne
 
 // stack round trip of PointMapping::Process (:789-801 then :991-1003): to the map with the predicted transform and
 // back again, in float, exactly as the reference does before it voxel-filters the stack
-__global__ void k_stack_roundtrip(const float4 *__restrict__ in, int n, Quat<float> q, Vec3<float> t, float4 *__restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float4 p = in[i];
+__device__ __forceinline__ float4 stack_roundtrip_point(const float4 p, const Quat<float> &q, const Vec3<float> &t) {
   Vec3<float> m = rotate(q, Vec3<float>(p.x, p.y, p.z));
   m = Vec3<float>(m.x + t.x, m.y + t.y, m.z + t.z);
   Vec3<float> v(m.x - t.x, m.y - t.y, m.z - t.z);
   Vec3<float> r = rotate(conj(q), v);
-  out[i] = make_float4(r.x, r.y, r.z, p.w);
+  return make_float4(r.x, r.y, r.z, p.w);
+}
+__global__ void k_stack_roundtrip(const float4 *__restrict__ in, int n, Quat<float> q, Vec3<float> t, float4 *__restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = stack_roundtrip_point(in[i], q, t);
+}
+
+// ---- the kernels of ProcessBatch (include/lio_map_batch.h) around the keyframe chain of cloud_kernels.h: plain streaming kernels, 256 threads, one
+// float4 per lane, every sensor (or cloud) with its own record of a device table.  A block beyond a record's own points leaves at once.
+// One sensor's stack clouds (0 corner, 1 surf) and the transform_tobe_mapped_ its association left
+struct MbStackRec { const float4 *in[2]; float4 *out[2]; int n[2]; Quat<float> q; Vec3<float> t; };
+// grid (cdiv(max n, 256), 2, sensors): k_stack_roundtrip's body on every sensor's two clouds with the sensor's own T0
+__global__ void __launch_bounds__(256) k_mb_roundtrip(const MbStackRec *__restrict__ recs) {
+  const MbStackRec &r = recs[blockIdx.z];
+  const int c = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= r.n[c]) return;
+  r.out[c][i] = stack_roundtrip_point(r.in[c][i], r.q, r.t);
+}
+// One from-map cloud of an iterating sensor: its bounds blocks (launch_cloud_bounds's count) and its first row of the chain's partials
+struct MbBoundsRec { const float4 *pts; int n; int nb; int off; };
+// grid (max nb, clouds): launch_cloud_bounds of every cloud through the voxel filter's block fold (cloud_device.h).  Minimum and maximum do
+// not hang on the order and the count is an exact float sum, so the VoxParams are launch_cloud_bounds's.
+__global__ void __launch_bounds__(VOX_TILE) k_mb_bounds(const MbBoundsRec *__restrict__ recs, float *__restrict__ partial_all) {
+  const MbBoundsRec r = recs[blockIdx.y];
+  if (int(blockIdx.x) >= r.nb) return;
+  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+  float cnt = 0;
+  for (int i = blockIdx.x * VOX_TILE + threadIdx.x; i < r.n; i += r.nb * VOX_TILE) {
+    const float4 p = r.pts[i];
+    if (!finite3(p)) continue;
+    cnt += 1.f;
+    mn[0] = fminf(mn[0], p.x); mn[1] = fminf(mn[1], p.y); mn[2] = fminf(mn[2], p.z);
+    mx[0] = fmaxf(mx[0], p.x); mx[1] = fmaxf(mx[1], p.y); mx[2] = fmaxf(mx[2], p.z);
+  }
+  vox_block_partial(mn, mx, cnt, partial_all + (size_t(r.off) + blockIdx.x) * 8);
+}
+// one block per cloud
+__global__ void __launch_bounds__(VOX_TILE) k_mb_bounds_fold(const MbBoundsRec *__restrict__ recs, const float *__restrict__ partial_all,
+                                                             VoxParams *__restrict__ out) {
+  const MbBoundsRec r = recs[blockIdx.x];
+  VoxParams v;
+  if (vox_fold_bounds(partial_all + size_t(r.off) * 8, r.nb, 1.0f, v)) out[blockIdx.x] = v;
+}
+// One iterating sensor's slice [slot_off, slot_off + Mc + Ms) of the chain's arrays and where the handle keeps the same: its filtered stacks
+// (taken), and its own stack_all_ / f_coef_ / f_abs_ / f_valid_ (given back)
+struct MbSliceRec { const float4 *stack_ds[2]; int M[2]; int slot_off; float4 *stack_all; float4 *coef; float4 *abs_coef; uint8_t *valid; };
+// grid (cdiv(max M, 256), 2, sensors): the filtered corner stack, then the surf stack, into the chain's stack_all
+__global__ void __launch_bounds__(256) k_mb_take(const MbSliceRec *__restrict__ recs, float4 *__restrict__ stack_all) {
+  const MbSliceRec &r = recs[blockIdx.z];
+  const int c = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= r.M[c]) return;
+  stack_all[r.slot_off + (c ? r.M[0] : 0) + i] = r.stack_ds[c][i];
+}
+// grid (cdiv(max Mc + Ms, 256), 4, sensors): what the last executed round left at the sensor's slots, into the handle (array 0 the stack,
+// 1 coef, 2 abs_coef, 3 the valid bytes)
+__global__ void __launch_bounds__(256) k_mb_give(const MbSliceRec *__restrict__ recs, const float4 *__restrict__ stack_all, const float4 *__restrict__ coef,
+                                                 const float4 *__restrict__ abs_coef, const uint8_t *__restrict__ valid) {
+  const MbSliceRec &r = recs[blockIdx.z];
+  const int a = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= r.M[0] + r.M[1]) return;
+  const int slot = r.slot_off + i;
+  if (a == 0) r.stack_all[i] = stack_all[slot];
+  else if (a == 1) r.coef[i] = coef[slot];
+  else if (a == 2) r.abs_coef[i] = abs_coef[slot];
+  else r.valid[i] = valid[slot];
 }
 
 // Surround map, step 1: the bin of every point of [corner pool | surf pool].  A point of surround cube `slot` (list order) and class
@@ -276,6 +339,38 @@ inline Vec3<double> r2ypr_deg(const Mat3<double> &R) {
 inline Mat3<double> to_double(const Mat3<float> &m) { Mat3<double> r; for (int k = 0; k < 9; ++k) r.m[k] = double(m.m[k]); return r; }
 
 }  // namespace
+
+// ProcessBatch's scratch, kept by the first handle of a call.  No results live here: poses, clouds, maps and the score list's arrays are the
+// handles' own.
+struct MapChain {
+  std::vector<MappingDev::Step> steps;
+  std::vector<MbStackRec> h_stack;
+  DBuf<MbStackRec> d_stack;
+  std::vector<int> act;                 // the handles (indices into the call) whose rounds run: the keyframe table's order
+  std::vector<MbBoundsRec> h_brecs;
+  DBuf<MbBoundsRec> d_brecs;
+  DBuf<float> d_bpartial;
+  DBuf<VoxParams> d_bounds;
+  HostBuf<VoxParams> h_bounds;          // pinned: 2 * nA
+  std::vector<MbSliceRec> h_slices;
+  DBuf<MbSliceRec> d_slices;
+  DBuf<float4> stack_all, coef, abs_coef;
+  DBuf<uint8_t> valid;
+  DBuf<double> partials;
+  HostBuf<char> h_table;                // pinned: nA KfMapDesc, nA KfDesc, nA OdomState, one behind the other; the states come back into it
+  DBuf<char> d_table;
+  DBuf<int> d_nconv;
+  HostBuf<int> h_nconv;
+  hipEvent_t ev = nullptr;              // behind the round trip of the stacks: every handle's filters wait for it
+  MapChain() {
+    LIO_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    d_nconv.reserve(1);
+    h_nconv.alloc(1, hipHostMallocDefault, true);
+  }
+  ~MapChain() { if (ev) (void)hipEventDestroy(ev); }
+  MapChain(const MapChain &) = delete;
+  MapChain &operator=(const MapChain &) = delete;
+};
 
 // ------------------------------------------------------------------------------------------------
 MappingDev::MappingDev(const lio_map_config &cfg) : cfg_(cfg) {
@@ -539,10 +634,45 @@ size_t MappingDev::GetFullCloud(float *out) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// The phases in the order, on the streams and with the waits Process has always had (ProcessBatch below lines them up across handles)
 void MappingDev::Process(const float *corner_last, size_t n_corner, const float *surf_last, size_t n_surf, const Rigid<float> &sum) {
   hipStream_t s = stream_;
   const bool dbg = std::getenv("LIO_DEBUG_TIMING") != nullptr;
   const double tt0 = now_ms();
+  Step st;
+  StepBegin(sum, st);
+  // stack clouds go up while the host does the cube bookkeeping
+  const float *src[2] = {corner_last, surf_last};
+  const size_t cnt[2] = {n_corner, n_surf};
+  for (int c = 0; c < 2; ++c) {
+    StepUpload(c, src[c], cnt[c], st);
+    if (cnt[c])
+      hipLaunchKernelGGL(k_stack_roundtrip, dim3(cdiv(int(cnt[c]), 256)), dim3(256), 0, s, cls_[c].in.p, int(cnt[c]), st.T0.rot, st.T0.pos, cls_[c].stack_raw.p);
+  }
+  StepWindow(st);
+  if (st.relayout[0] || st.relayout[1]) LIO_HIP(hipStreamSynchronize(s));
+  StepLayoutFinish(st);
+
+  const double tt1 = now_ms();
+  StepFilterLaunch(st);
+  StepFilterFinish();
+
+  const double tt2 = now_ms();
+  if (StepOptimizes()) Optimize(FourDof());
+
+  const double tt3 = now_ms();
+  if (StepUpdates()) {
+    StepUpdateLaunch(st);
+    LIO_HIP(hipStreamSynchronize(s));
+    StepUpdateFinish();
+  }
+  StepRegisterFull();
+  if (dbg)
+    std::fprintf(stderr, "[lio_hip map timing] upload+layout %.3f  stack voxel %.3f  optimise %.3f (%d rounds)  map update %.3f  total %.3f ms\n", tt1 - tt0,
+                 tt2 - tt1, tt3 - tt2, iterations_, now_ms() - tt3, now_ms() - tt0);
+}
+
+void MappingDev::StepBegin(const Rigid<float> &sum, Step &st) {
   transform_sum_ = sum;
   score_ready_ = false;
   iterations_ = 0; num_selected_ = 0; degenerate_ = false; kz_ = 0;
@@ -568,18 +698,20 @@ void MappingDev::Process(const float *corner_last, size_t n_corner, const float 
       transform_tobe_mapped_ = full;
     }
   }
-  const Rigid<float> T0 = transform_tobe_mapped_;
-  // stack clouds go up while the host does the cube bookkeeping
-  const float *src[2] = {corner_last, surf_last};
-  const size_t cnt[2] = {n_corner, n_surf};
-  for (int c = 0; c < 2; ++c) {
-    ClassMap &m = cls_[c];
-    m.n_stack = 0;
-    if (!cnt[c]) continue;
-    m.in.reserve(cnt[c]); m.stack_raw.reserve(cnt[c]);
-    LIO_HIP(hipMemcpyAsync(m.in.p, src[c], cnt[c] * sizeof(float4), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_stack_roundtrip, dim3(cdiv(int(cnt[c]), 256)), dim3(256), 0, s, m.in.p, int(cnt[c]), T0.rot, T0.pos, m.stack_raw.p);
-  }
+  st.T0 = transform_tobe_mapped_;
+}
+
+void MappingDev::StepUpload(int c, const float *src, size_t n, Step &st) {
+  ClassMap &m = cls_[c];
+  m.n_stack = 0;
+  st.cnt[c] = n;
+  if (!n) return;
+  m.in.reserve(n); m.stack_raw.reserve(n);
+  LIO_HIP(hipMemcpyAsync(m.in.p, src, n * sizeof(float4), hipMemcpyHostToDevice, stream_));
+}
+
+void MappingDev::StepWindow(Step &st) {
+  const Rigid<float> &T0 = st.T0;
   point_on_z_axis(T0, pz_);
   // sensor cube and window shift (:808-925); absolute keys make the shift a change of cen_ only
   const float posv[3] = {T0.pos.x, T0.pos.y, T0.pos.z};
@@ -615,71 +747,99 @@ void MappingDev::Process(const float *corner_last, size_t n_corner, const float 
         if (fov) valid_idx_.push_back(uint32_t(i + L * j + L * Wd * k));
         surround_idx_.push_back(uint32_t(i + L * j + L * Wd * k));   // :984
       }
-  const MapValidSet vs = MakeValidSet(valid_idx_.data(), valid_idx_.size(), cen_);
+  st.vs = MakeValidSet(valid_idx_.data(), valid_idx_.size(), cen_);
 
   // laser_cloud_*_from_map_ = tail of the pool after the layout pass
-  bool relayout[2];
   for (int c = 0; c < 2; ++c) {
-    relayout[c] = !LayoutMatches(cls_[c], vs);
-    if (relayout[c]) LayoutLaunch(cls_[c], vs);
+    st.relayout[c] = !LayoutMatches(cls_[c], st.vs);
+    if (st.relayout[c]) LayoutLaunch(cls_[c], st.vs);
   }
-  if (relayout[0] || relayout[1]) LIO_HIP(hipStreamSynchronize(s));
-  for (int c = 0; c < 2; ++c) if (relayout[c]) LayoutFinish(cls_[c], vs);
+}
 
-  const double tt1 = now_ms();
-  // VoxelGrid of the stacks (:1005-1015)
+void MappingDev::StepLayoutFinish(Step &st) {
+  for (int c = 0; c < 2; ++c) if (st.relayout[c]) LayoutFinish(cls_[c], st.vs);
+}
+
+// VoxelGrid of the stacks (:1005-1015)
+void MappingDev::StepFilterLaunch(const Step &st) {
+  hipStream_t s = stream_;
   const float leaf[2] = {cfg_.corner_filter_size, cfg_.surf_filter_size};
-  // the two filters are independent: the surf one goes to a second stream, forked after the round-trip kernels above
+  // the two filters are independent: the surf one goes to a second stream, forked after the round trip of the stacks
   LIO_HIP(hipEventRecord(ev_fork_, s));
   LIO_HIP(hipStreamWaitEvent(stream2_, ev_fork_, 0));
   hipStream_t vs_stream[2] = {s, stream2_};
-  for (int c = 0; c < 2; ++c) cls_[c].vox.launch(cls_[c].stack_raw.p, cnt[c], leaf[c], cls_[c].stack_ds, vs_stream[c]);
+  for (int c = 0; c < 2; ++c) cls_[c].vox.launch(cls_[c].stack_raw.p, st.cnt[c], leaf[c], cls_[c].stack_ds, vs_stream[c]);
   // finish() only waits for the output COUNT (posted to the host's mailbox); the consumers on `s` wait for the surf filter's
   // stream through an event
   LIO_HIP(hipEventRecord(ev_join_, stream2_));
   LIO_HIP(hipStreamWaitEvent(s, ev_join_, 0));
+}
+void MappingDev::StepFilterFinish() {
   for (int c = 0; c < 2; ++c) cls_[c].n_stack = cls_[c].vox.finish();
+}
 
-  const double tt2 = now_ms();
-  if (builder) {  // MapBuilder.cc:527-558: optimise every skip_count-th call, always update the map
-    if (odom_count_ % cfg_.skip_count == 0) Optimize(cfg_.enable_4d != 0);
-    else {
-      n_from_map_[0] = cls_[0].n_valid; n_from_map_[1] = cls_[1].n_valid; from_map_in_u_ = false;
-      transform_bef_mapped_ = transform_sum_; transform_aft_mapped_ = transform_tobe_mapped_;
-    }
-    ++odom_count_;
-  } else {
-    Optimize(false);
+// MapBuilder.cc:527-558: optimise every skip_count-th call, always update the map
+bool MappingDev::StepOptimizes() {
+  if (!cfg_.map_builder) return true;
+  const bool optimise = odom_count_ % cfg_.skip_count == 0;
+  if (!optimise) {
+    n_from_map_[0] = cls_[0].n_valid; n_from_map_[1] = cls_[1].n_valid; from_map_in_u_ = false;
+    transform_bef_mapped_ = transform_sum_; transform_aft_mapped_ = transform_tobe_mapped_;
   }
+  ++odom_count_;
+  return optimise;
+}
 
-  const double tt3 = now_ms();
-  if (builder || !imu_inited_) {
-    for (int c = 0; c < 2; ++c) UpdateLaunch(cls_[c], cls_[c].stack_ds.p, cls_[c].n_stack, vs, transform_tobe_mapped_, leaf[c]);
-    LIO_HIP(hipStreamSynchronize(s));
-    for (int c = 0; c < 2; ++c) UpdateFinish(cls_[c]);
-    from_map_in_u_ = true;
-  }
-  if (!imu_inited_ && n_full_ && !full_mapped_) {   // PublishResults (:1105 -> :1244-1248): PointAssociateToMap on full_cloud_, in place
-    const Rigid<float> &T = transform_tobe_mapped_;
-    const float q[4] = {T.rot.x, T.rot.y, T.rot.z, T.rot.w}, p[3] = {T.pos.x, T.pos.y, T.pos.z};
-    std::swap(full_, full_in_);
-    full_.reserve(n_full_);
-    if (full_read_) LIO_HIP(hipStreamWaitEvent(s, ev_full_read_, 0));
-    launch_rigid_map(full_in_.p, int(n_full_), q, p, full_.p, s);
-    LIO_HIP(hipEventRecord(ev_full_, s));
-    full_mapped_ = true; full_event_ = true;
-  }
-  if (dbg)
-    std::fprintf(stderr, "[lio_hip map timing] upload+layout %.3f  stack voxel %.3f  optimise %.3f (%d rounds)  map update %.3f  total %.3f ms\n", tt1 - tt0,
-                 tt2 - tt1, tt3 - tt2, iterations_, now_ms() - tt3, now_ms() - tt0);
+void MappingDev::StepUpdateLaunch(const Step &st) {
+  const float leaf[2] = {cfg_.corner_filter_size, cfg_.surf_filter_size};
+  for (int c = 0; c < 2; ++c) UpdateLaunch(cls_[c], cls_[c].stack_ds.p, cls_[c].n_stack, st.vs, transform_tobe_mapped_, leaf[c]);
+}
+void MappingDev::StepUpdateFinish() {
+  for (int c = 0; c < 2; ++c) UpdateFinish(cls_[c]);
+  from_map_in_u_ = true;
+}
+// PublishResults (:1105 -> :1244-1248): PointAssociateToMap on full_cloud_, in place
+void MappingDev::StepRegisterFull() {
+  if (imu_inited_ || !n_full_ || full_mapped_) return;
+  hipStream_t s = stream_;
+  const Rigid<float> &T = transform_tobe_mapped_;
+  const float q[4] = {T.rot.x, T.rot.y, T.rot.z, T.rot.w}, p[3] = {T.pos.x, T.pos.y, T.pos.z};
+  std::swap(full_, full_in_);
+  full_.reserve(n_full_);
+  if (full_read_) LIO_HIP(hipStreamWaitEvent(s, ev_full_read_, 0));
+  launch_rigid_map(full_in_.p, int(n_full_), q, p, full_.p, s);
+  LIO_HIP(hipEventRecord(ev_full_, s));
+  full_mapped_ = true; full_event_ = true;
+}
+
+bool MappingDev::OptimizeGate() {
+  n_from_map_[0] = cls_[0].n_valid; n_from_map_[1] = cls_[1].n_valid;
+  from_map_in_u_ = false;
+  return cls_[0].n_valid > 10 && cls_[1].n_valid > 100;  // :327-329 (no TransformUpdate either)
+}
+// every round has < 50 rows: the loop runs dry, then TransformUpdate
+void MappingDev::OptimizeDry() {
+  iterations_ = cfg_.num_max_iterations;
+  transform_bef_mapped_ = transform_sum_; transform_aft_mapped_ = transform_tobe_mapped_;
+}
+// the state the rounds ended with; M: the slots the score list's arrays hold
+void MappingDev::OptimizeEnd(const OdomState &st, int M, bool four_dof) {
+  transform_tobe_mapped_.rot = Quat<float>(st.T[3], st.T[0], st.T[1], st.T[2]);
+  transform_tobe_mapped_.pos = Vec3<float>(st.T[4], st.T[5], st.T[6]);
+  iterations_ = st.iters;
+  num_selected_ = st.nsel;
+  degenerate_ = st.degenerate != 0;
+  kz_ = degenerate_ ? st.kz : 0;
+  transform_bef_mapped_ = transform_sum_;            // TransformUpdate (:760-763)
+  transform_aft_mapped_ = transform_tobe_mapped_;
+  n_score_slots_ = size_t(M);
+  score_ready_ = !four_dof;  // OptimizeMap keeps no score list
 }
 
 void MappingDev::Optimize(bool four_dof) {
   hipStream_t s = stream_;
   ClassMap &mc = cls_[0], &ms = cls_[1];
-  n_from_map_[0] = mc.n_valid; n_from_map_[1] = ms.n_valid;
-  from_map_in_u_ = false;
-  if (mc.n_valid <= 10 || ms.n_valid <= 100) return;  // :327-329 (no TransformUpdate either)
+  if (!OptimizeGate()) return;
   // search grids over the two from-map clouds
   ClassMap *cm[2] = {&mc, &ms};
   for (ClassMap *m : cm) {
@@ -691,11 +851,7 @@ void MappingDev::Optimize(bool four_dof) {
   for (ClassMap *m : cm) m->grid.build(m->pool.p + m->n_rest, m->n_valid, m->h_bounds.p->mn, m->h_bounds.p->mx, cell, s);
 
   const int Mc = int(mc.n_stack), Ms = int(ms.n_stack), M = Mc + Ms;
-  if (M == 0) {  // every round has < 50 rows: the loop runs dry, then TransformUpdate
-    iterations_ = cfg_.num_max_iterations;
-    transform_bef_mapped_ = transform_sum_; transform_aft_mapped_ = transform_tobe_mapped_;
-    return;
-  }
+  if (M == 0) { OptimizeDry(); return; }
   stack_all_.reserve(size_t(M)); f_valid_.reserve(size_t(M)); f_coef_.reserve(size_t(M)); f_abs_.reserve(size_t(M));
   if (Mc) LIO_HIP(hipMemcpyAsync(stack_all_.p, mc.stack_ds.p, size_t(Mc) * sizeof(float4), hipMemcpyDeviceToDevice, s));
   if (Ms) LIO_HIP(hipMemcpyAsync(stack_all_.p + Mc, ms.stack_ds.p, size_t(Ms) * sizeof(float4), hipMemcpyDeviceToDevice, s));
@@ -736,17 +892,215 @@ void MappingDev::Optimize(bool four_dof) {
     wait_host_signal(sig, s);   // until > iter: the inner loop ran and its last round posted sig
     if (h_state_->converged) done = true;
   }
-  const OdomState st = *h_state_;
-  transform_tobe_mapped_.rot = Quat<float>(st.T[3], st.T[0], st.T[1], st.T[2]);
-  transform_tobe_mapped_.pos = Vec3<float>(st.T[4], st.T[5], st.T[6]);
-  iterations_ = st.iters;
-  num_selected_ = st.nsel;
-  degenerate_ = st.degenerate != 0;
-  kz_ = degenerate_ ? st.kz : 0;
-  transform_bef_mapped_ = transform_sum_;            // TransformUpdate (:760-763)
-  transform_aft_mapped_ = transform_tobe_mapped_;
-  n_score_slots_ = size_t(M);
-  score_ready_ = !four_dof;  // OptimizeMap keeps no score list
+  OptimizeEnd(*h_state_, M, four_dof);
+}
+
+MapChain &MappingDev::Chain() {
+  if (!chain_) chain_.reset(new MapChain);
+  return *chain_;
+}
+
+// ------------------------------------------------------------------------------------------------
+// include/lio_map_batch.h.  Every phase runs for all handles before the next one starts; the work of a handle stays on its own streams but
+// for the launches that serve every sensor at once (the stacks' round trip, the from-map bounds, the rounds and what goes around them),
+// which run on m[0]'s stream.  Every handle is idle when the call starts (each lio_map_* call returns synchronised).
+void MappingDev::ProcessBatch(MappingDev *const *m, int n, const float *const *corner_last, const size_t *n_corner, const float *const *surf_last,
+                              const size_t *n_surf, const Rigid<float> *sums) {
+  // the round launches carry these as launch parameters: without common values there is no common chain
+  bool common = true;
+  for (int k = 1; k < n; ++k) {
+    const lio_map_config &a = m[0]->cfg_, &b = m[k]->cfg_;
+    common = common && a.min_match_sq_dis == b.min_match_sq_dis && a.min_plane_dis == b.min_plane_dis && a.num_max_iterations == b.num_max_iterations &&
+             m[0]->FourDof() == m[k]->FourDof();
+  }
+  if (!common) {
+    for (int k = 0; k < n; ++k) {
+      m[k]->Process(corner_last[k], n_corner[k], surf_last[k], n_surf[k], sums[k]);
+      m[k]->Sync();
+    }
+    return;
+  }
+  for (int k = 0; k < n; ++k)
+    if (n_corner[k] > size_t(INT_MAX) - 255 || n_surf[k] > size_t(INT_MAX) - 255) throw CapacityError("lio_map_process_batch: a cloud exceeds 2^31 points");
+  MapChain &ch = m[0]->Chain();
+  hipStream_t s0 = m[0]->stream_;
+  const lio_map_config &cfg = m[0]->cfg_;
+  const bool four_dof = m[0]->FourDof();
+
+  // ---- 1. prepare: association, uploads, cube bookkeeping and the layout pass per handle, no wait in between; one launch for every round trip
+  ch.steps.assign(size_t(n), Step());
+  ch.h_stack.assign(size_t(n), MbStackRec());
+  size_t max_in = 0;
+  for (int k = 0; k < n; ++k) {
+    MappingDev &d = *m[k];
+    Step &st = ch.steps[size_t(k)];
+    d.StepBegin(sums[k], st);
+    d.StepUpload(0, corner_last[k], n_corner[k], st);
+    d.StepUpload(1, surf_last[k], n_surf[k], st);
+    if (k && (n_corner[k] || n_surf[k])) {   // the round trip on s0 reads what this stream uploads
+      LIO_HIP(hipEventRecord(d.ev_join_, d.stream_));
+      LIO_HIP(hipStreamWaitEvent(s0, d.ev_join_, 0));
+    }
+    MbStackRec &r = ch.h_stack[size_t(k)];
+    for (int c = 0; c < 2; ++c) {
+      r.in[c] = d.cls_[c].in.p; r.out[c] = d.cls_[c].stack_raw.p; r.n[c] = int(st.cnt[c]);
+      max_in = std::max(max_in, st.cnt[c]);
+    }
+    r.q = st.T0.rot; r.t = st.T0.pos;
+    d.StepWindow(st);
+  }
+  if (max_in) {
+    ch.d_stack.reserve(size_t(n));
+    LIO_HIP(hipMemcpyAsync(ch.d_stack.p, ch.h_stack.data(), size_t(n) * sizeof(MbStackRec), hipMemcpyHostToDevice, s0));
+    hipLaunchKernelGGL(k_mb_roundtrip, dim3(cdiv(max_in, 256), 2, n), dim3(256), 0, s0, ch.d_stack.p);
+    LIO_HIP(hipGetLastError());
+    LIO_HIP(hipEventRecord(ch.ev, s0));
+  }
+  for (int k = 0; k < n; ++k) {   // one pass of waits over the handles that re-laid out
+    MappingDev &d = *m[k];
+    Step &st = ch.steps[size_t(k)];
+    if (st.relayout[0] || st.relayout[1]) LIO_HIP(hipStreamSynchronize(d.stream_));
+    d.StepLayoutFinish(st);
+  }
+
+  // ---- 2. filter: every handle's two VoxelGrids in flight before the first count is waited for
+  for (int k = 0; k < n; ++k) {
+    MappingDev &d = *m[k];
+    if (k && max_in) LIO_HIP(hipStreamWaitEvent(d.stream_, ch.ev, 0));
+    d.StepFilterLaunch(ch.steps[size_t(k)]);
+  }
+  for (int k = 0; k < n; ++k) m[k]->StepFilterFinish();
+
+  // ---- 3. who iterates; the bounds of their from-map clouds in two launches, one copy back, one wait; their grids on their own streams
+  ch.act.clear();
+  for (int k = 0; k < n; ++k) {
+    MappingDev &d = *m[k];
+    if (!d.StepOptimizes() || !d.OptimizeGate()) continue;   // a skipped MapBuilder call; from-map clouds too small (:327-329)
+    if (d.cls_[0].n_stack + d.cls_[1].n_stack == 0) { d.OptimizeDry(); continue; }
+    ch.act.push_back(k);
+  }
+  const int na = int(ch.act.size());
+  if (na) {
+    ch.h_brecs.assign(size_t(2 * na), MbBoundsRec());
+    size_t bpart_total = 0;
+    int max_bnb = 0;
+    for (int j = 0; j < na; ++j) {
+      MappingDev &d = *m[ch.act[size_t(j)]];
+      for (int c = 0; c < 2; ++c) {
+        const ClassMap &cm = d.cls_[c];
+        if (cm.n_valid > size_t(INT_MAX) - 255) throw CapacityError("lio_map_process_batch: a from-map cloud exceeds 2^31 points");
+        MbBoundsRec &r = ch.h_brecs[size_t(2 * j + c)];
+        r.pts = cm.pool.p + cm.n_rest; r.n = int(cm.n_valid);
+        r.nb = std::max(1, std::min(cdiv(r.n, 256), 512));   // (launch_cloud_bounds)
+        r.off = int(bpart_total);
+        bpart_total += size_t(r.nb);
+        max_bnb = std::max(max_bnb, r.nb);
+      }
+    }
+    ch.d_brecs.reserve(size_t(2 * na)); ch.d_bpartial.reserve(bpart_total * 8); ch.d_bounds.reserve(size_t(2 * na));
+    if (ch.h_bounds.n < size_t(2 * na)) ch.h_bounds.alloc(size_t(2 * na) + size_t(na), hipHostMallocDefault);
+    LIO_HIP(hipMemcpyAsync(ch.d_brecs.p, ch.h_brecs.data(), size_t(2 * na) * sizeof(MbBoundsRec), hipMemcpyHostToDevice, s0));
+    hipLaunchKernelGGL(k_mb_bounds, dim3(max_bnb, 2 * na), dim3(VOX_TILE), 0, s0, ch.d_brecs.p, ch.d_bpartial.p);
+    hipLaunchKernelGGL(k_mb_bounds_fold, dim3(2 * na), dim3(VOX_TILE), 0, s0, ch.d_brecs.p, ch.d_bpartial.p, ch.d_bounds.p);
+    LIO_HIP(hipGetLastError());
+    LIO_HIP(hipMemcpyAsync(ch.h_bounds.p, ch.d_bounds.p, size_t(2 * na) * sizeof(VoxParams), hipMemcpyDeviceToHost, s0));
+    LIO_HIP(hipStreamSynchronize(s0));
+    const float cell = scan_to_map_cell_edge(cfg.min_match_sq_dis);
+    for (int j = 0; j < na; ++j) {
+      MappingDev &d = *m[ch.act[size_t(j)]];
+      for (int c = 0; c < 2; ++c) {
+        ClassMap &cm = d.cls_[c];
+        const VoxParams &b = ch.h_bounds.p[2 * j + c];
+        cm.grid.build(cm.pool.p + cm.n_rest, cm.n_valid, b.mn, b.mx, cell, d.stream_);
+      }
+    }
+
+    // ---- 4. the rounds: the keyframe chain of cloud_kernels.h on a table of nA, on s0 behind every other iterating handle's stream
+    ch.h_slices.assign(size_t(na), MbSliceRec());
+    size_t slots = 0, part_total = 0;
+    int max_Mc = 0, max_Ms = 0, max_nb = 0;
+    const size_t off_kd = size_t(na) * sizeof(KfMapDesc), off_st = off_kd + ((size_t(na) * sizeof(KfDesc) + 7) & ~size_t(7));
+    const size_t table_bytes = off_st + size_t(na) * sizeof(OdomState);
+    if (ch.h_table.n < table_bytes) ch.h_table.alloc(table_bytes + table_bytes / 2, hipHostMallocDefault);
+    ch.d_table.reserve(table_bytes);
+    KfMapDesc *h_md = reinterpret_cast<KfMapDesc *>(ch.h_table.p);
+    KfDesc *h_kd = reinterpret_cast<KfDesc *>(ch.h_table.p + off_kd);
+    OdomState *h_st = reinterpret_cast<OdomState *>(ch.h_table.p + off_st);
+    for (int j = 0; j < na; ++j) {
+      MappingDev &d = *m[ch.act[size_t(j)]];
+      ClassMap &mc = d.cls_[0], &ms = d.cls_[1];
+      if (mc.n_stack + ms.n_stack + slots > size_t(INT_MAX) - 255) throw CapacityError("lio_map_process_batch: the filtered stacks exceed 2^31 points");
+      const int Mc = int(mc.n_stack), Ms = int(ms.n_stack), M = Mc + Ms;
+      const int nb = odom_rows_blocks(M);
+      h_md[j] = KfMapDesc{mc.grid.sorted(), mc.grid.cells(), mc.grid.desc(), ms.grid.sorted(), ms.grid.cells(), ms.grid.desc()};
+      h_kd[j] = KfDesc{int(slots), Mc, Ms, j, nb, int(part_total), {d.pz_[0], d.pz_[1], d.pz_[2]}};
+      h_st[j] = odom_state_at(d.transform_tobe_mapped_);
+      d.stack_all_.reserve(size_t(M)); d.f_valid_.reserve(size_t(M)); d.f_coef_.reserve(size_t(M)); d.f_abs_.reserve(size_t(M));
+      MbSliceRec &r = ch.h_slices[size_t(j)];
+      r.stack_ds[0] = mc.stack_ds.p; r.stack_ds[1] = ms.stack_ds.p; r.M[0] = Mc; r.M[1] = Ms; r.slot_off = int(slots);
+      r.stack_all = d.stack_all_.p; r.coef = d.f_coef_.p; r.abs_coef = d.f_abs_.p; r.valid = d.f_valid_.p;
+      slots += size_t(M); part_total += size_t(nb);
+      max_Mc = std::max(max_Mc, Mc); max_Ms = std::max(max_Ms, Ms); max_nb = std::max(max_nb, nb);
+      if (ch.act[size_t(j)]) {   // its filters (the surf one joined in) and its grids
+        LIO_HIP(hipEventRecord(d.ev_join_, d.stream_));
+        LIO_HIP(hipStreamWaitEvent(s0, d.ev_join_, 0));
+      }
+    }
+    ch.stack_all.reserve(slots); ch.valid.reserve(slots); ch.coef.reserve(slots); ch.abs_coef.reserve(slots);
+    ch.partials.reserve(part_total * 28);
+    ch.d_slices.reserve(size_t(na));
+    LIO_HIP(hipMemcpyAsync(ch.d_slices.p, ch.h_slices.data(), size_t(na) * sizeof(MbSliceRec), hipMemcpyHostToDevice, s0));
+    LIO_HIP(hipMemcpyAsync(ch.d_table.p, ch.h_table.p, table_bytes, hipMemcpyHostToDevice, s0));
+    LIO_HIP(hipMemsetAsync(ch.d_nconv.p, 0, sizeof(int), s0));
+    const int max_M = std::max(max_Mc, max_Ms);   // (> 0: every sensor of the table has a stack)
+    hipLaunchKernelGGL(k_mb_take, dim3(cdiv(max_M, 256), 2, na), dim3(256), 0, s0, ch.d_slices.p, ch.stack_all.p);
+    LIO_HIP(hipGetLastError());
+    const KfMapDesc *d_md = reinterpret_cast<const KfMapDesc *>(ch.d_table.p);
+    const KfDesc *d_kd = reinterpret_cast<const KfDesc *>(ch.d_table.p + off_kd);
+    OdomState *d_st = reinterpret_cast<OdomState *>(ch.d_table.p + off_st);
+    const int mode = four_dof ? 2 : 1;
+    const int max_it = cfg.num_max_iterations;
+    // the looks at the convergence counter come where Optimize has them; a sensor that has converged stays frozen (its blocks leave at once)
+    static const int kPeek[] = {6, 8, 10};
+    int iter = 0, peek_i = 0;
+    while (iter < max_it) {
+      int until = max_it;
+      while (peek_i < 3 && kPeek[peek_i] <= iter) ++peek_i;
+      if (peek_i < 3) until = std::min(max_it, kPeek[peek_i]);
+      for (; iter < until; ++iter) {
+        // eight lanes per query; no processing order (every stack is one sweep's, a few thousand queries)
+        launch_kf_round(d_kd, d_md, d_st, na, max_Mc, max_Ms, 8, ch.stack_all.p, nullptr, cfg.min_match_sq_dis, cfg.min_plane_dis, mode, ch.valid.p, ch.coef.p,
+                        ch.abs_coef.p, s0);
+        launch_kf_rows(d_kd, d_st, na, max_nb, ch.stack_all.p, ch.valid.p, ch.coef.p, ch.partials.p, mode, s0);
+        launch_kf_update(d_kd, d_st, na, ch.partials.p, iter, 50, four_dof ? 1 : 0, ch.d_nconv.p, nullptr, HostSignal(), s0);
+      }
+      if (iter >= max_it) break;
+      LIO_HIP(hipMemcpyAsync(ch.h_nconv.p, ch.d_nconv.p, sizeof(int), hipMemcpyDeviceToHost, s0));
+      LIO_HIP(hipStreamSynchronize(s0));
+      if (*ch.h_nconv.p >= na) break;
+    }
+    // ---- 5. give back: every sensor's slice of the chain's arrays into its handle, the states in one copy, one wait
+    hipLaunchKernelGGL(k_mb_give, dim3(cdiv(max_Mc + max_Ms, 256), 4, na), dim3(256), 0, s0, ch.d_slices.p, ch.stack_all.p, ch.coef.p, ch.abs_coef.p, ch.valid.p);
+    LIO_HIP(hipGetLastError());
+    LIO_HIP(hipMemcpyAsync(h_st, d_st, size_t(na) * sizeof(OdomState), hipMemcpyDeviceToHost, s0));
+    LIO_HIP(hipStreamSynchronize(s0));
+    for (int j = 0; j < na; ++j) {
+      MappingDev &d = *m[ch.act[size_t(j)]];
+      d.OptimizeEnd(h_st[j], int(d.cls_[0].n_stack + d.cls_[1].n_stack), four_dof);
+    }
+  }
+  // the map update and the full cloud's registration per handle on its own stream (the chain has been waited for: the poses are on the
+  // host), then one pass of waits
+  for (int k = 0; k < n; ++k) {
+    MappingDev &d = *m[k];
+    if (d.StepUpdates()) d.StepUpdateLaunch(ch.steps[size_t(k)]);
+    d.StepRegisterFull();
+  }
+  for (int k = 0; k < n; ++k) {
+    MappingDev &d = *m[k];
+    LIO_HIP(hipStreamSynchronize(d.stream_));
+    if (d.StepUpdates()) d.StepUpdateFinish();
+  }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -316,6 +316,12 @@ _FRONTEND_SIGS = {
     "lio_odom_process_batch_from_pp": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.POINTER(TransformF), C.POINTER(TransformF),
                                                  c_int32_p, c_int32_p]),
 }
+# include/lio_map_batch.h: the scan-to-map step of many sensors through one launch chain (the product only, attached like _EXT_SIGS)
+_MAP_BATCH_SIGS = {
+    "lio_map_process_batch": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, _c_float_pp, _c_size_p, _c_float_pp, _c_size_p, C.POINTER(TransformF),
+                                        C.POINTER(TransformF), c_int32_p, c_int32_p]),
+}
+MAP_BATCH_MAX_SENSORS = 1024   # LIO_MAP_BATCH_MAX_SENSORS
 
 
 def _dp(a):
@@ -366,7 +372,8 @@ class LioLib:
         self.backend = self.dll.lio_backend().decode()
         self.has_ext = self.backend.startswith("hip")
         if self.has_ext:
-            for name, (res, args) in list(_EXT_SIGS.items()) + list(_FULL_SIGS.items()) + list(_ODOM_BATCH_SIGS.items()) + list(_FRONTEND_SIGS.items()):
+            for name, (res, args) in (list(_EXT_SIGS.items()) + list(_FULL_SIGS.items()) + list(_ODOM_BATCH_SIGS.items()) + list(_FRONTEND_SIGS.items())
+                                      + list(_MAP_BATCH_SIGS.items())):
                 fn = getattr(self.dll, name)
                 fn.restype = res
                 fn.argtypes = args
@@ -846,6 +853,30 @@ class PointMapping:
         kz = C.c_int(0)
         deg = self.lib.dll.lio_map_get_degeneracy(self.h, C.byref(kz))
         return dict(T_aft=Ta.to_np(), iterations=it.value, num_selected=ns.value, degenerate=int(deg), kz=kz.value)
+
+    @staticmethod
+    def process_batch(handles, inputs):
+        """lio_map_process_batch (include/lio_map_batch.h): one sweep of every PointMapping of `handles` with the rounds of all of them in
+        one launch chain; inputs[k] = (corner_last, surf_last, T_sum) of sensor k.  -> list of the dicts process() returns."""
+        n = len(handles)
+        if n < 1 or len(inputs) != n:
+            raise LioError("process_batch: one (corner_last, surf_last, T_sum) per handle, at least one handle")
+        lib = handles[0].lib
+        cl = [[_f32(c).reshape(-1, 4) for c in inp[:2]] for inp in inputs]   # (kept alive until the call returns)
+        H = (C.c_void_p * n)(*[h.h for h in handles])
+        args = []
+        for w in range(2):
+            args += [(c_float_p * n)(*[_fp(cl[k][w]) for k in range(n)]), (C.c_size_t * n)(*[cl[k][w].shape[0] for k in range(n)])]
+        Ts = (TransformF * n)(*[TransformF.make(*inp[2]) for inp in inputs])
+        Ta = (TransformF * n)()
+        it, ns = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        _chk(lib.dll.lio_map_process_batch(H, n, *args, Ts, Ta, it.ctypes.data_as(c_int32_p), ns.ctypes.data_as(c_int32_p)), "lio_map_process_batch")
+        out = []
+        for k, h in enumerate(handles):
+            kz = C.c_int(0)
+            deg = lib.dll.lio_map_get_degeneracy(h.h, C.byref(kz))
+            out.append(dict(T_aft=Ta[k].to_np(), iterations=int(it[k]), num_selected=int(ns[k]), degenerate=int(deg), kz=kz.value))
+        return out
 
     def set_init_flag(self, on):
         _chk(self.lib.dll.lio_map_set_init_flag(self.h, 1 if on else 0), "lio_map_set_init_flag")
