@@ -442,14 +442,18 @@ void lio_map_destroy(lio_map *h) {
   if (h && h->borrowed) { std::fprintf(stderr, "[lio_hip] lio_map_destroy: the handle belongs to a lio_est (lio_est_map); ignored\n"); return; }
   delete h;
 }
+// what lio_map_process and lio_map_process_batch answer for one handle after its step; each pointer may be null
+static void map_step_results(const MappingDev &m, lio_transform_f *Taft, int32_t *iters, int32_t *nsel) {
+  if (Taft) fromT(m.transform_aft_mapped_, Taft);
+  if (iters) *iters = m.iterations_;
+  if (nsel) *nsel = m.num_selected_;
+}
 int lio_map_process(lio_map *h, const float *corner, size_t nc, const float *surf, size_t ns, const lio_transform_f *Tsum, lio_transform_f *Taft,
                     int *iters, int *nsel) {
   if (!h || !Tsum || (!corner && nc) || (!surf && ns)) return LIO_ERR_ARG;
   return guarded([&] {
     h->m->Process(corner, nc, surf, ns, toT(*Tsum));
-    if (Taft) fromT(h->m->transform_aft_mapped_, Taft);
-    if (iters) *iters = h->m->iterations_;
-    if (nsel) *nsel = h->m->num_selected_;
+    map_step_results(*h->m, Taft, iters, nsel);
     return LIO_OK;
   });
 }
@@ -472,11 +476,7 @@ int lio_map_process_batch(lio_map *const *handles, int n_sensors, const float *c
     std::vector<Rigidf> sums;
     for (int k = 0; k < n_sensors; ++k) { m.push_back(handles[k]->m.get()); sums.push_back(toT(Tsum[k])); }
     MappingDev::ProcessBatch(m.data(), n_sensors, corner, nc, surf, ns, sums.data());
-    for (int k = 0; k < n_sensors; ++k) {
-      if (Taft) fromT(m[size_t(k)]->transform_aft_mapped_, &Taft[k]);
-      if (iters) iters[k] = m[size_t(k)]->iterations_;
-      if (nsel) nsel[k] = m[size_t(k)]->num_selected_;
-    }
+    for (int k = 0; k < n_sensors; ++k) map_step_results(*m[size_t(k)], Taft ? Taft + k : nullptr, iters ? iters + k : nullptr, nsel ? nsel + k : nullptr);
     return int(LIO_OK);
   });
 }

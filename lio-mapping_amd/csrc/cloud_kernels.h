@@ -211,7 +211,8 @@ void launch_gn_fold(const double *partials, int nblocks, int wide, double *sums_
 void launch_gn_step(const double *sums, OdomState *st, int iter, int min_rows, int left_update, hipStream_t s);
 
 // ---- the scan-to-map Gauss-Newton loop (OptimizeMap / OptimizeTransformTobeMapped, MapBuilder.cc:624-1014, PointMapping.cc:325-753) for a
-// table of keyframes: B independent loops in the batched refinement (config 5, kf_batch.hip), a table of one in the map handle (mapping.hip).
+// table of keyframes: B independent loops in the batched refinement (config 5, kf_batch.hip), the iterating sensors of a call in the map handles
+// (mapping.hip; lio_map_process: a table of one).
 // Slots of keyframe k = [slot_off, slot_off + Mc) corner, then Ms surf, in one concatenated stack.  Three launches per round:
 //   round  : corner line search + surf plane search (PointMapping.cc:377-619), blockIdx.y picks the branch
 //   rows   : mat_A / mat_B (Estimator.cc:1272-1301) reduced to nb partials of 28 doubles.  b_from_coef != 0: mat_B = -coef.w (the distance
@@ -243,10 +244,12 @@ void launch_kf_round(const KfDesc *kd, const KfMapDesc *md, const OdomState *st,
                      float4 *abs_coef_or_null, hipStream_t s);
 void launch_kf_rows(const KfDesc *kd, const OdomState *st, int n_keyframes, int max_nb, const float4 *stack_all, const uint8_t *valid, const float4 *coef,
                     double *partials, int b_from_coef, hipStream_t s);
-// n_converged (device int, optional) is incremented once per keyframe when it converges.  sig (a launch of ONE keyframe only): the block posts
-// the keyframe's state to the host's mailbox `mail` behind the update (dev.h: HostSignal), converged before this launch or not
+// n_converged (device int, optional) is incremented once per keyframe when it converges.  sig.flag != nullptr: behind the update block k posts
+// keyframe k's state to its own slot of the host's mailbox (`mail` + k * KF_MAIL_STRIDE) and then sig.seq to its own completion word
+// sig.flag + k, converged before this launch or not; the host waits with sig.nslots = n_keyframes (dev.h: HostSignal)
+#define KF_MAIL_STRIDE 64   // bytes per keyframe in the mailbox
 void launch_kf_update(const KfDesc *kd, OdomState *st, int n_keyframes, const double *partials, int iter, int min_rows, int left_update, int *n_converged,
-                      OdomState *mail, const HostSignal &sig, hipStream_t s);
+                      char *mail, const HostSignal &sig, hipStream_t s);
 
 #if defined(__HIPCC__)
 // Fixed-order sum of `nblocks` rows of 28 doubles by a 256-thread block: 8 groups of 32 lanes take the rows b = g (mod 8)

@@ -745,16 +745,18 @@ __global__ void __launch_bounds__(ODOM_ROW_THREADS) k_kf_rows(const KfDesc *__re
 }
 
 __global__ void k_kf_update(const KfDesc *__restrict__ kd, OdomState *st, const double *__restrict__ partials, int iter, int min_rows, int left_update,
-                            int *n_converged, OdomState *mail, HostSignal sig) {
+                            int *n_converged, char *mail, HostSignal sig) {
   const int k = blockIdx.x;
   if (!st[k].converged) {
     const KfDesc d = kd[k];
     odom_update_body(partials + size_t(d.part_off) * 28, d.nb, st + k, iter, min_rows, left_update);
     if (n_converged && threadIdx.x == 0 && st[k].converged) atomicAdd(n_converged, 1);
   }
-  if (sig.flag) {   // the rounds at which the host looks at the convergence flag post the state to its mailbox (dev.h); a launch of one keyframe
+  if (sig.flag) {   // the rounds at which the host looks post every keyframe's state to its own mailbox slot, then its own completion word (dev.h)
     __syncthreads();
-    if (threadIdx.x < 64) post_host_mail(sig, mail, st + k, int(sizeof(OdomState) / 4), threadIdx.x);
+    HostSignal mine = sig;
+    mine.flag = sig.flag + k;
+    if (threadIdx.x < 64) post_host_mail(mine, mail + size_t(k) * KF_MAIL_STRIDE, st + k, int(sizeof(OdomState) / 4), threadIdx.x);
   }
 }
 
@@ -802,8 +804,8 @@ void launch_kf_rows(const KfDesc *kd, const OdomState *st, int n_keyframes, int 
   LIO_HIP(hipGetLastError());
 }
 void launch_kf_update(const KfDesc *kd, OdomState *st, int n_keyframes, const double *partials, int iter, int min_rows, int left_update, int *n_converged,
-                      OdomState *mail, const HostSignal &sig, hipStream_t s) {
-  if (sig.flag && n_keyframes != 1) throw DeviceError("launch_kf_update: only a launch of one keyframe posts to the host's mailbox");
+                      char *mail, const HostSignal &sig, hipStream_t s) {
+  static_assert(sizeof(OdomState) <= KF_MAIL_STRIDE, "mailbox layout");
   hipLaunchKernelGGL(k_kf_update, dim3(n_keyframes), dim3(256), 0, s, kd, st, partials, iter, min_rows, left_update, n_converged, mail, sig);
   LIO_HIP(hipGetLastError());
 }

@@ -2,9 +2,10 @@
 // Each keyframe runs the scan-to-map Gauss-Newton loop of MapBuilder::OptimizeMap (MapBuilder.cc:624-1014, 4-DoF) or
 // PointMapping::OptimizeTransformTobeMapped (PointMapping.cc:325-753, 6-DoF) against its local map.  Keyframes are
 // independent, so the batch is the parallel dimension: every stage of a round is ONE launch over all keyframes.
-// The three launches (cloud_kernels.h: launch_kf_round / _rows / _update) are the only form of that loop in the product: the map handle
-// (mapping.hip: MappingDev::Optimize) runs them on a table of one keyframe, with the unsigned plane written for its score list and the
-// state posted to its pinned mailbox.  What is the batch's own: the query order, the lanes-per-query rule and the convergence count.
+// The three launches (cloud_kernels.h: launch_kf_round / _rows / _update) are the only form of that loop in the product: the map handles
+// (mapping.hip: MapChain::Iterate) run them on a table of the call's iterating sensors (lio_map_process: a table of one), with the unsigned
+// plane written for the score lists and every sensor's state posted to its own slot of a pinned mailbox.  What is the batch's own: the
+// query order, the lanes-per-query rule and the convergence count (the n_converged peek: Refine passes no signal).
 #pragma once
 #include <memory>
 #include <vector>

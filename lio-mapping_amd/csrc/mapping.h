@@ -8,6 +8,10 @@
 // are inside it; extracting the FOV cubes is one 8-bit radix pass + gather that leaves the pool as
 // [rest | valid cubes in valid_idx order], so laser_cloud_*_from_map_ is a contiguous tail of the pool; the per-cube
 // VoxelGrid of UpdateMapDatabase is ONE segmented voxel pass with 64-bit (cube rank, voxel) keys.
+//
+// One route steps a handle: ProcessBatch drives a MapChain (mapping.hip) through prepare, filter, grids, table, rounds, give back and
+// update for all handles of a call, and Process is ProcessBatch of the handle alone.  The Gauss-Newton rounds are the keyframe chain of
+// cloud_kernels.h on a table of the call's iterating sensors; the host reads convergence and the final states from per-sensor mailboxes.
 #pragma once
 #include <memory>
 #include <vector>
@@ -38,10 +42,7 @@ struct MapSurroundSet {
 
 struct MapCounters { int n_valid, n_rest, n_new_valid, n_new_rest, n_out, pad[3]; };
 
-// the keyframe table of one that Optimize runs the scan-to-map chain on (cloud_kernels.h): one record of each kind and the loop's state
-struct KfOne { KfMapDesc md; KfDesc kd; OdomState st; };
-
-struct MapChain;   // mapping.hip: the launch chain of ProcessBatch and its scratch
+struct MapChain;   // mapping.hip: the launch chain every step runs through (prepare, filter, grids, table, rounds, give back, update) and its scratch
 
 class MappingDev {
  public:
@@ -52,10 +53,11 @@ class MappingDev {
   MappingDev(const MappingDev &) = delete;
   MappingDev &operator=(const MappingDev &) = delete;
 
+  // ProcessBatch of this handle alone
   void Process(const float *corner_last, size_t n_corner, const float *surf_last, size_t n_surf, const Rigid<float> &transform_sum);
-  // include/lio_map_batch.h: Process of n distinct handles, one sweep each, with the phases lined up across the handles and the rounds of all
-  // of them in one launch chain.  Array k of every argument belongs to m[k].  Every handle ends in the state Process alone leaves, bit for
-  // bit.  Returns synchronised.
+  // include/lio_map_batch.h: one sweep for each of n distinct handles, with the steps of the chain lined up across the handles and the rounds
+  // of all of them in one keyframe table.  Array k of every argument belongs to m[k].  Every handle ends in the state a chain of one leaves,
+  // bit for bit.  Handles without common launch parameters run as chains of one.  Returns synchronised (the full cloud's registration too).
   static void ProcessBatch(MappingDev *const *m, int n, const float *const *corner_last, const size_t *n_corner, const float *const *surf_last,
                            const size_t *n_surf, const Rigid<float> *transform_sum);
   void UpdateMapDatabase(const float *corner_ds, size_t n_corner, const float *surf_ds, size_t n_surf, const uint32_t *valid_idx, size_t n_valid,
@@ -112,14 +114,11 @@ class MappingDev {
     DBuf<unsigned long long> k64, k64b;
     DBuf<int> flags, pos;
     DBuf<int> cube_bounds;          // [LIO_MAP_MAX_VALID][6] order-preserving int images of min/max
-    DBuf<float> partial;
-    DBuf<VoxParams> bounds;
     KnnGrid grid;
     VoxelGridDev vox;
     DBuf<float4> in, stack_raw, stack_ds;
     size_t n_stack = 0;
     HostBuf<MapCounters> h_counters;
-    HostBuf<VoxParams> h_bounds;
   };
 
   MapValidSet MakeValidSet(const uint32_t *valid_idx, size_t n, const int cen_of_idx[3]) const;
@@ -128,29 +127,21 @@ class MappingDev {
   void LayoutFinish(ClassMap &m, const MapValidSet &vs);   // after a stream sync
   void UpdateLaunch(ClassMap &m, const float4 *new_sensor_pts, size_t n_new, const MapValidSet &vs, const Rigid<float> &T, float leaf);
   void UpdateFinish(ClassMap &m);
-  void Optimize(bool four_dof);
 
-  // ---- the phases of Process.  Process runs them one after the other on its own streams with the waits it has always had; ProcessBatch runs
-  // each phase for every handle before the next one starts, so that a wait is one pass over the handles instead of one stop per handle.
-  struct Step {            // what one Process carries between its phases
+  // ---- what a step does on the handle alone; MapChain's steps (mapping.hip) call these for every handle of a call
+  struct Step {            // what one handle carries between the chain's steps
     Rigid<float> T0;       // transform_tobe_mapped_ after the association: the stack's round trip, the window and the FOV test use it
     MapValidSet vs;
     size_t cnt[2];
     bool relayout[2];
   };
   void StepBegin(const Rigid<float> &transform_sum, Step &st);           // the call's resets, TransformAssociateToMap / the 4-D one
-  void StepUpload(int c, const float *src, size_t n, Step &st);          // one stack cloud to in; stack_raw sized for its round trip
   void StepWindow(Step &st);                                             // cube bookkeeping, valid set, surround set, LayoutLaunch where the layout changed
-  void StepLayoutFinish(Step &st);                                       // after a wait for stream_
   void StepFilterLaunch(const Step &st);                                 // the two VoxelGrids, the surf one on stream2_, joined back into stream_
-  void StepFilterFinish();                                               // waits for the two counts
   bool StepOptimizes();                                                  // MapBuilder's skip_count: false on a call that only updates the map (and does what that call does)
-  bool OptimizeGate();                                                   // Optimize's first lines: false when the from-map clouds are too small
-  void OptimizeDry();                                                    // ... an empty stack: the loop runs dry, then TransformUpdate
-  void OptimizeEnd(const OdomState &st, int M, bool four_dof);           // ... its last lines: the state the rounds ended with, TransformUpdate
+  void TransformUpdate();                                                // :760-763
+  void OptimizeEnd(const OdomState &st, int M, bool four_dof);           // the state the rounds ended with into the handle, TransformUpdate
   bool StepUpdates() const { return cfg_.map_builder != 0 || !imu_inited_; }
-  void StepUpdateLaunch(const Step &st);                                 // UpdateLaunch of both classes
-  void StepUpdateFinish();                                               // after a wait for stream_
   void StepRegisterFull();                                               // PublishResults on full_cloud_, once per set
   bool FourDof() const { return cfg_.map_builder != 0 && cfg_.enable_4d != 0; }
   MapChain &Chain();
@@ -164,13 +155,6 @@ class MappingDev {
   DBuf<float4> stack_all_;
   DBuf<uint8_t> f_valid_;
   DBuf<float4> f_coef_, f_abs_;
-  DBuf<KfOne> d_one_;
-  DBuf<double> d_partials_;
-  HostBuf<char> h_mail_;          // pinned, coherent: the state's mailbox
-  OdomState *h_state_ = nullptr;  // ... the state in it
-  unsigned *h_flag_ = nullptr;    // its completion word
-  KfOne *h_one_ = nullptr;        // ... and the table of one that Optimize uploads
-  unsigned seq_ = 0;
   size_t n_score_slots_ = 0;
   bool score_ready_ = false;
   size_t n_from_map_[2] = {0, 0};  // sizes of laser_cloud_{corner,surf}_from_map_ of the last Process
@@ -188,7 +172,7 @@ class MappingDev {
   bool full_mapped_ = false;        // this set has been through PublishResults
   bool system_init_ = false;        // MapBuilder.h:65
   int odom_count_ = 0;              // MapBuilder.h:69
-  std::unique_ptr<MapChain> chain_;  // ProcessBatch's scratch when this handle is the first of a call; no results live there
+  std::unique_ptr<MapChain> chain_;  // the chain's scratch when this handle is the first of a call (Process: the only one); no results live there
 };
 
 }  // namespace lio

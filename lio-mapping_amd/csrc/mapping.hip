@@ -2,8 +2,6 @@
 // kernel or a rocPRIM primitive; the host only does the 6-DoF bookkeeping (transform algebra, cube-window shift,
 // FOV test of <= 125 cubes).
 #include <cstring>
-#include <cstdio>
-#include <cstdlib>
 
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
@@ -228,17 +226,12 @@ __device__ __forceinline__ float4 stack_roundtrip_point(const float4 p, const Qu
   Vec3<float> r = rotate(conj(q), v);
   return make_float4(r.x, r.y, r.z, p.w);
 }
-__global__ void k_stack_roundtrip(const float4 *__restrict__ in, int n, Quat<float> q, Vec3<float> t, float4 *__restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  out[i] = stack_roundtrip_point(in[i], q, t);
-}
 
 // ---- the kernels of ProcessBatch (include/lio_map_batch.h) around the keyframe chain of cloud_kernels.h: plain streaming kernels, 256 threads, one
 // float4 per lane, every sensor (or cloud) with its own record of a device table.  A block beyond a record's own points leaves at once.
 // One sensor's stack clouds (0 corner, 1 surf) and the transform_tobe_mapped_ its association left
 struct MbStackRec { const float4 *in[2]; float4 *out[2]; int n[2]; Quat<float> q; Vec3<float> t; };
-// grid (cdiv(max n, 256), 2, sensors): k_stack_roundtrip's body on every sensor's two clouds with the sensor's own T0
+// grid (cdiv(max n, 256), 2, sensors): stack_roundtrip_point on every sensor's two clouds with the sensor's own T0
 __global__ void __launch_bounds__(256) k_mb_roundtrip(const MbStackRec *__restrict__ recs) {
   const MbStackRec &r = recs[blockIdx.z];
   const int c = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
@@ -340,36 +333,50 @@ inline Mat3<double> to_double(const Mat3<float> &m) { Mat3<double> r; for (int k
 
 }  // namespace
 
-// ProcessBatch's scratch, kept by the first handle of a call.  No results live here: poses, clouds, maps and the score list's arrays are the
-// handles' own.
+// The launch chain of ProcessBatch and its scratch, kept by the first handle of a call (Process: the handle itself).  No results live here: poses,
+// clouds, maps and the score list's arrays are the handles' own.  The members below the buffers are the call's steps in their order; the work of
+// a handle stays on its own streams but for the launches that serve every sensor at once, which run on the first handle's stream s0.
 struct MapChain {
+  MappingDev *const *m = nullptr;       // the call's handles
+  int n = 0;
+  hipStream_t s0 = nullptr;
   std::vector<MappingDev::Step> steps;
   std::vector<MbStackRec> h_stack;
   DBuf<MbStackRec> d_stack;
+  bool any_stack = false;               // some handle brought a cloud: the round trip ran
   std::vector<int> act;                 // the handles (indices into the call) whose rounds run: the keyframe table's order
   std::vector<MbBoundsRec> h_brecs;
   DBuf<MbBoundsRec> d_brecs;
   DBuf<float> d_bpartial;
   DBuf<VoxParams> d_bounds;
   HostBuf<VoxParams> h_bounds;          // pinned: 2 * nA
-  std::vector<MbSliceRec> h_slices;
-  DBuf<MbSliceRec> d_slices;
   DBuf<float4> stack_all, coef, abs_coef;
   DBuf<uint8_t> valid;
   DBuf<double> partials;
-  HostBuf<char> h_table;                // pinned: nA KfMapDesc, nA KfDesc, nA OdomState, one behind the other; the states come back into it
+  HostBuf<char> h_table;                // pinned: nA KfMapDesc, nA KfDesc, nA OdomState, nA MbSliceRec, one behind the other: one upload
   DBuf<char> d_table;
-  DBuf<int> d_nconv;
-  HostBuf<int> h_nconv;
-  hipEvent_t ev = nullptr;              // behind the round trip of the stacks: every handle's filters wait for it
-  MapChain() {
-    LIO_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    d_nconv.reserve(1);
-    h_nconv.alloc(1, hipHostMallocDefault, true);
-  }
+  size_t off_kd = 0, off_st = 0, off_sl = 0;
+  int max_Mc = 0, max_Ms = 0, max_nb = 0;
+  HostBuf<char> h_mail;                 // pinned, coherent: mail_cap states of KF_MAIL_STRIDE bytes, then mail_cap completion words (dev.h: HostSignal)
+  size_t mail_cap = 0;
+  unsigned seq = 0;
+  hipEvent_t ev = nullptr;              // behind the round trip of the stacks: every other handle's filters wait for it
+  MapChain() { LIO_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); }
   ~MapChain() { if (ev) (void)hipEventDestroy(ev); }
   MapChain(const MapChain &) = delete;
   MapChain &operator=(const MapChain &) = delete;
+
+  int nA() const { return int(act.size()); }
+  MappingDev &dev(int j) const { return *m[act[size_t(j)]]; }
+  OdomState &mail(int j) const { return *reinterpret_cast<OdomState *>(h_mail.p + size_t(j) * KF_MAIL_STRIDE); }   // sensor j's slot
+  void Prepare(MappingDev *const *handles, int n_handles, const float *const *corner_last, const size_t *n_corner, const float *const *surf_last,
+               const size_t *n_surf, const Rigid<float> *sums);
+  void Filter();
+  void MakeGrids();
+  void FillTable();
+  void Iterate();
+  void GiveBack();
+  void Update();
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -385,18 +392,9 @@ MappingDev::MappingDev(const lio_map_config &cfg) : cfg_(cfg) {
   LIO_HIP(hipEventCreateWithFlags(&ev_full_read_, hipEventDisableTiming));
   for (ClassMap &m : cls_) {
     m.h_counters.alloc(1, hipHostMallocDefault, true);
-    m.h_bounds.alloc(1, hipHostMallocDefault, true);
     m.counters.reserve(1);
-    m.bounds.reserve(1);
     m.cube_bounds.reserve(LIO_MAP_MAX_VALID * 6);
   }
-  // coherent: the update kernel posts the state and a completion word here (dev.h: HostSignal); behind them the table of one on its way up
-  h_mail_.alloc(128 + sizeof(KfOne), hipHostMallocCoherent, true);
-  static_assert(sizeof(OdomState) <= 64, "mailbox layout");
-  h_state_ = reinterpret_cast<OdomState *>(h_mail_.p);
-  h_flag_ = reinterpret_cast<unsigned *>(h_mail_.p + 64);
-  h_one_ = reinterpret_cast<KfOne *>(h_mail_.p + 128);
-  d_one_.reserve(1);
   sur_count_.reserve(1); sur_desc_.reserve(1);
   h_sur_count_.alloc(1, hipHostMallocDefault, true);
   h_sur_desc_.alloc(1, hipHostMallocDefault, true);
@@ -634,44 +632,13 @@ size_t MappingDev::GetFullCloud(float *out) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// The phases in the order, on the streams and with the waits Process has always had (ProcessBatch below lines them up across handles)
+// One step of a handle is a chain of one: the only route through the file
 void MappingDev::Process(const float *corner_last, size_t n_corner, const float *surf_last, size_t n_surf, const Rigid<float> &sum) {
-  hipStream_t s = stream_;
-  const bool dbg = std::getenv("LIO_DEBUG_TIMING") != nullptr;
-  const double tt0 = now_ms();
-  Step st;
-  StepBegin(sum, st);
-  // stack clouds go up while the host does the cube bookkeeping
-  const float *src[2] = {corner_last, surf_last};
-  const size_t cnt[2] = {n_corner, n_surf};
-  for (int c = 0; c < 2; ++c) {
-    StepUpload(c, src[c], cnt[c], st);
-    if (cnt[c])
-      hipLaunchKernelGGL(k_stack_roundtrip, dim3(cdiv(int(cnt[c]), 256)), dim3(256), 0, s, cls_[c].in.p, int(cnt[c]), st.T0.rot, st.T0.pos, cls_[c].stack_raw.p);
-  }
-  StepWindow(st);
-  if (st.relayout[0] || st.relayout[1]) LIO_HIP(hipStreamSynchronize(s));
-  StepLayoutFinish(st);
-
-  const double tt1 = now_ms();
-  StepFilterLaunch(st);
-  StepFilterFinish();
-
-  const double tt2 = now_ms();
-  if (StepOptimizes()) Optimize(FourDof());
-
-  const double tt3 = now_ms();
-  if (StepUpdates()) {
-    StepUpdateLaunch(st);
-    LIO_HIP(hipStreamSynchronize(s));
-    StepUpdateFinish();
-  }
-  StepRegisterFull();
-  if (dbg)
-    std::fprintf(stderr, "[lio_hip map timing] upload+layout %.3f  stack voxel %.3f  optimise %.3f (%d rounds)  map update %.3f  total %.3f ms\n", tt1 - tt0,
-                 tt2 - tt1, tt3 - tt2, iterations_, now_ms() - tt3, now_ms() - tt0);
+  MappingDev *self = this;
+  ProcessBatch(&self, 1, &corner_last, &n_corner, &surf_last, &n_surf, &sum);
 }
 
+// ---- what a step does on the handle alone, called by the chain's steps below
 void MappingDev::StepBegin(const Rigid<float> &sum, Step &st) {
   transform_sum_ = sum;
   score_ready_ = false;
@@ -699,15 +666,6 @@ void MappingDev::StepBegin(const Rigid<float> &sum, Step &st) {
     }
   }
   st.T0 = transform_tobe_mapped_;
-}
-
-void MappingDev::StepUpload(int c, const float *src, size_t n, Step &st) {
-  ClassMap &m = cls_[c];
-  m.n_stack = 0;
-  st.cnt[c] = n;
-  if (!n) return;
-  m.in.reserve(n); m.stack_raw.reserve(n);
-  LIO_HIP(hipMemcpyAsync(m.in.p, src, n * sizeof(float4), hipMemcpyHostToDevice, stream_));
 }
 
 void MappingDev::StepWindow(Step &st) {
@@ -756,10 +714,6 @@ void MappingDev::StepWindow(Step &st) {
   }
 }
 
-void MappingDev::StepLayoutFinish(Step &st) {
-  for (int c = 0; c < 2; ++c) if (st.relayout[c]) LayoutFinish(cls_[c], st.vs);
-}
-
 // VoxelGrid of the stacks (:1005-1015)
 void MappingDev::StepFilterLaunch(const Step &st) {
   hipStream_t s = stream_;
@@ -774,8 +728,10 @@ void MappingDev::StepFilterLaunch(const Step &st) {
   LIO_HIP(hipEventRecord(ev_join_, stream2_));
   LIO_HIP(hipStreamWaitEvent(s, ev_join_, 0));
 }
-void MappingDev::StepFilterFinish() {
-  for (int c = 0; c < 2; ++c) cls_[c].n_stack = cls_[c].vox.finish();
+// TransformUpdate (:760-763)
+void MappingDev::TransformUpdate() {
+  transform_bef_mapped_ = transform_sum_;
+  transform_aft_mapped_ = transform_tobe_mapped_;
 }
 
 // MapBuilder.cc:527-558: optimise every skip_count-th call, always update the map
@@ -784,20 +740,25 @@ bool MappingDev::StepOptimizes() {
   const bool optimise = odom_count_ % cfg_.skip_count == 0;
   if (!optimise) {
     n_from_map_[0] = cls_[0].n_valid; n_from_map_[1] = cls_[1].n_valid; from_map_in_u_ = false;
-    transform_bef_mapped_ = transform_sum_; transform_aft_mapped_ = transform_tobe_mapped_;
+    TransformUpdate();
   }
   ++odom_count_;
   return optimise;
 }
 
-void MappingDev::StepUpdateLaunch(const Step &st) {
-  const float leaf[2] = {cfg_.corner_filter_size, cfg_.surf_filter_size};
-  for (int c = 0; c < 2; ++c) UpdateLaunch(cls_[c], cls_[c].stack_ds.p, cls_[c].n_stack, st.vs, transform_tobe_mapped_, leaf[c]);
+// the state the rounds ended with; M: the slots the score list's arrays hold
+void MappingDev::OptimizeEnd(const OdomState &st, int M, bool four_dof) {
+  transform_tobe_mapped_.rot = Quat<float>(st.T[3], st.T[0], st.T[1], st.T[2]);
+  transform_tobe_mapped_.pos = Vec3<float>(st.T[4], st.T[5], st.T[6]);
+  iterations_ = st.iters;
+  num_selected_ = st.nsel;
+  degenerate_ = st.degenerate != 0;
+  kz_ = degenerate_ ? st.kz : 0;
+  TransformUpdate();
+  n_score_slots_ = size_t(M);
+  score_ready_ = !four_dof;  // OptimizeMap keeps no score list
 }
-void MappingDev::StepUpdateFinish() {
-  for (int c = 0; c < 2; ++c) UpdateFinish(cls_[c]);
-  from_map_in_u_ = true;
-}
+
 // PublishResults (:1105 -> :1244-1248): PointAssociateToMap on full_cloud_, in place
 void MappingDev::StepRegisterFull() {
   if (imu_inited_ || !n_full_ || full_mapped_) return;
@@ -812,295 +773,262 @@ void MappingDev::StepRegisterFull() {
   full_mapped_ = true; full_event_ = true;
 }
 
-bool MappingDev::OptimizeGate() {
-  n_from_map_[0] = cls_[0].n_valid; n_from_map_[1] = cls_[1].n_valid;
-  from_map_in_u_ = false;
-  return cls_[0].n_valid > 10 && cls_[1].n_valid > 100;  // :327-329 (no TransformUpdate either)
-}
-// every round has < 50 rows: the loop runs dry, then TransformUpdate
-void MappingDev::OptimizeDry() {
-  iterations_ = cfg_.num_max_iterations;
-  transform_bef_mapped_ = transform_sum_; transform_aft_mapped_ = transform_tobe_mapped_;
-}
-// the state the rounds ended with; M: the slots the score list's arrays hold
-void MappingDev::OptimizeEnd(const OdomState &st, int M, bool four_dof) {
-  transform_tobe_mapped_.rot = Quat<float>(st.T[3], st.T[0], st.T[1], st.T[2]);
-  transform_tobe_mapped_.pos = Vec3<float>(st.T[4], st.T[5], st.T[6]);
-  iterations_ = st.iters;
-  num_selected_ = st.nsel;
-  degenerate_ = st.degenerate != 0;
-  kz_ = degenerate_ ? st.kz : 0;
-  transform_bef_mapped_ = transform_sum_;            // TransformUpdate (:760-763)
-  transform_aft_mapped_ = transform_tobe_mapped_;
-  n_score_slots_ = size_t(M);
-  score_ready_ = !four_dof;  // OptimizeMap keeps no score list
-}
-
-void MappingDev::Optimize(bool four_dof) {
-  hipStream_t s = stream_;
-  ClassMap &mc = cls_[0], &ms = cls_[1];
-  if (!OptimizeGate()) return;
-  // search grids over the two from-map clouds
-  ClassMap *cm[2] = {&mc, &ms};
-  for (ClassMap *m : cm) {
-    launch_cloud_bounds(m->pool.p + m->n_rest, int(m->n_valid), m->partial, m->bounds.p, s);
-    LIO_HIP(hipMemcpyAsync(m->h_bounds.p, m->bounds.p, sizeof(VoxParams), hipMemcpyDeviceToHost, s));
-  }
-  LIO_HIP(hipStreamSynchronize(s));
-  const float cell = scan_to_map_cell_edge(cfg_.min_match_sq_dis);
-  for (ClassMap *m : cm) m->grid.build(m->pool.p + m->n_rest, m->n_valid, m->h_bounds.p->mn, m->h_bounds.p->mx, cell, s);
-
-  const int Mc = int(mc.n_stack), Ms = int(ms.n_stack), M = Mc + Ms;
-  if (M == 0) { OptimizeDry(); return; }
-  stack_all_.reserve(size_t(M)); f_valid_.reserve(size_t(M)); f_coef_.reserve(size_t(M)); f_abs_.reserve(size_t(M));
-  if (Mc) LIO_HIP(hipMemcpyAsync(stack_all_.p, mc.stack_ds.p, size_t(Mc) * sizeof(float4), hipMemcpyDeviceToDevice, s));
-  if (Ms) LIO_HIP(hipMemcpyAsync(stack_all_.p + Mc, ms.stack_ds.p, size_t(Ms) * sizeof(float4), hipMemcpyDeviceToDevice, s));
-  // the loop is the keyframe chain of cloud_kernels.hip on a table of one: this window's two grids, the whole stack as one keyframe, the
-  // starting state — one upload
-  const int nb = odom_rows_blocks(M);
-  d_partials_.reserve(size_t(nb) * 28);
-  KfOne &one = *h_one_;
-  one.md = KfMapDesc{mc.grid.sorted(), mc.grid.cells(), mc.grid.desc(), ms.grid.sorted(), ms.grid.cells(), ms.grid.desc()};
-  one.kd = KfDesc{0, Mc, Ms, 0, nb, 0, {pz_[0], pz_[1], pz_[2]}};
-  one.st = odom_state_at(transform_tobe_mapped_);
-  *h_state_ = one.st;   // (what the loop's end reads when no round runs)
-  LIO_HIP(hipMemcpyAsync(d_one_.p, h_one_, sizeof(KfOne), hipMemcpyHostToDevice, s));
-  const KfMapDesc *d_md = &d_one_.p->md;
-  const KfDesc *d_kd = &d_one_.p->kd;
-  OdomState *d_st = &d_one_.p->st;
-  const int mode = four_dof ? 2 : 1;
-  const int max_it = cfg_.num_max_iterations;
-  int iter = 0;
-  // Convergence is read back at these rounds only: a peek costs a sync + D2H + relaunch bubble (~35 us), a round that runs
-  // after convergence costs three no-op launches (~18 us), and the loop typically needs 5-7 rounds.
-  static const int kPeek[] = {6, 8, 10, 10};
-  int peek_i = 0;
-  bool done = false;
-  while (iter < max_it && !done) {
-    int until = max_it;
-    while (peek_i < 4 && kPeek[peek_i] <= iter) ++peek_i;
-    if (peek_i < 4) until = std::min(max_it, kPeek[peek_i]);
-    HostSignal sig{};
-    for (; iter < until; ++iter) {
-      // eight lanes per query; no processing order (the stack is one sweep's, a few thousand queries)
-      launch_kf_round(d_kd, d_md, d_st, 1, Mc, Ms, 8, stack_all_.p, nullptr, cfg_.min_match_sq_dis, cfg_.min_plane_dis, mode, f_valid_.p, f_coef_.p, f_abs_.p, s);
-      launch_kf_rows(d_kd, d_st, 1, nb, stack_all_.p, f_valid_.p, f_coef_.p, d_partials_.p, mode, s);
-      // the last round before a look at the convergence flag posts the state to the host's mailbox (dev.h: HostSignal)
-      if (iter == until - 1) { sig.flag = h_flag_; sig.seq = ++seq_; }
-      launch_kf_update(d_kd, d_st, 1, d_partials_.p, iter, 50, four_dof ? 1 : 0, nullptr, h_state_, sig, s);
-    }
-    wait_host_signal(sig, s);   // until > iter: the inner loop ran and its last round posted sig
-    if (h_state_->converged) done = true;
-  }
-  OptimizeEnd(*h_state_, M, four_dof);
-}
-
 MapChain &MappingDev::Chain() {
   if (!chain_) chain_.reset(new MapChain);
   return *chain_;
 }
 
 // ------------------------------------------------------------------------------------------------
-// include/lio_map_batch.h.  Every phase runs for all handles before the next one starts; the work of a handle stays on its own streams but
-// for the launches that serve every sensor at once (the stacks' round trip, the from-map bounds, the rounds and what goes around them),
-// which run on m[0]'s stream.  Every handle is idle when the call starts (each lio_map_* call returns synchronised).
-void MappingDev::ProcessBatch(MappingDev *const *m, int n, const float *const *corner_last, const size_t *n_corner, const float *const *surf_last,
-                              const size_t *n_surf, const Rigid<float> *sums) {
-  // the round launches carry these as launch parameters: without common values there is no common chain
-  bool common = true;
-  for (int k = 1; k < n; ++k) {
-    const lio_map_config &a = m[0]->cfg_, &b = m[k]->cfg_;
-    common = common && a.min_match_sq_dis == b.min_match_sq_dis && a.min_plane_dis == b.min_plane_dis && a.num_max_iterations == b.num_max_iterations &&
-             m[0]->FourDof() == m[k]->FourDof();
-  }
-  if (!common) {
-    for (int k = 0; k < n; ++k) {
-      m[k]->Process(corner_last[k], n_corner[k], surf_last[k], n_surf[k], sums[k]);
-      m[k]->Sync();
-    }
-    return;
-  }
-  for (int k = 0; k < n; ++k)
-    if (n_corner[k] > size_t(INT_MAX) - 255 || n_surf[k] > size_t(INT_MAX) - 255) throw CapacityError("lio_map_process_batch: a cloud exceeds 2^31 points");
-  MapChain &ch = m[0]->Chain();
-  hipStream_t s0 = m[0]->stream_;
-  const lio_map_config &cfg = m[0]->cfg_;
-  const bool four_dof = m[0]->FourDof();
+// include/lio_map_batch.h.  Every step of the chain runs for all handles before the next one starts, so a wait is one pass over the handles
+// instead of one stop per handle.  Every handle is idle when the call starts (each lio_map_* call returns synchronised).
 
-  // ---- 1. prepare: association, uploads, cube bookkeeping and the layout pass per handle, no wait in between; one launch for every round trip
-  ch.steps.assign(size_t(n), Step());
-  ch.h_stack.assign(size_t(n), MbStackRec());
+// ---- 1. prepare: association, uploads, cube bookkeeping and the layout pass per handle, no wait in between; one launch for every round trip
+void MapChain::Prepare(MappingDev *const *handles, int n_handles, const float *const *corner_last, const size_t *n_corner, const float *const *surf_last,
+                       const size_t *n_surf, const Rigid<float> *sums) {
+  m = handles; n = n_handles; s0 = m[0]->stream_;
+  steps.assign(size_t(n), MappingDev::Step());
+  h_stack.assign(size_t(n), MbStackRec());
   size_t max_in = 0;
   for (int k = 0; k < n; ++k) {
     MappingDev &d = *m[k];
-    Step &st = ch.steps[size_t(k)];
+    MappingDev::Step &st = steps[size_t(k)];
     d.StepBegin(sums[k], st);
-    d.StepUpload(0, corner_last[k], n_corner[k], st);
-    d.StepUpload(1, surf_last[k], n_surf[k], st);
-    if (k && (n_corner[k] || n_surf[k])) {   // the round trip on s0 reads what this stream uploads
-      LIO_HIP(hipEventRecord(d.ev_join_, d.stream_));
-      LIO_HIP(hipStreamWaitEvent(s0, d.ev_join_, 0));
-    }
-    MbStackRec &r = ch.h_stack[size_t(k)];
+    // the stack clouds go up while the host does the cube bookkeeping; stack_raw is sized for their round trip
+    const float *src[2] = {corner_last[k], surf_last[k]};
+    st.cnt[0] = n_corner[k]; st.cnt[1] = n_surf[k];
+    MbStackRec &r = h_stack[size_t(k)];
     for (int c = 0; c < 2; ++c) {
-      r.in[c] = d.cls_[c].in.p; r.out[c] = d.cls_[c].stack_raw.p; r.n[c] = int(st.cnt[c]);
+      MappingDev::ClassMap &cm = d.cls_[c];
+      cm.n_stack = 0;
+      if (st.cnt[c]) {
+        cm.in.reserve(st.cnt[c]); cm.stack_raw.reserve(st.cnt[c]);
+        LIO_HIP(hipMemcpyAsync(cm.in.p, src[c], st.cnt[c] * sizeof(float4), hipMemcpyHostToDevice, d.stream_));
+      }
+      r.in[c] = cm.in.p; r.out[c] = cm.stack_raw.p; r.n[c] = int(st.cnt[c]);
       max_in = std::max(max_in, st.cnt[c]);
     }
     r.q = st.T0.rot; r.t = st.T0.pos;
+    if (k && (st.cnt[0] || st.cnt[1])) {   // the round trip on s0 reads what this stream uploads
+      LIO_HIP(hipEventRecord(d.ev_join_, d.stream_));
+      LIO_HIP(hipStreamWaitEvent(s0, d.ev_join_, 0));
+    }
     d.StepWindow(st);
   }
-  if (max_in) {
-    ch.d_stack.reserve(size_t(n));
-    LIO_HIP(hipMemcpyAsync(ch.d_stack.p, ch.h_stack.data(), size_t(n) * sizeof(MbStackRec), hipMemcpyHostToDevice, s0));
-    hipLaunchKernelGGL(k_mb_roundtrip, dim3(cdiv(max_in, 256), 2, n), dim3(256), 0, s0, ch.d_stack.p);
+  any_stack = max_in != 0;
+  if (any_stack) {
+    d_stack.reserve(size_t(n));
+    LIO_HIP(hipMemcpyAsync(d_stack.p, h_stack.data(), size_t(n) * sizeof(MbStackRec), hipMemcpyHostToDevice, s0));
+    hipLaunchKernelGGL(k_mb_roundtrip, dim3(cdiv(max_in, 256), 2, n), dim3(256), 0, s0, d_stack.p);
     LIO_HIP(hipGetLastError());
-    LIO_HIP(hipEventRecord(ch.ev, s0));
+    if (n > 1) LIO_HIP(hipEventRecord(ev, s0));
   }
   for (int k = 0; k < n; ++k) {   // one pass of waits over the handles that re-laid out
     MappingDev &d = *m[k];
-    Step &st = ch.steps[size_t(k)];
+    const MappingDev::Step &st = steps[size_t(k)];
     if (st.relayout[0] || st.relayout[1]) LIO_HIP(hipStreamSynchronize(d.stream_));
-    d.StepLayoutFinish(st);
+    for (int c = 0; c < 2; ++c) if (st.relayout[c]) d.LayoutFinish(d.cls_[c], st.vs);
   }
+}
 
-  // ---- 2. filter: every handle's two VoxelGrids in flight before the first count is waited for
+// ---- 2. filter: every handle's two VoxelGrids in flight before the first count is waited for
+void MapChain::Filter() {
   for (int k = 0; k < n; ++k) {
     MappingDev &d = *m[k];
-    if (k && max_in) LIO_HIP(hipStreamWaitEvent(d.stream_, ch.ev, 0));
-    d.StepFilterLaunch(ch.steps[size_t(k)]);
+    if (k && any_stack) LIO_HIP(hipStreamWaitEvent(d.stream_, ev, 0));
+    d.StepFilterLaunch(steps[size_t(k)]);
   }
-  for (int k = 0; k < n; ++k) m[k]->StepFilterFinish();
+  for (int k = 0; k < n; ++k)
+    for (MappingDev::ClassMap &cm : m[k]->cls_) cm.n_stack = cm.vox.finish();
+}
 
-  // ---- 3. who iterates; the bounds of their from-map clouds in two launches, one copy back, one wait; their grids on their own streams
-  ch.act.clear();
+// ---- 3. who iterates (`act`); the bounds of their from-map clouds in two launches, one copy back, one wait; their grids on their own streams
+void MapChain::MakeGrids() {
+  act.clear();
   for (int k = 0; k < n; ++k) {
     MappingDev &d = *m[k];
-    if (!d.StepOptimizes() || !d.OptimizeGate()) continue;   // a skipped MapBuilder call; from-map clouds too small (:327-329)
-    if (d.cls_[0].n_stack + d.cls_[1].n_stack == 0) { d.OptimizeDry(); continue; }
-    ch.act.push_back(k);
+    if (!d.StepOptimizes()) continue;   // a skipped MapBuilder call
+    d.n_from_map_[0] = d.cls_[0].n_valid; d.n_from_map_[1] = d.cls_[1].n_valid;
+    d.from_map_in_u_ = false;
+    if (!(d.cls_[0].n_valid > 10 && d.cls_[1].n_valid > 100)) continue;   // :327-329 (no TransformUpdate either)
+    if (d.cls_[0].n_stack + d.cls_[1].n_stack == 0) {   // every round has < 50 rows: the loop runs dry, then TransformUpdate
+      d.iterations_ = d.cfg_.num_max_iterations;
+      d.TransformUpdate();
+      continue;
+    }
+    act.push_back(k);
   }
-  const int na = int(ch.act.size());
-  if (na) {
-    ch.h_brecs.assign(size_t(2 * na), MbBoundsRec());
-    size_t bpart_total = 0;
-    int max_bnb = 0;
-    for (int j = 0; j < na; ++j) {
-      MappingDev &d = *m[ch.act[size_t(j)]];
-      for (int c = 0; c < 2; ++c) {
-        const ClassMap &cm = d.cls_[c];
-        if (cm.n_valid > size_t(INT_MAX) - 255) throw CapacityError("lio_map_process_batch: a from-map cloud exceeds 2^31 points");
-        MbBoundsRec &r = ch.h_brecs[size_t(2 * j + c)];
-        r.pts = cm.pool.p + cm.n_rest; r.n = int(cm.n_valid);
-        r.nb = std::max(1, std::min(cdiv(r.n, 256), 512));   // (launch_cloud_bounds)
-        r.off = int(bpart_total);
-        bpart_total += size_t(r.nb);
-        max_bnb = std::max(max_bnb, r.nb);
-      }
+  const int na = nA();
+  if (!na) return;
+  h_brecs.assign(size_t(2 * na), MbBoundsRec());
+  size_t bpart_total = 0;
+  int max_bnb = 0;
+  for (int j = 0; j < na; ++j)
+    for (int c = 0; c < 2; ++c) {
+      const MappingDev::ClassMap &cm = dev(j).cls_[c];
+      if (cm.n_valid > size_t(INT_MAX) - 255) throw CapacityError("lio_map_process_batch: a from-map cloud exceeds 2^31 points");
+      MbBoundsRec &r = h_brecs[size_t(2 * j + c)];
+      r.pts = cm.pool.p + cm.n_rest; r.n = int(cm.n_valid);
+      r.nb = std::max(1, std::min(cdiv(r.n, 256), 512));   // (launch_cloud_bounds)
+      r.off = int(bpart_total);
+      bpart_total += size_t(r.nb);
+      max_bnb = std::max(max_bnb, r.nb);
     }
-    ch.d_brecs.reserve(size_t(2 * na)); ch.d_bpartial.reserve(bpart_total * 8); ch.d_bounds.reserve(size_t(2 * na));
-    if (ch.h_bounds.n < size_t(2 * na)) ch.h_bounds.alloc(size_t(2 * na) + size_t(na), hipHostMallocDefault);
-    LIO_HIP(hipMemcpyAsync(ch.d_brecs.p, ch.h_brecs.data(), size_t(2 * na) * sizeof(MbBoundsRec), hipMemcpyHostToDevice, s0));
-    hipLaunchKernelGGL(k_mb_bounds, dim3(max_bnb, 2 * na), dim3(VOX_TILE), 0, s0, ch.d_brecs.p, ch.d_bpartial.p);
-    hipLaunchKernelGGL(k_mb_bounds_fold, dim3(2 * na), dim3(VOX_TILE), 0, s0, ch.d_brecs.p, ch.d_bpartial.p, ch.d_bounds.p);
-    LIO_HIP(hipGetLastError());
-    LIO_HIP(hipMemcpyAsync(ch.h_bounds.p, ch.d_bounds.p, size_t(2 * na) * sizeof(VoxParams), hipMemcpyDeviceToHost, s0));
-    LIO_HIP(hipStreamSynchronize(s0));
-    const float cell = scan_to_map_cell_edge(cfg.min_match_sq_dis);
-    for (int j = 0; j < na; ++j) {
-      MappingDev &d = *m[ch.act[size_t(j)]];
-      for (int c = 0; c < 2; ++c) {
-        ClassMap &cm = d.cls_[c];
-        const VoxParams &b = ch.h_bounds.p[2 * j + c];
-        cm.grid.build(cm.pool.p + cm.n_rest, cm.n_valid, b.mn, b.mx, cell, d.stream_);
-      }
+  d_brecs.reserve(size_t(2 * na)); d_bpartial.reserve(bpart_total * 8); d_bounds.reserve(size_t(2 * na));
+  if (h_bounds.n < size_t(2 * na)) h_bounds.alloc(size_t(2 * na) + size_t(na), hipHostMallocDefault);
+  LIO_HIP(hipMemcpyAsync(d_brecs.p, h_brecs.data(), size_t(2 * na) * sizeof(MbBoundsRec), hipMemcpyHostToDevice, s0));
+  hipLaunchKernelGGL(k_mb_bounds, dim3(max_bnb, 2 * na), dim3(VOX_TILE), 0, s0, d_brecs.p, d_bpartial.p);
+  hipLaunchKernelGGL(k_mb_bounds_fold, dim3(2 * na), dim3(VOX_TILE), 0, s0, d_brecs.p, d_bpartial.p, d_bounds.p);
+  LIO_HIP(hipGetLastError());
+  LIO_HIP(hipMemcpyAsync(h_bounds.p, d_bounds.p, size_t(2 * na) * sizeof(VoxParams), hipMemcpyDeviceToHost, s0));
+  LIO_HIP(hipStreamSynchronize(s0));
+  const float cell = scan_to_map_cell_edge(m[0]->cfg_.min_match_sq_dis);
+  for (int j = 0; j < na; ++j)
+    for (int c = 0; c < 2; ++c) {
+      MappingDev::ClassMap &cm = dev(j).cls_[c];
+      const VoxParams &b = h_bounds.p[2 * j + c];
+      cm.grid.build(cm.pool.p + cm.n_rest, cm.n_valid, b.mn, b.mx, cell, dev(j).stream_);
     }
+}
 
-    // ---- 4. the rounds: the keyframe chain of cloud_kernels.h on a table of nA, on s0 behind every other iterating handle's stream
-    ch.h_slices.assign(size_t(na), MbSliceRec());
-    size_t slots = 0, part_total = 0;
-    int max_Mc = 0, max_Ms = 0, max_nb = 0;
-    const size_t off_kd = size_t(na) * sizeof(KfMapDesc), off_st = off_kd + ((size_t(na) * sizeof(KfDesc) + 7) & ~size_t(7));
-    const size_t table_bytes = off_st + size_t(na) * sizeof(OdomState);
-    if (ch.h_table.n < table_bytes) ch.h_table.alloc(table_bytes + table_bytes / 2, hipHostMallocDefault);
-    ch.d_table.reserve(table_bytes);
-    KfMapDesc *h_md = reinterpret_cast<KfMapDesc *>(ch.h_table.p);
-    KfDesc *h_kd = reinterpret_cast<KfDesc *>(ch.h_table.p + off_kd);
-    OdomState *h_st = reinterpret_cast<OdomState *>(ch.h_table.p + off_st);
-    for (int j = 0; j < na; ++j) {
-      MappingDev &d = *m[ch.act[size_t(j)]];
-      ClassMap &mc = d.cls_[0], &ms = d.cls_[1];
-      if (mc.n_stack + ms.n_stack + slots > size_t(INT_MAX) - 255) throw CapacityError("lio_map_process_batch: the filtered stacks exceed 2^31 points");
-      const int Mc = int(mc.n_stack), Ms = int(ms.n_stack), M = Mc + Ms;
-      const int nb = odom_rows_blocks(M);
-      h_md[j] = KfMapDesc{mc.grid.sorted(), mc.grid.cells(), mc.grid.desc(), ms.grid.sorted(), ms.grid.cells(), ms.grid.desc()};
-      h_kd[j] = KfDesc{int(slots), Mc, Ms, j, nb, int(part_total), {d.pz_[0], d.pz_[1], d.pz_[2]}};
-      h_st[j] = odom_state_at(d.transform_tobe_mapped_);
-      d.stack_all_.reserve(size_t(M)); d.f_valid_.reserve(size_t(M)); d.f_coef_.reserve(size_t(M)); d.f_abs_.reserve(size_t(M));
-      MbSliceRec &r = ch.h_slices[size_t(j)];
-      r.stack_ds[0] = mc.stack_ds.p; r.stack_ds[1] = ms.stack_ds.p; r.M[0] = Mc; r.M[1] = Ms; r.slot_off = int(slots);
-      r.stack_all = d.stack_all_.p; r.coef = d.f_coef_.p; r.abs_coef = d.f_abs_.p; r.valid = d.f_valid_.p;
-      slots += size_t(M); part_total += size_t(nb);
-      max_Mc = std::max(max_Mc, Mc); max_Ms = std::max(max_Ms, Ms); max_nb = std::max(max_nb, nb);
-      if (ch.act[size_t(j)]) {   // its filters (the surf one joined in) and its grids
-        LIO_HIP(hipEventRecord(d.ev_join_, d.stream_));
-        LIO_HIP(hipStreamWaitEvent(s0, d.ev_join_, 0));
-      }
-    }
-    ch.stack_all.reserve(slots); ch.valid.reserve(slots); ch.coef.reserve(slots); ch.abs_coef.reserve(slots);
-    ch.partials.reserve(part_total * 28);
-    ch.d_slices.reserve(size_t(na));
-    LIO_HIP(hipMemcpyAsync(ch.d_slices.p, ch.h_slices.data(), size_t(na) * sizeof(MbSliceRec), hipMemcpyHostToDevice, s0));
-    LIO_HIP(hipMemcpyAsync(ch.d_table.p, ch.h_table.p, table_bytes, hipMemcpyHostToDevice, s0));
-    LIO_HIP(hipMemsetAsync(ch.d_nconv.p, 0, sizeof(int), s0));
-    const int max_M = std::max(max_Mc, max_Ms);   // (> 0: every sensor of the table has a stack)
-    hipLaunchKernelGGL(k_mb_take, dim3(cdiv(max_M, 256), 2, na), dim3(256), 0, s0, ch.d_slices.p, ch.stack_all.p);
-    LIO_HIP(hipGetLastError());
-    const KfMapDesc *d_md = reinterpret_cast<const KfMapDesc *>(ch.d_table.p);
-    const KfDesc *d_kd = reinterpret_cast<const KfDesc *>(ch.d_table.p + off_kd);
-    OdomState *d_st = reinterpret_cast<OdomState *>(ch.d_table.p + off_st);
-    const int mode = four_dof ? 2 : 1;
-    const int max_it = cfg.num_max_iterations;
-    // the looks at the convergence counter come where Optimize has them; a sensor that has converged stays frozen (its blocks leave at once)
-    static const int kPeek[] = {6, 8, 10};
-    int iter = 0, peek_i = 0;
-    while (iter < max_it) {
-      int until = max_it;
-      while (peek_i < 3 && kPeek[peek_i] <= iter) ++peek_i;
-      if (peek_i < 3) until = std::min(max_it, kPeek[peek_i]);
-      for (; iter < until; ++iter) {
-        // eight lanes per query; no processing order (every stack is one sweep's, a few thousand queries)
-        launch_kf_round(d_kd, d_md, d_st, na, max_Mc, max_Ms, 8, ch.stack_all.p, nullptr, cfg.min_match_sq_dis, cfg.min_plane_dis, mode, ch.valid.p, ch.coef.p,
-                        ch.abs_coef.p, s0);
-        launch_kf_rows(d_kd, d_st, na, max_nb, ch.stack_all.p, ch.valid.p, ch.coef.p, ch.partials.p, mode, s0);
-        launch_kf_update(d_kd, d_st, na, ch.partials.p, iter, 50, four_dof ? 1 : 0, ch.d_nconv.p, nullptr, HostSignal(), s0);
-      }
-      if (iter >= max_it) break;
-      LIO_HIP(hipMemcpyAsync(ch.h_nconv.p, ch.d_nconv.p, sizeof(int), hipMemcpyDeviceToHost, s0));
-      LIO_HIP(hipStreamSynchronize(s0));
-      if (*ch.h_nconv.p >= na) break;
-    }
-    // ---- 5. give back: every sensor's slice of the chain's arrays into its handle, the states in one copy, one wait
-    hipLaunchKernelGGL(k_mb_give, dim3(cdiv(max_Mc + max_Ms, 256), 4, na), dim3(256), 0, s0, ch.d_slices.p, ch.stack_all.p, ch.coef.p, ch.abs_coef.p, ch.valid.p);
-    LIO_HIP(hipGetLastError());
-    LIO_HIP(hipMemcpyAsync(h_st, d_st, size_t(na) * sizeof(OdomState), hipMemcpyDeviceToHost, s0));
-    LIO_HIP(hipStreamSynchronize(s0));
-    for (int j = 0; j < na; ++j) {
-      MappingDev &d = *m[ch.act[size_t(j)]];
-      d.OptimizeEnd(h_st[j], int(d.cls_[0].n_stack + d.cls_[1].n_stack), four_dof);
+// ---- 4. the keyframe table of cloud_kernels.h over `act`: every sensor's two grids, its whole stack as one keyframe, its starting state, and
+// where its slice of the chain's arrays lies in the handle — one upload; then the filtered stacks into the chain's stack_all
+void MapChain::FillTable() {
+  const int na = nA();
+  size_t slots = 0, part_total = 0;
+  max_Mc = max_Ms = max_nb = 0;
+  auto up8 = [](size_t b) { return (b + 7) & ~size_t(7); };
+  off_kd = size_t(na) * sizeof(KfMapDesc);
+  off_st = off_kd + up8(size_t(na) * sizeof(KfDesc));
+  off_sl = off_st + up8(size_t(na) * sizeof(OdomState));
+  const size_t table_bytes = off_sl + size_t(na) * sizeof(MbSliceRec);
+  if (h_table.n < table_bytes) h_table.alloc(table_bytes + table_bytes / 2, hipHostMallocDefault);
+  d_table.reserve(table_bytes);
+  KfMapDesc *h_md = reinterpret_cast<KfMapDesc *>(h_table.p);
+  KfDesc *h_kd = reinterpret_cast<KfDesc *>(h_table.p + off_kd);
+  OdomState *h_st = reinterpret_cast<OdomState *>(h_table.p + off_st);
+  MbSliceRec *h_sl = reinterpret_cast<MbSliceRec *>(h_table.p + off_sl);
+  for (int j = 0; j < na; ++j) {
+    MappingDev &d = dev(j);
+    MappingDev::ClassMap &mc = d.cls_[0], &ms = d.cls_[1];
+    if (mc.n_stack + ms.n_stack + slots > size_t(INT_MAX) - 255) throw CapacityError("lio_map_process_batch: the filtered stacks exceed 2^31 points");
+    const int Mc = int(mc.n_stack), Ms = int(ms.n_stack), M = Mc + Ms;
+    const int nb = odom_rows_blocks(M);
+    h_md[j] = KfMapDesc{mc.grid.sorted(), mc.grid.cells(), mc.grid.desc(), ms.grid.sorted(), ms.grid.cells(), ms.grid.desc()};
+    h_kd[j] = KfDesc{int(slots), Mc, Ms, j, nb, int(part_total), {d.pz_[0], d.pz_[1], d.pz_[2]}};
+    h_st[j] = odom_state_at(d.transform_tobe_mapped_);
+    d.stack_all_.reserve(size_t(M)); d.f_valid_.reserve(size_t(M)); d.f_coef_.reserve(size_t(M)); d.f_abs_.reserve(size_t(M));
+    h_sl[j] = MbSliceRec{{mc.stack_ds.p, ms.stack_ds.p}, {Mc, Ms}, int(slots), d.stack_all_.p, d.f_coef_.p, d.f_abs_.p, d.f_valid_.p};
+    slots += size_t(M); part_total += size_t(nb);
+    max_Mc = std::max(max_Mc, Mc); max_Ms = std::max(max_Ms, Ms); max_nb = std::max(max_nb, nb);
+    if (act[size_t(j)]) {   // s0 behind its filters (the surf one joined in) and its grids
+      LIO_HIP(hipEventRecord(d.ev_join_, d.stream_));
+      LIO_HIP(hipStreamWaitEvent(s0, d.ev_join_, 0));
     }
   }
-  // the map update and the full cloud's registration per handle on its own stream (the chain has been waited for: the poses are on the
-  // host), then one pass of waits
+  stack_all.reserve(slots); valid.reserve(slots); coef.reserve(slots); abs_coef.reserve(slots);
+  partials.reserve(part_total * 28);
+  LIO_HIP(hipMemcpyAsync(d_table.p, h_table.p, table_bytes, hipMemcpyHostToDevice, s0));
+  const int max_M = std::max(max_Mc, max_Ms);   // (> 0: every sensor of the table has a stack)
+  hipLaunchKernelGGL(k_mb_take, dim3(cdiv(max_M, 256), 2, na), dim3(256), 0, s0, reinterpret_cast<const MbSliceRec *>(d_table.p + off_sl), stack_all.p);
+  LIO_HIP(hipGetLastError());
+}
+
+// ---- 5. the rounds (:325-753), three launches each over the whole table.  Convergence is read back behind rounds 6, 8 and 10 only: a peek costs
+// a wait and a relaunch bubble (~35 us), a round that runs after convergence costs three no-op launches (~18 us), and the loop typically needs
+// 5-7 rounds.  The last round before a peek posts every sensor's state to its own mailbox slot (dev.h: HostSignal); the peek ends the loop
+// only when EVERY sensor has converged (one that converged earlier stays frozen: its blocks leave at once).  Leaves the last states in the mailbox.
+void MapChain::Iterate() {
+  const int na = nA();
+  const lio_map_config &cfg = m[0]->cfg_;
+  const bool four_dof = m[0]->FourDof();
+  if (mail_cap < size_t(na)) {   // (the stream is idle between calls: nobody still posts to the old one)
+    const size_t cap = size_t(na) + size_t(na) / 2;
+    h_mail.alloc(cap * (KF_MAIL_STRIDE + sizeof(unsigned)), hipHostMallocCoherent, true);
+    mail_cap = cap;
+  }
+  unsigned *flags = reinterpret_cast<unsigned *>(h_mail.p + mail_cap * KF_MAIL_STRIDE);
+  const OdomState *h_st = reinterpret_cast<const OdomState *>(h_table.p + off_st);
+  for (int j = 0; j < na; ++j) mail(j) = h_st[j];   // (what the loop's end reads when no round runs)
+  const KfMapDesc *d_md = reinterpret_cast<const KfMapDesc *>(d_table.p);
+  const KfDesc *d_kd = reinterpret_cast<const KfDesc *>(d_table.p + off_kd);
+  OdomState *d_st = reinterpret_cast<OdomState *>(d_table.p + off_st);
+  const int mode = four_dof ? 2 : 1;
+  const int max_it = cfg.num_max_iterations;
+  static const int kPeek[] = {6, 8, 10};
+  HostSignal sig{};
+  sig.nslots = na;
+  int iter = 0, peek_i = 0;
+  bool done = false;
+  while (iter < max_it && !done) {
+    int until = max_it;
+    while (peek_i < 3 && kPeek[peek_i] <= iter) ++peek_i;
+    if (peek_i < 3) until = std::min(max_it, kPeek[peek_i]);
+    for (; iter < until; ++iter) {
+      // eight lanes per query; no processing order (every stack is one sweep's, a few thousand queries)
+      launch_kf_round(d_kd, d_md, d_st, na, max_Mc, max_Ms, 8, stack_all.p, nullptr, cfg.min_match_sq_dis, cfg.min_plane_dis, mode, valid.p, coef.p, abs_coef.p, s0);
+      launch_kf_rows(d_kd, d_st, na, max_nb, stack_all.p, valid.p, coef.p, partials.p, mode, s0);
+      HostSignal sg{};
+      if (iter == until - 1) { sig.flag = flags; sig.seq = ++seq; sg = sig; }
+      launch_kf_update(d_kd, d_st, na, partials.p, iter, 50, four_dof ? 1 : 0, nullptr, h_mail.p, sg, s0);
+    }
+    wait_host_signal(sig, s0);   // until > iter: the inner loop ran and its last round posted sig
+    done = true;
+    for (int j = 0; j < na; ++j) done = done && mail(j).converged;
+  }
+}
+
+// ---- 6. give back: every sensor's slice of the chain's arrays into its handle (nobody waits for it before the call's last pass), the states
+// from the mailbox
+void MapChain::GiveBack() {
+  const int na = nA();
+  hipLaunchKernelGGL(k_mb_give, dim3(cdiv(max_Mc + max_Ms, 256), 4, na), dim3(256), 0, s0, reinterpret_cast<const MbSliceRec *>(d_table.p + off_sl), stack_all.p,
+                     coef.p, abs_coef.p, valid.p);
+  LIO_HIP(hipGetLastError());
+  for (int j = 0; j < na; ++j) dev(j).OptimizeEnd(mail(j), int(dev(j).cls_[0].n_stack + dev(j).cls_[1].n_stack), m[0]->FourDof());
+}
+
+// ---- 7. update: the map update and the full cloud's registration per handle on its own stream (the poses are on the host), then one pass of
+// waits: the call returns synchronised
+void MapChain::Update() {
   for (int k = 0; k < n; ++k) {
     MappingDev &d = *m[k];
-    if (d.StepUpdates()) d.StepUpdateLaunch(ch.steps[size_t(k)]);
+    const float leaf[2] = {d.cfg_.corner_filter_size, d.cfg_.surf_filter_size};
+    if (d.StepUpdates())
+      for (int c = 0; c < 2; ++c) d.UpdateLaunch(d.cls_[c], d.cls_[c].stack_ds.p, d.cls_[c].n_stack, steps[size_t(k)].vs, d.transform_tobe_mapped_, leaf[c]);
     d.StepRegisterFull();
   }
   for (int k = 0; k < n; ++k) {
     MappingDev &d = *m[k];
     LIO_HIP(hipStreamSynchronize(d.stream_));
-    if (d.StepUpdates()) d.StepUpdateFinish();
+    if (!d.StepUpdates()) continue;
+    for (int c = 0; c < 2; ++c) d.UpdateFinish(d.cls_[c]);
+    d.from_map_in_u_ = true;
   }
+}
+
+void MappingDev::ProcessBatch(MappingDev *const *m, int n, const float *const *corner_last, const size_t *n_corner, const float *const *surf_last,
+                              const size_t *n_surf, const Rigid<float> *sums) {
+  for (int k = 0; k < n; ++k)
+    if (n_corner[k] > size_t(INT_MAX) - 255 || n_surf[k] > size_t(INT_MAX) - 255) throw CapacityError("lio_map_process_batch: a cloud exceeds 2^31 points");
+  // the round launches carry these as launch parameters: without common values there is no common chain, a chain of one per handle
+  for (int k = 1; k < n; ++k) {
+    const lio_map_config &a = m[0]->cfg_, &b = m[k]->cfg_;
+    if (a.min_match_sq_dis == b.min_match_sq_dis && a.min_plane_dis == b.min_plane_dis && a.num_max_iterations == b.num_max_iterations &&
+        m[0]->FourDof() == m[k]->FourDof())
+      continue;
+    for (int j = 0; j < n; ++j) ProcessBatch(m + j, 1, corner_last + j, n_corner + j, surf_last + j, n_surf + j, sums + j);
+    return;
+  }
+  MapChain &ch = m[0]->Chain();
+  ch.Prepare(m, n, corner_last, n_corner, surf_last, n_surf, sums);
+  ch.Filter();
+  ch.MakeGrids();
+  if (ch.nA()) {
+    ch.FillTable();
+    ch.Iterate();
+    ch.GiveBack();
+  }
+  ch.Update();
 }
 
 // ------------------------------------------------------------------------------------------------

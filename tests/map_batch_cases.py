@@ -1,6 +1,6 @@
 """Inputs of the batched scan-to-map tests (include/lio_map_batch.h): tests/test_map_batch_abi.py asserts on the CPU oracle that every
-sensor kind does what its name says, tests/test_gpu_map_batch.py then compares lio_map_process_batch with lio_map_process alone on twin
-handles, bit for bit.
+sensor kind does what its name says, tests/test_gpu_map_batch.py then compares one chain of B sensors (lio_map_process_batch) with B
+chains of one (lio_map_process) on twin handles, bit for bit.
 
 The material is mapping_util.drifting_inputs(oracle, "indoor", N_FRAMES): indoor VLP-16 feature clouds with a drifting transform_sum,
 extracted once per process.  A sensor is a dict:
@@ -66,6 +66,13 @@ def builder(oracle, j, n_steps, extra_prep=0, **cfg):
     assert j + p + n_steps <= N_FRAMES
     cfg = dict(dict(map_builder=1, enable_4d=1, skip_count=2), **cfg)
     return _sensor(f"builder{j}", "builder", fr[j + p:j + p + n_steps], prep=fr[j:j + p], cfg=cfg)
+
+
+def still(oracle, j, n_steps):
+    """the last sweep of the prep again, with its transform_sum: the association leaves transform_tobe_mapped_ where the step before ended,
+    on a map that already holds the sweep, so the loop converges well before the first peek (2 or 3 rounds on the oracle)"""
+    fr = frames(oracle)
+    return _sensor(f"still{j}", "still", [fr[j + 1]] * n_steps, prep=fr[j:j + 2])
 
 
 def first_call(oracle, n_steps):

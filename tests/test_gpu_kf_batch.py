@@ -72,9 +72,10 @@ def _assert_twin(hip, mh, r, T0, **batch_kw):
 
 
 def test_batch_equals_single_keyframe_handle(hip, oracle):
-    """The scan-to-map handle runs the batch's launch chain on a table of one keyframe (csrc/mapping.hip: Optimize), so the two agree
-    by construction; what this still guards is everything around the chain — the handle's table (grids, stack, start state in one
-    upload), its mailbox peeks at rounds 6, 8 and 10, and the batch's query order, lane split and convergence count.  Three cuts of
+    """The scan-to-map handle runs the batch's launch chain on a table of one keyframe (csrc/mapping.hip: MapChain::Iterate on a chain
+    of one), so the two agree by construction; what this still guards is everything around the chain — the handle's table (grids,
+    stack, start state in one upload), the per-sensor mailboxes it reads behind rounds 6, 8 and 10 where the batch reads its
+    convergence count, and the batch's query order and lane split.  Refine shares no host code with the handle.  Three cuts of
     the stacks: full; no corner point (the corner half of the round launch has no block to run); 3 corner + 20 surf points (fewer
     than 50 rows every round: the loop runs dry through all three peeks and the start pose comes back untouched)."""
     from mapping_util import drifting_inputs

@@ -1,6 +1,8 @@
-"""lio_map_process_batch (include/lio_map_batch.h) against lio_map_process alone on twin handles: the same sweeps, every getter of every
-handle after every step, np.array_equal on uint32 views — no tolerance.  The sensors are those of tests/map_batch_cases.py (indoor VLP-16
-sweeps, a few thousand queries each); tests/test_map_batch_abi.py shows on the CPU oracle that each kind does what its name says."""
+"""One chain of B sensors against B chains of one (include/lio_map_batch.h).  lio_map_process is lio_map_process_batch of one handle, so the
+twin handles here differ in what shares a launch chain, not in the route: one set steps handle by handle (each a table of one on its own
+scratch), the other in ONE call (one table, the first handle's scratch).  The same sweeps, every getter of every handle after every
+step, np.array_equal on uint32 views — no tolerance.  The sensors are those of tests/map_batch_cases.py (indoor VLP-16 sweeps, a few
+thousand queries each); tests/test_map_batch_abi.py shows on the CPU oracle that each kind does what its name says."""
 import ctypes as C
 
 import numpy as np
@@ -84,7 +86,8 @@ def _compare_step(alone, batch, sensors, ra, rb, k):
 
 
 def _run(hip, sensors, n_steps, how=None, orders=None):
-    """twin handles through n_steps: the first set alone, the second as how[k] says ('batch' by default) -> the alone results per step"""
+    """twin handles through n_steps: the first set as chains of one, the second as how[k] says ('batch': one chain of all, the default) ->
+    the results of the chains of one per step"""
     alone, batch = _twins(hip, sensors)
     results = []
     for k in range(n_steps):
@@ -130,10 +133,53 @@ def test_map_builder_handles_that_optimise_and_skip_share_a_call(hip, oracle):
     assert any(0 in row and max(row) > 0 for row in its), its    # a skipped call beside an optimising one
 
 
+def test_mixed_peeks_in_one_chain(hip, oracle):
+    """Every peek (behind rounds 6, 8 and 10) sees converged and unconverged mailboxes side by side: one sensor converges before round 6,
+    one between rounds 6 and 10, and a dry one (3 corner + 20 surf points: fewer than 50 rows in every round) never does."""
+    sensors = [cases.moving(oracle, 0, 2), cases.still(oracle, 0, 2), cases.dry(oracle, 2)]
+    res, _, batch = _run(hip, sensors, 2)
+    its = [[r["iterations"] for r in step] for step in res]
+    print("iterations per step (moving0, still0, dry):", its)
+    mid, early, never = its[1]
+    assert early < 6 and 6 <= mid < 10 and never == batch[0].cfg.num_max_iterations, its
+
+
+@pytest.mark.parametrize("kind", ["one_block", "two_blocks"])
+def test_score_list_after_a_chain_of_one_and_a_chain_of_many(hip, oracle, kind):
+    """The score list is read from the handle's own arrays, which the chain hands back: the same list after lio_map_process and after a
+    call among other sensors, on both sides of the 2048-slot step of odom_rows_blocks, and still the same after other handles have
+    used the chain that handed it back."""
+    target, others = cases.blocks(oracle, kind, 1), [cases.moving(oracle, 0, 2), cases.moving(oracle, 1, 2)]
+    one = cases.make_handle(hip, target)
+    one.process(*target["steps"][0])
+    slots = len(one.cloud(0)) + len(one.cloud(1))
+    assert slots <= cases.ROW_STEP - cases.MARGIN if kind == "one_block" else slots >= cases.ROW_STEP + cases.MARGIN, slots
+    want = [_bits(a) for a in one.score_point_coeff()]
+    assert len(want[0]) >= 50
+    first, many, last = cases.make_handle(hip, others[0]), cases.make_handle(hip, target), cases.make_handle(hip, others[1])
+    capi.PointMapping.process_batch([first, many, last], [others[0]["steps"][0], target["steps"][0], others[1]["steps"][0]])
+    for got, ref in zip(many.score_point_coeff(), want):
+        assert np.array_equal(_bits(got), ref)
+    capi.PointMapping.process_batch([first, last], [others[0]["steps"][1], others[1]["steps"][1]])   # the same chain without `many`
+    other = cases.make_handle(hip, others[0])
+    other.process(*others[0]["steps"][0])                                                             # ... and a chain of one of another handle
+    for m in (many, one):
+        for got, ref in zip(m.score_point_coeff(), want):
+            assert np.array_equal(_bits(got), ref)
+
+
 def test_handles_without_common_launch_parameters_fall_back(hip, oracle):
+    """6-DoF, 4-DoF and another round limit share no launch parameters: the call runs a chain of one per handle, each on the handle's own
+    scratch.  _run holds every handle of that call to a handle stepped alone, bit for bit, after each of two consecutive steps; the second
+    step reuses every handle's own chain."""
     sensors = [cases.moving(oracle, 0, 2), cases.builder(oracle, 1, 2), cases.moving(oracle, 2, 2, num_max_iterations=3)]
-    res, _, _ = _run(hip, sensors, 2)
+    res, alone, batch = _run(hip, sensors, 2)
+    assert len(res) == 2
     assert all(step[2]["iterations"] <= 3 for step in res)
+    assert any(step[0]["iterations"] > 3 for step in res)       # ... so the first handle did not run under the third one's limit
+    assert len({(m.cfg.map_builder, m.cfg.num_max_iterations) for m in batch}) == 3
+    for j, (a, b) in enumerate(zip(alone, batch)):              # (once more after the last step, handle by handle)
+        _assert_same(_state(a), _state(b), ("fall-back", j))
 
 
 def test_batch_alone_batch_on_the_same_handles(hip, oracle):

@@ -9,9 +9,13 @@ over the steps after the warm-up; a GPU is required, and the CPU oracle library 
 
     python tools/map_batch_cost.py [--steps 12] [--batches 1,8,64] [--kinds indoor,outdoor] [--out FILE.json]
 
---parent-lib PATH additionally times lio_map_process ALONE of this tree against another build of the product (the parent commit's
-liblio_hip.so) in the same process, alternating, the order swapped every pair, 24 steps: what the split of Process into phases costs the
-one-sensor call.  Criterion (docs/scan_to_map.md): this tree's median is not above the other build's slowest step.
+--parent-lib PATH additionally times this tree against another build of the product (the parent commit's liblio_hip.so) in the same
+process, alternating, the order swapped every pair, equal bits asserted at every step: lio_map_process ALONE (24 steps), the same with a
+full cloud of FULL_POINTS points set before every step (the registration the call waits for; the set itself is not timed), and
+lio_map_process_batch at the sizes of --parent-batches.  Criterion (docs/scan_to_map.md): this tree's median is not above the other
+build's slowest step.
+--this-lib PATH takes another build in this tree's place: with the parent's library and a byte copy of it under another name the same
+lines are an A/A run, whose gap between the two medians is what a gap between this tree and the parent is held against.
 """
 import argparse
 import json
@@ -28,6 +32,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 WARMUP = 3   # the first steps grow the buffers and load the code objects
 N_FRAMES = 6
+FULL_POINTS = 2049   # the full clouds of tests/test_gpu_full_cloud_estimator.py
 
 
 def _ms(fn):
@@ -86,22 +91,51 @@ def measure_batch(hip, kind, frames, B, steps):
                 holds=bool(med_b <= np.max(t_loop)) if B == 1 else bool(med_b < np.min(t_loop)))
 
 
-def measure_parent(hip, parent, kind, frames, steps):
+def measure_parent(hip, parent, kind, frames, steps, full_points=0):
     from lio_amd import capi
 
     here, there = capi.PointMapping(hip), capi.PointMapping(parent)
     walk = _walk(len(frames))
     t_here, t_there, its = [], [], []
+    rng = np.random.default_rng(7)
     for k in range(WARMUP + steps):
         corner, surf, T_sum, _ = frames[walk[k % len(walk)]]
+        if full_points:
+            full = np.zeros((full_points, 4), np.float32)
+            full[:, :3] = rng.uniform(-8, 8, (full_points, 3))
+            here.set_full_cloud(full), there.set_full_cloud(full)
         if k % 2:
             (ra, a), (rb, b) = _ms(lambda: here.process(corner, surf, T_sum)), _ms(lambda: there.process(corner, surf, T_sum))
         else:
             (rb, b), (ra, a) = _ms(lambda: there.process(corner, surf, T_sum)), _ms(lambda: here.process(corner, surf, T_sum))
         assert np.array_equal(_words(here, ra), _words(there, rb)), (kind, k)   # same results as the parent
+        if full_points:
+            assert here.full_cloud().tobytes() == there.full_cloud().tobytes(), (kind, k)
         if k >= WARMUP:
             t_here.append(a), t_there.append(b), its.append(ra["iterations"])
-    return dict(what="single_vs_parent", kind=kind, steps_measured=steps, iterations_median=int(np.median(its)), this_tree_ms=_stats(t_here),
+    return dict(what="single_vs_parent", kind=kind, full_points=full_points, steps_measured=steps, iterations_median=int(np.median(its)),
+                this_tree_ms=_stats(t_here), parent_ms=_stats(t_there), holds=bool(np.median(t_here) <= np.max(t_there)))
+
+
+def measure_batch_parent(hip, parent, kind, frames, B, steps):
+    """one lio_map_process_batch of B copies in this tree against the same call of the other build"""
+    from lio_amd import capi
+
+    here, there = [capi.PointMapping(hip) for _ in range(B)], [capi.PointMapping(parent) for _ in range(B)]
+    walk = _walk(len(frames))
+    t_here, t_there, its = [], [], []
+    for k in range(WARMUP + steps):
+        corner, surf, T_sum, _ = frames[walk[k % len(walk)]]
+        inputs = [(corner, surf, T_sum)] * B
+        if k % 2:
+            (ra, a), (rb, b) = _ms(lambda: capi.PointMapping.process_batch(here, inputs)), _ms(lambda: capi.PointMapping.process_batch(there, inputs))
+        else:
+            (rb, b), (ra, a) = _ms(lambda: capi.PointMapping.process_batch(there, inputs)), _ms(lambda: capi.PointMapping.process_batch(here, inputs))
+        for j in sorted({0, B // 2, B - 1}):
+            assert np.array_equal(_words(here[j], ra[j]), _words(there[j], rb[j])), (kind, B, k, j)
+        if k >= WARMUP:
+            t_here.append(a), t_there.append(b), its.append(ra[0]["iterations"])
+    return dict(what="batch_vs_parent", kind=kind, B=B, steps_measured=steps, iterations_median=int(np.median(its)), this_tree_ms=_stats(t_here),
                 parent_ms=_stats(t_there), holds=bool(np.median(t_here) <= np.max(t_there)))
 
 
@@ -111,6 +145,8 @@ def main():
     ap.add_argument("--batches", default="1,8,64")
     ap.add_argument("--kinds", default="indoor,outdoor")
     ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--parent-batches", default="8,64")
+    ap.add_argument("--this-lib", default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert args.steps >= 8, "medians over at least 8 steps"
@@ -121,7 +157,7 @@ def main():
     from mapping_util import drifting_inputs
     from odom_batch_cost import load_parent
 
-    hip = capi.load_hip()
+    hip = load_parent(args.this_lib) if args.this_lib else capi.load_hip()
     parent = load_parent(args.parent_lib) if args.parent_lib else None
     oracle = capi.LioLib(os.path.join(ROOT, "oracle", "liblio_oracle.so"))
     results = []
@@ -131,8 +167,12 @@ def main():
             results.append(measure_batch(hip, kind, frames, B, args.steps))
             print(json.dumps(results[-1]), flush=True)
         if parent is not None:
-            results.append(measure_parent(hip, parent, kind, frames, max(args.steps, 24)))
-            print(json.dumps(results[-1]), flush=True)
+            for full_points in (0, FULL_POINTS):
+                results.append(measure_parent(hip, parent, kind, frames, max(args.steps, 24), full_points))
+                print(json.dumps(results[-1]), flush=True)
+            for B in [int(b) for b in args.parent_batches.split(",") if b]:
+                results.append(measure_batch_parent(hip, parent, kind, frames, B, args.steps))
+                print(json.dumps(results[-1]), flush=True)
     if args.out:
         with open(args.out, "w") as f:
             json.dump(results, f, indent=1)

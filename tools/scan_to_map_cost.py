@@ -3,7 +3,10 @@
 Both libraries are loaded into one process and get the same bytes.  A GPU is required; the inputs are the ones of the test suite
 (tests/mapping_util.py, tests/kf_util.py, tests/gn_cases.py), so the CPU oracle library has to be built too.
 
-    python tools/scan_to_map_cost.py --parent-lib PATH [--steps 24] [--skip-bits] [--skip-speed] [--out FILE.json]
+    python tools/scan_to_map_cost.py --parent-lib PATH [--this-lib PATH] [--steps 24] [--skip-bits] [--skip-speed] [--out FILE.json]
+
+--this-lib PATH takes another build in this tree's place: with the other build and a byte copy of it under another name the speed lines
+are an A/A run, whose gap between the two medians is what a gap between this tree and the other build is held against.
 
 bits   every 32-bit word of the outputs compared as uint32 (a NaN equals a NaN of the same bits):
          lio_map_process over the sequences of test_mapping_sequence_matches_oracle (indoor 5, outdoor 3 sweeps) and of
@@ -177,6 +180,7 @@ def speed(hip, parent, oracle, steps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", required=True)
+    ap.add_argument("--this-lib", default=None)
     ap.add_argument("--steps", type=int, default=24)
     ap.add_argument("--skip-bits", action="store_true")
     ap.add_argument("--skip-speed", action="store_true")
@@ -189,7 +193,7 @@ def main():
     from lio_amd import capi
     from odom_batch_cost import load_parent
 
-    hip, parent = capi.load_hip(), load_parent(args.parent_lib)
+    hip, parent = load_parent(args.this_lib) if args.this_lib else capi.load_hip(), load_parent(args.parent_lib)
     oracle = capi.LioLib(os.path.join(ROOT, "oracle", "liblio_oracle.so"))
     out = {}
     if not args.skip_bits:
