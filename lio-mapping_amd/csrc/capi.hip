@@ -12,6 +12,7 @@
 #include "../../include/lio_odom_batch.h"
 #include "../../include/lio_frontend_batch.h"
 #include "../../include/lio_map_batch.h"
+#include "../../include/lio_vox_sort.h"
 #include "est_batch.h"
 #include "seg_sort.h"
 #include "estimator.h"
@@ -662,6 +663,30 @@ int lio_voxel_grid(const float *xyzi, size_t n, float leaf, float *out, size_t *
     if (m) LIO_HIP(hipMemcpyAsync(out, sc.b.p, m * sizeof(float4), hipMemcpyDeviceToHost, sc.s));
     LIO_HIP(hipStreamSynchronize(sc.s));
     *n_out = m;
+    return LIO_OK;
+  });
+}
+
+// include/lio_vox_sort.h
+static_assert(LIO_VOX_SORT_SAMPLE == VSORT_PATH_SAMPLE && LIO_VOX_SORT_SINGLE == VSORT_PATH_SINGLE && LIO_VOX_SORT_LIBRARY == VSORT_PATH_LIBRARY &&
+              LIO_VOX_SORT_SINGLE_MAX == VSORT_CAP && LIO_VOX_SORT_BUCKET_CAP == VSORT_CAP && LIO_VOX_SORT_MEAN_BUCKET == VSORT_MEAN &&
+              LIO_VOX_SORT_OVERSAMPLE == VSORT_OVERSAMPLE && LIO_VOX_SORT_SAMPLE_MAX == VSORT_MAX_N, "the header states the sizing rule of cloud_kernels.h");
+int lio_vox_sort_pairs(const uint32_t *keys, size_t n, uint32_t *keys_out, uint32_t *vals_out, int *path_out) {
+  if (!keys || n == 0 || !keys_out || !vals_out) return LIO_ERR_ARG;
+  if (n >= size_t(INT_MAX)) return LIO_ERR_CAPACITY;
+  return guarded([&] {
+    Scratch &sc = scratch();
+    const int path = sc.vox.sort_pairs_hook(keys, n, keys_out, vals_out, sc.s);
+    if (path_out) *path_out = path;
+    return LIO_OK;
+  });
+}
+int lio_vox_sort_stats(uint64_t out[3]) {
+  if (!out) return LIO_ERR_ARG;
+  return guarded([&] {
+    unsigned long long c[3];
+    scratch().vox.sort_stats(c);
+    for (int k = 0; k < 3; ++k) out[k] = c[k];
     return LIO_OK;
   });
 }

@@ -240,6 +240,137 @@ __device__ __forceinline__ VoxSlot vox_centroid_tile(const float4 *__restrict__ 
   return VoxSlot{pos, head};
 }
 
+// ---- the filter's sort of (key, index) pairs: a sample sort (cloud_kernels.h states the sizing rule)
+#define VSORT_THREADS 256            // threads of the kernels that sort in registers
+#define VSORT_SCATTER_THREADS 512    // threads of the bucket scatter, VSORT_SCATTER_ITEMS points each
+#define VSORT_SCATTER_ITEMS 2
+
+// the value of lane (byte_addr / 4) of the wave, both halves of a pair
+__device__ __forceinline__ unsigned long long vsort_from_lane(unsigned long long v, int byte_addr) {
+  const uint32_t lo = uint32_t(__builtin_amdgcn_ds_bpermute(byte_addr, int(uint32_t(v))));
+  const uint32_t hi = uint32_t(__builtin_amdgcn_ds_bpermute(byte_addr, int(uint32_t(v >> 32))));
+  return (static_cast<unsigned long long>(hi) << 32) | lo;
+}
+
+// VSORT_THREADS * E pairs sorted ascending by a bitonic network, by a block of VSORT_THREADS threads: thread t holds the entries
+// t E + e in registers, before and after.  A step with stride j pairs entry i with i ^ j: inside the thread for j < E (no traffic at
+// all), in another lane of the wave for E <= j < 64 E (one lane permute per half), and only for j >= 64 E in another wave (through `lds`,
+// VSORT_THREADS * E entries, two barriers).  Both partners of a cross-thread step hold all E partners of each other, so each keeps the
+// minima or the maxima.  (Through LDS alone every step was a dependent read - write - barrier chain: 285 ns a step.)
+template <int E>
+__device__ __forceinline__ void vsort_block(unsigned long long (&v)[E], unsigned long long *__restrict__ lds) {
+  constexpr int P = VSORT_THREADS * E;
+  const int base = int(threadIdx.x) * E, lane = int(threadIdx.x) & 63;
+#pragma unroll 1
+  for (int k = 2; k <= P; k <<= 1) {
+#pragma unroll 1
+    for (int j = k >> 1; j >= 64 * E; j >>= 1) {
+      __syncthreads();   // the readers of the step before are done
+#pragma unroll
+      for (int e = 0; e < E; ++e) lds[base + e] = v[e];
+      __syncthreads();
+      const bool keep_min = ((base & j) == 0) == ((base & k) == 0);
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const unsigned long long o = lds[(base ^ j) + e];
+        if ((o < v[e]) == keep_min) v[e] = o;   // equal only for two fillers: either stays
+      }
+    }
+#pragma unroll 1
+    for (int j = min(k >> 1, 32 * E); j >= E; j >>= 1) {
+      const bool keep_min = ((base & j) == 0) == ((base & k) == 0);
+      const int partner = (lane ^ (j / E)) << 2;
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const unsigned long long o = vsort_from_lane(v[e], partner);
+        if ((o < v[e]) == keep_min) v[e] = o;
+      }
+    }
+#pragma unroll
+    for (int j = E / 2; j > 0; j >>= 1) {
+      if (j < k) {
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          if ((e & j) == 0) {
+            const bool asc = ((base + e) & k) == 0;
+            const unsigned long long x = v[e], y = v[e | j];
+            if ((x > y) == asc) { v[e] = y; v[e | j] = x; }
+          }
+        }
+      }
+    }
+  }
+}
+
+// the E for m entries: the smallest power of two with VSORT_THREADS * E >= m
+__device__ __forceinline__ int vsort_items_for(int m) {
+  int E = 1;
+  while (VSORT_THREADS * E < m) E <<= 1;
+  return E;
+}
+
+// m pairs (key << 32 | index) at src sorted and written to keys_out / vals_out at `off`; m <= VSORT_THREADS * E; lds: VSORT_THREADS * E pairs
+template <int E>
+__device__ __forceinline__ void vsort_pairs_sort_store(const unsigned long long *__restrict__ src, int m, unsigned long long *__restrict__ lds,
+                                                       uint32_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out, int off) {
+  unsigned long long v[E];
+  const int base = int(threadIdx.x) * E;
+#pragma unroll
+  for (int e = 0; e < E; ++e) v[e] = base + e < m ? src[base + e] : ~0ull;   // behind every pair: an index is below 2^32 - 1
+  vsort_block<E>(v, lds);
+#pragma unroll
+  for (int e = 0; e < E; ++e)
+    if (base + e < m) { keys_out[off + base + e] = uint32_t(v[e] >> 32); vals_out[off + base + e] = uint32_t(v[e]); }
+}
+// The number of pairs (ss[j], j), j < S, below `mine`: the sorted position of `mine` among them.  ss: LDS, S a multiple of four;
+// VSORT_RANK_LANES neighbouring lanes (part = 0 ..) share the count and all get it.
+#define VSORT_RANK_LANES 16
+__device__ __forceinline__ int vsort_rank_of(const uint32_t *__restrict__ ss, int S, int part, unsigned long long mine) {
+  int rank = 0;
+  const uint4 *ss4 = reinterpret_cast<const uint4 *>(ss);
+  for (int q = part; q < S / 4; q += VSORT_RANK_LANES) {
+    const uint4 k4 = ss4[q];
+    const uint32_t j = uint32_t(q) * 4;
+    rank += ((static_cast<unsigned long long>(k4.x) << 32) | j) < mine;
+    rank += ((static_cast<unsigned long long>(k4.y) << 32) | (j + 1)) < mine;
+    rank += ((static_cast<unsigned long long>(k4.z) << 32) | (j + 2)) < mine;
+    rank += ((static_cast<unsigned long long>(k4.w) << 32) | (j + 3)) < mine;
+  }
+#pragma unroll
+  for (int o = VSORT_RANK_LANES / 2; o > 0; o >>= 1) rank += __shfl_xor(rank, o, 64);
+  return rank;
+}
+
+// Splitters of the n keys for NB buckets.  The sample: S = OVERSAMPLE * NB keys at the fixed positions floor((j + 0.5) n / S).  Splitter
+// b (b = 1 .. NB - 1) is entry OVERSAMPLE * b of the sorted sample, found without sorting: the rank of sample i is the number of samples
+// below it as pairs (key, i), counted by VSORT_RANK_LANES lanes over the whole sample in LDS (`ss`, S keys); the sample whose rank is
+// OVERSAMPLE * b writes splitter b.  A block ranks VSORT_THREADS / VSORT_RANK_LANES samples; no block waits for another.
+// (One block sorting the sample was the longest kernel of the three: 13 us for 1384 keys, and it grows with NB.)
+template <int OVERSAMPLE>
+__device__ __forceinline__ void vsort_pick_splitters(const uint32_t *__restrict__ keys, int n, int NB, uint32_t *__restrict__ ss,
+                                                     uint32_t *__restrict__ splitters) {
+  const int S = OVERSAMPLE * NB;
+  static_assert(OVERSAMPLE % 4 == 0, "the sample is read four keys at a time");
+  // floor((2 t + 1) n / (2 S)) with n = q S + r is t q + floor((q S + (2 t + 1) r) / (2 S)): 32-bit arithmetic (r < S <= 8192, n < 2^19), no 64-bit division per load
+  const uint32_t q = uint32_t(n) / uint32_t(S), r = uint32_t(n) % uint32_t(S);
+  for (int t = threadIdx.x; t < S; t += VSORT_THREADS) ss[t] = keys[uint32_t(t) * q + (q * uint32_t(S) + (2u * uint32_t(t) + 1u) * r) / (2u * uint32_t(S))];
+  __syncthreads();
+  const int i = blockIdx.x * (VSORT_THREADS / VSORT_RANK_LANES) + int(threadIdx.x) / VSORT_RANK_LANES, part = int(threadIdx.x) % VSORT_RANK_LANES;
+  const unsigned long long mine = i < S ? (static_cast<unsigned long long>(ss[i]) << 32) | uint32_t(i) : 0ull;
+  const int rank = vsort_rank_of(ss, S, part, mine);
+  if (part == 0 && i < S && rank >= OVERSAMPLE && rank % OVERSAMPLE == 0) splitters[rank / OVERSAMPLE - 1] = uint32_t(mine >> 32);
+}
+
+// bucket of a key = number of splitters <= key (upper bound): equal keys share a bucket
+__device__ __forceinline__ int vsort_bucket_of(const uint32_t *__restrict__ spl, int NB, uint32_t key) {
+  int lo = 0, hi = NB - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (spl[mid] <= key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
 // ------------------------------------------------------------------------------------------------
 // what a solve's feature stage starts from
 // ------------------------------------------------------------------------------------------------

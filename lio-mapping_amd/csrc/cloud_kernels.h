@@ -38,8 +38,28 @@ void launch_rigid_map(const float4 *in, int n, const float q[4], const float p[3
 // min/max (VoxParams.mn/.mx, n_valid) of a device cloud; `partial` is scratch.  No host sync.
 void launch_cloud_bounds(const float4 *pts, int n, DBuf<float> &partial, VoxParams *d_out, hipStream_t s);
 
+// The filter's sort of the n (key, index) pairs: a sample sort in three launches (splitters, bucket scatter, bucket sort + compaction).
+// Sizing, a pure function of n:
+//   n <= VSORT_CAP                      keys_ sorted directly in one launch, by rank: every workgroup holds all keys in LDS and places 16 of them
+//   VSORT_CAP < n <= VSORT_MAX_N        NB = ceil(n / VSORT_MEAN) buckets of VSORT_CAP pairs each (more than 10 x the mean bucket, which is <= VSORT_MEAN;
+//                                       the fullest bucket sets the third kernel's time, so the mean is small),
+//                                       S = VSORT_OVERSAMPLE * NB sample keys at the positions floor((j + 0.5) n / S) of this call's keys
+//   n > VSORT_MAX_N                     the library's radix sort
+// A bucket that would pass its capacity raises the overflow word; finish() then redoes the filter with the library's sort.
+#define VSORT_CAP 4096            // pairs a bucket holds = pairs one workgroup sorts (16 per thread; 32 KB of LDS for the strides that cross waves)
+#define VSORT_MEAN 384
+#define VSORT_OVERSAMPLE 8
+#define VSORT_MAX_BUCKETS 1024    // splitters and per-workgroup bucket counters live in LDS
+#define VSORT_MAX_N (VSORT_MAX_BUCKETS * VSORT_MEAN)
+enum VoxSortPath { VSORT_PATH_SAMPLE = 0, VSORT_PATH_SINGLE = 1, VSORT_PATH_LIBRARY = 2 };
+inline int vsort_buckets(size_t n) { return int((n + VSORT_MEAN - 1) / VSORT_MEAN); }
+
 class VoxelGridDev {
  public:
+  // runs whose result came from the sample sort, from the direct one-launch sort, and from the library's sort (VoxSortPath order)
+  void sort_stats(unsigned long long out[3]) const { for (int k = 0; k < 3; ++k) out[k] = n_path_[k]; }
+  // the sort enqueue() runs, on caller-given host keys with values = positions (lio_vox_sort_pairs); returns the path that gave the result
+  int sort_pairs_hook(const uint32_t *keys, size_t n, uint32_t *keys_out, uint32_t *vals_out, hipStream_t s);
   // Filters `in` (device, n points) with cubic leaf; result in `out`; returns the output count (host sync).
   // host_params (optional) receives the bounds used.
   size_t run(const float4 *in, size_t n, float leaf, DBuf<float4> &out, hipStream_t s, VoxParams *host_params = nullptr);
@@ -55,8 +75,15 @@ class VoxelGridDev {
  private:
   const float4 *p_in_ = nullptr; size_t p_n_ = 0; DBuf<float4> *p_out_ = nullptr; hipStream_t p_stream_ = nullptr;  // the pending launch
   float p_leaf_ = 0.f;
-  void enqueue(bool exact);
-  HostBuf<char> h_mail_;            // pinned, coherent, allocated on first use
+  void enqueue(bool exact, bool library);
+  void reserve_sort(size_t n, hipStream_t s);
+  int enqueue_sort(size_t n, hipStream_t s, bool library);   // keys_ / vals_ -> keys2_ / vals2_; returns the VoxSortPath taken
+  DBuf<uint32_t> splitters_;
+  DBuf<int> fill_;
+  DBuf<unsigned long long> pairs_;  // NB bucket regions of VSORT_CAP pairs (key << 32 | index)
+  int last_path_ = VSORT_PATH_LIBRARY;
+  unsigned long long n_path_[3] = {0, 0, 0};
+  HostBuf<char> h_mail_;           // pinned, coherent, allocated on first use
   int *h_count_ = nullptr;          // ... its views: output count, followed by the VoxParams
   VoxParams *h_params_ = nullptr;
   DBuf<float> partial_;

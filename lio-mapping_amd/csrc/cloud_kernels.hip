@@ -159,6 +159,106 @@ __global__ void __launch_bounds__(VOX_TILE) k_vox_keys_abs(const float4 *__restr
   vox_block_partial(mn, mx, cnt, partial + size_t(blockIdx.x) * 8);
 }
 
+// ---- the sort between the keys and the tile heads (cloud_kernels.h: sizing rule; docs/voxel_sort.md).  The values are the points' own
+// indices, so the stable sort by key IS the sort by the 64-bit pair (key, index): any correct sort of the pairs gives the library's
+// keys2_ / vals2_ bit for bit, whatever order the atomics of the scatter hand out.  No kernel waits for another workgroup.
+// 1: splitters from a sample of this call's keys; the fill counters and the overflow word go back to zero here (no fill command per run)
+__global__ void __launch_bounds__(VSORT_THREADS) k_vsort_splitters(const uint32_t *__restrict__ keys, int n, int NB, uint32_t *__restrict__ splitters,
+                                                                  int *__restrict__ fill, int *__restrict__ overflow) {
+  __shared__ __attribute__((aligned(16))) uint32_t ss[VSORT_OVERSAMPLE * VSORT_MAX_BUCKETS];
+  if (blockIdx.x == 0) {
+    for (int b = threadIdx.x; b < NB; b += VSORT_THREADS) fill[b] = 0;
+    if (threadIdx.x == 0) *overflow = 0;
+  }
+  vsort_pick_splitters<VSORT_OVERSAMPLE>(keys, n, NB, ss, splitters);
+}
+
+// 2: every point into its bucket's region of VSORT_CAP pairs; one global atomic per (workgroup, non-empty bucket) reserves the room
+__global__ void __launch_bounds__(VSORT_SCATTER_THREADS) k_vsort_scatter(const uint32_t *__restrict__ keys, int n, int NB,
+                                                                        const uint32_t *__restrict__ splitters, int *__restrict__ fill,
+                                                                        unsigned long long *__restrict__ pairs, int *__restrict__ overflow) {
+  __shared__ uint32_t sspl[VSORT_MAX_BUCKETS];
+  __shared__ int scnt[VSORT_MAX_BUCKETS], sbase[VSORT_MAX_BUCKETS];
+  const int tid = threadIdx.x;
+  for (int b = tid; b < NB; b += VSORT_SCATTER_THREADS) { scnt[b] = 0; if (b < NB - 1) sspl[b] = splitters[b]; }
+  __syncthreads();
+  uint32_t key[VSORT_SCATTER_ITEMS];
+  int bucket[VSORT_SCATTER_ITEMS], rank[VSORT_SCATTER_ITEMS];
+#pragma unroll
+  for (int r = 0; r < VSORT_SCATTER_ITEMS; ++r) {
+    const int i = (blockIdx.x * VSORT_SCATTER_ITEMS + r) * VSORT_SCATTER_THREADS + tid;
+    bucket[r] = -1;
+    if (i < n) {
+      key[r] = keys[i];
+      bucket[r] = vsort_bucket_of(sspl, NB, key[r]);
+      rank[r] = atomicAdd(&scnt[bucket[r]], 1);
+    }
+  }
+  __syncthreads();
+  for (int b = tid; b < NB; b += VSORT_SCATTER_THREADS) {
+    const int c = scnt[b];
+    if (c > 0) sbase[b] = atomicAdd(&fill[b], c);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < VSORT_SCATTER_ITEMS; ++r) {
+    if (bucket[r] < 0) continue;
+    const int i = (blockIdx.x * VSORT_SCATTER_ITEMS + r) * VSORT_SCATTER_THREADS + tid;
+    const int pos = sbase[bucket[r]] + rank[r];
+    if (pos < VSORT_CAP) pairs[size_t(bucket[r]) * VSORT_CAP + pos] = (static_cast<unsigned long long>(key[r]) << 32) | uint32_t(i);
+    else *overflow = 1;   // nothing is written beyond the capacity; finish() redoes the filter with the library sort
+  }
+}
+
+// 3: workgroup b sorts bucket b (registers; LDS for the strides that cross waves) and writes it behind the buckets before it
+__global__ void __launch_bounds__(VSORT_THREADS) k_vsort_buckets(const unsigned long long *__restrict__ pairs, const int *__restrict__ fill, int NB, int n,
+                                                                const int *__restrict__ overflow, uint32_t *__restrict__ keys_out,
+                                                                uint32_t *__restrict__ vals_out) {
+  __shared__ unsigned long long sp[VSORT_CAP];
+  __shared__ int swave[VSORT_THREADS / 64];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  if (*overflow) {
+    // the run is going to be redone: leave "no point" everywhere, so that the kernels behind gather through no stale index
+    const int chunk = (n + NB - 1) / NB;
+    for (int i = b * chunk + tid; i < min(n, (b + 1) * chunk); i += VSORT_THREADS) keys_out[i] = VOX_KEY_NONE;
+    return;
+  }
+  int before = 0;
+  for (int j = tid; j < b; j += VSORT_THREADS) before += min(fill[j], VSORT_CAP);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) before += __shfl_xor(before, o, 64);
+  if ((tid & 63) == 0) swave[tid >> 6] = before;
+  const int m = min(fill[b], VSORT_CAP);
+  __syncthreads();
+  int off = 0;
+#pragma unroll
+  for (int w = 0; w < VSORT_THREADS / 64; ++w) off += swave[w];
+  const unsigned long long *src = pairs + size_t(b) * VSORT_CAP;
+  switch (vsort_items_for(m)) {   // uniform over the block
+    case 1: vsort_pairs_sort_store<1>(src, m, sp, keys_out, vals_out, off); break;
+    case 2: vsort_pairs_sort_store<2>(src, m, sp, keys_out, vals_out, off); break;
+    case 4: vsort_pairs_sort_store<4>(src, m, sp, keys_out, vals_out, off); break;
+    case 8: vsort_pairs_sort_store<8>(src, m, sp, keys_out, vals_out, off); break;
+    default: vsort_pairs_sort_store<16>(src, m, sp, keys_out, vals_out, off); break;
+  }
+}
+
+// n <= VSORT_CAP: the keys are sorted directly, in one launch, by rank: every workgroup holds all keys in LDS and counts, for
+// VSORT_THREADS / VSORT_RANK_LANES of them, the pairs (key, index) below; that count is the pair's place.  (One workgroup sorting 2048 pairs
+// by the bitonic network of k_vsort_buckets took 20 us, then 11: 66 steps on one compute unit.)
+__global__ void __launch_bounds__(VSORT_THREADS) k_vsort_single(const uint32_t *__restrict__ keys, int n, int *__restrict__ overflow,
+                                                               uint32_t *__restrict__ keys_out, uint32_t *__restrict__ vals_out) {
+  __shared__ __attribute__((aligned(16))) uint32_t ss[VSORT_CAP];
+  if (blockIdx.x == 0 && threadIdx.x == 0) *overflow = 0;
+  const int S = (n + 3) & ~3;   // fillers behind the keys: equal to "no point", but with indices behind every key's
+  for (int t = threadIdx.x; t < S; t += VSORT_THREADS) ss[t] = t < n ? keys[t] : VOX_KEY_NONE;
+  __syncthreads();
+  const int i = blockIdx.x * (VSORT_THREADS / VSORT_RANK_LANES) + int(threadIdx.x) / VSORT_RANK_LANES, part = int(threadIdx.x) % VSORT_RANK_LANES;
+  const unsigned long long mine = i < n ? (static_cast<unsigned long long>(ss[i]) << 32) | uint32_t(i) : 0ull;
+  const int rank = vsort_rank_of(ss, S, part, mine);
+  if (part == 0 && i < n) { keys_out[rank] = uint32_t(mine >> 32); vals_out[rank] = uint32_t(i); }
+}
+
 // heads (first entry of a run of equal keys) in each VOX_TILE-entry tile of the sorted keys
 __global__ void __launch_bounds__(VOX_TILE) k_vox_tile_heads(const uint32_t *__restrict__ keys, int n, int *__restrict__ tile_heads,
                                                              const float *__restrict__ partial, int npartial, float inv_leaf, VoxParams *__restrict__ params) {
@@ -174,11 +274,12 @@ __global__ void __launch_bounds__(VOX_TILE) k_vox_tile_heads(const uint32_t *__r
 
 // Centroids of the sorted runs (cloud_device.h: vox_centroid_tile).  The last tile's block knows the total and posts it (with the
 // bounds) to the host's mailbox.
-struct VoxMail { int count; VoxParams params; int range_overflow; };
+struct VoxMail { int count; VoxParams params; int range_overflow; int sort_overflow; };
 __global__ void __launch_bounds__(VOX_TILE) k_vox_centroids(const float4 *__restrict__ pts, const uint32_t *__restrict__ keys,
                                                             const uint32_t *__restrict__ vals, const int *__restrict__ tile_heads, int n,
                                                             float4 *__restrict__ out, int *__restrict__ count, const VoxParams *__restrict__ params,
-                                                            int *__restrict__ range_overflow, VoxMail *mail, HostSignal sig) {
+                                                            int *__restrict__ range_overflow, const int *__restrict__ sort_overflow, VoxMail *mail,
+                                                            HostSignal sig) {
   const VoxSlot r = vox_centroid_tile(pts, keys, vals, tile_heads, n, blockIdx.x, out);
   if (blockIdx.x == gridDim.x - 1) {   // the last tile knows the total
     __shared__ VoxMail smail;
@@ -186,7 +287,7 @@ __global__ void __launch_bounds__(VOX_TILE) k_vox_centroids(const float4 *__rest
     if (tid == VOX_TILE - 1) {
       const int total = r.pos + (r.head ? 1 : 0);
       *count = total;
-      smail.count = total; smail.params = *params; smail.range_overflow = *range_overflow;
+      smail.count = total; smail.params = *params; smail.range_overflow = *range_overflow; smail.sort_overflow = *sort_overflow;
       if (sig.flag) *range_overflow = 0;   // the mail carries it: leave the flag clear for the next run (no fill command in front of it)
     }
     if (sig.flag) {
@@ -209,12 +310,13 @@ void launch_cloud_bounds(const float4 *pts, int n, DBuf<float> &partial, VoxPara
 void VoxelGridDev::launch(const float4 *in, size_t n, float leaf, DBuf<float4> &out, hipStream_t s) {
   p_in_ = in; p_n_ = n; p_out_ = &out; p_stream_ = s; p_leaf_ = leaf;
   if (n == 0) return;
-  enqueue(false);
+  enqueue(false, false);
 }
 
 // exact == false: absolute-cell keys, bounds folded on the side (4 stages: keys, sort, tile heads, centroids);
 // exact == true: PCL's own index from the bounds (two more launches in front), used when the cloud leaves the key's range.
-void VoxelGridDev::enqueue(bool exact) {
+// library == true: the sort is the library's (a bucket of the sample sort overflowed).
+void VoxelGridDev::enqueue(bool exact, bool library) {
   const float4 *in = p_in_;
   const size_t n = p_n_;
   DBuf<float4> &out = *p_out_;
@@ -224,8 +326,7 @@ void VoxelGridDev::enqueue(bool exact) {
   const int nkb = cdiv(ni, VOX_TILE);
   partial_.reserve(size_t(std::max(nkb, 512)) * 8);
   params_.reserve(1);
-  keys_.reserve(n); keys2_.reserve(n); vals_.reserve(n); vals2_.reserve(n);
-  if (count_.cap < 2) { count_.reserve(2); LIO_HIP(hipMemsetAsync(count_.p, 0, count_.cap * sizeof(int), s)); }
+  reserve_sort(n, s);
   out.reserve(n);
   if (!h_count_) {
     // coherent pinned memory: k_vox_centroids posts the count, the bounds and the range flag here (VoxMail), then the completion word
@@ -247,10 +348,7 @@ void VoxelGridDev::enqueue(bool exact) {
     hipLaunchKernelGGL(k_vox_keys_abs, dim3(nkb), dim3(VOX_TILE), 0, s, in, ni, inv_leaf, keys_.p, vals_.p, partial_.p, d_range);
     npartial = nkb;
   }
-  size_t tmp_bytes = 0;
-  LIO_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys_.p, keys2_.p, vals_.p, vals2_.p, n, 0, 32, s));
-  tmp_.reserve(tmp_bytes + 256);
-  LIO_HIP(rocprim::radix_sort_pairs(tmp_.p, tmp_bytes, keys_.p, keys2_.p, vals_.p, vals2_.p, n, 0, 32, s));
+  last_path_ = enqueue_sort(n, s, library);
   const int ntiles = cdiv(ni, VOX_TILE);
   tile_heads_.reserve(ntiles);
   hipLaunchKernelGGL(k_vox_tile_heads, dim3(ntiles + 1), dim3(VOX_TILE), 0, s, keys2_.p, ni, tile_heads_.p, partial_.p, npartial, inv_leaf, params_.p);
@@ -258,14 +356,64 @@ void VoxelGridDev::enqueue(bool exact) {
   if (use_signal_) { sig_.flag = h_flag_; sig_.seq = ++seq_; }
 
   hipLaunchKernelGGL(k_vox_centroids, dim3(ntiles), dim3(VOX_TILE), 0, s, in, keys2_.p, vals2_.p, tile_heads_.p, ni, out.p, count_.p, params_.p, d_range,
-                     reinterpret_cast<VoxMail *>(h_count_), sig_);
+                     count_.p + 2, reinterpret_cast<VoxMail *>(h_count_), sig_);
   LIO_HIP(hipGetLastError());
   if (!sig_.flag) {
     VoxMail *m = reinterpret_cast<VoxMail *>(h_count_);
     LIO_HIP(hipMemcpyAsync(&m->count, count_.p, sizeof(int), hipMemcpyDeviceToHost, s));
     LIO_HIP(hipMemcpyAsync(&m->params, params_.p, sizeof(VoxParams), hipMemcpyDeviceToHost, s));
     LIO_HIP(hipMemcpyAsync(&m->range_overflow, d_range, sizeof(int), hipMemcpyDeviceToHost, s));
+    LIO_HIP(hipMemcpyAsync(&m->sort_overflow, count_.p + 2, sizeof(int), hipMemcpyDeviceToHost, s));
   }
+}
+
+// count_: [0] the output count, [1] the range flag, [2] the sort's overflow word (put back to zero by whichever sort runs)
+void VoxelGridDev::reserve_sort(size_t n, hipStream_t s) {
+  keys_.reserve(n); keys2_.reserve(n); vals_.reserve(n); vals2_.reserve(n);
+  if (count_.cap < 3) { count_.reserve(3); LIO_HIP(hipMemsetAsync(count_.p, 0, count_.cap * sizeof(int), s)); }
+}
+
+int VoxelGridDev::enqueue_sort(size_t n, hipStream_t s, bool library) {
+  const int ni = int(n);
+  int *d_overflow = count_.p + 2;
+  if (library || n > size_t(VSORT_MAX_N)) {
+    LIO_HIP(hipMemsetAsync(d_overflow, 0, sizeof(int), s));
+    size_t tmp_bytes = 0;
+    LIO_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys_.p, keys2_.p, vals_.p, vals2_.p, n, 0, 32, s));
+    tmp_.reserve(tmp_bytes + 256);
+    LIO_HIP(rocprim::radix_sort_pairs(tmp_.p, tmp_bytes, keys_.p, keys2_.p, vals_.p, vals2_.p, n, 0, 32, s));
+    return VSORT_PATH_LIBRARY;
+  }
+  if (ni <= VSORT_CAP) {
+    hipLaunchKernelGGL(k_vsort_single, dim3(cdiv(ni, VSORT_THREADS / VSORT_RANK_LANES)), dim3(VSORT_THREADS), 0, s, keys_.p, ni, d_overflow, keys2_.p, vals2_.p);
+    return VSORT_PATH_SINGLE;
+  }
+  const int NB = vsort_buckets(n);
+  splitters_.reserve(NB); fill_.reserve(NB); pairs_.reserve(size_t(NB) * VSORT_CAP);
+  hipLaunchKernelGGL(k_vsort_splitters, dim3(cdiv(VSORT_OVERSAMPLE * NB, VSORT_THREADS / VSORT_RANK_LANES)), dim3(VSORT_THREADS), 0, s, keys_.p, ni, NB,
+                     splitters_.p, fill_.p, d_overflow);
+  hipLaunchKernelGGL(k_vsort_scatter, dim3(cdiv(ni, VSORT_SCATTER_THREADS * VSORT_SCATTER_ITEMS)), dim3(VSORT_SCATTER_THREADS), 0, s, keys_.p, ni, NB,
+                     splitters_.p, fill_.p, pairs_.p, d_overflow);
+  hipLaunchKernelGGL(k_vsort_buckets, dim3(NB), dim3(VSORT_THREADS), 0, s, pairs_.p, fill_.p, NB, ni, d_overflow, keys2_.p, vals2_.p);
+  return VSORT_PATH_SAMPLE;
+}
+
+int VoxelGridDev::sort_pairs_hook(const uint32_t *keys, size_t n, uint32_t *keys_out, uint32_t *vals_out, hipStream_t s) {
+  reserve_sort(n, s);
+  std::vector<uint32_t> iota(n);
+  for (size_t i = 0; i < n; ++i) iota[i] = uint32_t(i);
+  LIO_HIP(hipMemcpyAsync(keys_.p, keys, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  LIO_HIP(hipMemcpyAsync(vals_.p, iota.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  int path = enqueue_sort(n, s, false);
+  LIO_HIP(hipGetLastError());
+  int overflow = 0;
+  LIO_HIP(hipMemcpyAsync(&overflow, count_.p + 2, sizeof(int), hipMemcpyDeviceToHost, s));
+  LIO_HIP(hipStreamSynchronize(s));
+  if (overflow) path = enqueue_sort(n, s, true);   // what finish() does on the mail's word
+  LIO_HIP(hipMemcpyAsync(keys_out, keys2_.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  LIO_HIP(hipMemcpyAsync(vals_out, vals2_.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  LIO_HIP(hipStreamSynchronize(s));
+  return path;
 }
 
 size_t VoxelGridDev::finish(VoxParams *host_params) {
@@ -274,12 +422,19 @@ size_t VoxelGridDev::finish(VoxParams *host_params) {
     return 0;
   }
   const VoxMail *m = reinterpret_cast<const VoxMail *>(h_count_);
-  bool redone = false;
+  bool redone = false, exact = false, library = false;
   for (;;) {
     if (sig_.flag) wait_host_signal(sig_, p_stream_);   // the count is out; the centroids follow in stream order
     else LIO_HIP(hipStreamSynchronize(p_stream_));
-    if (m->range_overflow == 1 && !redone) {
-      enqueue(true);   // the cloud spans more cells than the absolute key holds
+    if (m->range_overflow == 1 && !exact) {
+      exact = true;   // the cloud spans more cells than the absolute key holds
+      enqueue(exact, library);
+      redone = true;
+      continue;
+    }
+    if (m->sort_overflow == 1 && !library) {
+      library = true;   // a bucket of the sample sort was full: its keys2_ / vals2_ are not the sort
+      enqueue(exact, library);
       redone = true;
       continue;
     }
@@ -288,6 +443,7 @@ size_t VoxelGridDev::finish(VoxParams *host_params) {
     if (redone) LIO_HIP(hipStreamSynchronize(p_stream_));
     break;
   }
+  ++n_path_[last_path_];
   int count = m->count;
   const VoxParams hp = m->params;
   if (hp.overflow) {  // PCL: "Leaf size is too small for the input dataset" -> output = input

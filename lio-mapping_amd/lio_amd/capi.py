@@ -322,6 +322,14 @@ _MAP_BATCH_SIGS = {
                                         C.POINTER(TransformF), c_int32_p, c_int32_p]),
 }
 MAP_BATCH_MAX_SENSORS = 1024   # LIO_MAP_BATCH_MAX_SENSORS
+# include/lio_vox_sort.h: the voxel filter's sort on caller-given keys and the counters of the paths it took (the product only, attached like _EXT_SIGS)
+_c_uint32_p = C.POINTER(C.c_uint32)
+_VOX_SORT_SIGS = {
+    "lio_vox_sort_pairs": (C.c_int, [_c_uint32_p, C.c_size_t, _c_uint32_p, _c_uint32_p, C.POINTER(C.c_int)]),
+    "lio_vox_sort_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
+}
+VOX_SORT_SAMPLE, VOX_SORT_SINGLE, VOX_SORT_LIBRARY = 0, 1, 2   # LIO_VOX_SORT_* paths
+VOX_SORT_SINGLE_MAX, VOX_SORT_BUCKET_CAP, VOX_SORT_MEAN_BUCKET, VOX_SORT_OVERSAMPLE = 4096, 4096, 384, 8   # the sizing rule of the header
 
 
 def _dp(a):
@@ -377,6 +385,12 @@ class LioLib:
                 fn = getattr(self.dll, name)
                 fn.restype = res
                 fn.argtypes = args
+            # a build from before the sample sort still loads (the A/B tools take one as --parent-lib); only a call to these fails there
+            for name, (res, args) in _VOX_SORT_SIGS.items():
+                fn = getattr(self.dll, name, None)
+                if fn is not None:
+                    fn.restype = res
+                    fn.argtypes = args
 
     def deskew_to_end(self, xyzi, T_es: TransformF, time_factor=10.0, keep_intensity=False):
         """lio_deskew_to_end (include/lio_full_cloud.h, test hook): the estimator's TransformToEnd, Estimator.cc:62-103."""
@@ -450,6 +464,20 @@ class LioLib:
                                          so.ctypes.data_as(c_int32_p), sn.ctypes.data_as(c_int32_p), so.shape[0], int(bits), int(passes),
                                          ko.ctypes.data_as(u32), vo.ctypes.data_as(u32)), "lio_seg_sort_pairs")
         return ko, vo
+
+    def vox_sort_pairs(self, keys):
+        """lio_vox_sort_pairs (include/lio_vox_sort.h): the voxel filter's sort of (key, position) -> (sorted keys, their positions, LIO_VOX_SORT_* path)"""
+        k = np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1)
+        ko, vo, path = np.zeros_like(k), np.zeros_like(k), C.c_int(-1)
+        _chk(self.dll.lio_vox_sort_pairs(k.ctypes.data_as(_c_uint32_p), k.size, ko.ctypes.data_as(_c_uint32_p), vo.ctypes.data_as(_c_uint32_p),
+                                         C.byref(path)), "lio_vox_sort_pairs")
+        return ko, vo, path.value
+
+    def vox_sort_stats(self):
+        """lio_vox_sort_stats: lio_voxel_grid runs of this thread by the sort that gave their result (sample, direct, library)"""
+        out = (C.c_uint64 * 3)()
+        _chk(self.dll.lio_vox_sort_stats(out), "lio_vox_sort_stats")
+        return tuple(int(v) for v in out)
 
     def voxel_grid(self, xyzi, leaf):
         xyzi = _f32(xyzi).reshape(-1, 4)
