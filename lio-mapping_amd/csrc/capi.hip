@@ -13,6 +13,7 @@
 #include "../../include/lio_frontend_batch.h"
 #include "../../include/lio_map_batch.h"
 #include "../../include/lio_vox_sort.h"
+#include "../../include/lio_seg_bounds.h"
 #include "est_batch.h"
 #include "seg_sort.h"
 #include "estimator.h"
@@ -687,6 +688,31 @@ int lio_vox_sort_stats(uint64_t out[3]) {
     unsigned long long c[3];
     scratch().vox.sort_stats(c);
     for (int k = 0; k < 3; ++k) out[k] = c[k];
+    return LIO_OK;
+  });
+}
+
+// include/lio_seg_bounds.h
+static_assert(sizeof(lio_seg_bounds_out) == sizeof(VoxParams) && offsetof(lio_seg_bounds_out, minb) == offsetof(VoxParams, minb) &&
+              offsetof(lio_seg_bounds_out, n_valid) == offsetof(VoxParams, n_valid), "the header states VoxParams");
+int lio_seg_bounds(const float *const *xyzi, const size_t *n, int nseg, float inv_leaf, lio_seg_bounds_out *out) {
+  if (!xyzi || !n || nseg < 1 || !(inv_leaf > 0) || !out) return LIO_ERR_ARG;
+  for (int k = 0; k < nseg; ++k) {
+    if (!xyzi[k] && n[k]) return LIO_ERR_ARG;
+    if (n[k] >= size_t(INT_MAX)) return LIO_ERR_CAPACITY;
+  }
+  return guarded([&] {
+    hipStream_t s = scratch().s;
+    std::vector<DBuf<float4>> clouds(static_cast<size_t>(nseg));
+    GridBatch gb;
+    gb.begin(0, nseg);
+    for (int k = 0; k < nseg; ++k) {
+      DBuf<float4> &c = clouds[size_t(k)];
+      c.reserve(std::max<size_t>(n[k], 1));
+      if (n[k]) LIO_HIP(hipMemcpyAsync(c.p, xyzi[k], n[k] * sizeof(float4), hipMemcpyHostToDevice, s));
+      gb.add(c.p, int(n[k]));
+    }
+    std::memcpy(out, gb.bounds(s, inv_leaf), size_t(nseg) * sizeof(VoxParams));
     return LIO_OK;
   });
 }

@@ -60,7 +60,7 @@ __device__ __forceinline__ uint32_t cell_key_clamped(const float4 &p, const Grid
 }
 
 // The counting sort by cell of KnnGrid::build, per point, stated once for a grid built alone (k_cell_count, k_cell_place) and for the grids
-// of a batch built side by side (odometry.hip: k_ob_cell_count, k_ob_cell_place).  Point i takes a slot inside its cell ...
+// of a batch built side by side (GridBatch: k_seg_cell_count, k_seg_cell_place).  Point i takes a slot inside its cell ...
 __device__ __forceinline__ void cell_count_point(const float4 *__restrict__ pts, int i, const GridDesc &g, uint32_t *__restrict__ keys,
                                                  uint32_t *__restrict__ slot, int *__restrict__ cnt) {
   const uint32_t c = cell_key_clamped(pts[i], g);
@@ -145,6 +145,20 @@ __device__ __forceinline__ void vox_block_partial(float (&mn)[3], float (&mx)[3]
     for (int w = 1; w < VOX_TILE / 64; ++w) v = t < 3 ? fminf(v, sm[t][w]) : (t < 6 ? fmaxf(v, sm[t][w]) : v + sm[t][w]);
     row[t] = v;
   }
+}
+// The bounds pass of a cloud, per block: block `block` of the cloud's `nb` (cloud_bounds_blocks) takes the finite points of pts[0, n) at the
+// stride nb * VOX_TILE -> row[0 .. 6].  Stated once for every cloud whose bounds are asked for on their own (k_seg_bounds, k_cloud_bounds).
+__device__ __forceinline__ void cloud_bounds_block(const float4 *__restrict__ pts, int n, int block, int nb, float *__restrict__ row) {
+  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+  float cnt = 0;
+  for (int i = block * VOX_TILE + threadIdx.x; i < n; i += nb * VOX_TILE) {
+    const float4 p = pts[i];
+    if (!finite3(p)) continue;
+    cnt += 1.f;
+    mn[0] = fminf(mn[0], p.x); mn[1] = fminf(mn[1], p.y); mn[2] = fminf(mn[2], p.z);
+    mx[0] = fmaxf(mx[0], p.x); mx[1] = fmaxf(mx[1], p.y); mx[2] = fmaxf(mx[2], p.z);
+  }
+  vox_block_partial(mn, mx, cnt, row);
 }
 
 // `nb` rows of partials (eight floats each) folded by a VOX_TILE-thread block into the cloud's VoxParams: min, max, PCL's cell bounds and its

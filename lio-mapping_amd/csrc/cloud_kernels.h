@@ -5,6 +5,7 @@
 //   laser-odom rows/update      : Estimator::CalculateLaserOdom (Estimator.cc:1242-1359)
 //   deskew                      : TransformToEnd (Estimator.cc:62-103)
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 
@@ -35,8 +36,13 @@ void launch_deskew_to_end(float4 *pts, int n, const float q[4], const float p[3]
 // out = rot * in + pos, intensity kept (PointAssociateToMap, PointMapping.cc:303-314); out of place
 void launch_rigid_map(const float4 *in, int n, const float q[4], const float p[3], float4 *out, hipStream_t s);
 
-// min/max (VoxParams.mn/.mx, n_valid) of a device cloud; `partial` is scratch.  No host sync.
-void launch_cloud_bounds(const float4 *pts, int n, DBuf<float> &partial, VoxParams *d_out, hipStream_t s);
+// The bounds pass (VoxParams) of device clouds, side by side.  A cloud of n points is reduced by cloud_bounds_blocks(n) blocks of 256 threads into
+// rows of eight floats (cloud_device.h: cloud_bounds_block), which one more block folds (vox_fold_bounds).  Minimum and maximum do not hang
+// on the order and the count is a float sum of integers below 2^24, so a cloud has the same VoxParams alone and in any batch.
+inline int cloud_bounds_blocks(int n) { return std::max(1, std::min(cdiv(n, 256), 512)); }
+struct BoundsSeg { const float4 *pts; int n, nb, off; };   // a cloud, its blocks, its first row of `partial`
+// d_segs: nseg records on the device; grid (max_nb, nseg), the blocks beyond a cloud's nb leave at once; d_out[k] = cloud k's.  No host sync.
+void launch_seg_bounds(const BoundsSeg *d_segs, int nseg, int max_nb, float *partial, float inv_leaf, VoxParams *d_out, hipStream_t s);
 
 // The filter's sort of the n (key, index) pairs: a sample sort in three launches (splitters, bucket scatter, bucket sort + compaction).
 // Sizing, a pure function of n:
@@ -149,8 +155,52 @@ class KnnGrid {
   DBuf<uint32_t> keys_, keys2_, vals_, vals2_;
   DBuf<float4> sorted_;
   DBuf<int> cells_, cnt_;
-  bool cnt_dirty_ = false;   // k_cell_count ran, k_cell_place (which re-zeroes cnt_) did not
+  // The count table's invariant (GridBatch's too): all zeros between builds.  A fresh table is filled once; after that every point's place
+  // kernel puts its cell's count back, so a build needs no fill command.  dirty: a count kernel was enqueued and its place kernel was not (a
+  // build that threw in between) — the next build fills the table again.
+  bool cnt_dirty_ = false;
   DBuf<char> tmp_;
+};
+
+// The grids of a call's clouds, built side by side: the bounds pass above over all of them (two launches, one read-back, one wait), the layout
+// on the host, then KnnGrid::build's counting sort (cell_count_point, block_exclusive_scan, cell_place_point) in three launches over all of
+// them.  Every grid has its slice of one count table and one cell table, and its run starts are offsets into ONE sorted array.  The records the
+// kernels read lie behind the caller's own records (`head`) in one staging table: the bounds pass uploads the BoundsSeg records alone, the
+// build the head and the GridSeg records in one copy.
+struct GridSeg { const float4 *pts; GridDesc g; int pt_off, cell_off, ncells; };   // pt_off < 0: not built here
+class GridBatch {
+ public:
+  // a call: room for head_bytes (a multiple of 8) of the caller's records and for `clouds` clouds; returns the caller's part, zeroed
+  void *begin(size_t head_bytes, int clouds);
+  const void *head_dev() const { return d_tab_.p; }
+  void add(const float4 *pts, int n);
+  // upload of the clouds' BoundsSeg records, the two launches, one read-back, one wait: cloud i's bounds at [i]
+  const VoxParams *bounds(hipStream_t s, float inv_leaf = 1.0f);
+  // the grids over the bounds (a cloud without a finite point: over the origin) at the given cell edge, and their slices; a grid of more than
+  // cells_cap cells gets none (shared(i) false: the caller builds it with a KnnGrid of its own, with desc(i))
+  void layout(float cell, size_t cells_cap);
+  bool shared(int i) const { return gseg(i).pt_off >= 0; }
+  const GridDesc &desc(int i) const { return gseg(i).g; }
+  const float4 *sorted(int) const { return sorted_.p; }
+  const int *cells(int i) const { return cells_.p + gseg(i).cell_off; }
+  // upload of the head as the caller left it and the GridSeg records, then count, scan and place of the shared grids
+  void build(hipStream_t s);
+
+ private:
+  BoundsSeg *bseg() { return reinterpret_cast<BoundsSeg *>(h_tab_.data() + off_b_); }
+  GridSeg &gseg(int i) const { return reinterpret_cast<GridSeg *>(const_cast<char *>(h_tab_.data()) + off_g_)[i]; }
+  std::vector<char> h_tab_;   // head | GridSeg x clouds | BoundsSeg x clouds
+  DBuf<char> d_tab_;
+  size_t off_b_ = 0, off_g_ = 0, part_total_ = 0;
+  int n_ = 0, max_nb_ = 0, max_pts_ = 0;
+  bool any_shared_ = false;
+  DBuf<float> partial_;
+  DBuf<VoxParams> d_bounds_;
+  HostBuf<VoxParams> h_bounds_;   // pinned landing zone
+  DBuf<uint32_t> keys_, slot_;
+  DBuf<int> cnt_, cells_;
+  DBuf<float4> sorted_;
+  bool cnt_dirty_ = false;        // (KnnGrid: the count table's invariant)
 };
 
 // order (optional): the queries are PROCESSED in this order — order[t] = slot (slot_off + index into stack) of the t-th query — so that the lanes
@@ -218,6 +268,38 @@ inline void point_on_z_axis(const Rigid<float> &T, float pz[3]) {
   const Vec3<float> z = rotate(T.rot, Vec3<float>(0.f, 0.f, 10.f));
   pz[0] = z.x + T.pos.x; pz[1] = z.y + T.pos.y; pz[2] = z.z + T.pos.z;
 }
+// The states of n sensors posted by one launch (one block each, state_mail_slot + post_host_mail) and the completion words behind them, in
+// pinned coherent memory: STATE_MAIL_STRIDE bytes per slot, then one word per slot (dev.h: HostSignal).
+class StateMail {
+ public:
+  // room for n sensors, zeroed when it grows (by half).  Only between calls: the stream is idle, nobody still posts to the old memory
+  void reserve(int n) {
+    if (cap_ >= size_t(n)) return;
+    cap_ = size_t(n) + size_t(n) / 2;
+    buf_.alloc(cap_ * (STATE_MAIL_STRIDE + sizeof(unsigned)), hipHostMallocCoherent, true);
+  }
+  char *base() const { return buf_.p; }
+  OdomState &slot(int j) const { return *reinterpret_cast<OdomState *>(buf_.p + size_t(j) * STATE_MAIL_STRIDE); }
+  // the signal of the next launch that posts n states
+  const HostSignal &arm(int n) {
+    sig_.flag = reinterpret_cast<unsigned *>(buf_.p + cap_ * STATE_MAIL_STRIDE); sig_.seq = ++seq_; sig_.nslots = n;
+    return sig_;
+  }
+  void wait(hipStream_t s) const { wait_host_signal(sig_, s); }   // for the last armed launch
+  bool all_converged(int n) const {
+    bool all = true;
+    for (int j = 0; j < n; ++j) all = all && slot(j).converged;
+    return all;
+  }
+
+ private:
+  HostBuf<char> buf_;
+  size_t cap_ = 0;
+  unsigned seq_ = 0;
+  HostSignal sig_{};
+};
+static_assert(sizeof(OdomState) <= STATE_MAIL_STRIDE, "mailbox layout");
+
 // blocks of a row reduction over nslots slots (28 doubles of partials each)
 int odom_rows_blocks(int nslots);
 // One round of the newest frame's loop in two launches (search + plane fit + rows per block; fold + update).  a.fr[0] names the
@@ -272,9 +354,8 @@ void launch_kf_round(const KfDesc *kd, const KfMapDesc *md, const OdomState *st,
 void launch_kf_rows(const KfDesc *kd, const OdomState *st, int n_keyframes, int max_nb, const float4 *stack_all, const uint8_t *valid, const float4 *coef,
                     double *partials, int b_from_coef, hipStream_t s);
 // n_converged (device int, optional) is incremented once per keyframe when it converges.  sig.flag != nullptr: behind the update block k posts
-// keyframe k's state to its own slot of the host's mailbox (`mail` + k * KF_MAIL_STRIDE) and then sig.seq to its own completion word
-// sig.flag + k, converged before this launch or not; the host waits with sig.nslots = n_keyframes (dev.h: HostSignal)
-#define KF_MAIL_STRIDE 64   // bytes per keyframe in the mailbox
+// keyframe k's state to its own slot of the host's mailbox (StateMail::base(), armed for n_keyframes) and then sig.seq to its own completion
+// word, converged before this launch or not
 void launch_kf_update(const KfDesc *kd, OdomState *st, int n_keyframes, const double *partials, int iter, int min_rows, int left_update, int *n_converged,
                       char *mail, const HostSignal &sig, hipStream_t s);
 

@@ -88,32 +88,29 @@ void launch_rigid_map(const float4 *in, int n, const float q[4], const float p[3
 // ------------------------------------------------------------------------------------------------
 // voxel grid
 // ------------------------------------------------------------------------------------------------
-__global__ void k_bounds_partial(const float4 *__restrict__ pts, int n, float *__restrict__ partial) {
-  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-  int cnt = 0;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    float4 p = pts[i];
-    if (!finite3(p)) continue;
-    ++cnt;
-    mn[0] = fminf(mn[0], p.x); mn[1] = fminf(mn[1], p.y); mn[2] = fminf(mn[2], p.z);
-    mx[0] = fmaxf(mx[0], p.x); mx[1] = fmaxf(mx[1], p.y); mx[2] = fmaxf(mx[2], p.z);
-  }
-  __shared__ float sm[7][256];
-  int t = threadIdx.x;
-  for (int d = 0; d < 3; ++d) { sm[d][t] = mn[d]; sm[3 + d][t] = mx[d]; }
-  sm[6][t] = float(cnt);
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if (t < st) {
-      for (int d = 0; d < 3; ++d) { sm[d][t] = fminf(sm[d][t], sm[d][t + st]); sm[3 + d][t] = fmaxf(sm[3 + d][t], sm[3 + d][t + st]); }
-      sm[6][t] += sm[6][t + st];
-    }
-    __syncthreads();
-  }
-  if (t < 7) partial[blockIdx.x * 8 + t] = sm[t][0];
+// The bounds pass (cloud_kernels.h).  grid (max nb, clouds): cloud blockIdx.y by its first nb blocks ...
+__global__ void __launch_bounds__(VOX_TILE) k_seg_bounds(const BoundsSeg *__restrict__ recs, float *__restrict__ partial) {
+  const BoundsSeg r = recs[blockIdx.y];
+  if (int(blockIdx.x) >= r.nb) return;
+  cloud_bounds_block(r.pts, r.n, blockIdx.x, r.nb, partial + (size_t(r.off) + blockIdx.x) * 8);
 }
-
-__global__ void __launch_bounds__(256) k_bounds_final(const float *__restrict__ partial, int nb, float inv_leaf, VoxParams *out) {
+// ... and one block per cloud
+__global__ void __launch_bounds__(VOX_TILE) k_seg_bounds_fold(const BoundsSeg *__restrict__ recs, const float *__restrict__ partial, float inv_leaf,
+                                                              VoxParams *__restrict__ out) {
+  const BoundsSeg r = recs[blockIdx.x];
+  VoxParams v;
+  if (vox_fold_bounds(partial + size_t(r.off) * 8, r.nb, inv_leaf, v)) out[blockIdx.x] = v;
+}
+void launch_seg_bounds(const BoundsSeg *d_segs, int nseg, int max_nb, float *partial, float inv_leaf, VoxParams *d_out, hipStream_t s) {
+  hipLaunchKernelGGL(k_seg_bounds, dim3(max_nb, nseg), dim3(VOX_TILE), 0, s, d_segs, partial);
+  hipLaunchKernelGGL(k_seg_bounds_fold, dim3(nseg), dim3(VOX_TILE), 0, s, d_segs, partial, inv_leaf, d_out);
+  LIO_HIP(hipGetLastError());
+}
+// The same pass over one cloud that the launch itself names (the filter's exact path: no record to upload): gridDim.x blocks, then one
+__global__ void __launch_bounds__(VOX_TILE) k_cloud_bounds(const float4 *__restrict__ pts, int n, float *__restrict__ partial) {
+  cloud_bounds_block(pts, n, blockIdx.x, gridDim.x, partial + size_t(blockIdx.x) * 8);
+}
+__global__ void __launch_bounds__(VOX_TILE) k_cloud_bounds_fold(const float *__restrict__ partial, int nb, float inv_leaf, VoxParams *out) {
   VoxParams v;
   if (vox_fold_bounds(partial, nb, inv_leaf, v)) *out = v;
 }
@@ -297,14 +294,6 @@ __global__ void __launch_bounds__(VOX_TILE) k_vox_centroids(const float4 *__rest
   }
 }
 
-void launch_cloud_bounds(const float4 *pts, int n, DBuf<float> &partial, VoxParams *d_out, hipStream_t s) {
-  const int nb = std::max(1, std::min(cdiv(n, 256), 512));
-  partial.reserve(size_t(nb) * 8);
-  hipLaunchKernelGGL(k_bounds_partial, dim3(nb), dim3(256), 0, s, pts, n, partial.p);
-  hipLaunchKernelGGL(k_bounds_final, dim3(1), dim3(256), 0, s, partial.p, nb, 1.0f, d_out);
-  LIO_HIP(hipGetLastError());
-}
-
 // launch() enqueues the whole filter on `s` (no host sync); finish() waits for it and returns the output count.  Two
 // filters launched on two streams overlap (the scan-to-map step filters its corner and surf stacks that way).
 void VoxelGridDev::launch(const float4 *in, size_t n, float leaf, DBuf<float4> &out, hipStream_t s) {
@@ -340,9 +329,9 @@ void VoxelGridDev::enqueue(bool exact, bool library) {
   if (!use_signal_) LIO_HIP(hipMemsetAsync(d_range, 0, sizeof(int), s));   // copy-back path: the host reads the flag behind the kernels, so they cannot clear it
   int npartial = 0;
   if (exact) {
-    const int nb = std::min(cdiv(ni, 256), 512);
-    hipLaunchKernelGGL(k_bounds_partial, dim3(nb), dim3(256), 0, s, in, ni, partial_.p);
-    hipLaunchKernelGGL(k_bounds_final, dim3(1), dim3(256), 0, s, partial_.p, nb, inv_leaf, params_.p);
+    const int nb = cloud_bounds_blocks(ni);
+    hipLaunchKernelGGL(k_cloud_bounds, dim3(nb), dim3(VOX_TILE), 0, s, in, ni, partial_.p);
+    hipLaunchKernelGGL(k_cloud_bounds_fold, dim3(1), dim3(VOX_TILE), 0, s, partial_.p, nb, inv_leaf, params_.p);
     hipLaunchKernelGGL(k_vox_keys, dim3(cdiv(ni, 256)), dim3(256), 0, s, in, ni, inv_leaf, params_.p, keys_.p, vals_.p);
   } else {
     hipLaunchKernelGGL(k_vox_keys_abs, dim3(nkb), dim3(VOX_TILE), 0, s, in, ni, inv_leaf, keys_.p, vals_.p, partial_.p, d_range);
@@ -503,6 +492,86 @@ void KnnGrid::build(const float4 *pts, size_t n, const float mn[3], const float 
   tmp_.reserve(tmp_bytes + 256);
   LIO_HIP(rocprim::exclusive_scan(tmp_.p, tmp_bytes, cnt_.p, cells_.p, 0, ncells + 1, rocprim::plus<int>(), s));
   if (ni) hipLaunchKernelGGL(k_cell_place, dim3(cdiv(ni, 256)), dim3(256), 0, s, pts, keys_.p, vals_.p, ni, cells_.p, sorted_.p, cnt_.p);
+  LIO_HIP(hipGetLastError());
+  cnt_dirty_ = false;
+}
+
+// ---- GridBatch (cloud_kernels.h).  grid (cdiv(max points, 256), grids): k_cell_count's body with the grid's own record
+__global__ void __launch_bounds__(256) k_seg_cell_count(const GridSeg *__restrict__ segs, uint32_t *__restrict__ keys, uint32_t *__restrict__ slot,
+                                                        int *__restrict__ cnt) {
+  const GridSeg &r = segs[blockIdx.y];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r.pt_off < 0 || i >= r.g.n_points) return;
+  cell_count_point(r.pts, i, r.g, keys + r.pt_off, slot + r.pt_off, cnt + r.cell_off);
+}
+// one workgroup per grid walks the grid's own count table: no block waits for another.  The run starts begin at the grid's first sorted entry
+__global__ void __launch_bounds__(SEG_SCAN_THREADS) k_seg_cell_scan(const GridSeg *__restrict__ segs, const int *__restrict__ cnt, int *__restrict__ cells) {
+  const GridSeg &r = segs[blockIdx.x];
+  if (r.pt_off < 0) return;
+  block_exclusive_scan(cnt + r.cell_off, cells + r.cell_off, r.ncells + 1, r.pt_off);
+}
+__global__ void __launch_bounds__(256) k_seg_cell_place(const GridSeg *__restrict__ segs, const uint32_t *__restrict__ keys, const uint32_t *__restrict__ slot,
+                                                        const int *__restrict__ cells, float4 *__restrict__ sorted, int *__restrict__ cnt) {
+  const GridSeg &r = segs[blockIdx.y];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r.pt_off < 0 || i >= r.g.n_points) return;
+  cell_place_point(r.pts, keys + r.pt_off, slot + r.pt_off, i, cells + r.cell_off, sorted, cnt + r.cell_off);
+}
+
+void *GridBatch::begin(size_t head_bytes, int clouds) {
+  off_g_ = head_bytes; off_b_ = off_g_ + size_t(clouds) * sizeof(GridSeg);
+  h_tab_.assign(off_b_ + size_t(clouds) * sizeof(BoundsSeg), 0);
+  d_tab_.reserve(std::max<size_t>(h_tab_.size(), 1));
+  n_ = max_nb_ = max_pts_ = 0; part_total_ = 0;
+  any_shared_ = false;   // until layout(): a call without clouds builds nothing
+  return h_tab_.data();
+}
+void GridBatch::add(const float4 *pts, int n) {
+  const int nb = cloud_bounds_blocks(n);
+  bseg()[n_++] = BoundsSeg{pts, n, nb, int(part_total_)};
+  part_total_ += size_t(nb);
+  max_nb_ = std::max(max_nb_, nb); max_pts_ = std::max(max_pts_, n);
+}
+const VoxParams *GridBatch::bounds(hipStream_t s, float inv_leaf) {
+  partial_.reserve(part_total_ * 8); d_bounds_.reserve(size_t(n_));
+  if (h_bounds_.n < size_t(n_)) h_bounds_.alloc(size_t(n_) + size_t(n_) / 2, hipHostMallocDefault);
+  LIO_HIP(hipMemcpyAsync(d_tab_.p + off_b_, h_tab_.data() + off_b_, size_t(n_) * sizeof(BoundsSeg), hipMemcpyHostToDevice, s));
+  launch_seg_bounds(reinterpret_cast<const BoundsSeg *>(d_tab_.p + off_b_), n_, max_nb_, partial_.p, inv_leaf, d_bounds_.p, s);
+  LIO_HIP(hipMemcpyAsync(h_bounds_.p, d_bounds_.p, size_t(n_) * sizeof(VoxParams), hipMemcpyDeviceToHost, s));
+  LIO_HIP(hipStreamSynchronize(s));
+  return h_bounds_.p;
+}
+void GridBatch::layout(float cell, size_t cells_cap) {
+  size_t cell_total = 0, pt_off = 0;
+  for (int i = 0; i < n_; ++i) {
+    VoxParams &b = h_bounds_.p[i];
+    if (b.n_valid == 0)   // a cloud without a finite point (the test hooks allow empty ones) has no bounds
+      for (int e = 0; e < 3; ++e) b.mn[e] = b.mx[e] = 0.f;
+    GridSeg &g = gseg(i);
+    g.pts = bseg()[i].pts; g.g.n_points = bseg()[i].n; g.pt_off = -1;
+    const size_t ncells = grid_extent(g.g, b.mn, b.mx, cell);
+    if (ncells > cells_cap) continue;
+    g.pt_off = int(pt_off); g.cell_off = int(cell_total); g.ncells = int(ncells);
+    pt_off += size_t(g.g.n_points); cell_total += ncells + 1;
+    if (pt_off > size_t(INT_MAX) || cell_total > size_t(INT_MAX)) throw CapacityError("GridBatch: the points or the cell tables exceed 2^31 entries");
+    any_shared_ = true;
+  }
+  cells_.reserve(std::max<size_t>(cell_total, 1));
+  if (cnt_.cap < std::max<size_t>(cell_total, 1)) { cnt_.reserve(std::max<size_t>(cell_total, 1)); cnt_dirty_ = true; }
+  keys_.reserve(std::max<size_t>(pt_off, 1)); slot_.reserve(std::max<size_t>(pt_off, 1)); sorted_.reserve(std::max<size_t>(pt_off, 1));
+}
+void GridBatch::build(hipStream_t s) {
+  if (any_shared_ && cnt_dirty_) LIO_HIP(hipMemsetAsync(cnt_.p, 0, cnt_.cap * sizeof(int), s));
+  LIO_HIP(hipMemcpyAsync(d_tab_.p, h_tab_.data(), off_b_, hipMemcpyHostToDevice, s));
+  if (!any_shared_) return;
+  // no point at all (the hooks' empty clouds): nothing to count or place, and no launch of zero blocks; the scan still runs, so every cell's
+  // run starts (and ends) at its grid's base
+  const GridSeg *segs = reinterpret_cast<const GridSeg *>(d_tab_.p + off_g_);
+  const int pb = cdiv(max_pts_, 256);
+  cnt_dirty_ = true;   // until k_seg_cell_place has been enqueued
+  if (pb) hipLaunchKernelGGL(k_seg_cell_count, dim3(pb, n_), dim3(256), 0, s, segs, keys_.p, slot_.p, cnt_.p);
+  hipLaunchKernelGGL(k_seg_cell_scan, dim3(n_), dim3(SEG_SCAN_THREADS), 0, s, segs, cnt_.p, cells_.p);
+  if (pb) hipLaunchKernelGGL(k_seg_cell_place, dim3(pb, n_), dim3(256), 0, s, segs, keys_.p, slot_.p, cells_.p, sorted_.p, cnt_.p);
   LIO_HIP(hipGetLastError());
   cnt_dirty_ = false;
 }
@@ -911,8 +980,8 @@ __global__ void k_kf_update(const KfDesc *__restrict__ kd, OdomState *st, const 
   if (sig.flag) {   // the rounds at which the host looks post every keyframe's state to its own mailbox slot, then its own completion word (dev.h)
     __syncthreads();
     HostSignal mine = sig;
-    mine.flag = sig.flag + k;
-    if (threadIdx.x < 64) post_host_mail(mine, mail + size_t(k) * KF_MAIL_STRIDE, st + k, int(sizeof(OdomState) / 4), threadIdx.x);
+    char *slot = state_mail_slot(mail, mine, k);
+    if (threadIdx.x < 64) post_host_mail(mine, slot, st + k, int(sizeof(OdomState) / 4), threadIdx.x);
   }
 }
 
@@ -961,7 +1030,6 @@ void launch_kf_rows(const KfDesc *kd, const OdomState *st, int n_keyframes, int 
 }
 void launch_kf_update(const KfDesc *kd, OdomState *st, int n_keyframes, const double *partials, int iter, int min_rows, int left_update, int *n_converged,
                       char *mail, const HostSignal &sig, hipStream_t s) {
-  static_assert(sizeof(OdomState) <= KF_MAIL_STRIDE, "mailbox layout");
   hipLaunchKernelGGL(k_kf_update, dim3(n_keyframes), dim3(256), 0, s, kd, st, partials, iter, min_rows, left_update, n_converged, mail, sig);
   LIO_HIP(hipGetLastError());
 }

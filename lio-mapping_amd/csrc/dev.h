@@ -118,6 +118,7 @@ struct HostSignal {
   unsigned seq = 0;
   int nslots = 1;
 };
+#define STATE_MAIL_STRIDE 64   // bytes per sensor in a state mailbox (cloud_kernels.h: StateMail)
 // spin until every word == seq; every ~64k polls the stream is queried so that a faulted kernel raises instead of hanging
 inline void wait_host_signal(const HostSignal &sig, hipStream_t s) {
   const volatile unsigned *flag = sig.flag;
@@ -158,6 +159,11 @@ __device__ __forceinline__ void post_host_mail(const HostSignal &sig, void *dst,
   if (lane < nwords) host_store(reinterpret_cast<unsigned *>(dst) + lane, reinterpret_cast<const unsigned *>(src)[lane]);
   host_signal_drain();
   if (lane == 0) host_store(sig.flag, sig.seq);
+}
+// block k of a launch that posts one state per block (StateMail): its own slot of `mail`, and `sig` moved to its own completion word
+__device__ __forceinline__ char *state_mail_slot(char *mail, HostSignal &sig, int k) {
+  if (sig.flag) sig.flag += k;
+  return mail + size_t(k) * STATE_MAIL_STRIDE;
 }
 #endif
 

@@ -238,31 +238,6 @@ __global__ void __launch_bounds__(256) k_mb_roundtrip(const MbStackRec *__restri
   if (i >= r.n[c]) return;
   r.out[c][i] = stack_roundtrip_point(r.in[c][i], r.q, r.t);
 }
-// One from-map cloud of an iterating sensor: its bounds blocks (launch_cloud_bounds's count) and its first row of the chain's partials
-struct MbBoundsRec { const float4 *pts; int n; int nb; int off; };
-// grid (max nb, clouds): launch_cloud_bounds of every cloud through the voxel filter's block fold (cloud_device.h).  Minimum and maximum do
-// not hang on the order and the count is an exact float sum, so the VoxParams are launch_cloud_bounds's.
-__global__ void __launch_bounds__(VOX_TILE) k_mb_bounds(const MbBoundsRec *__restrict__ recs, float *__restrict__ partial_all) {
-  const MbBoundsRec r = recs[blockIdx.y];
-  if (int(blockIdx.x) >= r.nb) return;
-  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-  float cnt = 0;
-  for (int i = blockIdx.x * VOX_TILE + threadIdx.x; i < r.n; i += r.nb * VOX_TILE) {
-    const float4 p = r.pts[i];
-    if (!finite3(p)) continue;
-    cnt += 1.f;
-    mn[0] = fminf(mn[0], p.x); mn[1] = fminf(mn[1], p.y); mn[2] = fminf(mn[2], p.z);
-    mx[0] = fmaxf(mx[0], p.x); mx[1] = fmaxf(mx[1], p.y); mx[2] = fmaxf(mx[2], p.z);
-  }
-  vox_block_partial(mn, mx, cnt, partial_all + (size_t(r.off) + blockIdx.x) * 8);
-}
-// one block per cloud
-__global__ void __launch_bounds__(VOX_TILE) k_mb_bounds_fold(const MbBoundsRec *__restrict__ recs, const float *__restrict__ partial_all,
-                                                             VoxParams *__restrict__ out) {
-  const MbBoundsRec r = recs[blockIdx.x];
-  VoxParams v;
-  if (vox_fold_bounds(partial_all + size_t(r.off) * 8, r.nb, 1.0f, v)) out[blockIdx.x] = v;
-}
 // One iterating sensor's slice [slot_off, slot_off + Mc + Ms) of the chain's arrays and where the handle keeps the same: its filtered stacks
 // (taken), and its own stack_all_ / f_coef_ / f_abs_ / f_valid_ (given back)
 struct MbSliceRec { const float4 *stack_ds[2]; int M[2]; int slot_off; float4 *stack_all; float4 *coef; float4 *abs_coef; uint8_t *valid; };
@@ -345,11 +320,7 @@ struct MapChain {
   DBuf<MbStackRec> d_stack;
   bool any_stack = false;               // some handle brought a cloud: the round trip ran
   std::vector<int> act;                 // the handles (indices into the call) whose rounds run: the keyframe table's order
-  std::vector<MbBoundsRec> h_brecs;
-  DBuf<MbBoundsRec> d_brecs;
-  DBuf<float> d_bpartial;
-  DBuf<VoxParams> d_bounds;
-  HostBuf<VoxParams> h_bounds;          // pinned: 2 * nA
+  GridBatch clouds;                     // the from-map clouds of `act` (2 * nA): their bounds side by side; the grids are the handles' own
   DBuf<float4> stack_all, coef, abs_coef;
   DBuf<uint8_t> valid;
   DBuf<double> partials;
@@ -357,9 +328,7 @@ struct MapChain {
   DBuf<char> d_table;
   size_t off_kd = 0, off_st = 0, off_sl = 0;
   int max_Mc = 0, max_Ms = 0, max_nb = 0;
-  HostBuf<char> h_mail;                 // pinned, coherent: mail_cap states of KF_MAIL_STRIDE bytes, then mail_cap completion words (dev.h: HostSignal)
-  size_t mail_cap = 0;
-  unsigned seq = 0;
+  StateMail mail;                       // the sensors' states at the peeks
   hipEvent_t ev = nullptr;              // behind the round trip of the stacks: every other handle's filters wait for it
   MapChain() { LIO_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); }
   ~MapChain() { if (ev) (void)hipEventDestroy(ev); }
@@ -368,7 +337,6 @@ struct MapChain {
 
   int nA() const { return int(act.size()); }
   MappingDev &dev(int j) const { return *m[act[size_t(j)]]; }
-  OdomState &mail(int j) const { return *reinterpret_cast<OdomState *>(h_mail.p + size_t(j) * KF_MAIL_STRIDE); }   // sensor j's slot
   void Prepare(MappingDev *const *handles, int n_handles, const float *const *corner_last, const size_t *n_corner, const float *const *surf_last,
                const size_t *n_surf, const Rigid<float> *sums);
   void Filter();
@@ -859,33 +827,19 @@ void MapChain::MakeGrids() {
   }
   const int na = nA();
   if (!na) return;
-  h_brecs.assign(size_t(2 * na), MbBoundsRec());
-  size_t bpart_total = 0;
-  int max_bnb = 0;
+  clouds.begin(0, 2 * na);
   for (int j = 0; j < na; ++j)
     for (int c = 0; c < 2; ++c) {
       const MappingDev::ClassMap &cm = dev(j).cls_[c];
       if (cm.n_valid > size_t(INT_MAX) - 255) throw CapacityError("lio_map_process_batch: a from-map cloud exceeds 2^31 points");
-      MbBoundsRec &r = h_brecs[size_t(2 * j + c)];
-      r.pts = cm.pool.p + cm.n_rest; r.n = int(cm.n_valid);
-      r.nb = std::max(1, std::min(cdiv(r.n, 256), 512));   // (launch_cloud_bounds)
-      r.off = int(bpart_total);
-      bpart_total += size_t(r.nb);
-      max_bnb = std::max(max_bnb, r.nb);
+      clouds.add(cm.pool.p + cm.n_rest, int(cm.n_valid));
     }
-  d_brecs.reserve(size_t(2 * na)); d_bpartial.reserve(bpart_total * 8); d_bounds.reserve(size_t(2 * na));
-  if (h_bounds.n < size_t(2 * na)) h_bounds.alloc(size_t(2 * na) + size_t(na), hipHostMallocDefault);
-  LIO_HIP(hipMemcpyAsync(d_brecs.p, h_brecs.data(), size_t(2 * na) * sizeof(MbBoundsRec), hipMemcpyHostToDevice, s0));
-  hipLaunchKernelGGL(k_mb_bounds, dim3(max_bnb, 2 * na), dim3(VOX_TILE), 0, s0, d_brecs.p, d_bpartial.p);
-  hipLaunchKernelGGL(k_mb_bounds_fold, dim3(2 * na), dim3(VOX_TILE), 0, s0, d_brecs.p, d_bpartial.p, d_bounds.p);
-  LIO_HIP(hipGetLastError());
-  LIO_HIP(hipMemcpyAsync(h_bounds.p, d_bounds.p, size_t(2 * na) * sizeof(VoxParams), hipMemcpyDeviceToHost, s0));
-  LIO_HIP(hipStreamSynchronize(s0));
+  const VoxParams *bounds = clouds.bounds(s0);
   const float cell = scan_to_map_cell_edge(m[0]->cfg_.min_match_sq_dis);
   for (int j = 0; j < na; ++j)
     for (int c = 0; c < 2; ++c) {
       MappingDev::ClassMap &cm = dev(j).cls_[c];
-      const VoxParams &b = h_bounds.p[2 * j + c];
+      const VoxParams &b = bounds[2 * j + c];
       cm.grid.build(cm.pool.p + cm.n_rest, cm.n_valid, b.mn, b.mx, cell, dev(j).stream_);
     }
 }
@@ -941,22 +895,15 @@ void MapChain::Iterate() {
   const int na = nA();
   const lio_map_config &cfg = m[0]->cfg_;
   const bool four_dof = m[0]->FourDof();
-  if (mail_cap < size_t(na)) {   // (the stream is idle between calls: nobody still posts to the old one)
-    const size_t cap = size_t(na) + size_t(na) / 2;
-    h_mail.alloc(cap * (KF_MAIL_STRIDE + sizeof(unsigned)), hipHostMallocCoherent, true);
-    mail_cap = cap;
-  }
-  unsigned *flags = reinterpret_cast<unsigned *>(h_mail.p + mail_cap * KF_MAIL_STRIDE);
+  mail.reserve(na);
   const OdomState *h_st = reinterpret_cast<const OdomState *>(h_table.p + off_st);
-  for (int j = 0; j < na; ++j) mail(j) = h_st[j];   // (what the loop's end reads when no round runs)
+  for (int j = 0; j < na; ++j) mail.slot(j) = h_st[j];   // (what the loop's end reads when no round runs)
   const KfMapDesc *d_md = reinterpret_cast<const KfMapDesc *>(d_table.p);
   const KfDesc *d_kd = reinterpret_cast<const KfDesc *>(d_table.p + off_kd);
   OdomState *d_st = reinterpret_cast<OdomState *>(d_table.p + off_st);
   const int mode = four_dof ? 2 : 1;
   const int max_it = cfg.num_max_iterations;
   static const int kPeek[] = {6, 8, 10};
-  HostSignal sig{};
-  sig.nslots = na;
   int iter = 0, peek_i = 0;
   bool done = false;
   while (iter < max_it && !done) {
@@ -968,12 +915,11 @@ void MapChain::Iterate() {
       launch_kf_round(d_kd, d_md, d_st, na, max_Mc, max_Ms, 8, stack_all.p, nullptr, cfg.min_match_sq_dis, cfg.min_plane_dis, mode, valid.p, coef.p, abs_coef.p, s0);
       launch_kf_rows(d_kd, d_st, na, max_nb, stack_all.p, valid.p, coef.p, partials.p, mode, s0);
       HostSignal sg{};
-      if (iter == until - 1) { sig.flag = flags; sig.seq = ++seq; sg = sig; }
-      launch_kf_update(d_kd, d_st, na, partials.p, iter, 50, four_dof ? 1 : 0, nullptr, h_mail.p, sg, s0);
+      if (iter == until - 1) sg = mail.arm(na);
+      launch_kf_update(d_kd, d_st, na, partials.p, iter, 50, four_dof ? 1 : 0, nullptr, mail.base(), sg, s0);
     }
-    wait_host_signal(sig, s0);   // until > iter: the inner loop ran and its last round posted sig
-    done = true;
-    for (int j = 0; j < na; ++j) done = done && mail(j).converged;
+    mail.wait(s0);   // until > iter: the inner loop ran and its last round posted
+    done = mail.all_converged(na);
   }
 }
 
@@ -984,7 +930,7 @@ void MapChain::GiveBack() {
   hipLaunchKernelGGL(k_mb_give, dim3(cdiv(max_Mc + max_Ms, 256), 4, na), dim3(256), 0, s0, reinterpret_cast<const MbSliceRec *>(d_table.p + off_sl), stack_all.p,
                      coef.p, abs_coef.p, valid.p);
   LIO_HIP(hipGetLastError());
-  for (int j = 0; j < na; ++j) dev(j).OptimizeEnd(mail(j), int(dev(j).cls_[0].n_stack + dev(j).cls_[1].n_stack), m[0]->FourDof());
+  for (int j = 0; j < na; ++j) dev(j).OptimizeEnd(mail.slot(j), int(dev(j).cls_[0].n_stack + dev(j).cls_[1].n_stack), m[0]->FourDof());
 }
 
 // ---- 7. update: the map update and the full cloud's registration per handle on its own stream (the poses are on the host), then one pass of

@@ -8,7 +8,7 @@
 //                on the ring bound is reproduced with a ballot inside the chunk.  Every fifth iteration.
 //   k_ob_rows    edge / plane coefficients (:391-435, :497-531), weights (A.7), rows of A and B (:548-571), reduced to per-block partials.
 //   k_ob_update  6x6 solve, degeneracy mask (threshold 10, A.6), update, abort test (:573-650).
-// and around them k_ob_take (the clouds from the feature extraction), k_ob_bounds .. k_ob_cell_place (the grids over the previous clouds, all
+// and around them k_ob_take (the clouds from the feature extraction), GridBatch (cloud_kernels.h: the grids over the previous clouds, all
 // sensors' side by side) and k_ob_to_end (TransformToEnd, :262-292).  k_odo_to_end is TransformToEnd of a caller's cloud (FullToEnd).
 // The <= 25 rounds run without a host round trip except a convergence peek every 5 rounds.
 // The test hooks (include/lio_test_hooks.h) build the same table for one sensor and launch k_ob_corr or k_ob_rows once over it; k_odo_sel and
@@ -427,12 +427,7 @@ struct OdoBatchRec {
   int nb;                     // its row blocks: max(1, min(cdiv(nq, ODO_ROW_THREADS), 64)), the partition it has alone
   int part_off;               // its first row (28 doubles each) of the batch's partials
   int trace_off;              // its first float of the batch's trace table (8 per iteration)
-  // the segmented build of its two grids over a.lastc (0) and a.lasts (1): the batch's tables hold every sensor's grids one behind the other
-  int b_nb[2], b_off[2];      // bounds: its blocks over the cloud (launch_cloud_bounds's count), its first row of the batch's bounds partials
-  int g_pt[2];                // the cloud's first entry in the batch's keys / slot / sorted arrays; < 0: this grid is built by KnnGrid::build
-  int g_cell[2], g_ncells[2]; // its slice (g_ncells + 1 entries) of the batch's count and cell tables
 };
-#define ODO_MAIL_STRIDE 64    // bytes per sensor in the batch's mailbox
 
 // grid (max nq, sensors) x 64: one wavefront per query; the blocks beyond a sensor's own queries leave at once
 __global__ void __launch_bounds__(64) k_ob_corr(const OdoBatchRec *__restrict__ recs, int *__restrict__ idx_all) {
@@ -454,9 +449,8 @@ __global__ void k_ob_update(const OdoBatchRec *__restrict__ recs, const double *
                             float *__restrict__ trace_all) {
   const OdoBatchRec &r = recs[blockIdx.x];
   HostSignal mine = sig;
-  if (sig.flag) mine.flag = sig.flag + blockIdx.x;
-  odo_update_body(partials_all + size_t(r.part_off) * 28, r.nb, r.st, iter, reinterpret_cast<OdomState *>(mail + size_t(blockIdx.x) * ODO_MAIL_STRIDE), mine,
-                  trace_all + r.trace_off);
+  char *slot = state_mail_slot(mail, mine, blockIdx.x);
+  odo_update_body(partials_all + size_t(r.part_off) * 28, r.nb, r.st, iter, reinterpret_cast<OdomState *>(slot), mine, trace_all + r.trace_off);
 }
 // grid (cdiv(max(n_ls + n_lf), 256), sensors): the less-sharp points of a sensor, then its less-flat points, each in place
 __global__ void __launch_bounds__(256) k_ob_to_end(const OdoBatchRec *__restrict__ recs) {
@@ -465,60 +459,6 @@ __global__ void __launch_bounds__(256) k_ob_to_end(const OdoBatchRec *__restrict
   if (i >= r.n_ls + r.n_lf) return;
   float4 *c = i < r.n_ls ? r.ls : r.lf;
   odo_to_end_body(c, c, i < r.n_ls ? i : i - r.n_ls, r.st, r.a.time_factor, r.a.no_deskew);
-}
-
-// ---- the segmented grid build: launch_cloud_bounds and KnnGrid::build of all 2 * nA previous clouds in five launches.  Grid `y` of a launch is
-// cloud y & 1 of sensor y >> 1.  The bounds are folded by the device code of launch_cloud_bounds (vox_block_partial, vox_fold_bounds: min and
-// max do not hang on the order, the count is an exact float sum), the cells are keyed and the points placed by k_cell_count's and
-// k_cell_place's bodies.  A grid's run starts are offsets into the batch's ONE sorted array, which is all odo_corr_body asks of them.
-__global__ void __launch_bounds__(VOX_TILE) k_ob_bounds(const OdoBatchRec *__restrict__ recs, float *__restrict__ partial_all) {
-  const OdoBatchRec &r = recs[blockIdx.y >> 1];
-  const int w = blockIdx.y & 1, nb = r.b_nb[w];
-  if (int(blockIdx.x) >= nb) return;
-  const float4 *pts = w ? r.a.lasts : r.a.lastc;
-  const int n = w ? r.a.nls : r.a.nlc;
-  float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-  float cnt = 0;
-  for (int i = blockIdx.x * VOX_TILE + threadIdx.x; i < n; i += nb * VOX_TILE) {
-    const float4 p = pts[i];
-    if (!finite3(p)) continue;
-    cnt += 1.f;
-    mn[0] = fminf(mn[0], p.x); mn[1] = fminf(mn[1], p.y); mn[2] = fminf(mn[2], p.z);
-    mx[0] = fmaxf(mx[0], p.x); mx[1] = fmaxf(mx[1], p.y); mx[2] = fmaxf(mx[2], p.z);
-  }
-  vox_block_partial(mn, mx, cnt, partial_all + (size_t(r.b_off[w]) + blockIdx.x) * 8);
-}
-// one block per cloud: out[2 * sensor + cloud]
-__global__ void __launch_bounds__(VOX_TILE) k_ob_bounds_fold(const OdoBatchRec *__restrict__ recs, const float *__restrict__ partial_all,
-                                                             VoxParams *__restrict__ out) {
-  const OdoBatchRec &r = recs[blockIdx.x >> 1];
-  const int w = blockIdx.x & 1;
-  VoxParams v;
-  if (vox_fold_bounds(partial_all + size_t(r.b_off[w]) * 8, r.b_nb[w], 1.0f, v)) out[blockIdx.x] = v;
-}
-// grid (cdiv(max points, 256), grids)
-__global__ void __launch_bounds__(256) k_ob_cell_count(const OdoBatchRec *__restrict__ recs, uint32_t *__restrict__ keys, uint32_t *__restrict__ slot,
-                                                       int *__restrict__ cnt) {
-  const OdoBatchRec &r = recs[blockIdx.y >> 1];
-  const int w = blockIdx.y & 1, off = r.g_pt[w];
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (off < 0 || i >= (w ? r.a.nls : r.a.nlc)) return;
-  cell_count_point(w ? r.a.lasts : r.a.lastc, i, w ? r.a.gs : r.a.gc, keys + off, slot + off, cnt + r.g_cell[w]);
-}
-// one workgroup per grid walks the grid's own count table: no block waits for another
-__global__ void __launch_bounds__(SEG_SCAN_THREADS) k_ob_cell_scan(const OdoBatchRec *__restrict__ recs, const int *__restrict__ cnt, int *__restrict__ cells) {
-  const OdoBatchRec &r = recs[blockIdx.x >> 1];
-  const int w = blockIdx.x & 1;
-  if (r.g_pt[w] < 0) return;
-  block_exclusive_scan(cnt + r.g_cell[w], cells + r.g_cell[w], r.g_ncells[w] + 1, r.g_pt[w]);
-}
-__global__ void __launch_bounds__(256) k_ob_cell_place(const OdoBatchRec *__restrict__ recs, const uint32_t *__restrict__ keys, const uint32_t *__restrict__ slot,
-                                                       const int *__restrict__ cells, float4 *__restrict__ sorted, int *__restrict__ cnt) {
-  const OdoBatchRec &r = recs[blockIdx.y >> 1];
-  const int w = blockIdx.y & 1, off = r.g_pt[w];
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (off < 0 || i >= (w ? r.a.nls : r.a.nlc)) return;
-  cell_place_point(w ? r.a.lasts : r.a.lastc, keys + off, slot + off, i, cells + r.g_cell[w], sorted, cnt + r.g_cell[w]);
 }
 
 // ---- the hand-over from the feature extraction (lio_odom_process_batch_from_pp): one sensor's four clouds, where the processor left them on
@@ -547,30 +487,21 @@ struct OdoChain {
   int max_iter = 0;
   std::vector<int> act, idle;        // who iterates, and who only carries its clouds to the sweep's end; the table holds `act`, then `idle`
   std::vector<OdomState> st, got;    // per handle: the state it starts from and ends with; per iterating sensor: the state its mailbox held
-  int max_nq = 0, max_nb = 0, max_np = 0, max_bnb = 0, max_pts = 0;   // the launches' widths: queries, row blocks, points to the end, bounds blocks, previous points
-  size_t idx_total = 0, part_total = 0, bpart_total = 0;
+  int max_nq = 0, max_nb = 0, max_np = 0;   // the launches' widths: queries, row blocks, points to the end
+  size_t idx_total = 0, part_total = 0;
   int nA() const { return int(act.size()); }
   int nE() const { return int(act.size() + idle.size()); }
   int who(int j) const { return j < nA() ? act[size_t(j)] : idle[size_t(j - nA())]; }   // the handle (index into o) of table record j
   OdometryDev &dev(int j) const { return *o[who(j)]; }
   // ---- the scratch
-  std::vector<OdoBatchRec> h_recs;
-  DBuf<OdoBatchRec> d_recs;
+  GridBatch grids;            // the grids over the previous clouds of `act`: 2 * j over a.lastc, 2 * j + 1 over a.lasts of record j
+  OdoBatchRec *h_recs = nullptr;         // the table, in front of the grids' own records in their staging table: one upload carries both
+  const OdoBatchRec *d_recs = nullptr;
   DBuf<int> d_idx;
   DBuf<double> d_partials;
   DBuf<float> d_trace;
   std::vector<float> h_trace;
-  DBuf<VoxParams> d_bounds;
-  HostBuf<VoxParams> h_bounds;
-  HostBuf<char> h_mail;       // pinned, coherent: mail_cap states of ODO_MAIL_STRIDE bytes, then mail_cap completion words
-  size_t mail_cap = 0;
-  unsigned seq = 0;
-  // the segmented grid build: bounds partials, and the grids' keys, slots, counts, run starts and cell-sorted points, one grid behind the other
-  DBuf<float> d_bpartial;
-  DBuf<uint32_t> g_keys, g_slot;
-  DBuf<int> g_cnt, g_cells;
-  DBuf<float4> g_sorted;
-  bool g_cnt_dirty = false;   // KnnGrid's invariant for g_cnt: all zeros between builds (k_ob_cell_place puts them back)
+  StateMail mail;
   std::vector<OdoTakeRec> h_take;
   DBuf<OdoTakeRec> d_take;
 
@@ -578,7 +509,6 @@ struct OdoChain {
   void TakeClouds(int n, const float *const *sharp, const size_t *n_sharp, const float *const *less_sharp, const size_t *n_ls, const float *const *flat,
                   const size_t *n_flat, const float *const *less_flat, const size_t *n_lf, bool on_device);
   void FillTable(const size_t *n_sharp, const size_t *n_flat, const size_t *n_ls, const size_t *n_lf);
-  void ReadBounds();
   void MakeGrids();
   void Iterate();
   void Finish();
@@ -670,14 +600,14 @@ void OdoChain::TakeClouds(int n, const float *const *sharp, const size_t *n_shar
 // whose sizes it states.  Array k of every argument belongs to o[k]; the clouds themselves lie in the handles.
 void OdoChain::FillTable(const size_t *n_sharp, const size_t *n_flat, const size_t *n_ls, const size_t *n_lf) {
   const int na = nA(), ne = nE();
-  h_recs.assign(size_t(ne), OdoBatchRec{});
-  idx_total = part_total = bpart_total = 0;
-  max_nq = max_nb = max_np = max_bnb = max_pts = 0;
-  size_t pt_total = 0;
+  h_recs = static_cast<OdoBatchRec *>(grids.begin(size_t(ne) * sizeof(OdoBatchRec), 2 * na));
+  d_recs = static_cast<const OdoBatchRec *>(grids.head_dev());
+  idx_total = part_total = 0;
+  max_nq = max_nb = max_np = 0;
   for (int j = 0; j < ne; ++j) {
     const int k = who(j);
     OdometryDev &d = *o[k];
-    OdoBatchRec &r = h_recs[size_t(j)];
+    OdoBatchRec &r = h_recs[j];
     r.a.time_factor = d.time_factor_; r.a.no_deskew = d.no_deskew_ ? 1 : 0;
     r.st = d.d_state_.p;
     r.ls = d.less_sharp_.p; r.n_ls = int(n_ls[k]); r.lf = d.less_flat_.p; r.n_lf = int(n_lf[k]);
@@ -694,17 +624,9 @@ void OdoChain::FillTable(const size_t *n_sharp, const size_t *n_flat, const size
     max_nq = std::max(max_nq, nq); max_nb = std::max(max_nb, r.nb);
     r.a.sharp = d.sharp_.p; r.a.nc = int(n_sharp[k]); r.a.flat = d.flat_.p; r.a.ns = int(n_flat[k]);
     r.a.lastc = d.last_corner_.p; r.a.nlc = int(d.n_last_corner_); r.a.lasts = d.last_surf_.p; r.a.nls = int(d.n_last_surf_);
-    for (int c = 0; c < 2; ++c) {
-      const int np = c ? r.a.nls : r.a.nlc;
-      r.b_nb[c] = std::max(1, std::min(cdiv(np, 256), 512));   // (launch_cloud_bounds)
-      r.b_off[c] = int(bpart_total);
-      bpart_total += size_t(r.b_nb[c]);
-      max_bnb = std::max(max_bnb, r.b_nb[c]); max_pts = std::max(max_pts, np);
-      pt_total += size_t(np);
-    }
+    grids.add(r.a.lastc, r.a.nlc);
+    grids.add(r.a.lasts, r.a.nls);
   }
-  if (pt_total > size_t(INT_MAX)) throw CapacityError("scan-to-scan odometry: the previous clouds exceed 2^31 points");
-  d_recs.reserve(size_t(ne));
   if (!na) return;
   d_idx.reserve(std::max<size_t>(idx_total, 1));
   if (idx_total) LIO_HIP(hipMemsetAsync(d_idx.p, 0xFF, idx_total * sizeof(int), s));
@@ -712,78 +634,29 @@ void OdoChain::FillTable(const size_t *n_sharp, const size_t *n_flat, const size
 }
 
 // ---- step 3: kdtree_corner_last_ / kdtree_surf_last_->setInputCloud (PointOdometry.cc:673-676) as 5 m grids over the previous clouds of `act`,
-// and the finished table on the device.
-// The bounds of all 2 * nA clouds -> h_bounds: two launches over the table (which so far names the clouds alone), one read-back, one wait
-void OdoChain::ReadBounds() {
-  const int na = nA();
-  d_bounds.reserve(size_t(2 * na));
-  if (h_bounds.n < size_t(2 * na)) h_bounds.alloc(size_t(2 * na) + size_t(na), hipHostMallocDefault);
-  d_bpartial.reserve(bpart_total * 8);
-  LIO_HIP(hipMemcpyAsync(d_recs.p, h_recs.data(), size_t(na) * sizeof(OdoBatchRec), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_ob_bounds, dim3(max_bnb, 2 * na), dim3(VOX_TILE), 0, s, d_recs.p, d_bpartial.p);
-  hipLaunchKernelGGL(k_ob_bounds_fold, dim3(2 * na), dim3(VOX_TILE), 0, s, d_recs.p, d_bpartial.p, d_bounds.p);
-  LIO_HIP(hipGetLastError());
-  LIO_HIP(hipMemcpyAsync(h_bounds.p, d_bounds.p, size_t(2 * na) * sizeof(VoxParams), hipMemcpyDeviceToHost, s));
-  LIO_HIP(hipStreamSynchronize(s));
-}
-// Every grid of at most LIO_ODOM_BATCH_GRID_CELLS_MAX cells gets a slice of the chain's tables and is built by count, scan and place, one
-// launch each over all of them; a larger one is built by its sensor's own KnnGrid.
+// and the finished table on the device.  The bounds of all 2 * nA clouds come back in one read-back behind the upload of the clouds' own
+// records; every grid of at most LIO_ODOM_BATCH_GRID_CELLS_MAX cells is then built by `grids` behind the second upload, a larger
+// one by its sensor's own KnnGrid.
 void OdoChain::MakeGrids() {
-  const int na = nA(), ne = nE();
-  bool any_shared = false;
+  const int na = nA();
   if (na) {
-    ReadBounds();
+    const VoxParams *b = grids.bounds(s);
     const float cell = 5.0f * 1.0001f;
-    size_t cell_total = 0, pt_off = 0;
+    grids.layout(cell, size_t(LIO_ODOM_BATCH_GRID_CELLS_MAX));
     for (int j = 0; j < na; ++j) {
       OdometryDev &d = dev(j);
-      OdoBatchRec &r = h_recs[size_t(j)];
-      VoxParams *b = h_bounds.p + 2 * j;
+      OdoArgs &a = h_recs[j].a;
       for (int c = 0; c < 2; ++c) {
-        if (b[c].n_valid == 0)   // a cloud without a finite point (the test hooks allow empty ones) has no bounds
-          for (int e = 0; e < 3; ++e) b[c].mn[e] = b[c].mx[e] = 0.f;
-        GridDesc &g = c ? r.a.gs : r.a.gc;
-        const int np = c ? r.a.nls : r.a.nlc;
-        g.n_points = np;
-        const size_t ncells = grid_extent(g, b[c].mn, b[c].mx, cell);
-        if (ncells > size_t(LIO_ODOM_BATCH_GRID_CELLS_MAX)) {
-          KnnGrid &own = c ? d.grid_s_ : d.grid_c_;
-          own.build(c ? r.a.lasts : r.a.lastc, size_t(np), b[c].mn, b[c].mx, cell, s);
-          r.g_pt[c] = -1;
-          continue;
-        }
-        r.g_pt[c] = int(pt_off); r.g_cell[c] = int(cell_total); r.g_ncells[c] = int(ncells);
-        pt_off += size_t(np); cell_total += ncells + 1;
-        any_shared = true;
+        const int i = 2 * j + c;
+        KnnGrid &own = c ? d.grid_s_ : d.grid_c_;
+        if (!grids.shared(i)) own.build(c ? a.lasts : a.lastc, size_t(c ? a.nls : a.nlc), b[i].mn, b[i].mx, cell, s);
+        (c ? a.gs : a.gc) = grids.desc(i);
+        (c ? a.gs_sorted : a.gc_sorted) = grids.shared(i) ? grids.sorted(i) : own.sorted();
+        (c ? a.gs_cells : a.gc_cells) = grids.shared(i) ? grids.cells(i) : own.cells();
       }
     }
-    if (cell_total > size_t(INT_MAX)) throw CapacityError("scan-to-scan odometry: the cell tables exceed 2^31 entries");
-    g_cells.reserve(std::max<size_t>(cell_total, 1));
-    if (g_cnt.cap < cell_total || g_cnt_dirty) {   // a fresh table starts zeroed; after that k_ob_cell_place leaves it zeroed
-      g_cnt.reserve(std::max<size_t>(cell_total, 1));
-      LIO_HIP(hipMemsetAsync(g_cnt.p, 0, g_cnt.cap * sizeof(int), s));
-    }
-    g_keys.reserve(std::max<size_t>(pt_off, 1)); g_slot.reserve(std::max<size_t>(pt_off, 1)); g_sorted.reserve(std::max<size_t>(pt_off, 1));
-    // (every buffer is in place: a grid's arguments are its slice of the cell table and the base of the shared sorted array)
-    for (int j = 0; j < na; ++j) {
-      OdometryDev &d = dev(j);
-      OdoBatchRec &r = h_recs[size_t(j)];
-      r.a.gc_sorted = r.g_pt[0] < 0 ? d.grid_c_.sorted() : g_sorted.p; r.a.gc_cells = r.g_pt[0] < 0 ? d.grid_c_.cells() : g_cells.p + r.g_cell[0];
-      r.a.gs_sorted = r.g_pt[1] < 0 ? d.grid_s_.sorted() : g_sorted.p; r.a.gs_cells = r.g_pt[1] < 0 ? d.grid_s_.cells() : g_cells.p + r.g_cell[1];
-    }
   }
-  LIO_HIP(hipMemcpyAsync(d_recs.p, h_recs.data(), size_t(ne) * sizeof(OdoBatchRec), hipMemcpyHostToDevice, s));
-  if (any_shared) {
-    // no point at all (max_pts == 0, the hooks' empty previous clouds): nothing to count or place, and no launch of zero blocks; the scan
-    // still runs, so every cell's run starts (and ends) at its grid's base
-    const int pb = cdiv(max_pts, 256);
-    g_cnt_dirty = true;   // until k_ob_cell_place has been enqueued
-    if (pb) hipLaunchKernelGGL(k_ob_cell_count, dim3(pb, 2 * na), dim3(256), 0, s, d_recs.p, g_keys.p, g_slot.p, g_cnt.p);
-    hipLaunchKernelGGL(k_ob_cell_scan, dim3(2 * na), dim3(SEG_SCAN_THREADS), 0, s, d_recs.p, g_cnt.p, g_cells.p);
-    if (pb) hipLaunchKernelGGL(k_ob_cell_place, dim3(pb, 2 * na), dim3(256), 0, s, d_recs.p, g_keys.p, g_slot.p, g_cells.p, g_sorted.p, g_cnt.p);
-    LIO_HIP(hipGetLastError());
-    g_cnt_dirty = false;
-  }
+  grids.build(s);
 }
 
 // ---- step 4: the <= max_iter iterations of `act` (:325-651).  The host looks at the sensors' mailboxes where the reference refreshes the
@@ -791,41 +664,28 @@ void OdoChain::MakeGrids() {
 // kernels leave at once).  Leaves every sensor's last state in `got`.
 void OdoChain::Iterate() {
   const int na = nA();
-  static_assert(sizeof(OdomState) <= ODO_MAIL_STRIDE, "mailbox layout");
   d_trace.reserve(size_t(na) * size_t(max_iter) * 8);
-  if (mail_cap < size_t(na)) {   // (the stream is idle between calls: nobody still posts to the old one)
-    const size_t cap = size_t(na) + size_t(na) / 2;
-    h_mail.alloc(cap * (ODO_MAIL_STRIDE + sizeof(unsigned)), hipHostMallocCoherent, true);
-    mail_cap = cap;
-  }
-  char *mail = h_mail.p;
-  unsigned *flags = reinterpret_cast<unsigned *>(h_mail.p + mail_cap * ODO_MAIL_STRIDE);
+  mail.reserve(na);
   got.assign(size_t(na), OdomState{});
   auto read_mail = [&] {
-    bool all = true;
-    for (int j = 0; j < na; ++j) {
-      got[size_t(j)] = *reinterpret_cast<const OdomState *>(mail + size_t(j) * ODO_MAIL_STRIDE);
-      all = all && got[size_t(j)].converged;
-    }
-    return all;
+    for (int j = 0; j < na; ++j) got[size_t(j)] = mail.slot(j);
+    return mail.all_converged(na);
   };
-  HostSignal sig{};
-  sig.nslots = na;
   bool have_state = false;
   for (int iter = 0; iter < max_iter; ++iter) {
     if (iter > 0 && iter % 5 == 0) {
-      wait_host_signal(sig, s);
+      mail.wait(s);
       if (read_mail()) { have_state = true; break; }
     }
-    if (iter % 5 == 0 && max_nq > 0) hipLaunchKernelGGL(k_ob_corr, dim3(max_nq, na), dim3(64), 0, s, d_recs.p, d_idx.p);
-    hipLaunchKernelGGL(k_ob_rows, dim3(max_nb, na), dim3(ODO_ROW_THREADS), 0, s, d_recs.p, d_idx.p, iter, d_partials.p);
+    if (iter % 5 == 0 && max_nq > 0) hipLaunchKernelGGL(k_ob_corr, dim3(max_nq, na), dim3(64), 0, s, d_recs, d_idx.p);
+    hipLaunchKernelGGL(k_ob_rows, dim3(max_nb, na), dim3(ODO_ROW_THREADS), 0, s, d_recs, d_idx.p, iter, d_partials.p);
     HostSignal sg{};
-    if (iter % 5 == 4 || iter == max_iter - 1) { sig.flag = flags; sig.seq = ++seq; sg = sig; }
-    hipLaunchKernelGGL(k_ob_update, dim3(na), dim3(256), 0, s, d_recs.p, d_partials.p, iter, mail, sg, d_trace.p);
+    if (iter % 5 == 4 || iter == max_iter - 1) sg = mail.arm(na);
+    hipLaunchKernelGGL(k_ob_update, dim3(na), dim3(256), 0, s, d_recs, d_partials.p, iter, mail.base(), sg, d_trace.p);
   }
   LIO_HIP(hipGetLastError());
   if (!have_state) {   // the last iteration posted (max_iter >= 1)
-    wait_host_signal(sig, s);
+    mail.wait(s);
     read_mail();
   }
 }
@@ -842,14 +702,14 @@ void OdoChain::Finish() {
     for (int j = 0; j < na; ++j) {
       st[size_t(act[size_t(j)])] = got[size_t(j)];
       for (int i = 0; i < got[size_t(j)].iters; ++i) {
-        const float *T = &h_trace[size_t(h_recs[size_t(j)].trace_off) + size_t(i) * 8];
+        const float *T = &h_trace[size_t(h_recs[j].trace_off) + size_t(i) * 8];
         dev(j).es_trace_.push_back(Rigid<float>(Quat<float>(T[3], T[0], T[1], T[2]), Vec3<float>(T[4], T[5], T[6])));
       }
     }
   }
   // (a sensor of `idle` keeps the state it was given: nothing ran on it)
   for (int j = 0; j < ne; ++j) dev(j).Accumulate(st[size_t(who(j))]);
-  if (max_np) hipLaunchKernelGGL(k_ob_to_end, dim3(cdiv(max_np, 256), ne), dim3(256), 0, s, d_recs.p);
+  if (max_np) hipLaunchKernelGGL(k_ob_to_end, dim3(cdiv(max_np, 256), ne), dim3(256), 0, s, d_recs);
   LIO_HIP(hipGetLastError());
 }
 
@@ -916,7 +776,7 @@ void OdometryDev::Correspondences(const float *sharp, size_t n_sharp, const floa
   OdoChain &ch = HookTable(sharp, n_sharp, flat, n_flat, last_corner, n_lc, last_surf, n_lsf, T);
   hipStream_t s = ch.s;
   const size_t nq = n_sharp + n_flat;
-  if (ch.max_nq > 0) hipLaunchKernelGGL(k_ob_corr, dim3(ch.max_nq, 1), dim3(64), 0, s, ch.d_recs.p, ch.d_idx.p);
+  if (ch.max_nq > 0) hipLaunchKernelGGL(k_ob_corr, dim3(ch.max_nq, 1), dim3(64), 0, s, ch.d_recs, ch.d_idx.p);
   d_sel_.reserve(std::max<size_t>(3 * nq, 1));
   if (nq) hipLaunchKernelGGL(k_odo_sel, dim3(cdiv(nq, 256)), dim3(256), 0, s, ch.h_recs[0].a, d_state_.p, d_sel_.p);
   LIO_HIP(hipGetLastError());
@@ -940,7 +800,7 @@ void OdometryDev::Rows(const float *sharp, size_t n_sharp, const float *flat, si
   if (n_sharp) LIO_HIP(hipMemcpyAsync(ch.d_idx.p, corner_idx, 2 * n_sharp * sizeof(int), hipMemcpyHostToDevice, s));
   if (n_flat) LIO_HIP(hipMemcpyAsync(ch.d_idx.p + 2 * n_sharp, surf_idx, 3 * n_flat * sizeof(int), hipMemcpyHostToDevice, s));
   const int nb = ch.max_nb;
-  hipLaunchKernelGGL(k_ob_rows, dim3(nb, 1), dim3(ODO_ROW_THREADS), 0, s, ch.d_recs.p, ch.d_idx.p, iter, ch.d_partials.p);
+  hipLaunchKernelGGL(k_ob_rows, dim3(nb, 1), dim3(ODO_ROW_THREADS), 0, s, ch.d_recs, ch.d_idx.p, iter, ch.d_partials.p);
   d_sel_.reserve(std::max<size_t>(7 * nq, 1));
   DBuf<uint8_t> ok_dev;
   ok_dev.reserve(std::max<size_t>(nq, 1));

@@ -332,6 +332,17 @@ VOX_SORT_SAMPLE, VOX_SORT_SINGLE, VOX_SORT_LIBRARY = 0, 1, 2   # LIO_VOX_SORT_* 
 VOX_SORT_SINGLE_MAX, VOX_SORT_BUCKET_CAP, VOX_SORT_MEAN_BUCKET, VOX_SORT_OVERSAMPLE = 4096, 4096, 384, 8   # the sizing rule of the header
 
 
+# include/lio_seg_bounds.h: the bounds pass the sensor chains share, on caller-given clouds (the product only, attached like _VOX_SORT_SIGS)
+class SegBoundsOut(C.Structure):
+    _fields_ = [("mn", C.c_float * 3), ("mx", C.c_float * 3), ("minb", C.c_int32 * 3), ("divb", C.c_int32 * 3), ("overflow", C.c_int32),
+                ("n_valid", C.c_int32)]
+
+
+_SEG_BOUNDS_SIGS = {
+    "lio_seg_bounds": (C.c_int, [_c_float_pp, _c_size_p, C.c_int, C.c_float, C.POINTER(SegBoundsOut)]),
+}
+
+
 def _dp(a):
     return None if a is None else a.ctypes.data_as(c_double_p)
 
@@ -386,7 +397,7 @@ class LioLib:
                 fn.restype = res
                 fn.argtypes = args
             # a build from before the sample sort still loads (the A/B tools take one as --parent-lib); only a call to these fails there
-            for name, (res, args) in _VOX_SORT_SIGS.items():
+            for name, (res, args) in list(_VOX_SORT_SIGS.items()) + list(_SEG_BOUNDS_SIGS.items()):
                 fn = getattr(self.dll, name, None)
                 if fn is not None:
                     fn.restype = res
@@ -478,6 +489,16 @@ class LioLib:
         out = (C.c_uint64 * 3)()
         _chk(self.dll.lio_vox_sort_stats(out), "lio_vox_sort_stats")
         return tuple(int(v) for v in out)
+
+    def seg_bounds(self, clouds, inv_leaf):
+        """lio_seg_bounds (include/lio_seg_bounds.h): one bounds pass over all `clouds` -> per cloud dict(mn, mx, minb, divb, overflow, n_valid)"""
+        cs = [_f32(c).reshape(-1, 4) for c in clouds]
+        ptrs = (c_float_p * len(cs))(*[_fp(c) if c.shape[0] else None for c in cs])
+        ns = (C.c_size_t * len(cs))(*[c.shape[0] for c in cs])
+        out = (SegBoundsOut * len(cs))()
+        _chk(self.dll.lio_seg_bounds(ptrs, ns, len(cs), float(inv_leaf), out), "lio_seg_bounds")
+        return [dict(mn=np.array(o.mn, np.float32), mx=np.array(o.mx, np.float32), minb=np.array(o.minb, np.int32), divb=np.array(o.divb, np.int32),
+                     overflow=int(o.overflow), n_valid=int(o.n_valid)) for o in out]
 
     def voxel_grid(self, xyzi, leaf):
         xyzi = _f32(xyzi).reshape(-1, 4)

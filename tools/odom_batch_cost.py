@@ -10,6 +10,8 @@ min - max over the steps after the warm-up; a GPU is required.
 
 --parent-lib PATH additionally times lio_odom_process ALONE of this tree against another build of the product (the parent commit's
 liblio_hip.so) on the same sweeps, alternating, the order swapped every pair: what a change of the chain costs the one-sensor call.
+--this-lib PATH takes another build in this tree's place (tools/map_batch_cost.py has the same): with the other build and a byte copy of
+it under another name the lines against --parent-lib are an A/A run, whose gap is what a gap between this tree and the parent is held against.
 
 --frontend times instead what feeding the batch from the PointProcessor on the device buys (include/lio_frontend_batch.h).  B processors
 take the sweep of the step through ONE lio_pp_process_batch (not timed); then, alternating as above and with equal bits asserted at
@@ -196,6 +198,7 @@ def main():
     ap.add_argument("--batches", default="1,8,64")
     ap.add_argument("--kinds", default="indoor,outdoor")
     ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--this-lib", default=None)
     ap.add_argument("--frontend", action="store_true")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -205,7 +208,7 @@ def main():
     assert torch.cuda.is_available(), "needs a GPU"
     from lio_amd import capi
 
-    hip = capi.load_hip()
+    hip = load_parent(args.this_lib) if args.this_lib else capi.load_hip()   # --this-lib: another build in this tree's place (A/A runs)
     parent = load_parent(args.parent_lib) if args.parent_lib else None
     results = []
     for kind in args.kinds.split(",") if args.frontend else []:
