@@ -8,8 +8,9 @@
 //
 // The eigensolver is the Householder + implicit-QL pair (tridiag_ql_lds below): the method of the host path and of the reference's
 // Eigen::SelfAdjointEigenSolver.  Which eigenvalues of the badly graded S (entries from 1e9 down to 1e-4) fall on which side of the
-// absolute 1e-8 cut is rounding noise on every such path (tests/golden/README.md); the tests pin the invariants (J^T J, J^T r, r^T r, the
-// kept spectrum), not single eigenvectors.
+// absolute 1e-8 cut is rounding noise on every such path (tests/golden/README.md); tests/test_gpu_marg_device.py pins the invariants
+// (J^T J, J^T r, r^T r, the kept spectrum) on such systems, tests/test_gpu_marg_tail.py the eigenpairs themselves against the Schur
+// complement in 40 digits on systems whose spectra keep clear of the cut (structured, clustered, indefinite, rank-deficient Amm, every m).
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -279,12 +280,62 @@ __device__ int tridiag_ql_lds(double *A, double *Z, int n, int ld, double *work,
   return sweeps;   // (wave 0's count; thread 0 reports it)
 }
 
+// Parameters that nothing couples to (a row of S that is zero off its diagonal) go to the front, in their order: the reduction leaves
+// the leading indices alone (u_k = 0 there) and QL deflates them first, before any shift, so their eigenvalue is the diagonal entry and
+// their eigenvector the unit vector bit for bit.  Left in the middle, index i is the sub-diagonal position of row i + 1, and the reflector
+// of that row mixes it into the rest.  pos[i]: where parameter i stands in the permuted matrix; perm: its inverse; iso: n ints of scratch.
+// Returns whether anything moved (uniform).  No such row, or all of them in front already: S is not touched.  V is scratch (the
+// eigensolver initialises it itself).  Kept out of line: inlined, its few registers cost marg_schur_body 54 more and a spill.
+__device__ __noinline__ bool marg_uncoupled_to_front(double *S, double *V, int n, int ld, int *iso, int *pos, int *perm, int *flag) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwave = MARG_THREADS / 64;
+  for (int i = wave; i < n; i += nwave) {
+    bool coupled = false;
+    for (int j = lane; j < n; j += 64) coupled = coupled || (j != i && !(S[i * ld + j] == 0.0));
+    const bool any = __ballot(coupled) != 0ull;
+    if (lane == 0) iso[i] = any ? 0 : 1;
+  }
+  __syncthreads();
+  if (wave == 0) {
+    const int k0 = lane, k1 = lane + 64;
+    const bool i0 = k0 < n && iso[k0] != 0, i1 = k1 < n && iso[k1] != 0;
+    const unsigned long long b0 = __ballot(i0), b1 = __ballot(i1), below = (1ull << lane) - 1ull;
+    const int n0 = __popcll(b0), n_iso = n0 + __popcll(b1);
+    const int r0 = __popcll(b0 & below), r1 = n0 + __popcll(b1 & below);   // the uncoupled ones in front of k0, of k1
+    const int p0 = i0 ? r0 : n_iso + k0 - r0, p1 = i1 ? r1 : n_iso + k1 - r1;
+    if (k0 < n) { pos[k0] = p0; perm[p0] = k0; }
+    if (k1 < n) { pos[k1] = p1; perm[p1] = k1; }
+    const bool moved = __ballot((k0 < n && p0 != k0) || (k1 < n && p1 != k1)) != 0ull;
+    if (lane == 0) flag[0] = moved ? 1 : 0;
+  }
+  __syncthreads();
+  const bool moved = flag[0] != 0;
+  if (moved) {   // S <- P S P^T through V
+    for (int i = wave; i < n; i += nwave)
+      for (int j = lane; j < n; j += 64) V[i * ld + j] = S[perm[i] * ld + perm[j]];
+    __syncthreads();
+    for (int i = wave; i < n; i += nwave)
+      for (int j = lane; j < n; j += 64) S[i * ld + j] = V[i * ld + j];
+    __syncthreads();
+  }
+  return moved;
+}
+// ... and the eigenvectors' rows back into the parameters' order afterwards, through `tmp` (n x n, ld)
+__device__ __noinline__ void marg_rows_to_parameter_order(double *tmp, double *V, int n, int ld, const int *pos) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwave = MARG_THREADS / 64;
+  for (int i = wave; i < n; i += nwave)
+    for (int j = lane; j < n; j += 64) tmp[i * ld + j] = V[pos[i] * ld + j];
+  __syncthreads();
+  for (int i = wave; i < n; i += nwave)
+    for (int j = lane; j < n; j += 64) V[i * ld + j] = tmp[i * ld + j];
+  __syncthreads();
+}
+
 struct MargLds {
   double *S, *V;      // np2 x ld2 each
   double *a1, *v1;    // 16 x 17 each: the marginalised block and its eigenvectors
   double *ainv;       // 16 x 16
   double *T;          // n x 16
-  double *bs, *ev, *w, *cs;
+  double *bs, *ev, *w, *cs;   // cs: np2 + 16 doubles, holds the permutation of the uncoupled parameters (2 np2 ints)
   double *work;       // the eigensolver's vectors: 9 max(n, 16) + 16
   int *ord, *flag;
 };
@@ -384,12 +435,16 @@ __device__ void marg_schur_body(const double *__restrict__ A, const double *__re
       }
   }
   __syncthreads();
+  // ---- parameters that nothing couples to go to the front (marg_uncoupled_to_front); the permutation lives over cs, which nothing else uses
+  int *pos = reinterpret_cast<int *>(L.cs);
+  const bool moved = marg_uncoupled_to_front(L.S, L.V, n, ld2, L.ord, pos, pos + np2, L.flag);
   stamp(3);
   const int sweeps2 = tridiag_ql_lds(L.S, L.V, n, ld2, L.work, stamps ? stamps + 8 : nullptr);
   stamp(4);
   // ---- ascending eigenvalues (rank sort; ties by index), then the square-root factors
   for (int i = tid; i < n; i += MARG_THREADS) L.ev[i] = L.S[i * ld2 + i];
   __syncthreads();
+  if (moved) marg_rows_to_parameter_order(L.S, L.V, n, ld2, pos);   // (uniform; S is dead: its diagonal is read)
   for (int i = tid; i < n; i += MARG_THREADS) {
     const double x = L.ev[i];
     int rank = 0;
@@ -608,7 +663,7 @@ bool MargSchurDev::Run(const double *A, const double *b, int m, int n, double ep
   last_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   static const bool dbg = std::getenv("LIO_DEBUG_TIMING") != nullptr;
   if (dbg)
-    std::fprintf(stderr, "[lio_hip marg timing] device Schur + eigen m %d n %d: %.3f ms (Jacobi sweeps %d + %d)\n", m, n, last_ms_,
+    std::fprintf(stderr, "[lio_hip marg timing] device Schur + eigen m %d n %d: %.3f ms (QL sweeps %d + %d)\n", m, n, last_ms_,
                  int(h_out[size_t(n) * n + 2 * n]), int(h_out[size_t(n) * n + 2 * n + 1]));
   return true;
 }

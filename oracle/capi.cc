@@ -1237,13 +1237,13 @@ int lio_marginalize_schur(const double *A, const double *b, int m, int n, double
   const int pos = m + n;
   Mat Am(pos, pos);
   for (int i = 0; i < pos * pos; ++i) Am.a[i] = A[i];
-  std::vector<double> bv(b, b + pos), lr;
+  std::vector<double> bv(b, b + pos), lr, ev;
   Mat lj;
-  MarginalizeSchur(Am, bv, m, n, lj, lr);
+  MarginalizeSchur(Am, bv, m, n, lj, lr, &ev);
   for (int i = 0; i < n * n; ++i) lin_jac[i] = lj.a[i];
   for (int i = 0; i < n; ++i) lin_res[i] = lr[i];
-  if (evals)   // row k of lin_jac = sqrt(s_k) v_k^T with |v_k| = 1
-    for (int k = 0; k < n; ++k) { double s2 = 0; for (int i = 0; i < n; ++i) s2 += lj.a[size_t(k) * n + i] * lj.a[size_t(k) * n + i]; evals[k] = s2; }
+  // the eigenvalues themselves, ascending as lio_c.h promises (the squared norms of lin_jac's rows round tied eigenvalues apart, in any order)
+  if (evals) for (int k = 0; k < n; ++k) evals[k] = ev[k];
   return LIO_OK;
 }
 int orc_marginalize_schur(const double *A, const double *b, int m, int n, double *lin_jac, double *lin_res) {

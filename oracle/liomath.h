@@ -387,7 +387,8 @@ inline void sym_eigen(int n, const T *A_in, T *evals, T *V) {
   }
   std::vector<int> order(n);
   for (int i = 0; i < n; ++i) order[i] = i;
-  std::sort(order.begin(), order.end(), [&](int a, int b) { return A[size_t(a) * n + a] < A[size_t(b) * n + b]; });
+  // (stable: equal eigenvalues stay in the order of their diagonal positions, which is what the product's rank sort gives them)
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return A[size_t(a) * n + a] < A[size_t(b) * n + b]; });
   for (int k = 0; k < n; ++k) {
     evals[k] = T(A[size_t(order[k]) * n + order[k]]);
     for (int i = 0; i < n; ++i) V[size_t(i) * n + k] = T(U[size_t(i) * n + order[k]]);

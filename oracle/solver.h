@@ -496,7 +496,9 @@ static inline SolveSummary SolveDogleg(WindowProblem &P, int max_num_iterations,
 // The dense tail of MarginalizationInfo::Marginalize (MarginalizationFactor.cc:271-302) on an assembled (A, b) whose first m
 // rows / columns are the dropped blocks: Amm^+ by eigen-decomposition with eigenvalues <= 1e-8 zeroed, Schur complement,
 // second eigen-decomposition -> linearized_jacobians = sqrt(S) V^T, linearized_residuals = sqrt(S^+) V^T b.
-static inline void MarginalizeSchur(const Mat &A, const std::vector<double> &b, int m, int n, Mat &lin_jac, std::vector<double> &lin_res) {
+// evals (optional): the n eigenvalues of the Schur complement, ascending, cut ones included as they came out.
+static inline void MarginalizeSchur(const Mat &A, const std::vector<double> &b, int m, int n, Mat &lin_jac, std::vector<double> &lin_res,
+                                    std::vector<double> *evals = nullptr) {
   const double eps = 1e-8;
   Mat Amm(m, m);
   for (int i = 0; i < m; ++i) for (int j = 0; j < m; ++j) Amm(i, j) = 0.5 * (A(i, j) + A(j, i));
@@ -517,8 +519,16 @@ static inline void MarginalizeSchur(const Mat &A, const std::vector<double> &b, 
   std::vector<double> Tb = matvec(T, bmm);
   Mat S(n, n); std::vector<double> bs(n);
   for (int i = 0; i < n; ++i) { bs[i] = brr[i] - Tb[i]; for (int j = 0; j < n; ++j) S(i, j) = Arr(i, j) - TA(i, j); }
+  // SelfAdjointEigenSolver reads the lower triangle only (:293), the Jacobi sweeps of sym_eigen read both: an A that is not symmetric
+  // leaves an S that is not, and its lower triangle is mirrored (as oracle/ref_shim/Eigen/Eigen does).  A symmetric A — every A the
+  // estimator assembles — leaves triangles that differ by the rounding of T Amr only; that S goes in as it is, so the chains recorded
+  // from this oracle (tests/golden) keep their bits.
+  bool a_symmetric = true;
+  for (int i = 0; i < m + n && a_symmetric; ++i) for (int j = 0; j < i; ++j) if (A(i, j) != A(j, i)) { a_symmetric = false; break; }
+  if (!a_symmetric) for (int i = 0; i < n; ++i) for (int j = i + 1; j < n; ++j) S(i, j) = S(j, i);
   std::vector<double> ev2(n); Mat V2(n, n);
   sym_eigen<double>(n, S.a.data(), ev2.data(), V2.a.data());
+  if (evals) *evals = ev2;
   lin_jac = Mat(n, n); lin_res.assign(n, 0.0);
   for (int k = 0; k < n; ++k) {
     double Sk = ev2[k] > eps ? ev2[k] : 0.0, Sik = ev2[k] > eps ? 1.0 / ev2[k] : 0.0;

@@ -1,5 +1,5 @@
-"""Marginalization's dense tail on the device (csrc/marg_kernels.hip; MarginalizationFactor.cc:271-302): the Jacobi
-eigensolver + fp64-MFMA Schur complement against the numpy second source (tests/golden/second_source.py), the oracle, and —
+"""Marginalization's dense tail on the device (csrc/marg_kernels.hip; MarginalizationFactor.cc:271-302): the Householder +
+implicit-QL eigensolver + fp64-MFMA Schur complement against the numpy second source (tests/golden/second_source.py), the oracle, and —
 through the estimator with device_solve = 1 — against the host path and the oracle on a chain of solves."""
 import os
 import sys
@@ -52,6 +52,7 @@ def test_device_schur_and_eigen_vs_numpy(hip, oracle, m, n, n_null):
     # the null directions come out as rounding noise (|s| ~ 1e-12 here) on both sides and are cut
     _compare(J, r, s, J2, r2, s2, 1e-7)
     Jo, ro, so = oracle.marginalize_schur(A, b, m)
+    assert np.all(np.diff(so) >= 0)
     _compare(J, r, s, Jo, ro, np.where(so > 0, so, 0.0), 1e-7)
 
 
