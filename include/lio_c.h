@@ -204,7 +204,14 @@ lio_map *lio_map_create(const lio_map_config *cfg_or_null);
 void lio_map_destroy(lio_map *);
 /* Handlers + PointMapping::Process (:765-1110) for one sweep: corner_last / surf_last are the odometry's
  * last_corner_cloud_/last_surf_cloud_, transform_sum the accumulated odometry.  Outputs (any may be null):
- * transform_aft_mapped_, iterations run, rows selected in the last round. */
+ * transform_aft_mapped_, iterations run, rows selected in the last round.
+ * Range of the product's cube window: every map point carries the offset of its cube from the window's centre cube packed into ten bits
+ * per axis (-512 .. 511), and the centre moves by one with every cube the window shifts (laser_cloud_cen_*, unbounded in the reference
+ * and the oracle).  A window fits while its centre stays in [-491, 512] along x and y and in [-501, 512] along z, which no path can
+ * leave within 24.7 km of the map's origin along x or y and 25.2 km along z (50 m cubes; the sensor's cube is kept 3 cubes inside
+ * the window, so the centre a position needs depends on the way there).  A pose whose window would not fit makes lio_map_process and
+ * its batched form return LIO_ERR_CAPACITY before any device work and with every handle of the call unchanged; lio_map_update_map_database checks the same (it cannot move the window, so it never fails this on a handle whose last
+ * process succeeded). */
 int lio_map_process(lio_map *, const float *corner_last_xyzi, size_t n_corner, const float *surf_last_xyzi, size_t n_surf,
                     const lio_transform_f *transform_sum, lio_transform_f *transform_aft_mapped_out, int *iterations_out,
                     int *num_selected_out);
@@ -218,15 +225,20 @@ int lio_map_set_init_flag(lio_map *, int imu_inited);
 int lio_map_set_transform_tobe_mapped(lio_map *, const lio_transform_f *);
 int lio_map_get_transform_tobe_mapped(const lio_map *, lio_transform_f *out);
 /* UpdateMapDatabase (:1112-1208): add the down-sampled stacks (sensor frame) at `transform`, then VoxelGrid every
- * cube of valid_idx (indices relative to cube_center, re-based on the current centre as :1171-1186 does). */
+ * cube of valid_idx (indices relative to cube_center, re-based on the current centre as :1171-1186 does; entries that leave the window
+ * are skipped, duplicates count once).  An index >= 4851 is LIO_ERR_ARG; more than 125 distinct cubes inside the window are
+ * LIO_ERR_CAPACITY in the product (the reference's own lists hold at most the 5 x 5 x 5 neighbourhood).  Either way nothing changes.
+ * The clouds of lio_map_get_cloud are not touched: they stay those of the last lio_map_process. */
 int lio_map_update_map_database(lio_map *, const float *corner_ds_xyzi, size_t n_corner, const float *surf_ds_xyzi, size_t n_surf,
                                 const uint32_t *valid_idx, size_t n_valid, const lio_transform_f *transform,
                                 const int cube_center[3]);
-/* clouds of the last Process; returns the count, copies when out is non-null */
+/* clouds of the last Process, until the next Process (a lio_map_update_map_database or lio_est_refresh_map in between does not change
+ * them); returns the count, copies when out is non-null */
 size_t lio_map_get_cloud(const lio_map *, int which, float *xyzi_or_null);
 /* one cube of laser_cloud_corner_array_ (cls 0) / laser_cloud_surf_array_ (cls 1); cube_idx = ToIndex(i,j,k) */
 size_t lio_map_get_cube(const lio_map *, int cls, uint32_t cube_idx, float *xyzi_or_null);
-/* laser_cloud_cen_{length,width,height}_ and laser_cloud_valid_idx_ (<= 125 entries); returns the valid count */
+/* laser_cloud_cen_{length,width,height}_ and laser_cloud_valid_idx_ (<= 125 entries) in the order the selection loop of the last Process
+ * pushed them (:933-986: i outermost, k innermost, which is not ascending index order); returns the valid count */
 size_t lio_map_get_cube_state(const lio_map *, int cube_center_out[3], uint32_t *valid_idx_or_null);
 /* score_point_coeff_ (:725-750): descending score; point = p_ori (xyzi), coeff = abs_coeff (4 floats). Returns the count. */
 size_t lio_map_get_score_point_coeff(const lio_map *, float *score_or_null, float *point_xyzi_or_null, float *coeff_or_null);

@@ -46,7 +46,8 @@ extern "C" {
  *
  * Arguments are checked before any device work and before any handle changes: a null handle or array (transform_sum included),
  * n_sensors < 1, a null cloud with a non-zero count or the same handle twice give LIO_ERR_ARG; n_sensors > LIO_MAP_BATCH_MAX_SENSORS gives
- * LIO_ERR_CAPACITY.  A handle borrowed from an estimator (lio_est_map, lio_ext.h) gives LIO_ERR_STATE: its estimator steps it, and taking
+ * LIO_ERR_CAPACITY, and so does a sensor whose pose would carry its cube window beyond the range of the packed cube keys (about 24.7 km
+ * from the map's origin, see lio_map_process in lio_c.h).  A handle borrowed from an estimator (lio_est_map, lio_ext.h) gives LIO_ERR_STATE: its estimator steps it, and taking
  * such handles into a batch is left to a later version.  A device failure gives LIO_ERR_DEVICE.
  *
  * Ownership.  Results live in each handle's own buffers, as after lio_map_process.  The chain's scratch (record tables, the concatenated

@@ -136,6 +136,10 @@ class MappingDev {
     bool relayout[2];
   };
   void StepBegin(const Rigid<float> &transform_sum, Step &st);           // the call's resets, TransformAssociateToMap / the 4-D one
+  Rigid<float> AssociatedPose(const Rigid<float> &transform_sum) const;  // the transform_tobe_mapped_ StepBegin would leave; changes nothing
+  void WindowAt(const Rigid<float> &T0, int cen[3], int cc[3]) const;    // the centre the window shift would leave at T0 and the sensor's cube
+  static bool CenFits(const int cen[3]);                                 // every cube offset of a window centred so fits the packed key
+  void KeepFromMap();                                                    // the from-map clouds into their own buffers before the pool is rewritten
   void StepWindow(Step &st);                                             // cube bookkeeping, valid set, surround set, LayoutLaunch where the layout changed
   void StepFilterLaunch(const Step &st);                                 // the two VoxelGrids, the surf one on stream2_, joined back into stream_
   bool StepOptimizes();                                                  // MapBuilder's skip_count: false on a call that only updates the map (and does what that call does)
@@ -159,6 +163,8 @@ class MappingDev {
   bool score_ready_ = false;
   size_t n_from_map_[2] = {0, 0};  // sizes of laser_cloud_{corner,surf}_from_map_ of the last Process
   bool from_map_in_u_ = false;      // the map update moved them into the work list
+  bool from_map_kept_ = false;      // a direct UpdateMapDatabase copied them into from_map_keep_ before it rewrote the pool and the work list
+  DBuf<float4> from_map_keep_[2];
   // surround-map assembly: bin per point of [corner pool | surf pool], one 8-bit seg_sort pass over it, gather
   DBuf<uint32_t> sur_bin_, sur_bin2_, sur_src_, sur_hist_;
   DBuf<SegDesc> sur_desc_;

@@ -22,6 +22,8 @@ namespace {
 __host__ __device__ inline uint32_t pack_cube(int ai, int aj, int ak) {
   return (uint32_t(ai + 512) << 20) | (uint32_t(aj + 512) << 10) | uint32_t(ak + 512);
 }
+// what pack_cube holds per axis: the offsets of a window's cubes from its centre, [-cen, dim - cen), must lie inside (MappingDev::CenFits)
+constexpr int kCubeOffsetMin = -512, kCubeOffsetMax = 511;
 __host__ __device__ inline void unpack_cube(uint32_t k, int &ai, int &aj, int &ak) {
   ai = int((k >> 20) & 1023u) - 512; aj = int((k >> 10) & 1023u) - 512; ak = int(k & 1023u) - 512;
 }
@@ -378,7 +380,16 @@ MappingDev::~MappingDev() {
   if (stream_) (void)hipStreamDestroy(stream_);
 }
 
+// cen_ moves by one per cube the window shifts (StepWindow), without bound; the keys keep ten bits per axis
+bool MappingDev::CenFits(const int cen[3]) {
+  const int dims[3] = {L, Wd, H};
+  for (int d = 0; d < 3; ++d)
+    if (-cen[d] < kCubeOffsetMin || dims[d] - 1 - cen[d] > kCubeOffsetMax) return false;
+  return true;
+}
+
 MapValidSet MappingDev::MakeValidSet(const uint32_t *valid_idx, size_t n, const int cen_of_idx[3]) const {
+  if (!CenFits(cen_)) throw CapacityError("PointMapping: the cube window lies beyond the range of the packed cube keys");
   MapValidSet vs;
   std::memset(&vs, 0, sizeof(vs));
   const int dims[3] = {L, Wd, H};
@@ -395,7 +406,7 @@ MapValidSet MappingDev::MakeValidSet(const uint32_t *valid_idx, size_t n, const 
   }
   std::sort(keys.begin(), keys.end());
   keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
-  if (keys.size() > LIO_MAP_MAX_VALID) throw std::runtime_error("PointMapping: more than 125 valid cubes");
+  if (keys.size() > LIO_MAP_MAX_VALID) throw CapacityError("PointMapping: more than 125 valid cubes");
   vs.n = int(keys.size());
   for (int k = 0; k < vs.n; ++k) vs.key[k] = keys[k];
   return vs;
@@ -493,8 +504,23 @@ void MappingDev::UpdateFinish(ClassMap &m) {
   m.n = m.n_rest + m.n_valid;
 }
 
+// laser_cloud_*_from_map_ stay what the last Process selected until the next Process (GetCloud).  They lie in the pool's valid tail or, after
+// that Process's own update, at the head of the work list; an update from outside a Process rewrites both, so its first one copies them out.
+void MappingDev::KeepFromMap() {
+  if (from_map_kept_) return;
+  for (int c = 0; c < 2; ++c) {
+    const size_t n = n_from_map_[c];
+    if (!n) continue;
+    const ClassMap &m = cls_[c];
+    from_map_keep_[c].reserve(n);
+    LIO_HIP(hipMemcpyAsync(from_map_keep_[c].p, from_map_in_u_ ? m.u_pts.p : m.pool.p + m.n_rest, n * sizeof(float4), hipMemcpyDeviceToDevice, stream_));
+  }
+  from_map_kept_ = true;
+}
+
 void MappingDev::UpdateMapDatabase(const float *corner_ds, size_t n_corner, const float *surf_ds, size_t n_surf, const uint32_t *valid_idx,
                                    size_t n_valid, const Rigid<float> &T, const int cube_center[3]) {
+  (void)MakeValidSet(valid_idx, n_valid, cube_center);   // a list or a window the keys cannot hold is refused before the first copy
   const float *src[2] = {corner_ds, surf_ds};
   const size_t cnt[2] = {n_corner, n_surf};
   for (int c = 0; c < 2; ++c) {
@@ -512,7 +538,8 @@ void MappingDev::UpdateMapDatabase(const float4 *d_corner_ds, size_t n_corner, c
     LIO_HIP(hipEventRecord(ev_fork_, producer));
     LIO_HIP(hipStreamWaitEvent(s, ev_fork_, 0));
   }
-  const MapValidSet vs = MakeValidSet(valid_idx, n_valid, cube_center);
+  const MapValidSet vs = MakeValidSet(valid_idx, n_valid, cube_center);   // (throws before anything of the handle has changed)
+  KeepFromMap();
   bool relayout[2];
   for (int c = 0; c < 2; ++c) {
     relayout[c] = !LayoutMatches(cls_[c], vs);
@@ -611,43 +638,57 @@ void MappingDev::StepBegin(const Rigid<float> &sum, Step &st) {
   transform_sum_ = sum;
   score_ready_ = false;
   iterations_ = 0; num_selected_ = 0; degenerate_ = false; kz_ = 0;
-  const bool builder = cfg_.map_builder != 0;
-  if (builder && !system_init_) {  // MapBuilder::ProcessMap (MapBuilder.cc:227-232)
+  st.T0 = AssociatedPose(sum);
+  if (cfg_.map_builder && !system_init_) {  // MapBuilder::ProcessMap (MapBuilder.cc:227-232)
     system_init_ = true;
-    transform_bef_mapped_ = transform_tobe_mapped_ = transform_aft_mapped_ = transform_sum_;
+    transform_bef_mapped_ = transform_aft_mapped_ = transform_sum_;
   }
+  transform_tobe_mapped_ = st.T0;
+}
+
+Rigid<float> MappingDev::AssociatedPose(const Rigid<float> &sum) const {
+  const bool builder = cfg_.map_builder != 0;
+  Rigid<float> bef = transform_bef_mapped_, tobe = transform_tobe_mapped_;
+  if (builder && !system_init_) bef = tobe = sum;  // MapBuilder::ProcessMap (MapBuilder.cc:227-232)
   if (builder || !imu_inited_) {  // TransformAssociateToMap (:755-758) / Transform4DAssociateToMap (MapBuilder.cc:55-75)
-    const Rigid<float> sumT = fromAffine(linearOf(transform_sum_), transform_sum_.pos);
-    const Rigid<float> incre = compose(rinverse(transform_bef_mapped_), sumT);
-    const Rigid<float> full = compose(transform_tobe_mapped_, incre);
+    const Rigid<float> sumT = fromAffine(linearOf(sum), sum.pos);
+    const Rigid<float> incre = compose(rinverse(bef), sumT);
+    const Rigid<float> full = compose(tobe, incre);
     if (builder && cfg_.enable_4d) {
       // keep the odometry's roll/pitch, take only the yaw of the increment
       const Vec3<double> r0 = r2ypr_deg(to_double(toRot(normalized(full.rot))));
-      const Vec3<double> r00 = r2ypr_deg(to_double(toRot(normalized(transform_sum_.rot))));
+      const Vec3<double> r00 = r2ypr_deg(to_double(toRot(normalized(sum.rot))));
       const float y = float(double(float(r0.x - r00.x)) / 180.0 * M_PI);
       Mat3<float> Rz = Mat3<float>::identity();
       Rz(0, 0) = std::cos(y); Rz(0, 1) = -std::sin(y); Rz(1, 0) = std::sin(y); Rz(1, 1) = std::cos(y);
-      transform_tobe_mapped_.pos = full.pos;
-      transform_tobe_mapped_.rot = fromRot(Rz * toRot(normalized(transform_sum_.rot)));
+      tobe.pos = full.pos;
+      tobe.rot = fromRot(Rz * toRot(normalized(sum.rot)));
     } else {
-      transform_tobe_mapped_ = full;
+      tobe = full;
     }
   }
-  st.T0 = transform_tobe_mapped_;
+  return tobe;
+}
+
+// sensor cube and window shift (:808-925); absolute keys make the shift a change of the centre only
+void MappingDev::WindowAt(const Rigid<float> &T0, int cen[3], int cc[3]) const {
+  const float posv[3] = {T0.pos.x, T0.pos.y, T0.pos.z};
+  const int dims[3] = {L, Wd, H};
+  for (int d = 0; d < 3; ++d) {
+    cen[d] = cen_[d];
+    cc[d] = cube_coord(posv[d], cen[d]);
+    while (cc[d] < 3) { ++cc[d]; ++cen[d]; }
+    while (cc[d] >= dims[d] - 3) { --cc[d]; --cen[d]; }
+  }
 }
 
 void MappingDev::StepWindow(Step &st) {
   const Rigid<float> &T0 = st.T0;
   point_on_z_axis(T0, pz_);
-  // sensor cube and window shift (:808-925); absolute keys make the shift a change of cen_ only
   const float posv[3] = {T0.pos.x, T0.pos.y, T0.pos.z};
-  const int dims[3] = {L, Wd, H};
-  int cc[3];
-  for (int d = 0; d < 3; ++d) {
-    cc[d] = cube_coord(posv[d], cen_[d]);
-    while (cc[d] < 3) { ++cc[d]; ++cen_[d]; }
-    while (cc[d] >= dims[d] - 3) { --cc[d]; --cen_[d]; }
-  }
+  int cc[3], cen[3];
+  WindowAt(T0, cen, cc);
+  for (int d = 0; d < 3; ++d) cen_[d] = cen[d];
   // cubes of the 5x5x5 neighbourhood with a corner inside the +-60 deg cone (:938-989)
   valid_idx_.clear();
   surround_idx_.clear();
@@ -707,7 +748,7 @@ bool MappingDev::StepOptimizes() {
   if (!cfg_.map_builder) return true;
   const bool optimise = odom_count_ % cfg_.skip_count == 0;
   if (!optimise) {
-    n_from_map_[0] = cls_[0].n_valid; n_from_map_[1] = cls_[1].n_valid; from_map_in_u_ = false;
+    n_from_map_[0] = cls_[0].n_valid; n_from_map_[1] = cls_[1].n_valid; from_map_in_u_ = from_map_kept_ = false;
     TransformUpdate();
   }
   ++odom_count_;
@@ -816,7 +857,7 @@ void MapChain::MakeGrids() {
     MappingDev &d = *m[k];
     if (!d.StepOptimizes()) continue;   // a skipped MapBuilder call
     d.n_from_map_[0] = d.cls_[0].n_valid; d.n_from_map_[1] = d.cls_[1].n_valid;
-    d.from_map_in_u_ = false;
+    d.from_map_in_u_ = d.from_map_kept_ = false;
     if (!(d.cls_[0].n_valid > 10 && d.cls_[1].n_valid > 100)) continue;   // :327-329 (no TransformUpdate either)
     if (d.cls_[0].n_stack + d.cls_[1].n_stack == 0) {   // every round has < 50 rows: the loop runs dry, then TransformUpdate
       d.iterations_ = d.cfg_.num_max_iterations;
@@ -956,6 +997,12 @@ void MappingDev::ProcessBatch(MappingDev *const *m, int n, const float *const *c
                               const size_t *n_surf, const Rigid<float> *sums) {
   for (int k = 0; k < n; ++k)
     if (n_corner[k] > size_t(INT_MAX) - 255 || n_surf[k] > size_t(INT_MAX) - 255) throw CapacityError("lio_map_process_batch: a cloud exceeds 2^31 points");
+  // a pose whose window the packed cube keys cannot hold is refused before any handle changes and before the first launch
+  for (int k = 0; k < n; ++k) {
+    int cen[3], cc[3];
+    m[k]->WindowAt(m[k]->AssociatedPose(sums[k]), cen, cc);
+    if (!CenFits(cen)) throw CapacityError("lio_map_process_batch: a sensor's cube window lies beyond the range of the packed cube keys");
+  }
   // the round launches carry these as launch parameters: without common values there is no common chain, a chain of one per handle
   for (int k = 1; k < n; ++k) {
     const lio_map_config &a = m[0]->cfg_, &b = m[k]->cfg_;
@@ -986,7 +1033,7 @@ size_t MappingDev::GetCloud(int which, float *out) {
   if (which < 2) { src = m.stack_ds.p; n = m.n_stack; }
   else {
     n = n_from_map_[which & 1];
-    src = from_map_in_u_ ? m.u_pts.p : m.pool.p + m.n_rest;
+    src = from_map_kept_ ? from_map_keep_[which & 1].p : from_map_in_u_ ? m.u_pts.p : m.pool.p + m.n_rest;
   }
   if (out && n) {
     LIO_HIP(hipMemcpyAsync(out, src, n * sizeof(float4), hipMemcpyDeviceToHost, s));

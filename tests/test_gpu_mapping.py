@@ -42,7 +42,9 @@ def _compare_cubes(mh, mo, idx_list, atol, strict=True):
             a, b = mh.cube(cls, idx), mo.cube(cls, idx)
             if strict:
                 assert a.shape == b.shape, (cls, idx, a.shape, b.shape)
-                if len(a):
+                if len(a) and atol == 0:   # a pose both sides share to the bit: the cube map is exact (docs/cube_map.md), order included
+                    assert a.tobytes() == b.tobytes(), (cls, idx)
+                elif len(a):
                     np.testing.assert_allclose(a, b, rtol=0, atol=atol)
             else:
                 bad += _cloud_mismatch(a, b, atol)
@@ -100,7 +102,7 @@ def test_mapping_first_frame_and_small_maps(hip, oracle):
         _assert_pose_close(rh["T_aft"], ro["T_aft"])
         _assert_pose_close(mh.transform_tobe_mapped(), mo.transform_tobe_mapped())
     _, vo = mo.cube_state()
-    _compare_cubes(mh, mo, vo, atol=1e-5)
+    _compare_cubes(mh, mo, vo, atol=0)
     # empty inputs are legal
     e = np.zeros((0, 4), np.float32)
     rh, ro = mh.process(e, e, T), mo.process(e, e, T)
@@ -124,7 +126,7 @@ def test_mapping_window_shift_matches_oracle(hip, oracle):
         np.testing.assert_array_equal(vh, vo)
         # every cube of the window, not only the valid ones: the shift must drop exactly what the reference drops
         occupied = [i for i in all_idx if len(mo.cube(1, i)) or len(mo.cube(0, i))]
-        assert _compare_cubes(mh, mo, occupied, atol=1e-4) > 0
+        assert _compare_cubes(mh, mo, occupied, atol=0) > 0
         empty_probe = [i for i in all_idx[::37] if i not in occupied]
         for i in empty_probe:
             assert len(mh.cube(0, i)) == 0 and len(mh.cube(1, i)) == 0
