@@ -189,6 +189,41 @@ int lio_gn_step(int family, const double *sums, const lio_gn_state *state_in, in
 int lio_gn_round(const float *map_xyzi, size_t n_map, const float *stack_xyzi, size_t m, const lio_transform_f *T, float min_match_sq_dis,
                  float min_plane_dis, int lanes_per_query, int32_t *nb_out, double *partials_out, lio_gn_state *state_out);
 
+/* ---- The device-resident trust-region loop (csrc/solve_step.h: k_bw_aux, k_bw_solve_step), stopped early and read out as numbers. */
+
+/* n >= 0 replaces lio_est_config.max_num_iterations for the handle's later solves (read at every solve: the packed problem and the
+ * length of the batch's launch chain); a negative n is LIO_ERR_ARG.  n = 0 stops the device loop behind its first linearisation, n = 1
+ * behind the decision on its first candidate.  The oracle applies it to its own loop. */
+int lio_est_set_max_num_iterations(lio_est *, int n);
+
+/* What the last lio_est_batch_solve left on the device for window `window`: the problem the kernels read, the loop's state and the aux
+ * row of the last launch A that ran for the window (evaluated at `cand`).  Waits for the batch.  LIO_ERR_STATE when the window was not
+ * solved on the device; a null pointer or a window outside the batch is LIO_ERR_ARG.  The oracle returns zeros.  Every array has a
+ * fixed size (the LIO_DSL_* counts below); entries beyond what the window uses are zero.  F = 8 frames, the most a window optimises + 1.
+ *   ints     [0] Wo [1] n [2] ex_col [3] n_prior [4] have_prior [5] use_ex_prior [6] n_keep [7] it [8] successful [9] termination
+ *            [10] need_host [11] ntrace [12] n_pad [13] started [14] done [15] max_iterations
+ *            [16, 144)   prior_col[128]: tangent column of H -> column of the prior, -1: none
+ *            [144, 194)  the kept blocks of the prior, 10 x (kind: 0 pose 1 speed-bias 2 extrinsic, index, size, offset in the prior's
+ *                        tangent vector, offset in x0)
+ *            [194, 201)  present[7] of the IMU factors
+ *   problem  [0, 90) x0 of the kept blocks  [90, 93) ex_prior_pos  [93, 97) ex_prior_rot (w, x, y, z)
+ *            [97 + 470 i, ..) IMU factor i < 7: dp 3 | dq 4 (w, x, y, z) | dv 3 | ba 3 | bg 3 | g 3 | sum_dt | jac 225 | sqrt_info 225
+ *            [3387, ..) the prior the solve READ, np = n_prior: JtJ np x np | lin_jac np x np | lin_res np | Jtr0 np
+ *   state    a parameter set is pose F x 7 (p, q as x y z w) | speed-bias F x 9 | extrinsic 7 = 135 doubles
+ *            [0, 135) x, the accepted point  [135, 270) cand  [270, 354) cand_Rt 7 x 12 (R row-major, t)
+ *            [354, 482) scale  [482, 610) g (scaled)  [610, 614) costs0 (marg, pim, ppp, extrinsic prior)  [614, 654) trace
+ *            [654, 664) radius, mu, alpha, dogleg_norm, model_change, step_norm, x_cost, x_norm, gmax, n_lidar
+ *            [664, 664 + n n) Hcur, the scaled H at x: the stored upper triangle mirrored into a full row-major n x n
+ *   aux      [0, 6524) imu_out 7 x 932 (J^T J 30 x 30 | J^T r 30 | cost | present)  [6524, 8260) lmap 7 x 248 (L 18 x 13 | l 13 | pad)
+ *            [8260, 8341) prior_out (J^T r np | cost)  [8341, 8385) exprior_out (J^T J 6 x 6 | J^T r 6 | cost | pad)
+ *            [8385, 10191) the lidar moments the last launch B folded, at cand, 7 x 258 (S 16 x 16 row-major, cost, count): the slot
+ *                        of lio_est_batch_get_moments when x equals cand (first linearisation, accepted step), the other one otherwise */
+#define LIO_DSL_INTS 208
+#define LIO_DSL_PROBLEM (3387 + 2 * 80 * 80 + 2 * 80)
+#define LIO_DSL_STATE (664 + 128 * 128)
+#define LIO_DSL_AUX 10191
+int lio_est_batch_get_linearization(lio_est_batch *, int window, int32_t *ints, double *problem, double *state, double *aux);
+
 #ifdef __cplusplus
 }
 #endif

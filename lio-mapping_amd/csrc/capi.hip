@@ -1373,6 +1373,11 @@ int lio_est_force_moments_per_lane(lio_est *h, int per_lane) {
   h->e->resident_.ForcePerLane(per_lane);
   return LIO_OK;
 }
+int lio_est_set_max_num_iterations(lio_est *h, int n) {
+  if (!h || n < 0) return LIO_ERR_ARG;
+  h->e->cfg_.max_num_iterations = n;
+  return LIO_OK;
+}
 int lio_est_get_laser_odom_transform(const lio_est *h, lio_transform_f *out) {
   if (!h || !out) return LIO_ERR_ARG;
   fromT(h->e->laser_odom_transform_, out);
@@ -1587,6 +1592,15 @@ int lio_est_batch_get_moments(lio_est_batch *h, int window, double *out, double 
   if (window >= int(h->members.size())) return LIO_ERR_ARG;
   return guarded([&] {
     const bool ok = window < h->n1 ? h->b->GetMoments(window, out, Rt) : h->b2->GetMoments(window - h->n1, out, Rt);
+    return ok ? int(LIO_OK) : int(LIO_ERR_STATE);
+  });
+}
+int lio_est_batch_get_linearization(lio_est_batch *h, int window, int32_t *ints, double *problem, double *state, double *aux) {
+  if (!h || !ints || !problem || !state || !aux || window < 0) return LIO_ERR_ARG;
+  if (!h->b) return LIO_ERR_STATE;
+  if (window >= int(h->members.size())) return LIO_ERR_ARG;
+  return guarded([&] {
+    const bool ok = window < h->n1 ? h->b->GetLinearization(window, ints, problem, state, aux) : h->b2->GetLinearization(window - h->n1, ints, problem, state, aux);
     return ok ? int(LIO_OK) : int(LIO_ERR_STATE);
   });
 }

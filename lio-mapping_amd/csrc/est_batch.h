@@ -62,6 +62,9 @@ class EstimatorBatch {
   // (S 16 x 16 row-major, cost, count) — and the T_{pivot<-i} of that point (Wo x 12: R row-major, t).  false: the window was not
   // solved on the device.  Waits for the batch.
   bool GetMoments(int w, double *out, double *Rt);
+  // Test hook (lio_est_batch_get_linearization): window w's DevProblem, DevState, prior buffer, scaled H and aux row as the last Solve()
+  // left them on the device, as the flat arrays of include/lio_test_hooks.h.  false: not solved on the device.  Waits for the batch.
+  bool GetLinearization(int w, int32_t *ints, double *problem, double *state, double *aux);
   // lio_est_get_features of a member whose last Solve() ran on the device: its feature slots live in the batch's arrays, at the
   // window's own slot offsets behind these pointers.  Waits for the batch.
   void FeatureSlots(int w, const uint8_t **valid, const float4 **coef, const float **score);

@@ -1,6 +1,7 @@
 // est_batch.hip — host orchestration of the batched solve (see est_batch.h).  The kernels: batch_kernels.hip (map / feature stages),
 // solve_kernels.hip (launch A / launch B of the trust-region loop), marg_kernels.hip (marginalization).
 #include "est_batch.h"
+#include "../../include/lio_test_hooks.h"
 
 #include <exception>
 #include <string>
@@ -265,6 +266,84 @@ bool EstimatorBatch::GetMoments(int w, double *out, double *Rt) {
   for (int f = 0; f < Wo; ++f) {
     std::memcpy(out + size_t(f) * 258, S.data() + size_t(f) * LIO_MOMENT_OUT, 258 * sizeof(double));
     relative_lidar_pose(st[0].x.pose[0], st[0].x.pose[f + 1], st[0].x.ex, Rt + size_t(f) * 12, Rt + size_t(f) * 12 + 9);
+  }
+  return true;
+}
+
+bool EstimatorBatch::GetLinearization(int w, int32_t *ints, double *problem, double *state, double *aux) {
+  if (w < 0 || w >= size() || !win_[size_t(w)].device) return false;
+  Sync();
+  for (hipStream_t g : stream_grp_) LIO_HIP(hipStreamSynchronize(g));
+  std::fill(ints, ints + LIO_DSL_INTS, 0);
+  std::fill(problem, problem + LIO_DSL_PROBLEM, 0.0);
+  std::fill(state, state + LIO_DSL_STATE, 0.0);
+  std::fill(aux, aux + LIO_DSL_AUX, 0.0);
+  const std::vector<DevProblem> pbv = fetch(d_pb_.p + w, 1);
+  const std::vector<DevState> stv = fetch(d_st_.p + w, 1);
+  const DevProblem &pb = pbv[0];
+  const DevState &st = stv[0];
+  const double *slab = slab_.p + size_t(w) * lay_.total;
+  const int Wo = pb.Wo, n = pb.n, np = pb.n_prior;
+  const int iv[16] = {Wo, n, pb.ex_col, np, pb.have_prior, pb.use_ex_prior, pb.n_keep, st.it, st.successful, st.termination, st.need_host, st.ntrace,
+                      pb.n_pad, st.started, st.done, pb.max_iterations};
+  std::copy(iv, iv + 16, ints);
+  for (int i = 0; i < DS_MAX_NPAD; ++i) ints[16 + i] = pb.prior_col[i];
+  for (int b = 0; b < DS_MAX_KEEP; ++b) {
+    int32_t *k = ints + 144 + 5 * b;
+    k[0] = pb.keep_kind[b]; k[1] = pb.keep_index[b]; k[2] = pb.keep_size[b]; k[3] = pb.keep_idx[b]; k[4] = pb.keep_x0[b];
+  }
+  std::copy(pb.prior_x0, pb.prior_x0 + DS_MAX_KEEP * 9, problem);
+  std::copy(pb.ex_prior_pos, pb.ex_prior_pos + 3, problem + 90);
+  std::copy(pb.ex_prior_rot, pb.ex_prior_rot + 4, problem + 93);
+  for (int i = 0; i < DS_MAX_WO; ++i) {
+    const DevPim &pm = pb.pim[i];
+    ints[194 + i] = pm.present;
+    double *o = problem + 97 + 470 * i;
+    std::copy(pm.dp, pm.dp + 3, o); std::copy(pm.dq, pm.dq + 4, o + 3); std::copy(pm.dv, pm.dv + 3, o + 7); std::copy(pm.ba, pm.ba + 3, o + 10);
+    std::copy(pm.bg, pm.bg + 3, o + 13); std::copy(pm.g, pm.g + 3, o + 16); o[19] = pm.sum_dt;
+    std::copy(pm.jac, pm.jac + 225, o + 20); std::copy(pm.sqrt_info, pm.sqrt_info + 225, o + 245);
+  }
+  if (pb.have_prior && np > 0 && np <= MARG_MAX_N) {
+    const std::vector<double> pm = fetch(slab + lay_.prior[win_[size_t(w)].cur], ds_prior_mats_size(np));
+    std::copy(pm.begin(), pm.end(), problem + 3387);
+  }
+  auto params = [](const DevParams &P, double *o) {
+    std::copy(&P.pose[0][0], &P.pose[0][0] + (DS_MAX_WO + 1) * 7, o);
+    std::copy(&P.sb[0][0], &P.sb[0][0] + (DS_MAX_WO + 1) * 9, o + 56);
+    std::copy(P.ex, P.ex + 7, o + 128);
+  };
+  params(st.x, state); params(st.cand, state + 135);
+  std::copy(&st.cand_Rt[0][0], &st.cand_Rt[0][0] + DS_MAX_WO * 12, state + 270);
+  std::copy(st.scale, st.scale + DS_MAX_NPAD, state + 354);
+  std::copy(st.g, st.g + DS_MAX_NPAD, state + 482);
+  std::copy(st.costs0, st.costs0 + 4, state + 610);
+  std::copy(st.trace, st.trace + 40, state + 614);
+  const double sc[10] = {st.radius, st.mu, st.alpha, st.dogleg_norm, st.model_change, st.step_norm, st.x_cost, st.x_norm, st.gmax, st.n_lidar};
+  std::copy(sc, sc + 10, state + 654);
+  {
+    const int ld = pb.ld;
+    const std::vector<double> Hc = fetch(slab + lay_.Hcur, size_t(pb.n_pad) * ld);
+    for (int r = 0; r < n; ++r)
+      for (int c = r; c < n; ++c) state[664 + size_t(r) * n + c] = state[664 + size_t(c) * n + r] = Hc[size_t(r) * ld + c];
+  }
+  {
+    const std::vector<double> a = fetch(slab + lay_.imu, size_t(Wo) * DS_IMU_OUT);
+    std::copy(a.begin(), a.begin() + size_t(Wo) * DS_IMU_OUT, aux);
+    const std::vector<double> l = fetch(slab + lay_.lmap, size_t(Wo) * DS_LMAP_OUT);
+    std::copy(l.begin(), l.begin() + size_t(Wo) * DS_LMAP_OUT, aux + 6524);
+    if (pb.have_prior && np > 0 && np <= MARG_MAX_N) {
+      const std::vector<double> p = fetch(slab + lay_.prior_out, size_t(np) + 1);
+      std::copy(p.begin(), p.begin() + np + 1, aux + 8260);
+    }
+    if (pb.use_ex_prior) {
+      const std::vector<double> x = fetch(slab + lay_.exprior, DS_EXP_OUT);
+      std::copy(x.begin(), x.begin() + DS_EXP_OUT, aux + 8341);
+    }
+    // launch B folds into the slot that is NOT s_cur and then flips s_cur when the folded point becomes the accepted one (x == cand)
+    const bool at_x = std::memcmp(&st.x, &st.cand, sizeof(DevParams)) == 0;
+    const int slot = at_x ? st.s_cur : 1 - st.s_cur;
+    const std::vector<double> S = fetch(slab + lay_.Sbuf + size_t(slot) * Wo * LIO_MOMENT_OUT, size_t(Wo) * LIO_MOMENT_OUT);
+    for (int f = 0; f < Wo; ++f) std::copy(S.begin() + size_t(f) * LIO_MOMENT_OUT, S.begin() + size_t(f) * LIO_MOMENT_OUT + 258, aux + 8385 + size_t(f) * 258);
   }
   return true;
 }

@@ -755,6 +755,10 @@ LIO_HD void solve_step(const X &x, const DevProblem &pb, DevState &st, const Ste
       C.x_cost = total; st.trace[0] = total; st.ntrace = 1;
       C.radius = 1e4; C.mu = 1e-8; C.alpha = 0; C.dogleg_norm = 0; C.reuse = 0; C.invalid = 0; C.it = 0; C.successful = 0; C.termination = 0;
       st.started = 1;
+      // the initial point is the accepted point until a step is accepted: its moments are the ones just folded into the candidate slot,
+      // and s_cur must name them (the marginalization and lio_est_batch_get_moments read S_buf at s_cur when no step is accepted; a
+      // rejected candidate is folded into the other slot)
+      st.s_cur = 1 - st.s_cur;
     } else {
       st.n_lidar = cnt;
       bool fin = false;

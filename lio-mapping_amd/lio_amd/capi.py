@@ -265,6 +265,8 @@ _TEST_SIGS = {
     "lio_est_eval_lidar_moments": (C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p, C.POINTER(C.c_int)]),
     "lio_est_force_moments_per_lane": (C.c_int, [C.c_void_p, C.c_int]),
     "lio_est_batch_get_moments": (C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
+    "lio_est_set_max_num_iterations": (C.c_int, [C.c_void_p, C.c_int]),
+    "lio_est_batch_get_linearization": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), c_double_p, c_double_p, c_double_p]),
     "lio_knn_walk": (C.c_int, [c_float_p, C.c_size_t, c_float_p, C.c_size_t, C.c_float, C.c_int, c_int32_p, c_float_p, c_float_p]),
     "lio_fit_five": (C.c_int, [C.c_int, c_float_p, c_float_p, c_float_p, C.c_size_t, C.POINTER(TransformF), c_float_p, C.c_float, C.c_float,
                                c_uint8_p, c_float_p, c_float_p, c_float_p]),
@@ -1368,6 +1370,10 @@ class Estimator:
         """residuals per lane of the resident moments kernel for later solves and eval_lidar_moments: 1 / 2 / 4 / 8, 0 = chosen per window"""
         _chk(self.lib.dll.lio_est_force_moments_per_lane(self.h, int(per_lane)), "lio_est_force_moments_per_lane")
 
+    def set_max_num_iterations(self, n):
+        """test hook: max_num_iterations of the handle's later solves (0: stop behind the first linearisation)"""
+        _chk(self.lib.dll.lio_est_set_max_num_iterations(self.h, int(n)), "lio_est_set_max_num_iterations")
+
     def laser_odom_transform(self):
         T = TransformF()
         _chk(self.lib.dll.lio_est_get_laser_odom_transform(self.h, C.byref(T)), "lio_est_get_laser_odom_transform")
@@ -1511,6 +1517,53 @@ class EstimatorBatch:
         out, Rt = np.zeros((wo, 258)), np.zeros((wo, 12))
         _chk(self.lib.dll.lio_est_batch_get_moments(self.h, int(window), _dp(out), _dp(Rt)), "lio_est_batch_get_moments")
         return out, Rt
+
+    DSL_SIZES = (208, 3387 + 2 * 80 * 80 + 2 * 80, 664 + 128 * 128, 10191)   # LIO_DSL_INTS, _PROBLEM, _STATE, _AUX
+
+    def linearization(self, window):
+        """lio_est_batch_get_linearization of window `window`, unpacked by the layout of include/lio_test_hooks.h into a dict:
+        the problem the device loop read, its state and the aux row of its last launch A (at `cand`)."""
+        ni, npb, nst, nax = self.DSL_SIZES
+        ints = np.zeros(ni, np.int32)
+        pbm, st, aux = np.zeros(npb), np.zeros(nst), np.zeros(nax)
+        _chk(self.lib.dll.lio_est_batch_get_linearization(self.h, int(window), ints.ctypes.data_as(C.POINTER(C.c_int32)), _dp(pbm), _dp(st), _dp(aux)),
+             "lio_est_batch_get_linearization")
+        names = ["Wo", "n", "ex_col", "n_prior", "have_prior", "use_ex_prior", "n_keep", "it", "successful", "termination", "need_host", "ntrace", "n_pad",
+                 "started", "done", "max_iterations"]
+        d = {k: int(v) for k, v in zip(names, ints[:16])}
+        wo, n, npr = d["Wo"], d["n"], d["n_prior"]
+        d["prior_col"] = ints[16:16 + n].copy()
+        d["keep"] = ints[144:194].reshape(10, 5)[:d["n_keep"]].copy()   # kind, index, size, offset, x0 offset
+        d["present"] = ints[194:194 + wo].copy()
+        d["prior_x0"] = pbm[0:90].copy()
+        d["ex_prior_pos"], d["ex_prior_rot"] = pbm[90:93].copy(), pbm[93:97].copy()
+        pims = []
+        for i in range(wo):
+            o = pbm[97 + 470 * i:97 + 470 * (i + 1)]
+            pims.append(dict(dp=o[0:3].copy(), dq=o[3:7].copy(), dv=o[7:10].copy(), ba=o[10:13].copy(), bg=o[13:16].copy(), g=o[16:19].copy(),
+                             sum_dt=float(o[19]), jac=o[20:245].reshape(15, 15).copy(), sqrt_info=o[245:470].reshape(15, 15).copy()))
+        d["pim"] = pims
+        m = pbm[3387:]
+        d["prior"] = dict(JtJ=m[:npr * npr].reshape(npr, npr).copy(), lin_jac=m[npr * npr:2 * npr * npr].reshape(npr, npr).copy(),
+                          lin_res=m[2 * npr * npr:2 * npr * npr + npr].copy(), Jtr0=m[2 * npr * npr + npr:2 * npr * npr + 2 * npr].copy())
+
+        def params(v):
+            return dict(pose=v[0:56].reshape(8, 7)[:wo + 1].copy(), sb=v[56:128].reshape(8, 9)[:wo + 1].copy(), ex=v[128:135].copy())
+
+        d["x"], d["cand"] = params(st[0:135]), params(st[135:270])
+        d["cand_Rt"] = st[270:354].reshape(7, 12)[:wo].copy()
+        d["scale"], d["g"] = st[354:354 + n].copy(), st[482:482 + n].copy()
+        d["costs0"] = st[610:614].copy()
+        d["trace"] = st[614:614 + d["ntrace"]].copy()
+        for k, nm in enumerate(["radius", "mu", "alpha", "dogleg_norm", "model_change", "step_norm", "x_cost", "x_norm", "gmax", "n_lidar"]):
+            d[nm] = float(st[654 + k])
+        d["Hcur"] = st[664:664 + n * n].reshape(n, n).copy()
+        d["imu_out"] = aux[0:6524].reshape(7, 932)[:wo].copy()
+        d["lmap"] = aux[6524:8260].reshape(7, 248)[:wo].copy()
+        d["prior_out"] = aux[8260:8260 + npr + 1].copy()
+        d["exprior_out"] = aux[8341:8385].copy()
+        d["cand_moments"] = aux[8385:10191].reshape(7, 258)[:wo].copy()
+        return d
 
     def clock(self):
         out = (C.c_double * 24)()

@@ -1029,6 +1029,12 @@ int lio_est_force_moments_per_lane(lio_est *h, int per_lane) {
   if (!h || !(per_lane == 0 || per_lane == 1 || per_lane == 2 || per_lane == 4 || per_lane == 8)) return LIO_ERR_ARG;
   return LIO_OK;   // no resident kernel: nothing to force
 }
+int lio_est_set_max_num_iterations(lio_est *h, int n) {
+  if (!h || n < 0) return LIO_ERR_ARG;
+  h->est.cfg.max_num_iterations = n;
+  if (h->snap) h->snap->cfg.max_num_iterations = n;   // (a restore brings the whole estimator back, its configuration included)
+  return LIO_OK;
+}
 int lio_est_get_laser_odom_transform(const lio_est *h, lio_transform_f *out) {
   if (!h || !out) return LIO_ERR_ARG;
   fromT(h->est.laser_odom_transform, out);
@@ -1213,6 +1219,16 @@ int lio_est_batch_get_moments(lio_est_batch *b, int window, double *out, double 
   const int Wo = b->members[size_t(window)]->est.Wo;
   for (int k = 0; k < Wo * 258; ++k) out[k] = 0.0;
   for (int k = 0; k < Wo * 12; ++k) Rt[k] = 0.0;
+  return LIO_OK;
+}
+int lio_est_batch_get_linearization(lio_est_batch *b, int window, int32_t *ints, double *problem, double *state, double *aux) {
+  if (!b || !ints || !problem || !state || !aux || window < 0) return LIO_ERR_ARG;
+  if (b->dissolved) return LIO_ERR_STATE;
+  if (window >= int(b->members.size())) return LIO_ERR_ARG;
+  for (int k = 0; k < LIO_DSL_INTS; ++k) ints[k] = 0;
+  for (int k = 0; k < LIO_DSL_PROBLEM; ++k) problem[k] = 0.0;
+  for (int k = 0; k < LIO_DSL_STATE; ++k) state[k] = 0.0;
+  for (int k = 0; k < LIO_DSL_AUX; ++k) aux[k] = 0.0;
   return LIO_OK;
 }
 int lio_est_batch_get_clock(const lio_est_batch *b, double *out) {

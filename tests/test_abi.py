@@ -80,6 +80,7 @@ def test_each_test_hook_is_bound_and_exported_by_both_libraries(oracle):
     hooks = _declared_test_hooks()
     assert len(hooks) >= 10 and "lio_knn_walk" in hooks and "lio_fit_five" in hooks and "lio_odom_correspondences" in hooks
     assert {"lio_gn_rows_map", "lio_gn_rows_odom", "lio_gn_fold", "lio_gn_step", "lio_gn_round"} <= set(hooks)
+    assert {"lio_est_set_max_num_iterations", "lio_est_batch_get_linearization"} <= set(hooks)
     assert set(hooks) == set(capi._TEST_SIGS.keys())
     assert not set(hooks) & set(_declared_symbols())
     dll = ctypes.CDLL(capi.HIP_LIB_PATH)
@@ -102,6 +103,8 @@ def test_test_hook_header_is_plain_c_and_links(tmp_path, oracle, lib):
                    "  if (lio_est_eval_lidar_moments(NULL, 1, NULL, NULL, &path) != LIO_ERR_ARG || path != 7) return 1;\n"
                    "  if (lio_est_batch_get_moments(NULL, 0, NULL, NULL) != LIO_ERR_ARG) return 2;\n"
                    "  if (lio_est_force_moments_per_lane(NULL, 0) != LIO_ERR_ARG) return 3;\n"
+                   "  if (lio_est_set_max_num_iterations(NULL, 1) != LIO_ERR_ARG) return 60;\n"
+                   "  if (lio_est_batch_get_linearization(NULL, 0, NULL, NULL, NULL, NULL) != LIO_ERR_ARG) return 61;\n"
                    "  {\n"
                    "    float map[8] = {0, 0, 0, 0, 1, 1, 1, 0}, q[4] = {0, 0, 0, 0}, sqd[5] = {7, 7, 7, 7, 7}, nbr[15];\n"
                    "    int32_t idx[5] = {7, 7, 7, 7, 7};\n"
