@@ -12,6 +12,7 @@
 #include "../../include/lio_odom_batch.h"
 #include "../../include/lio_frontend_batch.h"
 #include "../../include/lio_map_batch.h"
+#include "../../include/lio_map_from_odom.h"
 #include "../../include/lio_vox_sort.h"
 #include "../../include/lio_seg_bounds.h"
 #include "est_batch.h"
@@ -479,6 +480,63 @@ int lio_map_process_batch(lio_map *const *handles, int n_sensors, const float *c
     for (int k = 0; k < n_sensors; ++k) { m.push_back(handles[k]->m.get()); sums.push_back(toT(Tsum[k])); }
     MappingDev::ProcessBatch(m.data(), n_sensors, corner, nc, surf, ns, sums.data());
     for (int k = 0; k < n_sensors; ++k) map_step_results(*m[size_t(k)], Taft ? Taft + k : nullptr, iters ? iters + k : nullptr, nsel ? nsel + k : nullptr);
+    return int(LIO_OK);
+  });
+}
+// include/lio_map_from_odom.h.  Every check comes before any device work and before any handle changes; every pp[k] is resolved to
+// (processor, sweep) as pp_read resolves it, and the shared processors stay locked until the chain, which reads their clouds, has returned
+// synchronised.
+int lio_map_process_batch_from_odom(lio_map *const *handles, lio_odom *const *odom, lio_pp *const *pp, int n_sensors, lio_transform_f *Taft,
+                                    int32_t *iters, int32_t *nsel) {
+  if (!handles || !odom || n_sensors < 1) return LIO_ERR_ARG;
+  if (n_sensors > LIO_MAP_BATCH_MAX_SENSORS) return LIO_ERR_CAPACITY;
+  for (int k = 0; k < n_sensors; ++k)
+    if (!handles[k] || !odom[k]) return LIO_ERR_ARG;
+  {
+    std::vector<const lio_map *> sorted(handles, handles + n_sensors);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return LIO_ERR_ARG;   // the same handle twice
+  }
+  for (int k = 0; k < n_sensors; ++k) {
+    if (handles[k]->borrowed || !handles[k]->m) return LIO_ERR_STATE;   // an estimator's map (lio_est_map) is stepped by its estimator
+    if (!odom[k]->o->processed()) return LIO_ERR_STATE;                 // no sweep to hand over
+  }
+  return guarded([&] {
+    const size_t n = size_t(n_sensors);
+    std::vector<lio_pp_pool *> pools;
+    for (size_t k = 0; pp && k < n; ++k)
+      if (pp[k] && pp[k]->pool && pp[k]->pool_sweep >= 0) pools.push_back(pp[k]->pool.get());
+    std::sort(pools.begin(), pools.end());   // (one order for every caller)
+    pools.erase(std::unique(pools.begin(), pools.end()), pools.end());
+    std::vector<std::unique_lock<std::mutex>> locks;
+    for (lio_pp_pool *p : pools) locks.emplace_back(p->mu);
+    std::vector<MappingDev *> m(n);
+    std::vector<Rigidf> sums(n);
+    std::vector<const float *> src[2];
+    std::vector<size_t> cnt[2];
+    for (int c = 0; c < 2; ++c) { src[c].resize(n); cnt[c].resize(n); }
+    std::vector<MapFullSource> full(n, MapFullSource{});
+    for (size_t k = 0; k < n; ++k) {
+      m[k] = handles[k]->m.get();
+      const OdometryDev::DeviceView v = odom[k]->o->View();
+      sums[k] = odom[k]->o->transform_sum_;
+      for (int c = 0; c < 2; ++c) { src[c][k] = reinterpret_cast<const float *>(v.last[c]); cnt[c][k] = v.n_last[c]; }
+      const lio_pp *h = pp ? pp[k] : nullptr;
+      if (!h) continue;   // this handle's full cloud stays
+      const bool pooled = h->pool && h->pool_sweep >= 0;
+      if (pooled && h->pool_gen != h->pool->gen)
+        throw std::runtime_error("lio_map_process_batch_from_odom: a processor's batch results were overwritten by a later lio_pp_process_batch on the storage it shared");
+      PointProcessorDev &p = pooled ? h->pool->pp : *h->pp;
+      try { p.ProcessFinish(); }   // a sweep still in flight (lio_pp_process_async) is waited for
+      catch (const CapacityError &e) { throw std::runtime_error(e.what()); }
+      if (!p.has_results()) throw std::runtime_error("lio_map_process_batch_from_odom: a processor has no completed sweep");
+      MapFullSource &f = full[k];
+      f.set = true;
+      p.DeviceRings(pooled ? h->pool_sweep : 0, f.pts, f.n);
+      f.to_end = v.to_end; f.time_factor = v.time_factor; f.no_deskew = v.no_deskew;
+    }
+    MappingDev::ProcessBatch(m.data(), n_sensors, src[0].data(), cnt[0].data(), src[1].data(), cnt[1].data(), sums.data(), full.data());
+    for (size_t k = 0; k < n; ++k) map_step_results(*m[k], Taft ? Taft + k : nullptr, iters ? iters + k : nullptr, nsel ? nsel + k : nullptr);
     return int(LIO_OK);
   });
 }

@@ -36,6 +36,19 @@ __device__ __forceinline__ float4 to_end_point(float4 p, float s, const Quat<flo
   p.x = v.x + te.x; p.y = v.y + te.y; p.z = v.z + te.z;
   return p;
 }
+// The odometry's TransformToEnd (PointOdometry.cc:261-292) of point i with the transform_es_ the iterations left on the device; out == in: in
+// place.  Stated once for the odometry's own clouds, lio_odom_full_to_end and the full cloud the scan-to-map step takes from the odometry
+// (mapping.hip: k_mb_from_odom): the same instructions, so the same bits.
+__device__ __forceinline__ void odo_to_end_body(const float4 *in, float4 *out, const int i, const OdomState *__restrict__ st, float time_factor,
+                                                int no_deskew) {
+  Quat<float> qe(st->T[3], st->T[0], st->T[1], st->T[2]);
+  Vec3<float> te(st->T[4], st->T[5], st->T[6]);
+  float4 p = in[i];
+  float s = time_factor * (p.w - int(p.w));
+  if (no_deskew) s = 0;
+  p.w = float(int(p.w));
+  out[i] = to_end_point<false>(p, s, qe, te);
+}
 // PointAssociateToMap (PointMapping.cc:303-314): rot * p + pos in the operation order of rotate (hmath.h), intensity kept
 __device__ __forceinline__ float4 rigid_map_point(float4 p, const Quat<float> &q, const Vec3<float> &t) {
   const Vec3<float> v = rotate(q, Vec3<float>(p.x, p.y, p.z));

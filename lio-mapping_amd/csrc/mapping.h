@@ -42,6 +42,17 @@ struct MapSurroundSet {
 
 struct MapCounters { int n_valid, n_rest, n_new_valid, n_new_rest, n_out, pad[3]; };
 
+// The full cloud a handle takes with a step whose clouds lie in device memory (lio_map_process_batch_from_odom): what SetFullCloud does, fed from
+// the device.  The stack clouds of such a step lie where ProcessBatch's corner_last / surf_last point.
+struct MapFullSource {
+  bool set;                  // false: the handle's full cloud stays as it is
+  const float4 *pts;         // n points in the sensor frame at their own times; n = 0 clears the handle's full cloud
+  size_t n;
+  const OdomState *to_end;   // an odometry's device-side transform_es_: the points go through its TransformToEnd on the way; null: a copy
+  float time_factor;
+  int no_deskew;
+};
+
 struct MapChain;   // mapping.hip: the launch chain every step runs through (prepare, filter, grids, table, rounds, give back, update) and its scratch
 
 class MappingDev {
@@ -58,8 +69,10 @@ class MappingDev {
   // include/lio_map_batch.h: one sweep for each of n distinct handles, with the steps of the chain lined up across the handles and the rounds
   // of all of them in one keyframe table.  Array k of every argument belongs to m[k].  Every handle ends in the state a chain of one leaves,
   // bit for bit.  Handles without common launch parameters run as chains of one.  Returns synchronised (the full cloud's registration too).
+  // full_on_device (include/lio_map_from_odom.h; null: the clouds are the host's): the clouds lie in device memory, complete and left alone
+  // until the call returns, and full_on_device[k] is the full cloud m[k] takes with them; one launch takes all of it, no copy per handle.
   static void ProcessBatch(MappingDev *const *m, int n, const float *const *corner_last, const size_t *n_corner, const float *const *surf_last,
-                           const size_t *n_surf, const Rigid<float> *transform_sum);
+                           const size_t *n_surf, const Rigid<float> *transform_sum, const MapFullSource *full_on_device = nullptr);
   void UpdateMapDatabase(const float *corner_ds, size_t n_corner, const float *surf_ds, size_t n_surf, const uint32_t *valid_idx, size_t n_valid,
                          const Rigid<float> &T, const int cube_center[3]);
   // the same with the stacks where they live (HBM, sensor frame): no cloud crosses PCIe.  producer: the stream that wrote them (the
@@ -146,6 +159,7 @@ class MappingDev {
   void TransformUpdate();                                                // :760-763
   void OptimizeEnd(const OdomState &st, int M, bool four_dof);           // the state the rounds ended with into the handle, TransformUpdate
   bool StepUpdates() const { return cfg_.map_builder != 0 || !imu_inited_; }
+  void FullBegin(size_t n);                                              // a new full cloud of n points, before its points are written: the count, "not registered yet", room
   void StepRegisterFull();                                               // PublishResults on full_cloud_, once per set
   bool FourDof() const { return cfg_.map_builder != 0 && cfg_.enable_4d != 0; }
   MapChain &Chain();

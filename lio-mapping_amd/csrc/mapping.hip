@@ -240,6 +240,22 @@ __global__ void __launch_bounds__(256) k_mb_roundtrip(const MbStackRec *__restri
   if (i >= r.n[c]) return;
   r.out[c][i] = stack_roundtrip_point(r.in[c][i], r.q, r.t);
 }
+// One sensor of a step fed from the device (lio_map_process_batch_from_odom): its stack clouds where the odometry keeps them, and the full
+// cloud it takes with them (n_full = 0: none), through the odometry's TransformToEnd (st) or as it is (st null), into the handle's full_
+struct MbFromOdomRec { MbStackRec stack; const float4 *full_in; float4 *full_out; int n_full; const OdomState *st; float time_factor; int no_deskew; };
+// grid (cdiv(max n, 256), 3, sensors): y 0 and 1 are k_mb_roundtrip's, y 2 is lio_odom_full_to_end then lio_map_set_full_cloud with no copy between
+__global__ void __launch_bounds__(256) k_mb_from_odom(const MbFromOdomRec *__restrict__ recs) {
+  const MbFromOdomRec &r = recs[blockIdx.z];
+  const int c = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+  if (c < 2) {
+    if (i >= r.stack.n[c]) return;
+    r.stack.out[c][i] = stack_roundtrip_point(r.stack.in[c][i], r.stack.q, r.stack.t);
+    return;
+  }
+  if (i >= r.n_full) return;
+  if (r.st) odo_to_end_body(r.full_in, r.full_out, i, r.st, r.time_factor, r.no_deskew);
+  else r.full_out[i] = r.full_in[i];
+}
 // One iterating sensor's slice [slot_off, slot_off + Mc + Ms) of the chain's arrays and where the handle keeps the same: its filtered stacks
 // (taken), and its own stack_all_ / f_coef_ / f_abs_ / f_valid_ (given back)
 struct MbSliceRec { const float4 *stack_ds[2]; int M[2]; int slot_off; float4 *stack_all; float4 *coef; float4 *abs_coef; uint8_t *valid; };
@@ -320,7 +336,9 @@ struct MapChain {
   std::vector<MappingDev::Step> steps;
   std::vector<MbStackRec> h_stack;
   DBuf<MbStackRec> d_stack;
-  bool any_stack = false;               // some handle brought a cloud: the round trip ran
+  std::vector<MbFromOdomRec> h_from;    // a step fed from the device: this table in the place of h_stack
+  DBuf<MbFromOdomRec> d_from;
+  bool any_stack = false;               // some handle brought a cloud: the round trip (fed from the device: k_mb_from_odom) ran
   std::vector<int> act;                 // the handles (indices into the call) whose rounds run: the keyframe table's order
   GridBatch clouds;                     // the from-map clouds of `act` (2 * nA): their bounds side by side; the grids are the handles' own
   DBuf<float4> stack_all, coef, abs_coef;
@@ -340,7 +358,7 @@ struct MapChain {
   int nA() const { return int(act.size()); }
   MappingDev &dev(int j) const { return *m[act[size_t(j)]]; }
   void Prepare(MappingDev *const *handles, int n_handles, const float *const *corner_last, const size_t *n_corner, const float *const *surf_last,
-               const size_t *n_surf, const Rigid<float> *sums);
+               const size_t *n_surf, const Rigid<float> *sums, const MapFullSource *full_on_device);
   void Filter();
   void MakeGrids();
   void FillTable();
@@ -601,10 +619,13 @@ size_t MappingDev::GetSurround(float leaf, float *out) {
   return m;
 }
 
-void MappingDev::SetFullCloud(const float *xyzi, size_t n) {
+void MappingDev::FullBegin(size_t n) {
   n_full_ = n; full_mapped_ = false; full_event_ = false;
+  if (n) full_.reserve(n);
+}
+void MappingDev::SetFullCloud(const float *xyzi, size_t n) {
+  FullBegin(n);
   if (!n) return;
-  full_.reserve(n);
   if (full_read_) LIO_HIP(hipStreamWaitEvent(stream_, ev_full_read_, 0));
   LIO_HIP(hipMemcpyAsync(full_.p, xyzi, n * sizeof(float4), hipMemcpyHostToDevice, stream_));
   LIO_HIP(hipStreamSynchronize(stream_));   // the caller may reuse the source right after the call
@@ -791,12 +812,16 @@ MapChain &MappingDev::Chain() {
 // include/lio_map_batch.h.  Every step of the chain runs for all handles before the next one starts, so a wait is one pass over the handles
 // instead of one stop per handle.  Every handle is idle when the call starts (each lio_map_* call returns synchronised).
 
-// ---- 1. prepare: association, uploads, cube bookkeeping and the layout pass per handle, no wait in between; one launch for every round trip
+// ---- 1. prepare: association, uploads, cube bookkeeping and the layout pass per handle, no wait in between; one launch for every round trip.
+// Fed from the device (full_on_device): no staging buffer, no upload and no event per handle — the sources are complete; the one launch reads
+// the stack clouds where they lie and takes every handle's full cloud beside them.
 void MapChain::Prepare(MappingDev *const *handles, int n_handles, const float *const *corner_last, const size_t *n_corner, const float *const *surf_last,
-                       const size_t *n_surf, const Rigid<float> *sums) {
+                       const size_t *n_surf, const Rigid<float> *sums, const MapFullSource *full_on_device) {
   m = handles; n = n_handles; s0 = m[0]->stream_;
+  const bool on_device = full_on_device != nullptr;
   steps.assign(size_t(n), MappingDev::Step());
-  h_stack.assign(size_t(n), MbStackRec());
+  h_stack.assign(on_device ? 0 : size_t(n), MbStackRec());
+  h_from.assign(on_device ? size_t(n) : 0, MbFromOdomRec());
   size_t max_in = 0;
   for (int k = 0; k < n; ++k) {
     MappingDev &d = *m[k];
@@ -805,29 +830,46 @@ void MapChain::Prepare(MappingDev *const *handles, int n_handles, const float *c
     // the stack clouds go up while the host does the cube bookkeeping; stack_raw is sized for their round trip
     const float *src[2] = {corner_last[k], surf_last[k]};
     st.cnt[0] = n_corner[k]; st.cnt[1] = n_surf[k];
-    MbStackRec &r = h_stack[size_t(k)];
+    MbStackRec &r = on_device ? h_from[size_t(k)].stack : h_stack[size_t(k)];
     for (int c = 0; c < 2; ++c) {
       MappingDev::ClassMap &cm = d.cls_[c];
       cm.n_stack = 0;
-      if (st.cnt[c]) {
-        cm.in.reserve(st.cnt[c]); cm.stack_raw.reserve(st.cnt[c]);
-        LIO_HIP(hipMemcpyAsync(cm.in.p, src[c], st.cnt[c] * sizeof(float4), hipMemcpyHostToDevice, d.stream_));
-      }
-      r.in[c] = cm.in.p; r.out[c] = cm.stack_raw.p; r.n[c] = int(st.cnt[c]);
+      if (st.cnt[c] && !on_device) cm.in.reserve(st.cnt[c]);
+      if (st.cnt[c]) cm.stack_raw.reserve(st.cnt[c]);
+      if (st.cnt[c] && !on_device) LIO_HIP(hipMemcpyAsync(cm.in.p, src[c], st.cnt[c] * sizeof(float4), hipMemcpyHostToDevice, d.stream_));
+      r.in[c] = on_device ? reinterpret_cast<const float4 *>(src[c]) : cm.in.p; r.out[c] = cm.stack_raw.p; r.n[c] = int(st.cnt[c]);
       max_in = std::max(max_in, st.cnt[c]);
     }
     r.q = st.T0.rot; r.t = st.T0.pos;
-    if (k && (st.cnt[0] || st.cnt[1])) {   // the round trip on s0 reads what this stream uploads
+    if (!on_device && k && (st.cnt[0] || st.cnt[1])) {   // the round trip on s0 reads what this stream uploads
       LIO_HIP(hipEventRecord(d.ev_join_, d.stream_));
       LIO_HIP(hipStreamWaitEvent(s0, d.ev_join_, 0));
     }
+    if (on_device && full_on_device[k].set) {   // SetFullCloud, the points written by the launch below
+      const MapFullSource &f = full_on_device[k];
+      MbFromOdomRec &fr = h_from[size_t(k)];
+      d.FullBegin(f.n);
+      if (f.n) {
+        if (d.full_read_) LIO_HIP(hipStreamWaitEvent(s0, d.ev_full_read_, 0));
+        fr.full_in = f.pts; fr.full_out = d.full_.p; fr.n_full = int(f.n);
+        fr.st = f.to_end; fr.time_factor = f.time_factor; fr.no_deskew = f.no_deskew;
+        max_in = std::max(max_in, f.n);
+      }
+    }
     d.StepWindow(st);
   }
+  // the filters (Filter) and the full clouds' registration (Update) run on the handles' own streams: those wait for `ev` in Filter
   any_stack = max_in != 0;
   if (any_stack) {
-    d_stack.reserve(size_t(n));
-    LIO_HIP(hipMemcpyAsync(d_stack.p, h_stack.data(), size_t(n) * sizeof(MbStackRec), hipMemcpyHostToDevice, s0));
-    hipLaunchKernelGGL(k_mb_roundtrip, dim3(cdiv(max_in, 256), 2, n), dim3(256), 0, s0, d_stack.p);
+    if (on_device) {
+      d_from.reserve(size_t(n));
+      LIO_HIP(hipMemcpyAsync(d_from.p, h_from.data(), size_t(n) * sizeof(MbFromOdomRec), hipMemcpyHostToDevice, s0));
+      hipLaunchKernelGGL(k_mb_from_odom, dim3(cdiv(max_in, 256), 3, n), dim3(256), 0, s0, d_from.p);
+    } else {
+      d_stack.reserve(size_t(n));
+      LIO_HIP(hipMemcpyAsync(d_stack.p, h_stack.data(), size_t(n) * sizeof(MbStackRec), hipMemcpyHostToDevice, s0));
+      hipLaunchKernelGGL(k_mb_roundtrip, dim3(cdiv(max_in, 256), 2, n), dim3(256), 0, s0, d_stack.p);
+    }
     LIO_HIP(hipGetLastError());
     if (n > 1) LIO_HIP(hipEventRecord(ev, s0));
   }
@@ -994,9 +1036,10 @@ void MapChain::Update() {
 }
 
 void MappingDev::ProcessBatch(MappingDev *const *m, int n, const float *const *corner_last, const size_t *n_corner, const float *const *surf_last,
-                              const size_t *n_surf, const Rigid<float> *sums) {
+                              const size_t *n_surf, const Rigid<float> *sums, const MapFullSource *full) {
   for (int k = 0; k < n; ++k)
-    if (n_corner[k] > size_t(INT_MAX) - 255 || n_surf[k] > size_t(INT_MAX) - 255) throw CapacityError("lio_map_process_batch: a cloud exceeds 2^31 points");
+    if (n_corner[k] > size_t(INT_MAX) - 255 || n_surf[k] > size_t(INT_MAX) - 255 || (full && full[k].set && full[k].n > size_t(INT_MAX) - 255))
+      throw CapacityError("lio_map_process_batch: a cloud exceeds 2^31 points");
   // a pose whose window the packed cube keys cannot hold is refused before any handle changes and before the first launch
   for (int k = 0; k < n; ++k) {
     int cen[3], cc[3];
@@ -1009,11 +1052,11 @@ void MappingDev::ProcessBatch(MappingDev *const *m, int n, const float *const *c
     if (a.min_match_sq_dis == b.min_match_sq_dis && a.min_plane_dis == b.min_plane_dis && a.num_max_iterations == b.num_max_iterations &&
         m[0]->FourDof() == m[k]->FourDof())
       continue;
-    for (int j = 0; j < n; ++j) ProcessBatch(m + j, 1, corner_last + j, n_corner + j, surf_last + j, n_surf + j, sums + j);
+    for (int j = 0; j < n; ++j) ProcessBatch(m + j, 1, corner_last + j, n_corner + j, surf_last + j, n_surf + j, sums + j, full ? full + j : nullptr);
     return;
   }
   MapChain &ch = m[0]->Chain();
-  ch.Prepare(m, n, corner_last, n_corner, surf_last, n_surf, sums);
+  ch.Prepare(m, n, corner_last, n_corner, surf_last, n_surf, sums, full);
   ch.Filter();
   ch.MakeGrids();
   if (ch.nA()) {

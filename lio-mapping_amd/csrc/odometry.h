@@ -25,6 +25,15 @@ class OdometryDev {
                            const size_t *n_ls, const float *const *flat, const size_t *n_flat, const float *const *less_flat, const size_t *n_lf,
                            bool on_device = false);
   size_t GetLastCloud(int which, float *out);
+  // What lio_map_process_batch_from_odom (include/lio_map_from_odom.h) reads of the handle, where it lies on the device; nothing of the handle
+  // changes.  last / n_last: what GetLastCloud answers (0 corner, 1 surf).  to_end, time_factor, no_deskew: what FullToEnd runs a cloud
+  // through; to_end is null where FullToEnd copies (odometry disabled, or no publishing step yet).
+  struct DeviceView { const float4 *last[2]; size_t n_last[2]; const OdomState *to_end; float time_factor; int no_deskew; };
+  DeviceView View() const {
+    return DeviceView{{last_corner_.p, last_surf_.p}, {n_last_corner_, n_last_surf_}, enable_odom_ && to_end_ready_ ? d_state_.p : nullptr, time_factor_,
+                      no_deskew_ ? 1 : 0};
+  }
+  bool processed() const { return inited_; }   // a process call has completed
   // TransformToEnd(full_cloud_) with the last Process's transform_es_ (:725-730); a byte copy while the odometry is disabled
   void FullToEnd(const float *xyzi, size_t n, float *out);
   // the correspondence search of one iteration on caller-given clouds and transform_es_ (lio_odom_correspondences,

@@ -397,17 +397,7 @@ void launch_gn_odo_step(const double *sums, OdomState *st, int iter, hipStream_t
   LIO_HIP(hipGetLastError());
 }
 
-// TransformToEnd (:261-292) with the transform_es_ the iterations left on the device; out == in: in place
-__device__ __forceinline__ void odo_to_end_body(const float4 *in, float4 *out, const int i, const OdomState *__restrict__ st, float time_factor,
-                                                int no_deskew) {
-  Quat<float> qe(st->T[3], st->T[0], st->T[1], st->T[2]);
-  Vec3<float> te(st->T[4], st->T[5], st->T[6]);
-  float4 p = in[i];
-  float s = time_factor * (p.w - int(p.w));
-  if (no_deskew) s = 0;
-  p.w = float(int(p.w));
-  out[i] = to_end_point<false>(p, s, qe, te);
-}
+// TransformToEnd (:261-292) of a caller's cloud: odo_to_end_body (cloud_device.h)
 __global__ void __launch_bounds__(256) k_odo_to_end(const float4 *in, float4 *out, int n, const OdomState *__restrict__ st, float time_factor, int no_deskew) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;

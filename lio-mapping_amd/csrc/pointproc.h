@@ -93,6 +93,8 @@ class PointProcessorDev {
     for (int w = 0; w < 4; ++w)
       if (n[w] > (w < 3 ? cls_stride_ : pts_stride_)) throw std::runtime_error("PointProcessor: a cloud's count exceeds its storage");
   }
+  // sweep k's ring-ordered cloud (LIO_PP_RINGS) where the last launch left it on the device, and its count; nothing of the processor changes
+  void DeviceRings(int k, const float4 *&src, size_t &n) const;
   float StartOri();   // start_ori_ of the selected sweep of the last Process (one small D2H unless infer_start_ori already fetched it)
 
  private:

@@ -1050,6 +1050,15 @@ void PointProcessorDev::SelectSweep(int k) {
   counts_.n_ring_points = ring_offsets_[rings_];
 }
 
+void PointProcessorDev::DeviceRings(int k, const float4 *&src, size_t &n) const {
+  src = nullptr; n = 0;
+  if (last_empty_ || over_capacity_ || !processed_) return;   // (SelectSweep: every count reads zero)
+  if (k < 0 || k >= nsw_) throw std::runtime_error("PointProcessor: no such sweep in the last batch");
+  const int cnt = (h_record(k) + kCountInts)[rings_];   // (SelectSweep: the end of the last ring)
+  if (cnt < 0 || size_t(cnt) > pts_stride_) throw std::runtime_error("PointProcessor: a cloud's count exceeds its storage");
+  src = ring_cloud_.p + size_t(k) * pts_stride_; n = size_t(cnt);
+}
+
 size_t PointProcessorDev::Count(int which) const {
   switch (which) {
     case LIO_PP_RINGS: return size_t(counts_.n_ring_points);

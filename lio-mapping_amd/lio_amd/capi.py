@@ -324,6 +324,11 @@ _MAP_BATCH_SIGS = {
                                         C.POINTER(TransformF), c_int32_p, c_int32_p]),
 }
 MAP_BATCH_MAX_SENSORS = 1024   # LIO_MAP_BATCH_MAX_SENSORS
+# include/lio_map_from_odom.h: the batched scan-to-map step fed from the odometry on the device (the product only, attached like _MAP_BATCH_SIGS)
+_MAP_FROM_ODOM_SIGS = {
+    "lio_map_process_batch_from_odom": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.POINTER(TransformF),
+                                                  c_int32_p, c_int32_p]),
+}
 # include/lio_vox_sort.h: the voxel filter's sort on caller-given keys and the counters of the paths it took (the product only, attached like _EXT_SIGS)
 _c_uint32_p = C.POINTER(C.c_uint32)
 _VOX_SORT_SIGS = {
@@ -394,7 +399,7 @@ class LioLib:
         self.has_ext = self.backend.startswith("hip")
         if self.has_ext:
             for name, (res, args) in (list(_EXT_SIGS.items()) + list(_FULL_SIGS.items()) + list(_ODOM_BATCH_SIGS.items()) + list(_FRONTEND_SIGS.items())
-                                      + list(_MAP_BATCH_SIGS.items())):
+                                      + list(_MAP_BATCH_SIGS.items()) + list(_MAP_FROM_ODOM_SIGS.items())):
                 fn = getattr(self.dll, name)
                 fn.restype = res
                 fn.argtypes = args
@@ -922,6 +927,29 @@ class PointMapping:
         Ta = (TransformF * n)()
         it, ns = np.zeros(n, np.int32), np.zeros(n, np.int32)
         _chk(lib.dll.lio_map_process_batch(H, n, *args, Ts, Ta, it.ctypes.data_as(c_int32_p), ns.ctypes.data_as(c_int32_p)), "lio_map_process_batch")
+        out = []
+        for k, h in enumerate(handles):
+            kz = C.c_int(0)
+            deg = lib.dll.lio_map_get_degeneracy(h.h, C.byref(kz))
+            out.append(dict(T_aft=Ta[k].to_np(), iterations=int(it[k]), num_selected=int(ns[k]), degenerate=int(deg), kz=kz.value))
+        return out
+
+    @staticmethod
+    def process_batch_from_odom(handles, odoms, processors_or_none=None):
+        """lio_map_process_batch_from_odom (include/lio_map_from_odom.h): process_batch with the clouds and T_sum of handles[k] taken from
+        the PointOdometry odoms[k] on the device, and its full cloud from the PointProcessor processors_or_none[k] (None, or a None entry:
+        the handle's full cloud stays as it is).  -> list of the dicts process() returns."""
+        n = len(handles)
+        if n < 1 or len(odoms) != n or (processors_or_none is not None and len(processors_or_none) != n):
+            raise LioError("process_batch_from_odom: one odometry (and one processor or None) per handle, at least one handle")
+        lib = handles[0].lib
+        H = (C.c_void_p * n)(*[h.h for h in handles])
+        O = (C.c_void_p * n)(*[o.h for o in odoms])
+        P = None if processors_or_none is None else (C.c_void_p * n)(*[None if p is None else p.h for p in processors_or_none])
+        Ta = (TransformF * n)()
+        it, ns = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        _chk(lib.dll.lio_map_process_batch_from_odom(H, O, P, n, Ta, it.ctypes.data_as(c_int32_p), ns.ctypes.data_as(c_int32_p)),
+             "lio_map_process_batch_from_odom")
         out = []
         for k, h in enumerate(handles):
             kz = C.c_int(0)

@@ -178,7 +178,7 @@ def load_parent(path):
     from lio_amd import capi
 
     dll = ctypes.CDLL(path)
-    tables = [capi._ODOM_BATCH_SIGS, capi._FRONTEND_SIGS, capi._MAP_BATCH_SIGS]
+    tables = [capi._ODOM_BATCH_SIGS, capi._FRONTEND_SIGS, capi._MAP_BATCH_SIGS, capi._MAP_FROM_ODOM_SIGS]
     saved = [dict(t) for t in tables]
     for t in tables:
         for name in list(t):
