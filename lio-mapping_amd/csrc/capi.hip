@@ -22,8 +22,6 @@
 #include "host_init.h"
 #include "kf_batch.h"
 #include <mutex>
-#include <thread>
-#include <atomic>
 #include <algorithm>
 
 #include "mapping.h"
@@ -36,23 +34,13 @@ struct lio_pim { std::shared_ptr<Preintegration> p; };
 // (members are destroyed in reverse order: the batch of one that serves lio_est_config.device_solve goes before the estimator it adopted)
 struct lio_map { std::unique_ptr<MappingDev> m; bool borrowed = false; };   // borrowed: the member of a lio_est (lio_est_map), not for lio_map_destroy
 struct lio_est { std::unique_ptr<Estimator> e; EstConfig cfg; lio_map map; lio_map_config map_cfg; std::unique_ptr<EstimatorBatch> solo; bool adopted = false; struct lio_est_batch *owner = nullptr; };
-// A batch of at least kBatchSplitFrom windows is TWO EstimatorBatch objects (the first and the second half of the windows) solved side by
-// side from two host threads: one part's host phases (describe, pack, write-back), syncs and latency-bound stages fill with the other
-// part's kernels (tools/batches_in_flight.py: 2 x 256 windows 20.1 k solves/s against 19.0 k for 1 x 512, 2 x 64 17.4 k against 16.1 k).
-// Every window's results are those of the window alone whatever the partition (the batch's contract), so the split is an execution
-// choice like the others ("parts", lio_est_batch_set_option).
-struct lio_est_batch {
-  std::unique_ptr<EstimatorBatch> b, b2;   // b2: the second part (null: one part)
-  int n1 = 0;                              // windows of b
-  int parts_opt = 0;                       // 0: by size, 1, 2
-  std::vector<std::pair<std::string, int>> options;   // what lio_est_batch_set_option has set, re-applied when the partition changes
-  std::vector<lio_est *> members;
-};
-static constexpr int kBatchSplitFrom = 96;    // measured (profiles/r6_n_batch_parts.txt): 16 .. 64 windows within noise, 96: + 4 %, 128 .. 512: + 7-8 %
+// `parts`: the batch's one or two EstimatorBatch objects (est_batch.h); null once the batch is dissolved.  `members`: adoption and ownership.
+struct lio_est_batch { std::unique_ptr<BatchParts> parts; std::vector<lio_est *> members; };
 // lio_pp_process_batch runs its sweeps through ONE multi-sweep processor shared by the handles of the call (`pool`); a handle whose last
 // sweep went that way reads its results from sweep `pool_sweep` of it.  The pool is shared state: its users take `mu`.
-// `gen` counts the pool's batches: a handle whose results a LATER batch of other handles overwrote (same pool, its own sweep not among them)
-// is told so instead of being handed somebody else's sweep.
+// `gen` counts the pool's batches, from 1.  A handle reads the pool only while its `pool_gen` is the pool's: a handle whose results a LATER
+// batch of other handles overwrote (same pool, its own sweep not among them) is told so instead of being handed somebody else's sweep, and
+// pool_gen = 0 is a lease on nothing (the handle of a batch that failed).
 struct lio_pp_pool { PointProcessorDev pp; std::mutex mu; unsigned long gen = 0; lio_pp_pool(float lo, float up, int r, const lio_pp_config &c) : pp(lo, up, r, c) {} };
 struct lio_pp { std::unique_ptr<PointProcessorDev> pp; std::shared_ptr<lio_pp_pool> pool; int pool_sweep = -1; unsigned long pool_gen = 0; };
 struct lio_odom { std::unique_ptr<OdometryDev> o; };
@@ -82,33 +70,162 @@ template <typename F> static int guarded(F &&f) {
   }
 }
 
-// the processor that holds the handle's last sweep, ready to be read: f(processor) under the pool's lock when that is the shared one
+// what a size_t accessor answers: f(), or 0 when it throws
+template <typename F> static size_t guarded_count(F &&f) {
+  size_t n = 0;
+  guarded([&] { n = f(); return LIO_OK; });
+  return n;
+}
+// a new handle that `build` has filled, or null (no memory, or build threw: reported as guarded reports it)
+template <typename H, typename F> static H *make_handle(F &&build) {
+  H *h = new (std::nothrow) H;
+  if (h && guarded([&] { build(*h); return LIO_OK; }) != LIO_OK) { delete h; h = nullptr; }
+  return h;
+}
+// no pointer twice (null entries are the caller's to refuse)
+template <typename T> static bool distinct(T *const *ptrs, size_t n) {
+  std::vector<const void *> sorted(ptrs, ptrs + n);
+  std::sort(sorted.begin(), sorted.end(), std::less<const void *>());
+  return std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end();
+}
+
+// The processors that hold the handles' last sweeps, ready to be read for as long as the lease lives: the handle's own one, or sweep
+// pool_sweep of the one it shares.  The distinct shared ones are locked in address order (one order for every caller) until the lease
+// goes; a handle whose pool has run another batch since is refused; a sweep still in flight (lio_pp_process_async) is waited for.
+// A null handle (or a null array) gives an empty slot.  What differs between the readers is theirs to say: `capacity_is_state` reports a
+// processor that ended over capacity as the reader's state error instead of passing its own capacity error on, `need_results` refuses a
+// processor without a completed sweep, and selecting the sweep (SelectSweep) is the reader's call.
+class PpLease {
+ public:
+  PpLease(const lio_pp *const *handles, size_t n, const char *who, bool capacity_is_state, bool need_results) : slot_(handles ? n : 0) {
+    std::vector<lio_pp_pool *> pools;
+    for (size_t k = 0; k < slot_.size(); ++k)
+      if (handles[k] && shared(handles[k])) pools.push_back(handles[k]->pool.get());
+    std::sort(pools.begin(), pools.end(), std::less<lio_pp_pool *>());
+    pools.erase(std::unique(pools.begin(), pools.end()), pools.end());
+    for (lio_pp_pool *p : pools) locks_.emplace_back(p->mu);
+    for (size_t k = 0; k < slot_.size(); ++k) {
+      const lio_pp *h = handles[k];
+      if (!h) continue;   // an empty slot
+      if (shared(h) && h->pool_gen != h->pool->gen)
+        throw std::runtime_error(std::string(who) + ": a processor's batch results were overwritten by a later lio_pp_process_batch on the storage it shared");
+      PointProcessorDev &p = shared(h) ? h->pool->pp : *h->pp;
+      try { p.ProcessFinish(); }
+      catch (const CapacityError &e) { if (!capacity_is_state) throw; throw std::runtime_error(e.what()); }
+      if (need_results && !p.has_results()) throw std::runtime_error(std::string(who) + ": a processor has no completed sweep");
+      slot_[k] = {&p, shared(h) ? h->pool_sweep : 0};
+    }
+  }
+  static bool shared(const lio_pp *h) { return h->pool && h->pool_sweep >= 0; }
+  PointProcessorDev *pp(size_t k) const { return k < slot_.size() ? slot_[k].pp : nullptr; }   // null: an empty slot
+  int sweep(size_t k) const { return slot_[k].sweep; }
+
+ private:
+  struct Slot { PointProcessorDev *pp = nullptr; int sweep = 0; };
+  std::vector<Slot> slot_;
+  std::vector<std::unique_lock<std::mutex>> locks_;
+};
+// f(the processor that holds the handle's last sweep, that sweep selected)
 template <typename F> static int pp_read(const lio_pp *h, F &&f) {
   return guarded([&] {
-    if (h->pool && h->pool_sweep >= 0) {
-      std::lock_guard<std::mutex> lk(h->pool->mu);
-      if (h->pool_gen != h->pool->gen) throw std::runtime_error("lio_pp: this handle's batch results were overwritten by a later lio_pp_process_batch on the storage it shared");
-      h->pool->pp.ProcessFinish();
-      h->pool->pp.SelectSweep(h->pool_sweep);
-      f(h->pool->pp);
-    } else {
-      h->pp->ProcessFinish();   // a sweep still in flight (lio_pp_process_async) is waited for
-      f(*h->pp);
-    }
+    PpLease lease(&h, 1, "lio_pp", false, false);
+    PointProcessorDev &p = *lease.pp(0);
+    if (PpLease::shared(h)) p.SelectSweep(lease.sweep(0));   // (a handle's own processor has one sweep, selected since it finished)
+    f(p);
     return LIO_OK;
   });
 }
 
-// f(part, first window of the part) on every part — two parts on two host threads
-template <typename F> static void batch_for_parts(lio_est_batch *h, F &&f) {
-  if (!h->b2) { f(*h->b, 0); return; }
-  std::exception_ptr err2;
-  std::thread t2([&] { try { f(*h->b2, h->n1); } catch (...) { err2 = std::current_exception(); } });
-  std::exception_ptr err1;
-  try { f(*h->b, 0); } catch (...) { err1 = std::current_exception(); }
-  t2.join();
-  if (err1) std::rethrow_exception(err1);
-  if (err2) std::rethrow_exception(err2);
+// The front the two batch calls share, behind the caller's own null checks: the refusals in the order the headers state them (the sensor
+// count; a null handle or what `arg_ok(k)` refuses of sensor k's other arguments; the same handle twice; an estimator's map), then the
+// handles' devices in the caller's order.  Nothing here touches the device or a handle.
+template <typename ArgOk> static int map_batch_devices(lio_map *const *handles, int n, ArgOk &&arg_ok, std::vector<MappingDev *> &m) {
+  if (n > LIO_MAP_BATCH_MAX_SENSORS) return LIO_ERR_CAPACITY;
+  for (int k = 0; k < n; ++k)
+    if (!handles[k] || !arg_ok(k)) return LIO_ERR_ARG;
+  if (!distinct(handles, size_t(n))) return LIO_ERR_ARG;
+  for (int k = 0; k < n; ++k)
+    if (handles[k]->borrowed || !handles[k]->m) return LIO_ERR_STATE;   // an estimator's map (lio_est_map) is stepped by its estimator
+  for (int k = 0; k < n; ++k) m.push_back(handles[k]->m.get());
+  return LIO_OK;
+}
+// the stateless blocks' device scratch, one per host thread
+struct Scratch {
+  hipStream_t s = nullptr;
+  DBuf<float4> a, b, coef, abs_coef;
+  VoxelGridDev vox;
+  KnnGrid grid;
+  DBuf<uint8_t> valid;
+  DBuf<float> score, tf, sqd, nbr;
+  DBuf<int32_t> idx;
+  DBuf<double> gn_partials, gn_sums;   // the Gauss-Newton hooks
+  DBuf<OdomState> gn_state;
+  DBuf<KfDesc> gn_kd;
+  DBuf<float> gn_rows;
+  float tf_host[8];
+  // The round trip of a stateless block, all on `s`: up(), the launches, down(), one sync() at the end (host memory handed to up() lives until then).
+  // host -> device.  The buffer holds at least one element (the kernels take its pointer when n == 0 too); an empty upload is skipped
+  template <typename T> void up(DBuf<T> &d, const void *src, size_t n) {
+    room(d, n);
+    if (n) LIO_HIP(hipMemcpyAsync(d.p, src, n * sizeof(T), hipMemcpyHostToDevice, s));
+  }
+  template <typename T> void room(DBuf<T> &d, size_t n) { d.reserve(std::max<size_t>(n, 1)); }   // for n results
+  template <typename T> void down(void *dst, const T *src, size_t n) {   // device -> host; an empty download is skipped
+    if (n) LIO_HIP(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, s));
+  }
+  void sync() { LIO_HIP(hipStreamSynchronize(s)); }
+  void up_tf(const lio_transform_f &T) {   // into `tf`, as the feature kernels read a transform: q (x y z w), p, pad
+    const float v[8] = {T.q[0], T.q[1], T.q[2], T.q[3], T.p[0], T.p[1], T.p[2], 0.f};
+    std::memcpy(tf_host, v, sizeof(v));
+    up(tf, tf_host, 8);
+  }
+  // the K-NN grid of cell edge `cell` over the host map that up() has put into `a`
+  void grid_over_a(const float *map, size_t n_map, float cell) {
+    float mn[3], mx[3];
+    host_cloud_bounds(map, n_map, mn, mx);
+    grid.build(a.p, n_map, mn, mx, cell, s);
+  }
+};
+// one frame of M points at tf_index 0, slots from 0
+static FeatArgs one_frame(const float4 *stack, int M, float mm, float mp) {
+  FeatArgs fa{};
+  fa.nframes = 1; fa.max_M = M; fa.min_match_sq_dis = mm; fa.min_plane_dis = mp;
+  fa.fr[0].stack = stack; fa.fr[0].M = M; fa.fr[0].slot_off = 0; fa.fr[0].tf_index = 0;
+  return fa;
+}
+static Scratch &scratch() {
+  static thread_local Scratch sc;
+  if (!sc.s) {
+    int nd = 0;
+    LIO_HIP(hipGetDeviceCount(&nd));
+    if (nd <= 0) throw DeviceError("no HIP device: the product has no CPU path");
+    LIO_HIP(hipStreamCreate(&sc.s));
+  }
+  return sc;
+}
+
+// the prior's linearization point, block after block: read into `out` (null: only counted) or, with `in`, written from it; the length
+static int prior_x0(MargPrior &pr, double *out, const double *in = nullptr) {
+  int len = 0;
+  for (auto &b : pr.x0)
+    for (double &v : b) { if (in) v = in[len]; else if (out) out[len] = v; ++len; }
+  return len;
+}
+// the last marginalization's prior as one n x n matrix and one n-vector of it (picked by `mat` / `vec`) and x0; returns n, 0 without a prior
+template <typename Mat, typename Vec> static int est_get_prior(const lio_est *h, Mat &&mat, Vec &&vec, double *M, double *v, double *x0, int *x0_len) {
+  if (!h) return LIO_ERR_ARG;
+  // JoinMarg rethrows a failed worker task: nothing may unwind through the C boundary
+  return guarded([&] {
+    h->e->JoinMarg();
+    const auto &pr = h->e->last_marg_;
+    if (!pr) return 0;
+    const int n = pr->n;
+    if (M) std::memcpy(M, mat(*pr), sizeof(double) * size_t(n) * n);
+    if (v) std::memcpy(v, vec(*pr), sizeof(double) * n);
+    const int len = prior_x0(*pr, x0);
+    if (x0_len) *x0_len = len;
+    return n;
+  });
 }
 
 extern "C" {
@@ -122,10 +239,13 @@ void lio_pp_default_config(lio_pp_config *c) {
   c->max_corner_sharp = 2; c->max_corner_less_sharp = 20; c->max_surf_flat = 4; c->less_flat_filter_size = 0.2f;
   c->infer_start_ori = 0; c->rad_diff = 0.2;
 }
-int lio_pp_check_config(float lo, float up, int rings, const lio_pp_config *c) {
-  if (rings <= 0 || rings > LIO_PP_MAX_RINGS || !(up > lo)) return LIO_ERR_ARG;
+static lio_pp_config pp_config_or_default(const lio_pp_config *c) {
   lio_pp_config cfg;
   if (c) cfg = *c; else lio_pp_default_config(&cfg);
+  return cfg;
+}
+static int pp_check_config(float lo, float up, int rings, const lio_pp_config &cfg) {
+  if (rings <= 0 || rings > LIO_PP_MAX_RINGS || !(up > lo)) return LIO_ERR_ARG;
   if (cfg.num_scan_subregions < 1 || cfg.num_scan_subregions > 16 || cfg.num_curvature_regions < 1 || cfg.num_curvature_regions > 8) return LIO_ERR_ARG;
   // pick caps size LDS tables and device reserves; the leaf is inverted: keep them in sane ranges
   const int caps[3] = {cfg.max_corner_sharp, cfg.max_corner_less_sharp, cfg.max_surf_flat};
@@ -140,21 +260,17 @@ int lio_pp_check_config(float lo, float up, int rings, const lio_pp_config *c) {
   if (cfg.max_corner_less_sharp + cfg.max_surf_flat > 64) return LIO_ERR_CAPACITY;
   return LIO_OK;
 }
+int lio_pp_check_config(float lo, float up, int rings, const lio_pp_config *c) { return pp_check_config(lo, up, rings, pp_config_or_default(c)); }
 lio_pp *lio_pp_create(float lo, float up, int rings, const lio_pp_config *c) {
-  const int chk = lio_pp_check_config(lo, up, rings, c);
+  const lio_pp_config cfg = pp_config_or_default(c);
+  const int chk = pp_check_config(lo, up, rings, cfg);
   if (chk != LIO_OK) {
     if (chk == LIO_ERR_CAPACITY)
       std::fprintf(stderr, "lio_pp_create: LIO_ERR_CAPACITY — max_corner_less_sharp + max_surf_flat > 64 picks per subregion is beyond k_ring_pick's per-wave pick table "
                            "(lio_pp_check_config reports the code)\n");
     return nullptr;
   }
-  lio_pp_config cfg;
-  if (c) cfg = *c; else lio_pp_default_config(&cfg);
-  lio_pp *h = new (std::nothrow) lio_pp;
-  if (!h) return nullptr;
-  int rc = guarded([&] { h->pp.reset(new PointProcessorDev(lo, up, rings, cfg)); return LIO_OK; });
-  if (rc != LIO_OK) { delete h; return nullptr; }
-  return h;
+  return make_handle<lio_pp>([&](lio_pp &h) { h.pp.reset(new PointProcessorDev(lo, up, rings, cfg)); });
 }
 void lio_pp_destroy(lio_pp *h) { delete h; }
 float lio_pp_start_ori(const lio_pp *h) {
@@ -183,10 +299,10 @@ static int pp_process_batch(lio_pp *const *handles, const float *const *xyzi, co
   bool same = true;
   for (int k = 0; k < n_sweeps; ++k) {
     if (!handles[k] || (!xyzi[k] && n[k]) || (ring && !ring[k] && n[k])) return LIO_ERR_ARG;
-    for (int j = 0; j < k; ++j) if (handles[j] == handles[k]) return LIO_ERR_ARG;
     same = same && handles[k]->pp->SameSensor(*handles[0]->pp);
   }
   if (n_sweeps == 0) return LIO_OK;
+  if (!distinct(handles, size_t(n_sweeps))) return LIO_ERR_ARG;
   if (n_sweeps >= 2 && same) {
     // ONE launch chain over all sweeps: the handles share a multi-sweep processor (kept for the next call), every handle reads its own
     // sweep of it; a sweep's start azimuth still goes through ITS handle's ten-sweep history (infer_start_ori)
@@ -198,14 +314,19 @@ static int pp_process_batch(lio_pp *const *handles, const float *const *xyzi, co
       }
       std::vector<StartOriFilter *> filters(static_cast<size_t>(n_sweeps));
       std::lock_guard<std::mutex> lk(pool->mu);
-      ++pool->gen;
+      ++pool->gen;   // the chain overwrites the pool's storage: every lease on it ends here
+      // Everything below can throw (a handle's own sweep still in flight may have ended over capacity), and nothing is served of a failed
+      // call: until the chain has finished, the handles of the call hold a lease on nothing
+      for (int k = 0; k < n_sweeps; ++k) { handles[k]->pool = pool; handles[k]->pool_sweep = k; handles[k]->pool_gen = 0; }
+      const auto lease = [&] { for (int k = 0; k < n_sweeps; ++k) handles[k]->pool_gen = pool->gen; };
       for (int k = 0; k < n_sweeps; ++k) {
         handles[k]->pp->ProcessFinish();
-        handles[k]->pool = pool; handles[k]->pool_sweep = k; handles[k]->pool_gen = pool->gen;
         filters[size_t(k)] = &handles[k]->pp->start_ori_filter();
       }
       pool->pp.ProcessLaunchBatch(xyzi, ring, n, n_sweeps, on_device, filters.data());
-      pool->pp.ProcessFinish();
+      try { pool->pp.ProcessFinish(); }
+      catch (const CapacityError &) { lease(); throw; }   // finished, over capacity: the pool's processor reads zero for every sweep
+      lease();
       return LIO_OK;
     });
   }
@@ -270,19 +391,13 @@ int lio_pp_get_ring_intensity(const lio_pp *h, float *out) {
 // ---------------------------------------------------------------- PointOdometry
 lio_odom *lio_odom_create(float scan_period, int io_ratio, int max_iter, int no_deskew) {
   if (!(scan_period > 0) || max_iter < 1) return nullptr;
-  lio_odom *h = new (std::nothrow) lio_odom;
-  if (!h) return nullptr;
-  int rc = guarded([&] { h->o.reset(new OdometryDev(scan_period, io_ratio, max_iter, no_deskew != 0)); return LIO_OK; });
-  if (rc != LIO_OK) { delete h; return nullptr; }
-  return h;
+  return make_handle<lio_odom>([&](lio_odom &h) { h.o.reset(new OdometryDev(scan_period, io_ratio, max_iter, no_deskew != 0)); });
 }
 void lio_odom_destroy(lio_odom *h) { delete h; }
 // the handles' devices in the caller's order; false: the same handle twice
 static bool odom_devices(lio_odom *const *handles, int n, std::vector<OdometryDev *> &o) {
   for (int k = 0; k < n; ++k) o.push_back(handles[k]->o.get());
-  std::vector<OdometryDev *> sorted = o;
-  std::sort(sorted.begin(), sorted.end());
-  return std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end();
+  return distinct(handles, size_t(n));
 }
 // what a step hands back per sensor; every array is optional
 static void odom_results(OdometryDev *const *o, int n, lio_transform_f *Tsum, lio_transform_f *Tes, int32_t *iters, int32_t *nsel) {
@@ -320,8 +435,7 @@ int lio_odom_process_batch(lio_odom *const *handles, int n_sensors, const float 
     return int(LIO_OK);
   });
 }
-// include/lio_frontend_batch.h.  Every pp[k] is resolved to (processor, sweep) as pp_read resolves it; the shared processors stay locked
-// until the chain, which reads their clouds, has returned synchronised.
+// include/lio_frontend_batch.h.  The lease on the processors is held until the chain, which reads their clouds, has returned synchronised.
 int lio_odom_process_batch_from_pp(lio_odom *const *handles, lio_pp *const *pp, int n_sensors, lio_transform_f *Tsum, lio_transform_f *Tes,
                                    int32_t *iters, int32_t *nsel) {
   if (!handles || !pp || n_sensors < 1) return LIO_ERR_ARG;
@@ -332,28 +446,14 @@ int lio_odom_process_batch_from_pp(lio_odom *const *handles, lio_pp *const *pp, 
     const size_t n = size_t(n_sensors);
     std::vector<OdometryDev *> o;
     if (!odom_devices(handles, n_sensors, o)) return int(LIO_ERR_ARG);
-    std::vector<lio_pp_pool *> pools;
-    for (size_t k = 0; k < n; ++k)
-      if (pp[k]->pool && pp[k]->pool_sweep >= 0) pools.push_back(pp[k]->pool.get());
-    std::sort(pools.begin(), pools.end());   // (one order for every caller)
-    pools.erase(std::unique(pools.begin(), pools.end()), pools.end());
-    std::vector<std::unique_lock<std::mutex>> locks;
-    for (lio_pp_pool *p : pools) locks.emplace_back(p->mu);
+    const PpLease lease(pp, n, "lio_odom_process_batch_from_pp", true, true);
     // the host table: four (source, count) pairs per sensor
     std::vector<const float *> src[4];
     std::vector<size_t> cnt[4];
     for (int c = 0; c < 4; ++c) { src[c].resize(n); cnt[c].resize(n); }
     for (size_t k = 0; k < n; ++k) {
-      const lio_pp *h = pp[k];
-      const bool pooled = h->pool && h->pool_sweep >= 0;
-      if (pooled && h->pool_gen != h->pool->gen)
-        throw std::runtime_error("lio_odom_process_batch_from_pp: a processor's batch results were overwritten by a later lio_pp_process_batch on the storage it shared");
-      PointProcessorDev &p = pooled ? h->pool->pp : *h->pp;
-      try { p.ProcessFinish(); }   // a sweep still in flight (lio_pp_process_async) is waited for
-      catch (const CapacityError &e) { throw std::runtime_error(e.what()); }
-      if (!p.has_results()) throw std::runtime_error("lio_odom_process_batch_from_pp: a processor has no completed sweep");
       const float4 *s4[4]; size_t n4[4];
-      p.DeviceClouds(pooled ? h->pool_sweep : 0, s4, n4);
+      lease.pp(k)->DeviceClouds(lease.sweep(k), s4, n4);
       for (int c = 0; c < 4; ++c) { src[c][k] = reinterpret_cast<const float *>(s4[c]); cnt[c][k] = n4[c]; }
     }
     OdometryDev::ProcessBatch(o.data(), n_sensors, src[0].data(), cnt[0].data(), src[1].data(), cnt[1].data(), src[2].data(), cnt[2].data(), src[3].data(),
@@ -376,9 +476,7 @@ int lio_odom_enable(lio_odom *h, int on) {
 }
 size_t lio_odom_get_last_cloud(const lio_odom *h, int which, float *out) {
   if (!h || which < 0 || which > 1) return 0;
-  size_t n = 0;
-  guarded([&] { n = h->o->GetLastCloud(which, out); return LIO_OK; });
-  return n;
+  return guarded_count([&] { return h->o->GetLastCloud(which, out); });
 }
 
 // ---------------------------------------------------------------- ImuInitializer (host)
@@ -435,28 +533,27 @@ lio_map *lio_map_create(const lio_map_config *c) {
   if (c) cfg = *c; else lio_map_default_config(&cfg);
   if (!(cfg.corner_filter_size > 0) || !(cfg.surf_filter_size > 0) || cfg.num_max_iterations < 1) return nullptr;
   if (cfg.map_builder && cfg.skip_count < 1) return nullptr;
-  lio_map *h = new (std::nothrow) lio_map;
-  if (!h) return nullptr;
-  int rc = guarded([&] { h->m.reset(new MappingDev(cfg)); return LIO_OK; });
-  if (rc != LIO_OK) { delete h; return nullptr; }
-  return h;
+  return make_handle<lio_map>([&](lio_map &h) { h.m.reset(new MappingDev(cfg)); });
 }
 void lio_map_destroy(lio_map *h) {
   if (h && h->borrowed) { std::fprintf(stderr, "[lio_hip] lio_map_destroy: the handle belongs to a lio_est (lio_est_map); ignored\n"); return; }
   delete h;
 }
-// what lio_map_process and lio_map_process_batch answer for one handle after its step; each pointer may be null
-static void map_step_results(const MappingDev &m, lio_transform_f *Taft, int32_t *iters, int32_t *nsel) {
-  if (Taft) fromT(m.transform_aft_mapped_, Taft);
-  if (iters) *iters = m.iterations_;
-  if (nsel) *nsel = m.num_selected_;
+// what a step hands back per handle; every array is optional
+static void map_results(MappingDev *const *m, int n, lio_transform_f *Taft, int32_t *iters, int32_t *nsel) {
+  for (int k = 0; k < n; ++k) {
+    if (Taft) fromT(m[k]->transform_aft_mapped_, &Taft[k]);
+    if (iters) iters[k] = m[k]->iterations_;
+    if (nsel) nsel[k] = m[k]->num_selected_;
+  }
 }
 int lio_map_process(lio_map *h, const float *corner, size_t nc, const float *surf, size_t ns, const lio_transform_f *Tsum, lio_transform_f *Taft,
                     int *iters, int *nsel) {
   if (!h || !Tsum || (!corner && nc) || (!surf && ns)) return LIO_ERR_ARG;
   return guarded([&] {
-    h->m->Process(corner, nc, surf, ns, toT(*Tsum));
-    map_step_results(*h->m, Taft, iters, nsel);
+    MappingDev *m = h->m.get();
+    m->Process(corner, nc, surf, ns, toT(*Tsum));
+    map_results(&m, 1, Taft, iters, nsel);
     return LIO_OK;
   });
 }
@@ -464,79 +561,47 @@ int lio_map_process(lio_map *h, const float *corner, size_t nc, const float *sur
 int lio_map_process_batch(lio_map *const *handles, int n_sensors, const float *const *corner, const size_t *nc, const float *const *surf, const size_t *ns,
                           const lio_transform_f *Tsum, lio_transform_f *Taft, int32_t *iters, int32_t *nsel) {
   if (!handles || n_sensors < 1 || !corner || !nc || !surf || !ns || !Tsum) return LIO_ERR_ARG;
-  if (n_sensors > LIO_MAP_BATCH_MAX_SENSORS) return LIO_ERR_CAPACITY;
-  for (int k = 0; k < n_sensors; ++k)
-    if (!handles[k] || (!corner[k] && nc[k]) || (!surf[k] && ns[k])) return LIO_ERR_ARG;
-  {
-    std::vector<const lio_map *> sorted(handles, handles + n_sensors);
-    std::sort(sorted.begin(), sorted.end());
-    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return LIO_ERR_ARG;   // the same handle twice
-  }
-  for (int k = 0; k < n_sensors; ++k)
-    if (handles[k]->borrowed || !handles[k]->m) return LIO_ERR_STATE;   // an estimator's map (lio_est_map) is stepped by its estimator
+  std::vector<MappingDev *> m;
+  const int rc = map_batch_devices(handles, n_sensors, [&](int k) { return (corner[k] || !nc[k]) && (surf[k] || !ns[k]); }, m);
+  if (rc != LIO_OK) return rc;
   return guarded([&] {
-    std::vector<MappingDev *> m;
     std::vector<Rigidf> sums;
-    for (int k = 0; k < n_sensors; ++k) { m.push_back(handles[k]->m.get()); sums.push_back(toT(Tsum[k])); }
+    for (int k = 0; k < n_sensors; ++k) sums.push_back(toT(Tsum[k]));
     MappingDev::ProcessBatch(m.data(), n_sensors, corner, nc, surf, ns, sums.data());
-    for (int k = 0; k < n_sensors; ++k) map_step_results(*m[size_t(k)], Taft ? Taft + k : nullptr, iters ? iters + k : nullptr, nsel ? nsel + k : nullptr);
+    map_results(m.data(), n_sensors, Taft, iters, nsel);
     return int(LIO_OK);
   });
 }
-// include/lio_map_from_odom.h.  Every check comes before any device work and before any handle changes; every pp[k] is resolved to
-// (processor, sweep) as pp_read resolves it, and the shared processors stay locked until the chain, which reads their clouds, has returned
-// synchronised.
+// include/lio_map_from_odom.h.  Every check comes before any device work and before any handle changes; the lease on the processors is
+// held until the chain, which reads their clouds, has returned synchronised.  A null `pp`, or a null entry: this handle's full cloud stays.
 int lio_map_process_batch_from_odom(lio_map *const *handles, lio_odom *const *odom, lio_pp *const *pp, int n_sensors, lio_transform_f *Taft,
                                     int32_t *iters, int32_t *nsel) {
   if (!handles || !odom || n_sensors < 1) return LIO_ERR_ARG;
-  if (n_sensors > LIO_MAP_BATCH_MAX_SENSORS) return LIO_ERR_CAPACITY;
+  std::vector<MappingDev *> m;
+  const int rc = map_batch_devices(handles, n_sensors, [&](int k) { return odom[k] != nullptr; }, m);
+  if (rc != LIO_OK) return rc;
   for (int k = 0; k < n_sensors; ++k)
-    if (!handles[k] || !odom[k]) return LIO_ERR_ARG;
-  {
-    std::vector<const lio_map *> sorted(handles, handles + n_sensors);
-    std::sort(sorted.begin(), sorted.end());
-    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return LIO_ERR_ARG;   // the same handle twice
-  }
-  for (int k = 0; k < n_sensors; ++k) {
-    if (handles[k]->borrowed || !handles[k]->m) return LIO_ERR_STATE;   // an estimator's map (lio_est_map) is stepped by its estimator
-    if (!odom[k]->o->processed()) return LIO_ERR_STATE;                 // no sweep to hand over
-  }
+    if (!odom[k]->o->processed()) return LIO_ERR_STATE;   // no sweep to hand over
   return guarded([&] {
     const size_t n = size_t(n_sensors);
-    std::vector<lio_pp_pool *> pools;
-    for (size_t k = 0; pp && k < n; ++k)
-      if (pp[k] && pp[k]->pool && pp[k]->pool_sweep >= 0) pools.push_back(pp[k]->pool.get());
-    std::sort(pools.begin(), pools.end());   // (one order for every caller)
-    pools.erase(std::unique(pools.begin(), pools.end()), pools.end());
-    std::vector<std::unique_lock<std::mutex>> locks;
-    for (lio_pp_pool *p : pools) locks.emplace_back(p->mu);
-    std::vector<MappingDev *> m(n);
+    const PpLease lease(pp, n, "lio_map_process_batch_from_odom", true, true);
     std::vector<Rigidf> sums(n);
     std::vector<const float *> src[2];
     std::vector<size_t> cnt[2];
     for (int c = 0; c < 2; ++c) { src[c].resize(n); cnt[c].resize(n); }
     std::vector<MapFullSource> full(n, MapFullSource{});
     for (size_t k = 0; k < n; ++k) {
-      m[k] = handles[k]->m.get();
       const OdometryDev::DeviceView v = odom[k]->o->View();
       sums[k] = odom[k]->o->transform_sum_;
       for (int c = 0; c < 2; ++c) { src[c][k] = reinterpret_cast<const float *>(v.last[c]); cnt[c][k] = v.n_last[c]; }
-      const lio_pp *h = pp ? pp[k] : nullptr;
-      if (!h) continue;   // this handle's full cloud stays
-      const bool pooled = h->pool && h->pool_sweep >= 0;
-      if (pooled && h->pool_gen != h->pool->gen)
-        throw std::runtime_error("lio_map_process_batch_from_odom: a processor's batch results were overwritten by a later lio_pp_process_batch on the storage it shared");
-      PointProcessorDev &p = pooled ? h->pool->pp : *h->pp;
-      try { p.ProcessFinish(); }   // a sweep still in flight (lio_pp_process_async) is waited for
-      catch (const CapacityError &e) { throw std::runtime_error(e.what()); }
-      if (!p.has_results()) throw std::runtime_error("lio_map_process_batch_from_odom: a processor has no completed sweep");
+      if (!lease.pp(k)) continue;
       MapFullSource &f = full[k];
       f.set = true;
-      p.DeviceRings(pooled ? h->pool_sweep : 0, f.pts, f.n);
+      lease.pp(k)->DeviceRings(lease.sweep(k), f.pts, f.n);
       f.to_end = v.to_end; f.time_factor = v.time_factor; f.no_deskew = v.no_deskew;
     }
     MappingDev::ProcessBatch(m.data(), n_sensors, src[0].data(), cnt[0].data(), src[1].data(), cnt[1].data(), sums.data(), full.data());
-    for (size_t k = 0; k < n; ++k) map_step_results(*m[k], Taft ? Taft + k : nullptr, iters ? iters + k : nullptr, nsel ? nsel + k : nullptr);
+    map_results(m.data(), n_sensors, Taft, iters, nsel);
     return int(LIO_OK);
   });
 }
@@ -569,15 +634,11 @@ int lio_map_update_map_database(lio_map *h, const float *corner, size_t nc, cons
 }
 size_t lio_map_get_cloud(const lio_map *h, int which, float *out) {
   if (!h || which < 0 || which > 3) return 0;
-  size_t n = 0;
-  guarded([&] { n = h->m->GetCloud(which, out); return LIO_OK; });
-  return n;
+  return guarded_count([&] { return h->m->GetCloud(which, out); });
 }
 size_t lio_map_get_cube(const lio_map *h, int cls, uint32_t idx, float *out) {
   if (!h || cls < 0 || cls > 1 || idx >= uint32_t(MappingDev::L * MappingDev::Wd * MappingDev::H)) return 0;
-  size_t n = 0;
-  guarded([&] { n = h->m->GetCube(cls, idx, out); return LIO_OK; });
-  return n;
+  return guarded_count([&] { return h->m->GetCube(cls, idx, out); });
 }
 size_t lio_map_get_cube_state(const lio_map *h, int cen[3], uint32_t *valid) {
   if (!h) return 0;
@@ -587,9 +648,7 @@ size_t lio_map_get_cube_state(const lio_map *h, int cen[3], uint32_t *valid) {
 }
 size_t lio_map_get_score_point_coeff(const lio_map *h, float *score, float *point, float *coeff) {
   if (!h) return 0;
-  size_t n = 0;
-  guarded([&] { n = h->m->GetScorePointCoeff(score, point, coeff); return LIO_OK; });
-  return n;
+  return guarded_count([&] { return h->m->GetScorePointCoeff(score, point, coeff); });
 }
 
 // ---------------------------------------------------------------- batched keyframe refinement
@@ -598,11 +657,7 @@ lio_kf_batch *lio_kf_batch_create(const lio_map_config *c) {
   lio_map_config cfg;
   if (c) cfg = *c; else lio_map_default_config(&cfg);
   if (cfg.num_max_iterations < 1) return nullptr;
-  lio_kf_batch *h = new (std::nothrow) lio_kf_batch;
-  if (!h) return nullptr;
-  int rc = guarded([&] { h->b.reset(new KfBatchDev(cfg)); return LIO_OK; });
-  if (rc != LIO_OK) { delete h; return nullptr; }
-  return h;
+  return make_handle<lio_kf_batch>([&](lio_kf_batch &h) { h.b.reset(new KfBatchDev(cfg)); });
 }
 void lio_kf_batch_destroy(lio_kf_batch *h) { delete h; }
 int lio_kf_batch_add_map(lio_kf_batch *h, const float *corner, size_t nc, const float *surf, size_t ns) {
@@ -685,42 +740,14 @@ int lio_compact_decode(const float *d, size_t n, lio_transform_f *T, size_t *nc,
 }
 
 // ---------------------------------------------------------------- stateless blocks
-struct Scratch {
-  hipStream_t s = nullptr;
-  DBuf<float4> a, b, c;
-  VoxelGridDev vox;
-  KnnGrid grid;
-  DBuf<uint8_t> valid;
-  DBuf<float4> coef, abs_coef;
-  DBuf<float> score, tf;
-  DBuf<int32_t> idx;
-  DBuf<float> sqd, nbr;
-  DBuf<float> bounds;
-  DBuf<double> gn_partials, gn_sums;   // the Gauss-Newton hooks
-  DBuf<OdomState> gn_state;
-  DBuf<KfDesc> gn_kd;
-  DBuf<float> gn_rows;
-};
-static Scratch &scratch() {
-  static thread_local Scratch sc;
-  if (!sc.s) {
-    int nd = 0;
-    LIO_HIP(hipGetDeviceCount(&nd));
-    if (nd <= 0) throw DeviceError("no HIP device: the product has no CPU path");
-    LIO_HIP(hipStreamCreate(&sc.s));
-  }
-  return sc;
-}
-
 int lio_voxel_grid(const float *xyzi, size_t n, float leaf, float *out, size_t *n_out) {
   if ((!xyzi && n) || !out || !n_out || !(leaf > 0)) return LIO_ERR_ARG;
   return guarded([&] {
     Scratch &sc = scratch();
-    sc.a.reserve(std::max<size_t>(n, 1));
-    if (n) LIO_HIP(hipMemcpyAsync(sc.a.p, xyzi, n * sizeof(float4), hipMemcpyHostToDevice, sc.s));
+    sc.up(sc.a, xyzi, n);
     size_t m = sc.vox.run(sc.a.p, n, leaf, sc.b, sc.s);
-    if (m) LIO_HIP(hipMemcpyAsync(out, sc.b.p, m * sizeof(float4), hipMemcpyDeviceToHost, sc.s));
-    LIO_HIP(hipStreamSynchronize(sc.s));
+    sc.down(out, sc.b.p, m);
+    sc.sync();
     *n_out = m;
     return LIO_OK;
   });
@@ -760,14 +787,14 @@ int lio_seg_bounds(const float *const *xyzi, const size_t *n, int nseg, float in
     if (n[k] >= size_t(INT_MAX)) return LIO_ERR_CAPACITY;
   }
   return guarded([&] {
-    hipStream_t s = scratch().s;
+    Scratch &sc = scratch();
+    hipStream_t s = sc.s;
     std::vector<DBuf<float4>> clouds(static_cast<size_t>(nseg));
     GridBatch gb;
     gb.begin(0, nseg);
     for (int k = 0; k < nseg; ++k) {
       DBuf<float4> &c = clouds[size_t(k)];
-      c.reserve(std::max<size_t>(n[k], 1));
-      if (n[k]) LIO_HIP(hipMemcpyAsync(c.p, xyzi[k], n[k] * sizeof(float4), hipMemcpyHostToDevice, s));
+      sc.up(c, xyzi[k], n[k]);
       gb.add(c.p, int(n[k]));
     }
     std::memcpy(out, gb.bounds(s, inv_leaf), size_t(nseg) * sizeof(VoxParams));
@@ -781,19 +808,12 @@ int lio_knn(const float *map, size_t n_map, const float *query, size_t m, int k,
   if (m > size_t(INT_MAX) / 8 || n_map > size_t(INT_MAX)) return LIO_ERR_CAPACITY;   // eight lanes per query, int thread ids
   return guarded([&] {
     Scratch &sc = scratch();
-    sc.a.reserve(std::max<size_t>(n_map, 1)); sc.b.reserve(std::max<size_t>(m, 1));
-    sc.idx.reserve(std::max<size_t>(m * k, 1)); sc.sqd.reserve(std::max<size_t>(m * k, 1));
-    if (n_map) LIO_HIP(hipMemcpyAsync(sc.a.p, map, n_map * sizeof(float4), hipMemcpyHostToDevice, sc.s));
-    if (m) LIO_HIP(hipMemcpyAsync(sc.b.p, query, m * sizeof(float4), hipMemcpyHostToDevice, sc.s));
-    float mn[3], mx[3];
-    host_cloud_bounds(map, n_map, mn, mx);
-    sc.grid.build(sc.a.p, n_map, mn, mx, knn_cell_edge(radius_sq), sc.s);
+    sc.up(sc.a, map, n_map); sc.up(sc.b, query, m);
+    sc.room(sc.idx, m * k); sc.room(sc.sqd, m * k);
+    sc.grid_over_a(map, n_map, knn_cell_edge(radius_sq));
     launch_knn(sc.b.p, int(m), k, radius_sq, sc.grid.sorted(), sc.grid.cells(), sc.grid.desc(), sc.idx.p, sc.sqd.p, sc.s);
-    if (m) {
-      LIO_HIP(hipMemcpyAsync(idx, sc.idx.p, m * k * sizeof(int32_t), hipMemcpyDeviceToHost, sc.s));
-      LIO_HIP(hipMemcpyAsync(sqd, sc.sqd.p, m * k * sizeof(float), hipMemcpyDeviceToHost, sc.s));
-    }
-    LIO_HIP(hipStreamSynchronize(sc.s));
+    sc.down(idx, sc.idx.p, m * k); sc.down(sqd, sc.sqd.p, m * k);
+    sc.sync();
     return LIO_OK;
   });
 }
@@ -805,20 +825,12 @@ int lio_knn_walk(const float *map, size_t n_map, const float *query, size_t m, f
   if (m > size_t(INT_MAX) / 8 || n_map > size_t(INT_MAX)) return LIO_ERR_CAPACITY;
   return guarded([&] {
     Scratch &sc = scratch();
-    sc.a.reserve(std::max<size_t>(n_map, 1)); sc.b.reserve(std::max<size_t>(m, 1));
-    sc.idx.reserve(std::max<size_t>(m * 5, 1)); sc.sqd.reserve(std::max<size_t>(m * 5, 1)); sc.nbr.reserve(std::max<size_t>(m * 15, 1));
-    if (n_map) LIO_HIP(hipMemcpyAsync(sc.a.p, map, n_map * sizeof(float4), hipMemcpyHostToDevice, sc.s));
-    if (m) LIO_HIP(hipMemcpyAsync(sc.b.p, query, m * sizeof(float4), hipMemcpyHostToDevice, sc.s));
-    float mn[3], mx[3];
-    host_cloud_bounds(map, n_map, mn, mx);
-    sc.grid.build(sc.a.p, n_map, mn, mx, cell, sc.s);
+    sc.up(sc.a, map, n_map); sc.up(sc.b, query, m);
+    sc.room(sc.idx, m * 5); sc.room(sc.sqd, m * 5); sc.room(sc.nbr, m * 15);
+    sc.grid_over_a(map, n_map, cell);
     launch_knn_walk(sc.b.p, int(m), lanes_per_query, sc.grid.sorted(), sc.grid.cells(), sc.grid.desc(), sc.idx.p, sc.sqd.p, sc.nbr.p, sc.s);
-    if (m) {
-      LIO_HIP(hipMemcpyAsync(idx, sc.idx.p, m * 5 * sizeof(int32_t), hipMemcpyDeviceToHost, sc.s));
-      LIO_HIP(hipMemcpyAsync(sqd, sc.sqd.p, m * 5 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
-      LIO_HIP(hipMemcpyAsync(nbr_xyz, sc.nbr.p, m * 15 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
-    }
-    LIO_HIP(hipStreamSynchronize(sc.s));
+    sc.down(idx, sc.idx.p, m * 5); sc.down(sqd, sc.sqd.p, m * 5); sc.down(nbr_xyz, sc.nbr.p, m * 15);
+    sc.sync();
     return LIO_OK;
   });
 }
@@ -829,26 +841,14 @@ int lio_fit_five(int form, const float *nbr_xyz, const float *fifth_sqd, const f
   if (m > size_t(INT_MAX) / 5) return LIO_ERR_CAPACITY;   // positions 5 i .. 5 i + 4 are ints
   return guarded([&] {
     Scratch &sc = scratch();
-    sc.a.reserve(std::max<size_t>(m * 5, 1)); sc.b.reserve(std::max<size_t>(m, 1)); sc.sqd.reserve(std::max<size_t>(m, 1));
-    sc.valid.reserve(std::max<size_t>(m, 1)); sc.coef.reserve(std::max<size_t>(m, 1)); sc.score.reserve(std::max<size_t>(m, 1));
-    sc.abs_coef.reserve(std::max<size_t>(m, 1)); sc.tf.reserve(8);
     std::vector<float4> nb(m * 5);   // the fits load float4 map points; .w (the original index) is not read by them
     for (size_t k = 0; k < m * 5; ++k) nb[k] = make_float4(nbr_xyz[3 * k], nbr_xyz[3 * k + 1], nbr_xyz[3 * k + 2], 0.f);
-    const float tf[8] = {T->q[0], T->q[1], T->q[2], T->q[3], T->p[0], T->p[1], T->p[2], 0.f};
-    LIO_HIP(hipMemcpyAsync(sc.tf.p, tf, sizeof(tf), hipMemcpyHostToDevice, sc.s));
-    if (m) {
-      LIO_HIP(hipMemcpyAsync(sc.a.p, nb.data(), m * 5 * sizeof(float4), hipMemcpyHostToDevice, sc.s));
-      LIO_HIP(hipMemcpyAsync(sc.b.p, stack, m * sizeof(float4), hipMemcpyHostToDevice, sc.s));
-      LIO_HIP(hipMemcpyAsync(sc.sqd.p, fifth_sqd, m * sizeof(float), hipMemcpyHostToDevice, sc.s));
-    }
+    sc.up_tf(*T);
+    sc.up(sc.a, nb.data(), m * 5); sc.up(sc.b, stack, m); sc.up(sc.sqd, fifth_sqd, m);
+    sc.room(sc.valid, m); sc.room(sc.coef, m); sc.room(sc.score, m); sc.room(sc.abs_coef, m);
     launch_fit_five(form, mm, mp, fixed_pz, sc.tf.p, sc.b.p, int(m), sc.a.p, sc.sqd.p, sc.valid.p, sc.coef.p, sc.score.p, sc.abs_coef.p, sc.s);
-    if (m) {
-      LIO_HIP(hipMemcpyAsync(valid, sc.valid.p, m, hipMemcpyDeviceToHost, sc.s));
-      LIO_HIP(hipMemcpyAsync(coeff, sc.coef.p, m * sizeof(float4), hipMemcpyDeviceToHost, sc.s));
-      LIO_HIP(hipMemcpyAsync(score, sc.score.p, m * sizeof(float), hipMemcpyDeviceToHost, sc.s));
-      LIO_HIP(hipMemcpyAsync(abs_coeff, sc.abs_coef.p, m * sizeof(float4), hipMemcpyDeviceToHost, sc.s));
-    }
-    LIO_HIP(hipStreamSynchronize(sc.s));   // also keeps nb and tf alive until the uploads have read them
+    sc.down(valid, sc.valid.p, m); sc.down(coeff, sc.coef.p, m); sc.down(score, sc.score.p, m); sc.down(abs_coeff, sc.abs_coef.p, m);
+    sc.sync();   // also keeps nb alive until its upload has read it
     return LIO_OK;
   });
 }
@@ -883,28 +883,24 @@ int lio_gn_rows_map(int form, const float *stack, size_t m, const uint8_t *valid
   return guarded([&] {
     Scratch &sc = scratch();
     const int M = int(m), nb = odom_rows_blocks(M);
-    sc.b.reserve(std::max<size_t>(m, 1)); sc.valid.reserve(std::max<size_t>(m, 1)); sc.coef.reserve(std::max<size_t>(m, 1));
-    sc.idx.reserve(std::max<size_t>((m + 3) / 4, 1));   // ok_out, as bytes
-    sc.gn_rows.reserve(std::max<size_t>(m * 7, 1)); sc.gn_partials.reserve(size_t(nb) * 28); sc.gn_state.reserve(1); sc.gn_kd.reserve(1);
+    sc.room(sc.idx, (m + 3) / 4);   // ok_out, as bytes
+    sc.room(sc.gn_rows, m * 7); sc.gn_partials.reserve(size_t(nb) * 28);
     const OdomState st = odom_state_at(toT(*T));
-    LIO_HIP(hipMemcpyAsync(sc.gn_state.p, &st, sizeof(st), hipMemcpyHostToDevice, sc.s));
+    sc.up(sc.gn_state, &st, 1);
     LIO_HIP(hipMemsetAsync(sc.gn_partials.p, 0, size_t(nb) * 28 * sizeof(double), sc.s));
+    sc.up(sc.b, stack, m); sc.up(sc.valid, valid, m); sc.up(sc.coef, coeff, m);
     if (m) {
-      LIO_HIP(hipMemcpyAsync(sc.b.p, stack, m * sizeof(float4), hipMemcpyHostToDevice, sc.s));
-      LIO_HIP(hipMemcpyAsync(sc.valid.p, valid, m, hipMemcpyHostToDevice, sc.s));
-      LIO_HIP(hipMemcpyAsync(sc.coef.p, coeff, m * sizeof(float4), hipMemcpyHostToDevice, sc.s));
       // what production launches (csrc/mapping.hip, csrc/kf_batch.hip): the rows kernel over a keyframe table, here one record of M slots
       // in odom_rows_blocks(M) blocks
       const KfDesc kd{0, 0, M, 0, nb, 0, {0.f, 0.f, 0.f}};
-      LIO_HIP(hipMemcpyAsync(sc.gn_kd.p, &kd, sizeof(kd), hipMemcpyHostToDevice, sc.s));
+      sc.up(sc.gn_kd, &kd, 1);
       launch_kf_rows(sc.gn_kd.p, sc.gn_state.p, 1, nb, sc.b.p, sc.valid.p, sc.coef.p, sc.gn_partials.p, form, sc.s);
       uint8_t *ok_dev = reinterpret_cast<uint8_t *>(sc.idx.p);
       launch_gn_rows_map(sc.b.p, M, sc.valid.p, sc.coef.p, sc.gn_state.p, form, ok_dev, sc.gn_rows.p, sc.s);
-      LIO_HIP(hipMemcpyAsync(ok_out, ok_dev, m, hipMemcpyDeviceToHost, sc.s));
-      LIO_HIP(hipMemcpyAsync(rows_out, sc.gn_rows.p, m * 7 * sizeof(float), hipMemcpyDeviceToHost, sc.s));
+      sc.down(ok_out, ok_dev, m); sc.down(rows_out, sc.gn_rows.p, m * 7);
     }
-    LIO_HIP(hipMemcpyAsync(partials_out, sc.gn_partials.p, size_t(nb) * 28 * sizeof(double), hipMemcpyDeviceToHost, sc.s));
-    LIO_HIP(hipStreamSynchronize(sc.s));
+    sc.down(partials_out, sc.gn_partials.p, size_t(nb) * 28);
+    sc.sync();
     *nb_out = nb;
     return LIO_OK;
   });
@@ -945,11 +941,10 @@ int lio_gn_fold(const double *partials, int nblocks, int wide, double *sums_out)
   if (nblocks > INT_MAX / 32) return LIO_ERR_CAPACITY;   // reduce_partials28 indexes b * 28 + c in int
   return guarded([&] {
     Scratch &sc = scratch();
-    sc.gn_partials.reserve(std::max<size_t>(size_t(nblocks) * 28, 1)); sc.gn_sums.reserve(28);
-    if (nblocks) LIO_HIP(hipMemcpyAsync(sc.gn_partials.p, partials, size_t(nblocks) * 28 * sizeof(double), hipMemcpyHostToDevice, sc.s));
+    sc.up(sc.gn_partials, partials, size_t(nblocks) * 28); sc.room(sc.gn_sums, 28);
     launch_gn_fold(sc.gn_partials.p, nblocks, wide, sc.gn_sums.p, sc.s);
-    LIO_HIP(hipMemcpyAsync(sums_out, sc.gn_sums.p, 28 * sizeof(double), hipMemcpyDeviceToHost, sc.s));
-    LIO_HIP(hipStreamSynchronize(sc.s));
+    sc.down(sums_out, sc.gn_sums.p, 28);
+    sc.sync();
     return LIO_OK;
   });
 }
@@ -960,13 +955,11 @@ int lio_gn_step(int family, const double *sums, const lio_gn_state *state_in, in
   for (int k = 0; k < 7; ++k) if (!std::isfinite(state_in->T[k])) return LIO_ERR_ARG;
   return guarded([&] {
     Scratch &sc = scratch();
-    sc.gn_sums.reserve(28); sc.gn_state.reserve(1);
-    LIO_HIP(hipMemcpyAsync(sc.gn_sums.p, sums, 28 * sizeof(double), hipMemcpyHostToDevice, sc.s));
-    LIO_HIP(hipMemcpyAsync(sc.gn_state.p, state_in, sizeof(OdomState), hipMemcpyHostToDevice, sc.s));
+    sc.up(sc.gn_sums, sums, 28); sc.up(sc.gn_state, state_in, 1);
     if (family == 0) launch_gn_step(sc.gn_sums.p, sc.gn_state.p, iter, min_rows, left_update ? 1 : 0, sc.s);
     else launch_gn_odo_step(sc.gn_sums.p, sc.gn_state.p, iter, sc.s);
-    LIO_HIP(hipMemcpyAsync(state_out, sc.gn_state.p, sizeof(OdomState), hipMemcpyDeviceToHost, sc.s));
-    LIO_HIP(hipStreamSynchronize(sc.s));
+    sc.down(state_out, sc.gn_state.p, 1);
+    sc.sync();
     return LIO_OK;
   });
 }
@@ -979,24 +972,15 @@ int lio_gn_round(const float *map, size_t n_map, const float *stack, size_t m, c
   return guarded([&] {
     Scratch &sc = scratch();
     const int M = int(m), nb = M > 0 ? odom_round_blocks(M, lpq) : 0;
-    sc.a.reserve(std::max<size_t>(n_map, 1)); sc.b.reserve(std::max<size_t>(m, 1));
-    sc.valid.reserve(std::max<size_t>(m, 1)); sc.coef.reserve(std::max<size_t>(m, 1)); sc.score.reserve(std::max<size_t>(m, 1));
-    sc.gn_partials.reserve(std::max<size_t>(size_t(nb) * 28, 1)); sc.gn_state.reserve(1);
-    if (n_map) LIO_HIP(hipMemcpyAsync(sc.a.p, map, n_map * sizeof(float4), hipMemcpyHostToDevice, sc.s));
-    if (m) LIO_HIP(hipMemcpyAsync(sc.b.p, stack, m * sizeof(float4), hipMemcpyHostToDevice, sc.s));
+    sc.up(sc.a, map, n_map); sc.up(sc.b, stack, m);
+    sc.room(sc.valid, m); sc.room(sc.coef, m); sc.room(sc.score, m); sc.room(sc.gn_partials, size_t(nb) * 28);
     const OdomState st = odom_state_at(toT(*T));
-    LIO_HIP(hipMemcpyAsync(sc.gn_state.p, &st, sizeof(st), hipMemcpyHostToDevice, sc.s));
-    float mn[3], mx[3];   // the grid of lio_calculate_features
-    host_cloud_bounds(map, n_map, mn, mx);
-    sc.grid.build(sc.a.p, n_map, mn, mx, knn_cell_edge(mm), sc.s);
-    FeatArgs fa{};
-    fa.nframes = 1; fa.max_M = M; fa.min_match_sq_dis = mm; fa.min_plane_dis = mp;
-    fa.fr[0].stack = sc.b.p; fa.fr[0].M = M; fa.fr[0].slot_off = 0; fa.fr[0].tf_index = 0;
-    launch_odom_round(fa, 0, 0, 0, sc.gn_state.p, sc.grid.sorted(), sc.grid.cells(), sc.grid.desc(), sc.valid.p, sc.coef.p, sc.score.p, sc.gn_partials.p, sc.s,
-                      nullptr, HostSignal(), lpq);
-    if (nb) LIO_HIP(hipMemcpyAsync(partials_out, sc.gn_partials.p, size_t(nb) * 28 * sizeof(double), hipMemcpyDeviceToHost, sc.s));
-    LIO_HIP(hipMemcpyAsync(state_out, sc.gn_state.p, sizeof(OdomState), hipMemcpyDeviceToHost, sc.s));
-    LIO_HIP(hipStreamSynchronize(sc.s));
+    sc.up(sc.gn_state, &st, 1);
+    sc.grid_over_a(map, n_map, knn_cell_edge(mm));   // the grid of lio_calculate_features
+    launch_odom_round(one_frame(sc.b.p, M, mm, mp), 0, 0, 0, sc.gn_state.p, sc.grid.sorted(), sc.grid.cells(), sc.grid.desc(), sc.valid.p, sc.coef.p, sc.score.p,
+                      sc.gn_partials.p, sc.s, nullptr, HostSignal(), lpq);
+    sc.down(partials_out, sc.gn_partials.p, size_t(nb) * 28); sc.down(state_out, sc.gn_state.p, 1);
+    sc.sync();
     *nb_out = nb;
     return LIO_OK;
   });
@@ -1007,25 +991,13 @@ int lio_calculate_features(const float *map, size_t n_map, const float *stack, s
   if ((!map && n_map) || (!stack && m) || !T || !valid || !coeff || !score || !(mm > 0)) return LIO_ERR_ARG;
   return guarded([&] {
     Scratch &sc = scratch();
-    sc.a.reserve(std::max<size_t>(n_map, 1)); sc.b.reserve(std::max<size_t>(m, 1));
-    sc.valid.reserve(std::max<size_t>(m, 1)); sc.coef.reserve(std::max<size_t>(m, 1)); sc.score.reserve(std::max<size_t>(m, 1)); sc.tf.reserve(8);
-    if (n_map) LIO_HIP(hipMemcpyAsync(sc.a.p, map, n_map * sizeof(float4), hipMemcpyHostToDevice, sc.s));
-    if (m) LIO_HIP(hipMemcpyAsync(sc.b.p, stack, m * sizeof(float4), hipMemcpyHostToDevice, sc.s));
-    float tf[8] = {T->q[0], T->q[1], T->q[2], T->q[3], T->p[0], T->p[1], T->p[2], 0.f};
-    LIO_HIP(hipMemcpyAsync(sc.tf.p, tf, sizeof(tf), hipMemcpyHostToDevice, sc.s));
-    float mn[3], mx[3];
-    host_cloud_bounds(map, n_map, mn, mx);
-    sc.grid.build(sc.a.p, n_map, mn, mx, knn_cell_edge(mm), sc.s);
-    FeatArgs fa{};
-    fa.nframes = 1; fa.max_M = int(m); fa.min_match_sq_dis = mm; fa.min_plane_dis = mp;
-    fa.fr[0].stack = sc.b.p; fa.fr[0].M = int(m); fa.fr[0].slot_off = 0; fa.fr[0].tf_index = 0;
-    launch_features(fa, sc.tf.p, sc.grid.sorted(), sc.grid.cells(), sc.grid.desc(), sc.valid.p, sc.coef.p, sc.score.p, nullptr, sc.s);
-    if (m) {
-      LIO_HIP(hipMemcpyAsync(valid, sc.valid.p, m, hipMemcpyDeviceToHost, sc.s));
-      LIO_HIP(hipMemcpyAsync(coeff, sc.coef.p, m * sizeof(float4), hipMemcpyDeviceToHost, sc.s));
-      LIO_HIP(hipMemcpyAsync(score, sc.score.p, m * sizeof(float), hipMemcpyDeviceToHost, sc.s));
-    }
-    LIO_HIP(hipStreamSynchronize(sc.s));
+    sc.up(sc.a, map, n_map); sc.up(sc.b, stack, m);
+    sc.room(sc.valid, m); sc.room(sc.coef, m); sc.room(sc.score, m);
+    sc.up_tf(*T);
+    sc.grid_over_a(map, n_map, knn_cell_edge(mm));
+    launch_features(one_frame(sc.b.p, int(m), mm, mp), sc.tf.p, sc.grid.sorted(), sc.grid.cells(), sc.grid.desc(), sc.valid.p, sc.coef.p, sc.score.p, nullptr, sc.s);
+    sc.down(valid, sc.valid.p, m); sc.down(coeff, sc.coef.p, m); sc.down(score, sc.score.p, m);
+    sc.sync();
     return LIO_OK;
   });
 }
@@ -1104,39 +1076,38 @@ void lio_est_default_config(lio_est_config *c) {
   c->acc_n = 0.1; c->gyr_n = 0.01; c->acc_w = 0.0002; c->gyr_w = 2.0e-5; c->g_norm = 9.805;
   c->max_num_iterations = 10; c->max_solver_time = 0.10; c->extrinsic_stage = 2; c->init_window_factor = 3;
 }
+static EstConfig to_est_config(const lio_est_config &c) {
+  EstConfig e;
+  e.W = c.window_size; e.Wo = c.opt_window_size;
+  e.corner_filter_size = c.corner_filter_size; e.surf_filter_size = c.surf_filter_size;
+  e.min_match_sq_dis = c.min_match_sq_dis; e.min_plane_dis = c.min_plane_dis;
+  e.transform_lb = toT(c.transform_lb);
+  e.opt_extrinsic = c.opt_extrinsic; e.imu_factor = c.imu_factor; e.point_distance_factor = c.point_distance_factor;
+  e.prior_factor = c.prior_factor; e.marginalization_factor = c.marginalization_factor;
+  e.enable_deskew = c.enable_deskew; e.cutoff_deskew = c.cutoff_deskew; e.keep_features = c.keep_features;
+  e.pim.acc_n = c.acc_n; e.pim.gyr_n = c.gyr_n; e.pim.acc_w = c.acc_w; e.pim.gyr_w = c.gyr_w; e.pim.g_norm = c.g_norm;
+  e.max_num_iterations = c.max_num_iterations; e.max_solver_time = c.max_solver_time; e.extrinsic_stage = c.extrinsic_stage;
+  e.init_window_factor = c.init_window_factor > 0 ? c.init_window_factor : 1;
+  e.device_solve = c.device_solve != 0; e.inline_marg = c.inline_marg != 0;
+  e.stream_sync = c.stream_sync != 0;
+  e.resident_moments = (c.resident_moments >= 1 && c.resident_moments <= 3) ? c.resident_moments : 0;
+  return e;
+}
 lio_est *lio_est_create(const lio_est_config *c) {
   if (!c || c->window_size < 1 || c->opt_window_size < 1 || c->opt_window_size > c->window_size || c->window_size + 1 > LIO_MAX_FRAMES) return nullptr;
-  lio_est *h = new (std::nothrow) lio_est;
-  if (!h) return nullptr;
-  EstConfig &e = h->cfg;
-  e.W = c->window_size; e.Wo = c->opt_window_size;
-  e.corner_filter_size = c->corner_filter_size; e.surf_filter_size = c->surf_filter_size;
-  e.min_match_sq_dis = c->min_match_sq_dis; e.min_plane_dis = c->min_plane_dis;
-  e.transform_lb = toT(c->transform_lb);
-  e.opt_extrinsic = c->opt_extrinsic; e.imu_factor = c->imu_factor; e.point_distance_factor = c->point_distance_factor;
-  e.prior_factor = c->prior_factor; e.marginalization_factor = c->marginalization_factor;
-  e.enable_deskew = c->enable_deskew; e.cutoff_deskew = c->cutoff_deskew; e.keep_features = c->keep_features;
-  e.pim.acc_n = c->acc_n; e.pim.gyr_n = c->gyr_n; e.pim.acc_w = c->acc_w; e.pim.gyr_w = c->gyr_w; e.pim.g_norm = c->g_norm;
-  e.max_num_iterations = c->max_num_iterations; e.max_solver_time = c->max_solver_time; e.extrinsic_stage = c->extrinsic_stage;
-  e.init_window_factor = c->init_window_factor > 0 ? c->init_window_factor : 1;
-  e.device_solve = c->device_solve != 0; e.inline_marg = c->inline_marg != 0;
-  e.stream_sync = c->stream_sync != 0;
-  e.resident_moments = (c->resident_moments >= 1 && c->resident_moments <= 3) ? c->resident_moments : 0;
-  // Estimator.cc:189-194: the estimator's filter sizes and thresholds configure its PointMapping base (created on first use)
-  h->map_cfg.corner_filter_size = c->corner_filter_size; h->map_cfg.surf_filter_size = c->surf_filter_size;
-  h->map_cfg.min_match_sq_dis = c->min_match_sq_dis; h->map_cfg.min_plane_dis = c->min_plane_dis; h->map_cfg.num_max_iterations = 10;
-  h->map_cfg.map_builder = 0; h->map_cfg.enable_4d = 1; h->map_cfg.skip_count = 2;
-  int rc = guarded([&] {
-    h->e.reset(new Estimator(e));
-    if (e.device_solve) {   // a batch of one window: the device loop and the device marginalization serve this handle's solves
-      h->solo.reset(new EstimatorBatch({h->e.get()}));
-      EstimatorBatch *b = h->solo.get();
-      h->e->solve_hook_ = [b](lio_solve_report *rep) { b->Solve(rep); return b->window_ok(0); };
+  return make_handle<lio_est>([&](lio_est &h) {
+    h.cfg = to_est_config(*c);
+    // Estimator.cc:189-194: the estimator's filter sizes and thresholds configure its PointMapping base (created on first use)
+    lio_map_default_config(&h.map_cfg);
+    h.map_cfg.corner_filter_size = c->corner_filter_size; h.map_cfg.surf_filter_size = c->surf_filter_size;
+    h.map_cfg.min_match_sq_dis = c->min_match_sq_dis; h.map_cfg.min_plane_dis = c->min_plane_dis;
+    h.e.reset(new Estimator(h.cfg));
+    if (h.cfg.device_solve) {   // a batch of one window: the device loop and the device marginalization serve this handle's solves
+      EstimatorBatch *b = new EstimatorBatch({h.e.get()});
+      h.solo.reset(b);
+      h.e->solve_hook_ = [b](lio_solve_report *rep) { b->Solve(rep); return b->window_ok(0); };
     }
-    return LIO_OK;
   });
-  if (rc != LIO_OK) { delete h; return nullptr; }
-  return h;
 }
 static void dissolve_batch(lio_est_batch *B);
 void lio_est_destroy(lio_est *h) {
@@ -1163,6 +1134,8 @@ int lio_est_process_laser_odom(lio_est *h, const lio_transform_f *T, const float
   if (!h || !T || (!surf && ns) || (!corner && nc)) return LIO_ERR_ARG;
   return guarded([&] { return h->e->ProcessLaserOdom(toT(*T), surf, ns, corner, nc, stamp, rep) ? LIO_OK : LIO_ERR_STATE; });
 }
+// int thread ids, one point per lane in workgroups of 256: the last workgroup's tail lanes must not pass INT_MAX
+static constexpr size_t kMaxCloudPoints = size_t(INT_MAX) - 255;
 // the estimator's PointMapping base, created on first use (Estimator.cc:189-194: configured from the estimator's own sizes)
 static MappingDev &est_map(lio_est *h) {
   if (!h->map.m) { h->map.m.reset(new MappingDev(h->map_cfg)); h->map.borrowed = true; }
@@ -1180,34 +1153,12 @@ int lio_est_process_compact(lio_est *h, const float *data, size_t n, double stam
   return guarded([&] {
     Estimator &e = *h->e;
     if (e.inited_ && !e.cfg_.imu_factor) return LIO_ERR_STATE;  // LOAM-only operation after init is not part of this path
-    MappingDev &m = est_map(h);
-    const float *corner = data + 4 * 3, *surf = data + 4 * (3 + nc);
-    if (e.full_cloud()) {
-      if (nf > size_t(INT_MAX) - 255) return LIO_ERR_CAPACITY;
-      m.SetFullCloud(data + 4 * (3 + nc + ns), nf);
-    }   // CompactDataHandler's third block (PointMapping.cc:212-224)
-    if (e.inited_) {  // :780-803: predict transform_tobe_mapped_ with the IMU-propagated body motion
-      const int W = e.W_;
-      auto bodyPose = [&](int i) {
-        // Quaterniond(R).cast<float>(): build the quaternion in double, then cast
-        const Quat<double> qd = fromRot(e.Rs_[i]);
-        return Rigidf(Quat<float>(float(qd.w), float(qd.x), float(qd.y), float(qd.z)), Vec3<float>(float(e.Ps_[i].x), float(e.Ps_[i].y), float(e.Ps_[i].z)));
-      };
-      const Rigidf d_trans = compose(rinverse(bodyPose(W - 1)), bodyPose(W));
-      m.transform_tobe_mapped_ = compose(compose(compose(m.transform_tobe_mapped_, e.transform_lb_), d_trans), rinverse(e.transform_lb_));
-      m.transform_sum_ = toT(Tsum);
-    } else {
-      m.Process(corner, nc, surf, ns, toT(Tsum));
-    }
-    const Rigidf T_to_init = m.transform_aft_mapped_;
+    est_map(h);
+    if (e.full_cloud() && nf > kMaxCloudPoints) return LIO_ERR_CAPACITY;
+    Rigidf T_to_init;
+    const bool ok = e.ProcessCompact(toT(Tsum), data + 4 * 3, nc, data + 4 * (3 + nc), ns, data + 4 * (3 + nc + ns), nf, stamp, &T_to_init, rep);
     if (T_out) fromT(T_to_init, T_out);
-    const bool was_inited = e.inited_;
-    const bool ok = was_inited ? e.ProcessLaserOdom(T_to_init, reinterpret_cast<const float4 *>(surf), ns, false, stamp, rep,
-                                                    reinterpret_cast<const float4 *>(corner), nc, false)
-                               : e.ProcessLaserOdom(T_to_init, m.StackDevice(1), m.StackSize(1), true, stamp, rep, m.StackDevice(0), m.StackSize(0), true);
-    if (!ok) return LIO_ERR_STATE;
-    if (!was_inited && e.inited_) m.imu_inited_ = true;  // SetInitFlag(true) (:545)
-    return LIO_OK;
+    return ok ? LIO_OK : LIO_ERR_STATE;
   });
 }
 // ---------------------------------------------------------------- include/lio_ext.h: the map refresh and the surround map
@@ -1227,9 +1178,7 @@ int lio_est_refresh_map(lio_est *h) {
 }
 size_t lio_map_get_surround(lio_map *h, float leaf, float *xyzi_or_null) {
   if (!h || !h->m || !(leaf > 0)) return 0;
-  size_t n = 0;
-  guarded([&] { n = h->m->GetSurround(leaf, xyzi_or_null); return LIO_OK; });
-  return n;
+  return guarded_count([&] { return h->m->GetSurround(leaf, xyzi_or_null); });
 }
 int lio_est_get_last_map_refresh(const lio_est *h, int *applied, lio_transform_f *T, int cube_center[3], uint32_t *valid_idx, int *n_valid,
                                  size_t *n_corner, float *corner_xyzi_or_null, size_t *n_surf, float *surf_xyzi_or_null) {
@@ -1254,8 +1203,6 @@ int lio_est_get_last_map_refresh(const lio_est *h, int *applied, lio_transform_f
   });
 }
 // ---------------------------------------------------------------- include/lio_full_cloud.h: the full-resolution sweep
-// int thread ids, one point per lane in workgroups of 256: the last workgroup's tail lanes must not pass INT_MAX
-static constexpr size_t kMaxCloudPoints = size_t(INT_MAX) - 255;
 // PointOdometry.cc:261-292 at :725-730
 int lio_odom_full_to_end(lio_odom *h, const float *xyzi, size_t n, float *xyzi_out) {
   if (!h || (n && (!xyzi || !xyzi_out))) return LIO_ERR_ARG;
@@ -1271,9 +1218,7 @@ int lio_map_set_full_cloud(lio_map *h, const float *xyzi, size_t n) {
 // PointMapping.cc:1244-1251
 size_t lio_map_get_full_cloud(const lio_map *h, float *xyzi_or_null) {
   if (!h || !h->m) return 0;
-  size_t n = 0;
-  guarded([&] { n = h->m->GetFullCloud(xyzi_or_null); return LIO_OK; });
-  return n;
+  return guarded_count([&] { return h->m->GetFullCloud(xyzi_or_null); });
 }
 // Estimator.cc:482, :2355-2420
 int lio_est_set_full_cloud(lio_est *h, int on) {
@@ -1316,11 +1261,10 @@ int lio_deskew_to_end(const float *xyzi, size_t n, const lio_transform_f *T_es, 
   if (!n) return LIO_OK;
   return guarded([&] {
     Scratch &sc = scratch();
-    sc.a.reserve(n);
-    LIO_HIP(hipMemcpyAsync(sc.a.p, xyzi, n * sizeof(float4), hipMemcpyHostToDevice, sc.s));
+    sc.up(sc.a, xyzi, n);
     launch_deskew_to_end(sc.a.p, int(n), T_es->q, T_es->p, time_factor, sc.s, keep_intensity != 0);
-    LIO_HIP(hipMemcpyAsync(xyzi_out, sc.a.p, n * sizeof(float4), hipMemcpyDeviceToHost, sc.s));
-    LIO_HIP(hipStreamSynchronize(sc.s));
+    sc.down(xyzi_out, sc.a.p, n);
+    sc.sync();
     return LIO_OK;
   });
 }
@@ -1382,9 +1326,7 @@ int lio_est_set_surf_stack(lio_est *h, int frame, const float *xyzi, size_t n) {
 }
 size_t lio_est_get_surf_stack(const lio_est *h, int frame, float *out) {
   if (!h || frame < 0 || frame > h->e->W_) return 0;
-  size_t n = 0;
-  guarded([&] { n = h->e->GetSurfStack(frame, out); return LIO_OK; });
-  return n;
+  return guarded_count([&] { return h->e->GetSurfStack(frame, out); });
 }
 int lio_est_set_preintegration(lio_est *h, int frame, const double acc0[3], const double gyr0[3], const double ba[3], const double bg[3],
                                const double *dt, const double *acc, const double *gyr, size_t ns) {
@@ -1406,15 +1348,11 @@ int lio_est_build_local_map(lio_est *h) {
 }
 size_t lio_est_get_local_map(const lio_est *h, float *out) {
   if (!h) return 0;
-  size_t n = 0;
-  guarded([&] { n = h->e->GetLocalMap(out); return LIO_OK; });
-  return n;
+  return guarded_count([&] { return h->e->GetLocalMap(out); });
 }
 size_t lio_est_get_features(const lio_est *h, int frame, double *pt, double *co, double *sc) {
   if (!h) return 0;
-  size_t n = 0;
-  guarded([&] { n = h->e->GetFeatures(frame, pt, co, sc); return LIO_OK; });
-  return n;
+  return guarded_count([&] { return h->e->GetFeatures(frame, pt, co, sc); });
 }
 int lio_est_eval_lidar_moments(lio_est *h, int n_passes, const double *Rt, double *out, int *path_out) {
   if (!h || n_passes < 1 || !Rt || !out) return LIO_ERR_ARG;
@@ -1442,50 +1380,21 @@ int lio_est_get_laser_odom_transform(const lio_est *h, lio_transform_f *out) {
   return LIO_OK;
 }
 int lio_est_get_prior(const lio_est *h, double *JtJ, double *Jtr, double *x0, int *x0_len) {
-  if (!h) return LIO_ERR_ARG;
-  return guarded([&] {
-    const_cast<lio_est *>(h)->e->JoinMarg();
-    const auto &pr = h->e->last_marg_;
-    if (!pr) return 0;
-    const int n = pr->n;
-    if (JtJ) std::memcpy(JtJ, pr->JtJ.a.data(), sizeof(double) * size_t(n) * n);
-    if (Jtr) std::memcpy(Jtr, pr->Jtr0.data(), sizeof(double) * n);
-    int len = 0;
-    for (const auto &b : pr->x0) { if (x0) for (double v : b) x0[len++] = v; else len += int(b.size()); }
-    if (x0_len) *x0_len = len;
-    return n;
-  });
+  return est_get_prior(h, [](MargPrior &p) { return p.JtJ.a.data(); }, [](MargPrior &p) { return p.Jtr0.data(); }, JtJ, Jtr, x0, x0_len);
 }
 int lio_est_get_prior_factor(const lio_est *h, double *lin_jac, double *lin_res, double *x0, int *x0_len) {
-  if (!h) return LIO_ERR_ARG;
-  // JoinMarg rethrows a failed worker task: nothing may unwind through the C boundary
-  return guarded([&] {
-    const_cast<lio_est *>(h)->e->JoinMarg();
-    const auto &pr = h->e->last_marg_;
-    if (!pr) return 0;
-    const int n = pr->n;
-    if (lin_jac) std::memcpy(lin_jac, pr->lin_jac.a.data(), sizeof(double) * size_t(n) * n);
-    if (lin_res) std::memcpy(lin_res, pr->lin_res.data(), sizeof(double) * n);
-    int len = 0;
-    for (const auto &b : pr->x0) { if (x0) for (double v : b) x0[len++] = v; else len += int(b.size()); }
-    if (x0_len) *x0_len = len;
-    return n;
-  });
+  return est_get_prior(h, [](MargPrior &p) { return p.lin_jac.a.data(); }, [](MargPrior &p) { return p.lin_res.data(); }, lin_jac, lin_res, x0, x0_len);
 }
 int lio_est_set_prior_factor(lio_est *h, int n, const double *lin_jac, const double *lin_res, const double *x0, int x0_len) {
   if (!h || !lin_jac || !lin_res || !x0 || n <= 0) return LIO_ERR_ARG;
   return guarded([&] {
     h->e->JoinMarg();
     const auto &old = h->e->last_marg_;
-    if (!old || old->n != n) return LIO_ERR_STATE;
-    int len = 0;
-    for (const auto &b : old->x0) len += int(b.size());
-    if (len != x0_len) return LIO_ERR_STATE;
+    if (!old || old->n != n || prior_x0(*old, nullptr) != x0_len) return LIO_ERR_STATE;
     auto pr = std::make_shared<MargPrior>(*old);   // the old object may still be referenced by a snapshot
     std::memcpy(pr->lin_jac.a.data(), lin_jac, sizeof(double) * size_t(n) * n);
     std::memcpy(pr->lin_res.data(), lin_res, sizeof(double) * n);
-    len = 0;
-    for (auto &b : pr->x0) for (double &v : b) v = x0[len++];
+    prior_x0(*pr, nullptr, x0);
     pr->finalize();
     h->e->last_marg_ = pr;
     return LIO_OK;
@@ -1541,46 +1450,22 @@ int lio_est_solve_restored(lio_est *h, int steps, lio_solve_report *rep) {
 }
 
 // ---------------------------------------------------------------- batched windows
-// (re)builds the batch's EstimatorBatch objects for its partition and re-applies the options set so far
-static void batch_build_parts(lio_est_batch *h) {
-  h->b.reset(); h->b2.reset();   // (a part's destructor brings its device-resident priors back to the host objects)
-  const int n = int(h->members.size());
-  const int want = h->parts_opt ? h->parts_opt : (n >= kBatchSplitFrom ? 2 : 1);
-  const int parts = (want == 2 && n >= 2) ? 2 : 1;
-  h->n1 = parts == 2 ? (n + 1) / 2 : n;
-  std::vector<Estimator *> es;
-  for (int i = 0; i < h->n1; ++i) es.push_back(h->members[size_t(i)]->e.get());
-  h->b.reset(new EstimatorBatch(es));
-  if (parts == 2) {
-    es.clear();
-    for (int i = h->n1; i < n; ++i) es.push_back(h->members[size_t(i)]->e.get());
-    h->b2.reset(new EstimatorBatch(es));
-  }
-  bool groups_set = false;
-  for (const auto &o : h->options) {
-    if (o.first == "loop_groups" && o.second != 0) groups_set = true;
-    h->b->SetOption(o.first.c_str(), o.second);
-    if (h->b2) h->b2->SetOption(o.first.c_str(), o.second);
-  }
-  // two parts side by side are two launch chains already: one loop group each unless the caller asked for a number
-  if (h->b2 && !groups_set) { h->b->SetOption("loop_groups", 1); h->b2->SetOption("loop_groups", 1); }
-}
+static bool batch_live(const lio_est_batch *h) { return h->parts && h->parts->built(); }
 lio_est_batch *lio_est_batch_create(lio_est *const *windows, int n) {
   if (!windows || n < 1 || n > 65535) return nullptr;
-  for (int i = 0; i < n; ++i) {
+  for (int i = 0; i < n; ++i)
     if (!windows[i] || windows[i]->adopted || windows[i]->solo) return nullptr;
-    for (int j = 0; j < i; ++j) if (windows[j] == windows[i]) return nullptr;
-  }
-  lio_est_batch *h = new (std::nothrow) lio_est_batch;
-  if (!h) return nullptr;
-  for (int i = 0; i < n; ++i) h->members.push_back(windows[i]);
-  int rc = guarded([&] { batch_build_parts(h); return LIO_OK; });
-  if (rc != LIO_OK) { (void)guarded([&] { h->b.reset(); h->b2.reset(); return LIO_OK; }); delete h; return nullptr; }
-  for (int i = 0; i < n; ++i) { windows[i]->adopted = true; windows[i]->owner = h; }
+  if (!distinct(windows, size_t(n))) return nullptr;
+  lio_est_batch *h = make_handle<lio_est_batch>([&](lio_est_batch &b) {
+    std::vector<Estimator *> es;
+    for (int i = 0; i < n; ++i) { b.members.push_back(windows[i]); es.push_back(windows[i]->e.get()); }
+    b.parts.reset(new BatchParts(es));
+  });
+  for (int i = 0; h && i < n; ++i) { windows[i]->adopted = true; windows[i]->owner = h; }
   return h;
 }
 static void dissolve_batch(lio_est_batch *B) {
-  (void)guarded([&] { B->b.reset(); B->b2.reset(); return LIO_OK; });
+  (void)guarded([&] { B->parts.reset(); return LIO_OK; });
   for (lio_est *m : B->members) { m->adopted = false; m->owner = nullptr; }
   B->members.clear();
 }
@@ -1589,51 +1474,27 @@ void lio_est_batch_destroy(lio_est_batch *h) {
   dissolve_batch(h);
   delete h;
 }
-int lio_est_batch_size(const lio_est_batch *h) { return (h && h->b) ? h->b->size() + (h->b2 ? h->b2->size() : 0) : 0; }
+int lio_est_batch_size(const lio_est_batch *h) { return (h && batch_live(h)) ? h->parts->size() : 0; }
 int lio_est_batch_solve(lio_est_batch *h, lio_solve_report *reps) {
   if (!h) return LIO_ERR_ARG;
-  if (!h->b) return LIO_ERR_STATE;
+  if (!batch_live(h)) return LIO_ERR_STATE;
   for (lio_est *m : h->members) if (!m->e->inited_) return LIO_ERR_STATE;
-  return guarded([&] { batch_for_parts(h, [&](EstimatorBatch &b, int w0) { b.Solve(reps ? reps + w0 : nullptr); }); return LIO_OK; });
+  return guarded([&] { h->parts->Solve(reps); return LIO_OK; });
 }
 int lio_est_batch_set_option(lio_est_batch *h, const char *name, int value) {
   if (!h || !name) return LIO_ERR_ARG;
-  if (!h->b) return LIO_ERR_STATE;
-  if (std::string(name) == "parts") {   // the partition: 0 by size (two parts from kBatchSplitFrom windows), 1, 2
-    if (value < 0 || value > 2) return LIO_ERR_ARG;
-    if (value == h->parts_opt) return LIO_OK;
-    h->parts_opt = value;
-    return guarded([&] { batch_build_parts(h); return LIO_OK; });
-  }
-  if (!h->b->SetOption(name, value)) return LIO_ERR_ARG;
-  if (h->b2) h->b2->SetOption(name, value);
-  bool found = false;
-  for (auto &o : h->options) if (o.first == name) { o.second = value; found = true; }
-  if (!found) h->options.emplace_back(name, value);
-  if (h->b2 && std::string(name) == "loop_groups" && value == 0) { h->b->SetOption("loop_groups", 1); h->b2->SetOption("loop_groups", 1); }
-  return LIO_OK;
+  if (!batch_live(h)) return LIO_ERR_STATE;
+  return guarded([&] { return h->parts->SetOption(name, value) ? LIO_OK : LIO_ERR_ARG; });
 }
 int lio_est_batch_solve_restored(lio_est_batch *h, int steps, lio_solve_report *reps) {
   if (!h || steps < 0) return LIO_ERR_ARG;
-  if (!h->b) return LIO_ERR_STATE;
-  return guarded([&] {
-    std::atomic<int> bad{0};
-    batch_for_parts(h, [&](EstimatorBatch &b, int w0) {   // (every part loops on its own: nothing ties the parts' steps together)
-      const int w1 = w0 + b.size();
-      for (int k = 0; k < steps && !bad.load(); ++k) {
-        for (int w = w0; w < w1; ++w) if (!h->members[size_t(w)]->e->Restore()) { bad.store(1); return; }
-        for (int w = w0; w < w1; ++w) if (!h->members[size_t(w)]->e->inited_) { bad.store(1); return; }
-        b.Solve(reps ? reps + w0 : nullptr);
-      }
-      b.Sync();
-    });
-    return bad.load() ? int(LIO_ERR_STATE) : int(LIO_OK);
-  });
+  if (!batch_live(h)) return LIO_ERR_STATE;
+  return guarded([&] { return h->parts->SolveRestored(steps, reps) ? LIO_OK : LIO_ERR_STATE; });
 }
 int lio_est_batch_sync(lio_est_batch *h) {
   if (!h) return LIO_ERR_ARG;
-  if (!h->b) return LIO_ERR_STATE;
-  return guarded([&] { h->b->Sync(); if (h->b2) h->b2->Sync(); return LIO_OK; });
+  if (!batch_live(h)) return LIO_ERR_STATE;
+  return guarded([&] { h->parts->Sync(); return LIO_OK; });
 }
 int lio_seg_sort_pairs(const unsigned *keys, const unsigned *vals, size_t n_total, const int *seg_off, const int *seg_n, int nseg, int bits, int passes, unsigned *keys_out,
                        unsigned *vals_out) {
@@ -1641,47 +1502,26 @@ int lio_seg_sort_pairs(const unsigned *keys, const unsigned *vals, size_t n_tota
 }
 int lio_est_batch_stage_digest(lio_est_batch *h, int stage, unsigned long long *out) {
   if (!h || !out || stage < 0 || stage > 9) return LIO_ERR_ARG;
-  if (!h->b) return LIO_ERR_STATE;
-  return guarded([&] { h->b->StageDigest(stage, out); if (h->b2) h->b2->StageDigest(stage, out + h->n1); return LIO_OK; });
+  if (!batch_live(h)) return LIO_ERR_STATE;
+  return guarded([&] { h->parts->StageDigest(stage, out); return LIO_OK; });
 }
 int lio_est_batch_get_moments(lio_est_batch *h, int window, double *out, double *Rt) {
   if (!h || !out || !Rt || window < 0) return LIO_ERR_ARG;
-  if (!h->b) return LIO_ERR_STATE;
-  if (window >= int(h->members.size())) return LIO_ERR_ARG;
-  return guarded([&] {
-    const bool ok = window < h->n1 ? h->b->GetMoments(window, out, Rt) : h->b2->GetMoments(window - h->n1, out, Rt);
-    return ok ? int(LIO_OK) : int(LIO_ERR_STATE);
-  });
+  if (!batch_live(h)) return LIO_ERR_STATE;
+  if (window >= h->parts->size()) return LIO_ERR_ARG;
+  return guarded([&] { return h->parts->GetMoments(window, out, Rt) ? LIO_OK : LIO_ERR_STATE; });
 }
 int lio_est_batch_get_linearization(lio_est_batch *h, int window, int32_t *ints, double *problem, double *state, double *aux) {
   if (!h || !ints || !problem || !state || !aux || window < 0) return LIO_ERR_ARG;
-  if (!h->b) return LIO_ERR_STATE;
-  if (window >= int(h->members.size())) return LIO_ERR_ARG;
-  return guarded([&] {
-    const bool ok = window < h->n1 ? h->b->GetLinearization(window, ints, problem, state, aux) : h->b2->GetLinearization(window - h->n1, ints, problem, state, aux);
-    return ok ? int(LIO_OK) : int(LIO_ERR_STATE);
-  });
+  if (!batch_live(h)) return LIO_ERR_STATE;
+  if (window >= h->parts->size()) return LIO_ERR_ARG;
+  return guarded([&] { return h->parts->GetLinearization(window, ints, problem, state, aux) ? LIO_OK : LIO_ERR_STATE; });
 }
 int lio_est_batch_get_clock(const lio_est_batch *h, double *out) {
   if (!h || !out) return LIO_ERR_ARG;
-  if (!h->b) return LIO_ERR_STATE;
+  if (!batch_live(h)) return LIO_ERR_STATE;
   BatchClock c;
-  const int rc = guarded([&] {
-    c = const_cast<lio_est_batch *>(h)->b->clock();
-    if (h->b2) {
-      // two parts: host phases ran side by side (the longer one counts); device times, counts and launches add up — the parts' stages
-      // overlap on the GPU, so the summed device times exceed the wall time and every rate derived from them is a lower bound
-      const BatchClock d = const_cast<lio_est_batch *>(h)->b2->clock();
-      c.describe = std::max(c.describe, d.describe); c.map = std::max(c.map, d.map); c.grid_features = std::max(c.grid_features, d.grid_features);
-      c.pack = std::max(c.pack, d.pack); c.solve = std::max(c.solve, d.solve); c.finish = std::max(c.finish, d.finish);
-      c.fallback = std::max(c.fallback, d.fallback); c.total = std::max(c.total, d.total);
-      c.n_device += d.n_device; c.n_host += d.n_host; c.rounds = std::max(c.rounds, d.rounds);
-      for (int k = 0; k < 6; ++k) c.dev[k] += d.dev[k];
-      c.dev_marg_wait += d.dev_marg_wait;
-      for (int k = 0; k < 3; ++k) { c.kernel_ms[k] += d.kernel_ms[k]; c.kernel_launches[k] += d.kernel_launches[k]; }
-    }
-    return LIO_OK;
-  });
+  const int rc = guarded([&] { c = h->parts->clock(); return LIO_OK; });
   if (rc != LIO_OK) return rc;
   for (int k = 0; k < 6; ++k) out[10 + k] = c.dev[k];
   out[0] = c.describe; out[1] = c.map; out[2] = c.grid_features; out[3] = c.pack; out[4] = c.solve; out[5] = c.finish; out[6] = c.fallback; out[7] = c.total;

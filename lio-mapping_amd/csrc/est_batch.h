@@ -19,8 +19,13 @@
 // lio_est_config.device_solve selects for a single handle) and inside any batch.  Windows whose problem the device loop does not
 // take (not initialised yet, the convergence_flag_ logic changing the problem's shape, factor sharding) are solved by the
 // single-window path inside the same call.
+//
+// What the C ABI calls a batch (lio_est_batch) is a BatchParts, below: one EstimatorBatch, or two solved side by side.  The partition
+// (the split rule, re-partitioning, the windows' addressing across the parts, the merged clock) lives there and nowhere else.
 #pragma once
 #include <memory>
+#include <string>
+#include <utility>
 #include <vector>
 
 #include "batch_kernels.h"
@@ -69,6 +74,7 @@ class EstimatorBatch {
   // window's own slot offsets behind these pointers.  Waits for the batch.
   void FeatureSlots(int w, const uint8_t **valid, const float4 **coef, const float **score);
   hipStream_t stream() const { return stream_; }
+  int device() const { return device_id_; }
   // execution choices (batch_kernels.h: BatchKnobs) by name: lanes_per_query, loop_groups, aux_threads, finish_threads, time_kernels;
   // false: unknown name or a value the knob does not take
   bool SetOption(const char *name, int value);
@@ -132,6 +138,41 @@ class EstimatorBatch {
   DBuf<int> tile_heads_, range_overflow_, cells_all_, nconv_;
   DBuf<VoxParams> vparams_;
   DBuf<uint8_t> valid_all_;
+};
+
+// A batch of at least kBatchSplitFrom windows is TWO EstimatorBatch objects (the first and the second half of the windows) solved side by
+// side from two host threads: one part's host phases (describe, pack, write-back), syncs and latency-bound stages fill with the other
+// part's kernels (tools/batches_in_flight.py: 2 x 256 windows 20.1 k solves/s against 19.0 k for 1 x 512, 2 x 64 17.4 k against 16.1 k).
+// Every window's results are those of the window alone whatever the partition (the batch's contract), so the split is an execution
+// choice like the others: the option "parts" (0: by size, 1, 2).  Windows are addressed by their index in the whole batch.
+class BatchParts {
+ public:
+  static constexpr int kBatchSplitFrom = 96;   // measured (profiles/r6_n_batch_parts.txt): 16 .. 64 windows within noise, 96: + 4 %, 128 .. 512: + 7-8 %
+  explicit BatchParts(const std::vector<Estimator *> &windows) : e_(windows) { Build(); }
+  bool built() const { return bool(b_[0]); }   // false: a re-partition failed and left no parts
+  int size() const { return int(e_.size()); }
+  // "parts" re-partitions (the options set so far are applied to the new parts); every other name is EstimatorBatch::SetOption on every part
+  bool SetOption(const char *name, int value);
+  void Solve(lio_solve_report *reps);   // reps: size() reports, or null
+  // `steps` times: Restore() every window, Solve; then Sync.  Every part loops on its own: nothing ties the parts' steps together.  false: a
+  // window had no snapshot or is not initialised (both parts stop).
+  bool SolveRestored(int steps, lio_solve_report *reps);
+  void Sync();
+  void StageDigest(int stage, unsigned long long *out);   // out: size() digests
+  bool GetMoments(int w, double *out, double *Rt) { return part(w).GetMoments(w, out, Rt); }
+  bool GetLinearization(int w, int32_t *ints, double *problem, double *state, double *aux) { return part(w).GetLinearization(w, ints, problem, state, aux); }
+  // two parts: host phases ran side by side (the longer one counts); device times, counts and launches add up — the parts' stages
+  // overlap on the GPU, so the summed device times exceed the wall time and every rate derived from them is a lower bound
+  BatchClock clock();
+ private:
+  void Build(), ApplyOptions();   // Build: (re)builds the parts for the partition in force and applies the options set so far
+  EstimatorBatch &part(int &w) { if (w < n1_) return *b_[0]; w -= n1_; return *b_[1]; }   // the part that holds window w; w becomes its index there
+  template <typename F> void ForParts(F &&f);   // f(part, first window of the part) on every part — two parts on two host threads
+  std::vector<Estimator *> e_;
+  std::unique_ptr<EstimatorBatch> b_[2];   // b_[1]: the second part (null: one part)
+  int n1_ = 0;                             // windows of b_[0]
+  int parts_opt_ = 0;                      // 0: by size, 1, 2
+  std::vector<std::pair<std::string, int>> options_;   // what SetOption has set, applied again when the partition changes
 };
 
 }  // namespace lio

@@ -3,6 +3,8 @@
 #include "est_batch.h"
 #include "../../include/lio_test_hooks.h"
 
+#include <algorithm>
+#include <atomic>
 #include <exception>
 #include <string>
 #include <thread>
@@ -727,6 +729,83 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
     R.ms_total = t5 - t0;
   }
   return B;
+}
+
+// ---------------------------------------------------------------- the partition
+void BatchParts::Build() {
+  b_[0].reset(); b_[1].reset();   // (a part's destructor brings its device-resident priors back to the host objects)
+  const int n = size();
+  const int want = parts_opt_ ? parts_opt_ : (n >= kBatchSplitFrom ? 2 : 1);
+  n1_ = (want == 2 && n >= 2) ? (n + 1) / 2 : n;
+  std::unique_ptr<EstimatorBatch> first(new EstimatorBatch(std::vector<Estimator *>(e_.begin(), e_.begin() + n1_)));
+  if (n1_ < n) b_[1].reset(new EstimatorBatch(std::vector<Estimator *>(e_.begin() + n1_, e_.end())));
+  b_[0] = std::move(first);   // (built() only once every part stands)
+  ApplyOptions();
+}
+void BatchParts::ApplyOptions() {
+  bool groups_set = false;
+  for (const auto &o : options_) {
+    if (o.first == "loop_groups" && o.second != 0) groups_set = true;
+    for (auto &b : b_) if (b) b->SetOption(o.first.c_str(), o.second);
+  }
+  // two parts side by side are two launch chains already: one loop group each unless the caller asked for a number
+  if (b_[1] && !groups_set) for (auto &b : b_) b->SetOption("loop_groups", 1);
+}
+bool BatchParts::SetOption(const char *name, int value) {
+  if (!name) return false;
+  if (std::string(name) == "parts") {
+    if (value < 0 || value > 2) return false;
+    if (value != parts_opt_) { parts_opt_ = value; Build(); }
+    return true;
+  }
+  if (!b_[0]->SetOption(name, value)) return false;
+  bool found = false;
+  for (auto &o : options_) if (o.first == name) { o.second = value; found = true; }
+  if (!found) options_.emplace_back(name, value);
+  ApplyOptions();
+  return true;
+}
+template <typename F> void BatchParts::ForParts(F &&f) {
+  if (!b_[1]) { f(*b_[0], 0); return; }
+  std::exception_ptr err1, err2;   // the first part's is rethrown in preference to the second's
+  std::thread t2([&] {   // (the current device is per thread)
+    try { LIO_HIP(hipSetDevice(b_[1]->device())); f(*b_[1], n1_); } catch (...) { err2 = std::current_exception(); }
+  });
+  try { f(*b_[0], 0); } catch (...) { err1 = std::current_exception(); }
+  t2.join();
+  if (err1 || err2) std::rethrow_exception(err1 ? err1 : err2);
+}
+void BatchParts::Solve(lio_solve_report *reps) { ForParts([&](EstimatorBatch &b, int w0) { b.Solve(reps ? reps + w0 : nullptr); }); }
+bool BatchParts::SolveRestored(int steps, lio_solve_report *reps) {
+  std::atomic<int> bad{0};
+  ForParts([&](EstimatorBatch &b, int w0) {
+    const int w1 = w0 + b.size();
+    for (int k = 0; k < steps && !bad.load(); ++k) {
+      for (int w = w0; w < w1; ++w) if (!e_[size_t(w)]->Restore()) { bad.store(1); return; }
+      for (int w = w0; w < w1; ++w) if (!e_[size_t(w)]->inited_) { bad.store(1); return; }
+      b.Solve(reps ? reps + w0 : nullptr);
+    }
+    b.Sync();
+  });
+  return !bad.load();
+}
+void BatchParts::Sync() { for (auto &b : b_) if (b) b->Sync(); }
+void BatchParts::StageDigest(int stage, unsigned long long *out) {
+  b_[0]->StageDigest(stage, out);
+  if (b_[1]) b_[1]->StageDigest(stage, out + n1_);
+}
+BatchClock BatchParts::clock() {
+  BatchClock c = b_[0]->clock();
+  if (!b_[1]) return c;
+  const BatchClock d = b_[1]->clock();
+  c.describe = std::max(c.describe, d.describe); c.map = std::max(c.map, d.map); c.grid_features = std::max(c.grid_features, d.grid_features);
+  c.pack = std::max(c.pack, d.pack); c.solve = std::max(c.solve, d.solve); c.finish = std::max(c.finish, d.finish);
+  c.fallback = std::max(c.fallback, d.fallback); c.total = std::max(c.total, d.total);
+  c.n_device += d.n_device; c.n_host += d.n_host; c.rounds = std::max(c.rounds, d.rounds);
+  for (int k = 0; k < 6; ++k) c.dev[k] += d.dev[k];
+  c.dev_marg_wait += d.dev_marg_wait;
+  for (int k = 0; k < 3; ++k) { c.kernel_ms[k] += d.kernel_ms[k]; c.kernel_launches[k] += d.kernel_launches[k]; }
+  return c;
 }
 
 }  // namespace lio

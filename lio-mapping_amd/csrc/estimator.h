@@ -208,6 +208,11 @@ class Estimator {
   // corner: read only while the map refresh is on (PushFrame)
   bool ProcessLaserOdom(const Rigidf &transform_in, const float4 *surf, size_t n_surf, bool surf_on_device, double stamp, lio_solve_report *rep,
                         const float4 *corner = nullptr, size_t n_corner = 0, bool corner_on_device = false);
+  // ProcessCompactData (Estimator.cc:776-856) on the decoded blocks of a /compact_data message, map_ being the PointMapping base: before
+  // initialisation the scan-to-map step and its stacks, afterwards the pose predicted from the IMU-propagated body motion, go into
+  // ProcessLaserOdom.  *T_to_init: the pose that went in.  false: ProcessLaserOdom refused.
+  bool ProcessCompact(const Rigidf &transform_sum, const float *corner, size_t nc, const float *surf, size_t ns, const float *full, size_t nf, double stamp,
+                      Rigidf *T_to_init, lio_solve_report *rep);
   bool PushFrame(const Rigidf &transform_in, const float *surf, size_t n_surf, const float *corner, size_t n_corner, double stamp,
                  bool surf_on_device = false, bool corner_on_device = false);
   // ---- the map-database refresh (Estimator.cc:703-708), off unless SetMapRefresh(true, map): PushFrame then keeps the optimisation-window

@@ -273,6 +273,32 @@ bool Estimator::ProcessLaserOdom(const Rigidf &transform_in, const float *surf, 
                           false);
 }
 
+// Estimator.cc:776-856
+bool Estimator::ProcessCompact(const Rigidf &transform_sum, const float *corner, size_t nc, const float *surf, size_t ns, const float *full, size_t nf,
+                               double stamp, Rigidf *T_to_init, lio_solve_report *rep) {
+  MappingDev &m = *map_;
+  if (full_cloud_) m.SetFullCloud(full, nf);   // CompactDataHandler's third block (PointMapping.cc:212-224)
+  if (inited_) {  // :780-803: predict transform_tobe_mapped_ with the IMU-propagated body motion
+    auto bodyPose = [&](int i) {
+      // Quaterniond(R).cast<float>(): build the quaternion in double, then cast
+      const Quat<double> qd = fromRot(Rs_[i]);
+      return Rigidf(Quat<float>(float(qd.w), float(qd.x), float(qd.y), float(qd.z)), Vec3<float>(float(Ps_[i].x), float(Ps_[i].y), float(Ps_[i].z)));
+    };
+    const Rigidf d_trans = compose(rinverse(bodyPose(W_ - 1)), bodyPose(W_));
+    m.transform_tobe_mapped_ = compose(compose(compose(m.transform_tobe_mapped_, transform_lb_), d_trans), rinverse(transform_lb_));
+    m.transform_sum_ = transform_sum;
+  } else {
+    m.Process(corner, nc, surf, ns, transform_sum);
+  }
+  *T_to_init = m.transform_aft_mapped_;
+  const bool was_inited = inited_;
+  const bool ok = was_inited ? ProcessLaserOdom(*T_to_init, reinterpret_cast<const float4 *>(surf), ns, false, stamp, rep,
+                                                reinterpret_cast<const float4 *>(corner), nc, false)
+                             : ProcessLaserOdom(*T_to_init, m.StackDevice(1), m.StackSize(1), true, stamp, rep, m.StackDevice(0), m.StackSize(0), true);
+  if (ok && !was_inited && inited_) m.imu_inited_ = true;  // SetInitFlag(true) (:545)
+  return ok;
+}
+
 // Estimator.cc:430-774
 bool Estimator::ProcessLaserOdom(const Rigidf &transform_in, const float4 *surf, size_t n_surf, bool surf_on_device, double stamp,
                                  lio_solve_report *rep, const float4 *corner, size_t n_corner, bool corner_on_device) {

@@ -5,7 +5,8 @@ the oracle, which equals the reference's own PointProcessor.cc on them (tests/go
 Exactly equal: ring offsets, ring cloud coordinates, the three (ring, index) lists, the pick clouds' coordinates, curvature, mask, the
 less-flat count and coordinates.  Intensities carry a relative time that goes through atan2f: within the 8e-6 that
 tests/test_gpu_parity.py allows, with its seam rule and nothing wider.  Then the same sweeps through lio_pp_process_rings_batch (LDS
-sized by the batch's longest ring), through one reused handle, and the two capacity limits as LIO_ERR_CAPACITY."""
+sized by the batch's longest ring), through one reused handle, the two capacity limits as LIO_ERR_CAPACITY, and a shared batch that fails
+in front of its chain, which serves nothing to any of its handles."""
 import numpy as np
 import pytest
 
@@ -116,3 +117,29 @@ def test_over_capacity_through_wait_and_batch(hip):
     capi.PointProcessor.process_rings_batch(pps, [c[3] for c in sweeps], [c[4] for c in sweeps])
     for p in pps:
         assert_same_results(results(p), single(hip, sub_limit))
+
+
+def test_failed_batch_serves_nothing_to_any_handle(hip):
+    """a shared batch that fails in front of its chain — the second handle's own lio_pp_process_async sweep ended over the ring capacity, which
+    the batch meets when it waits for that sweep — leaves EVERY handle of the call with nothing to serve (include/lio_c.h), the first one
+    included, whose place in the shared storage still holds the batch before; the next batch then serves each handle its own sweep"""
+    (ring_case, _), _ = over_capacity_sweeps()
+    names = ["gaps", "tiny_ns8", "gaps", "tiny_ns8"]
+    cs = [case(n) for n in names]
+    assert all(c[1] == ring_case[1] and c[2] == ring_case[2] == {} for c in cs)   # one sensor: one shared chain
+    pps = [make_pp(hip, c[1], c[2]) for c in cs]
+    batch = lambda: capi.PointProcessor.process_rings_batch(pps, [c[3] for c in cs], [c[4] for c in cs])
+    batch()
+    assert all(int(hip.dll.lio_pp_count(p.h, 0)) > 0 for p in pps)      # served from the shared storage
+    pps[1].process_async(ring_case[3])                                   # the 4081-point arc: flagged by the kernel, left unfinished
+    with pytest.raises(capi.LioError, match="code -4"):
+        batch()
+    offs = np.ones(ring_case[1] + 1, np.int32)
+    for p in pps:
+        assert [int(hip.dll.lio_pp_count(p.h, w)) for w in range(5)] == [0] * 5
+        offs[:] = 1
+        rc = hip.dll.lio_pp_get_ring_offsets(p.h, offs.ctypes.data_as(capi.c_int32_p))
+        assert rc == -2 or (rc == 0 and not offs.any())                   # LIO_ERR_STATE, or all zeros
+    batch()
+    for p, n in zip(pps, names):
+        assert_same_results(results(p), single(hip, n))
