@@ -38,15 +38,8 @@ __global__ void __launch_bounds__(BW_THREADS) k_bw_concat_keys(const BatchWin *_
     const BwSeg &sg = W.seg[sidx];
     const float4 p = rebase(local_all, sg.src)[gid - sg.dst_off];
     float4 o;
-    if (sg.identity) {
-      o = p;
-    } else {
-      const float *m = sg.tf.m;
-      o.x = m[0] * p.x + m[1] * p.y + m[2] * p.z + m[3];
-      o.y = m[4] * p.x + m[5] * p.y + m[6] * p.z + m[7];
-      o.z = m[8] * p.x + m[9] * p.y + m[10] * p.z + m[11];
-      o.w = p.w;
-    }
+    if (sg.identity) o = p;
+    else o = affine_map_point(sg.tf.m, p);
     if (sg.set_intensity) o.w = sg.intensity;
     local_all[W.loc_off + gid] = o;
     if (finite3(o)) {
@@ -71,11 +64,7 @@ __global__ void __launch_bounds__(BW_THREADS) k_bw_key_layout(const BatchWin *__
   params[w] = v;
   KeyLayout L{0, 0, 0, 0, 0, 0};
   if (v.n_valid > 0 && !range_overflow[w]) {
-    // floor(x inv_leaf) is monotone in x: the smallest stored cell coordinate of the window is the bound's
-    L.mx = v.minb[0] + 1024; L.my = v.minb[1] + 1024; L.mz = v.minb[2] + 256;
-    const int bx = bits_for(v.divb[0]), by = bits_for(v.divb[1]), bz = bits_for(v.divb[2]);
-    L.bx = bx; L.by = bx + by; L.bits = bx + by + bz;
-    if (L.bits > max_bits) range_overflow[w] = 1;   // the launch's passes order max_bits + 1 bits ("no point" sits one above the real keys): single-window path
+    if (!vox_key_layout(v.minb, v.divb, max_bits, L)) range_overflow[w] = 1;   // the launch's passes order max_bits + 1 bits: single-window path
   }
   layout[w] = L;
 }

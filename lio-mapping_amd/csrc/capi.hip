@@ -1491,6 +1491,43 @@ int lio_est_batch_solve_restored(lio_est_batch *h, int steps, lio_solve_report *
   if (!batch_live(h)) return LIO_ERR_STATE;
   return guarded([&] { return h->parts->SolveRestored(steps, reps) ? LIO_OK : LIO_ERR_STATE; });
 }
+// ---- include/lio_est_push_batch.h: every refusal comes before a window is touched
+static int push_batch_check(const lio_est_batch *h, const lio_est_frame *frames) {
+  if (!h || !frames) return LIO_ERR_ARG;
+  if (!batch_live(h)) return LIO_ERR_STATE;
+  const int n = h->parts->size();
+  for (int w = 0; w < n; ++w)
+    if ((!frames[w].surf_xyzi && frames[w].n_surf) || (!frames[w].corner_xyzi && frames[w].n_corner)) return LIO_ERR_ARG;
+  size_t total = 0;   // the chain indexes the clouds of a part, each rounded up to 256 points, by int
+  for (int w = 0; w < n; ++w) {
+    if (frames[w].n_surf > kMaxCloudPoints || frames[w].n_corner > kMaxCloudPoints) return LIO_ERR_CAPACITY;
+    total += frames[w].n_surf + frames[w].n_corner + 512;
+    if (total > (size_t(1) << 30)) return LIO_ERR_CAPACITY;
+  }
+  return h->parts->PushReady() ? LIO_OK : LIO_ERR_STATE;
+}
+int lio_est_batch_push_frames(lio_est_batch *h, const lio_est_frame *frames) {
+  const int rc = push_batch_check(h, frames);
+  if (rc != LIO_OK) return rc;
+  return guarded([&] { h->parts->PushFrames(frames); return LIO_OK; });
+}
+int lio_est_batch_slide_windows(lio_est_batch *h) {
+  if (!h) return LIO_ERR_ARG;
+  if (!batch_live(h)) return LIO_ERR_STATE;
+  for (lio_est *m : h->members) if (!m->e->inited_) return LIO_ERR_STATE;
+  return guarded([&] { h->parts->SlideWindows(); return LIO_OK; });
+}
+int lio_est_batch_process_laser_odom(lio_est_batch *h, const lio_est_frame *frames, lio_solve_report *reps) {
+  const int rc = push_batch_check(h, frames);
+  if (rc != LIO_OK) return rc;
+  return guarded([&] { return h->parts->ProcessLaserOdom(frames, reps) ? LIO_OK : LIO_ERR_STATE; });
+}
+int lio_est_batch_push_stats(const lio_est_batch *h, int *out8) {
+  if (!h || !out8) return LIO_ERR_ARG;
+  if (!batch_live(h)) return LIO_ERR_STATE;
+  h->parts->PushStats(out8);
+  return LIO_OK;
+}
 int lio_est_batch_sync(lio_est_batch *h) {
   if (!h) return LIO_ERR_ARG;
   if (!batch_live(h)) return LIO_ERR_STATE;

@@ -36,6 +36,25 @@ __device__ __forceinline__ float4 to_end_point(float4 p, float s, const Quat<flo
   p.x = v.x + te.x; p.y = v.y + te.y; p.z = v.z + te.z;
   return p;
 }
+// The estimator's TransformToEnd (Estimator.cc:62-103) of one point as the cloud carries it: s from the fraction of the intensity; KEEP (:79)
+// carries the intensity through, else the ring is stripped.  Stated once for a cloud de-skewed on its own (k_deskew_to_end) and for the clouds
+// of a batched push (est_push.hip: k_bp_take_keys).
+template <bool KEEP>
+__device__ __forceinline__ float4 deskew_to_end_point(float4 p, const Quat<float> &qe, const Vec3<float> &te, float time_factor) {
+  float s = time_factor * (p.w - int(p.w));
+  if (!KEEP) p.w -= int(p.w);
+  return to_end_point<true>(p, s, qe, te);
+}
+// pcl::transformPointCloud of one point by the row-major 3x4 [R | t]: m00*x + m01*y + m02*z + m03, intensity kept.  Stated once for the
+// concat of one window (k_transform_concat), of a batch's local maps (k_bw_concat_keys) and of a batch's slides (k_bp_slide).
+__device__ __forceinline__ float4 affine_map_point(const float *__restrict__ m, const float4 &p) {
+  float4 o;
+  o.x = m[0] * p.x + m[1] * p.y + m[2] * p.z + m[3];
+  o.y = m[4] * p.x + m[5] * p.y + m[6] * p.z + m[7];
+  o.z = m[8] * p.x + m[9] * p.y + m[10] * p.z + m[11];
+  o.w = p.w;
+  return o;
+}
 // The odometry's TransformToEnd (PointOdometry.cc:261-292) of point i with the transform_es_ the iterations left on the device; out == in: in
 // place.  Stated once for the odometry's own clouds, lio_odom_full_to_end and the full cloud the scan-to-map step takes from the odometry
 // (mapping.hip: k_mb_from_odom): the same instructions, so the same bits.

@@ -30,16 +30,8 @@ __global__ void k_transform_concat(ConcatArgs a, float4 *__restrict__ dst) {
   int local = gid - sg.dst_off;
   float4 p = sg.src[local];
   float4 o;
-  if (sg.identity) {
-    o = p;
-  } else {
-    const float *m = sg.tf.m;
-    // pcl::transformPointCloud: m00*x + m01*y + m02*z + m03
-    o.x = m[0] * p.x + m[1] * p.y + m[2] * p.z + m[3];
-    o.y = m[4] * p.x + m[5] * p.y + m[6] * p.z + m[7];
-    o.z = m[8] * p.x + m[9] * p.y + m[10] * p.z + m[11];
-    o.w = p.w;
-  }
+  if (sg.identity) o = p;
+  else o = affine_map_point(sg.tf.m, p);   // pcl::transformPointCloud
   if (sg.set_intensity) o.w = sg.intensity;
   dst[gid] = o;
 }
@@ -59,10 +51,7 @@ template <bool KEEP>
 __global__ void __launch_bounds__(256) k_deskew_to_end(float4 *pts, int n, Quat<float> qe, Vec3<float> te, float time_factor) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  float4 p = pts[i];
-  float s = time_factor * (p.w - int(p.w));
-  if (!KEEP) p.w -= int(p.w);
-  pts[i] = to_end_point<true>(p, s, qe, te);
+  pts[i] = deskew_to_end_point<KEEP>(pts[i], qe, te, time_factor);
 }
 void launch_deskew_to_end(float4 *pts, int n, const float q[4], const float p[3], float time_factor, hipStream_t s, bool keep_intensity) {
   if (n <= 0) return;

@@ -28,7 +28,9 @@
 #include <utility>
 #include <vector>
 
+#include "../../include/lio_est_push_batch.h"
 #include "batch_kernels.h"
+#include "est_push.h"
 #include "estimator.h"
 #include "marg_kernels.h"
 
@@ -55,6 +57,14 @@ class EstimatorBatch {
   int size() const { return int(m_.size()); }
   // SolveOptimization of every member; reps: size() reports, or null.  Returns the number of windows that were solved.
   int Solve(lio_solve_report *reps);
+  // PushFrame of every member (include/lio_est_push_batch.h; est_push.h: the chain), frames: size() entries.  The caller has checked that no
+  // member refuses its frame (Estimator::PushRefused) and that every member is initialised.  Returns synchronised with the uploads.
+  void PushFrames(const lio_est_frame *frames);
+  // SlideWindow of every member: one launch, no wait
+  void SlideWindows();
+  // ProcessLaserOdom of every (initialised) member: push, Solve, RefreshMap where it is on, slide, last_event_.  false: a member's solve failed
+  bool ProcessLaserOdom(const lio_est_frame *frames, lio_solve_report *reps);
+  const int *push_stats() const { return push_stats_; }   // of the last PushFrames (lio_est_batch_push_stats)
   // waits for everything the batch has enqueued (the marginalizations of the last Solve)
   void Sync();
   const BatchClock &clock();   // waits for the batch's stream (the device stage times come from events on it)
@@ -93,6 +103,7 @@ class EstimatorBatch {
     int cur = 0;                               // buffer holding prior_used
     int bpf = 1, max_slots = 0;
     int key_bits = 0;                          // bits the window's relative voxel keys took in its last solve (0: not known yet)
+    int push_bits = 0;                         // ... and the most that a cloud of its last push took (its own figure: a sweep is not a local map)
     size_t part_off = 0;                       // doubles into partials_
   };
   void Init(), Close() noexcept;
@@ -138,6 +149,13 @@ class EstimatorBatch {
   DBuf<int> tile_heads_, range_overflow_, cells_all_, nconv_;
   DBuf<VoxParams> vparams_;
   DBuf<uint8_t> valid_all_;
+  // the per-sweep work of the members (est_push.h)
+  PushChain push_;
+  std::vector<PushPlan> plans_;
+  int push_stats_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  hipEvent_t ev_slide_ = nullptr;   // behind the upload of the slide records: the next call rewrites their pinned staging
+  HostBuf<BpSlide> h_slide_;
+  DBuf<BpSlide> d_slide_;
 };
 
 // A batch of at least kBatchSplitFrom windows is TWO EstimatorBatch objects (the first and the second half of the windows) solved side by
@@ -157,6 +175,13 @@ class BatchParts {
   // `steps` times: Restore() every window, Solve; then Sync.  Every part loops on its own: nothing ties the parts' steps together.  false: a
   // window had no snapshot or is not initialised (both parts stop).
   bool SolveRestored(int steps, lio_solve_report *reps);
+  // include/lio_est_push_batch.h: every part pushes and slides its own windows on its own stream.  PushReady: every window is initialised and
+  // none refuses its frame — the caller's check in front of PushFrames / ProcessLaserOdom, before any window is touched.
+  bool PushReady() const;
+  void PushFrames(const lio_est_frame *frames);
+  void SlideWindows();
+  bool ProcessLaserOdom(const lio_est_frame *frames, lio_solve_report *reps);   // false: a window's solve failed
+  void PushStats(int out[8]) const;   // the parts' counters of the last push, added up
   void Sync();
   void StageDigest(int stage, unsigned long long *out);   // out: size() digests
   bool GetMoments(int w, double *out, double *Rt) { return part(w).GetMoments(w, out, Rt); }

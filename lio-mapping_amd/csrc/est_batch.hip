@@ -84,6 +84,7 @@ void EstimatorBatch::Close() noexcept {   // (the pinned and device buffers are 
   for (hipEvent_t e : ev_grp_) if (e) (void)hipEventDestroy(e);
   if (ev_fork_) (void)hipEventDestroy(ev_fork_);
   if (ev_marg_) (void)hipEventDestroy(ev_marg_);
+  if (ev_slide_) (void)hipEventDestroy(ev_slide_);
   for (hipStream_t g : stream_grp_) if (g) (void)hipStreamDestroy(g);
   if (stream_marg_) (void)hipStreamDestroy(stream_marg_);
   if (stream_) (void)hipStreamDestroy(stream_);
@@ -731,6 +732,124 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
   return B;
 }
 
+// ---------------------------------------------------------------- the members' per-sweep work (include/lio_est_push_batch.h)
+// Estimator::PushFrame of every member with the device work of all of them in one chain (est_push.h): PushFrameBegin per window, the clouds
+// that are filtered through the chain (one wait), a flagged cloud through its handle's own filter, PushFrameEnd per window.
+void EstimatorBatch::PushFrames(const lio_est_frame *fr) {
+  const int B = size();
+  hipStream_t s = stream_;
+  for (int &v : push_stats_) v = 0;
+  plans_.clear();
+  plans_.resize(size_t(B));
+  push_.begin(2 * B);
+  std::vector<int> cloud(size_t(2 * B), -1);   // the chain's cloud of window w's surf [2 w] and corner [2 w + 1] sweep
+  // three 9-bit passes when every window's clouds took at most 26 bits in its previous push, four while unknown (Solve: the local maps' rule)
+  int passes = 3;
+  for (int w = 0; w < B; ++w) {
+    Estimator *e = m_[size_t(w)];
+    PushPlan &pl = plans_[size_t(w)];
+    const lio_est_frame &f = fr[w];
+    const Rigidf T(Quat<float>(f.transform_in.q[3], f.transform_in.q[0], f.transform_in.q[1], f.transform_in.q[2]),
+                   Vec3<float>(f.transform_in.p[0], f.transform_in.p[1], f.transform_in.p[2]));
+    e->PushFrameBegin(T, f.n_surf, f.n_corner, f.stamp, pl);
+    if (pl.filter) {
+      if (pl.corner_cloud)
+        cloud[size_t(2 * w + 1)] = push_.add(f.corner_xyzi, f.n_corner, e->cfg_.corner_filter_size, pl.deskew, pl.q, pl.p, 10.f, pl.corner_cloud->buf.p);
+      cloud[size_t(2 * w)] = push_.add(f.surf_xyzi, f.n_surf, e->cfg_.surf_filter_size, pl.deskew, pl.q, pl.p, 10.f, pl.fresh.buf.p);
+      if (win_[size_t(w)].push_bits == 0 || win_[size_t(w)].push_bits > 26) passes = 4;
+    } else {   // both de-skew switches off (Estimator.cc:474-480): the clouds go into the handle's buffers as they are
+      if (pl.corner_cloud) {
+        if (f.n_corner) LIO_HIP(hipMemcpyAsync(pl.corner_cloud->buf.p, f.corner_xyzi, f.n_corner * sizeof(float4), hipMemcpyHostToDevice, s));
+        pl.corner_cloud->n = f.n_corner;
+        ++push_stats_[2];
+      }
+      if (f.n_surf) LIO_HIP(hipMemcpyAsync(pl.fresh.buf.p, f.surf_xyzi, f.n_surf * sizeof(float4), hipMemcpyHostToDevice, s));
+      pl.fresh.n = f.n_surf;
+      ++push_stats_[2];
+    }
+  }
+  bool waited = push_.run(passes, s);
+  if (!waited && push_stats_[2]) { LIO_HIP(hipStreamSynchronize(s)); waited = true; }   // the caller may reuse its buffers on return
+  push_stats_[3] = waited ? 1 : 0;
+  push_stats_[4] = push_.clouds() ? passes : 0;
+  for (int w = 0; w < B; ++w) {
+    Estimator *e = m_[size_t(w)];
+    PushPlan &pl = plans_[size_t(w)];
+    int bits = 0;
+    for (int k = 1; k >= 0; --k) {   // (corner, then surf: PushFrame's order)
+      const int i = cloud[size_t(2 * w + k)];
+      if (i < 0) continue;
+      const BpVoxOut &o = push_.out(i);
+      const size_t n = k ? pl.n_corner : pl.n_surf;
+      size_t count = size_t(o.count);
+      if (o.flagged || o.params.overflow) {
+        // keys beyond the absolute range or the passes, or PCL's "leaf size too small": the handle's own filter has the exact and the
+        // output-equals-input forms; it reads the cloud as the chain staged it (de-skewed already)
+        count = k ? e->vox_corner_.run(push_.input(i), n, e->cfg_.corner_filter_size, pl.corner_cloud->buf, s)
+                  : e->vox_.run(push_.input(i), n, e->cfg_.surf_filter_size, pl.fresh.buf, s);
+        ++push_stats_[1];
+      } else {
+        ++push_stats_[0];
+      }
+      if (o.params.n_valid > 0) bits = std::max(bits, std::max(1, bits_for(o.params.divb[0]) + bits_for(o.params.divb[1]) + bits_for(o.params.divb[2])));
+      if (k) pl.corner_cloud->n = count;
+      else pl.fresh.n = count;
+    }
+    if (bits) win_[size_t(w)].push_bits = bits;
+    e->PushFrameEnd(pl);
+  }
+  plans_.clear();
+}
+
+// Estimator::SlideWindow of every member: SlideBegin per window, the concats of all of them in one launch, SlideEnd per window
+void EstimatorBatch::SlideWindows() {
+  const int B = size();
+  hipStream_t s = stream_;
+  if (!ev_slide_) LIO_HIP(hipEventCreateWithFlags(&ev_slide_, hipEventDisableTiming));
+  else LIO_HIP(hipEventSynchronize(ev_slide_));   // the previous call's table has left the pinned staging (long done: no stream is waited for)
+  if (h_slide_.n < size_t(B)) h_slide_.alloc(size_t(B), hipHostMallocDefault, true);
+  d_slide_.reserve(size_t(B), s);
+  std::vector<ConcatArgs> ca(static_cast<size_t>(B));
+  std::vector<char> concat(size_t(B), 0);
+  int max_total = 0;
+  for (int w = 0; w < B; ++w) {
+    Estimator *e = m_[size_t(w)];
+    concat[size_t(w)] = e->SlideBegin(ca[size_t(w)]) ? 1 : 0;
+    BpSlide &S = h_slide_.p[w];
+    std::memset(static_cast<void *>(&S), 0, sizeof(S));
+    if (!concat[size_t(w)]) continue;
+    for (int k = 0; k < 2; ++k) {
+      const ConcatSeg &c = ca[size_t(w)].seg[k];
+      S.seg[k] = BwSeg{c.src, c.n, c.dst_off, c.identity, c.set_intensity, c.intensity, c.tf};
+    }
+    S.total = ca[size_t(w)].total;
+    S.dst = e->slide_dst();
+    max_total = std::max(max_total, S.total);
+  }
+  if (max_total > 0) {
+    LIO_HIP(hipMemcpyAsync(d_slide_.p, h_slide_.p, sizeof(BpSlide) * size_t(B), hipMemcpyHostToDevice, s));
+    LIO_HIP(hipEventRecord(ev_slide_, s));
+    launch_bp_slide(d_slide_.p, B, max_total, s);
+  }
+  for (int w = 0; w < B; ++w) m_[size_t(w)]->SlideEnd(concat[size_t(w)] != 0, ca[size_t(w)]);
+}
+
+// Estimator::ProcessLaserOdom (Estimator.cc:430-774) of initialised members: push, solve, the map refresh (:703-708), slide
+bool EstimatorBatch::ProcessLaserOdom(const lio_est_frame *fr, lio_solve_report *reps) {
+  const int B = size();
+  for (Estimator *e : m_) ++e->laser_odom_recv_count_;
+  PushFrames(fr);
+  Solve(reps);
+  bool ok = true;
+  for (int w = 0; w < B; ++w) {
+    if (m_[size_t(w)]->map_refresh()) m_[size_t(w)]->RefreshMap();
+    ok = ok && window_ok(w);
+  }
+  SlideWindows();
+  for (Estimator *e : m_) e->last_event_ = Estimator::EV_SOLVED;
+  return ok;
+}
+
 // ---------------------------------------------------------------- the partition
 void BatchParts::Build() {
   b_[0].reset(); b_[1].reset();   // (a part's destructor brings its device-resident priors back to the host objects)
@@ -788,6 +907,21 @@ bool BatchParts::SolveRestored(int steps, lio_solve_report *reps) {
     b.Sync();
   });
   return !bad.load();
+}
+bool BatchParts::PushReady() const {
+  for (const Estimator *e : e_) if (!e->inited_ || e->PushRefused()) return false;
+  return true;
+}
+void BatchParts::PushFrames(const lio_est_frame *frames) { ForParts([&](EstimatorBatch &b, int w0) { b.PushFrames(frames + w0); }); }
+void BatchParts::SlideWindows() { ForParts([&](EstimatorBatch &b, int) { b.SlideWindows(); }); }
+bool BatchParts::ProcessLaserOdom(const lio_est_frame *frames, lio_solve_report *reps) {
+  std::atomic<int> bad{0};
+  ForParts([&](EstimatorBatch &b, int w0) { if (!b.ProcessLaserOdom(frames + w0, reps ? reps + w0 : nullptr)) bad.store(1); });
+  return !bad.load();
+}
+void BatchParts::PushStats(int out[8]) const {
+  for (int k = 0; k < 8; ++k) out[k] = 0;
+  for (const auto &b : b_) if (b) for (int k = 0; k < 8; ++k) out[k] += b->push_stats()[k];
 }
 void BatchParts::Sync() { for (auto &b : b_) if (b) b->Sync(); }
 void BatchParts::StageDigest(int stage, unsigned long long *out) {

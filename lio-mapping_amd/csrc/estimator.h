@@ -186,6 +186,19 @@ class MargWorker {
 
 class EstimatorBatch;
 
+// What PushFrameBegin leaves for the device work of a push and for PushFrameEnd.  The single call (PushFrame) and the batched one
+// (EstimatorBatch::PushFrames) do the device work in between; the bookkeeping on both sides of it is one piece of code.
+struct PushPlan {
+  int n_before = 0;
+  size_t n_surf = 0, n_corner = 0;
+  bool filter = false;                         // de-skewed and filtered (Estimator.cc:678-693); else the clouds go in as they come (:474-480)
+  bool deskew = false;                         // ... with TransformToEnd by (q, p) in front of the filter (enable_deskew without cutoff_deskew)
+  float q[4] = {0.f, 0.f, 0.f, 1.f}, p[3] = {0.f, 0.f, 0.f};
+  Rigidf full_tes;                             // transform_es_ as SolveOptimization meets it (:2355): identity unless this push computes it
+  DeviceCloud fresh;                           // the recycled buffer of the slot being (re)written, room for n_surf points; n is the device work's to set
+  std::shared_ptr<DeviceCloud> corner_cloud;   // map refresh only: this frame's corner cloud, room for n_corner points; n likewise
+};
+
 // One window as BOTH solve paths read it (Estimator::PlanWindow): the single-window path fills ConcatArgs / SolveSetup / FeatArgs from
 // it, the batched path BatchWin.  The slot layout it goes with is the estimator's slot_off_ / nslots_ / total_slots_.
 struct WindowPlan {
@@ -215,6 +228,17 @@ class Estimator {
                       Rigidf *T_to_init, lio_solve_report *rep);
   bool PushFrame(const Rigidf &transform_in, const float *surf, size_t n_surf, const float *corner, size_t n_corner, double stamp,
                  bool surf_on_device = false, bool corner_on_device = false);
+  // PushFrame in two parts with the device work in between (the single call's: PushFrame; a batch's: est_push.h).  PushRefused: the de-skew
+  // precondition fails — checked before the window is touched.  PushFrameBegin: the LaserFrame and pre-integration pushes, the refresh ring's
+  // slot, buffer recycling, transform_es, the destinations reserved.  PushFrameEnd: PushCloud, PushFull, the counts.
+  bool PushRefused() const { return inited_ && (cfg_.enable_deskew || cfg_.cutoff_deskew) && !cfg_.cutoff_deskew && imu_stamped_.empty(); }
+  void PushFrameBegin(const Rigidf &transform_in, size_t n_surf, size_t n_corner, double stamp, PushPlan &pl);
+  void PushFrameEnd(PushPlan &pl);
+  // SlideWindow likewise: SlideBegin fills the concat of Estimator.cc:2602-2615 and reserves the scratch cloud (false: no local map yet, no
+  // device work), SlideEnd swaps the stacks and pushes the state
+  bool SlideBegin(ConcatArgs &ca);
+  void SlideEnd(bool concat, const ConcatArgs &ca);
+  float4 *slide_dst() const { return scratch_cloud_.buf.p; }
   // ---- the map-database refresh (Estimator.cc:703-708), off unless SetMapRefresh(true, map): PushFrame then keeps the optimisation-window
   // buffers (and the corner clouds they need), ProcessLaserOdom refreshes between SolveOptimization and SlideWindow
   void SetMapRefresh(bool on, MappingDev *map);

@@ -392,21 +392,21 @@ std::shared_ptr<DeviceCloud> Estimator::AcquireCornerCloud() {
   return corner_pool_.back();
 }
 
-bool Estimator::PushFrame(const Rigidf &transform_in, const float *surf, size_t n_surf, const float *corner, size_t n_corner, double stamp,
-                          bool surf_on_device, bool corner_on_device) {
+void Estimator::PushFrameBegin(const Rigidf &transform_in, size_t n_surf, size_t n_corner, double stamp, PushPlan &pl) {
   frames_dirty_ = true;
-  // every precondition is checked BEFORE the window is touched: a refused frame leaves the estimator as it was
-  if (inited_ && (cfg_.enable_deskew || cfg_.cutoff_deskew) && !cfg_.cutoff_deskew && imu_stamped_.empty()) return false;
+  pl.n_surf = n_surf; pl.n_corner = n_corner;
   LaserFrame lf;
   lf.time = stamp; lf.transform = transform_in; lf.pim = tmp_pre_integration_;
   push_at(pre_integrations_, n_frames_, tmp_pre_integration_);
   push_at(all_laser_transforms_, n_frames_, lf);
   tmp_pre_integration_ = std::make_shared<Preintegration>(acc_last_, gyr_last_, Bas_[cir_buf_count_], Bgs_[cir_buf_count_], cfg_.pim);
   const int n_before = n_frames_;
+  pl.n_before = n_before;
   if (n_frames_ < W_ + 1) ++n_frames_;
   // the stacks are pushed as they come before initialisation and with both de-skew switches off (:474-480), else de-skewed and filtered (:678-693)
   const bool as_is = !inited_ || !(cfg_.enable_deskew || cfg_.cutoff_deskew);
-  std::shared_ptr<DeviceCloud> corner_cloud;
+  pl.filter = !as_is;
+  std::shared_ptr<DeviceCloud> &corner_cloud = pl.corner_cloud;
   if (map_refresh_) {
     // Estimator.cc:467-471 and :484-485.  The stacks of :484-485 are surf_stack_.last() / corner_stack_.last() AT THAT LINE: this frame's
     // when :474-480 has just pushed them, but the PREVIOUS frame's when the de-skewed stacks are only pushed at :689-693
@@ -429,33 +429,13 @@ bool Estimator::PushFrame(const Rigidf &transform_in, const float *surf, size_t 
     }
   }
   ++frame_seq_;
-  DeviceCloud fresh = std::move(stacks_[n_before < W_ + 1 ? n_before : 0]);  // recycle the buffer of the slot being (re)written
-  if (as_is && corner_cloud) {
-    corner_cloud->buf.reserve(std::max<size_t>(n_corner, 1));
-    if (n_corner)
-      LIO_HIP(hipMemcpyAsync(corner_cloud->buf.p, corner, n_corner * sizeof(float4), corner_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
-    corner_cloud->n = n_corner;
-  }
-  if (!inited_) {  // :474-481: the stacks are the scan-to-map stage's down-sampled clouds, pushed as they are
-    fresh.buf.reserve(std::max<size_t>(n_surf, 1));
-    if (n_surf)
-      LIO_HIP(hipMemcpyAsync(fresh.buf.p, surf, n_surf * sizeof(float4), surf_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
-    fresh.n = n_surf;
-    fresh.id = ++g_content_id;
-    PushFull(Rigidf());
-    LIO_HIP(hipStreamSynchronize(stream_));  // the source may be reused by the caller right after the call
-    PushCloud(std::move(fresh), n_surf, n_before);
-    return true;
-  }
-  Rigidf full_tes;   // transform_es_ as SolveOptimization meets it (:2355): identity unless this push computes it
-  // host -> HBM (the only PCIe traffic of the step besides the small state/moment exchanges)
-  upload_.buf.reserve(std::max<size_t>(n_surf, 1));
-  if (n_surf)
-    LIO_HIP(hipMemcpyAsync(upload_.buf.p, surf, n_surf * sizeof(float4), surf_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
-  upload_.n = n_surf;
-  if (cfg_.enable_deskew || cfg_.cutoff_deskew) {
-    float q[4] = {0.f, 0.f, 0.f, 1.f}, p[3] = {0.f, 0.f, 0.f};
+  pl.fresh = std::move(stacks_[n_before < W_ + 1 ? n_before : 0]);  // recycle the buffer of the slot being (re)written
+  pl.fresh.buf.reserve(std::max<size_t>(n_surf, 1));
+  if (corner_cloud) corner_cloud->buf.reserve(std::max<size_t>(n_corner, 1));
+  if (pl.filter) {
+    float (&q)[4] = pl.q, (&p)[3] = pl.p;
     if (!cfg_.cutoff_deskew) {
+      pl.deskew = true;
       double time_e = imu_stamped_.back().time;
       Rigidf T_e = imu_stamped_.back().T;
       double time_s = time_e;
@@ -472,9 +452,47 @@ bool Estimator::PushFrame(const Rigidf &transform_in, const float *surf, size_t 
       body_es.pos = s * body_es.pos;
       Rigidf tes = compose(compose(transform_lb_, body_es), rinverse(transform_lb_));
       q[0] = tes.rot.x; q[1] = tes.rot.y; q[2] = tes.rot.z; q[3] = tes.rot.w; p[0] = tes.pos.x; p[1] = tes.pos.y; p[2] = tes.pos.z;
-      full_tes = tes;
-      launch_deskew_to_end(upload_.buf.p, int(n_surf), q, p, 10.f, stream_);
+      pl.full_tes = tes;
     }
+  }
+}
+
+void Estimator::PushFrameEnd(PushPlan &pl) {
+  const size_t nfresh = pl.fresh.n;
+  pl.fresh.id = ++g_content_id;
+  PushCloud(std::move(pl.fresh), nfresh, pl.n_before);
+  PushFull(pl.full_tes);
+}
+
+bool Estimator::PushFrame(const Rigidf &transform_in, const float *surf, size_t n_surf, const float *corner, size_t n_corner, double stamp,
+                          bool surf_on_device, bool corner_on_device) {
+  frames_dirty_ = true;
+  // every precondition is checked BEFORE the window is touched: a refused frame leaves the estimator as it was
+  if (PushRefused()) return false;
+  PushPlan pl;
+  PushFrameBegin(transform_in, n_surf, n_corner, stamp, pl);
+  DeviceCloud &fresh = pl.fresh;
+  const std::shared_ptr<DeviceCloud> &corner_cloud = pl.corner_cloud;
+  if (!pl.filter && corner_cloud) {
+    if (n_corner)
+      LIO_HIP(hipMemcpyAsync(corner_cloud->buf.p, corner, n_corner * sizeof(float4), corner_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
+    corner_cloud->n = n_corner;
+  }
+  if (!inited_) {  // :474-481: the stacks are the scan-to-map stage's down-sampled clouds, pushed as they are
+    if (n_surf)
+      LIO_HIP(hipMemcpyAsync(fresh.buf.p, surf, n_surf * sizeof(float4), surf_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
+    fresh.n = n_surf;
+    PushFrameEnd(pl);
+    LIO_HIP(hipStreamSynchronize(stream_));  // the source may be reused by the caller right after the call
+    return true;
+  }
+  // host -> HBM (the only PCIe traffic of the step besides the small state/moment exchanges)
+  upload_.buf.reserve(std::max<size_t>(n_surf, 1));
+  if (n_surf)
+    LIO_HIP(hipMemcpyAsync(upload_.buf.p, surf, n_surf * sizeof(float4), surf_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
+  upload_.n = n_surf;
+  if (pl.filter) {
+    if (pl.deskew) launch_deskew_to_end(upload_.buf.p, int(n_surf), pl.q, pl.p, 10.f, stream_);
     // corner clouds are only consumed under USE_CORNER (off in the shipped build, Estimator.h:55) and by the map refresh: processed
     // for the refresh's ring only (:670, :684-687, :692)
     if (corner_cloud) {
@@ -483,19 +501,15 @@ bool Estimator::PushFrame(const Rigidf &transform_in, const float *surf, size_t 
         LIO_HIP(hipMemcpyAsync(upload_corner_.buf.p, corner, n_corner * sizeof(float4), corner_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
                                stream_));
       upload_corner_.n = n_corner;
-      if (!cfg_.cutoff_deskew) launch_deskew_to_end(upload_corner_.buf.p, int(n_corner), q, p, 10.f, stream_);
+      if (pl.deskew) launch_deskew_to_end(upload_corner_.buf.p, int(n_corner), pl.q, pl.p, 10.f, stream_);
       corner_cloud->n = vox_corner_.run(upload_corner_.buf.p, n_corner, cfg_.corner_filter_size, corner_cloud->buf, stream_);
     }
     fresh.n = vox_.run(upload_.buf.p, n_surf, cfg_.surf_filter_size, fresh.buf, stream_);
   } else {
-    fresh.buf.reserve(std::max<size_t>(n_surf, 1));
     if (n_surf) LIO_HIP(hipMemcpyAsync(fresh.buf.p, upload_.buf.p, n_surf * sizeof(float4), hipMemcpyDeviceToDevice, stream_));
     fresh.n = n_surf;
   }
-  size_t nfresh = fresh.n;
-  fresh.id = ++g_content_id;
-  PushCloud(std::move(fresh), nfresh, n_before);
-  PushFull(full_tes);
+  PushFrameEnd(pl);
   return true;
 }
 
@@ -1153,7 +1167,15 @@ void Estimator::AssembleSystem(WindowParams &P, WindowSystem &sys) const {
 }
 
 void Estimator::SlideWindow() {
-  if (init_local_map_) {
+  ConcatArgs ca{};
+  const bool concat = SlideBegin(ca);
+  if (concat) launch_transform_concat(ca, scratch_cloud_.buf.p, stream_);
+  SlideEnd(concat, ca);
+}
+
+bool Estimator::SlideBegin(ConcatArgs &ca) {
+  if (!init_local_map_) return false;
+  {
     const int pivot = W_ - Wo_;
     const Rigidd lb = toDouble(transform_lb_);
     const Rigidd T_pivot = LidarPose(pivot, lb);
@@ -1161,7 +1183,7 @@ void Estimator::SlideWindow() {
     const Rigidd T_li = LidarPose(i, lb);
     const Rigidf tf = toFloat(compose(rinverse(T_li), T_pivot));
     const size_t drop = std::min(size_surf_stack_[0], stacks_[pivot].n);
-    ConcatArgs ca{};
+    ca = ConcatArgs{};
     ca.nseg = 2;
     ca.seg[0].src = stacks_[pivot].buf.p + drop; ca.seg[0].n = int(stacks_[pivot].n - drop); ca.seg[0].dst_off = 0;
     ca.seg[0].identity = 0; ca.seg[0].set_intensity = 0; ca.seg[0].intensity = 0; ca.seg[0].tf = affineOf(tf);
@@ -1169,7 +1191,13 @@ void Estimator::SlideWindow() {
     ca.seg[1].identity = 1; ca.seg[1].set_intensity = 0; ca.seg[1].intensity = 0;
     ca.total = ca.seg[0].n + ca.seg[1].n;
     scratch_cloud_.buf.reserve(std::max(ca.total, 1));
-    launch_transform_concat(ca, scratch_cloud_.buf.p, stream_);
+  }
+  return true;
+}
+
+void Estimator::SlideEnd(bool concat, const ConcatArgs &ca) {
+  if (concat) {
+    const int i = W_ - Wo_ + 1;
     scratch_cloud_.n = size_t(ca.total);
     scratch_cloud_.id = ++g_content_id;
     // no host wait: the swap exchanges host-side handles only, and every reader or writer of either buffer (the next solve's

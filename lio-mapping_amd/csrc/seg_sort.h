@@ -37,6 +37,17 @@ struct KeyLayout { int mx, my, mz; int bx, by; int bits; };   // mins in the sto
 // bits a key takes to number `extent` values (a window's cells along an axis, the cells of a grid)
 LIO_HD int bits_for(int extent) { int b = 0; while ((1 << b) < extent) ++b; return b; }
 
+// The layout of a cloud with points whose stored keys span the cells minb .. minb + divb - 1 (VoxParams): floor(x inv_leaf) is monotone in x,
+// so the smallest stored cell coordinate of the cloud is the bound's.  False: the relative keys take more than max_bits — what the caller's
+// passes order, minus one ("no point" sits one above the real keys).  Stated once for the local maps of a batched solve (k_bw_key_layout)
+// and the clouds of a batched push (k_bp_key_layout).
+LIO_HD bool vox_key_layout(const int minb[3], const int divb[3], int max_bits, KeyLayout &L) {
+  L.mx = minb[0] + 1024; L.my = minb[1] + 1024; L.mz = minb[2] + 256;
+  const int bx = bits_for(divb[0]), by = bits_for(divb[1]), bz = bits_for(divb[2]);
+  L.bx = bx; L.by = bx + by; L.bits = bx + by + bz;
+  return L.bits <= max_bits;
+}
+
 struct SegSortPlan {
   int threads;          // 256 or 512 per block: tile = threads * SS_ITEMS
   int max_tiles;        // tiles of the largest segment

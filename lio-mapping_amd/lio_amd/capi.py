@@ -329,6 +329,20 @@ _MAP_FROM_ODOM_SIGS = {
     "lio_map_process_batch_from_odom": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.POINTER(TransformF),
                                                   c_int32_p, c_int32_p]),
 }
+# include/lio_est_push_batch.h: PushFrame / SlideWindow / ProcessLaserOdom of the windows of a batch through one launch chain (the product
+# only; attached where the library has them, so that a build from before them still loads as an A/B tool's --parent-lib)
+class EstFrame(C.Structure):
+    _fields_ = [("transform_in", TransformF), ("surf_xyzi", c_float_p), ("n_surf", C.c_size_t), ("corner_xyzi", c_float_p), ("n_corner", C.c_size_t),
+                ("stamp", C.c_double)]
+
+
+_EST_PUSH_SIGS = {
+    "lio_est_batch_push_frames": (C.c_int, [C.c_void_p, C.POINTER(EstFrame)]),
+    "lio_est_batch_slide_windows": (C.c_int, [C.c_void_p]),
+    "lio_est_batch_process_laser_odom": (C.c_int, [C.c_void_p, C.POINTER(EstFrame), C.POINTER(SolveReport)]),
+    "lio_est_batch_push_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+}
+PUSH_STATS = ("chain", "redone", "as_is", "host_waits", "sort_passes")   # lio_est_batch_push_stats [0 .. 4]
 # include/lio_vox_sort.h: the voxel filter's sort on caller-given keys and the counters of the paths it took (the product only, attached like _EXT_SIGS)
 _c_uint32_p = C.POINTER(C.c_uint32)
 _VOX_SORT_SIGS = {
@@ -404,7 +418,7 @@ class LioLib:
                 fn.restype = res
                 fn.argtypes = args
             # a build from before the sample sort still loads (the A/B tools take one as --parent-lib); only a call to these fails there
-            for name, (res, args) in list(_VOX_SORT_SIGS.items()) + list(_SEG_BOUNDS_SIGS.items()):
+            for name, (res, args) in list(_VOX_SORT_SIGS.items()) + list(_SEG_BOUNDS_SIGS.items()) + list(_EST_PUSH_SIGS.items()):
                 fn = getattr(self.dll, name, None)
                 if fn is not None:
                     fn.restype = res
@@ -1526,6 +1540,43 @@ class EstimatorBatch:
 
     def sync(self):
         _chk(self.lib.dll.lio_est_batch_sync(self.h), "lio_est_batch_sync")
+
+    # ---- include/lio_est_push_batch.h (tests and tools)
+    @staticmethod
+    def frames(items):
+        """items: per window (TransformF, surf, corner, stamp) -> (EstFrame array, the arrays it points into)"""
+        arr = (EstFrame * max(len(items), 1))()
+        keep = []
+        for k, (T, surf, corner, stamp) in enumerate(items):
+            s, c = _f32(surf).reshape(-1, 4), _f32(corner).reshape(-1, 4)
+            keep += [s, c]
+            arr[k].transform_in = T
+            arr[k].surf_xyzi, arr[k].n_surf = (_fp(s) if s.shape[0] else None), s.shape[0]
+            arr[k].corner_xyzi, arr[k].n_corner = (_fp(c) if c.shape[0] else None), c.shape[0]
+            arr[k].stamp = stamp
+        return arr, keep
+
+    def push_frames(self, items):
+        """lio_est_batch_push_frames: lio_est_push_frame of every window; items as frames() takes them, one per window"""
+        assert len(items) == len(self.members)
+        arr, keep = self.frames(items)
+        _chk(self.lib.dll.lio_est_batch_push_frames(self.h, arr), "lio_est_batch_push_frames")
+
+    def slide(self):
+        _chk(self.lib.dll.lio_est_batch_slide_windows(self.h), "lio_est_batch_slide_windows")
+
+    def process_laser_odom(self, items):
+        """lio_est_batch_process_laser_odom -> one SolveReport per window"""
+        assert len(items) == len(self.members)
+        arr, keep = self.frames(items)
+        reps = (SolveReport * len(self.members))()
+        _chk(self.lib.dll.lio_est_batch_process_laser_odom(self.h, arr, reps), "lio_est_batch_process_laser_odom")
+        return list(reps)
+
+    def push_stats(self):
+        out = (C.c_int * 8)()
+        _chk(self.lib.dll.lio_est_batch_push_stats(self.h, out), "lio_est_batch_push_stats")
+        return dict(zip(PUSH_STATS, [int(v) for v in out[:5]]))
 
     STAGES = ("filtered_map", "knn_grid", "feature_flags", "plane_coefficients", "newest_frame_state", "solver_state", "moments", "jacobi_scaling", "scaled_hessian", "new_prior")
 
