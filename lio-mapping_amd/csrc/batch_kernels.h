@@ -3,9 +3,11 @@
 // ONE launch over all windows of the batch, indexed by blockIdx.y / .z through a per-window descriptor in device memory.
 // The per-window arithmetic is the single-window kernels' (cloud_device.h), and every partition (blocks of a round, tiles of a
 // filter) is a function of the window's own sizes: a window gives the same bits alone (B = 1) and inside any batch.
+// The local maps' voxel filter behind the concat is the segmented filter of seg_vox.h, which the batched push (est_push.h) runs too.
 #pragma once
 #include "cloud_kernels.h"
 #include "seg_sort.h"
+#include "seg_vox.h"
 
 namespace lio {
 
@@ -13,14 +15,12 @@ namespace lio {
 #define BW_KEY_NONE 0x7FFFFFFFu  // stored voxel key of the batched filter (absolute cells, 31 bits): all ones = no point
 #define LIO_BW_MAX_STATIC 7     // frames whose features do not depend on the newest frame's rounds
 
-struct BwSeg { const float4 *src; int n; int dst_off; int identity; int set_intensity; float intensity; Affine3f tf; };
-
 struct BatchWin {
-  // ---- BuildLocalMap: concat into local_all[loc_off, loc_off + n_local), keys, filter
-  BwSeg seg[LIO_BW_MAX_SEG];
-  int nseg, n_local;
-  int loc_off, loc_cap;          // this window's range of the batch's point arrays (both multiples of 256)
-  float inv_leaf;
+  // ---- BuildLocalMap: concat into local_all[vox.off, vox.off + vox.n), keys, filter (vox.dst null: the batch's filtered array); vox.off is
+  // this window's first point in every point array of the batch
+  ConcatSeg seg[LIO_BW_MAX_SEG];
+  int nseg;
+  VoxSeg vox;
   // ---- feature slots: this window's range of the batch's slot arrays (valid / coef / score)
   int slot_base, n_slots;
   FeatFrame fr[LIO_BW_MAX_STATIC];   // slot_off is an offset into the batch's arrays, tf_index an index into tf
@@ -30,9 +30,6 @@ struct BatchWin {
   float tf[LIO_BW_MAX_STATIC + 1][8];   // local transforms (qx qy qz qw px py pz pad); the last entry is the newest frame's start
   float min_match_sq_dis, min_plane_dis;
 };
-
-// what the filter reports per window (read by the host after the stream has drained)
-struct BwVoxOut { int count; VoxParams params; int range_overflow; };
 
 // the K-NN grid of a window (host-computed from the filter's bounds, uploaded before the cell build)
 struct BatchGrid { GridDesc g; int cell_off; int n_filtered; };
@@ -50,14 +47,9 @@ struct BatchKnobs {
 
 int bw_round_blocks(int M);   // search blocks of one round of a window's newest frame: 64 queries each, whatever the lanes per query
 
-// concat + voxel keys (absolute cells) + per-block bounds; then, one block per window, the bounds folded into VoxParams and the key layout
-// the segmented sort runs on (seg_sort.h).  keys: loc-array sized; partial: 8 floats per 256-point block
-// max_bits: what the passes the caller is going to run can order, minus one (a window that needs more is flagged in range_overflow)
-void launch_bw_concat_keys(const BatchWin *win, int B, int max_local, float4 *local_all, uint32_t *keys, float *partial, VoxParams *params, KeyLayout *layout,
-                           int *range_overflow, int max_bits, hipStream_t s);
-// sorted (relative) keys -> tile heads -> centroids, counts
-void launch_bw_vox_finish(const BatchWin *win, int B, int max_cap, const float4 *local_all, const uint32_t *keys_sorted, const uint32_t *vals_sorted, int *tile_heads,
-                          float4 *filtered_all, const VoxParams *params, int *range_overflow, BwVoxOut *out, hipStream_t s);
+// concat + voxel keys (absolute cells) + per-block bounds: the producer in front of SegVoxFilter::finish (seg_vox.h).  keys, partial, flag: the
+// filter's (keys: loc-array sized; partial: 8 floats per 256-point block)
+void launch_bw_concat_keys(const BatchWin *win, int B, int max_local, float4 *local_all, uint32_t *keys, float *partial, int *flag, hipStream_t s);
 // feature flags cleared, the newest frames' Gauss-Newton states started
 void launch_bw_setup(const BatchWin *win, int B, int max_slots, uint8_t *valid_all, OdomState *odom, int *n_converged, hipStream_t s);
 // K-NN grid: cell keys of the filtered points; (segmented sort by the caller); cell-sorted points + the dense table of run starts

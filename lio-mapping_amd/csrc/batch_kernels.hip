@@ -20,101 +20,29 @@ int bw_round_blocks(int M) { return std::max(1, cdiv(M, 64)); }
 // BuildLocalMap, first half: pcl::transformPointCloud + `+=` (Estimator.cc:1480-1507) and, from the point still in registers, the
 // filter's sort key — the window above PCL's voxel index in absolute cells (cloud_kernels.hip: k_vox_keys_abs; the window in the
 // high word keeps every window's points together through ONE sort of the whole batch) — and the block's share of the bounds.
+// The layout, the sort, the heads and the centroids behind it: SegVoxFilter::finish (seg_vox.hip).
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(BW_THREADS) k_bw_concat_keys(const BatchWin *__restrict__ win, float4 *__restrict__ local_all, uint32_t *__restrict__ keys,
-                                                              float *__restrict__ partial, int *__restrict__ range_overflow) {
+__global__ void __launch_bounds__(VOX_TILE) k_bw_concat_keys(const BatchWin *__restrict__ win, float4 *__restrict__ local_all, uint32_t *__restrict__ keys,
+                                                            float *__restrict__ partial, int *__restrict__ flag) {
   const int w = blockIdx.y;
   const BatchWin &W = win[w];
-  const int base = int(blockIdx.x) * BW_THREADS;
-  if (base >= W.loc_cap) return;
+  const int base = int(blockIdx.x) * VOX_TILE;
+  if (base >= W.vox.cap) return;
   const int gid = base + threadIdx.x;
   float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
   float cnt = 0;
-  uint32_t key = BW_KEY_NONE;
-  if (gid < W.n_local) {
-    int sidx = 0;
-    for (int k = 1; k < W.nseg; ++k)
-      if (gid >= W.seg[k].dst_off) sidx = k;
-    const BwSeg &sg = W.seg[sidx];
-    const float4 p = rebase(local_all, sg.src)[gid - sg.dst_off];
-    float4 o;
-    if (sg.identity) o = p;
-    else o = affine_map_point(sg.tf.m, p);
-    if (sg.set_intensity) o.w = sg.intensity;
-    local_all[W.loc_off + gid] = o;
-    if (finite3(o)) {
-      cnt = 1.f;
-      mn[0] = mx[0] = o.x; mn[1] = mx[1] = o.y; mn[2] = mx[2] = o.z;
-      // z 9 bits (+-102 m of height at a 0.4 m leaf; a window beyond that takes the single-window path); the sort runs on the key relative
-      // to the window's bounds (seg_sort.h: KeyLayout)
-      if (!vox_abs_key<9>(o, W.inv_leaf, key)) range_overflow[w] = 1;
-    }
-    keys[W.loc_off + gid] = key;
+  if (gid < W.vox.n) {
+    const float4 o = concat_point(W.seg, W.nseg, gid, local_all);
+    local_all[W.vox.off + gid] = o;
+    // z 9 bits (+-102 m of height at a 0.4 m leaf; a window beyond that takes the single-window path); the sort runs on the key relative
+    // to the window's bounds (seg_sort.h: KeyLayout)
+    keys[W.vox.off + gid] = vox_take_point<9, BW_KEY_NONE>(o, W.vox.inv_leaf, mn, mx, cnt, flag + w);
   }
-  vox_block_partial(mn, mx, cnt, partial + (size_t(W.loc_off / BW_THREADS) + blockIdx.x) * 8);
+  vox_block_partial(mn, mx, cnt, partial + (size_t(W.vox.off / VOX_TILE) + blockIdx.x) * 8);
 }
-
-// the window's bounds folded into VoxParams (cloud_device.h: vox_fold_bounds), and from them how the sort sees the keys: one block per window
-__global__ void __launch_bounds__(BW_THREADS) k_bw_key_layout(const BatchWin *__restrict__ win, const float *__restrict__ partial, VoxParams *__restrict__ params,
-                                                             KeyLayout *__restrict__ layout, int *__restrict__ range_overflow, int max_bits) {
-  const int w = blockIdx.x;
-  const BatchWin &W = win[w];
-  VoxParams v;
-  if (!vox_fold_bounds(partial + size_t(W.loc_off / BW_THREADS) * 8, W.loc_cap / BW_THREADS, W.inv_leaf, v)) return;
-  params[w] = v;
-  KeyLayout L{0, 0, 0, 0, 0, 0};
-  if (v.n_valid > 0 && !range_overflow[w]) {
-    if (!vox_key_layout(v.minb, v.divb, max_bits, L)) range_overflow[w] = 1;   // the launch's passes order max_bits + 1 bits: single-window path
-  }
-  layout[w] = L;
-}
-
-void launch_bw_concat_keys(const BatchWin *win, int B, int max_local, float4 *local_all, uint32_t *keys, float *partial, VoxParams *params, KeyLayout *layout,
-                           int *range_overflow, int max_bits, hipStream_t s) {
+void launch_bw_concat_keys(const BatchWin *win, int B, int max_local, float4 *local_all, uint32_t *keys, float *partial, int *flag, hipStream_t s) {
   if (B <= 0 || max_local <= 0) return;
-  hipLaunchKernelGGL(k_bw_concat_keys, dim3(cdiv(max_local, BW_THREADS), B), dim3(BW_THREADS), 0, s, win, local_all, keys, partial, range_overflow);
-  hipLaunchKernelGGL(k_bw_key_layout, dim3(B), dim3(BW_THREADS), 0, s, win, partial, params, layout, range_overflow, max_bits);
-  LIO_HIP(hipGetLastError());
-}
-
-// ------------------------------------------------------------------------------------------------
-// pcl::VoxelGrid (Estimator.cc:1518-1519), behind the sort: heads per 256-entry tile of a window's sorted range, then the centroids — a
-// run is added up in sorted order, i.e. in ascending original index (the sort is stable), the order the oracle fixes.  Keys: the sort's
-// relative keys, all ones = no point (sorted last); positions from n_local on hold nothing.
-// ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(BW_THREADS) k_bw_vox_heads(const BatchWin *__restrict__ win, const uint32_t *__restrict__ keys, int *__restrict__ tile_heads) {
-  const BatchWin &W = win[blockIdx.y];
-  if (int(blockIdx.x) >= W.loc_cap / BW_THREADS) return;
-  vox_tile_head_count(keys + W.loc_off, W.n_local, blockIdx.x, tile_heads + W.loc_off / BW_THREADS + blockIdx.x);
-}
-
-__global__ void __launch_bounds__(BW_THREADS) k_bw_vox_centroids(const BatchWin *__restrict__ win, const float4 *__restrict__ pts, const uint32_t *__restrict__ keys,
-                                                                const uint32_t *__restrict__ vals, const int *__restrict__ tile_heads, float4 *__restrict__ out,
-                                                                const VoxParams *__restrict__ params, int *__restrict__ range_overflow,
-                                                                BwVoxOut *__restrict__ vout) {
-  const int w = blockIdx.y;
-  const BatchWin &W = win[w];
-  const int ntiles = W.loc_cap / BW_THREADS;
-  if (int(blockIdx.x) >= ntiles) return;
-  // (vals index the batch's point array: pts is not shifted)
-  const VoxSlot r = vox_centroid_tile(pts, keys + W.loc_off, vals + W.loc_off, tile_heads + W.loc_off / BW_THREADS, W.n_local, blockIdx.x, out + W.loc_off);
-  if (int(blockIdx.x) == ntiles - 1 && threadIdx.x == BW_THREADS - 1) {   // the window's last tile knows the total
-    BwVoxOut o;
-    o.count = r.pos + (r.head ? 1 : 0);
-    o.params = params[w];
-    o.range_overflow = range_overflow[w];
-    range_overflow[w] = 0;   // clear for the next solve (no fill command in front of it)
-    vout[w] = o;
-  }
-}
-
-void launch_bw_vox_finish(const BatchWin *win, int B, int max_cap, const float4 *local_all, const uint32_t *keys_sorted, const uint32_t *vals_sorted, int *tile_heads,
-                          float4 *filtered_all, const VoxParams *params, int *range_overflow, BwVoxOut *out, hipStream_t s) {
-  if (B <= 0 || max_cap <= 0) return;
-  const int ntiles = max_cap / BW_THREADS;
-  hipLaunchKernelGGL(k_bw_vox_heads, dim3(ntiles, B), dim3(BW_THREADS), 0, s, win, keys_sorted, tile_heads);
-  hipLaunchKernelGGL(k_bw_vox_centroids, dim3(ntiles, B), dim3(BW_THREADS), 0, s, win, local_all, keys_sorted, vals_sorted, tile_heads, filtered_all, params,
-                     range_overflow, out);
+  hipLaunchKernelGGL(k_bw_concat_keys, dim3(cdiv(max_local, VOX_TILE), B), dim3(VOX_TILE), 0, s, win, local_all, keys, partial, flag);
   LIO_HIP(hipGetLastError());
 }
 
@@ -152,7 +80,7 @@ __global__ void __launch_bounds__(BW_THREADS) k_bw_cell_keys(const BatchWin *__r
   const BatchGrid &G = grid[w];
   const int i = int(blockIdx.x) * BW_THREADS + threadIdx.x;
   if (i >= G.n_filtered) return;
-  const int gi = win[w].loc_off + i;
+  const int gi = win[w].vox.off + i;
   keys[gi] = cell_key_clamped(filtered_all[gi], G.g);
 }
 // behind the sort by cell: the cell-sorted points, and the table — entry c = position of the first point whose cell is >= c (an empty cell
@@ -167,7 +95,7 @@ __global__ void __launch_bounds__(BW_THREADS) k_bw_cell_table(const BatchWin *__
   const int n = G.n_filtered;
   const int i0 = int(blockIdx.x) * BW_THREADS;
   if (i0 >= max(n, 1)) return;
-  const int off = win[w].loc_off, i = i0 + threadIdx.x, lane = threadIdx.x & 63;
+  const int off = win[w].vox.off, i = i0 + threadIdx.x, lane = threadIdx.x & 63;
   const int ncells = G.g.dims[0] * G.g.dims[1] * G.g.dims[2];
   int *cells = cells_all + G.cell_off;
   if (n == 0) {   // (block 0 only)

@@ -10,6 +10,7 @@
 
 #include <cfloat>
 #include <climits>
+#include <cstddef>
 
 #include "cloud_kernels.h"
 #include "hmath.h"
@@ -45,14 +46,32 @@ __device__ __forceinline__ float4 deskew_to_end_point(float4 p, const Quat<float
   if (!KEEP) p.w -= int(p.w);
   return to_end_point<true>(p, s, qe, te);
 }
-// pcl::transformPointCloud of one point by the row-major 3x4 [R | t]: m00*x + m01*y + m02*z + m03, intensity kept.  Stated once for the
-// concat of one window (k_transform_concat), of a batch's local maps (k_bw_concat_keys) and of a batch's slides (k_bp_slide).
+// pcl::transformPointCloud of one point by the row-major 3x4 [R | t]: m00*x + m01*y + m02*z + m03, intensity kept
 __device__ __forceinline__ float4 affine_map_point(const float *__restrict__ m, const float4 &p) {
   float4 o;
   o.x = m[0] * p.x + m[1] * p.y + m[2] * p.z + m[3];
   o.y = m[4] * p.x + m[5] * p.y + m[6] * p.z + m[7];
   o.z = m[8] * p.x + m[9] * p.y + m[10] * p.z + m[11];
   o.w = p.w;
+  return o;
+}
+// Position g of a concat of `nseg` segments (pcl::transformPointCloud + `+=`, Estimator.cc:1480-1507, :2602-2615): the segment that holds it,
+// the load, the segment's map or none, its intensity.  Stated once for the concat of one window (k_transform_concat), of a batch's local maps
+// (k_bw_concat_keys) and of a batch's slides (k_bp_slide); the caller keeps its own range test or clamp of g.  base: the kernel-argument
+// pointer the segments' sources are tied to (dev.h: rebase); nullptr where the segments arrive as kernel arguments themselves.
+template <class B> __device__ __forceinline__ const float4 *concat_src(B *base, const float4 *p) { return rebase(base, p); }
+__device__ __forceinline__ const float4 *concat_src(std::nullptr_t, const float4 *p) { return p; }
+template <class B>
+__device__ __forceinline__ float4 concat_point(const ConcatSeg *__restrict__ seg, int nseg, int g, B base) {
+  int sidx = 0;
+  for (int k = 1; k < nseg; ++k)
+    if (g >= seg[k].dst_off) sidx = k;
+  const ConcatSeg &sg = seg[sidx];
+  const float4 p = concat_src(base, sg.src)[g - sg.dst_off];
+  float4 o;
+  if (sg.identity) o = p;
+  else o = affine_map_point(sg.tf.m, p);
+  if (sg.set_intensity) o.w = sg.intensity;
   return o;
 }
 // The odometry's TransformToEnd (PointOdometry.cc:261-292) of point i with the transform_es_ the iterations left on the device; out == in: in
@@ -158,6 +177,19 @@ __device__ __forceinline__ bool vox_abs_key(const float4 &p, float inv_leaf, uin
   if (!(fabsf(cx) < 1024.f && fabsf(cy) < 1024.f && fabsf(cz) < float(ZOFF - 1))) return false;
   key = (uint32_t(int(cz) + ZOFF) << 22) | (uint32_t(int(cy) + 1024) << 11) | uint32_t(int(cx) + 1024);
   return true;
+}
+// A point still in registers taken into the filter: its stored key (NONE: no point, i.e. not finite) and the lane's share (mn, mx, cnt) of
+// the bounds; a finite point beyond the key's range raises *flag and keeps NONE.  Stated once for the single-window filter (k_vox_keys_abs),
+// the local maps of a batched solve (k_bw_concat_keys) and the clouds of a batched push (k_bp_take_keys).
+template <int ZBITS, uint32_t NONE>
+__device__ __forceinline__ uint32_t vox_take_point(const float4 &p, float inv_leaf, float (&mn)[3], float (&mx)[3], float &cnt, int *__restrict__ flag) {
+  uint32_t key = NONE;
+  if (finite3(p)) {
+    cnt = 1.f;
+    mn[0] = mx[0] = p.x; mn[1] = mx[1] = p.y; mn[2] = mx[2] = p.z;
+    if (!vox_abs_key<ZBITS>(p, inv_leaf, key)) *flag = 1;
+  }
+  return key;
 }
 
 // the block's bounds and count of finite points from every lane's (mn, mx, cnt) -> row[0 .. 6]: wave shuffles, then the four waves through LDS

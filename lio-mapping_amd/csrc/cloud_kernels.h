@@ -25,9 +25,10 @@ struct Affine3f { float m[12]; };  // row-major 3x4: [R | t]
 
 #define LIO_MAX_FRAMES 32
 
-struct ConcatSeg { const float4 *src; int n; int dst_off; int set_intensity; float intensity; Affine3f tf; int identity; };
+// dst[seg.dst_off + k] = tf * src[k] (or src[k] when identity); intensity optionally overwritten.  One segment record for the concat of one
+// window (ConcatArgs), of a batch's local maps (batch_kernels.h: BatchWin) and of a batch's slides (est_push.h: BpSlide)
+struct ConcatSeg { const float4 *src; int n; int dst_off; int identity; int set_intensity; float intensity; Affine3f tf; };
 struct ConcatArgs { ConcatSeg seg[LIO_MAX_FRAMES]; int nseg; int total; };
-// dst[seg.dst_off + k] = tf * src[k] (or src[k] when identity); intensity optionally overwritten
 void launch_transform_concat(const ConcatArgs &a, float4 *dst, hipStream_t s);
 
 // TransformToEnd (Estimator.cc:62-103) in place; tes = q(xyzw), p.  keep_intensity (:79): the form SolveOptimization runs on the

@@ -23,17 +23,7 @@ namespace lio {
 __global__ void k_transform_concat(ConcatArgs a, float4 *__restrict__ dst) {
   int gid = blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= a.total) return;
-  int sidx = 0;
-  for (int k = 1; k < a.nseg; ++k)
-    if (gid >= a.seg[k].dst_off) sidx = k;
-  const ConcatSeg &sg = a.seg[sidx];
-  int local = gid - sg.dst_off;
-  float4 p = sg.src[local];
-  float4 o;
-  if (sg.identity) o = p;
-  else o = affine_map_point(sg.tf.m, p);   // pcl::transformPointCloud
-  if (sg.set_intensity) o.w = sg.intensity;
-  dst[gid] = o;
+  dst[gid] = concat_point(a.seg, a.nseg, gid, nullptr);   // (the sources are kernel arguments: nothing to tie them to)
 }
 
 void launch_transform_concat(const ConcatArgs &a, float4 *dst, hipStream_t s) {
@@ -132,14 +122,7 @@ __global__ void __launch_bounds__(VOX_TILE) k_vox_keys_abs(const float4 *__restr
   float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
   float cnt = 0;
   if (i < n) {
-    const float4 p = pts[i];
-    uint32_t key = VOX_KEY_NONE;
-    if (finite3(p)) {
-      cnt = 1.f;
-      mn[0] = mx[0] = p.x; mn[1] = mx[1] = p.y; mn[2] = mx[2] = p.z;
-      if (!vox_abs_key<10>(p, inv_leaf, key)) *range_overflow = 1;
-    }
-    keys[i] = key;
+    keys[i] = vox_take_point<10, VOX_KEY_NONE>(pts[i], inv_leaf, mn, mx, cnt, range_overflow);
     vals[i] = uint32_t(i);
   }
   vox_block_partial(mn, mx, cnt, partial + size_t(blockIdx.x) * 8);

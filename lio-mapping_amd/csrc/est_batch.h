@@ -102,8 +102,8 @@ class EstimatorBatch {
     std::shared_ptr<MargPrior> dev_prior[2];   // which host object each of the two device prior buffers holds
     int cur = 0;                               // buffer holding prior_used
     int bpf = 1, max_slots = 0;
-    int key_bits = 0;                          // bits the window's relative voxel keys took in its last solve (0: not known yet)
-    int push_bits = 0;                         // ... and the most that a cloud of its last push took (its own figure: a sweep is not a local map)
+    int key_bits = 0;                          // SegVoxFilter::bits_taken of the window's local map in its last solve (0: not known yet)
+    int push_bits = 0;                         // ... and the most over the clouds of its last push (its own figure: a sweep is not a local map)
     size_t part_off = 0;                       // doubles into partials_
   };
   void Init(), Close() noexcept;
@@ -132,22 +132,22 @@ class EstimatorBatch {
   Slab lay_{};
   BatchClock clk_;
   // pinned staging (one entry per window)
-  HostBuf<BatchWin> h_win_; HostBuf<BatchGrid> h_grid_; HostBuf<BwVoxOut> h_vout_; HostBuf<OdomState> h_odom_;
+  HostBuf<BatchWin> h_win_; HostBuf<BatchGrid> h_grid_; HostBuf<OdomState> h_odom_;
   HostBuf<BatchSolve> h_bs_; HostBuf<DevProblem> h_pb_; HostBuf<DevState> h_st_; HostBuf<DevMarg> h_mg_;
   HostBuf<double> h_prior_;   // one ds_prior_mats_size(MARG_MAX_N) slot per window: priors on their way to the device
   HostBuf<int> h_nconv_;
   // device
-  DBuf<BatchWin> d_win_; DBuf<BatchGrid> d_grid_; DBuf<BwVoxOut> d_vout_; DBuf<OdomState> d_odom_;
+  DBuf<BatchWin> d_win_; DBuf<BatchGrid> d_grid_; DBuf<OdomState> d_odom_;
   DBuf<BatchSolve> d_bs_; DBuf<DevProblem> d_pb_; DBuf<DevState> d_st_; DBuf<DevMarg> d_mg_;
   DBuf<double> slab_, partials_, odom_partials_;
   DBuf<float4> local_all_, filtered_all_, sorted_all_, coef_all_;
-  DBuf<uint32_t> keys_, keysb_, vals_, valsb_, ckeys_, sort_hist_;   // the segmented sort's ping-pong pairs (filter, then K-NN grid) and its histograms
-  DBuf<SegDesc> d_seg_;
-  DBuf<KeyLayout> d_layout_;
+  // The one segmented voxel filter of the part (seg_vox.h): Solve's local maps and PushFrames' sweeps take turns on stream_, and each reads its
+  // results behind its own wait.  Solve's K-NN cell sort borrows the filter's sort scratch between the two.
+  SegVoxFilter vox_;
+  DBuf<SegDesc> d_seg_;     // the K-NN cell sort's segments
   HostBuf<SegDesc> h_seg_;
-  DBuf<float> bounds_partial_, score_all_;
-  DBuf<int> tile_heads_, range_overflow_, cells_all_, nconv_;
-  DBuf<VoxParams> vparams_;
+  DBuf<float> score_all_;
+  DBuf<int> cells_all_, nconv_;
   DBuf<uint8_t> valid_all_;
   // the per-sweep work of the members (est_push.h)
   PushChain push_;

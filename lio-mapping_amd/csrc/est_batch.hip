@@ -1,5 +1,5 @@
 // est_batch.hip — host orchestration of the batched solve (see est_batch.h).  The kernels: batch_kernels.hip (map / feature stages),
-// solve_kernels.hip (launch A / launch B of the trust-region loop), marg_kernels.hip (marginalization).
+// seg_vox.hip (the voxel filter of the local maps and of the pushed sweeps), solve_kernels.hip (launch A / launch B of the trust-region loop), marg_kernels.hip (marginalization).
 #include "est_batch.h"
 #include "../../include/lio_test_hooks.h"
 
@@ -44,11 +44,11 @@ void EstimatorBatch::Init() {
   win_.resize(B);
   for (size_t w = 0; w < B; ++w) { win_[w].e = m_[w]; m_[w]->AdoptStream(stream_); }
   const auto pin = [](auto &h, size_t n) { h.alloc(n, hipHostMallocDefault, true); };   // zero-filled; B >= 1: no empty allocation
-  pin(h_win_, B); pin(h_grid_, B); pin(h_vout_, B); pin(h_odom_, B); pin(h_bs_, B); pin(h_pb_, B); pin(h_st_, B); pin(h_mg_, B);
-  pin(h_prior_, B * ds_prior_mats_size(MARG_MAX_N)); pin(h_nconv_, 4); pin(h_seg_, 2 * B);
-  d_win_.reserve(B); d_grid_.reserve(B); d_vout_.reserve(B); d_odom_.reserve(B); d_bs_.reserve(B); d_pb_.reserve(B); d_st_.reserve(B); d_mg_.reserve(B);
-  range_overflow_.reserve(B); vparams_.reserve(B); nconv_.reserve(4); d_seg_.reserve(2 * B); d_layout_.reserve(B);
-  LIO_HIP(hipMemsetAsync(range_overflow_.p, 0, sizeof(int) * range_overflow_.cap, stream_));
+  pin(h_win_, B); pin(h_grid_, B); pin(h_odom_, B); pin(h_bs_, B); pin(h_pb_, B); pin(h_st_, B); pin(h_mg_, B);
+  pin(h_prior_, B * ds_prior_mats_size(MARG_MAX_N)); pin(h_nconv_, 4); pin(h_seg_, B);
+  d_win_.reserve(B); d_grid_.reserve(B); d_odom_.reserve(B); d_bs_.reserve(B); d_pb_.reserve(B); d_st_.reserve(B); d_mg_.reserve(B);
+  nconv_.reserve(4); d_seg_.reserve(B);
+  vox_.reserve(0, 2 * int(B), stream_);   // (the tables of a push with the map refresh on: no pinned allocation inside a call)
   LIO_HIP(hipMemsetAsync(d_mg_.p, 0, sizeof(DevMarg) * d_mg_.cap, stream_));
   // the scratch slab of a window (doubles)
   size_t o = 0;
@@ -177,7 +177,7 @@ void EstimatorBatch::StageDigest(int stage, unsigned long long *out) {
     unsigned long long h = 0;
     switch (stage) {
       case 0: {
-        const std::vector<float4> p = fetch(filtered_all_.p + bw.loc_off, size_t(G.n_filtered));
+        const std::vector<float4> p = fetch(filtered_all_.p + bw.vox.off, size_t(G.n_filtered));
         h = fnv1a(p.data(), size_t(G.n_filtered) * sizeof(float4), mix64(G.n_filtered));
         break;
       }
@@ -381,21 +381,20 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
       Wn.max_slots = e->BatchDescribe(bw);
     } else {
       std::memset(&bw, 0, sizeof(bw));
-      bw.inv_leaf = 1.f;
+      bw.vox.inv_leaf = 1.f;
     }
-    bw.loc_off = off; bw.loc_cap = round_up(std::max(bw.n_local, 1), 256); off += bw.loc_cap;
+    bw.vox.off = off; bw.vox.cap = round_up(std::max(bw.vox.n, 1), 256); off += bw.vox.cap;
     bw.slot_base = slot; slot += round_up(bw.n_slots, 16);
     for (int k = 0; k < bw.nstatic; ++k) { bw.fr[k].slot_off += bw.slot_base; max_M = std::max(max_M, bw.fr[k].M); q_static += bw.fr[k].M; }
     bw.newest.slot_off += bw.slot_base; q_newest += bw.newest.M;
     bw.part_off = part_rows; part_rows += bw.nb_round;
-    max_cap = std::max(max_cap, bw.loc_cap); max_slots = std::max(max_slots, bw.n_slots); max_static = std::max(max_static, bw.nstatic);
+    max_cap = std::max(max_cap, bw.vox.cap); max_slots = std::max(max_slots, bw.n_slots); max_static = std::max(max_static, bw.nstatic);
     max_nb = std::max(max_nb, bw.nb_round);
   }
   const size_t N = size_t(off);
   if (N > size_t(INT_MAX) / 2) throw std::runtime_error("EstimatorBatch: the batch's local maps exceed 2^30 points");
   local_all_.reserve(N, s); filtered_all_.reserve(N, s); sorted_all_.reserve(N, s);
-  keys_.reserve(N, s); keysb_.reserve(N, s); vals_.reserve(N, s); valsb_.reserve(N, s); ckeys_.reserve(N, s);
-  bounds_partial_.reserve(N / 256 * 8, s); tile_heads_.reserve(N / 256, s);
+  vox_.reserve(N, B, s);
   valid_all_.reserve(std::max(slot, 16), s); coef_all_.reserve(std::max(slot, 16), s); score_all_.reserve(std::max(slot, 16), s);
   odom_partials_.reserve(size_t(std::max(part_rows, 1)) * 28, s);
   const double t1 = now_ms();
@@ -406,27 +405,12 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
   LIO_HIP(hipMemsetAsync(nconv_.p, 0, sizeof(int), s));
   launch_bw_setup(d_win_.p, B, max_slots, valid_all_.p, d_odom_.p, nconv_.p, s);
   // The filter's order: 9-bit passes over the keys relative to each window's bounds (pass 0 converts the stored absolute keys on the fly
-  // and numbers the values); every window sorts its own range.  Three passes order 27 bits — 26 of key and "no point" above them — which
-  // is what a 200 m x 200 m x 25 m map at a 0.4 m leaf takes; the bounds are only known on the device, so the host goes by what each
-  // window's keys took in its previous solve (4 passes while unknown).  A window that outgrows the guess is flagged by
-  // the layout kernel and re-done by the single-window path.
+  // and numbers the values); every window sorts its own range.  The host goes by what each window's keys took in its previous solve
+  // (seg_vox.h: the pass rule); a window that outgrows the guess is flagged by the layout kernel and re-done by the single-window path.
   int vox_passes = 3;
-  for (int w = 0; w < B; ++w) if (win_[w].device && (win_[w].key_bits == 0 || win_[w].key_bits > 26)) vox_passes = 4;
-  launch_bw_concat_keys(d_win_.p, B, max_cap, local_all_.p, ckeys_.p, bounds_partial_.p, vparams_.p, d_layout_.p, range_overflow_.p,
-                        std::min(31, SS_MAX_BITS * vox_passes - 1), s);
-  const uint32_t *keys_sorted = nullptr, *vals_sorted = nullptr;
-  {
-    SegDesc *seg = h_seg_.p;
-    for (int w = 0; w < B; ++w) seg[w] = SegDesc{h_win_.p[w].loc_off, h_win_.p[w].n_local, 0};
-    const SegSortPlan plan = seg_sort_plan(seg, B, SS_MAX_BITS);
-    sort_hist_.reserve(std::max<size_t>(plan.hist_entries, 1), s);
-    LIO_HIP(hipMemcpyAsync(d_seg_.p, seg, sizeof(SegDesc) * B, hipMemcpyHostToDevice, s));
-    const SegSortPair sorted = seg_sort_passes(d_seg_.p, B, plan, ckeys_.p, nullptr, {keys_.p, vals_.p}, {keysb_.p, valsb_.p}, sort_hist_.p, SS_MAX_BITS, vox_passes,
-                                               d_layout_.p, s);
-    keys_sorted = sorted.keys; vals_sorted = sorted.vals;
-  }
-  launch_bw_vox_finish(d_win_.p, B, max_cap, local_all_.p, keys_sorted, vals_sorted, tile_heads_.p, filtered_all_.p, vparams_.p, range_overflow_.p, d_vout_.p, s);
-  LIO_HIP(hipMemcpyAsync(h_vout_.p, d_vout_.p, sizeof(BwVoxOut) * B, hipMemcpyDeviceToHost, s));
+  for (int w = 0; w < B; ++w) if (win_[w].device) vox_passes = std::max(vox_passes, SegVoxFilter::passes_for(win_[w].key_bits));
+  launch_bw_concat_keys(d_win_.p, B, max_cap, local_all_.p, vox_.keys(), vox_.partial(), vox_.flag(), s);
+  vox_.finish(&d_win_.p->vox, &h_win_.p->vox, sizeof(BatchWin), B, vox_passes, local_all_.p, filtered_all_.p, s);
   LIO_HIP(hipEventRecord(ev_[1], s));
   LIO_HIP(hipStreamSynchronize(s));
   const double t2 = now_ms();
@@ -438,15 +422,12 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
     Win &Wn = win_[w];
     BatchGrid &G = h_grid_.p[w];
     std::memset(&G, 0, sizeof(G));
-    const BwVoxOut &vo = h_vout_.p[w];
+    const VoxSegOut &vo = vox_.out(w);
     size_t ncells = 1;
     G.g.dims[0] = G.g.dims[1] = G.g.dims[2] = 1;
     G.g.inv_cell = 1.f;
-    {   // what the window's relative keys took: the next solve's guess for the number of sort passes
-      const int kb = bits_for(vo.params.divb[0]) + bits_for(vo.params.divb[1]) + bits_for(vo.params.divb[2]);
-      Wn.key_bits = vo.params.n_valid > 0 ? std::max(kb, 1) : Wn.key_bits;
-    }
-    if (Wn.device && (vo.params.overflow || vo.range_overflow)) Wn.device = false;   // PCL's own index / "leaf too small" / keys beyond the passes: the single-window path has those forms
+    if (const int kb = SegVoxFilter::bits_taken(vo.params)) Wn.key_bits = kb;   // the next solve's guess for the number of sort passes
+    if (Wn.device && (vo.params.overflow || vo.flagged)) Wn.device = false;   // PCL's own index / "leaf too small" / keys beyond the passes: the single-window path has those forms
     if (Wn.device && vo.count > 0) {
       ncells = grid_extent(G.g, vo.params.mn, vo.params.mx, knn_cell_edge(Wn.e->cfg_.min_match_sq_dis));
       if (ncells > (size_t(1) << 28)) { Wn.device = false; ncells = 1; G.g.dims[0] = G.g.dims[1] = G.g.dims[2] = 1; }
@@ -460,21 +441,21 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
   if (cell_total > size_t(INT_MAX)) throw std::runtime_error("EstimatorBatch: the batch's cell tables exceed 2^31 entries");
   cells_all_.reserve(cell_total, s);
   LIO_HIP(hipMemcpyAsync(d_grid_.p, h_grid_.p, sizeof(BatchGrid) * B, hipMemcpyHostToDevice, s));
-  launch_bw_cell_keys(d_win_.p, d_grid_.p, B, max_filtered, filtered_all_.p, ckeys_.p, s);
+  launch_bw_cell_keys(d_win_.p, d_grid_.p, B, max_filtered, filtered_all_.p, vox_.keys(), s);
   {
-    // a window's filtered points ordered by cell: as many 9-bit passes as the largest table's index needs
-    SegDesc *seg = h_seg_.p + B;
+    // a window's filtered points ordered by cell: as many 9-bit passes as the largest table's index needs, on the filter's sort scratch
+    // (the filter is done: the host has waited for it)
+    SegDesc *seg = h_seg_.p;
     int bits = 1;
     for (int w = 0; w < B; ++w) {
-      seg[w] = SegDesc{h_win_.p[w].loc_off, h_grid_.p[w].n_filtered, 0};
+      seg[w] = SegDesc{h_win_.p[w].vox.off, h_grid_.p[w].n_filtered, 0};
       bits = std::max(bits, bits_for(h_grid_.p[w].g.dims[0] * h_grid_.p[w].g.dims[1] * h_grid_.p[w].g.dims[2]));   // (at most 2^28 cells: checked above)
     }
     const int passes = std::max(1, (bits + SS_MAX_BITS - 1) / SS_MAX_BITS);
     const SegSortPlan plan = seg_sort_plan(seg, B, SS_MAX_BITS);
-    sort_hist_.reserve(std::max<size_t>(plan.hist_entries, 1), s);
-    LIO_HIP(hipMemcpyAsync(d_seg_.p + B, seg, sizeof(SegDesc) * B, hipMemcpyHostToDevice, s));
-    const SegSortPair sorted = seg_sort_passes(d_seg_.p + B, B, plan, ckeys_.p, nullptr, {keys_.p, vals_.p}, {keysb_.p, valsb_.p}, sort_hist_.p, SS_MAX_BITS, passes,
-                                               nullptr, s);
+    uint32_t *hist = vox_.hist(plan.hist_entries, s);
+    LIO_HIP(hipMemcpyAsync(d_seg_.p, seg, sizeof(SegDesc) * B, hipMemcpyHostToDevice, s));
+    const SegSortPair sorted = seg_sort_passes(d_seg_.p, B, plan, vox_.keys(), nullptr, vox_.ping(), vox_.pong(), hist, SS_MAX_BITS, passes, nullptr, s);
     launch_bw_cell_table(d_win_.p, d_grid_.p, B, max_filtered, filtered_all_.p, sorted.keys, sorted.vals, cells_all_.p, sorted_all_.p, s);
   }
   LIO_HIP(hipEventRecord(ev_[2], s));
@@ -743,7 +724,7 @@ void EstimatorBatch::PushFrames(const lio_est_frame *fr) {
   plans_.resize(size_t(B));
   push_.begin(2 * B);
   std::vector<int> cloud(size_t(2 * B), -1);   // the chain's cloud of window w's surf [2 w] and corner [2 w + 1] sweep
-  // three 9-bit passes when every window's clouds took at most 26 bits in its previous push, four while unknown (Solve: the local maps' rule)
+  // by what every window's clouds took in its previous push (seg_vox.h: the pass rule, as for Solve's local maps)
   int passes = 3;
   for (int w = 0; w < B; ++w) {
     Estimator *e = m_[size_t(w)];
@@ -756,7 +737,7 @@ void EstimatorBatch::PushFrames(const lio_est_frame *fr) {
       if (pl.corner_cloud)
         cloud[size_t(2 * w + 1)] = push_.add(f.corner_xyzi, f.n_corner, e->cfg_.corner_filter_size, pl.deskew, pl.q, pl.p, 10.f, pl.corner_cloud->buf.p);
       cloud[size_t(2 * w)] = push_.add(f.surf_xyzi, f.n_surf, e->cfg_.surf_filter_size, pl.deskew, pl.q, pl.p, 10.f, pl.fresh.buf.p);
-      if (win_[size_t(w)].push_bits == 0 || win_[size_t(w)].push_bits > 26) passes = 4;
+      passes = std::max(passes, SegVoxFilter::passes_for(win_[size_t(w)].push_bits));
     } else {   // both de-skew switches off (Estimator.cc:474-480): the clouds go into the handle's buffers as they are
       if (pl.corner_cloud) {
         if (f.n_corner) LIO_HIP(hipMemcpyAsync(pl.corner_cloud->buf.p, f.corner_xyzi, f.n_corner * sizeof(float4), hipMemcpyHostToDevice, s));
@@ -768,7 +749,7 @@ void EstimatorBatch::PushFrames(const lio_est_frame *fr) {
       ++push_stats_[2];
     }
   }
-  bool waited = push_.run(passes, s);
+  bool waited = push_.run(vox_, passes, s);
   if (!waited && push_stats_[2]) { LIO_HIP(hipStreamSynchronize(s)); waited = true; }   // the caller may reuse its buffers on return
   push_stats_[3] = waited ? 1 : 0;
   push_stats_[4] = push_.clouds() ? passes : 0;
@@ -779,7 +760,7 @@ void EstimatorBatch::PushFrames(const lio_est_frame *fr) {
     for (int k = 1; k >= 0; --k) {   // (corner, then surf: PushFrame's order)
       const int i = cloud[size_t(2 * w + k)];
       if (i < 0) continue;
-      const BpVoxOut &o = push_.out(i);
+      const VoxSegOut &o = vox_.out(i);
       const size_t n = k ? pl.n_corner : pl.n_surf;
       size_t count = size_t(o.count);
       if (o.flagged || o.params.overflow) {
@@ -791,7 +772,7 @@ void EstimatorBatch::PushFrames(const lio_est_frame *fr) {
       } else {
         ++push_stats_[0];
       }
-      if (o.params.n_valid > 0) bits = std::max(bits, std::max(1, bits_for(o.params.divb[0]) + bits_for(o.params.divb[1]) + bits_for(o.params.divb[2])));
+      bits = std::max(bits, SegVoxFilter::bits_taken(o.params));
       if (k) pl.corner_cloud->n = count;
       else pl.fresh.n = count;
     }
@@ -818,10 +799,7 @@ void EstimatorBatch::SlideWindows() {
     BpSlide &S = h_slide_.p[w];
     std::memset(static_cast<void *>(&S), 0, sizeof(S));
     if (!concat[size_t(w)]) continue;
-    for (int k = 0; k < 2; ++k) {
-      const ConcatSeg &c = ca[size_t(w)].seg[k];
-      S.seg[k] = BwSeg{c.src, c.n, c.dst_off, c.identity, c.set_intensity, c.intensity, c.tf};
-    }
+    S.seg[0] = ca[size_t(w)].seg[0]; S.seg[1] = ca[size_t(w)].seg[1];
     S.total = ca[size_t(w)].total;
     S.dst = e->slide_dst();
     max_total = std::max(max_total, S.total);

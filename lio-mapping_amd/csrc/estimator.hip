@@ -1309,13 +1309,11 @@ int Estimator::BatchDescribe(BatchWin &bw) {
   FusePivotOnce();
   const WindowPlan pl = PlanWindow(W_ - Wo_);
   std::memset(&bw, 0, sizeof(bw));
-  bw.inv_leaf = 1.0f / cfg_.surf_filter_size;
+  bw.vox.inv_leaf = 1.0f / cfg_.surf_filter_size;
   bw.min_match_sq_dis = cfg_.min_match_sq_dis; bw.min_plane_dis = cfg_.min_plane_dis;
   bw.keep = pl.keep_mult > 1 ? 1 : 0;
-  for (; bw.nseg < pl.nseg; ++bw.nseg) {
-    const ConcatSeg &c = pl.seg[bw.nseg];
-    bw.seg[bw.nseg] = BwSeg{c.src, c.n, c.dst_off, c.identity, c.set_intensity, c.intensity, c.tf};
-  }
+  std::copy(pl.seg, pl.seg + pl.nseg, bw.seg);   // (BatchEligible: at most LIO_BW_MAX_SEG)
+  bw.nseg = pl.nseg;
   for (int i = pl.pivot + 1; i <= W_; ++i) {
     const int k = (i == W_) ? LIO_BW_MAX_STATIC : bw.nstatic;
     std::memcpy(bw.tf[k], pl.tf[i], sizeof(bw.tf[k]));
@@ -1323,7 +1321,7 @@ int Estimator::BatchDescribe(BatchWin &bw) {
     f.stack = stacks_[i].buf.p; f.M = int(stacks_[i].n); f.slot_off = slot_off_[i]; f.tf_index = k;
     if (i < W_) ++bw.nstatic;
   }
-  bw.n_local = pl.n_local;
+  bw.vox.n = pl.n_local;
   bw.n_slots = int(total_slots_);
   bw.nb_round = bw.newest.M > 0 ? bw_round_blocks(bw.newest.M) : 0;
   return pl.max_slots;

@@ -39,8 +39,8 @@ LIO_HD int bits_for(int extent) { int b = 0; while ((1 << b) < extent) ++b; retu
 
 // The layout of a cloud with points whose stored keys span the cells minb .. minb + divb - 1 (VoxParams): floor(x inv_leaf) is monotone in x,
 // so the smallest stored cell coordinate of the cloud is the bound's.  False: the relative keys take more than max_bits — what the caller's
-// passes order, minus one ("no point" sits one above the real keys).  Stated once for the local maps of a batched solve (k_bw_key_layout)
-// and the clouds of a batched push (k_bp_key_layout).
+// passes order, minus one ("no point" sits one above the real keys).  Called by the segmented filter's layout kernel (seg_vox.hip:
+// k_seg_vox_layout), for the local maps of a batched solve and the clouds of a batched push alike.
 LIO_HD bool vox_key_layout(const int minb[3], const int divb[3], int max_bits, KeyLayout &L) {
   L.mx = minb[0] + 1024; L.my = minb[1] + 1024; L.mz = minb[2] + 256;
   const int bx = bits_for(divb[0]), by = bits_for(divb[1]), bz = bits_for(divb[2]);

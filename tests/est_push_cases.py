@@ -178,6 +178,21 @@ def beyond_the_key(seed=17):
     return c
 
 
+SHARED_SWEEP = 257         # points of every sweep of the shared-filter case: two tiles of 256, the second with one point
+
+
+def beyond_the_abs_range(seed=29):
+    """a sweep with one return 500 m out along x: cell 1250 of a 0.4 m leaf, outside the filter's absolute key (|x| cells < 1024)"""
+    c = room(SHARED_SWEEP, seed)
+    c[100, 0:3] = (500.0, 0.5, 0.5)
+    return c
+
+
+def stray_above(stack):
+    """`stack` with a return 300 m up behind it (tests/test_gpu_batch.py: the window beyond the filter's key range, z cells < 255)"""
+    return np.ascontiguousarray(np.vstack([stack, np.array([[0.5, 0.5, 300.0, stack[0, 3]]], np.float32)]))
+
+
 def pcl_overflow(seed=19):
     """returns at +-2e5 m on every axis: (4e5 / 0.4 + 1)^3 voxels pass INT_MAX — PCL's "leaf size is too small": output = input"""
     c = room(400, seed)

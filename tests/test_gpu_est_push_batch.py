@@ -191,6 +191,56 @@ def test_map_refresh_and_full_cloud_ride_the_chain(hip):
     batch.close()
 
 
+def test_push_and_solve_leave_nothing_behind_in_the_filter_they_share(hip):
+    """Solve's local maps and PushFrames' sweeps go through the part's one SegVoxFilter: a flag or a table that one leaves behind would reach the
+    other.  Two windows with the map refresh on (four clouds, more than windows), sweeps of 257 points.  (a) a push whose first surf sweep has a
+    return beyond the absolute key range: one cloud redone; (b) the solve behind it takes both windows on the device; (c) a solve whose first local
+    map lies beyond the key range, then a push of ordinary sweeps: all four through the chain.  S: single handles with device_solve = 1."""
+    n = cases.SHARED_SWEEP
+
+    def make(device_solve):
+        return [cases.window(hip, 4, 2, seed, refresh=True, optex=0, device_solve=device_solve) for seed in (3, 5)]
+
+    def sweeps(k, first_surf=None):
+        return [item(k, surf=cases.room(n, 40 + 4 * w) if (w or first_surf is None) else first_surf, corner=cases.room(n, 41 + 4 * w)) for w in range(2)]
+
+    def push(k, items):
+        for e in S + B:
+            cases.imu(e, k)
+        for e, it in zip(S, items):
+            cases.push_single(e, it)
+        batch.push_frames(items)
+        return batch.push_stats()
+
+    S, B = make(1), make(0)
+    batch = capi.EstimatorBatch(hip, B)
+    assert_twins(S, B, "as built")
+    # (a)
+    st = push(5, sweeps(5, cases.beyond_the_abs_range()))
+    assert (st["chain"], st["redone"], st["as_is"], st["host_waits"]) == (3, 1, 0, 1), st
+    assert_twins(S, B, "(a) push")
+    # (b)
+    _same_reports([e.solve() for e in S], batch.solve(), "(b)")
+    assert int(batch.clock()["n_device"]) == 2, batch.clock()
+    assert_twins(S, B, "(b) solve", prior=True)
+    # (c)
+    for e in S:
+        e.slide()
+    batch.slide()
+    assert_twins(S, B, "(c) slide", prior=True)
+    pivot = B[0].W - 2
+    stray = cases.stray_above(B[0].get_surf_stack(pivot))
+    for e in (S[0], B[0]):
+        e.set_surf_stack(pivot, stray)
+    _same_reports([e.solve() for e in S], batch.solve(), "(c)")
+    assert int(batch.clock()["n_device"]) == 1, batch.clock()   # (window 0 was flagged: this solve did raise what the next push must not see)
+    assert_twins(S, B, "(c) solve", prior=True)
+    st = push(6, sweeps(6))
+    assert (st["chain"], st["redone"], st["as_is"], st["host_waits"]) == (4, 0, 0, 1), st
+    assert_twins(S, B, "(c) push", prior=True)
+    batch.close()
+
+
 def test_two_parts_give_the_bits_of_one(hip):
     """A batch of four with the option "parts" = 2 against its twin with "parts" = 1: equal bits, two host waits reported."""
     seeds = (3, 5, 7, 9)

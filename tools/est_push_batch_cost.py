@@ -15,7 +15,8 @@ without the solve (push + slide alone).  Medians with min - max over the steps a
 Criteria (orderings against the host route of the same run): at B = 64 and 512 the new call's median is below the host route's fastest step;
 at B = 1 it is not above the host route's slowest step.
 --parent-lib PATH times B x lio_est_push_frame + B x lio_est_slide_window ALONE, this tree against another build of the product (the parent
-commit's liblio_hip.so), in one process: this tree's median not above the other build's slowest step.
+commit's liblio_hip.so), in one process: this tree's median not above the other build's slowest step.  Where that build has the batched calls
+too, they are timed the same way (push + slide alone, and the composite), every run listed.
 --only-device runs the new call alone (a kernel trace of it without the host route's launches in it).
 """
 import argparse
@@ -201,6 +202,37 @@ def measure_parent(hip, parent, kind, ds, clouds, B, steps):
                 holds=bool(np.median(t_mine) <= np.max(t_theirs)))
 
 
+def measure_parent_batched(hip, parent, kind, ds, clouds, B, steps):
+    """the batched calls themselves — lio_est_batch_push_frames + _slide_windows alone, and lio_est_batch_process_laser_odom — this tree against
+    another build that has them, alternating in one process; equal bits asserted at every step"""
+    W, Wo, _ = WINDOWS[kind]
+    k = W + 1 + EXTRA
+    sets = []
+    for lib in (hip, parent):
+        src = source_window(lib, ds, clouds, kind, W, Wo)
+        sets.append(Stepper(lib, clones(lib, ds, kind, W, Wo, src, B), ds.frames[k], clouds[k][0], clouds[k][1]))
+    mine, theirs = sets
+    out = dict(what="batched_calls_vs_parent_build", kind=kind, B=B, steps_measured=steps)
+    for solve in (True, False):
+        t_mine, t_theirs = [], []
+        for s in range(WARMUP + steps):
+            mine.prepare(), theirs.prepare()
+            if s % 2:
+                a, b = mine.batched(solve), theirs.batched(solve)
+            else:
+                b, a = theirs.batched(solve), mine.batched(solve)
+            for j in sorted({0, B // 2, B - 1}):
+                assert np.array_equal(mine.words(j, solve), theirs.words(j, solve)), (kind, B, s, j, solve)
+            if s >= WARMUP:
+                t_mine.append(a), t_theirs.append(b)
+        out["step" if solve else "push_slide"] = dict(this_ms=_stats(t_mine), parent_ms=_stats(t_theirs), this_runs=[round(v, 4) for v in t_mine],
+                                                      parent_runs=[round(v, 4) for v in t_theirs], holds=bool(np.median(t_mine) <= np.max(t_theirs)))
+    out["push_stats"] = mine.batch.push_stats()
+    for st in sets:
+        st.batch.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=16)
@@ -234,6 +266,9 @@ def main():
             for B in [int(b) for b in args.parent_batches.split(",") if b]:
                 results.append(measure_parent(hip, parent, kind, ds, clouds, B, args.steps))
                 print(json.dumps(results[-1]), flush=True)
+                if hasattr(parent.dll, "lio_est_batch_push_frames"):
+                    results.append(measure_parent_batched(hip, parent, kind, ds, clouds, B, args.steps))
+                    print(json.dumps(results[-1]), flush=True)
     if args.out:
         with open(args.out, "w") as f:
             json.dump(results, f, indent=1)
