@@ -14,6 +14,7 @@
 
 #include "cloud_kernels.h"
 #include "hmath.h"
+#include "knn_merge.h"
 
 #if defined(__HIPCC__)
 namespace lio {
@@ -514,6 +515,10 @@ __device__ __forceinline__ void knn_insert(unsigned long long key, int j, unsign
 //      register arrays), i.e. ceil(T / (LPQ * KNN_BATCH)) round trips (3-4 at ~100 candidates);
 //   3. xor-shuffle merge of the LPQ partial lists.
 // The candidate SET and the total order (d2, original index) are unchanged, so the result is bit-identical to the serial walk.
+// With four or more lanes per query and K = 5 nothing goes through knn_insert: a trip's four candidates enter by ONE knn_merge4 and a
+// butterfly stage is ONE knn_merge5 (knn_merge.h: fixed networks — ten compare-exchanges and four selects for a trip, five and five for
+// a stage, against the sixteen and twenty guarded compare-exchanges of four and five insertions; docs/knn_merge.md has the counts and
+// the kernel times).  The five smallest of a set of distinct keys and their order are unique, so the lists keep their bits.
 template <int K, int LPQ>
 __device__ inline void knn_scan_group(const Vec3<float> &q, bool active, int sub, const float4 *__restrict__ map,
                                       const int *__restrict__ cells, const GridDesc &g, float (&bd)[K], int (&bi)[K], int (&bj)[K]) {
@@ -619,14 +624,31 @@ __device__ inline void knn_scan_group(const Vec3<float> &q, bool active, int sub
           jj[b] = f < T ? j : -1;
           p[b] = f < T ? map[j] : make_float4(0, 0, 0, 0);
         }
+        if constexpr (K == 5 && KNN_BATCH == 4) {
+          // the trip's four candidates in one merge; a position past the list's end carries the sentinel's key (it cannot enter, like a
+          // NaN distance, whose key lies above the sentinel's), and the wave skips the merge when no lane holds a key below its fifth
+          unsigned long long ck[KNN_BATCH];
+          bool any = false;
 #pragma unroll
-        for (int b = 0; b < KNN_BATCH; ++b) {
-          if (jj[b] < 0) continue;
-          float ddx = p[b].x - q.x, ddy = p[b].y - q.y, ddz = p[b].z - q.z;
-          float d = ddx * ddx;
-          d += ddy * ddy;
-          d += ddz * ddz;
-          knn_insert<K>(knn_key(d, __float_as_int(p[b].w)), jj[b], bk, bj);
+          for (int b = 0; b < KNN_BATCH; ++b) {
+            float ddx = p[b].x - q.x, ddy = p[b].y - q.y, ddz = p[b].z - q.z;
+            float d = ddx * ddx;
+            d += ddy * ddy;
+            d += ddz * ddz;
+            ck[b] = jj[b] < 0 ? knn_key(INFINITY, INT_MAX) : knn_key(d, __float_as_int(p[b].w));
+            any = any || ck[b] < bk[K - 1];
+          }
+          if (any) knn_merge4(bk, bj, ck, jj);
+        } else {
+#pragma unroll
+          for (int b = 0; b < KNN_BATCH; ++b) {
+            if (jj[b] < 0) continue;
+            float ddx = p[b].x - q.x, ddy = p[b].y - q.y, ddz = p[b].z - q.z;
+            float d = ddx * ddx;
+            d += ddy * ddy;
+            d += ddz * ddz;
+            knn_insert<K>(knn_key(d, __float_as_int(p[b].w)), jj[b], bk, bj);
+          }
         }
       }
     }
@@ -641,8 +663,12 @@ __device__ inline void knn_scan_group(const Vec3<float> &q, bool active, int sub
       ok[k] = (static_cast<unsigned long long>(hi) << 32) | lo;
       oj[k] = __shfl_xor(bj[k], m, 64);
     }
+    if constexpr (K == 5 && LPQ >= 4) {
+      knn_merge5(bk, bj, ok, oj);
+    } else {
 #pragma unroll
-    for (int c = 0; c < K; ++c) knn_insert<K>(ok[c], oj[c], bk, bj);
+      for (int c = 0; c < K; ++c) knn_insert<K>(ok[c], oj[c], bk, bj);
+    }
   }
 #pragma unroll
   for (int k = 0; k < K; ++k) { bd[k] = __uint_as_float(static_cast<unsigned int>(bk[k] >> 32)); bi[k] = int(static_cast<unsigned int>(bk[k])); }
