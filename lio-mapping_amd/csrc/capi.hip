@@ -9,6 +9,7 @@
 #include "../../include/lio_test_hooks.h"
 #include "../../include/lio_ext.h"
 #include "../../include/lio_full_cloud.h"
+#include "../../include/lio_est_from_odom.h"
 #include "../../include/lio_odom_batch.h"
 #include "../../include/lio_frontend_batch.h"
 #include "../../include/lio_map_batch.h"
@@ -1526,6 +1527,59 @@ int lio_est_batch_push_stats(const lio_est_batch *h, int *out8) {
   if (!h || !out8) return LIO_ERR_ARG;
   if (!batch_live(h)) return LIO_ERR_STATE;
   h->parts->PushStats(out8);
+  return LIO_OK;
+}
+// ---- include/lio_est_from_odom.h: the windows' sweeps taken from the odometry handles on the device.  Every refusal comes before a window, a
+// map or the device is touched, in the header's order; the lease on the processors is held until the parts, which read their clouds, have
+// returned synchronised.  f(the sources, one per window) runs the call.
+static int est_from_odom(lio_est_batch *h, lio_odom *const *odom, lio_pp *const *pp, const double *stamps, bool need_T, const void *T, bool composite,
+                         const char *who, const std::function<int(const EstOdomSource *)> &f) {
+  if (!h || !odom || !stamps || (need_T && !T)) return LIO_ERR_ARG;
+  const int n = batch_live(h) ? h->parts->size() : 0;
+  for (int w = 0; w < n; ++w)
+    if (!odom[w]) return LIO_ERR_ARG;
+  if (!batch_live(h) || !h->parts->PushReady()) return LIO_ERR_STATE;
+  for (int w = 0; w < n; ++w) {
+    if (composite && !h->members[size_t(w)]->e->cfg_.imu_factor) return LIO_ERR_STATE;   // (as lio_est_process_compact)
+    if (!odom[w]->o->processed()) return LIO_ERR_STATE;                                  // no sweep to hand over
+  }
+  return guarded([&] {
+    const PpLease lease(pp, size_t(n), who, true, true);
+    std::vector<EstOdomSource> src(static_cast<size_t>(n));
+    size_t total = 0;   // push_batch_check's limits, the full cloud included
+    for (int w = 0; w < n; ++w) {
+      const OdometryDev::DeviceView v = odom[w]->o->View();
+      EstOdomSource &S = src[size_t(w)];
+      S = EstOdomSource{{v.last[0], v.last[1]}, {v.n_last[0], v.n_last[1]}, odom[w]->o->transform_sum_, MapFullSource{}};
+      if (lease.pp(size_t(w))) {
+        S.full.set = true;
+        lease.pp(size_t(w))->DeviceRings(lease.sweep(size_t(w)), S.full.pts, S.full.n);
+        S.full.to_end = v.to_end; S.full.time_factor = v.time_factor; S.full.no_deskew = v.no_deskew;
+      }
+      if (S.n_last[0] > kMaxCloudPoints || S.n_last[1] > kMaxCloudPoints || S.full.n > kMaxCloudPoints) return int(LIO_ERR_CAPACITY);
+      total += S.n_last[0] + S.n_last[1] + S.full.n + 768;
+      if (total > (size_t(1) << 30)) return int(LIO_ERR_CAPACITY);
+    }
+    if (composite) for (lio_est *m : h->members) est_map(m);   // (behind the last refusal, as lio_est_process_compact creates it)
+    return int(f(src.data()));
+  });
+}
+int lio_est_batch_push_frames_from_odom(lio_est_batch *h, lio_odom *const *odom, lio_pp *const *pp, const lio_transform_f *T_in, const double *stamps) {
+  return est_from_odom(h, odom, pp, stamps, true, T_in, false, "lio_est_batch_push_frames_from_odom", [&](const EstOdomSource *src) {
+    h->parts->PushFramesFrom(src, T_in, stamps);
+    return LIO_OK;
+  });
+}
+int lio_est_batch_process_compact_from_odom(lio_est_batch *h, lio_odom *const *odom, lio_pp *const *pp, const double *stamps, lio_transform_f *T_out,
+                                            lio_solve_report *reps) {
+  return est_from_odom(h, odom, pp, stamps, false, nullptr, true, "lio_est_batch_process_compact_from_odom", [&](const EstOdomSource *src) {
+    return h->parts->ProcessCompactFrom(src, stamps, T_out, reps) ? LIO_OK : LIO_ERR_STATE;
+  });
+}
+int lio_est_batch_from_odom_stats(const lio_est_batch *h, int *out8) {
+  if (!h || !out8) return LIO_ERR_ARG;
+  if (!batch_live(h)) return LIO_ERR_STATE;
+  h->parts->FromOdomStats(out8);
   return LIO_OK;
 }
 int lio_est_batch_sync(lio_est_batch *h) {

@@ -717,34 +717,77 @@ int EstimatorBatch::Solve(lio_solve_report *reps) {
 // Estimator::PushFrame of every member with the device work of all of them in one chain (est_push.h): PushFrameBegin per window, the clouds
 // that are filtered through the chain (one wait), a flagged cloud through its handle's own filter, PushFrameEnd per window.
 void EstimatorBatch::PushFrames(const lio_est_frame *fr) {
+  std::vector<PushInput> in(static_cast<size_t>(size()));
+  for (int w = 0; w < size(); ++w) {
+    const lio_est_frame &f = fr[w];
+    in[size_t(w)] = PushInput{Rigidf(Quat<float>(f.transform_in.q[3], f.transform_in.q[0], f.transform_in.q[1], f.transform_in.q[2]),
+                                     Vec3<float>(f.transform_in.p[0], f.transform_in.p[1], f.transform_in.p[2])),
+                              f.surf_xyzi, f.corner_xyzi, f.n_surf, f.n_corner, f.stamp, nullptr};
+  }
+  PushAll(in.data(), false);
+}
+
+// The device-fed pushes (include/lio_est_from_odom.h).  composite: the message's third block of ProcessCompactData — a window with its full cloud
+// on takes the given one or, given none, has it cleared; in the push form such a window keeps what it has.
+void EstimatorBatch::PushFrom(const EstOdomSource *src, const Rigidf *T_in, const double *stamps, bool composite) {
+  const int B = size();
+  std::vector<PushInput> in(static_cast<size_t>(B));
+  std::vector<MapFullSource> full(size_t(B), MapFullSource{});
+  for (int w = 0; w < B; ++w) {
+    Estimator *e = m_[size_t(w)];
+    const EstOdomSource &S = src[w];
+    if (e->full_cloud()) {
+      if (S.full.set) full[size_t(w)] = S.full;
+      else if (composite) full[size_t(w)].set = true;   // an empty third block: n = 0 clears it
+    }
+    in[size_t(w)] = PushInput{T_in[w], reinterpret_cast<const float *>(S.last[1]), reinterpret_cast<const float *>(S.last[0]), S.n_last[1], S.n_last[0], stamps[w],
+                              &full[size_t(w)]};
+  }
+  PushAll(in.data(), true);
+}
+void EstimatorBatch::PushFramesFrom(const EstOdomSource *src, const lio_transform_f *T_in, const double *stamps) {
+  std::vector<Rigidf> T(static_cast<size_t>(size()));
+  for (int w = 0; w < size(); ++w)
+    T[size_t(w)] = Rigidf(Quat<float>(T_in[w].q[3], T_in[w].q[0], T_in[w].q[1], T_in[w].q[2]), Vec3<float>(T_in[w].p[0], T_in[w].p[1], T_in[w].p[2]));
+  PushFrom(src, T.data(), stamps, false);
+}
+
+// Estimator::PushFrame of every member, the sweeps where `in` says (on_device: no cloud goes up, and the launch that takes the sweeps writes the
+// maps' full clouds too, in front of PushFrameEnd's PushFull)
+void EstimatorBatch::PushAll(const PushInput *in, bool on_device) {
   const int B = size();
   hipStream_t s = stream_;
   for (int &v : push_stats_) v = 0;
+  if (on_device) for (int &v : from_stats_) v = 0;
   plans_.clear();
   plans_.resize(size_t(B));
-  push_.begin(2 * B);
+  push_.begin(2 * B, on_device ? B : 0, on_device);
+  const hipMemcpyKind as_is_kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   std::vector<int> cloud(size_t(2 * B), -1);   // the chain's cloud of window w's surf [2 w] and corner [2 w + 1] sweep
   // by what every window's clouds took in its previous push (seg_vox.h: the pass rule, as for Solve's local maps)
   int passes = 3;
   for (int w = 0; w < B; ++w) {
     Estimator *e = m_[size_t(w)];
     PushPlan &pl = plans_[size_t(w)];
-    const lio_est_frame &f = fr[w];
-    const Rigidf T(Quat<float>(f.transform_in.q[3], f.transform_in.q[0], f.transform_in.q[1], f.transform_in.q[2]),
-                   Vec3<float>(f.transform_in.p[0], f.transform_in.p[1], f.transform_in.p[2]));
-    e->PushFrameBegin(T, f.n_surf, f.n_corner, f.stamp, pl);
+    const PushInput &f = in[w];
+    if (on_device && f.full && f.full->set) {   // lio_map_set_full_cloud, the points written by the chain's launch (Estimator::ProcessCompact: SetFullCloud first)
+      const MapFullSource &F = *f.full;
+      if (float4 *dst = e->map_->FullTake(F.n, s)) push_.add_full(BpFull{F.pts, dst, int(F.n), F.to_end, F.time_factor, F.no_deskew});
+      ++from_stats_[2];
+    }
+    e->PushFrameBegin(f.transform_in, f.n_surf, f.n_corner, f.stamp, pl);
     if (pl.filter) {
       if (pl.corner_cloud)
-        cloud[size_t(2 * w + 1)] = push_.add(f.corner_xyzi, f.n_corner, e->cfg_.corner_filter_size, pl.deskew, pl.q, pl.p, 10.f, pl.corner_cloud->buf.p);
-      cloud[size_t(2 * w)] = push_.add(f.surf_xyzi, f.n_surf, e->cfg_.surf_filter_size, pl.deskew, pl.q, pl.p, 10.f, pl.fresh.buf.p);
+        cloud[size_t(2 * w + 1)] = push_.add(f.corner, f.n_corner, e->cfg_.corner_filter_size, pl.deskew, pl.q, pl.p, 10.f, pl.corner_cloud->buf.p);
+      cloud[size_t(2 * w)] = push_.add(f.surf, f.n_surf, e->cfg_.surf_filter_size, pl.deskew, pl.q, pl.p, 10.f, pl.fresh.buf.p);
       passes = std::max(passes, SegVoxFilter::passes_for(win_[size_t(w)].push_bits));
     } else {   // both de-skew switches off (Estimator.cc:474-480): the clouds go into the handle's buffers as they are
       if (pl.corner_cloud) {
-        if (f.n_corner) LIO_HIP(hipMemcpyAsync(pl.corner_cloud->buf.p, f.corner_xyzi, f.n_corner * sizeof(float4), hipMemcpyHostToDevice, s));
+        if (f.n_corner) LIO_HIP(hipMemcpyAsync(pl.corner_cloud->buf.p, f.corner, f.n_corner * sizeof(float4), as_is_kind, s));
         pl.corner_cloud->n = f.n_corner;
         ++push_stats_[2];
       }
-      if (f.n_surf) LIO_HIP(hipMemcpyAsync(pl.fresh.buf.p, f.surf_xyzi, f.n_surf * sizeof(float4), hipMemcpyHostToDevice, s));
+      if (f.n_surf) LIO_HIP(hipMemcpyAsync(pl.fresh.buf.p, f.surf, f.n_surf * sizeof(float4), as_is_kind, s));
       pl.fresh.n = f.n_surf;
       ++push_stats_[2];
     }
@@ -753,6 +796,7 @@ void EstimatorBatch::PushFrames(const lio_est_frame *fr) {
   if (!waited && push_stats_[2]) { LIO_HIP(hipStreamSynchronize(s)); waited = true; }   // the caller may reuse its buffers on return
   push_stats_[3] = waited ? 1 : 0;
   push_stats_[4] = push_.clouds() ? passes : 0;
+  if (on_device) { from_stats_[0] = push_.clouds(); from_stats_[1] = push_stats_[2]; from_stats_[3] = push_.uploads(); }
   for (int w = 0; w < B; ++w) {
     Estimator *e = m_[size_t(w)];
     PushPlan &pl = plans_[size_t(w)];
@@ -814,9 +858,28 @@ void EstimatorBatch::SlideWindows() {
 
 // Estimator::ProcessLaserOdom (Estimator.cc:430-774) of initialised members: push, solve, the map refresh (:703-708), slide
 bool EstimatorBatch::ProcessLaserOdom(const lio_est_frame *fr, lio_solve_report *reps) {
-  const int B = size();
   for (Estimator *e : m_) ++e->laser_odom_recv_count_;
   PushFrames(fr);
+  return SolveRefreshSlide(reps);
+}
+// Estimator::ProcessCompact (Estimator.cc:776-856) of initialised members, the message never built: the prediction and transform_sum_
+// (CompactPredict), then ProcessLaserOdom with the sweeps and the third block taken on the device
+bool EstimatorBatch::ProcessCompactFrom(const EstOdomSource *src, const double *stamps, lio_transform_f *T_out, lio_solve_report *reps) {
+  const int B = size();
+  std::vector<Rigidf> T(static_cast<size_t>(B));
+  for (int w = 0; w < B; ++w) {
+    T[size_t(w)] = m_[size_t(w)]->CompactPredict(src[w].transform_sum);
+    if (T_out) {
+      const Rigidf &t = T[size_t(w)];
+      T_out[w] = lio_transform_f{{t.rot.x, t.rot.y, t.rot.z, t.rot.w}, {t.pos.x, t.pos.y, t.pos.z}};
+    }
+  }
+  for (Estimator *e : m_) ++e->laser_odom_recv_count_;
+  PushFrom(src, T.data(), stamps, true);
+  return SolveRefreshSlide(reps);
+}
+bool EstimatorBatch::SolveRefreshSlide(lio_solve_report *reps) {
+  const int B = size();
   Solve(reps);
   bool ok = true;
   for (int w = 0; w < B; ++w) {
@@ -896,6 +959,20 @@ bool BatchParts::ProcessLaserOdom(const lio_est_frame *frames, lio_solve_report 
   std::atomic<int> bad{0};
   ForParts([&](EstimatorBatch &b, int w0) { if (!b.ProcessLaserOdom(frames + w0, reps ? reps + w0 : nullptr)) bad.store(1); });
   return !bad.load();
+}
+void BatchParts::PushFramesFrom(const EstOdomSource *src, const lio_transform_f *T_in, const double *stamps) {
+  ForParts([&](EstimatorBatch &b, int w0) { b.PushFramesFrom(src + w0, T_in + w0, stamps + w0); });
+}
+bool BatchParts::ProcessCompactFrom(const EstOdomSource *src, const double *stamps, lio_transform_f *T_out, lio_solve_report *reps) {
+  std::atomic<int> bad{0};
+  ForParts([&](EstimatorBatch &b, int w0) {
+    if (!b.ProcessCompactFrom(src + w0, stamps + w0, T_out ? T_out + w0 : nullptr, reps ? reps + w0 : nullptr)) bad.store(1);
+  });
+  return !bad.load();
+}
+void BatchParts::FromOdomStats(int out[8]) const {
+  for (int k = 0; k < 8; ++k) out[k] = 0;
+  for (const auto &b : b_) if (b) for (int k = 0; k < 8; ++k) out[k] += b->from_odom_stats()[k];
 }
 void BatchParts::PushStats(int out[8]) const {
   for (int k = 0; k < 8; ++k) out[k] = 0;

@@ -11,6 +11,10 @@
 //                                straight into the HANDLE's stack buffer, one copy of the output table
 //   one host wait
 //
+// Device-fed form (include/lio_est_from_odom.h): a cloud whose points already lie in device memory (an odometry's last_corner_ / last_surf_) has
+// its pointer in the record and no range of the staging array; k_bp_take_keys_dev reads it where it lies, and the same launch writes the full
+// clouds of the call (BpFull: a processor's ring cloud through the odometry's TransformToEnd into a map's full cloud).  No upload per cloud.
+//
 // The filter is the EstimatorBatch's one SegVoxFilter; what is the chain's own is here: the staging and input arrays, the records, the uploads.
 // A cloud the filter cannot take (keys beyond the absolute range or beyond what the passes order, PCL's "leaf size too small") comes back
 // flagged and is left to the handle's own VoxelGridDev, which reads input(i).
@@ -29,6 +33,18 @@ struct BpCloud {
   int deskew;             // TransformToEnd by (qe, te, time_factor) in front of the filter
   float qe[4], te[3];     // qx qy qz qw
   float time_factor;
+  const float4 *src;      // the cloud where it lies in device memory (k_bp_take_keys_dev reads it there); null: staged at src_off
+};
+
+// A full cloud written by the device-fed launch: lio_odom_full_to_end then lio_map_set_full_cloud with no copy between (mapping.hip:
+// MbFromOdomRec's full part).  st null: a copy.
+struct BpFull {
+  const float4 *in;
+  float4 *out;
+  int n;
+  const OdomState *st;
+  float time_factor;
+  int no_deskew;
 };
 
 // SlideWindow of one window: the two segments of Estimator.cc:2602-2615 into the handle's scratch cloud
@@ -40,17 +56,24 @@ struct BpSlide {
 
 // the chain's producer in front of SegVoxFilter::finish (no host wait; keys, partial, flag: the filter's)
 void launch_bp_take_keys(const BpCloud *rec, int nclouds, int max_n, const float4 *staging, float4 *in_all, uint32_t *keys, float *partial, int *flag, hipStream_t s);
+// the same with the clouds read from the records' device sources, and the full clouds behind them (grid rows nclouds .. nclouds + nfull - 1)
+void launch_bp_take_keys_dev(const BpCloud *rec, int nclouds, const BpFull *full, int nfull, int max_n, float4 *in_all, uint32_t *keys, float *partial, int *flag,
+                             hipStream_t s);
 void launch_bp_slide(const BpSlide *rec, int nwin, int max_total, hipStream_t s);
 
 // The chain's arrays and records; owned by an EstimatorBatch (one per part), sized by the largest call so far.
 class PushChain {
  public:
-  // a call: begin(), add() per filtered cloud (host pointer; returns the cloud's index), run(), then vox.out(i) / input(i)
-  void begin(int max_clouds);
-  int add(const float *host_xyzi, size_t n, float leaf, bool deskew, const float q[4], const float p[3], float time_factor, float4 *dst);
+  // a call: begin(), add() per filtered cloud (returns the cloud's index), add_full() per full cloud, run(), then vox.out(i) / input(i).  The
+  // clouds of a call are all the host's (xyzi is a host pointer, staged and uploaded by run()) or, with on_device, all the device's (xyzi is a
+  // device pointer, complete and left alone until run() returns; only such a call takes full clouds).
+  void begin(int max_clouds, int max_full = 0, bool on_device = false);
+  int add(const float *xyzi, size_t n, float leaf, bool deskew, const float q[4], const float p[3], float time_factor, float4 *dst);
+  void add_full(const BpFull &f);
   int clouds() const { return n_; }
-  // uploads, the launches through vox.finish and the call's one wait; passes: 3 or 4.  No cloud: nothing is enqueued and nothing waited for
-  // (returns false)
+  int uploads() const { return uploads_; }   // host-to-device copies of cloud data the last run() issued
+  // uploads, the launches through vox.finish and the call's one wait; passes: 3 or 4.  No cloud and no full cloud: nothing is enqueued and
+  // nothing waited for (returns false)
   bool run(SegVoxFilter &vox, int passes, hipStream_t s);
   const float4 *input(int i) const { return in_all_.p + h_rec_.p[i].vox.off; }   // the cloud as the filter read it: staged, de-skewed
 
@@ -58,8 +81,11 @@ class PushChain {
   std::vector<const float *> src_;
   HostBuf<BpCloud> h_rec_;
   DBuf<BpCloud> d_rec_;
+  HostBuf<BpFull> h_full_;
+  DBuf<BpFull> d_full_;
   DBuf<float4> staging_, in_all_;
-  int n_ = 0, cap_ = 0, total_ = 0, max_n_ = 0;
+  int n_ = 0, cap_ = 0, total_ = 0, max_n_ = 0, staged_ = 0, nfull_ = 0, cap_full_ = 0, uploads_ = 0;
+  bool on_device_ = false;
 };
 
 }  // namespace lio

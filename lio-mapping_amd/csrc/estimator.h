@@ -226,6 +226,9 @@ class Estimator {
   // ProcessLaserOdom.  *T_to_init: the pose that went in.  false: ProcessLaserOdom refused.
   bool ProcessCompact(const Rigidf &transform_sum, const float *corner, size_t nc, const float *surf, size_t ns, const float *full, size_t nf, double stamp,
                       Rigidf *T_to_init, lio_solve_report *rep);
+  // the initialised branch of ProcessCompact in front of ProcessLaserOdom (:780-805): the prediction of the map's transform_tobe_mapped_, its
+  // transform_sum_; returns the pose that goes in.  ProcessCompact and the batch's device-fed composite (est_batch.h) both call it.
+  Rigidf CompactPredict(const Rigidf &transform_sum);
   bool PushFrame(const Rigidf &transform_in, const float *surf, size_t n_surf, const float *corner, size_t n_corner, double stamp,
                  bool surf_on_device = false, bool corner_on_device = false);
   // PushFrame in two parts with the device work in between (the single call's: PushFrame; a batch's: est_push.h).  PushRefused: the de-skew

@@ -273,20 +273,28 @@ bool Estimator::ProcessLaserOdom(const Rigidf &transform_in, const float *surf, 
                           false);
 }
 
+// Estimator.cc:780-803 and :805 of an initialised window: transform_tobe_mapped_ predicted with the IMU-propagated body motion, transform_sum_
+// taken, and the pose that goes into ProcessLaserOdom
+Rigidf Estimator::CompactPredict(const Rigidf &transform_sum) {
+  MappingDev &m = *map_;
+  auto bodyPose = [&](int i) {
+    // Quaterniond(R).cast<float>(): build the quaternion in double, then cast
+    const Quat<double> qd = fromRot(Rs_[i]);
+    return Rigidf(Quat<float>(float(qd.w), float(qd.x), float(qd.y), float(qd.z)), Vec3<float>(float(Ps_[i].x), float(Ps_[i].y), float(Ps_[i].z)));
+  };
+  const Rigidf d_trans = compose(rinverse(bodyPose(W_ - 1)), bodyPose(W_));
+  m.transform_tobe_mapped_ = compose(compose(compose(m.transform_tobe_mapped_, transform_lb_), d_trans), rinverse(transform_lb_));
+  m.transform_sum_ = transform_sum;
+  return m.transform_aft_mapped_;
+}
+
 // Estimator.cc:776-856
 bool Estimator::ProcessCompact(const Rigidf &transform_sum, const float *corner, size_t nc, const float *surf, size_t ns, const float *full, size_t nf,
                                double stamp, Rigidf *T_to_init, lio_solve_report *rep) {
   MappingDev &m = *map_;
   if (full_cloud_) m.SetFullCloud(full, nf);   // CompactDataHandler's third block (PointMapping.cc:212-224)
-  if (inited_) {  // :780-803: predict transform_tobe_mapped_ with the IMU-propagated body motion
-    auto bodyPose = [&](int i) {
-      // Quaterniond(R).cast<float>(): build the quaternion in double, then cast
-      const Quat<double> qd = fromRot(Rs_[i]);
-      return Rigidf(Quat<float>(float(qd.w), float(qd.x), float(qd.y), float(qd.z)), Vec3<float>(float(Ps_[i].x), float(Ps_[i].y), float(Ps_[i].z)));
-    };
-    const Rigidf d_trans = compose(rinverse(bodyPose(W_ - 1)), bodyPose(W_));
-    m.transform_tobe_mapped_ = compose(compose(compose(m.transform_tobe_mapped_, transform_lb_), d_trans), rinverse(transform_lb_));
-    m.transform_sum_ = transform_sum;
+  if (inited_) {  // :780-803
+    CompactPredict(transform_sum);
   } else {
     m.Process(corner, nc, surf, ns, transform_sum);
   }

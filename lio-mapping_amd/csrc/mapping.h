@@ -86,6 +86,9 @@ class MappingDev {
   // full_cloud_ (PointMapping.cc:212-224): the full-resolution sweep, sensor frame until a Process with the init flag off has mapped it
   // in place with the transform_tobe_mapped_ it ended with (PublishResults, :1244-1248) — once per set.  n = 0 clears it.
   void SetFullCloud(const float *xyzi, size_t n);
+  // SetFullCloud with the points written by the caller, on the stream `writer`: the handle's side of it (FullBegin), the wait for a reader of
+  // the old cloud on another stream, and where the n points go (null: n = 0, the cloud is cleared).  The caller returns synchronised.
+  float4 *FullTake(size_t n, hipStream_t writer);
   size_t GetFullCloud(float *out);
   const float4 *FullDevice() const { return full_.p; }
   size_t FullSize() const { return n_full_; }

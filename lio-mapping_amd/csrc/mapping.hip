@@ -623,11 +623,16 @@ void MappingDev::FullBegin(size_t n) {
   n_full_ = n; full_mapped_ = false; full_event_ = false;
   if (n) full_.reserve(n);
 }
-void MappingDev::SetFullCloud(const float *xyzi, size_t n) {
+float4 *MappingDev::FullTake(size_t n, hipStream_t writer) {
   FullBegin(n);
-  if (!n) return;
-  if (full_read_) LIO_HIP(hipStreamWaitEvent(stream_, ev_full_read_, 0));
-  LIO_HIP(hipMemcpyAsync(full_.p, xyzi, n * sizeof(float4), hipMemcpyHostToDevice, stream_));
+  if (!n) return nullptr;
+  if (full_read_) LIO_HIP(hipStreamWaitEvent(writer, ev_full_read_, 0));
+  return full_.p;
+}
+void MappingDev::SetFullCloud(const float *xyzi, size_t n) {
+  float4 *dst = FullTake(n, stream_);
+  if (!dst) return;
+  LIO_HIP(hipMemcpyAsync(dst, xyzi, n * sizeof(float4), hipMemcpyHostToDevice, stream_));
   LIO_HIP(hipStreamSynchronize(stream_));   // the caller may reuse the source right after the call
 }
 // a reader of FullDevice() on another stream is ordered behind the registration: no host wait

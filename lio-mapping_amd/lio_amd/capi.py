@@ -343,6 +343,14 @@ _EST_PUSH_SIGS = {
     "lio_est_batch_push_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
 }
 PUSH_STATS = ("chain", "redone", "as_is", "host_waits", "sort_passes")   # lio_est_batch_push_stats [0 .. 4]
+# include/lio_est_from_odom.h: the windows of a batch fed from the odometry handles on the device (the product only, attached like _EST_PUSH_SIGS)
+_EST_FROM_ODOM_SIGS = {
+    "lio_est_batch_push_frames_from_odom": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(TransformF), c_double_p]),
+    "lio_est_batch_process_compact_from_odom": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), c_double_p, C.POINTER(TransformF),
+                                                          C.POINTER(SolveReport)]),
+    "lio_est_batch_from_odom_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+}
+FROM_ODOM_STATS = ("device_sources", "as_is_copies", "full_clouds", "uploads")   # lio_est_batch_from_odom_stats [0 .. 3]
 # include/lio_vox_sort.h: the voxel filter's sort on caller-given keys and the counters of the paths it took (the product only, attached like _EXT_SIGS)
 _c_uint32_p = C.POINTER(C.c_uint32)
 _VOX_SORT_SIGS = {
@@ -418,7 +426,8 @@ class LioLib:
                 fn.restype = res
                 fn.argtypes = args
             # a build from before the sample sort still loads (the A/B tools take one as --parent-lib); only a call to these fails there
-            for name, (res, args) in list(_VOX_SORT_SIGS.items()) + list(_SEG_BOUNDS_SIGS.items()) + list(_EST_PUSH_SIGS.items()):
+            for name, (res, args) in list(_VOX_SORT_SIGS.items()) + (list(_SEG_BOUNDS_SIGS.items()) + list(_EST_PUSH_SIGS.items())
+                                                                             + list(_EST_FROM_ODOM_SIGS.items())):
                 fn = getattr(self.dll, name, None)
                 if fn is not None:
                     fn.restype = res
@@ -1577,6 +1586,42 @@ class EstimatorBatch:
         out = (C.c_int * 8)()
         _chk(self.lib.dll.lio_est_batch_push_stats(self.h, out), "lio_est_batch_push_stats")
         return dict(zip(PUSH_STATS, [int(v) for v in out[:5]]))
+
+    # ---- include/lio_est_from_odom.h
+    def _sources(self, odoms, pps, what):
+        n = len(self.members)
+        if len(odoms) != n or (pps is not None and len(pps) != n):
+            raise LioError(f"{what}: one odometry (and one processor or None) per window")
+        O = (C.c_void_p * n)(*[o.h for o in odoms])
+        P = None if pps is None else (C.c_void_p * n)(*[None if p is None else p.h for p in pps])
+        return O, P
+
+    def push_frames_from_odom(self, odoms, pps, transforms, stamps):
+        """lio_est_batch_push_frames_from_odom: push_frames with window w's clouds taken from the PointOdometry odoms[w] on the device, and
+        its map's full cloud from the PointProcessor pps[w] (pps None, or a None entry: the full cloud stays as it is)."""
+        n = len(self.members)
+        O, P = self._sources(odoms, pps, "push_frames_from_odom")
+        if len(transforms) != n or len(stamps) != n:
+            raise LioError("push_frames_from_odom: one transform and one stamp per window")
+        T = (TransformF * n)(*transforms)
+        t = _f64(stamps).reshape(-1)
+        _chk(self.lib.dll.lio_est_batch_push_frames_from_odom(self.h, O, P, T, _dp(t)), "lio_est_batch_push_frames_from_odom")
+
+    def process_compact_from_odom(self, odoms, pps, stamps):
+        """lio_est_batch_process_compact_from_odom -> (transform_to_init (q, p) per window, one SolveReport per window)"""
+        n = len(self.members)
+        O, P = self._sources(odoms, pps, "process_compact_from_odom")
+        if len(stamps) != n:
+            raise LioError("process_compact_from_odom: one stamp per window")
+        t = _f64(stamps).reshape(-1)
+        T, reps = (TransformF * n)(), (SolveReport * n)()
+        _chk(self.lib.dll.lio_est_batch_process_compact_from_odom(self.h, O, P, _dp(t), T, reps), "lio_est_batch_process_compact_from_odom")
+        return [T[k].to_np() for k in range(n)], list(reps)
+
+    def from_odom_stats(self):
+        out = (C.c_int * 8)()
+        _chk(self.lib.dll.lio_est_batch_from_odom_stats(self.h, out), "lio_est_batch_from_odom_stats")
+        return dict(zip(FROM_ODOM_STATS, [int(v) for v in out[:4]]))
 
     STAGES = ("filtered_map", "knn_grid", "feature_flags", "plane_coefficients", "newest_frame_state", "solver_state", "moments", "jacobi_scaling", "scaled_hessian", "new_prior")
 
