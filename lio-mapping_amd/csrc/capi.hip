@@ -126,6 +126,19 @@ class PpLease {
   std::vector<Slot> slot_;
   std::vector<std::unique_lock<std::mutex>> locks_;
 };
+// The hand-over from the odometry to the next stage (mapping.h: OdomSweep): the handle's last clouds and transform_sum_ where they lie on the
+// device, and the ring cloud of slot k's processor through the handle's TransformToEnd as the full cloud (an empty slot: full.set false).
+// The sources are valid only while `lease` lives: the caller holds it until the chain that reads them has returned synchronised.
+static OdomSweep odom_sweep(const lio_odom *odom, const PpLease &lease, size_t k) {
+  const OdometryDev::DeviceView v = odom->o->View();
+  OdomSweep S{v.last[0], v.last[1], odom->o->transform_sum_, MapFullSource{}};
+  if (lease.pp(k)) {
+    S.full.set = true;
+    lease.pp(k)->DeviceRings(lease.sweep(k), S.full.pts, S.full.n);
+    S.full.to_end = v.to_end;
+  }
+  return S;
+}
 // f(the processor that holds the handle's last sweep, that sweep selected)
 template <typename F> static int pp_read(const lio_pp *h, F &&f) {
   return guarded([&] {
@@ -314,6 +327,8 @@ static int pp_process_batch(lio_pp *const *handles, const float *const *xyzi, co
         pool = std::make_shared<lio_pp_pool>(a.lower(), a.upper(), a.rings(), a.config());
       }
       std::vector<StartOriFilter *> filters(static_cast<size_t>(n_sweeps));
+      std::vector<CloudSrc> sweeps(static_cast<size_t>(n_sweeps));
+      for (int k = 0; k < n_sweeps; ++k) sweeps[size_t(k)] = CloudSrc::at(xyzi[k], n[k], on_device);
       std::lock_guard<std::mutex> lk(pool->mu);
       ++pool->gen;   // the chain overwrites the pool's storage: every lease on it ends here
       // Everything below can throw (a handle's own sweep still in flight may have ended over capacity), and nothing is served of a failed
@@ -324,7 +339,7 @@ static int pp_process_batch(lio_pp *const *handles, const float *const *xyzi, co
         handles[k]->pp->ProcessFinish();
         filters[size_t(k)] = &handles[k]->pp->start_ori_filter();
       }
-      pool->pp.ProcessLaunchBatch(xyzi, ring, n, n_sweeps, on_device, filters.data());
+      pool->pp.ProcessLaunchBatch(sweeps.data(), ring, n_sweeps, filters.data());
       try { pool->pp.ProcessFinish(); }
       catch (const CapacityError &) { lease(); throw; }   // finished, over capacity: the pool's processor reads zero for every sweep
       lease();
@@ -338,7 +353,8 @@ static int pp_process_batch(lio_pp *const *handles, const float *const *xyzi, co
     h->pool_sweep = -1;
     rc = guarded([&] {
       StartOriFilter *f = &h->pp->start_ori_filter();
-      h->pp->ProcessLaunchBatch(&xyzi[launched], ring ? &ring[launched] : nullptr, &n[launched], 1, on_device, &f);
+      const CloudSrc sweep = CloudSrc::at(xyzi[launched], n[launched], on_device);
+      h->pp->ProcessLaunchBatch(&sweep, ring ? &ring[launched] : nullptr, 1, &f);
       return LIO_OK;
     });
   }
@@ -431,7 +447,10 @@ int lio_odom_process_batch(lio_odom *const *handles, int n_sensors, const float 
   return guarded([&] {
     std::vector<OdometryDev *> o;
     if (!odom_devices(handles, n_sensors, o)) return int(LIO_ERR_ARG);
-    OdometryDev::ProcessBatch(o.data(), n_sensors, sharp, n_sharp, less_sharp, n_ls, flat, n_flat, less_flat, n_lf);
+    std::vector<OdometryDev::Clouds> in(static_cast<size_t>(n_sensors));
+    for (int k = 0; k < n_sensors; ++k)
+      in[size_t(k)] = OdometryDev::Clouds{{CloudSrc::host(sharp[k], n_sharp[k]), CloudSrc::host(less_sharp[k], n_ls[k]), CloudSrc::host(flat[k], n_flat[k]), CloudSrc::host(less_flat[k], n_lf[k])}};
+    OdometryDev::ProcessBatch(o.data(), n_sensors, in.data());
     odom_results(o.data(), n_sensors, Tsum, Tes, iters, nsel);
     return int(LIO_OK);
   });
@@ -448,17 +467,13 @@ int lio_odom_process_batch_from_pp(lio_odom *const *handles, lio_pp *const *pp, 
     std::vector<OdometryDev *> o;
     if (!odom_devices(handles, n_sensors, o)) return int(LIO_ERR_ARG);
     const PpLease lease(pp, n, "lio_odom_process_batch_from_pp", true, true);
-    // the host table: four (source, count) pairs per sensor
-    std::vector<const float *> src[4];
-    std::vector<size_t> cnt[4];
-    for (int c = 0; c < 4; ++c) { src[c].resize(n); cnt[c].resize(n); }
+    std::vector<OdometryDev::Clouds> in(n);
     for (size_t k = 0; k < n; ++k) {
       const float4 *s4[4]; size_t n4[4];
       lease.pp(k)->DeviceClouds(lease.sweep(k), s4, n4);
-      for (int c = 0; c < 4; ++c) { src[c][k] = reinterpret_cast<const float *>(s4[c]); cnt[c][k] = n4[c]; }
+      for (int c = 0; c < 4; ++c) in[k].c[c] = CloudSrc::device(s4[c], n4[c]);
     }
-    OdometryDev::ProcessBatch(o.data(), n_sensors, src[0].data(), cnt[0].data(), src[1].data(), cnt[1].data(), src[2].data(), cnt[2].data(), src[3].data(),
-                              cnt[3].data(), true);
+    OdometryDev::ProcessBatch(o.data(), n_sensors, in.data());
     odom_results(o.data(), n_sensors, Tsum, Tes, iters, nsel);
     return int(LIO_OK);
   });
@@ -566,9 +581,9 @@ int lio_map_process_batch(lio_map *const *handles, int n_sensors, const float *c
   const int rc = map_batch_devices(handles, n_sensors, [&](int k) { return (corner[k] || !nc[k]) && (surf[k] || !ns[k]); }, m);
   if (rc != LIO_OK) return rc;
   return guarded([&] {
-    std::vector<Rigidf> sums;
-    for (int k = 0; k < n_sensors; ++k) sums.push_back(toT(Tsum[k]));
-    MappingDev::ProcessBatch(m.data(), n_sensors, corner, nc, surf, ns, sums.data());
+    std::vector<OdomSweep> sweeps(static_cast<size_t>(n_sensors));
+    for (int k = 0; k < n_sensors; ++k) sweeps[size_t(k)] = OdomSweep{CloudSrc::host(corner[k], nc[k]), CloudSrc::host(surf[k], ns[k]), toT(Tsum[k]), MapFullSource{}};
+    MappingDev::ProcessBatch(m.data(), n_sensors, sweeps.data());
     map_results(m.data(), n_sensors, Taft, iters, nsel);
     return int(LIO_OK);
   });
@@ -586,22 +601,9 @@ int lio_map_process_batch_from_odom(lio_map *const *handles, lio_odom *const *od
   return guarded([&] {
     const size_t n = size_t(n_sensors);
     const PpLease lease(pp, n, "lio_map_process_batch_from_odom", true, true);
-    std::vector<Rigidf> sums(n);
-    std::vector<const float *> src[2];
-    std::vector<size_t> cnt[2];
-    for (int c = 0; c < 2; ++c) { src[c].resize(n); cnt[c].resize(n); }
-    std::vector<MapFullSource> full(n, MapFullSource{});
-    for (size_t k = 0; k < n; ++k) {
-      const OdometryDev::DeviceView v = odom[k]->o->View();
-      sums[k] = odom[k]->o->transform_sum_;
-      for (int c = 0; c < 2; ++c) { src[c][k] = reinterpret_cast<const float *>(v.last[c]); cnt[c][k] = v.n_last[c]; }
-      if (!lease.pp(k)) continue;
-      MapFullSource &f = full[k];
-      f.set = true;
-      lease.pp(k)->DeviceRings(lease.sweep(k), f.pts, f.n);
-      f.to_end = v.to_end; f.time_factor = v.time_factor; f.no_deskew = v.no_deskew;
-    }
-    MappingDev::ProcessBatch(m.data(), n_sensors, src[0].data(), cnt[0].data(), src[1].data(), cnt[1].data(), sums.data(), full.data());
+    std::vector<OdomSweep> sweeps(n);
+    for (size_t k = 0; k < n; ++k) sweeps[k] = odom_sweep(odom[k], lease, k);
+    MappingDev::ProcessBatch(m.data(), n_sensors, sweeps.data());
     map_results(m.data(), n_sensors, Taft, iters, nsel);
     return int(LIO_OK);
   });
@@ -1133,7 +1135,7 @@ int lio_est_process_imu_batch(lio_est *h, size_t n, const double *dt, const doub
 int lio_est_process_laser_odom(lio_est *h, const lio_transform_f *T, const float *surf, size_t ns, const float *corner, size_t nc, double stamp,
                                lio_solve_report *rep) {
   if (!h || !T || (!surf && ns) || (!corner && nc)) return LIO_ERR_ARG;
-  return guarded([&] { return h->e->ProcessLaserOdom(toT(*T), surf, ns, corner, nc, stamp, rep) ? LIO_OK : LIO_ERR_STATE; });
+  return guarded([&] { return h->e->ProcessLaserOdom(toT(*T), CloudSrc::host(surf, ns), CloudSrc::host(corner, nc), stamp, rep) ? LIO_OK : LIO_ERR_STATE; });
 }
 // int thread ids, one point per lane in workgroups of 256: the last workgroup's tail lanes must not pass INT_MAX
 static constexpr size_t kMaxCloudPoints = size_t(INT_MAX) - 255;
@@ -1284,7 +1286,7 @@ int lio_est_get_stage(const lio_est *h, int *stage, int *cir_buf_count, int *ext
 int lio_est_push_frame(lio_est *h, const lio_transform_f *T, const float *surf, size_t ns, const float *corner, size_t nc, double stamp) {
   if (!h || !T || (!surf && ns) || (!corner && nc)) return LIO_ERR_ARG;
   if (!h->e->inited_) return LIO_ERR_STATE;
-  return guarded([&] { return h->e->PushFrame(toT(*T), surf, ns, corner, nc, stamp) ? LIO_OK : LIO_ERR_STATE; });
+  return guarded([&] { return h->e->PushFrame(toT(*T), CloudSrc::host(surf, ns), CloudSrc::host(corner, nc), stamp) ? LIO_OK : LIO_ERR_STATE; });
 }
 int lio_est_solve_optimization(lio_est *h, lio_solve_report *rep) {
   if (!h) return LIO_ERR_ARG;
@@ -1533,7 +1535,7 @@ int lio_est_batch_push_stats(const lio_est_batch *h, int *out8) {
 // map or the device is touched, in the header's order; the lease on the processors is held until the parts, which read their clouds, have
 // returned synchronised.  f(the sources, one per window) runs the call.
 static int est_from_odom(lio_est_batch *h, lio_odom *const *odom, lio_pp *const *pp, const double *stamps, bool need_T, const void *T, bool composite,
-                         const char *who, const std::function<int(const EstOdomSource *)> &f) {
+                         const char *who, const std::function<int(const OdomSweep *)> &f) {
   if (!h || !odom || !stamps || (need_T && !T)) return LIO_ERR_ARG;
   const int n = batch_live(h) ? h->parts->size() : 0;
   for (int w = 0; w < n; ++w)
@@ -1545,19 +1547,12 @@ static int est_from_odom(lio_est_batch *h, lio_odom *const *odom, lio_pp *const 
   }
   return guarded([&] {
     const PpLease lease(pp, size_t(n), who, true, true);
-    std::vector<EstOdomSource> src(static_cast<size_t>(n));
+    std::vector<OdomSweep> src(static_cast<size_t>(n));
     size_t total = 0;   // push_batch_check's limits, the full cloud included
     for (int w = 0; w < n; ++w) {
-      const OdometryDev::DeviceView v = odom[w]->o->View();
-      EstOdomSource &S = src[size_t(w)];
-      S = EstOdomSource{{v.last[0], v.last[1]}, {v.n_last[0], v.n_last[1]}, odom[w]->o->transform_sum_, MapFullSource{}};
-      if (lease.pp(size_t(w))) {
-        S.full.set = true;
-        lease.pp(size_t(w))->DeviceRings(lease.sweep(size_t(w)), S.full.pts, S.full.n);
-        S.full.to_end = v.to_end; S.full.time_factor = v.time_factor; S.full.no_deskew = v.no_deskew;
-      }
-      if (S.n_last[0] > kMaxCloudPoints || S.n_last[1] > kMaxCloudPoints || S.full.n > kMaxCloudPoints) return int(LIO_ERR_CAPACITY);
-      total += S.n_last[0] + S.n_last[1] + S.full.n + 768;
+      const OdomSweep &S = src[size_t(w)] = odom_sweep(odom[w], lease, size_t(w));
+      if (S.corner.n > kMaxCloudPoints || S.surf.n > kMaxCloudPoints || S.full.n > kMaxCloudPoints) return int(LIO_ERR_CAPACITY);
+      total += S.corner.n + S.surf.n + S.full.n + 768;
       if (total > (size_t(1) << 30)) return int(LIO_ERR_CAPACITY);
     }
     if (composite) for (lio_est *m : h->members) est_map(m);   // (behind the last refusal, as lio_est_process_compact creates it)
@@ -1565,14 +1560,14 @@ static int est_from_odom(lio_est_batch *h, lio_odom *const *odom, lio_pp *const 
   });
 }
 int lio_est_batch_push_frames_from_odom(lio_est_batch *h, lio_odom *const *odom, lio_pp *const *pp, const lio_transform_f *T_in, const double *stamps) {
-  return est_from_odom(h, odom, pp, stamps, true, T_in, false, "lio_est_batch_push_frames_from_odom", [&](const EstOdomSource *src) {
+  return est_from_odom(h, odom, pp, stamps, true, T_in, false, "lio_est_batch_push_frames_from_odom", [&](const OdomSweep *src) {
     h->parts->PushFramesFrom(src, T_in, stamps);
     return LIO_OK;
   });
 }
 int lio_est_batch_process_compact_from_odom(lio_est_batch *h, lio_odom *const *odom, lio_pp *const *pp, const double *stamps, lio_transform_f *T_out,
                                             lio_solve_report *reps) {
-  return est_from_odom(h, odom, pp, stamps, false, nullptr, true, "lio_est_batch_process_compact_from_odom", [&](const EstOdomSource *src) {
+  return est_from_odom(h, odom, pp, stamps, false, nullptr, true, "lio_est_batch_process_compact_from_odom", [&](const OdomSweep *src) {
     return h->parts->ProcessCompactFrom(src, stamps, T_out, reps) ? LIO_OK : LIO_ERR_STATE;
   });
 }

@@ -88,6 +88,12 @@ __device__ __forceinline__ void odo_to_end_body(const float4 *in, float4 *out, c
   p.w = float(int(p.w));
   out[i] = to_end_point<false>(p, s, qe, te);
 }
+// Point i of a full cloud a take launch writes (cloud_kernels.h: FullTake), through TransformToEnd or, without a state, as it is: k_mb_from_odom
+// (mapping.hip) and k_bp_take_keys_dev (est_push.hip).  in, out, st: the record's pointers as the caller resolved them (as read, or dev.h: rebase).
+__device__ __forceinline__ void full_take_body(const float4 *in, float4 *out, const int i, const OdomState *st, const ToEnd &e) {
+  if (st) odo_to_end_body(in, out, i, st, e.time_factor, e.no_deskew);
+  else out[i] = in[i];
+}
 // PointAssociateToMap (PointMapping.cc:303-314): rot * p + pos in the operation order of rotate (hmath.h), intensity kept
 __device__ __forceinline__ float4 rigid_map_point(float4 p, const Quat<float> &q, const Vec3<float> &t) {
   const Vec3<float> v = rotate(q, Vec3<float>(p.x, p.y, p.z));

@@ -257,6 +257,12 @@ struct OdomState {
   int kz;            // number of leading components masked (A.6)
   int nsel;          // rows selected in the last round
 };
+// What the odometry's TransformToEnd runs a cloud through (OdometryDev::View, MapFullSource): the device-side transform_es_ the last step
+// left, and the handle's two de-skew parameters.  st null: a copy (odometry disabled, or no publishing step yet).
+struct ToEnd { const OdomState *st; float time_factor; int no_deskew; };
+// The device record of a full cloud written by a take launch (mapping.hip: k_mb_from_odom's row 2; est_push.hip: k_bp_take_keys_dev's rows
+// behind the clouds): lio_odom_full_to_end then lio_map_set_full_cloud with no copy between.  cloud_device.h: full_take_body.
+struct FullTake { const float4 *in; float4 *out; int n; ToEnd to_end; };
 // the state a Gauss-Newton loop starts from at pose T: no round run, nothing converged
 inline OdomState odom_state_at(const Rigid<float> &T) {
   OdomState st{};

@@ -49,16 +49,6 @@ struct BatchClock {   // host wall clock of the last Solve(), ms
   double dev_marg_wait = 0;   // of dev[3]: the stream's wait for the PREVIOUS solve's marginalization (it sits in front of the problems' upload)
 };
 
-// Where a window's sweep lies on the device (include/lio_est_from_odom.h): an odometry's last clouds (OdometryDev::View) and transform_sum_, and
-// the full cloud the window's map takes with them — a processor's ring cloud through that odometry's TransformToEnd (full.set false: no
-// processor was given).  Complete and left alone until the call returns.
-struct EstOdomSource {
-  const float4 *last[2];   // 0 corner, 1 surf
-  size_t n_last[2];
-  Rigidf transform_sum;
-  MapFullSource full;
-};
-
 class EstimatorBatch {
  public:
   explicit EstimatorBatch(const std::vector<Estimator *> &members);
@@ -75,11 +65,11 @@ class EstimatorBatch {
   void SlideWindows();
   // ProcessLaserOdom of every (initialised) member: push, Solve, RefreshMap where it is on, slide, last_event_.  false: a member's solve failed
   bool ProcessLaserOdom(const lio_est_frame *frames, lio_solve_report *reps);
-  // include/lio_est_from_odom.h: PushFrames / ProcessCompactData of every (initialised) member with the clouds read where src[w] says, no cloud
-  // through the host.  T_in: size() poses (PushFramesFrom); T_out: size() poses that went in, or null.  The caller has checked what PushFrames'
+  // include/lio_est_from_odom.h: PushFrames / ProcessCompactData of every (initialised) member with the clouds read where src[w] (mapping.h:
+  // OdomSweep) says, no cloud through the host.  T_in: size() poses (PushFramesFrom); T_out: size() poses that went in, or null.  The caller has checked what PushFrames'
   // caller checks, and that every member has its map.  Return synchronised.
-  void PushFramesFrom(const EstOdomSource *src, const lio_transform_f *T_in, const double *stamps);
-  bool ProcessCompactFrom(const EstOdomSource *src, const double *stamps, lio_transform_f *T_out, lio_solve_report *reps);
+  void PushFramesFrom(const OdomSweep *src, const lio_transform_f *T_in, const double *stamps);
+  bool ProcessCompactFrom(const OdomSweep *src, const double *stamps, lio_transform_f *T_out, lio_solve_report *reps);
   const int *push_stats() const { return push_stats_; }   // of the last PushFrames (lio_est_batch_push_stats)
   const int *from_odom_stats() const { return from_stats_; }   // of the last device-fed call (lio_est_batch_from_odom_stats)
   // waits for everything the batch has enqueued (the marginalizations of the last Solve)
@@ -127,13 +117,12 @@ class EstimatorBatch {
   // One window's sweep of a push, wherever it lies: the loop over the windows (PushAll) is stated once for PushFrames and PushFramesFrom
   struct PushInput {
     Rigidf transform_in;
-    const float *surf, *corner;   // host pointers, or with on_device device pointers
-    size_t n_surf, n_corner;
+    CloudSrc surf, corner;   // all of a call in one place (cloud_src.h)
     double stamp;
-    const MapFullSource *full;    // on_device: the full cloud the window's map takes in the same launch (null, or set false: none)
+    MapFullSource full;      // the device's: the full cloud the window's map takes in the same launch (set false: none)
   };
-  void PushAll(const PushInput *in, bool on_device);
-  void PushFrom(const EstOdomSource *src, const Rigidf *T_in, const double *stamps, bool composite);
+  void PushAll(const PushInput *in);
+  void PushFrom(const OdomSweep *src, const Rigidf *T_in, const double *stamps, bool composite);
   bool SolveRefreshSlide(lio_solve_report *reps);   // ProcessLaserOdom behind the push: Solve, RefreshMap where it is on, slide, last_event_
   void FetchPrior(int w, int buf, MargPrior &pr);
   void Materialize(int w, int buf);
@@ -212,8 +201,8 @@ class BatchParts {
   bool ProcessLaserOdom(const lio_est_frame *frames, lio_solve_report *reps);   // false: a window's solve failed
   void PushStats(int out[8]) const;   // the parts' counters of the last push, added up
   // include/lio_est_from_odom.h: the arrays hold size() entries; every part takes its own windows'
-  void PushFramesFrom(const EstOdomSource *src, const lio_transform_f *T_in, const double *stamps);
-  bool ProcessCompactFrom(const EstOdomSource *src, const double *stamps, lio_transform_f *T_out, lio_solve_report *reps);   // false: a window's solve failed
+  void PushFramesFrom(const OdomSweep *src, const lio_transform_f *T_in, const double *stamps);
+  bool ProcessCompactFrom(const OdomSweep *src, const double *stamps, lio_transform_f *T_out, lio_solve_report *reps);   // false: a window's solve failed
   void FromOdomStats(int out[8]) const;
   void Sync();
   void StageDigest(int stage, unsigned long long *out);   // out: size() digests

@@ -722,47 +722,44 @@ void EstimatorBatch::PushFrames(const lio_est_frame *fr) {
     const lio_est_frame &f = fr[w];
     in[size_t(w)] = PushInput{Rigidf(Quat<float>(f.transform_in.q[3], f.transform_in.q[0], f.transform_in.q[1], f.transform_in.q[2]),
                                      Vec3<float>(f.transform_in.p[0], f.transform_in.p[1], f.transform_in.p[2])),
-                              f.surf_xyzi, f.corner_xyzi, f.n_surf, f.n_corner, f.stamp, nullptr};
+                              CloudSrc::host(f.surf_xyzi, f.n_surf), CloudSrc::host(f.corner_xyzi, f.n_corner), f.stamp, MapFullSource{}};
   }
-  PushAll(in.data(), false);
+  PushAll(in.data());
 }
 
 // The device-fed pushes (include/lio_est_from_odom.h).  composite: the message's third block of ProcessCompactData — a window with its full cloud
 // on takes the given one or, given none, has it cleared; in the push form such a window keeps what it has.
-void EstimatorBatch::PushFrom(const EstOdomSource *src, const Rigidf *T_in, const double *stamps, bool composite) {
+void EstimatorBatch::PushFrom(const OdomSweep *src, const Rigidf *T_in, const double *stamps, bool composite) {
   const int B = size();
   std::vector<PushInput> in(static_cast<size_t>(B));
-  std::vector<MapFullSource> full(size_t(B), MapFullSource{});
   for (int w = 0; w < B; ++w) {
-    Estimator *e = m_[size_t(w)];
-    const EstOdomSource &S = src[w];
-    if (e->full_cloud()) {
-      if (S.full.set) full[size_t(w)] = S.full;
-      else if (composite) full[size_t(w)].set = true;   // an empty third block: n = 0 clears it
+    const OdomSweep &S = src[w];
+    PushInput &f = in[size_t(w)] = PushInput{T_in[w], S.surf, S.corner, stamps[w], MapFullSource{}};
+    if (m_[size_t(w)]->full_cloud()) {
+      if (S.full.set) f.full = S.full;
+      else if (composite) f.full.set = true;   // an empty third block: n = 0 clears it
     }
-    in[size_t(w)] = PushInput{T_in[w], reinterpret_cast<const float *>(S.last[1]), reinterpret_cast<const float *>(S.last[0]), S.n_last[1], S.n_last[0], stamps[w],
-                              &full[size_t(w)]};
   }
-  PushAll(in.data(), true);
+  PushAll(in.data());
 }
-void EstimatorBatch::PushFramesFrom(const EstOdomSource *src, const lio_transform_f *T_in, const double *stamps) {
+void EstimatorBatch::PushFramesFrom(const OdomSweep *src, const lio_transform_f *T_in, const double *stamps) {
   std::vector<Rigidf> T(static_cast<size_t>(size()));
   for (int w = 0; w < size(); ++w)
     T[size_t(w)] = Rigidf(Quat<float>(T_in[w].q[3], T_in[w].q[0], T_in[w].q[1], T_in[w].q[2]), Vec3<float>(T_in[w].p[0], T_in[w].p[1], T_in[w].p[2]));
   PushFrom(src, T.data(), stamps, false);
 }
 
-// Estimator::PushFrame of every member, the sweeps where `in` says (on_device: no cloud goes up, and the launch that takes the sweeps writes the
-// maps' full clouds too, in front of PushFrameEnd's PushFull)
-void EstimatorBatch::PushAll(const PushInput *in, bool on_device) {
+// Estimator::PushFrame of every member, the sweeps where `in` says (the device's: no cloud goes up, and the launch that takes the sweeps writes
+// the maps' full clouds too, in front of PushFrameEnd's PushFull)
+void EstimatorBatch::PushAll(const PushInput *in) {
   const int B = size();
+  const bool on_device = clouds_on_device(size_t(2) * size_t(B), [&](size_t i) { return i & 1 ? in[i / 2].corner : in[i / 2].surf; });
   hipStream_t s = stream_;
   for (int &v : push_stats_) v = 0;
   if (on_device) for (int &v : from_stats_) v = 0;
   plans_.clear();
   plans_.resize(size_t(B));
   push_.begin(2 * B, on_device ? B : 0, on_device);
-  const hipMemcpyKind as_is_kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   std::vector<int> cloud(size_t(2 * B), -1);   // the chain's cloud of window w's surf [2 w] and corner [2 w + 1] sweep
   // by what every window's clouds took in its previous push (seg_vox.h: the pass rule, as for Solve's local maps)
   int passes = 3;
@@ -770,25 +767,25 @@ void EstimatorBatch::PushAll(const PushInput *in, bool on_device) {
     Estimator *e = m_[size_t(w)];
     PushPlan &pl = plans_[size_t(w)];
     const PushInput &f = in[w];
-    if (on_device && f.full && f.full->set) {   // lio_map_set_full_cloud, the points written by the chain's launch (Estimator::ProcessCompact: SetFullCloud first)
-      const MapFullSource &F = *f.full;
-      if (float4 *dst = e->map_->FullTake(F.n, s)) push_.add_full(BpFull{F.pts, dst, int(F.n), F.to_end, F.time_factor, F.no_deskew});
+    if (on_device && f.full.set) {   // lio_map_set_full_cloud, the points written by the chain's launch (Estimator::ProcessCompact: SetFullCloud first)
+      const MapFullSource &F = f.full;
+      if (float4 *dst = e->map_->FullTake(F.n, s)) push_.add_full(FullTake{F.pts, dst, int(F.n), F.to_end});
       ++from_stats_[2];
     }
-    e->PushFrameBegin(f.transform_in, f.n_surf, f.n_corner, f.stamp, pl);
+    e->PushFrameBegin(f.transform_in, f.surf.n, f.corner.n, f.stamp, pl);
     if (pl.filter) {
       if (pl.corner_cloud)
-        cloud[size_t(2 * w + 1)] = push_.add(f.corner, f.n_corner, e->cfg_.corner_filter_size, pl.deskew, pl.q, pl.p, 10.f, pl.corner_cloud->buf.p);
-      cloud[size_t(2 * w)] = push_.add(f.surf, f.n_surf, e->cfg_.surf_filter_size, pl.deskew, pl.q, pl.p, 10.f, pl.fresh.buf.p);
+        cloud[size_t(2 * w + 1)] = push_.add(f.corner, e->cfg_.corner_filter_size, pl.deskew, pl.q, pl.p, 10.f, pl.corner_cloud->buf.p);
+      cloud[size_t(2 * w)] = push_.add(f.surf, e->cfg_.surf_filter_size, pl.deskew, pl.q, pl.p, 10.f, pl.fresh.buf.p);
       passes = std::max(passes, SegVoxFilter::passes_for(win_[size_t(w)].push_bits));
     } else {   // both de-skew switches off (Estimator.cc:474-480): the clouds go into the handle's buffers as they are
       if (pl.corner_cloud) {
-        if (f.n_corner) LIO_HIP(hipMemcpyAsync(pl.corner_cloud->buf.p, f.corner, f.n_corner * sizeof(float4), as_is_kind, s));
-        pl.corner_cloud->n = f.n_corner;
+        if (f.corner.n) LIO_HIP(hipMemcpyAsync(pl.corner_cloud->buf.p, f.corner.p, f.corner.n * sizeof(float4), f.corner.to_device(), s));
+        pl.corner_cloud->n = f.corner.n;
         ++push_stats_[2];
       }
-      if (f.n_surf) LIO_HIP(hipMemcpyAsync(pl.fresh.buf.p, f.surf, f.n_surf * sizeof(float4), as_is_kind, s));
-      pl.fresh.n = f.n_surf;
+      if (f.surf.n) LIO_HIP(hipMemcpyAsync(pl.fresh.buf.p, f.surf.p, f.surf.n * sizeof(float4), f.surf.to_device(), s));
+      pl.fresh.n = f.surf.n;
       ++push_stats_[2];
     }
   }
@@ -864,7 +861,7 @@ bool EstimatorBatch::ProcessLaserOdom(const lio_est_frame *fr, lio_solve_report 
 }
 // Estimator::ProcessCompact (Estimator.cc:776-856) of initialised members, the message never built: the prediction and transform_sum_
 // (CompactPredict), then ProcessLaserOdom with the sweeps and the third block taken on the device
-bool EstimatorBatch::ProcessCompactFrom(const EstOdomSource *src, const double *stamps, lio_transform_f *T_out, lio_solve_report *reps) {
+bool EstimatorBatch::ProcessCompactFrom(const OdomSweep *src, const double *stamps, lio_transform_f *T_out, lio_solve_report *reps) {
   const int B = size();
   std::vector<Rigidf> T(static_cast<size_t>(B));
   for (int w = 0; w < B; ++w) {
@@ -960,10 +957,10 @@ bool BatchParts::ProcessLaserOdom(const lio_est_frame *frames, lio_solve_report 
   ForParts([&](EstimatorBatch &b, int w0) { if (!b.ProcessLaserOdom(frames + w0, reps ? reps + w0 : nullptr)) bad.store(1); });
   return !bad.load();
 }
-void BatchParts::PushFramesFrom(const EstOdomSource *src, const lio_transform_f *T_in, const double *stamps) {
+void BatchParts::PushFramesFrom(const OdomSweep *src, const lio_transform_f *T_in, const double *stamps) {
   ForParts([&](EstimatorBatch &b, int w0) { b.PushFramesFrom(src + w0, T_in + w0, stamps + w0); });
 }
-bool BatchParts::ProcessCompactFrom(const EstOdomSource *src, const double *stamps, lio_transform_f *T_out, lio_solve_report *reps) {
+bool BatchParts::ProcessCompactFrom(const OdomSweep *src, const double *stamps, lio_transform_f *T_out, lio_solve_report *reps) {
   std::atomic<int> bad{0};
   ForParts([&](EstimatorBatch &b, int w0) {
     if (!b.ProcessCompactFrom(src + w0, stamps + w0, T_out ? T_out + w0 : nullptr, reps ? reps + w0 : nullptr)) bad.store(1);

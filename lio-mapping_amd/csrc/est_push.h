@@ -13,7 +13,7 @@
 //
 // Device-fed form (include/lio_est_from_odom.h): a cloud whose points already lie in device memory (an odometry's last_corner_ / last_surf_) has
 // its pointer in the record and no range of the staging array; k_bp_take_keys_dev reads it where it lies, and the same launch writes the full
-// clouds of the call (BpFull: a processor's ring cloud through the odometry's TransformToEnd into a map's full cloud).  No upload per cloud.
+// clouds of the call (cloud_kernels.h: FullTake, a processor's ring cloud through the odometry's TransformToEnd into a map's full cloud).
 //
 // The filter is the EstimatorBatch's one SegVoxFilter; what is the chain's own is here: the staging and input arrays, the records, the uploads.
 // A cloud the filter cannot take (keys beyond the absolute range or beyond what the passes order, PCL's "leaf size too small") comes back
@@ -23,6 +23,7 @@
 
 #include "batch_kernels.h"
 #include "cloud_kernels.h"
+#include "cloud_src.h"
 #include "seg_vox.h"
 
 namespace lio {
@@ -36,17 +37,6 @@ struct BpCloud {
   const float4 *src;      // the cloud where it lies in device memory (k_bp_take_keys_dev reads it there); null: staged at src_off
 };
 
-// A full cloud written by the device-fed launch: lio_odom_full_to_end then lio_map_set_full_cloud with no copy between (mapping.hip:
-// MbFromOdomRec's full part).  st null: a copy.
-struct BpFull {
-  const float4 *in;
-  float4 *out;
-  int n;
-  const OdomState *st;
-  float time_factor;
-  int no_deskew;
-};
-
 // SlideWindow of one window: the two segments of Estimator.cc:2602-2615 into the handle's scratch cloud
 struct BpSlide {
   ConcatSeg seg[2];
@@ -57,7 +47,7 @@ struct BpSlide {
 // the chain's producer in front of SegVoxFilter::finish (no host wait; keys, partial, flag: the filter's)
 void launch_bp_take_keys(const BpCloud *rec, int nclouds, int max_n, const float4 *staging, float4 *in_all, uint32_t *keys, float *partial, int *flag, hipStream_t s);
 // the same with the clouds read from the records' device sources, and the full clouds behind them (grid rows nclouds .. nclouds + nfull - 1)
-void launch_bp_take_keys_dev(const BpCloud *rec, int nclouds, const BpFull *full, int nfull, int max_n, float4 *in_all, uint32_t *keys, float *partial, int *flag,
+void launch_bp_take_keys_dev(const BpCloud *rec, int nclouds, const FullTake *full, int nfull, int max_n, float4 *in_all, uint32_t *keys, float *partial, int *flag,
                              hipStream_t s);
 void launch_bp_slide(const BpSlide *rec, int nwin, int max_total, hipStream_t s);
 
@@ -65,11 +55,11 @@ void launch_bp_slide(const BpSlide *rec, int nwin, int max_total, hipStream_t s)
 class PushChain {
  public:
   // a call: begin(), add() per filtered cloud (returns the cloud's index), add_full() per full cloud, run(), then vox.out(i) / input(i).  The
-  // clouds of a call are all the host's (xyzi is a host pointer, staged and uploaded by run()) or, with on_device, all the device's (xyzi is a
-  // device pointer, complete and left alone until run() returns; only such a call takes full clouds).
-  void begin(int max_clouds, int max_full = 0, bool on_device = false);
-  int add(const float *xyzi, size_t n, float leaf, bool deskew, const float q[4], const float p[3], float time_factor, float4 *dst);
-  void add_full(const BpFull &f);
+  // clouds of a call lie in one place (cloud_src.h), which begin() is told: the host's are staged and uploaded by run(), the device's are read
+  // where they lie, and only a device-fed call takes full clouds.
+  void begin(int max_clouds, int max_full = 0, bool device_fed = false);
+  int add(CloudSrc src, float leaf, bool deskew, const float q[4], const float p[3], float time_factor, float4 *dst);
+  void add_full(const FullTake &f);
   int clouds() const { return n_; }
   int uploads() const { return uploads_; }   // host-to-device copies of cloud data the last run() issued
   // uploads, the launches through vox.finish and the call's one wait; passes: 3 or 4.  No cloud and no full cloud: nothing is enqueued and
@@ -78,14 +68,14 @@ class PushChain {
   const float4 *input(int i) const { return in_all_.p + h_rec_.p[i].vox.off; }   // the cloud as the filter read it: staged, de-skewed
 
  private:
-  std::vector<const float *> src_;
+  std::vector<const float4 *> src_;
   HostBuf<BpCloud> h_rec_;
   DBuf<BpCloud> d_rec_;
-  HostBuf<BpFull> h_full_;
-  DBuf<BpFull> d_full_;
+  HostBuf<FullTake> h_full_;
+  DBuf<FullTake> d_full_;
   DBuf<float4> staging_, in_all_;
   int n_ = 0, cap_ = 0, total_ = 0, max_n_ = 0, staged_ = 0, nfull_ = 0, cap_full_ = 0, uploads_ = 0;
-  bool on_device_ = false;
+  bool device_fed_ = false;
 };
 
 }  // namespace lio

@@ -44,28 +44,25 @@ void launch_bp_take_keys(const BpCloud *rec, int nclouds, int max_n, const float
 }
 
 // The device-fed form (include/lio_est_from_odom.h).  Rows < nclouds: the same body, the point read from the record's source (an odometry's
-// last_corner_ / last_surf_; a cloud of no points has a source all the same: PushChain::run).  Rows >= nclouds: the full clouds, one BpFull each,
-// lio_odom_full_to_end (odo_to_end_body, or a copy where the record has no state) straight into a map's full cloud, as row 2 of k_mb_from_odom.
-__global__ void __launch_bounds__(VOX_TILE) k_bp_take_keys_dev(const BpCloud *__restrict__ rec, const int nclouds, const BpFull *__restrict__ full,
+// last_corner_ / last_surf_; a cloud of no points has a source all the same: PushChain::run).  Rows >= nclouds: the full clouds, one FullTake each,
+// through full_take_body (cloud_device.h) straight into a map's full cloud.
+__global__ void __launch_bounds__(VOX_TILE) k_bp_take_keys_dev(const BpCloud *__restrict__ rec, const int nclouds, const FullTake *__restrict__ full,
                                                               float4 *__restrict__ in_all, uint32_t *__restrict__ keys, float *__restrict__ partial,
                                                               int *__restrict__ flag) {
   const int c = blockIdx.y;
   const int base = int(blockIdx.x) * VOX_TILE;
   const int gid = base + threadIdx.x;
   if (c >= nclouds) {
-    const BpFull &F = full[c - nclouds];
+    const FullTake &F = full[c - nclouds];
     if (gid >= F.n) return;
-    const float4 *in = rebase(full, F.in);
-    float4 *out = rebase(full, F.out);
-    if (F.st) odo_to_end_body(in, out, gid, rebase(full, F.st), F.time_factor, F.no_deskew);
-    else out[gid] = in[gid];
+    full_take_body(rebase(full, F.in), rebase(full, F.out), gid, rebase(full, F.to_end.st), F.to_end);
     return;
   }
   const BpCloud &R = rec[c];
   if (base >= R.vox.cap) return;
   bp_take_keys_body(R, c, rebase(rec, R.src)[min(gid, max(R.vox.n - 1, 0))], gid, in_all, keys, partial, flag);
 }
-void launch_bp_take_keys_dev(const BpCloud *rec, int nclouds, const BpFull *full, int nfull, int max_n, float4 *in_all, uint32_t *keys, float *partial, int *flag,
+void launch_bp_take_keys_dev(const BpCloud *rec, int nclouds, const FullTake *full, int nfull, int max_n, float4 *in_all, uint32_t *keys, float *partial, int *flag,
                              hipStream_t s) {
   if (nclouds + nfull <= 0) return;
   hipLaunchKernelGGL(k_bp_take_keys_dev, dim3(std::max(1, cdiv(max_n, VOX_TILE)), nclouds + nfull), dim3(VOX_TILE), 0, s, rec, nclouds, full, in_all, keys, partial,
@@ -94,9 +91,9 @@ void launch_bp_slide(const BpSlide *rec, int nwin, int max_total, hipStream_t s)
 // ------------------------------------------------------------------------------------------------
 // the chain
 // ------------------------------------------------------------------------------------------------
-void PushChain::begin(int max_clouds, int max_full, bool on_device) {
+void PushChain::begin(int max_clouds, int max_full, bool device_fed) {
   n_ = 0; total_ = 0; max_n_ = 0; staged_ = 0; nfull_ = 0; uploads_ = 0;
-  on_device_ = on_device;
+  device_fed_ = device_fed;
   src_.clear();
   if (max_clouds > cap_) {
     const size_t c = size_t(max_clouds) + size_t(max_clouds) / 2;
@@ -110,27 +107,29 @@ void PushChain::begin(int max_clouds, int max_full, bool on_device) {
   }
 }
 
-int PushChain::add(const float *xyzi, size_t n, float leaf, bool deskew, const float q[4], const float p[3], float time_factor, float4 *dst) {
+int PushChain::add(CloudSrc src, float leaf, bool deskew, const float q[4], const float p[3], float time_factor, float4 *dst) {
   if (n_ >= cap_) throw std::runtime_error("PushChain: more clouds than the call announced");
+  if (src.on_device != device_fed_) throw std::logic_error("PushChain: a cloud does not lie where the call announced");
+  const size_t n = src.n;
   const int cap = int((std::max<size_t>(n, 1) + 255) / 256 * 256);
   if (size_t(total_) + size_t(cap) > size_t(INT_MAX) / 2) throw CapacityError("lio_est_batch_push_frames: the call's clouds exceed 2^30 points");
   BpCloud &R = h_rec_.p[n_];
-  R.src_off = on_device_ ? 0 : staged_;   // (a device source takes no range of the staging array)
+  R.src_off = device_fed_ ? 0 : staged_;   // (a device source takes no range of the staging array)
   R.vox = VoxSeg{int(n), total_, cap, 1.0f / leaf, dst};
   R.deskew = deskew ? 1 : 0;
   for (int k = 0; k < 4; ++k) R.qe[k] = q[k];
   for (int k = 0; k < 3; ++k) R.te[k] = p[k];
   R.time_factor = time_factor;
-  R.src = on_device_ && n ? reinterpret_cast<const float4 *>(xyzi) : nullptr;
-  src_.push_back(xyzi);
+  R.src = device_fed_ && n ? src.p : nullptr;
+  src_.push_back(src.p);
   total_ += cap;
-  if (!on_device_) staged_ += cap;
+  if (!device_fed_) staged_ += cap;
   max_n_ = std::max(max_n_, int(n));
   return n_++;
 }
 
-void PushChain::add_full(const BpFull &f) {
-  if (!on_device_ || nfull_ >= cap_full_) throw std::runtime_error("PushChain: more full clouds than the call announced");
+void PushChain::add_full(const FullTake &f) {
+  if (!device_fed_ || nfull_ >= cap_full_) throw std::runtime_error("PushChain: more full clouds than the call announced");
   h_full_.p[nfull_++] = f;
   max_n_ = std::max(max_n_, f.n);
 }
@@ -140,14 +139,14 @@ bool PushChain::run(SegVoxFilter &vox, int passes, hipStream_t s) {
   const size_t N = size_t(total_), C = size_t(n_);
   staging_.reserve(size_t(staged_), s); in_all_.reserve(N, s); d_rec_.reserve(C, s);
   if (n_) vox.reserve(N, n_, s);
-  if (on_device_) {
+  if (device_fed_) {
     // no cloud goes up: the records carry the sources.  The one load per lane is unconditional, so a cloud of no points reads (and drops) the
     // first point of its own range of the input array
     for (int i = 0; i < n_; ++i)
       if (!h_rec_.p[i].src) h_rec_.p[i].src = in_all_.p + h_rec_.p[i].vox.off;
     if (nfull_) {
       d_full_.reserve(size_t(nfull_), s);
-      LIO_HIP(hipMemcpyAsync(d_full_.p, h_full_.p, sizeof(BpFull) * size_t(nfull_), hipMemcpyHostToDevice, s));
+      LIO_HIP(hipMemcpyAsync(d_full_.p, h_full_.p, sizeof(FullTake) * size_t(nfull_), hipMemcpyHostToDevice, s));
     }
   } else {
     // the clouds into the staging array
@@ -161,7 +160,7 @@ bool PushChain::run(SegVoxFilter &vox, int passes, hipStream_t s) {
   }
   // the records in one table
   if (n_) LIO_HIP(hipMemcpyAsync(d_rec_.p, h_rec_.p, sizeof(BpCloud) * C, hipMemcpyHostToDevice, s));
-  if (on_device_) launch_bp_take_keys_dev(d_rec_.p, n_, d_full_.p, nfull_, max_n_, in_all_.p, vox.keys(), vox.partial(), vox.flag(), s);
+  if (device_fed_) launch_bp_take_keys_dev(d_rec_.p, n_, d_full_.p, nfull_, max_n_, in_all_.p, vox.keys(), vox.partial(), vox.flag(), s);
   else launch_bp_take_keys(d_rec_.p, n_, max_n_, staging_.p, in_all_.p, vox.keys(), vox.partial(), vox.flag(), s);
   if (n_) vox.finish(&d_rec_.p->vox, &h_rec_.p->vox, sizeof(BpCloud), n_, passes, in_all_.p, nullptr, s);
   LIO_HIP(hipStreamSynchronize(s));   // the call's one wait

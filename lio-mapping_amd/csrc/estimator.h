@@ -14,6 +14,7 @@
 
 #include "../../include/lio_c.h"
 #include "cloud_kernels.h"
+#include "cloud_src.h"
 #include "host_init.h"
 #include "host_solver.h"
 #include "batch_kernels.h"
@@ -215,12 +216,9 @@ class Estimator {
   ~Estimator();
 
   void ProcessImu(double dt, const V3d &acc, const V3d &gyr, double stamp);
-  bool ProcessLaserOdom(const Rigidf &transform_in, const float *surf, size_t n_surf, const float *corner, size_t n_corner, double stamp,
-                        lio_solve_report *rep);
-  // surf_on_device: the surf cloud already lives in HBM (the scan-to-map stage's down-sampled stack before initialisation)
-  // corner: read only while the map refresh is on (PushFrame)
-  bool ProcessLaserOdom(const Rigidf &transform_in, const float4 *surf, size_t n_surf, bool surf_on_device, double stamp, lio_solve_report *rep,
-                        const float4 *corner = nullptr, size_t n_corner = 0, bool corner_on_device = false);
+  // surf, corner: host or device (cloud_src.h; the scan-to-map stage's down-sampled stacks before initialisation are the device's).  corner
+  // is read only while the map refresh is on (PushFrame)
+  bool ProcessLaserOdom(const Rigidf &transform_in, CloudSrc surf, CloudSrc corner, double stamp, lio_solve_report *rep);
   // ProcessCompactData (Estimator.cc:776-856) on the decoded blocks of a /compact_data message, map_ being the PointMapping base: before
   // initialisation the scan-to-map step and its stacks, afterwards the pose predicted from the IMU-propagated body motion, go into
   // ProcessLaserOdom.  *T_to_init: the pose that went in.  false: ProcessLaserOdom refused.
@@ -229,8 +227,7 @@ class Estimator {
   // the initialised branch of ProcessCompact in front of ProcessLaserOdom (:780-805): the prediction of the map's transform_tobe_mapped_, its
   // transform_sum_; returns the pose that goes in.  ProcessCompact and the batch's device-fed composite (est_batch.h) both call it.
   Rigidf CompactPredict(const Rigidf &transform_sum);
-  bool PushFrame(const Rigidf &transform_in, const float *surf, size_t n_surf, const float *corner, size_t n_corner, double stamp,
-                 bool surf_on_device = false, bool corner_on_device = false);
+  bool PushFrame(const Rigidf &transform_in, CloudSrc surf, CloudSrc corner, double stamp);
   // PushFrame in two parts with the device work in between (the single call's: PushFrame; a batch's: est_push.h).  PushRefused: the de-skew
   // precondition fails — checked before the window is touched.  PushFrameBegin: the LaserFrame and pre-integration pushes, the refresh ring's
   // slot, buffer recycling, transform_es, the destinations reserved.  PushFrameEnd: PushCloud, PushFull, the counts.

@@ -267,12 +267,6 @@ void Estimator::PushCloud(DeviceCloud &&c, size_t n, int n_before) {
   push_at(size_surf_stack_, n_before, n);
 }
 
-bool Estimator::ProcessLaserOdom(const Rigidf &transform_in, const float *surf, size_t n_surf, const float *corner, size_t n_corner,
-                                 double stamp, lio_solve_report *rep) {
-  return ProcessLaserOdom(transform_in, reinterpret_cast<const float4 *>(surf), n_surf, false, stamp, rep, reinterpret_cast<const float4 *>(corner), n_corner,
-                          false);
-}
-
 // Estimator.cc:780-803 and :805 of an initialised window: transform_tobe_mapped_ predicted with the IMU-propagated body motion, transform_sum_
 // taken, and the pose that goes into ProcessLaserOdom
 Rigidf Estimator::CompactPredict(const Rigidf &transform_sum) {
@@ -300,21 +294,18 @@ bool Estimator::ProcessCompact(const Rigidf &transform_sum, const float *corner,
   }
   *T_to_init = m.transform_aft_mapped_;
   const bool was_inited = inited_;
-  const bool ok = was_inited ? ProcessLaserOdom(*T_to_init, reinterpret_cast<const float4 *>(surf), ns, false, stamp, rep,
-                                                reinterpret_cast<const float4 *>(corner), nc, false)
-                             : ProcessLaserOdom(*T_to_init, m.StackDevice(1), m.StackSize(1), true, stamp, rep, m.StackDevice(0), m.StackSize(0), true);
+  const bool ok = was_inited ? ProcessLaserOdom(*T_to_init, CloudSrc::host(surf, ns), CloudSrc::host(corner, nc), stamp, rep)
+                             : ProcessLaserOdom(*T_to_init, CloudSrc::device(m.StackDevice(1), m.StackSize(1)),
+                                                CloudSrc::device(m.StackDevice(0), m.StackSize(0)), stamp, rep);
   if (ok && !was_inited && inited_) m.imu_inited_ = true;  // SetInitFlag(true) (:545)
   return ok;
 }
 
 // Estimator.cc:430-774
-bool Estimator::ProcessLaserOdom(const Rigidf &transform_in, const float4 *surf, size_t n_surf, bool surf_on_device, double stamp,
-                                 lio_solve_report *rep, const float4 *corner, size_t n_corner, bool corner_on_device) {
+bool Estimator::ProcessLaserOdom(const Rigidf &transform_in, CloudSrc surf, CloudSrc corner, double stamp, lio_solve_report *rep) {
   ++laser_odom_recv_count_;
   if (!inited_ && laser_odom_recv_count_ % cfg_.init_window_factor != 0) { last_event_ = EV_SKIPPED; return true; }  // :436-439
-  if (!PushFrame(transform_in, reinterpret_cast<const float *>(surf), n_surf, reinterpret_cast<const float *>(corner), n_corner, stamp, surf_on_device,
-                 corner_on_device))
-    return false;
+  if (!PushFrame(transform_in, surf, corner, stamp)) return false;
   if (!inited_) {
     if (cir_buf_count_ == W_) {
       bool init_result = false;
@@ -472,8 +463,8 @@ void Estimator::PushFrameEnd(PushPlan &pl) {
   PushFull(pl.full_tes);
 }
 
-bool Estimator::PushFrame(const Rigidf &transform_in, const float *surf, size_t n_surf, const float *corner, size_t n_corner, double stamp,
-                          bool surf_on_device, bool corner_on_device) {
+bool Estimator::PushFrame(const Rigidf &transform_in, CloudSrc surf, CloudSrc corner, double stamp) {
+  const size_t n_surf = surf.n, n_corner = corner.n;
   frames_dirty_ = true;
   // every precondition is checked BEFORE the window is touched: a refused frame leaves the estimator as it was
   if (PushRefused()) return false;
@@ -482,13 +473,11 @@ bool Estimator::PushFrame(const Rigidf &transform_in, const float *surf, size_t 
   DeviceCloud &fresh = pl.fresh;
   const std::shared_ptr<DeviceCloud> &corner_cloud = pl.corner_cloud;
   if (!pl.filter && corner_cloud) {
-    if (n_corner)
-      LIO_HIP(hipMemcpyAsync(corner_cloud->buf.p, corner, n_corner * sizeof(float4), corner_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
+    if (n_corner) LIO_HIP(hipMemcpyAsync(corner_cloud->buf.p, corner.p, n_corner * sizeof(float4), corner.to_device(), stream_));
     corner_cloud->n = n_corner;
   }
   if (!inited_) {  // :474-481: the stacks are the scan-to-map stage's down-sampled clouds, pushed as they are
-    if (n_surf)
-      LIO_HIP(hipMemcpyAsync(fresh.buf.p, surf, n_surf * sizeof(float4), surf_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
+    if (n_surf) LIO_HIP(hipMemcpyAsync(fresh.buf.p, surf.p, n_surf * sizeof(float4), surf.to_device(), stream_));
     fresh.n = n_surf;
     PushFrameEnd(pl);
     LIO_HIP(hipStreamSynchronize(stream_));  // the source may be reused by the caller right after the call
@@ -496,8 +485,7 @@ bool Estimator::PushFrame(const Rigidf &transform_in, const float *surf, size_t 
   }
   // host -> HBM (the only PCIe traffic of the step besides the small state/moment exchanges)
   upload_.buf.reserve(std::max<size_t>(n_surf, 1));
-  if (n_surf)
-    LIO_HIP(hipMemcpyAsync(upload_.buf.p, surf, n_surf * sizeof(float4), surf_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream_));
+  if (n_surf) LIO_HIP(hipMemcpyAsync(upload_.buf.p, surf.p, n_surf * sizeof(float4), surf.to_device(), stream_));
   upload_.n = n_surf;
   if (pl.filter) {
     if (pl.deskew) launch_deskew_to_end(upload_.buf.p, int(n_surf), pl.q, pl.p, 10.f, stream_);
@@ -505,9 +493,7 @@ bool Estimator::PushFrame(const Rigidf &transform_in, const float *surf, size_t 
     // for the refresh's ring only (:670, :684-687, :692)
     if (corner_cloud) {
       upload_corner_.buf.reserve(std::max<size_t>(n_corner, 1));
-      if (n_corner)
-        LIO_HIP(hipMemcpyAsync(upload_corner_.buf.p, corner, n_corner * sizeof(float4), corner_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                               stream_));
+      if (n_corner) LIO_HIP(hipMemcpyAsync(upload_corner_.buf.p, corner.p, n_corner * sizeof(float4), corner.to_device(), stream_));
       upload_corner_.n = n_corner;
       if (pl.deskew) launch_deskew_to_end(upload_corner_.buf.p, int(n_corner), pl.q, pl.p, 10.f, stream_);
       corner_cloud->n = vox_corner_.run(upload_corner_.buf.p, n_corner, cfg_.corner_filter_size, corner_cloud->buf, stream_);

@@ -18,6 +18,7 @@
 
 #include "../../include/lio_c.h"
 #include "cloud_kernels.h"
+#include "cloud_src.h"
 #include "hmath.h"
 #include "seg_sort.h"
 
@@ -43,15 +44,16 @@ struct MapSurroundSet {
 struct MapCounters { int n_valid, n_rest, n_new_valid, n_new_rest, n_out, pad[3]; };
 
 // The full cloud a handle takes with a step whose clouds lie in device memory (lio_map_process_batch_from_odom): what SetFullCloud does, fed from
-// the device.  The stack clouds of such a step lie where ProcessBatch's corner_last / surf_last point.
+// the device.  Only such a step takes one.
 struct MapFullSource {
   bool set;                  // false: the handle's full cloud stays as it is
-  const float4 *pts;         // n points in the sensor frame at their own times; n = 0 clears the handle's full cloud
+  const float4 *pts;         // n points in the sensor frame at their own times, in device memory; n = 0 clears the handle's full cloud
   size_t n;
-  const OdomState *to_end;   // an odometry's device-side transform_es_: the points go through its TransformToEnd on the way; null: a copy
-  float time_factor;
-  int no_deskew;
+  ToEnd to_end;              // the odometry's TransformToEnd the points go through on the way (cloud_kernels.h; st null: a copy)
 };
+// One sensor's sweep as the scan-to-scan odometry hands it on, to a map (ProcessBatch) or to a window of the estimator (est_batch.h): the
+// last corner and surf clouds, host or device (cloud_src.h), its transform_sum_, and the full cloud that goes with them.
+struct OdomSweep { CloudSrc corner, surf; Rigid<float> transform_sum; MapFullSource full; };
 
 struct MapChain;   // mapping.hip: the launch chain every step runs through (prepare, filter, grids, table, rounds, give back, update) and its scratch
 
@@ -69,10 +71,9 @@ class MappingDev {
   // include/lio_map_batch.h: one sweep for each of n distinct handles, with the steps of the chain lined up across the handles and the rounds
   // of all of them in one keyframe table.  Array k of every argument belongs to m[k].  Every handle ends in the state a chain of one leaves,
   // bit for bit.  Handles without common launch parameters run as chains of one.  Returns synchronised (the full cloud's registration too).
-  // full_on_device (include/lio_map_from_odom.h; null: the clouds are the host's): the clouds lie in device memory, complete and left alone
-  // until the call returns, and full_on_device[k] is the full cloud m[k] takes with them; one launch takes all of it, no copy per handle.
-  static void ProcessBatch(MappingDev *const *m, int n, const float *const *corner_last, const size_t *n_corner, const float *const *surf_last,
-                           const size_t *n_surf, const Rigid<float> *transform_sum, const MapFullSource *full_on_device = nullptr);
+  // sweep[k] is m[k]'s; the clouds of a call lie in one place (cloud_src.h).  The device's (include/lio_map_from_odom.h): one launch takes
+  // them and every sweep[k].full, no copy per handle.
+  static void ProcessBatch(MappingDev *const *m, int n, const OdomSweep *sweep);
   void UpdateMapDatabase(const float *corner_ds, size_t n_corner, const float *surf_ds, size_t n_surf, const uint32_t *valid_idx, size_t n_valid,
                          const Rigid<float> &T, const int cube_center[3]);
   // the same with the stacks where they live (HBM, sensor frame): no cloud crosses PCIe.  producer: the stream that wrote them (the

@@ -241,9 +241,9 @@ __global__ void __launch_bounds__(256) k_mb_roundtrip(const MbStackRec *__restri
   r.out[c][i] = stack_roundtrip_point(r.in[c][i], r.q, r.t);
 }
 // One sensor of a step fed from the device (lio_map_process_batch_from_odom): its stack clouds where the odometry keeps them, and the full
-// cloud it takes with them (n_full = 0: none), through the odometry's TransformToEnd (st) or as it is (st null), into the handle's full_
-struct MbFromOdomRec { MbStackRec stack; const float4 *full_in; float4 *full_out; int n_full; const OdomState *st; float time_factor; int no_deskew; };
-// grid (cdiv(max n, 256), 3, sensors): y 0 and 1 are k_mb_roundtrip's, y 2 is lio_odom_full_to_end then lio_map_set_full_cloud with no copy between
+// cloud it takes with them (cloud_kernels.h; n = 0: none) into the handle's full_
+struct MbFromOdomRec { MbStackRec stack; FullTake full; };
+// grid (cdiv(max n, 256), 3, sensors): y 0 and 1 are k_mb_roundtrip's, y 2 is full_take_body (cloud_device.h)
 __global__ void __launch_bounds__(256) k_mb_from_odom(const MbFromOdomRec *__restrict__ recs) {
   const MbFromOdomRec &r = recs[blockIdx.z];
   const int c = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
@@ -252,9 +252,8 @@ __global__ void __launch_bounds__(256) k_mb_from_odom(const MbFromOdomRec *__res
     r.stack.out[c][i] = stack_roundtrip_point(r.stack.in[c][i], r.stack.q, r.stack.t);
     return;
   }
-  if (i >= r.n_full) return;
-  if (r.st) odo_to_end_body(r.full_in, r.full_out, i, r.st, r.time_factor, r.no_deskew);
-  else r.full_out[i] = r.full_in[i];
+  if (i >= r.full.n) return;
+  full_take_body(r.full.in, r.full.out, i, r.full.to_end.st, r.full.to_end);
 }
 // One iterating sensor's slice [slot_off, slot_off + Mc + Ms) of the chain's arrays and where the handle keeps the same: its filtered stacks
 // (taken), and its own stack_all_ / f_coef_ / f_abs_ / f_valid_ (given back)
@@ -357,8 +356,7 @@ struct MapChain {
 
   int nA() const { return int(act.size()); }
   MappingDev &dev(int j) const { return *m[act[size_t(j)]]; }
-  void Prepare(MappingDev *const *handles, int n_handles, const float *const *corner_last, const size_t *n_corner, const float *const *surf_last,
-               const size_t *n_surf, const Rigid<float> *sums, const MapFullSource *full_on_device);
+  void Prepare(MappingDev *const *handles, int n_handles, const OdomSweep *sweep);
   void Filter();
   void MakeGrids();
   void FillTable();
@@ -656,7 +654,8 @@ size_t MappingDev::GetFullCloud(float *out) {
 // One step of a handle is a chain of one: the only route through the file
 void MappingDev::Process(const float *corner_last, size_t n_corner, const float *surf_last, size_t n_surf, const Rigid<float> &sum) {
   MappingDev *self = this;
-  ProcessBatch(&self, 1, &corner_last, &n_corner, &surf_last, &n_surf, &sum);
+  const OdomSweep sweep{CloudSrc::host(corner_last, n_corner), CloudSrc::host(surf_last, n_surf), sum, MapFullSource{}};
+  ProcessBatch(&self, 1, &sweep);
 }
 
 // ---- what a step does on the handle alone, called by the chain's steps below
@@ -818,12 +817,11 @@ MapChain &MappingDev::Chain() {
 // instead of one stop per handle.  Every handle is idle when the call starts (each lio_map_* call returns synchronised).
 
 // ---- 1. prepare: association, uploads, cube bookkeeping and the layout pass per handle, no wait in between; one launch for every round trip.
-// Fed from the device (full_on_device): no staging buffer, no upload and no event per handle — the sources are complete; the one launch reads
-// the stack clouds where they lie and takes every handle's full cloud beside them.
-void MapChain::Prepare(MappingDev *const *handles, int n_handles, const float *const *corner_last, const size_t *n_corner, const float *const *surf_last,
-                       const size_t *n_surf, const Rigid<float> *sums, const MapFullSource *full_on_device) {
+// Fed from the device: no staging buffer, no upload and no event per handle — the sources are complete; the one launch reads the stack
+// clouds where they lie and takes every handle's full cloud beside them.
+void MapChain::Prepare(MappingDev *const *handles, int n_handles, const OdomSweep *sweep) {
   m = handles; n = n_handles; s0 = m[0]->stream_;
-  const bool on_device = full_on_device != nullptr;
+  const bool on_device = clouds_on_device(size_t(2) * size_t(n), [&](size_t i) { return i & 1 ? sweep[i / 2].surf : sweep[i / 2].corner; });
   steps.assign(size_t(n), MappingDev::Step());
   h_stack.assign(on_device ? 0 : size_t(n), MbStackRec());
   h_from.assign(on_device ? size_t(n) : 0, MbFromOdomRec());
@@ -831,18 +829,19 @@ void MapChain::Prepare(MappingDev *const *handles, int n_handles, const float *c
   for (int k = 0; k < n; ++k) {
     MappingDev &d = *m[k];
     MappingDev::Step &st = steps[size_t(k)];
-    d.StepBegin(sums[k], st);
+    const OdomSweep &sw = sweep[k];
+    d.StepBegin(sw.transform_sum, st);
     // the stack clouds go up while the host does the cube bookkeeping; stack_raw is sized for their round trip
-    const float *src[2] = {corner_last[k], surf_last[k]};
-    st.cnt[0] = n_corner[k]; st.cnt[1] = n_surf[k];
+    const CloudSrc src[2] = {sw.corner, sw.surf};
+    st.cnt[0] = sw.corner.n; st.cnt[1] = sw.surf.n;
     MbStackRec &r = on_device ? h_from[size_t(k)].stack : h_stack[size_t(k)];
     for (int c = 0; c < 2; ++c) {
       MappingDev::ClassMap &cm = d.cls_[c];
       cm.n_stack = 0;
       if (st.cnt[c] && !on_device) cm.in.reserve(st.cnt[c]);
       if (st.cnt[c]) cm.stack_raw.reserve(st.cnt[c]);
-      if (st.cnt[c] && !on_device) LIO_HIP(hipMemcpyAsync(cm.in.p, src[c], st.cnt[c] * sizeof(float4), hipMemcpyHostToDevice, d.stream_));
-      r.in[c] = on_device ? reinterpret_cast<const float4 *>(src[c]) : cm.in.p; r.out[c] = cm.stack_raw.p; r.n[c] = int(st.cnt[c]);
+      if (st.cnt[c] && !on_device) LIO_HIP(hipMemcpyAsync(cm.in.p, src[c].p, st.cnt[c] * sizeof(float4), src[c].to_device(), d.stream_));
+      r.in[c] = on_device ? src[c].p : cm.in.p; r.out[c] = cm.stack_raw.p; r.n[c] = int(st.cnt[c]);
       max_in = std::max(max_in, st.cnt[c]);
     }
     r.q = st.T0.rot; r.t = st.T0.pos;
@@ -850,14 +849,12 @@ void MapChain::Prepare(MappingDev *const *handles, int n_handles, const float *c
       LIO_HIP(hipEventRecord(d.ev_join_, d.stream_));
       LIO_HIP(hipStreamWaitEvent(s0, d.ev_join_, 0));
     }
-    if (on_device && full_on_device[k].set) {   // SetFullCloud, the points written by the launch below
-      const MapFullSource &f = full_on_device[k];
-      MbFromOdomRec &fr = h_from[size_t(k)];
+    if (on_device && sw.full.set) {   // SetFullCloud, the points written by the launch below
+      const MapFullSource &f = sw.full;
       d.FullBegin(f.n);
       if (f.n) {
         if (d.full_read_) LIO_HIP(hipStreamWaitEvent(s0, d.ev_full_read_, 0));
-        fr.full_in = f.pts; fr.full_out = d.full_.p; fr.n_full = int(f.n);
-        fr.st = f.to_end; fr.time_factor = f.time_factor; fr.no_deskew = f.no_deskew;
+        h_from[size_t(k)].full = FullTake{f.pts, d.full_.p, int(f.n), f.to_end};
         max_in = std::max(max_in, f.n);
       }
     }
@@ -1040,15 +1037,14 @@ void MapChain::Update() {
   }
 }
 
-void MappingDev::ProcessBatch(MappingDev *const *m, int n, const float *const *corner_last, const size_t *n_corner, const float *const *surf_last,
-                              const size_t *n_surf, const Rigid<float> *sums, const MapFullSource *full) {
+void MappingDev::ProcessBatch(MappingDev *const *m, int n, const OdomSweep *sweep) {
   for (int k = 0; k < n; ++k)
-    if (n_corner[k] > size_t(INT_MAX) - 255 || n_surf[k] > size_t(INT_MAX) - 255 || (full && full[k].set && full[k].n > size_t(INT_MAX) - 255))
+    if (sweep[k].corner.n > size_t(INT_MAX) - 255 || sweep[k].surf.n > size_t(INT_MAX) - 255 || (sweep[k].full.set && sweep[k].full.n > size_t(INT_MAX) - 255))
       throw CapacityError("lio_map_process_batch: a cloud exceeds 2^31 points");
   // a pose whose window the packed cube keys cannot hold is refused before any handle changes and before the first launch
   for (int k = 0; k < n; ++k) {
     int cen[3], cc[3];
-    m[k]->WindowAt(m[k]->AssociatedPose(sums[k]), cen, cc);
+    m[k]->WindowAt(m[k]->AssociatedPose(sweep[k].transform_sum), cen, cc);
     if (!CenFits(cen)) throw CapacityError("lio_map_process_batch: a sensor's cube window lies beyond the range of the packed cube keys");
   }
   // the round launches carry these as launch parameters: without common values there is no common chain, a chain of one per handle
@@ -1057,11 +1053,11 @@ void MappingDev::ProcessBatch(MappingDev *const *m, int n, const float *const *c
     if (a.min_match_sq_dis == b.min_match_sq_dis && a.min_plane_dis == b.min_plane_dis && a.num_max_iterations == b.num_max_iterations &&
         m[0]->FourDof() == m[k]->FourDof())
       continue;
-    for (int j = 0; j < n; ++j) ProcessBatch(m + j, 1, corner_last + j, n_corner + j, surf_last + j, n_surf + j, sums + j, full ? full + j : nullptr);
+    for (int j = 0; j < n; ++j) ProcessBatch(m + j, 1, sweep + j);
     return;
   }
   MapChain &ch = m[0]->Chain();
-  ch.Prepare(m, n, corner_last, n_corner, surf_last, n_surf, sums, full);
+  ch.Prepare(m, n, sweep);
   ch.Filter();
   ch.MakeGrids();
   if (ch.nA()) {

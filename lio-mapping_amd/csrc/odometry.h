@@ -4,6 +4,7 @@
 #include <memory>
 
 #include "cloud_kernels.h"
+#include "cloud_src.h"
 #include "hmath.h"
 
 namespace lio {
@@ -19,19 +20,17 @@ class OdometryDev {
   // n independent sensors, one sweep each, through one launch chain on o[0]'s stream (lio_odom_process_batch, include/lio_odom_batch.h):
   // array k of every argument belongs to o[k].  Process is the chain of one, and every sensor of a batch ends in the state it leaves, bit
   // for bit.  The chain's scratch stays with o[0].  Sensors whose max_iter differ are processed one after the other, a chain of one each.
-  // on_device (lio_odom_process_batch_from_pp, include/lio_frontend_batch.h): the clouds lie in device memory, complete and left alone until
-  // the call returns; one launch copies them and sets every sensor's starting state, no copy per sensor.
-  static void ProcessBatch(OdometryDev *const *o, int n, const float *const *sharp, const size_t *n_sharp, const float *const *less_sharp,
-                           const size_t *n_ls, const float *const *flat, const size_t *n_flat, const float *const *less_flat, const size_t *n_lf,
-                           bool on_device = false);
+  // in[k]: o[k]'s clouds, all of a call in one place (cloud_src.h).  The device's (lio_odom_process_batch_from_pp,
+  // include/lio_frontend_batch.h): one launch copies them and sets every sensor's starting state, no copy per sensor.
+  struct Clouds { CloudSrc c[4]; };   // sharp, less sharp, flat, less flat
+  static void ProcessBatch(OdometryDev *const *o, int n, const Clouds *in);
   size_t GetLastCloud(int which, float *out);
-  // What lio_map_process_batch_from_odom (include/lio_map_from_odom.h) reads of the handle, where it lies on the device; nothing of the handle
-  // changes.  last / n_last: what GetLastCloud answers (0 corner, 1 surf).  to_end, time_factor, no_deskew: what FullToEnd runs a cloud
-  // through; to_end is null where FullToEnd copies (odometry disabled, or no publishing step yet).
-  struct DeviceView { const float4 *last[2]; size_t n_last[2]; const OdomState *to_end; float time_factor; int no_deskew; };
+  // What the next stage (include/lio_map_from_odom.h, lio_est_from_odom.h) reads of the handle, where it lies on the device; nothing of the
+  // handle changes.  last: what GetLastCloud answers (0 corner, 1 surf).  to_end: what FullToEnd runs a cloud through (cloud_kernels.h).
+  struct DeviceView { CloudSrc last[2]; ToEnd to_end; };
   DeviceView View() const {
-    return DeviceView{{last_corner_.p, last_surf_.p}, {n_last_corner_, n_last_surf_}, enable_odom_ && to_end_ready_ ? d_state_.p : nullptr, time_factor_,
-                      no_deskew_ ? 1 : 0};
+    return DeviceView{{CloudSrc::device(last_corner_.p, n_last_corner_), CloudSrc::device(last_surf_.p, n_last_surf_)},
+                      ToEnd{enable_odom_ && to_end_ready_ ? d_state_.p : nullptr, time_factor_, no_deskew_ ? 1 : 0}};
   }
   bool processed() const { return inited_; }   // a process call has completed
   // TransformToEnd(full_cloud_) with the last Process's transform_es_ (:725-730); a byte copy while the odometry is disabled

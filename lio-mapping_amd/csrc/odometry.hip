@@ -496,9 +496,8 @@ struct OdoChain {
   DBuf<OdoTakeRec> d_take;
 
   void Begin(OdometryDev *const *handles, int n);
-  void TakeClouds(int n, const float *const *sharp, const size_t *n_sharp, const float *const *less_sharp, const size_t *n_ls, const float *const *flat,
-                  const size_t *n_flat, const float *const *less_flat, const size_t *n_lf, bool on_device);
-  void FillTable(const size_t *n_sharp, const size_t *n_flat, const size_t *n_ls, const size_t *n_lf);
+  void TakeClouds(int n, const OdometryDev::Clouds *in);
+  void FillTable(const OdometryDev::Clouds *in);
   void MakeGrids();
   void Iterate();
   void Finish();
@@ -521,9 +520,9 @@ OdoChain &OdometryDev::Chain() {
   return *chain_;
 }
 
-static void upload(DBuf<float4> &b, const float *src, size_t n, hipStream_t s) {
-  b.reserve(std::max<size_t>(n, 1));
-  if (n) LIO_HIP(hipMemcpyAsync(b.p, src, n * sizeof(float4), hipMemcpyHostToDevice, s));
+static void upload(DBuf<float4> &b, CloudSrc src, hipStream_t s) {
+  b.reserve(std::max<size_t>(src.n, 1));
+  if (src.n) LIO_HIP(hipMemcpyAsync(b.p, src.p, src.n * sizeof(float4), src.to_device(), s));
 }
 
 // What the host keeps of the state the iterations ended with: :654-656 accumulate, :663 normalise.  TransformToEnd (:660-661) runs on the
@@ -544,35 +543,36 @@ void OdoChain::Begin(OdometryDev *const *handles, int n) {
   st.assign(size_t(n), OdomState{});
 }
 
-// ---- step 1: the clouds and the starting state, per sensor: uploads from the host, or (on_device) one record of the take table each; who
-// iterates (`act`: previous clouds of more than 10 corner and 100 surf points), who only carries its clouds to the end (`idle`), who
-// only stores them (neither: the first sweep, :302-310, and the packer)
-void OdoChain::TakeClouds(int n, const float *const *sharp, const size_t *n_sharp, const float *const *less_sharp, const size_t *n_ls,
-                          const float *const *flat, const size_t *n_flat, const float *const *less_flat, const size_t *n_lf, bool on_device) {
+// ---- step 1: the clouds and the starting state, per sensor: uploads from the host, or (clouds on the device) one record of the take table
+// each; who iterates (`act`: previous clouds of more than 10 corner and 100 surf points), who only carries its clouds to the end (`idle`),
+// who only stores them (neither: the first sweep, :302-310, and the packer)
+void OdoChain::TakeClouds(int n, const OdometryDev::Clouds *in) {
+  const bool on_device = clouds_on_device(size_t(4) * size_t(n), [&](size_t i) { return in[i / 4].c[i % 4]; });
   if (on_device) h_take.assign(size_t(n), OdoTakeRec{});
   size_t max_take = 0;
-  // cloud c of sensor k: sharp, less sharp, flat, less flat
-  auto take = [&](int k, int c, DBuf<float4> &b, const float *src, size_t cnt) {
-    if (!on_device) { upload(b, src, cnt, s); return; }
-    if (cnt > size_t(INT_MAX)) throw CapacityError("lio_odom_process_batch_from_pp: a cloud exceeds 2^31 points");
-    b.reserve(std::max<size_t>(cnt, 1));
+  // cloud i of sensor k: sharp, less sharp, flat, less flat
+  auto take = [&](int k, int i, DBuf<float4> &b) {
+    const CloudSrc &src = in[k].c[i];
+    if (!on_device) { upload(b, src, s); return; }
+    if (src.n > size_t(INT_MAX)) throw CapacityError("lio_odom_process_batch_from_pp: a cloud exceeds 2^31 points");
+    b.reserve(std::max<size_t>(src.n, 1));
     OdoTakeRec &r = h_take[size_t(k)];
-    r.src[c] = reinterpret_cast<const float4 *>(src); r.dst[c] = b.p; r.n[c] = int(cnt);
-    max_take = std::max(max_take, cnt);
+    r.src[i] = src.p; r.dst[i] = b.p; r.n[i] = int(src.n);
+    max_take = std::max(max_take, src.n);
   };
   for (int k = 0; k < n; ++k) {
     OdometryDev &d = *o[k];
     d.iterations_done_ = 0; d.last_num_sel_ = 0; d.last_kz_ = 0; d.es_trace_.clear();
-    take(k, 1, d.less_sharp_, less_sharp[k], n_ls[k]);
-    take(k, 3, d.less_flat_, less_flat[k], n_lf[k]);
+    take(k, 1, d.less_sharp_);
+    take(k, 3, d.less_flat_);
     if (!d.inited_ || !d.enable_odom_) continue;
     OdomState &t = st[size_t(k)];
     t = odom_state_at(d.transform_es_);
     if (on_device) { h_take[size_t(k)].st = d.d_state_.p; h_take[size_t(k)].init = t; }
     else LIO_HIP(hipMemcpyAsync(d.d_state_.p, &t, sizeof(t), hipMemcpyHostToDevice, s));
     if (d.n_last_corner_ > 10 && d.n_last_surf_ > 100) {
-      take(k, 0, d.sharp_, sharp[k], n_sharp[k]);
-      take(k, 2, d.flat_, flat[k], n_flat[k]);
+      take(k, 0, d.sharp_);
+      take(k, 2, d.flat_);
       act.push_back(k);
     } else {
       idle.push_back(k);
@@ -587,8 +587,8 @@ void OdoChain::TakeClouds(int n, const float *const *sharp, const size_t *n_shar
 }
 
 // ---- step 2: the table of `act` and `idle`, all of it but the grids (the host does not know the previous clouds' bounds yet), and the buffers
-// whose sizes it states.  Array k of every argument belongs to o[k]; the clouds themselves lie in the handles.
-void OdoChain::FillTable(const size_t *n_sharp, const size_t *n_flat, const size_t *n_ls, const size_t *n_lf) {
+// whose sizes it states.  in[k]: the counts of o[k]'s clouds; the clouds themselves lie in the handles.
+void OdoChain::FillTable(const OdometryDev::Clouds *in) {
   const int na = nA(), ne = nE();
   h_recs = static_cast<OdoBatchRec *>(grids.begin(size_t(ne) * sizeof(OdoBatchRec), 2 * na));
   d_recs = static_cast<const OdoBatchRec *>(grids.head_dev());
@@ -597,22 +597,23 @@ void OdoChain::FillTable(const size_t *n_sharp, const size_t *n_flat, const size
   for (int j = 0; j < ne; ++j) {
     const int k = who(j);
     OdometryDev &d = *o[k];
+    const size_t n_sharp = in[k].c[0].n, n_ls = in[k].c[1].n, n_flat = in[k].c[2].n, n_lf = in[k].c[3].n;
     OdoBatchRec &r = h_recs[j];
     r.a.time_factor = d.time_factor_; r.a.no_deskew = d.no_deskew_ ? 1 : 0;
     r.st = d.d_state_.p;
-    r.ls = d.less_sharp_.p; r.n_ls = int(n_ls[k]); r.lf = d.less_flat_.p; r.n_lf = int(n_lf[k]);
-    if (n_ls[k] + n_lf[k] > size_t(INT_MAX)) throw CapacityError("scan-to-scan odometry: a sensor's clouds exceed 2^31 points");
+    r.ls = d.less_sharp_.p; r.n_ls = int(n_ls); r.lf = d.less_flat_.p; r.n_lf = int(n_lf);
+    if (n_ls + n_lf > size_t(INT_MAX)) throw CapacityError("scan-to-scan odometry: a sensor's clouds exceed 2^31 points");
     max_np = std::max(max_np, r.n_ls + r.n_lf);
     if (j >= na) continue;
-    if (n_sharp[k] + n_flat[k] > (size_t(1) << 25)) throw CapacityError("scan-to-scan odometry: a sensor's queries exceed 2^25");   // one 64-thread block each
+    if (n_sharp + n_flat > (size_t(1) << 25)) throw CapacityError("scan-to-scan odometry: a sensor's queries exceed 2^25");   // one 64-thread block each
     if (d.n_last_corner_ + d.n_last_surf_ > size_t(INT_MAX)) throw CapacityError("scan-to-scan odometry: a sensor's previous clouds exceed 2^31 points");
-    const int nq = int(n_sharp[k] + n_flat[k]);
+    const int nq = int(n_sharp + n_flat);
     r.idx_off = int(idx_total); r.part_off = int(part_total); r.trace_off = j * max_iter * 8;
     r.nb = std::max(1, std::min(cdiv(nq, ODO_ROW_THREADS), 64));
-    idx_total += 2 * n_sharp[k] + 3 * n_flat[k]; part_total += size_t(r.nb);
+    idx_total += 2 * n_sharp + 3 * n_flat; part_total += size_t(r.nb);
     if (idx_total > size_t(INT_MAX)) throw CapacityError("scan-to-scan odometry: the index table exceeds 2^31 entries");
     max_nq = std::max(max_nq, nq); max_nb = std::max(max_nb, r.nb);
-    r.a.sharp = d.sharp_.p; r.a.nc = int(n_sharp[k]); r.a.flat = d.flat_.p; r.a.ns = int(n_flat[k]);
+    r.a.sharp = d.sharp_.p; r.a.nc = int(n_sharp); r.a.flat = d.flat_.p; r.a.ns = int(n_flat);
     r.a.lastc = d.last_corner_.p; r.a.nlc = int(d.n_last_corner_); r.a.lasts = d.last_surf_.p; r.a.nls = int(d.n_last_surf_);
     grids.add(r.a.lastc, r.a.nlc);
     grids.add(r.a.lasts, r.a.nls);
@@ -706,22 +707,21 @@ void OdoChain::Finish() {
 void OdometryDev::Process(const float *sharp, size_t n_sharp, const float *less_sharp, size_t n_ls, const float *flat, size_t n_flat,
                           const float *less_flat, size_t n_lf) {
   OdometryDev *self = this;
-  ProcessBatch(&self, 1, &sharp, &n_sharp, &less_sharp, &n_ls, &flat, &n_flat, &less_flat, &n_lf);
+  const Clouds in{{CloudSrc::host(sharp, n_sharp), CloudSrc::host(less_sharp, n_ls), CloudSrc::host(flat, n_flat), CloudSrc::host(less_flat, n_lf)}};
+  ProcessBatch(&self, 1, &in);
 }
 
-void OdometryDev::ProcessBatch(OdometryDev *const *o, int n, const float *const *sharp, const size_t *n_sharp, const float *const *less_sharp,
-                               const size_t *n_ls, const float *const *flat, const size_t *n_flat, const float *const *less_flat, const size_t *n_lf,
-                               bool on_device) {
+void OdometryDev::ProcessBatch(OdometryDev *const *o, int n, const Clouds *in) {
   for (int k = 1; k < n; ++k)
     if (o[k]->max_iter_ != o[0]->max_iter_) {   // no common iteration count: no common chain, a chain of one per handle
-      for (int j = 0; j < n; ++j) ProcessBatch(o + j, 1, sharp + j, n_sharp + j, less_sharp + j, n_ls + j, flat + j, n_flat + j, less_flat + j, n_lf + j, on_device);
+      for (int j = 0; j < n; ++j) ProcessBatch(o + j, 1, in + j);
       return;
     }
   OdoChain &ch = o[0]->Chain();
   ch.Begin(o, n);
-  ch.TakeClouds(n, sharp, n_sharp, less_sharp, n_ls, flat, n_flat, less_flat, n_lf, on_device);
+  ch.TakeClouds(n, in);
   if (ch.nE()) {
-    ch.FillTable(n_sharp, n_flat, n_ls, n_lf);
+    ch.FillTable(in);
     ch.MakeGrids();
     if (ch.nA()) ch.Iterate();
     ch.Finish();
@@ -730,7 +730,7 @@ void OdometryDev::ProcessBatch(OdometryDev *const *o, int n, const float *const 
   for (int k = 0; k < n; ++k) {
     OdometryDev &d = *o[k];
     std::swap(d.last_corner_, d.less_sharp_); std::swap(d.last_surf_, d.less_flat_);
-    d.n_last_corner_ = n_ls[k]; d.n_last_surf_ = n_lf[k];
+    d.n_last_corner_ = in[k].c[1].n; d.n_last_surf_ = in[k].c[3].n;
     d.inited_ = true;
   }
 }
@@ -744,16 +744,16 @@ OdoChain &OdometryDev::HookTable(const float *sharp, size_t n_sharp, const float
   OdometryDev *self = this;
   OdoChain &ch = Chain();
   ch.Begin(&self, 1);
-  upload(sharp_, sharp, n_sharp, ch.s);
-  upload(flat_, flat, n_flat, ch.s);
-  upload(last_corner_, last_corner, n_lc, ch.s);
-  upload(last_surf_, last_surf, n_lsf, ch.s);
+  const Clouds in{{CloudSrc::host(sharp, n_sharp), CloudSrc(), CloudSrc::host(flat, n_flat), CloudSrc()}};   // (no less-sharp, no less-flat cloud)
+  upload(sharp_, in.c[0], ch.s);
+  upload(flat_, in.c[2], ch.s);
+  upload(last_corner_, CloudSrc::host(last_corner, n_lc), ch.s);
+  upload(last_surf_, CloudSrc::host(last_surf, n_lsf), ch.s);
   n_last_corner_ = n_lc; n_last_surf_ = n_lsf;
   ch.st[0] = odom_state_at(T);
   LIO_HIP(hipMemcpyAsync(d_state_.p, &ch.st[0], sizeof(OdomState), hipMemcpyHostToDevice, ch.s));
   ch.act.push_back(0);
-  const size_t none = 0;
-  ch.FillTable(&n_sharp, &n_flat, &none, &none);
+  ch.FillTable(&in);
   ch.MakeGrids();
   return ch;
 }
@@ -815,7 +815,7 @@ void OdometryDev::FullToEnd(const float *xyzi, size_t n, float *out) {
     return;
   }
   hipStream_t s = stream_;
-  upload(full_, xyzi, n, s);
+  upload(full_, CloudSrc::host(xyzi, n), s);
   hipLaunchKernelGGL(k_odo_to_end, dim3(cdiv(n, 256)), dim3(256), 0, s, full_.p, full_.p, int(n), d_state_.p, time_factor_, no_deskew_ ? 1 : 0);
   LIO_HIP(hipGetLastError());
   LIO_HIP(hipMemcpyAsync(out, full_.p, n * sizeof(float4), hipMemcpyDeviceToHost, s));

@@ -11,6 +11,7 @@
 
 #include "../../include/lio_c.h"
 #include "cloud_kernels.h"
+#include "cloud_src.h"
 
 #define LIO_PP_MAX_RINGS 128
 #define LIO_PP_MAX_RING_POINTS 4080   // 8 subregions of <= 512 sort slots each, ring resident in LDS
@@ -60,10 +61,10 @@ class PointProcessorDev {
   void ProcessLaunch(const float *xyzi, size_t n, const uint16_t *ring = nullptr);
   void ProcessFinish();
   // B sweeps through ONE launch chain (lio_pp_process_batch): every kernel of the chain runs once over all sweeps (the sweep in
-  // blockIdx.z), one copy brings every sweep's counts back.  xyzi[k]: host memory, or device memory when `on_device` (copied device
-  // to device into the handle's segments).  filters[k] (may be null): the ten-sweep start-azimuth history sweep k belongs to
-  // (infer_start_ori) — the handle's own when null and B = 1.  The accessors read the sweep SelectSweep() chose (0 after a launch).
-  void ProcessLaunchBatch(const float *const *xyzi, const uint16_t *const *ring, const size_t *n, int B, bool on_device, StartOriFilter *const *filters);
+  // blockIdx.z), one copy brings every sweep's counts back.  sweep[k]: all of a call in one place (cloud_src.h); the device's are read
+  // where they lie.  filters[k] (may be null): the ten-sweep start-azimuth history sweep k belongs to (infer_start_ori) — the handle's
+  // own when null and B = 1.  The accessors read the sweep SelectSweep() chose (0 after a launch).
+  void ProcessLaunchBatch(const CloudSrc *sweep, const uint16_t *const *ring, int B, StartOriFilter *const *filters);
   int sweeps() const { return nsw_; }
   void SelectSweep(int k);
   StartOriFilter &start_ori_filter() { return start_ori_filter_; }

@@ -843,30 +843,32 @@ void PointProcessorDev::Process(const float *xyzi, size_t n, const uint16_t *rin
 }
 void PointProcessorDev::ProcessLaunch(const float *xyzi, size_t n, const uint16_t *ring) {
   StartOriFilter *f = &start_ori_filter_;
-  ProcessLaunchBatch(&xyzi, ring ? &ring : nullptr, &n, 1, false, &f);
+  const CloudSrc sweep = CloudSrc::host(xyzi, n);
+  ProcessLaunchBatch(&sweep, ring ? &ring : nullptr, 1, &f);
 }
 
 // Everything B sweeps need, enqueued on the handle's stream: uploads, ring split, picks, less-flat filter, packing, and ONE copy of the
 // sweeps' state records into pinned memory.  Host buffers are read by the uploads: they must stay untouched until ProcessFinish().
-void PointProcessorDev::ProcessLaunchBatch(const float *const *xyzi, const uint16_t *const *ring, const size_t *n, int B, bool on_device,
-                                           StartOriFilter *const *filters) {
+void PointProcessorDev::ProcessLaunchBatch(const CloudSrc *sweep, const uint16_t *const *ring, int B, StartOriFilter *const *filters) {
+  const bool on_device = clouds_on_device(sweep, size_t(std::max(B, 0)));
   if (in_flight_) ProcessFinish();
   launched_ = true;
   std::memset(&counts_, 0, sizeof(counts_));
   std::fill(ring_offsets_.begin(), ring_offsets_.end(), 0);
   size_t n_max = 0;
-  for (int k = 0; k < B; ++k) n_max = std::max(n_max, n[k]);
+  for (int k = 0; k < B; ++k) n_max = std::max(n_max, sweep[k].n);
   // nothing to do: every count reads zero; the start azimuth stays the last sweep's, as the reference's member does (PointProcessor.cc:261-264)
   last_empty_ = (B <= 0 || n_max == 0);
   over_capacity_ = false;
   if (last_empty_) return;
   bool any_ring = false;
-  for (int k = 0; k < B; ++k) any_ring = any_ring || (ring && ring[k] && n[k]);
+  for (int k = 0; k < B; ++k) any_ring = any_ring || (ring && ring[k] && sweep[k].n);
   for (int k = 0; k < B && any_ring; ++k)
-    if (n[k] && !ring[k]) throw std::runtime_error("PointProcessor: a batch mixes sweeps with and without a ring field");
+    if (sweep[k].n && !ring[k]) throw std::runtime_error("PointProcessor: a batch mixes sweeps with and without a ring field");
   in_flight_ = true;
   nsw_ = B; sel_ = 0;
-  n_sw_.assign(n, n + B);
+  n_sw_.resize(size_t(B));
+  for (int k = 0; k < B; ++k) n_sw_[size_t(k)] = sweep[k].n;
   hipStream_t s = stream_;
   ReserveHost(B);
   const size_t stride = (n_max + PP_BIN_THREADS - 1) / PP_BIN_THREADS * PP_BIN_THREADS, tot = stride * size_t(B);
@@ -897,12 +899,12 @@ void PointProcessorDev::ProcessLaunchBatch(const float *const *xyzi, const uint1
   if (on_device) {
     // the two kernels that read the input take it where it lies: one table of B pointers goes up instead of B device-to-device copies
     d_in_table_.reserve(B);
-    for (int k = 0; k < B; ++k) h_ptr_[k] = reinterpret_cast<const float4 *>(xyzi[k]);
+    for (int k = 0; k < B; ++k) h_ptr_[k] = sweep[k].p;
     LIO_HIP(hipMemcpyAsync(d_in_table_.p, h_ptr_, size_t(B) * sizeof(const float4 *), hipMemcpyHostToDevice, s));
     d_in_table = d_in_table_.p;
   }
   for (int k = 0; k < B; ++k) {
-    if (n[k] && !on_device) LIO_HIP(hipMemcpyAsync(in_.p + size_t(k) * stride, xyzi[k], n[k] * sizeof(float4), up, s));
+    if (sweep[k].n && !on_device) LIO_HIP(hipMemcpyAsync(in_.p + size_t(k) * stride, sweep[k].p, sweep[k].n * sizeof(float4), up, s));
   }
   if (dbg) {
     LIO_HIP(hipStreamSynchronize(s));
@@ -914,7 +916,7 @@ void PointProcessorDev::ProcessLaunchBatch(const float *const *xyzi, const uint1
   if (B > 1) {
     d_n_.reserve(B);
     int *h_n = h_state_;   // (staged in the landing zone, which nothing else touches before this upload has run: the chain's later copies follow it on the stream)
-    for (int k = 0; k < B; ++k) h_n[k] = int(n[k]);
+    for (int k = 0; k < B; ++k) h_n[k] = int(sweep[k].n);
     LIO_HIP(hipMemcpyAsync(d_n_.p, h_n, size_t(B) * sizeof(int), hipMemcpyHostToDevice, s));
     d_n = d_n_.p;
   }
@@ -924,7 +926,7 @@ void PointProcessorDev::ProcessLaunchBatch(const float *const *xyzi, const uint1
   if (any_ring) {
     ring_in_.reserve(tot);
     for (int k = 0; k < B; ++k)
-      if (n[k]) LIO_HIP(hipMemcpyAsync(ring_in_.p + size_t(k) * stride, ring[k], n[k] * sizeof(uint16_t), up, s));
+      if (sweep[k].n) LIO_HIP(hipMemcpyAsync(ring_in_.p + size_t(k) * stride, ring[k], sweep[k].n * sizeof(uint16_t), up, s));
     // end_ori_ = 0 (:439): k_pp_init
     d_ring = ring_in_.p;
   }
@@ -948,7 +950,7 @@ void PointProcessorDev::ProcessLaunchBatch(const float *const *xyzi, const uint1
     float *h_used = reinterpret_cast<float *>(h_state_);   // (staging of the B values on their way up; the landing zone is idle)
     for (int k = 0; k < B; ++k) {
       StartOriFilter *f = (filters && filters[k]) ? filters[k] : &start_ori_filter_;
-      h_ori_[3 * k + 2] = n[k] ? f->Update(h_ori_[3 * k], h_ori_[3 * k + 1], cfg_.rad_diff) : std::nanf("");
+      h_ori_[3 * k + 2] = sweep[k].n ? f->Update(h_ori_[3 * k], h_ori_[3 * k + 1], cfg_.rad_diff) : std::nanf("");
       h_used[B + k] = h_ori_[3 * k + 2];
     }
     LIO_HIP(hipMemcpyAsync(start_ori_dev_.p + size_t(2) * B, h_used + B, size_t(B) * sizeof(float), hipMemcpyHostToDevice, s));
