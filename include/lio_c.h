@@ -532,7 +532,10 @@ int lio_est_solve_restored(lio_est *, int steps, lio_solve_report *report_or_nul
  * is ONE launch over all windows, the trust-region loop (ImuFactor.h:53-168 and the prior included) and the Schur-complement
  * marginalization run on the device, one workgroup per window.  A window gives the same bits alone (a batch of one) and inside
  * any batch.  Windows the device loop does not take (convergence_flag_ still changing the problem, factor sharding, a local map
- * beyond the batched filter's key range) are solved by the single-window path inside the same call.  Every window must be
+ * beyond the batched filter's key range, more than six optimised frames) are solved by the single-window path inside the same
+ * call.  Seven optimised frames (n_pad = 128, the reference's 12 / 7 indoor configuration) are taken once the handle asks for it:
+ * lio_est_set_device_solve_limit of lio_est_wide.h, the product only, off by default because the device loop and the host loop
+ * agree to about 1e-7 and not in bits; eight and more do not fit the LDS-resident factorisation.  Every window must be
  * initialised: lio_est_batch_solve checks all of them first and returns LIO_ERR_STATE without solving any otherwise.
  * lio_est_batch_create ADOPTS the handles: their device work moves to the batch's stream; they stay usable one at a time from the
  * thread that drives the batch (push frames, slide, snapshot / restore, getters) and should outlive the batch — lio_est_destroy of

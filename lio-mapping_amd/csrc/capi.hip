@@ -8,6 +8,7 @@
 #include "../../include/lio_c.h"
 #include "../../include/lio_test_hooks.h"
 #include "../../include/lio_ext.h"
+#include "../../include/lio_est_wide.h"
 #include "../../include/lio_full_cloud.h"
 #include "../../include/lio_est_from_odom.h"
 #include "../../include/lio_odom_batch.h"
@@ -1164,6 +1165,13 @@ int lio_est_process_compact(lio_est *h, const float *data, size_t n, double stam
     return ok ? LIO_OK : LIO_ERR_STATE;
   });
 }
+// ---------------------------------------------------------------- include/lio_est_wide.h: seven optimised frames on the device loop
+int lio_est_set_device_solve_limit(lio_est *h, int max_opt_window) {
+  if (!h || max_opt_window < LIO_DEVICE_SOLVE_LIMIT_DEFAULT || max_opt_window > LIO_DEVICE_SOLVE_LIMIT_MAX) return LIO_ERR_ARG;
+  h->e->device_solve_limit_ = max_opt_window;   // (read by BatchPackProblem at the next solve; a solve is one blocking call)
+  return LIO_OK;
+}
+int lio_est_get_device_solve_limit(const lio_est *h) { return h ? h->e->device_solve_limit_ : LIO_ERR_ARG; }
 // ---------------------------------------------------------------- include/lio_ext.h: the map refresh and the surround map
 lio_map *lio_est_map(lio_est *h) {
   if (!h) return nullptr;

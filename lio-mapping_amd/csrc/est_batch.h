@@ -17,7 +17,8 @@
 // the device; a host-side reader (lio_est_get_prior, a snapshot, the single-window solver) fetches it on demand.
 // Per-window arithmetic does not depend on the batch: a window gives the same bits alone (B = 1, which is what
 // lio_est_config.device_solve selects for a single handle) and inside any batch.  Windows whose problem the device loop does not
-// take (not initialised yet, the convergence_flag_ logic changing the problem's shape, factor sharding) are solved by the
+// take (not initialised yet, the convergence_flag_ logic changing the problem's shape, factor sharding, seven optimised frames
+// on a handle that has not asked for them: Estimator::device_solve_limit_) are solved by the
 // single-window path inside the same call.
 //
 // What the C ABI calls a batch (lio_est_batch) is a BatchParts, below: one EstimatorBatch, or two solved side by side.  The partition

@@ -278,6 +278,9 @@ class Estimator {
   // the problem of Estimator.cc:1660-1921 as the device loop reads it; *prior = the marginalization prior the problem uses.
   // false: this window's problem does not fit the device loop.
   bool BatchPackProblem(int bpf, DevProblem &pb, DevState &st, std::shared_ptr<MargPrior> *prior);
+  // the largest optimisation window BatchPackProblem hands to the device loop (include/lio_est_wide.h: 6, or 7 = n_pad 128).  A choice of
+  // the handle, not part of its state: Snapshot / Restore / CopySnapshotOf leave it alone.
+  int device_solve_limit_ = 6;
   // after the device loop: DoubleToVector, the report, convergence_flag_.  true: the window marginalises now — mg is filled
   // (linearisation point, layout) and *shell is the new prior without its matrices (they are computed on the device).
   bool BatchFinish(const DevState &st, const std::shared_ptr<MargPrior> &prior_used, lio_solve_report &R, DevMarg &mg, std::shared_ptr<MargPrior> *shell);

@@ -1334,6 +1334,7 @@ bool Estimator::BatchPackProblem(int bpf, DevProblem &pb, DevState &st, std::sha
   AssembleSystem(P, sys);
   if (prior) *prior = sys.prior;
   if (!ds_pack_problem(sys, P, cfg_.max_num_iterations, bpf, convergence_flag_, cfg_.imu_factor, pb, nullptr)) return false;
+  if (Wo_ > device_solve_limit_) return false;   // (lio_est_set_device_solve_limit: seven optimised frames are opt-in)
   if (ds_lds_doubles(pb.n_pad, Wo_) * sizeof(double) > 160 * 1024) return false;
   ds_init_state(P, st);
   return true;

@@ -77,9 +77,20 @@ struct DevState {
 
 // prior_mats layout: JtJ (np x np) | lin_jac (np x np) | lin_res (np) | Jtr0 (np)
 LIO_HD size_t ds_prior_mats_size(int np) { return size_t(2) * np * np + 2 * np; }
+// ---- the step kernel's LDS (docs/wide_window.md).  Stated once: carve_lds places the arrays, ds_lds_doubles is the end of the last one.
+//   A | gz | tmp | late | part | red | control
+// `late` is one region with two tenants whose lifetimes a workgroup barrier separates: until the barrier that ends P4 it holds zb (the
+// Wo lidar blocks of ds_lidar_blocks, 344 doubles each); behind it the arrays nothing touches before P6 — xinv (L11^-1 of every
+// panel: ds_ldlt_solve only) and the eight vectors hdiag, invd, scale, diag, grad, gn, g, step.  gz (from P4) and tmp (from P1) are live across that barrier and keep
+// bytes of their own, so do part (the prior's columns during P4, the factorisation's scratch later), red and the control block.
+#define DS_LATE_VECS 8
+LIO_HD size_t ds_late_doubles(int n_pad, int Wo) {
+  const size_t late = size_t(n_pad) * DS_NB + DS_LATE_VECS * size_t(n_pad), zb = size_t(Wo) * 344;
+  return late > zb ? late : zb;
+}
 // LDS doubles the step kernel needs for (n_pad, Wo)
 LIO_HD size_t ds_lds_doubles(int n_pad, int Wo) {
-  return size_t(n_pad) * (n_pad + 1) + 10 * size_t(n_pad) + size_t(Wo) * 344 + DS_PART + size_t(n_pad) * DS_NB + 64 + 32;   // (n_pad * 16: L11^-1 of every panel)
+  return size_t(n_pad) * (n_pad + 1) + 2 * size_t(n_pad) + ds_late_doubles(n_pad, Wo) + DS_PART + 64 + 32;
 }
 
 // ------------------------------------------------------------------------------------------------ executors
@@ -316,11 +327,17 @@ LIO_HD StepLds carve_lds(double *base, int n_pad, int Wo) {
   StepLds l;
   double *p = base;
   l.A = p; p += size_t(n_pad) * (n_pad + 1);
-  l.hdiag = p; p += n_pad; l.gz = p; p += n_pad; l.invd = p; p += n_pad; l.scale = p; p += n_pad; l.diag = p; p += n_pad;
-  l.grad = p; p += n_pad; l.gn = p; p += n_pad; l.g = p; p += n_pad; l.step = p; p += n_pad; l.tmp = p; p += n_pad;
-  l.zb = p; p += size_t(Wo) * 344;
+  l.gz = p; p += n_pad; l.tmp = p; p += n_pad;
+  // the late region: zb until the barrier behind P4's lidar pass, then xinv and the eight vectors (first written in P6 or later)
+  l.zb = p;
+  {
+    double *q = p;
+    l.xinv = q; q += size_t(n_pad) * DS_NB;
+    l.hdiag = q; q += n_pad; l.invd = q; q += n_pad; l.scale = q; q += n_pad; l.diag = q; q += n_pad;
+    l.grad = q; q += n_pad; l.gn = q; q += n_pad; l.g = q; q += n_pad; l.step = q; q += n_pad;
+  }
+  p += ds_late_doubles(n_pad, Wo);
   l.part = p; p += DS_PART;
-  l.xinv = p; p += size_t(n_pad) * DS_NB;
   l.red = p; p += 64;
   l.ctl = reinterpret_cast<int *>(p);
   return l;

@@ -294,6 +294,11 @@ _EXT_SIGS = {
     "lio_est_get_last_map_refresh": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(TransformF), C.POINTER(C.c_int), C.POINTER(C.c_uint32),
                                                C.POINTER(C.c_int), C.POINTER(C.c_size_t), c_float_p, C.POINTER(C.c_size_t), c_float_p]),
 }
+# include/lio_est_wide.h: seven optimised frames on the device loop (the product only, attached like _EXT_SIGS)
+_EST_WIDE_SIGS = {
+    "lio_est_set_device_solve_limit": (C.c_int, [C.c_void_p, C.c_int]),
+    "lio_est_get_device_solve_limit": (C.c_int, [C.c_void_p]),
+}
 # include/lio_full_cloud.h: the full-resolution sweep on the device (the product only, attached like _EXT_SIGS)
 _FULL_SIGS = {
     "lio_odom_full_to_end": (C.c_int, [C.c_void_p, c_float_p, C.c_size_t, c_float_p]),
@@ -427,7 +432,7 @@ class LioLib:
                 fn.argtypes = args
             # a build from before the sample sort still loads (the A/B tools take one as --parent-lib); only a call to these fails there
             for name, (res, args) in list(_VOX_SORT_SIGS.items()) + (list(_SEG_BOUNDS_SIGS.items()) + list(_EST_PUSH_SIGS.items())
-                                                                             + list(_EST_FROM_ODOM_SIGS.items())):
+                                                                             + list(_EST_FROM_ODOM_SIGS.items()) + list(_EST_WIDE_SIGS.items())):
                 fn = getattr(self.dll, name, None)
                 if fn is not None:
                     fn.restype = res
@@ -1295,6 +1300,17 @@ class Estimator:
 
     def set_map_refresh(self, on):
         _chk(self.lib.dll.lio_est_set_map_refresh(self.h, 1 if on else 0), "lio_est_set_map_refresh")
+
+    # ---- include/lio_est_wide.h (the product only)
+    def set_device_solve_limit(self, max_opt_window):
+        """the largest optimisation window of this handle the device loop takes: 6 (default) or 7"""
+        _chk(self.lib.dll.lio_est_set_device_solve_limit(self.h, int(max_opt_window)), f"lio_est_set_device_solve_limit({max_opt_window})")
+
+    def device_solve_limit(self):
+        rc = self.lib.dll.lio_est_get_device_solve_limit(self.h)
+        if rc < 0:
+            raise LioError(f"lio_est_get_device_solve_limit failed with code {rc}")
+        return int(rc)
 
     def refresh_map(self):
         """Estimator.cc:703-708 after a solve, before the slide -> 1 the map was updated, 0 masked / ring not full."""
